@@ -170,7 +170,12 @@ def main():
                          "templates, batch 128).  'none' skips them")
     ap.add_argument("--no-hard", action="store_true", help="skip the margin-free `parity.hard` workload (workload.py: only the best view planted)")
     ap.add_argument("--no-latency", action="store_true", help="skip the B = 1 per-detection latency (`latency_b1`) and the crop -> pose pipeline number (`pipeline`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (every detection's templates and correspondences) as DIR/<name>.npy "
+                         "(see dump_outputs); the inputs depend on the arguments only, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -274,6 +279,8 @@ def main():
     for _ in range(args.warmup):
         step()
     elapsed, (gathered, last) = timed(eng, args.steps)
+    if args.dump_outputs and rank == 0:   # the gathered records: every rank's detections
+        dump_outputs(args.dump_outputs, fe.unpack_result(gathered, *last.q_ids.shape[1:]))
     det_per_s = world * B * args.steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
     rank_ms = [1e3 * v / args.steps for v in per_rank_s]
@@ -293,9 +300,9 @@ def main():
         assert int(cnt.item()) == world == ranks_seen, "every rank must contribute its records to the gather"
     if args.skip_probes:
         if rank == 0:
-            print(json.dumps({"metric": "detections/sec (ViT+kNN match) on 518^2 crops vs 10k-template bank", "value": round(det_per_s, 2), "unit": "detections/s",
-                              "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "probes": "skipped", "ranks_seen": ranks_seen,
-                              **({"multi_gpu": multi} if multi is not None else {})}), flush=True)
+            print(result_line({"metric": "detections/sec (ViT+kNN match) on 518^2 crops vs 10k-template bank", "value": round(det_per_s, 2), "unit": "detections/s",
+                               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "probes": "skipped", "ranks_seen": ranks_seen,
+                               **({"multi_gpu": multi} if multi is not None else {})}), flush=True)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
@@ -624,10 +631,66 @@ def main():
             gc.collect()
             torch.cuda.empty_cache()
             result["other_configs"] = {c: other_config(c, args, dev, rank) for c in args.other_configs.split(",") if c}
-        print(json.dumps(result), flush=True)
+        print(result_line(result), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def result_line(record):
+    """The one JSON line on stdout: `record` without its prose -- the `what` / `note` explanations and the other descriptive strings
+    longer than 64 characters, which stay in this file next to the numbers they explain -- in compact separators.  With the prose the
+    default run's line passed 23 kB, more than a driver that keeps a bounded tail of the output receives whole; without it, about 14 kB."""
+    def strip(x):
+        if isinstance(x, dict):
+            return {k: strip(v) for k, v in x.items() if k == "metric" or not (isinstance(v, str) and len(v) > 64)}
+        if isinstance(x, list):
+            return [strip(v) for v in x]
+        return x
+    return json.dumps(strip(record), separators=(",", ":"))
+
+
+DUMP_LIMIT_BYTES = 63_000_000   # 64 MB in all, with room for the .npy headers
+
+
+def dump_outputs(out_dir, res, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed path receives from its last step, one DIR/<name>.npy per array.  Per detection b and
+    template slot j (the padded MatchResult, [B, n] and [B, n, K]): template_id, template_score, counts, and for the first counts[b, j] of
+    the K rows the entries of the reference's correspondence dict -- coord_2d, coord_2d_ids, coord_3d, coord_conf, nn_vertex_ids -- with
+    the cycle distances nn_dists.  Entries past counts (and slots without a template) are padding the kernels leave unwritten: they are
+    written as 0, ids as -1.  Integer fields are float64 (exact), the rest float32 as computed.  Every file holds finite numbers only: a
+    computed NaN / inf -- coord_conf is the reference's 1 - d / max(d) over a slot's buddies, 0 / 0 = NaN wherever all of them are exactly
+    cycle-consistent (every slot of the planted workload) -- is written as 0, and <name>_nonfinite.npy, written for such an array only,
+    marks it: 1 NaN, 2 +inf, 3 -inf, 0 finite.  Above `limit` bytes in all, a fixed, seeded sample of the detections is written instead,
+    its indices in detection_index.npy."""
+    import numpy as np
+    tid = res.template_ids.cpu().numpy()
+    has = tid >= 0
+    counts = np.where(has, res.counts.cpu().numpy(), 0)
+    row = (np.arange(res.q_ids.shape[2])[None, None, :] < counts[..., None]) & has[..., None]
+    ids = lambda t, m: np.where(m, t.cpu().numpy(), -1).astype(np.float64)
+    val = lambda t, m: np.where(m, t.cpu().numpy(), 0).astype(np.float32)
+    out = {"template_id": ids(res.template_ids, has), "template_score": val(res.template_scores, has), "counts": counts.astype(np.float64),
+           "coord_2d": val(res.coord_2d, row[..., None]), "coord_2d_ids": ids(res.q_ids, row), "coord_3d": val(res.coord_3d, row[..., None]),
+           "coord_conf": val(res.conf, row), "nn_vertex_ids": ids(res.feat_ids, row), "nn_dists": val(res.dists, row)}
+    fields = list(out)
+    for name in fields:
+        a = out[name]
+        bad = ~np.isfinite(a)
+        if bad.any():
+            out[name + "_nonfinite"] = np.where(bad, np.where(np.isnan(a), 1, np.where(a > 0, 2, 3)), 0).astype(np.float32)
+            a[bad] = 0
+    num_det, total = tid.shape[0], sum(a.nbytes for a in out.values())
+    if total > limit:
+        keep = np.sort(np.random.default_rng(0).choice(num_det, limit // (total // num_det + 8), replace=False))
+        out = {k: a[keep] for k, a in out.items()}
+        out["detection_index"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name in [f + "_nonfinite" for f in fields] + ["detection_index"]:   # left by an earlier dump into the same directory
+        if name not in out and os.path.exists(os.path.join(out_dir, name + ".npy")):
+            os.remove(os.path.join(out_dir, name + ".npy"))
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(arch, args, bank, wl, gpu_lists, dev_words=None, want_oracle_b=False):

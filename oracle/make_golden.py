@@ -578,6 +578,51 @@ def gen_wrappers(ref):
     print("wrappers.npz templates", out["template_ids"], "repre.pth bytes", os.path.getsize(os.path.join(rdir, "repre.pth")))
 
 
+REPRE_IO_SCALES = [[448.0, 224.0, 112.0, 56.0]]   # extra, non-tensor entry of the file written here: the reference's loader must skip it
+
+
+def gen_repre_io(ref):
+    """The way back for row R: a `repre.pth` written by THIS project's save_object_repre (the representation of tests/golden/repre_ref
+    plus the non-tensor extra entry) and read by the reference's own load_object_repre.  Records what that loader accepted and returned,
+    so that tests/test_repre_io.py holds every later file to it without the reference: its field names (a tensor entry it does not know
+    makes its constructor raise), the option-tuple fields, the top-level / projector / camera entries of the file it read, and its values
+    (option dicts, camera count, the PCA projection of seeded inputs through the sklearn model it rebuilt from our tensordict)."""
+    import dataclasses
+    import json
+    import tempfile
+
+    from foundpose_amd import repre_util
+    ours = repre_util.load_object_repre(os.path.join(OUT, "repre_ref"))
+    ours.extractor_fp8_act_scales = REPRE_IO_SCALES
+    with tempfile.TemporaryDirectory() as tmp:
+        repre_util.save_object_repre(ours, tmp)
+        written = torch.load(os.path.join(tmp, "repre.pth"), weights_only=True)
+        theirs = ref.repre_util.load_object_repre(tmp, tensor_device="cpu")
+    tensor_names = sorted(k for k, v in written.items() if torch.is_tensor(v))
+    for name in tensor_names:
+        assert torch.equal(getattr(theirs, name), getattr(ours, name)), name
+    x = torch.randn(7, WRAP["raw"], generator=torch.Generator().manual_seed(1))
+    proj = ref.projector_util.project_features(x, theirs.feat_raw_projectors)
+    cams = theirs.template_cameras_cam_from_model
+    out = {
+        "repre_fields": np.array(sorted(f.name for f in dataclasses.fields(ref.repre_util.FeatureBasedObjectRepre))),
+        "feat_opts_fields": np.array(ref.repre_util.FeatureOpts._fields),
+        "template_desc_opts_fields": np.array(ref.repre_util.TemplateDescOpts._fields),
+        "tensor_names": np.array(tensor_names),
+        "other_entries": np.array(sorted(k for k, v in written.items() if not torch.is_tensor(v))),
+        "projector_keys": np.array(sorted(written["feat_raw_projectors"][0]["pca_projector"])),
+        "camera_keys": np.array(sorted(written["template_cameras_cam_from_model"][0])),
+        "feat_opts": np.array(json.dumps(theirs.feat_opts._asdict())),
+        "template_desc_opts": np.array(json.dumps(theirs.template_desc_opts._asdict())),
+        "num_projectors": np.array(len(theirs.feat_raw_projectors)),
+        "num_cameras": np.array(len(cams)),
+        "camera_sizes": np.array([[c.width, c.height] for c in cams], np.int64),
+        "proj_x": t2n(x), "proj_out": t2n(proj).astype(np.float32),
+    }
+    np.savez_compressed(os.path.join(OUT, "repre_io.npz"), **out)
+    print("repre_io.npz tensors", tensor_names, "entries", out["other_entries"].tolist())
+
+
 # ------------------------------------------------------------------ result formats (SURVEY 8f-4)
 def gen_wrappers_cosine(ref):
     """`tfidf_knn_metric = "cosine"` for the visual-word search (scripts/infer.py:218-222 -> knn_util.py:52-57, 91-100): the reference's
@@ -718,6 +763,7 @@ def main():
     gen_crop(ref)
     gen_lift(ref)
     gen_wrappers(ref)
+    gen_repre_io(ref)
     gen_wrappers_cosine(ref)
     gen_results(ref)
 
