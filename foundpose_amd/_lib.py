@@ -85,6 +85,10 @@ _PROTOS = {
     "fp_attention": [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp],
     "fp_convert_f32_to_bf16": [vp, vp, i64, vp],
     "fp_warp_crops": [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp],
+    "fp_warp_depth": [vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp],
+    "fp_render_setup": [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "fp_render_raster": [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "fp_template_downsample": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
 }
 
 _lib = None

@@ -494,6 +494,60 @@ int fp_warp_crops(const void* src, int n_src, int src_h, int src_w, int channels
   return launch_warp_crops(a, ST(stream));
 }
 
+int fp_warp_depth(const float* src, int src_h, int src_w, const double* params, const int32_t* recompute, int batch,
+                  int out_h, int out_w, int depth_check, float* out, fp_stream_t stream) {
+  FP_REQUIRE(src && params && out, "fp_warp_depth: null pointer");
+  FP_REQUIRE(src_h >= 1 && src_w >= 1 && batch >= 1 && out_h >= 1 && out_w >= 1, "fp_warp_depth: empty problem");
+  WarpDepthArgs a{src, src_h, src_w, params, recompute, batch, out_h, out_w, depth_check, out};
+  return launch_warp_depth(a, ST(stream));
+}
+
+static int render_args(const float* verts, const float* normals, const float* colors, int num_verts, const int32_t* faces,
+                       int num_faces, const double* cams, int batch, int width, int height, void* vert_ws, void* tri_ws,
+                       int32_t* tile_counts, int64_t* tile_offsets, int32_t* lists, int64_t* status, float* color,
+                       float* depth, uint8_t* mask, int32_t* tri_id, int32_t* boxes, RenderArgs* a) {
+  FP_REQUIRE(verts && normals && colors && faces && cams && vert_ws && tri_ws && tile_counts && tile_offsets && status,
+             "fp_render: null pointer");
+  FP_REQUIRE(num_verts >= 1 && num_faces >= 1 && batch >= 1, "fp_render: empty problem");
+  FP_REQUIRE(width >= 1 && height >= 1 && width <= FP_RENDER_MAX_SIDE && height <= FP_RENDER_MAX_SIDE,
+             "fp_render: viewport %d x %d outside [1, %d]", width, height, FP_RENDER_MAX_SIDE);
+  FP_REQUIRE((long long)batch * num_faces < (1ll << 40) && (long long)batch * num_verts < (1ll << 40), "fp_render: batch too large");
+  *a = RenderArgs{verts, normals, colors, num_verts, faces, num_faces, cams, batch, width, height, vert_ws, tri_ws,
+                  tile_counts, reinterpret_cast<long long*>(tile_offsets), lists, reinterpret_cast<long long*>(status),
+                  color, depth, mask, tri_id, boxes};
+  return FP_OK;
+}
+
+int fp_render_setup(const float* verts, const float* normals, const float* colors, int num_verts, const int32_t* faces,
+                    int num_faces, const double* cams, int batch, int width, int height, void* vert_ws, void* tri_ws,
+                    int32_t* tile_counts, int64_t* tile_offsets, int32_t* lists, int64_t* status, float* color,
+                    float* depth, uint8_t* mask, int32_t* tri_id, int32_t* boxes, fp_stream_t stream) {
+  RenderArgs a;
+  TRY(render_args(verts, normals, colors, num_verts, faces, num_faces, cams, batch, width, height, vert_ws, tri_ws,
+                  tile_counts, tile_offsets, lists, status, color, depth, mask, tri_id, boxes, &a));
+  return launch_render_setup(a, ST(stream));
+}
+
+int fp_render_raster(const float* verts, const float* normals, const float* colors, int num_verts, const int32_t* faces,
+                     int num_faces, const double* cams, int batch, int width, int height, void* vert_ws, void* tri_ws,
+                     int32_t* tile_counts, int64_t* tile_offsets, int32_t* lists, int64_t* status, float* color,
+                     float* depth, uint8_t* mask, int32_t* tri_id, int32_t* boxes, fp_stream_t stream) {
+  RenderArgs a;
+  TRY(render_args(verts, normals, colors, num_verts, faces, num_faces, cams, batch, width, height, vert_ws, tri_ws,
+                  tile_counts, tile_offsets, lists, status, color, depth, mask, tri_id, boxes, &a));
+  FP_REQUIRE(lists && depth && mask, "fp_render_raster: null pointer");
+  return launch_render_raster(a, ST(stream));
+}
+
+int fp_template_downsample(const float* color, const float* depth, const uint8_t* mask, int batch, int out_h, int out_w,
+                           int factor, uint8_t* rgb, uint16_t* depth_u16, uint8_t* mask_out, int32_t* boxes,
+                           fp_stream_t stream) {
+  FP_REQUIRE(color && depth && mask && rgb && depth_u16 && mask_out, "fp_template_downsample: null pointer");
+  FP_REQUIRE(batch >= 1 && out_h >= 1 && out_w >= 1 && factor >= 1 && factor <= 16, "fp_template_downsample: bad shape");
+  DownsampleArgs a{color, depth, mask, batch, out_h, out_w, factor, rgb, depth_u16, mask_out, boxes};
+  return launch_template_downsample(a, ST(stream));
+}
+
 // ------------------------------------------------------------------ ViT forward (launch sequence in C++)
 }  // extern "C"
 

@@ -27,10 +27,8 @@ FP_DEVICE double dot3(double a0, double a1, double a2, double b0, double b1, dou
   return dadd(dadd(dmul(a0, b0), dmul(a1, b1)), dmul(a2, b2));
 }
 
-__global__ __launch_bounds__(256) void warp_crops_kernel(WarpArgs a) {
-  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
-  if (x >= a.out_w || y >= a.out_h) return;
-  const double* p = a.params + (size_t)b * 32;  // dst f[2] c[2] R[9] t[3] | src f[2] c[2] R[9] t[3]
+// Destination pixel (x, y) of one crop -> fp32 source window position (map_x, map_y).  p: the crop's 32 parameters.
+FP_DEVICE void crop_map(const double* p, int x, int y, int depth_check, float& fx, float& fy) {
   // window_to_eye of the crop camera: q = (w - c) / f, v = normalized([qx, qy, 1])
   const double qx = __ddiv_rn(dadd((double)x, -p[2]), p[0]), qy = __ddiv_rn(dadd((double)y, -p[3]), p[1]);
   double n = __dsqrt_rn(dadd(dadd(dmul(qx, qx), dmul(qy, qy)), 1.0));
@@ -50,8 +48,15 @@ __global__ __launch_bounds__(256) void warp_crops_kernel(WarpArgs a) {
   const double ez = dot3(dx, dy, dz, Rs[2], Rs[5], Rs[8]);
   // eye_to_window: (e.xy / e.z) * f + c; points behind the source camera map to -1
   double mx = dadd(dmul(__ddiv_rn(ex, ez), q[0]), q[2]), my = dadd(dmul(__ddiv_rn(ey, ez), q[1]), q[3]);
-  if (a.depth_check && ez < 0.0) mx = my = -1.0;
-  const float fx = (float)mx, fy = (float)my;  // .astype(np.float32)
+  if (depth_check && ez < 0.0) mx = my = -1.0;
+  fx = (float)mx, fy = (float)my;  // .astype(np.float32)
+}
+
+__global__ __launch_bounds__(256) void warp_crops_kernel(WarpArgs a) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
+  if (x >= a.out_w || y >= a.out_h) return;
+  float fx, fy;
+  crop_map(a.params + (size_t)b * 32, x, y, a.depth_check, fx, fy);  // dst f[2] c[2] R[9] t[3] | src f[2] c[2] R[9] t[3]
   const size_t plane = (size_t)a.out_h * a.out_w, pix = (size_t)y * a.out_w + x;
   if (a.map_out) {
     a.map_out[((size_t)b * 2 + 0) * plane + pix] = fx;
@@ -83,11 +88,53 @@ __global__ __launch_bounds__(256) void warp_crops_kernel(WarpArgs a) {
   }
 }
 
+// utils/misc.py:522-557 warp_depth_image, per destination pixel: the nearest source pixel through crop_map (cv2.remap
+// INTER_NEAREST with the same fp32 map), and, when the extrinsics differ (recompute[b]), the source depth re-expressed as
+// the z of the same surface point in the crop camera -- window_to_eye of the SOURCE pixel, scaled by depth / v.z,
+// eye_to_world of the source camera, world_to_eye of the crop camera -- in fp64 and assigned to fp32.  Depth 0 stays 0.
+__global__ __launch_bounds__(256) void warp_depth_kernel(WarpDepthArgs a) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
+  if (x >= a.out_w || y >= a.out_h) return;
+  const double* p = a.params + (size_t)b * 32;
+  float fx, fy;
+  crop_map(p, x, y, a.depth_check, fx, fy);
+  const int sx = __float2int_rn(fx), sy = __float2int_rn(fy);
+  float out = 0.f;
+  if (sx >= 0 && sx < a.src_w && sy >= 0 && sy < a.src_h) {
+    const float d = a.src[((size_t)b * a.src_h + sy) * a.src_w + sx];
+    out = d;
+    if (d > 0.f && (a.recompute == nullptr || a.recompute[b])) {
+      const double* q = p + 16;  // source camera
+      const double qx = __ddiv_rn(dadd((double)sx, -q[2]), q[0]), qy = __ddiv_rn(dadd((double)sy, -q[3]), q[1]);
+      double n = __dsqrt_rn(dadd(dadd(dmul(qx, qx), dmul(qy, qy)), 1.0));
+      n = fmax(5.43e-20, n);
+      const double vx = __ddiv_rn(qx, n), vy = __ddiv_rn(qy, n), vz = __ddiv_rn(1.0, n);
+      const double s = __ddiv_rn((double)d, vz);
+      const double ex = dmul(vx, s), ey = dmul(vy, s), ez = dmul(vz, s);
+      const double* Rs = q + 4;
+      const double wx = dadd(dot3(ex, ey, ez, Rs[0], Rs[1], Rs[2]), q[13]);
+      const double wy = dadd(dot3(ex, ey, ez, Rs[3], Rs[4], Rs[5]), q[14]);
+      const double wz = dadd(dot3(ex, ey, ez, Rs[6], Rs[7], Rs[8]), q[15]);
+      const double* Rd = p + 4;  // crop camera
+      const double dx = dadd(wx, -p[13]), dy = dadd(wy, -p[14]), dz = dadd(wz, -p[15]);
+      out = (float)dot3(dx, dy, dz, Rd[2], Rd[5], Rd[8]);
+    }
+  }
+  a.out[((size_t)b * a.out_h + y) * a.out_w + x] = out;
+}
+
 }  // namespace
 
 int launch_warp_crops(const WarpArgs& a, hipStream_t st) {
   dim3 grid(cdiv(a.out_w, 64), cdiv(a.out_h, 4), a.batch);
   hipLaunchKernelGGL(warp_crops_kernel, grid, dim3(256), 0, st, a);
   FP_CHECK_LAUNCH("warp_crops");
+  return FP_OK;
+}
+
+int launch_warp_depth(const WarpDepthArgs& a, hipStream_t st) {
+  dim3 grid(cdiv(a.out_w, 64), cdiv(a.out_h, 4), a.batch);
+  hipLaunchKernelGGL(warp_depth_kernel, grid, dim3(256), 0, st, a);
+  FP_CHECK_LAUNCH("warp_depth");
   return FP_OK;
 }

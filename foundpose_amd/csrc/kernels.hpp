@@ -97,6 +97,30 @@ struct WarpArgs {
 };
 int launch_warp_crops(const WarpArgs& a, hipStream_t st);
 
+struct WarpDepthArgs {
+  const float* src; int src_h, src_w;
+  const double* params; const int* recompute; int batch, out_h, out_w, depth_check;
+  float* out;
+};
+int launch_warp_depth(const WarpDepthArgs& a, hipStream_t st);
+
+// ---------------------------------------------------------------- render.hip
+struct RenderArgs {
+  const float* verts; const float* normals; const float* colors; int num_verts;
+  const int* faces; int num_faces;
+  const double* cams; int batch, width, height;
+  void* vert_ws; void* tri_ws; int* tile_counts; long long* tile_offsets; int* lists; long long* status;
+  float* color; float* depth; unsigned char* mask; int* tri_id; int* boxes;
+};
+int launch_render_setup(const RenderArgs& a, hipStream_t st);
+int launch_render_raster(const RenderArgs& a, hipStream_t st);
+
+struct DownsampleArgs {
+  const float* color; const float* depth; const unsigned char* mask; int batch, out_h, out_w, factor;
+  unsigned char* rgb; unsigned short* depth_u16; unsigned char* mask_out; int* boxes;
+};
+int launch_template_downsample(const DownsampleArgs& a, hipStream_t st);
+
 int launch_sqnorm_rows(const float* x, long long n, int d, int ld, float* out, hipStream_t st);
 int launch_normalize_rows(const float* x, long long n, int d, float eps, float* out, hipStream_t st);
 int launch_topk_rows(const float* vals, int rows, int n, int ld, const int* row_len, int k, int largest,

@@ -4,8 +4,9 @@ template metadata + RGB / depth / mask images in, `repre.pth` out, with the refe
 Per object: batched extractor forwards over the templates with the patch features registered in 3D through the rendered
 depth (bank_builder.register_templates_in_3d), PCA fitted on the device (projector_util.PCAProjector.fit), k-means visual
 words (cluster_util.kmeans), tf-idf template descriptors (bank_builder.calc_tfidf_descriptors), a 3-component PCA for
-visualisation, saved with repre_util.save_object_repre.  Rendering the templates themselves (scripts/gen_templates.py)
-is upstream of this step and outside the path.
+visualisation, saved with repre_util.save_object_repre.  The templates come from gen_templates (scripts/gen_templates.py
+on the device): from its directory on disk, or handed over in memory (generate_repre(templates=...), the uint8 / uint16
+tensors synthesize_templates(return_templates=True) returns -- the same values the PNGs hold, so the same bank).
 
   python -m foundpose_amd.gen_repre --opts configs/gen_repre/lmo.json --output-path <output>
 """
@@ -63,20 +64,31 @@ def load_template_metadata(output_path: str, opts: GenRepreOpts, object_lid: int
 
 
 def generate_raw_repre(opts: GenRepreOpts, object_dataset: str, object_lid: int, extractor, metadata: List[Dict[str, Any]],
-                       batch_size: int = 32) -> repre_util.FeatureBasedObjectRepre:
-    """gen_repre.py:67-214 for all templates of one object, batched: features registered in 3D + the template images and cameras."""
+                       batch_size: int = 32, images: Optional[Dict[str, torch.Tensor]] = None) -> repre_util.FeatureBasedObjectRepre:
+    """gen_repre.py:67-214 for all templates of one object, batched: features registered in 3D + the template images and cameras.
+    images: {"rgb" u8 [T,3,S,S], "depth" u16 [T,S,S], "mask" u8 [T,S,S]} instead of the PNGs the metadata points at."""
+    if images is not None:
+        images = {"rgb": images["rgb"].cpu(), "depth": torch.from_numpy(images["depth"].cpu().numpy().astype(np.float32)),
+                  "mask": torch.from_numpy(images["mask"].cpu().numpy().astype(np.float32))}
+        if not images["rgb"].shape[0] == images["depth"].shape[0] == images["mask"].shape[0] == len(metadata):
+            raise ValueError("in-memory templates and metadata disagree in length")
     templates, depths, masks, cams, T_mfc = [], [], [], [], []
     for data_id, s in enumerate(metadata):
         assert s["dataset"] == object_dataset and s["lid"] == object_lid and s["template_id"] == data_id
         c = s["cameras"]
         cam = crop_util.PinholePlaneCameraModel(c["ImageSizeX"], c["ImageSizeY"], (c["fx"], c["fy"]), (c["cx"], c["cy"]), np.array(c["T_WorldFromCamera"]))
-        img = _load_image(s["rgb_image_path"])
-        if img.ndim == 2:
-            img = np.stack([img] * 3, -1)
-        templates.append(torch.from_numpy(np.array(img[..., :3])).permute(2, 0, 1))
-        depths.append(torch.from_numpy(_load_image(s["depth_map_path"]).astype(np.float32)))
-        m = _load_image(s["binary_mask_path"])
-        masks.append(torch.from_numpy((m if m.ndim == 2 else m[..., 0]).astype(np.float32)))
+        if images is not None:
+            templates.append(images["rgb"][data_id])
+            depths.append(images["depth"][data_id])
+            masks.append(images["mask"][data_id])
+        else:
+            img = _load_image(s["rgb_image_path"])
+            if img.ndim == 2:
+                img = np.stack([img] * 3, -1)
+            templates.append(torch.from_numpy(np.array(img[..., :3])).permute(2, 0, 1))
+            depths.append(torch.from_numpy(_load_image(s["depth_map_path"]).astype(np.float32)))
+            m = _load_image(s["binary_mask_path"])
+            masks.append(torch.from_numpy((m if m.ndim == 2 else m[..., 0]).astype(np.float32)))
         T_wfm = np.eye(4)
         T_wfm[:3, :3], T_wfm[:3, 3:] = np.array(s["pose"]["R"], np.float64).reshape(3, 3), np.array(s["pose"]["t"], np.float64).reshape(3, 1)
         # float32 like the reference (gen_repre.py:150-161): T_model_from_camera = inv(T_world_from_model) @ T_world_from_camera
@@ -126,8 +138,9 @@ def finish_repre(opts: GenRepreOpts, repre: repre_util.FeatureBasedObjectRepre) 
 
 
 def generate_repre(opts: GenRepreOpts, dataset: str, lid: int, output_path: str, extractor=None, metadata: Optional[List[Dict[str, Any]]] = None,
-                   precision: str = "bf16", weights: Optional[str] = None) -> str:
-    """-> the directory holding repre.pth and config.json (<output>/object_repre/<dataset>/<version>/<lid>)."""
+                   precision: str = "bf16", weights: Optional[str] = None, templates: Optional[Dict[str, Any]] = None) -> str:
+    """-> the directory holding repre.pth and config.json (<output>/object_repre/<dataset>/<version>/<lid>).
+    templates: one object's entry of gen_templates.synthesize_templates(return_templates=True) (tensors + metadata)."""
     out_dir = repre_util.get_object_repre_dir_path(os.path.join(output_path, "object_repre"), opts.version, dataset, lid)
     if os.path.exists(out_dir) and not opts.overwrite:
         raise ValueError(f"Output directory already exists: {out_dir}")
@@ -139,9 +152,11 @@ def generate_repre(opts: GenRepreOpts, dataset: str, lid: int, output_path: str,
         json.dump(cfg, f, indent=2)
     if extractor is None:  # gen_repre.py:250-251; raises without a checkpoint (weights.py)
         extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
+    if templates is not None and metadata is None:
+        metadata = templates["metadata"]
     if metadata is None:
         metadata = load_template_metadata(output_path, opts, lid)
-    repre = finish_repre(opts, generate_raw_repre(opts, dataset, lid, extractor, metadata))
+    repre = finish_repre(opts, generate_raw_repre(opts, dataset, lid, extractor, metadata, images=templates))
     if getattr(extractor, "precision", None) == "fp8" and extractor.act_scales is not None:
         repre.extractor_fp8_act_scales = extractor.act_scales.tolist()  # the bank carries the scales it was extracted with
     repre_util.save_object_repre(repre, out_dir)

@@ -160,3 +160,39 @@ def make_planted_query(
     xs = (cells % num_grid).float() * cell + cell / 2
     ys = (cells // num_grid).float() * cell + cell / 2
     return torch.stack([xs, ys], 1).contiguous(), feats.contiguous()
+
+
+def make_blob_mesh(num_lat: int = 50, num_lon: int = 50, radius: float = 60.0, seed: int = 0):
+    """A closed, asymmetric, vertex-coloured triangle mesh (mm): a UV sphere with random low-frequency bumps, stretched
+    along x, colours varying with position -> renderer.Mesh with about 2 * num_lat * num_lon triangles."""
+    import numpy as np
+
+    from .renderer import Mesh, vertex_normals
+    rng = np.random.default_rng(seed)
+    th = np.linspace(0, np.pi, num_lat + 1)[1:-1]                 # rings between the poles
+    ph = np.linspace(0, 2 * np.pi, num_lon, endpoint=False)
+    T, P = np.meshgrid(th, ph, indexing="ij")
+    d = np.stack([np.sin(T) * np.cos(P), np.sin(T) * np.sin(P), np.cos(T)], -1).reshape(-1, 3)
+    d = np.concatenate([[[0.0, 0.0, 1.0]], d, [[0.0, 0.0, -1.0]]])
+    bump = np.zeros(len(d))
+    for _ in range(6):
+        c = rng.normal(size=3)
+        c /= np.linalg.norm(c)
+        bump += rng.uniform(0.05, 0.2) * np.exp(-np.sum((d - c) ** 2, 1) / rng.uniform(0.1, 0.5))
+    v = d * (radius * (1.0 + bump))[:, None] * np.array([1.4, 1.0, 0.8])
+    v[:, 0] += 0.3 * radius * (d[:, 1] > 0.5)                      # a lopsided ridge: no rotational symmetry
+    faces = []
+    ring = lambda i, j: 1 + i * num_lon + (j % num_lon)            # noqa: E731
+    for j in range(num_lon):
+        faces.append((0, ring(0, j), ring(0, j + 1)))
+        faces.append((len(d) - 1, ring(num_lat - 2, j + 1), ring(num_lat - 2, j)))
+    for i in range(num_lat - 2):
+        for j in range(num_lon):
+            faces.append((ring(i, j), ring(i + 1, j), ring(i + 1, j + 1)))
+            faces.append((ring(i, j), ring(i + 1, j + 1), ring(i, j + 1)))
+    faces = np.array(faces, np.int32)
+    u = (d + 1.0) / 2.0
+    col = np.stack([u[:, 0], 0.5 + 0.5 * np.sin(6 * u[:, 1] + 3 * u[:, 2]), 1.0 - u[:, 2]], 1)
+    col = np.rint(np.clip(col, 0, 1) * 255.0).astype(np.float32) / np.float32(255.0)
+    v = v.astype(np.float32)
+    return Mesh(vertices=v, faces=faces, colors=col.astype(np.float32), normals=vertex_normals(v, faces))

@@ -457,6 +457,52 @@ int fp_warp_crops(const void* src, int n_src, int src_h, int src_w, int channels
                   const double* params, int batch, int out_h, int out_w, int depth_check, void* out, float* map_out,
                   fp_stream_t stream);
 
+/* Depth counterpart of fp_warp_crops (utils/misc.py:522-557 warp_depth_image): src fp32 [batch, src_h, src_w] (mm, 0 =
+ * background; crop b reads image b), the same params and the same fp32 map, nearest source pixel; where recompute[b] is
+ * non-zero (null: every crop) a positive source depth is replaced by the z of the same surface point in the crop camera,
+ * computed in fp64 (the reference does this when the two extrinsics are not np.allclose).  out fp32 [batch, out_h, out_w]. */
+int fp_warp_depth(const float* src, int src_h, int src_w, const double* params, const int32_t* recompute, int batch,
+                  int out_h, int out_w, int depth_check, float* out, fp_stream_t stream);
+
+/* ---- template renderer (scripts/gen_templates.py) ----------------------------------------------
+ * One vertex-coloured triangle mesh seen by `batch` pinhole cameras.  Two calls with one host synchronisation between them:
+ *   fp_render_setup   transforms and snaps every vertex, builds the triangle records and per-tile counts, scans them.
+ *                     status [4] int64 afterwards: [1] flags (bit 0: a window coordinate beyond +-FP_RENDER_MAX_FIXED / 256
+ *                     pixels or a NaN; bit 1: a face index outside the vertex range), [2] total tile-list entries,
+ *                     [3] the smallest eye-space z of any vertex in any view (fp64 bits; the caller rejects <= 100 mm, the
+ *                     reference's near plane -- nothing is clipped).  [0] is internal.
+ *   fp_render_raster  fills the tile lists (lists: int32 [status[2]]) and rasterizes: color fp32 [batch, height, width, 3]
+ *                     (k / 255), depth fp32 [batch, height, width] (eye-space z, mm, 0 = background), mask u8 (255 / 0),
+ *                     tri_id int32 (face index, -1 = background; may be null), boxes int32 [batch, 4] (min x, min y,
+ *                     max x, max y of the covered pixels; INT_MAX / INT_MIN when nothing is covered).
+ * verts / normals fp32 [num_verts, 3] (mm / unit), colors fp32 [num_verts, 3] in [0, 1], faces int32 [num_faces, 3],
+ * cams [batch, 16] doubles: f[2], c[2], R[9] (row-major rotation of T_world_from_eye), t[3] (mm).
+ * Caller-owned workspaces: vert_ws batch * num_verts * FP_RENDER_VERT_BYTES, tri_ws batch * num_faces * FP_RENDER_TRI_BYTES,
+ * tile_counts int32 [batch * tiles], tile_offsets int64 [batch * tiles + 1], tiles = ceil(width / 32) * ceil(height / 32).
+ * Both calls take the same arguments; the outputs are ignored by fp_render_setup and the lists by neither. */
+#define FP_RENDER_TILE 32
+#define FP_RENDER_VERT_BYTES 40
+#define FP_RENDER_TRI_BYTES 144
+#define FP_RENDER_MAX_FIXED 536870912.0 /* 2^29: |window coordinate| x 256, keeps every edge function exact in int64 */
+#define FP_RENDER_MAX_SIDE 8192
+int fp_render_setup(const float* verts, const float* normals, const float* colors, int num_verts, const int32_t* faces,
+                    int num_faces, const double* cams, int batch, int width, int height, void* vert_ws, void* tri_ws,
+                    int32_t* tile_counts, int64_t* tile_offsets, int32_t* lists, int64_t* status, float* color,
+                    float* depth, uint8_t* mask, int32_t* tri_id, int32_t* boxes, fp_stream_t stream);
+int fp_render_raster(const float* verts, const float* normals, const float* colors, int num_verts, const int32_t* faces,
+                     int num_faces, const double* cams, int batch, int width, int height, void* vert_ws, void* tri_ws,
+                     int32_t* tile_counts, int64_t* tile_offsets, int32_t* lists, int64_t* status, float* color,
+                     float* depth, uint8_t* mask, int32_t* tri_id, int32_t* boxes, fp_stream_t stream);
+
+/* SSAA downsample by an integer factor (gen_templates.py:373-386 with the output casts of :389-480): color fp32
+ * [batch, 3, out_h * factor, out_w * factor] (fp_warp_crops' layout), depth fp32 and mask u8 [batch, out_h * factor,
+ * out_w * factor] -> rgb u8 [batch, 3, out_h, out_w] = trunc(255 * block mean), depth_u16 = round-half-even of the block's
+ * top-left sample (clamped to [0, 65535]), mask_out = the top-left sample; boxes int32 [batch, 4] (may be null): the box of
+ * the non-zero output mask pixels as in fp_render_raster. */
+int fp_template_downsample(const float* color, const float* depth, const uint8_t* mask, int batch, int out_h, int out_w,
+                           int factor, uint8_t* rgb, uint16_t* depth_u16, uint8_t* mask_out, int32_t* boxes,
+                           fp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
