@@ -207,3 +207,92 @@ def downsample(color_chw, depth, mask, f):
     rgb = (F32(255) * mean).astype(np.uint8)
     d = np.clip(np.rint(depth[::f, ::f]), 0, 65535).astype(np.uint16)
     return rgb, d, mask[::f, ::f].copy()
+
+
+def _boxes(X, Y, faces, W, H):
+    """Per-face pixel box (x0, y0, x1, y1) as render_setup_kernel clamps it, and whether the face is binned at all
+    (non-zero area, box not empty); vectorised over faces."""
+    x, y = X[faces], Y[faces]
+    area = (x[:, 1] - x[:, 0]) * (y[:, 2] - y[:, 0]) - (y[:, 1] - y[:, 0]) * (x[:, 2] - x[:, 0])
+    x0 = np.maximum(-((128 - x.min(1)) // 256), 0)
+    x1 = np.minimum((x.max(1) - 128) // 256, W - 1)
+    y0 = np.maximum(-((128 - y.min(1)) // 256), 0)
+    y1 = np.minimum((y.max(1) - 128) // 256, H - 1)
+    return x0, y0, x1, y1, (area != 0) & (x0 <= x1) & (y0 <= y1)
+
+
+def tile_counts(verts, faces, cam, W, H, tile=32):
+    """int64 [tiles_y * tiles_x]: how many triangle records each tile list holds (render_setup_kernel, pass 0)."""
+    X, Y, _, _ = transform(verts, np.zeros_like(verts), cam)
+    x0, y0, x1, y1, live = _boxes(X, Y, np.asarray(faces, np.int64), W, H)
+    tx, ty = -(-W // tile), -(-H // tile)
+    d = np.zeros((ty + 1, tx + 1), np.int64)   # 2-D difference array over each face's tile rectangle
+    tx0, ty0, tx1, ty1 = x0[live] // tile, y0[live] // tile, x1[live] // tile + 1, y1[live] // tile + 1
+    np.add.at(d, (ty0, tx0), 1)
+    np.add.at(d, (ty0, tx1), -1)
+    np.add.at(d, (ty1, tx0), -1)
+    np.add.at(d, (ty1, tx1), 1)
+    return d.cumsum(0).cumsum(1)[:ty, :tx].reshape(-1)
+
+
+def face_coverage(verts, faces, cam, W, H):
+    """int32 [H,W]: how many faces cover each pixel centre by the edge-function test alone (no z-test)."""
+    X, Y, z, _ = transform(verts, np.zeros_like(verts), cam)
+    count = np.zeros((H, W), np.int32)
+    for face in faces:
+        r = _setup(X, Y, z, face)
+        if r is None:
+            continue
+        A, B, C, _, _, _, tl, (mnx, mxx, mny, mxy) = r
+        x0, x1 = max(-((128 - mnx) // 256), 0), min((mxx - 128) // 256, W - 1)
+        y0, y1 = max(-((128 - mny) // 256), 0), min((mxy - 128) // 256, H - 1)
+        if x0 > x1 or y0 > y1:
+            continue
+        py, px = np.mgrid[y0:y1 + 1, x0:x1 + 1]
+        PX, PY = px.astype(np.int64) * 256 + 128, py.astype(np.int64) * 256 + 128
+        inside = np.ones(PX.shape, bool)
+        for k in range(3):
+            E = A[k] * PX + B[k] * PY + C[k]
+            inside &= (E > 0) | ((E == 0) & tl[k])
+        count[y0:y1 + 1, x0:x1 + 1] += inside
+    return count
+
+
+def random_sheet(nx, ny, x_range, y_range, plane, seed):
+    """A random triangulation of the world rectangle x_range x y_range on the plane z = plane[0] + plane[1] x + plane[2] y
+    (mm): a (nx+1) x (ny+1) vertex grid, interior vertices jittered by up to 0.3 cells, each cell split along a random
+    diagonal.  -> vertices float32 [V,3], faces int32 [F,3], the boundary vertex ids in order around the rectangle."""
+    rng = np.random.default_rng(seed)
+    gx, gy = np.linspace(*x_range, nx + 1), np.linspace(*y_range, ny + 1)
+    X, Y = np.meshgrid(gx, gy)                                    # [ny+1, nx+1]
+    hx, hy = (gx[1] - gx[0]) * 0.3, (gy[1] - gy[0]) * 0.3
+    X[1:-1, 1:-1] += rng.uniform(-hx, hx, (ny - 1, nx - 1))
+    Y[1:-1, 1:-1] += rng.uniform(-hy, hy, (ny - 1, nx - 1))
+    x, y = X.astype(np.float32).astype(np.float64).reshape(-1), Y.astype(np.float32).astype(np.float64).reshape(-1)
+    z = plane[0] + plane[1] * x + plane[2] * y
+    verts = np.stack([x, y, z], 1).astype(np.float32)
+    idx = lambda i, j: j * (nx + 1) + i   # noqa: E731
+    faces = []
+    for j in range(ny):
+        for i in range(nx):
+            a, b, c, d = idx(i, j), idx(i + 1, j), idx(i, j + 1), idx(i + 1, j + 1)
+            faces += [(a, b, d), (a, d, c)] if rng.random() < 0.5 else [(a, b, c), (b, d, c)]
+    ring = [idx(i, 0) for i in range(nx)] + [idx(nx, j) for j in range(ny)] + [idx(i, ny) for i in range(nx, 0, -1)] + \
+        [idx(0, j) for j in range(ny, 0, -1)]
+    return verts, np.array(faces, np.int32), np.array(ring, np.int64)
+
+
+def inside_polygon(PX, PY, px, py):
+    """Exact (integer) point-in-polygon of the points (PX, PY) against the closed polygon (px, py), all int64 fixed point.
+    -> +1 strictly inside, -1 strictly outside, 0 on the outline."""
+    inside = np.zeros(PX.shape, bool)
+    on = np.zeros(PX.shape, bool)
+    n = len(px)
+    for k in range(n):
+        ax, ay, bx, by = int(px[k]), int(py[k]), int(px[(k + 1) % n]), int(py[(k + 1) % n])
+        cross = (bx - ax) * (PY - ay) - (by - ay) * (PX - ax)
+        on |= (cross == 0) & (PX >= min(ax, bx)) & (PX <= max(ax, bx)) & (PY >= min(ay, by)) & (PY <= max(ay, by))
+        up = (ay <= PY) & (by > PY)
+        down = (by <= PY) & (ay > PY)
+        inside ^= (up & (cross > 0)) | (down & (cross < 0))
+    return np.where(on, 0, np.where(inside, 1, -1))

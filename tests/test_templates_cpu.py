@@ -200,3 +200,75 @@ def test_metadata_is_read_back_by_gen_repre(tmp_path):
     assert (got.width, got.height, got.f, got.c) == (224, 224, (511.25, 511.25), (111.5, 111.5))
     assert np.array_equal(got.T_world_from_eye, cam.T_world_from_eye)
     np.testing.assert_allclose(np.array(c["ModelViewMatrix"]) @ cam.T_world_from_eye, np.eye(4), atol=1e-12)
+
+
+# ---------------------------------------------------------------- restatement self-checks: a watertight random sheet
+SHEET_W, SHEET_H, SHEET_F, SHEET_C = 200, 150, 600.0, (100.3, 74.8)
+SHEET_PLANES = {"fronto": (500.0, 0.0, 0.0), "tilted": (500.0, 0.5, 0.25)}
+
+
+@pytest.mark.parametrize("kind", ["fronto", "tilted"])
+def test_random_sheet_is_covered_exactly_once(kind):
+    """A random triangulation of a rectangle spanning 7 x 5 tiles: by render_ref's edge functions (before any z-test) every
+    pixel centre strictly inside the snapped outline is covered by exactly one face, none outside is covered, and one on
+    the outline at most once."""
+    plane = SHEET_PLANES[kind]
+    v, f, ring = render_ref.random_sheet(12, 9, (-60.0, 60.0), (-45.0, 45.0), plane, seed=11)
+    cam = _cam(SHEET_W, SHEET_H, (SHEET_F, SHEET_F), SHEET_C)
+    count = render_ref.face_coverage(v, f, cam, SHEET_W, SHEET_H)
+    X, Y, _, _ = render_ref.transform(v, np.zeros_like(v), cam)
+    py, px = np.mgrid[0:SHEET_H, 0:SHEET_W]
+    side = render_ref.inside_polygon(px.astype(np.int64) * 256 + 128, py.astype(np.int64) * 256 + 128, X[ring], Y[ring])
+    assert (side == 1).sum() > 15000 and (side == -1).sum() > 5000
+    assert np.all(count[side == 1] == 1) and np.all(count[side == -1] == 0) and count.max() == 1
+    depth, tri, _ = render_ref.rasterize(v, f, cam, SHEET_W, SHEET_H)
+    assert np.array_equal(tri >= 0, count == 1)
+
+
+@pytest.mark.parametrize("kind", ["fronto", "tilted"])
+def test_random_sheet_depth_is_the_plane(kind):
+    """render_ref's depth against the exact fp64 ray-plane intersection.  Snapping moves each vertex by at most 1/512 px
+    per axis while keeping its 1/z; 1/z is affine in the window, so at a covered pixel the interpolated 1/z is the true
+    plane's at a point at most 1/512 px away per axis: |d(1/z)| <= (|d(1/z)/du| + |d(1/z)/dv|) / 512.  The fp32 vertex
+    positions and the fp32 result add a few fp32 ulps."""
+    p0, p1, p2 = SHEET_PLANES[kind]
+    v, f, _ = render_ref.random_sheet(12, 9, (-60.0, 60.0), (-45.0, 45.0), (p0, p1, p2), seed=11)
+    cam = _cam(SHEET_W, SHEET_H, (SHEET_F, SHEET_F), SHEET_C)
+    depth, tri, _ = render_ref.rasterize(v, f, cam, SHEET_W, SHEET_H)
+    ys, xs = np.nonzero(tri >= 0)
+    rx, ry = (xs + 0.5 - SHEET_C[0]) / SHEET_F, (ys + 0.5 - SHEET_C[1]) / SHEET_F
+    z_true = p0 / (1.0 - p1 * rx - p2 * ry)            # z = p0 + p1 x + p2 y with (x, y) = z (rx, ry)
+    a, b = p1 / (SHEET_F * p0), p2 / (SHEET_F * p0)    # the gradient of 1/z = (1 - p1 rx - p2 ry) / p0 per pixel
+    bound = z_true ** 2 * (abs(a) + abs(b)) / 512.0 * 1.001 + 4 * np.spacing(np.float32(z_true)).astype(np.float64)
+    err = np.abs(depth[ys, xs].astype(np.float64) - z_true)
+    assert np.all(err <= bound), (err.max(), bound.min())
+    if kind == "fronto":
+        assert np.all(depth[ys, xs] == np.float32(p0))
+    else:
+        assert err.max() > 1e-4   # the snap is visible: the bound is not vacuous
+
+
+def test_tile_counts_restate_the_binning():
+    """render_ref.tile_counts (vectorised) against a per-face loop over the boxes rasterize() uses, including faces that are
+    off-screen, zero-area, or end exactly on a tile border."""
+    from foundpose_amd import synthetic
+    m = synthetic.make_blob_mesh(20, 24, radius=60.0, seed=5)
+    v = np.concatenate([m.vertices, np.array([[31.5, 5.5, 512], [32.5, 40.5, 512], [-500, 3, 512], [90, 3, 512]], np.float32)])
+    n = len(m.vertices)
+    faces = np.concatenate([m.faces, np.array([[n, n + 1, n + 3], [n, n, n + 1], [n + 2, n + 2, n + 2], [n + 2, n + 3, n]], np.int32)])
+    W, H = 100, 70
+    blob_cam = _cam(W, H, (150.0, 150.0), (47.3, 33.1), np.array([[1, 0, 0, 5], [0, 1, 0, -3], [0, 0, 1, -380.0], [0, 0, 0, 1]]))
+    # the blob seen from 380 mm, then the screen-space faces alone (f = 512 at z = 512: world x, y are pixels)
+    for v, faces, cam in ((v, faces, blob_cam), (v[n:], faces[len(m.faces):] - n, _cam(W, H, (512.0, 512.0), (0.0, 0.0)))):
+        X, Y, z, _ = render_ref.transform(v, np.zeros_like(v), cam)
+        want = np.zeros((3, 4), np.int64)
+        for face in faces:
+            r = render_ref._setup(X, Y, z, face)
+            if r is None:
+                continue
+            mnx, mxx, mny, mxy = r[-1]
+            x0, x1 = max(-((128 - mnx) // 256), 0), min((mxx - 128) // 256, W - 1)
+            y0, y1 = max(-((128 - mny) // 256), 0), min((mxy - 128) // 256, H - 1)
+            if x0 <= x1 and y0 <= y1:
+                want[y0 // 32:y1 // 32 + 1, x0 // 32:x1 // 32 + 1] += 1
+        np.testing.assert_array_equal(render_ref.tile_counts(v, faces, cam, W, H), want.reshape(-1))
