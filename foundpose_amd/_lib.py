@@ -19,7 +19,7 @@ GEMM_SPLIT_F16F8 = 1 << 20   # FP_GEMM_SPLIT_F16F8 of the header
 VIT_NO_TALL_TILES = 1        # FP_VIT_NO_TALL_TILES of the header (fp_vit_model.flags)
 GEMM_F16 = 1 << 21           # FP_GEMM_F16 of the header: IEEE fp16 operands / outputs in fp_gemm_bf16, fp_gemm_bf16_ln
 SPLIT_SCALE_ACT, SPLIT_SCALE_QKV, SPLIT_SCALE_HID = 16.0, 16.0, 4.0  # FP_SPLIT_SCALE_* of the header
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 vp, i32, i64, f32, f64, u64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_uint64
 
@@ -49,7 +49,6 @@ class VitWorkspace(C.Structure):
 
 _PROTOS = {
     "fp_abi_version": [],
-    "fp_build_experiments": [],
     "fp_sqnorm_rows": [vp, i64, i32, vp, vp],
     "fp_normalize_rows": [vp, i64, i32, f32, vp, vp],
     "fp_knn_l2": [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],

@@ -25,19 +25,13 @@ def _newer(a, b):
     return not os.path.exists(b) or os.path.getmtime(a) > os.path.getmtime(b)
 
 
-EXPERIMENT_SOURCES = ["knn_cand.hip"]   # measured-slower kernels kept for A/B runs: FP_EXPERIMENTS=1 python -m foundpose_amd.build [--force]
-
-
 def build(force: bool = False, verbose: bool = True) -> str:
-    """The shipped library.  FP_EXPERIMENTS=1 in the environment of THIS BUILD TOOL (never read by the library) compiles every source with -DFP_EXPERIMENTS
-    and adds the experiment kernels (include/foundpose_amd.h fp_build_experiments); switching between the two needs --force."""
+    """Compiles the stale objects and links the library; returns its path."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    experiments = os.environ.get("FP_EXPERIMENTS", "0") not in ("", "0")
     os.makedirs(OBJDIR, exist_ok=True)
     hdr_paths = [os.path.join(CSRC, h) for h in HEADERS]
     jobs = []
-    flags = FLAGS + (["-DFP_EXPERIMENTS"] if experiments else [])
-    for src in SOURCES + (EXPERIMENT_SOURCES if experiments else []):
+    for src in SOURCES:
         sp = os.path.join(CSRC, src)
         obj = os.path.join(OBJDIR, os.path.splitext(src)[0] + ".o")
         stale = force or _newer(sp, obj) or any(_newer(h, obj) for h in hdr_paths)
@@ -47,7 +41,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         sp, obj, stale = job
         if not stale:
             return
-        cmd = [hipcc, *flags, "-x", "hip", "-c", sp, "-o", obj]
+        cmd = [hipcc, *FLAGS, "-x", "hip", "-c", sp, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

@@ -151,11 +151,7 @@ __global__ __launch_bounds__(256, 4) void attn_bf16_kernel(AttnArgs a) {
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
     // lazy rescale, per query: the exponent's reference m_run moves only when the tile maximum exceeds it by more than 8 in the
     // exponent (see attn_bf16_w64_kernel; the same rule, so the two kernels stay bit-identical)
-#ifdef FP_ATTN_EAGER_RESCALE
-    const bool moves = mx > m_run;
-#else
     const bool moves = mx - m_run > 8.f / (0.125f * 1.44269504088896340736f);
-#endif
     const bool grow = __any(moves);
     float alpha = 1.f;
     if (grow) {
@@ -236,18 +232,12 @@ __global__ __launch_bounds__(256, 4) void attn_bf16_kernel(AttnArgs a) {
 // Rows past the last token read as zeros (buffer range check) and are masked exactly like before.
 typedef __attribute__((address_space(3))) void lds_void_t;
 
-// QB = 32-query blocks per wave: 2 (4 waves per block, 208 VGPRs, 2 waves/SIMD -- the default) or 1 (8 waves per block of the
-// same 256 queries, <= 128 VGPRs, 4 waves/SIMD: more waves to overlap, twice the LDS fragment traffic per flop).
-// NW = waves per block (default 512 / (64 QB): a 256-query block); QB = 2 with NW = 8 is a 512-query block: a staged K/V tile then serves
-// twice the queries (variant 3, measured in DESIGN section 5).  Each wave stages GW = 8 / NW of the tile's eight 8-key row groups.
-// PF (variant 4, measurement): the NEXT tile's eight K fragments are read into registers under the current tile's P V MFMAs (its DMA was
-// issued at the top of this tile and has landed by then: the compiler drains vmcnt before the first transpose read anyway; one extra
-// barrier publishes the other waves' pieces), so the next tile's score MFMAs start without waiting for LDS.  Same arithmetic.
+// QB = 2 32-query blocks per wave, 4 waves: 208 VGPRs, 2 waves/SIMD.  Each wave stages two of the tile's eight 8-key row groups.
 // H16 ("f16" mode): q | k | v, P and the output are IEEE fp16 instead of bf16 (v_mfma_f32_32x32x16_f16; p <= 2^8 and a convex combination of v rows
 // both fit the format); everything else -- layouts, schedule, fp32 online softmax -- is shared.
-template <int QB, int NW = 8 / QB, bool PF = false, bool H16 = false>
-__global__ __launch_bounds__(NW * 64, 2) void attn_bf16_w64_kernel(AttnArgs a) {
-  constexpr int QBLK = NW * 32 * QB, GW = 8 / NW;
+template <bool H16>
+__global__ __launch_bounds__(256, 2) void attn_bf16_w64_kernel(AttnArgs a) {
+  constexpr int QB = 2, QBLK = 256;
   __shared__ __attribute__((aligned(16))) char KV[2][2][8192];  // [stage][K | V]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar: DMA offsets
   const int l31 = lane & 31, kh = lane >> 5;
@@ -287,7 +277,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bf16_w64_kernel(AttnArgs a) {
   // half the time.  Block-uniform.  (Running the launch's LAST blocks as such half blocks, to fill the drain of the final round with
   // twice as many blocks of half the lifetime, measured slower -- 345 / 353 / 363 us for the last 32 / 64 / 128 workgroup slots per
   // XCD against 344 without: the half blocks stage every K / V tile for half the queries.)
-  const bool short_tail = QB == 2 && qt == (NQ + QBLK - 1) / QBLK - 1 && NQ - qt * QBLK <= QBLK / 2;
+  const bool short_tail = qt == (NQ + QBLK - 1) / QBLK - 1 && NQ - qt * QBLK <= QBLK / 2;
   const int nqb = short_tail ? 1 : QB;
   const int q0 = qt * QBLK + wave * (32 * nqb);
   const bool active = q0 < NQ;  // wave-uniform; an inactive wave only stages tiles and keeps the barriers
@@ -300,21 +290,15 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bf16_w64_kernel(AttnArgs a) {
   const unsigned voff_k1 = rowoff + ((sp ^ ((sr >> 1) + 4)) << 4);  // odd row group: ... + 4
   const unsigned voff_v = rowoff + ((sp ^ (((sr >> 1) & 1) << 2)) << 4);
   const unsigned tile_stride = (unsigned)(64 * a.ld_qkv) * 2u, grp_stride = (unsigned)(8 * a.ld_qkv) * 2u;
-  const unsigned soff_k = (unsigned)(D + head * 64) * 2u + (unsigned)GW * wave * grp_stride, soff_v = soff_k + (unsigned)D * 2u;
-  const unsigned voff_kw = (wave & 1) ? voff_k1 : voff_k0;  // GW == 1: wave w stages row group w only
+  const unsigned soff_k = (unsigned)(D + head * 64) * 2u + 2u * wave * grp_stride, soff_v = soff_k + (unsigned)D * 2u;
   auto stage_tile = [&](int kt, int stage) {
     const unsigned t = kt * tile_stride;
-    char* kd = KV[stage][0] + wave * (1024 * GW);
-    char* vd = KV[stage][1] + wave * (1024 * GW);
-    if constexpr (GW == 2) {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)kd, 16, voff_k0, soff_k + t, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(kd + 1024), 16, voff_k1, soff_k + t + grp_stride, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)vd, 16, voff_v, soff_v + t, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(vd + 1024), 16, voff_v, soff_v + t + grp_stride, 0, 0);
-    } else {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)kd, 16, voff_kw, soff_k + t, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)vd, 16, voff_v, soff_v + t, 0, 0);
-    }
+    char* kd = KV[stage][0] + wave * 2048;
+    char* vd = KV[stage][1] + wave * 2048;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)kd, 16, voff_k0, soff_k + t, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(kd + 1024), 16, voff_k1, soff_k + t + grp_stride, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)vd, 16, voff_v, soff_v + t, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(vd + 1024), 16, voff_v, soff_v + t + grp_stride, 0, 0);
   };
   const int nkt = (N + 63) / 64;
   stage_tile(0, 0);
@@ -351,13 +335,6 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bf16_w64_kernel(AttnArgs a) {
   // the LDS-DMA of the iteration (one full load latency exposed per tile)
   __builtin_amdgcn_s_waitcnt(0x0f70);
   __syncthreads();
-  bf16x8 kfn[PF ? 4 : 1][2];   // PF: the K fragments of the tile about to be scored
-  if constexpr (PF) {
-#pragma unroll
-    for (int ds = 0; ds < 4; ++ds)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) kfn[ds][ks] = read_frag(KV[0][0], ks * 32 + krow, ds * 2 + kh);
-  }
   // one key tile; RAGGED (the last tile when N % 64 != 0) is a separate instantiation so that the full tiles carry no
   // masking code at all (inlined into one loop the compiler if-converts the mask into 120 selects per tile)
   auto tile = [&](int kt, auto ragged, auto qblocks, auto halfkeys) {
@@ -370,14 +347,12 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bf16_w64_kernel(AttnArgs a) {
     const int key0 = kt * 64;
     const char* Ks = KV[kt & 1][0];
     const char* Vs = KV[kt & 1][1];
-#ifndef FP_ATTN_NO_DMA  // (measurement builds, tools/attn_ablate.sh: the tile loop without its K/V stream -- every tile re-reads tile 0's image)
     // the other stage was last read one iteration ago.  (Issued from inside the softmax instead -- between the two query blocks, a
     // VALU-only stretch -- the kernel measured 1.5 % SLOWER: 362 vs 356 us; issued after the tile's first two K fragment reads: 344 vs 338.)
     if (!RAGGED && kt + 1 < nkt) stage_tile(kt + 1, (kt + 1) & 1);
-#endif
     bf16x8 pf[QC][4];
     if (active) {
-      if constexpr (!PF) __builtin_amdgcn_iglp_opt(1);  // the compiler's MFMA / LDS interleaving strategy 1 for the tile body: +0.5 % same-box (0, 2, 3: -1...-2 %); (its solver does not terminate on the PF body)
+      __builtin_amdgcn_iglp_opt(1);  // the compiler's MFMA / LDS interleaving strategy 1 for the tile body: +0.5 % same-box (0, 2, 3: -1...-2 %)
       // ---- S^T = K Q^T for both query blocks: sacc[qb][ks][r] = score(query l31 of block qb, key key0 + ks*32 + 16*(r>>3) + 8*kh + (r&7))
       f32x16 sacc[QC][2];
       // four independent accumulation chains (2 key halves x 2 query blocks) interleaved over the four 16-d steps (two chains, key
@@ -392,35 +367,11 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bf16_w64_kernel(AttnArgs a) {
       for (int ds = 0; ds < 4; ++ds)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-#ifdef FP_ATTN_NO_LDS  // (measurement builds: fragments from registers instead of LDS)
-          bf16x8 kf = qf[0][ds];
-          kf[0] = (__bf16)(float)((kt + ks) & 3);
-#else
-          const bf16x8 kf = PF ? kfn[PF ? ds : 0][ks] : read_frag(Ks, ks * 32 + krow, ds * 2 + kh);  // one K fragment, two MFMAs
-#endif
+          const bf16x8 kf = read_frag(Ks, ks * 32 + krow, ds * 2 + kh);  // one K fragment, two MFMAs
 #pragma unroll
           for (int qb = 0; qb < QC; ++qb)
             sacc[qb][ks] = mfma_h<H16>(kf, qf[qb][ds], sacc[qb][ks]);
         }
-#if !defined(FP_ATTN_NO_LDS) && defined(FP_ATTN_TR_ASM)
-      // (-DFP_ATTN_TR_ASM, measured and NOT the default.)  The tile's eight V^T fragments issued HERE (they land under the softmax)
-      // and as inline asm: through the builtin the compiler cannot tell a transpose read from an access to the stage the LDS-DMA
-      // is filling and puts s_waitcnt vmcnt(0) in front of the first one -- the prefetch of tile t+1 has to land in the middle of
-      // tile t.  (LDS returns in order, so the compiler's own lgkmcnt waits for its K reads stay conservative with these in the
-      // queue.)  Same speed within the noise of one box (347.6 / 347.0 us vs 341.5 / 350.0), 235 instead of 208 VGPRs.
-      s16x4 vlo[4][2], vhi[4][2];
-      {
-        const unsigned vs0 = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)(Vs + vrd0);
-        const unsigned vs1 = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)(Vs + (vrd0 ^ 64));
-#pragma unroll
-        for (int kstep = 0; kstep < 4; ++kstep) {
-          asm volatile("ds_read_b64_tr_b16 %0, %4 offset:%6\n\tds_read_b64_tr_b16 %1, %4 offset:%7\n\t"
-                       "ds_read_b64_tr_b16 %2, %5 offset:%6\n\tds_read_b64_tr_b16 %3, %5 offset:%7"
-                       : "=&v"(vlo[kstep][0]), "=&v"(vhi[kstep][0]), "=&v"(vlo[kstep][1]), "=&v"(vhi[kstep][1])
-                       : "v"(vs0), "v"(vs1), "n"(kstep * 2048), "n"(kstep * 2048 + 512));
-        }
-      }
-#endif
 #pragma unroll
       for (int qb = 0; qb < QC; ++qb) {
         if constexpr (RAGGED) {  // mask the padded keys (one lane-dependent limit, constant offsets)
@@ -448,11 +399,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bf16_w64_kernel(AttnArgs a) {
         // 1 - (1 - 1/t)^32) and the wave pays the rescale of its 64 accumulator registers nearly every tile.
         // The decision is per QUERY (a lane whose query does not move multiplies by exactly 1): a query's result does not depend
         // on which other queries share its wave -- selected-token runs stay bit-identical to the full forward.
-#ifdef FP_ATTN_EAGER_RESCALE
-        const bool moves = mx > m_run[qb];
-#else
         const bool moves = mx - m_run[qb] > LAZY_TH;
-#endif
         const bool grow = __any(moves);
         float alpha = 1.f;
         if (grow) {
@@ -489,74 +436,34 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bf16_w64_kernel(AttnArgs a) {
           }
       }
       // ---- O^T += V^T P^T over 4 steps of 16 keys; one V^T fragment serves both query blocks
-    }
-    if constexpr (PF && !RAGGED) {
-      if (kt + 1 < nkt) {     // (block-uniform, inactive waves included) the next tile's DMA has landed in every wave: publish it
-        __builtin_amdgcn_s_waitcnt(0x0f70);
-        __syncthreads();
-      }
-    }
-    if (active) {
-      if constexpr (PF && !RAGGED) {
-        if (kt + 1 < nkt) {   // ... and read its K fragments under the P V MFMAs below
-          const char* Kn = KV[(kt + 1) & 1][0];
-#pragma unroll
-          for (int ds = 0; ds < 4; ++ds)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) kfn[ds][ks] = read_frag(Kn, ks * 32 + krow, ds * 2 + kh);
-        }
-      }
-#if !defined(FP_ATTN_NO_LDS) && defined(FP_ATTN_TR_ASM)
-      asm volatile("s_waitcnt lgkmcnt(0)"  // the asm reads above (the compiler does not count them)
-                   : "+v"(vlo[0][0]), "+v"(vhi[0][0]), "+v"(vlo[0][1]), "+v"(vhi[0][1]), "+v"(vlo[1][0]), "+v"(vhi[1][0]), "+v"(vlo[1][1]), "+v"(vhi[1][1]),
-                     "+v"(vlo[2][0]), "+v"(vhi[2][0]), "+v"(vlo[2][1]), "+v"(vhi[2][1]), "+v"(vlo[3][0]), "+v"(vhi[3][0]), "+v"(vlo[3][1]), "+v"(vhi[3][1]));
-#endif
 #pragma unroll
       for (int kstep = 0; kstep < 2 * KS; ++kstep)
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
           const char* vp = Vs + (vrd0 ^ (dt << 6)) + kstep * 2048;  // + 512 B = 4 keys on
-#ifdef FP_ATTN_NO_LDS
-          bf16x8 vf = qf[0][kstep];
-          vf[0] = (__bf16)(float)((kt + dt) & 3);
-          (void)vp;
-#elif !defined(FP_ATTN_TR_ASM)
           const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vp));
           const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vp + 512));
           const bf16x8 vf = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-#else
-          (void)vp;
-          const bf16x8 vf = __builtin_bit_cast(bf16x8, __builtin_shufflevector(vlo[kstep][dt], vhi[kstep][dt], 0, 1, 2, 3, 4, 5, 6, 7));
-#endif
 #pragma unroll
           for (int qb = 0; qb < QC; ++qb)
             oacc[qb][dt] = mfma_h<H16>(vf, pf[qb][kstep], oacc[qb][dt]);
         }
     }
-#ifndef FP_ATTN_NO_BARRIER  // (measurement builds: no per-tile wait + barrier; only meaningful together with FP_ATTN_NO_DMA)
     if constexpr (!RAGGED) {
       __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the compiler does not wait for LDS-DMA before a barrier
       __syncthreads();
     }
-#endif
   };
   const int nfull = N / 64;
   auto run = [&](auto qblocks) {
     for (int kt = 0; kt < nfull; ++kt) tile(kt, std::false_type{}, qblocks, std::false_type{});
     if (nfull < nkt) {
-#ifndef FP_ATTN_NO_HALF  // (measurement build: the ragged tile always at full width)
-      if (!PF && N - nfull * 64 <= 32) tile(nfull, std::true_type{}, qblocks, std::true_type{});
-      else
-#endif
-      tile(nfull, std::true_type{}, qblocks, std::false_type{});
+      if (N - nfull * 64 <= 32) tile(nfull, std::true_type{}, qblocks, std::true_type{});
+      else tile(nfull, std::true_type{}, qblocks, std::false_type{});
     }
   };
-  if constexpr (QB == 2) {
-    if (short_tail) run(std::integral_constant<int, 1>{});
-    else run(std::integral_constant<int, 2>{});
-  } else {
-    run(std::integral_constant<int, QB>{});
-  }
+  if (short_tail) run(std::integral_constant<int, 1>{});
+  else run(std::integral_constant<int, 2>{});
 
   if (active) {
     float sat_amax = 0.f;  // fp8 output: largest |scale * o| quantised (saturation report)
@@ -601,7 +508,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bf16_w64_kernel(AttnArgs a) {
 }
 
 // ---------------------------------------------------------------- split-fp16 (f16x3 mode): near-exact attention on the fp16 MFMA
-// Same structure as attn_bf16_w64_kernel<1> (8 waves x one 32-query block, K/V tiles by LDS-DMA, S^T = K Q^T so a lane owns one
+// Same structure as attn_bf16_w64_kernel, on 8 waves x one 32-query block (K/V tiles by LDS-DMA, S^T = K Q^T so a lane owns one
 // query's scores, V^T by transpose reads), but every operand is a split-fp16 pair (common.hpp) and every product three MFMAs
 // (hi*hi + hi*lo + lo*hi, fp32 accumulate): q, k, v arrive as the split rows the qkv GEMM wrote (scale SQ each), P is split in
 // registers (scale 2^14; its row sum is taken from the unsplit fp32 values), the output leaves as a split row (scale out_scale).
@@ -615,7 +522,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_bf16_w64_kernel(AttnArgs a) {
 // which attn_launch / fp_attention_split require.
 constexpr float SPLIT_LAZY_TH = 1.f / (0.125f * 1.44269504088896340736f);
 
-// Per-wave state and the three per-tile phases both split-fp16 kernels run (the schedules differ, the arithmetic does not: bit-identical outputs).
+// Per-wave state and the three per-tile phases of the split-fp16 kernel.
 //   scores():  S^T = K Q^T for 64 keys.  A-row i of a 32-key half holds key i with bits 2 and 3 swapped, so that output register r of lane
 //              (query l31, half kh) is key 16 (r >> 3) + 8 kh + (r & 7) of its half: eight consecutive keys per 16-key step, which is the B
 //              operand layout of the P V MFMA -- P is packed where it is, no cross-lane exchange.
@@ -670,14 +577,8 @@ struct SplitAttnWave {
       for (int ks = 0; ks < 2; ++ks) {
         const int row = ks * 32 + krow;
         const char* kr = Ks + row * 256;
-#ifdef SPP_NO_LDS   // measurement build: fragments from registers (loop-variant through keys_left, so nothing is hoisted or merged)
-        kfh[ks] = qh[(ds + ks) & 3]; kfl[ks] = ql[(ds + ks + 1) & 3];
-        kfh[ks][0] = (_Float16)(float)(keys_left & 7); kfl[ks][1] = (_Float16)(float)((keys_left >> 3) & 7);
-        (void)kr;
-#else
         kfh[ks] = *reinterpret_cast<const f16x8*>(kr + ((ch ^ (row & 15)) << 4));
         kfl[ks] = *reinterpret_cast<const f16x8*>(kr + (((ch + 4) ^ (row & 15)) << 4));
-#endif
       }
       // the two key halves' chains interleaved (per accumulator the order is lo.hi, hi.lo, hi.hi over ds ascending)
       sacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfl[0], qh[ds], sacc[0], 0, 0, 0);
@@ -766,18 +667,12 @@ struct SplitAttnWave {
       for (int dt = 0; dt < 2; ++dt) {
         const char* vph = Vs + vrd0 + (((2 * dt) ^ kq) << 6) + kstep * 4096;       // hi unit of d-group dt (+ 1024 B = 4 keys on)
         const char* vpl = Vs + vrd0 + (((2 * dt + 1) ^ kq) << 6) + kstep * 4096;   // lo unit
-#ifdef SPP_NO_LDS
-        vfh[dt] = qh[(kstep + dt) & 3]; vfl[dt] = ql[(kstep + dt + 1) & 3];
-        vfh[dt][0] = (_Float16)(float)((size_t)Vs & 0x8000 ? 1 : 2); vfl[dt][1] = (_Float16)(float)((size_t)Vs & 0x10000 ? 1 : 3);
-        (void)vph; (void)vpl;
-#else
         const s16x4 h_lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vph));
         const s16x4 h_hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vph + 1024));
         const s16x4 l_lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vpl));
         const s16x4 l_hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vpl + 1024));
         vfh[dt] = __builtin_bit_cast(f16x8, __builtin_shufflevector(h_lo, h_hi, 0, 1, 2, 3, 4, 5, 6, 7));
         vfl[dt] = __builtin_bit_cast(f16x8, __builtin_shufflevector(l_lo, l_hi, 0, 1, 2, 3, 4, 5, 6, 7));
-#endif
       }
       oacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfl[0], ph[kstep], oacc[0], 0, 0, 0);
       oacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfl[1], ph[kstep], oacc[1], 0, 0, 0);
@@ -787,119 +682,9 @@ struct SplitAttnWave {
       oacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfh[1], ph[kstep], oacc[1], 0, 0, 0);
     }
   }
-  // The matrix phase of the role-split kernel's steady state -- P V of one tile, then S^T of the next -- as one pinned instruction order: the
-  // wave is alone on its SIMD's matrix pipe (its partner is in its softmax), so nobody else hides its LDS latency or fills its issue gaps.
-  // Eight steps of six MFMAs (four P V steps of 16 keys, four S steps of 16 d); the fragments of step i + 1 are read in the gaps behind the
-  // first four MFMAs of step i (two transpose reads or one b128 read per gap), `dma` (the wave's LDS-DMA loads of the tiles ahead) rides in the
-  // gaps of the first S step -- behind the last transpose read of the iteration.  Same MFMAs, same order per accumulator as pv() + scores().
-  template <class F>
-  FP_DEVICE void matrix(const char* Vs, const char* Ks, F&& dma) {
-#define SPP_PIN() __builtin_amdgcn_sched_barrier(0)
-    // (Measurement switches SPP_NOP_A / SPP_NOP_B: `s_nop n` behind every MFMA of this phase, A: one followed by fragment reads, B: one that is not.
-    // A wave whose NEXT instruction is an MFMA waiting for the busy matrix pipe holds the SIMD's issue arbitration -- beside 48 dense MFMAs a
-    // partner's 64 v_fma take 1536 cycles instead of 340, with one s_nop 7 per MFMA 408 (tools/ubench/mfma_valu_corun.hip) -- but THIS phase has
-    // fragment reads and their waits between its MFMAs already: every nop setting measured slower, 803 us without -> 807 ... 845 us.  Off.)
-#ifndef SPP_NOP_A
-#define SPP_NOP_A -1
-#endif
-#ifndef SPP_NOP_B
-#define SPP_NOP_B -1
-#endif
-#define SPP_STR2(x) #x
-#define SPP_STR(x) SPP_STR2(x)
-#define SPP_GAP_A() do { if (SPP_NOP_A >= 0) asm volatile("s_nop " SPP_STR(SPP_NOP_A)); } while (0)
-#define SPP_GAP_B() do { if (SPP_NOP_B >= 0) asm volatile("s_nop " SPP_STR(SPP_NOP_B)); } while (0)
-    auto ldv = [&](int kstep, int part) {  // part: 0 = hi of d-group 0, 1 = lo of d-group 0, 2 = hi of d-group 1, 3 = lo of d-group 1
-      const char* vp = Vs + vrd0 + ((part ^ kq) << 6) + kstep * 4096;
-      const s16x4 x = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vp));
-      const s16x4 y = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vp + 1024));
-      return __builtin_bit_cast(f16x8, __builtin_shufflevector(x, y, 0, 1, 2, 3, 4, 5, 6, 7));
-    };
-    auto ldk = [&](int ds, int part) {     // part: 0 = hi of key half 0, 1 = lo of key half 0, 2 = hi of key half 1, 3 = lo of key half 1
-      const int ch = (ds >> 1) * 8 + (ds & 1) * 2 + kh + (part & 1) * 4, row = (part >> 1) * 32 + krow;
-      return *reinterpret_cast<const f16x8*>(Ks + row * 256 + ((ch ^ (row & 15)) << 4));
-    };
-    f16x8 c[4], n[4];
-#pragma unroll
-    for (int part = 0; part < 4; ++part) c[part] = ldv(0, part);
-    SPP_PIN();
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      oacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(c[1], ph[k], oacc[0], 0, 0, 0);
-      SPP_PIN();
-      n[0] = k < 3 ? ldv(k + 1, 0) : ldk(0, 0);
-      SPP_GAP_A();
-      SPP_PIN();
-      oacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(c[3], ph[k], oacc[1], 0, 0, 0);
-      SPP_PIN();
-      n[1] = k < 3 ? ldv(k + 1, 1) : ldk(0, 1);
-      SPP_GAP_A();
-      SPP_PIN();
-      oacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(c[0], pl[k], oacc[0], 0, 0, 0);
-      SPP_PIN();
-      n[2] = k < 3 ? ldv(k + 1, 2) : ldk(0, 2);
-      SPP_GAP_A();
-      SPP_PIN();
-      oacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(c[2], pl[k], oacc[1], 0, 0, 0);
-      SPP_PIN();
-      n[3] = k < 3 ? ldv(k + 1, 3) : ldk(0, 3);
-      SPP_GAP_A();
-      SPP_PIN();
-      oacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(c[0], ph[k], oacc[0], 0, 0, 0);
-      SPP_PIN();
-      SPP_GAP_B();
-      SPP_PIN();
-      oacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(c[2], ph[k], oacc[1], 0, 0, 0);
-      SPP_PIN();
-      SPP_GAP_B();
-      SPP_PIN();
-#pragma unroll
-      for (int part = 0; part < 4; ++part) c[part] = n[part];
-    }
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ds = 0; ds < 4; ++ds) {
-      sacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(c[1], qh[ds], ds ? sacc[0] : zero, 0, 0, 0);
-      SPP_PIN();
-      if (ds < 3) n[0] = ldk(ds + 1, 0);
-      SPP_GAP_A();
-      SPP_PIN();
-      sacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(c[3], qh[ds], ds ? sacc[1] : zero, 0, 0, 0);
-      SPP_PIN();
-      if (ds < 3) n[1] = ldk(ds + 1, 1);
-      SPP_GAP_A();
-      SPP_PIN();
-      sacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(c[0], ql[ds], sacc[0], 0, 0, 0);
-      SPP_PIN();
-      if (ds < 3) n[2] = ldk(ds + 1, 2);
-      SPP_GAP_A();
-      SPP_PIN();
-      sacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(c[2], ql[ds], sacc[1], 0, 0, 0);
-      SPP_PIN();
-      if (ds < 3) n[3] = ldk(ds + 1, 3);
-      SPP_GAP_A();
-      SPP_PIN();
-      sacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(c[0], qh[ds], sacc[0], 0, 0, 0);
-      SPP_PIN();
-      if (ds == 0) dma();
-      SPP_GAP_B();
-      SPP_PIN();
-      sacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(c[2], qh[ds], sacc[1], 0, 0, 0);
-      SPP_PIN();
-      SPP_GAP_B();
-      SPP_PIN();
-      if (ds < 3) {
-#pragma unroll
-        for (int part = 0; part < 4; ++part) c[part] = n[part];
-      }
-    }
-#undef SPP_GAP_A
-#undef SPP_GAP_B
-#undef SPP_PIN
-  }
 };
 
-// Epilogue of the split-fp16 attention kernels: O = sum(P v) / l without the scales of P and v, written as a split-fp16 row or an f16f8 row.
+// Epilogue of the split-fp16 attention kernel: O = sum(P v) / l without the scales of P and v, written as a split-fp16 row or an f16f8 row.
 FP_DEVICE void split_attn_store(const AttnArgs& a, const f32x16 (&oacc)[2], float l_run, int q0, int l31, int kh, int NQ, int sel_base, int img, int N, int head) {
   const int q = q0 + l31;
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
@@ -1045,251 +830,6 @@ __global__ __launch_bounds__(512, 2) void attn_split_kernel(AttnArgs a) {
   if (active) split_attn_store(a, w.oacc, w.l_run, q0, l31, kh, NQ, sel_base, img, N, head);
 }
 
-#ifdef FP_EXPERIMENTS   // built, bit-identical and ~3 % SLOWER than attn_split_kernel (profiles/EXPERIMENTS.md round 5): measurement builds only
-// ---------------------------------------------------------------- split-fp16, role-split ("ping-pong") form (AttnArgs.variant 2 of the split kernels)
-// The same arithmetic as attn_split_kernel, instruction for instruction per query (same MFMA order per accumulator, same softmax, same
-// epilogue: bit-identical outputs), on another schedule.  In the lock-step kernel the two waves a 512-thread workgroup places on each SIMD
-// (waves w and w + 4) walk S -> softmax -> P V together behind one barrier per key tile, so the SIMD's matrix pipe idles while both waves are
-// in their softmax and its VALU while both are in their MFMAs: a tile costs the SUM of the two (measured: 48 MFMAs = 1536 cycles + ~300 VALU
-// per wave and tile, 7.0 k cycles per tile for the pair).  Here the waves of a SIMD run half a tile apart:
-//   even interval 2t:   waves 0-3: P V (t-1), S(t)         [matrix pipe]      waves 4-7: softmax(t-1)               [VALU]
-//   odd interval 2t+1:  waves 0-3: softmax(t)              [VALU]             waves 4-7: P V (t-1), S(t)           [matrix pipe]
-// with a barrier at the end of every interval (the one after the even interval orders nothing in memory, it keeps the two halves in anti-phase).
-// K / V tiles travel through a ring of three slots: every wave issues its rows of K(t+2) and V(t+1) right behind its P V (t-1) -- after its last
-// transpose read of the iteration (the compiler drains vmcnt in front of the first transpose read that follows an LDS-DMA) --, the loads of
-// iteration t have landed when iteration t + 1 ends (vmcnt(4) + barrier), one iteration ahead of their first reader.
-//   slot s: [K image 16 KiB | V image 16 KiB] (layouts as in attn_split_kernel); K(t) and V(t) live in slot t % 3
-// A short last query tile hands its 32-query blocks to waves 0, 4, 1, 5, ... so that both halves of a SIMD have work.
-constexpr int SPP_SLOT = 32768, SPP_LDS = 3 * SPP_SLOT;
-#ifdef SPP_NO_MIDBAR   // (measurement build: without the barrier that holds the two halves in anti-phase)
-#define SPP_MID_BARRIER() ((void)0)
-#else
-#define SPP_MID_BARRIER() __builtin_amdgcn_s_barrier()
-#endif
-
-__global__ __launch_bounds__(512, 2) void attn_split_pp_kernel(AttnArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char KVR[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, kh = lane >> 5;
-#if defined(SPP_GRP) && SPP_GRP == 1   // (measurement builds: tools/attn_split_ablate.sh)
-  const int grp = wave & 1;
-#else
-  const int grp = wave >> 2;  // 0: matrix phase in the even intervals; 1: half a tile behind
-#endif
-  int qt, head, img;
-  {
-    const int nqt = ((a.sel_off ? a.max_sel : a.n_tok) + 255) / 256, pairs = a.heads * a.batch, i = blockIdx.x;
-    int pair;
-    if ((pairs & 7) == 0) {  // as in attn_split_kernel: a pair's query tiles on one XCD, the short last tile at the end of the XCD's sequence
-      const int j = i >> 3;
-      if (a.tail_last && nqt > 1) {
-        const int nfull = (pairs >> 3) * (nqt - 1);
-        const bool tail = j >= nfull;
-        qt = tail ? nqt - 1 : j % (nqt - 1);
-        pair = (tail ? j - nfull : j / (nqt - 1)) * 8 + (i & 7);
-      } else {
-        qt = j % nqt;
-        pair = (j / nqt) * 8 + (i & 7);
-      }
-    } else {
-      qt = i % nqt;
-      pair = i / nqt;
-    }
-    head = pair % a.heads;
-    img = pair / a.heads;
-  }
-  const int N = a.n_tok, D = a.dim;
-  const _Float16* qkv = reinterpret_cast<const _Float16*>(a.qkv) + (size_t)img * N * a.ld_qkv;
-  const int sel_base = a.sel_off ? a.sel_off[img] : 0;
-  const int NQ = a.sel_off ? a.sel_off[img + 1] - sel_base : N;
-  if (qt * 256 >= NQ) return;  // block-uniform, before any barrier
-#if defined(SPP_GRP) && SPP_GRP == 1
-  const int q0 = qt * 256 + wave * 32;
-#else
-  const int q0 = qt * 256 + (((wave & 3) << 1) | grp) * 32;
-#endif
-  const bool active = q0 < NQ;  // wave-uniform; an inactive wave only stages tiles and keeps the barriers
-
-  // ---- staging (attn_split_kernel's): a DMA instruction moves 4 rows x 256 B; wave w issues row groups 2w, 2w + 1 of K and of V
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)qkv, 0, (unsigned)((size_t)N * a.ld_qkv * 2), 0x00020000);
-  const int sr = lane >> 4, sp = lane & 15;
-  const unsigned rowoff = (unsigned)(sr * a.ld_qkv) * 2u;
-  const unsigned voff_k0 = rowoff + ((unsigned)(sp ^ (4 * ((2 * wave) & 3) + sr)) << 4);
-  const unsigned voff_k1 = rowoff + ((unsigned)(sp ^ (4 * ((2 * wave + 1) & 3) + sr)) << 4);
-  const unsigned voff_v = rowoff + ((unsigned)((((sp >> 2) ^ sr) << 2) | (sp & 3)) << 4);
-  const unsigned tile_stride = (unsigned)(64 * a.ld_qkv) * 2u, grp_stride = (unsigned)(4 * a.ld_qkv) * 2u;
-  const unsigned soff_k = (unsigned)(2 * D + head * 128) * 2u + 2u * wave * grp_stride, soff_v = soff_k + (unsigned)(2 * D) * 2u;
-  auto stage_k = [&](int kt, int slot) {
-    const unsigned t = kt * tile_stride;
-    char* kd = KVR + slot * SPP_SLOT + wave * 2048;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)kd, 16, voff_k0, soff_k + t, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(kd + 1024), 16, voff_k1, soff_k + t + grp_stride, 0, 0);
-  };
-  auto stage_v = [&](int kt, int slot) {
-    const unsigned t = kt * tile_stride;
-    char* vd = KVR + slot * SPP_SLOT + 16384 + wave * 2048;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)vd, 16, voff_v, soff_v + t, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(vd + 1024), 16, voff_v, soff_v + t + grp_stride, 0, 0);
-  };
-  const int T = (N + 63) / 64;
-  stage_k(0, 0);
-  stage_v(0, 0);
-  if (T > 1) stage_k(1, 1);
-
-  SplitAttnWave w;
-  w.init(lane, a.in_scale);
-  {
-    const int q = q0 + l31;
-    int qc = q < NQ ? q : NQ - 1;
-    if (a.sel_rows) qc = a.sel_rows[sel_base + qc] - img * N;
-    w.load_q(qkv + (size_t)qc * a.ld_qkv + head * 128);
-  }
-#ifdef SPP_NO_MATRIX   // measurement build (tools/attn_split_ablate.sh): no MFMAs, scores = raw LDS words (values the compiler cannot fold)
-  auto s_phase = [&](int t, int slot) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int r = 0; r < 16; r += 4) {
-        const float4 x = *reinterpret_cast<const float4*>(KVR + slot * SPP_SLOT + (ks * 32 + l31) * 256 + kh * 64 + r * 4);
-        w.sacc[ks][r] = x.x * 1e-30f; w.sacc[ks][r + 1] = x.y * 1e-30f; w.sacc[ks][r + 2] = x.z * 1e-30f; w.sacc[ks][r + 3] = x.w * 1e-30f;
-      }
-  };
-  auto pv_phase = [&](int slot) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) w.oacc[0][r] += __builtin_bit_cast(float, __builtin_bit_cast(uint4, w.ph[r & 3])[r >> 2]) * 1e-30f;
-  };
-#else
-  auto s_phase = [&](int t, int slot) {
-    if (N - t * 64 < 64) w.scores<true>(KVR + slot * SPP_SLOT, N - t * 64);   // only the last tile can be ragged
-    else w.scores<false>(KVR + slot * SPP_SLOT, 64);
-  };
-  auto pv_phase = [&](int slot) { w.pv(KVR + slot * SPP_SLOT + 16384); };
-#endif
-#ifdef SPP_NO_SOFTMAX  // measurement build: the matrix phases alone (the scores stay live: no MFMA is eliminated)
-  auto softmax_phase = [&]() {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(w.sacc[ks][r]));
-  };
-#elif defined(SPP_PRIO) && SPP_PRIO == 1   // measurement builds: the softmax phase / the matrix phase at raised issue priority
-  auto softmax_phase = [&]() { __builtin_amdgcn_s_setprio(3); w.softmax(); __builtin_amdgcn_s_setprio(0); };
-#else
-  auto softmax_phase = [&]() { w.softmax(); };
-#endif
-  // this wave's rows of K(t+2) and V(t+1): always four loads (a tile index past the end reads out of range: zeros into a slot nobody reads),
-  // so "everything but this iteration's loads has landed" is vmcnt(4) in every iteration
-  auto stage_ahead = [&](int t, int s_prev, int s_next) {
-    stage_k(t + 2 < T ? t + 2 : T, s_prev);
-    stage_v(t + 1 < T ? t + 1 : T, s_next);
-  };
-#if defined(SPP_NO_MATRIX) || defined(SPP_NO_LDS) || defined(SPP_NO_PIPE)
-  auto matrix_phase = [&](int t, int sp, int sc, int sn) { pv_phase(sp); stage_ahead(t, sp, sn); s_phase(t, sc); };
-#else
-  auto matrix_phase = [&](int t, int sp, int sc, int sn) {
-#if defined(SPP_PRIO) && SPP_PRIO == 2
-    __builtin_amdgcn_s_setprio(3);
-#endif
-    w.matrix(KVR + sp * SPP_SLOT + 16384, KVR + sc * SPP_SLOT, [&]() { stage_ahead(t, sp, sn); });
-#if defined(SPP_PRIO) && SPP_PRIO == 2
-    __builtin_amdgcn_s_setprio(0);
-#endif
-  };
-#endif
-  auto end_of_iteration = [&]() {
-    __builtin_amdgcn_s_waitcnt(0x0f74);  // vmcnt(4)
-    __builtin_amdgcn_s_barrier();
-  };
-  auto next = [](int& s_prev, int& s_cur, int& s_next) { s_prev = s_cur, s_cur = s_next, s_next = s_next == 2 ? 0 : s_next + 1; };
-
-  __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0) as a builtin (see attn_bf16_w64_kernel)
-  __syncthreads();
-  int s_prev = 2, s_cur = 0, s_next = 1;
-  if (!active) {  // a wave without queries (short last query tile): its share of the staging and the barriers
-    for (int t = 0; t < T; ++t) {
-      if (grp == 0) stage_ahead(t, s_prev, s_next);
-      SPP_MID_BARRIER();
-      if (grp != 0) stage_ahead(t, s_prev, s_next);
-      end_of_iteration();
-      next(s_prev, s_cur, s_next);
-    }
-    SPP_MID_BARRIER();
-    return;
-  }
-#ifdef SPP_TIMELINE   // measurement build (tools/spp_timeline.py): s_memtime stamps of one workgroup's steady-state iterations, waves 0 and 4
-  long long* tl = reinterpret_cast<long long*>(KVR + SPP_LDS) + wave * 64;
-  int tl_n = 0;
-  const bool tl_on = blockIdx.x == SPP_TIMELINE && (wave & 3) == 0;
-#define SPP_STAMP() do { if (tl_on && tl_n < 64) { if (lane == 0) tl[tl_n] = clock64(); ++tl_n; } } while (0)
-#else
-#define SPP_STAMP() ((void)0)
-#endif
-  if (grp == 0) {
-    stage_ahead(0, s_prev, s_next);
-    s_phase(0, s_cur);
-    SPP_MID_BARRIER();
-    softmax_phase();
-    end_of_iteration();
-    next(s_prev, s_cur, s_next);
-    for (int t = 1; t < T; ++t) {
-      SPP_STAMP();
-      if (t < T - 1) {
-        matrix_phase(t, s_prev, s_cur, s_next);
-      } else {
-        pv_phase(s_prev);
-        stage_ahead(t, s_prev, s_next);
-        s_phase(t, s_cur);
-      }
-      SPP_STAMP();
-      SPP_MID_BARRIER();
-      SPP_STAMP();
-      softmax_phase();
-      SPP_STAMP();
-      __builtin_amdgcn_s_waitcnt(0x0f74);
-      SPP_STAMP();
-      __builtin_amdgcn_s_barrier();
-      next(s_prev, s_cur, s_next);
-    }
-    pv_phase(s_prev);
-    SPP_MID_BARRIER();
-  } else {
-    SPP_MID_BARRIER();
-    stage_ahead(0, s_prev, s_next);
-    s_phase(0, s_cur);
-    end_of_iteration();
-    next(s_prev, s_cur, s_next);
-    for (int t = 1; t < T; ++t) {
-      SPP_STAMP();
-      softmax_phase();   // of tile t - 1
-      SPP_STAMP();
-      SPP_MID_BARRIER();
-      SPP_STAMP();
-      if (t < T - 1) {
-        matrix_phase(t, s_prev, s_cur, s_next);
-      } else {
-        pv_phase(s_prev);
-        stage_ahead(t, s_prev, s_next);
-        s_phase(t, s_cur);
-      }
-      SPP_STAMP();
-      __builtin_amdgcn_s_waitcnt(0x0f74);
-      SPP_STAMP();
-      __builtin_amdgcn_s_barrier();
-      next(s_prev, s_cur, s_next);
-    }
-    softmax_phase();
-    SPP_MID_BARRIER();
-    pv_phase(s_prev);
-  }
-#ifdef SPP_TIMELINE
-  if (tl_on && lane == 0) {
-    long long* g = reinterpret_cast<long long*>(a.sat);   // the measurement build borrows the saturation pointer: [2][64] stamps
-    for (int i = 0; i < 64; ++i) g[(wave >> 2) * 64 + i] = i < tl_n ? tl[i] : 0;
-  }
-#endif
-  if (active) split_attn_store(a, w.oacc, w.l_run, q0, l31, kh, NQ, sel_base, img, N, head);
-}
-#endif  // FP_EXPERIMENTS
 
 // ---------------------------------------------------------------- fp32 parity-mode attention
 // qkv fp32 [B*N, 3D]; one thread per query row; keys/values of the (image, head) streamed through LDS.
@@ -1490,13 +1030,6 @@ __global__ __launch_bounds__(256, 2) void attn_f32_mfma_kernel(AttnArgs a) {
 
 }  // namespace
 
-#ifdef SPP_TIMELINE
-static long long* spp_tl_buf = nullptr;
-extern "C" int fp_debug_spp_timeline(long long* host_out) {  // [2][64]: wave 0's and wave 4's stamps of the last role-split launch
-  if (!spp_tl_buf) return 1;
-  return hipMemcpy(host_out, spp_tl_buf, 2 * 64 * sizeof(long long), hipMemcpyDeviceToHost) == hipSuccess ? 0 : 3;
-}
-#endif
 int attn_launch(const AttnArgs& a_in, int dtype, hipStream_t st) {
   AttnArgs a = a_in;
   FP_REQUIRE(a.dim % 64 == 0 && a.heads * 64 == a.dim, "attention: head_dim must be 64 (dim %d heads %d)", a.dim, a.heads);
@@ -1506,36 +1039,21 @@ int attn_launch(const AttnArgs& a_in, int dtype, hipStream_t st) {
     FP_REQUIRE(!h16 || (a.variant == 0 && a.out_fp8_scale <= 0.f && (size_t)a.n_tok * a.ld_qkv * 2 < 0xffffffffull),
                "attention(f16): the default kernel only (no work-split variants, no fp8 output), one image's qkv rows within 4 GiB");
     FP_REQUIRE(a.ld_qkv % 8 == 0 && (a.out_fp8_scale > 0.f ? a.ld_out % 4 == 0 : a.ld_out % 8 == 0), "attention(bf16): leading dims must keep 16-byte alignment");
-#ifdef FP_EXPERIMENTS
-    FP_REQUIRE(a.variant >= 0 && a.variant <= 4, "attention: unknown kernel variant %d", a.variant);
-#else   // the shipped library: the default work split and its 32-queries-per-wave cross-check; 2, 3, 4 (measured slower) live in FP_EXPERIMENTS builds
-    FP_REQUIRE(a.variant == 0 || a.variant == 1, "attention: kernel variant %d exists in FP_EXPERIMENTS builds only (0 = default, 1 = the cross-check kernel)", a.variant);
-#endif
-#ifdef FP_ATTN_DEFAULT_VARIANT  // (measurement build for same-box A/B runs of the whole pipeline: that split where 0 was asked for)
-    const int variant = a.variant == 0 ? FP_ATTN_DEFAULT_VARIANT : a.variant;
-#else
-    const int variant = a.variant;
-#endif
-    const int w64 = variant == 1 ? 0 : (variant == 2 ? 2 : 1);  // default: 64 queries per wave; 3: the same with 8 waves = 512-query blocks
+    FP_REQUIRE(a.variant == 0 || a.variant == 1, "attention: unknown kernel variant %d (0 = default, 1 = the cross-check kernel)", a.variant);
+    const bool w64 = a.variant == 0;  // default: 64 queries per wave
     FP_REQUIRE(a.out_fp8_scale <= 0.f || (w64 && a.ld_out % 4 == 0), "attention: the fp8 output exists in the 64-queries-per-wave kernel only");
     const bool sel = a.sel_off != nullptr;
     FP_REQUIRE(!sel || (a.sel_rows && a.max_sel >= 1), "attention: query selection needs sel_rows, sel_off and max_sel >= 1");
     FP_REQUIRE(!sel || (w64 && (size_t)a.n_tok * a.ld_qkv * 2 < 0xffffffffull), "attention: query selection exists in the 64-queries-per-wave kernel only");
     if (w64 && (size_t)a.n_tok * a.ld_qkv * 2 < 0xffffffffull) {
-      const unsigned grid = (unsigned)(cdiv(sel ? a.max_sel : a.n_tok, variant == 3 ? 512 : 256) * a.heads * a.batch);
+      const unsigned grid = (unsigned)(cdiv(sel ? a.max_sel : a.n_tok, 256) * a.heads * a.batch);
       // Block order: the last query tile of an (image, head) pair is short (1374 tokens = 5 x 256 + 94: the QC = 1 tail block ends in about half
       // the time).  Interleaved with the full blocks the short ones leave the final round of the launch as long as a full block; at the END of
       // each XCD's sequence the launch drains through half-length blocks: 343.6 -> 335.9 us in isolation, pipeline 1107.2 vs 1101.1 detections/s
       // (same box, three alternations; AttnArgs.tail_last = 0 is the other order).
       a.tail_last = 1;
-#ifdef FP_EXPERIMENTS
-      if (variant == 3) hipLaunchKernelGGL((attn_bf16_w64_kernel<2, 8>), dim3(grid), dim3(512), 0, st, a);
-      else if (variant == 4) hipLaunchKernelGGL((attn_bf16_w64_kernel<2, 4, true>), dim3(grid), dim3(256), 0, st, a);
-      else if (w64 == 2) hipLaunchKernelGGL(attn_bf16_w64_kernel<1>, dim3(grid), dim3(512), 0, st, a);
-      else
-#endif
-      if (h16) hipLaunchKernelGGL((attn_bf16_w64_kernel<2, 4, false, true>), dim3(grid), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL(attn_bf16_w64_kernel<2>, dim3(grid), dim3(256), 0, st, a);
+      if (h16) hipLaunchKernelGGL(attn_bf16_w64_kernel<true>, dim3(grid), dim3(256), 0, st, a);
+      else hipLaunchKernelGGL(attn_bf16_w64_kernel<false>, dim3(grid), dim3(256), 0, st, a);
     } else {
       hipLaunchKernelGGL(attn_bf16_kernel, dim3(cdiv(a.n_tok, 128) * a.heads * a.batch), dim3(256), 0, st, a);
     }
@@ -1546,28 +1064,11 @@ int attn_launch(const AttnArgs& a_in, int dtype, hipStream_t st) {
     FP_REQUIRE((size_t)a.n_tok * a.ld_qkv * 2 < 0xffffffffull, "attention(f16x3): one image's qkv rows must fit a 4-GiB buffer resource");
     a.tail_last = 1;
     const dim3 grid((unsigned)(cdiv(a.sel_off ? a.max_sel : a.n_tok, 256) * a.heads * a.batch));
-    // variant 0 / 1 = the lock-step kernel (what the pipeline runs), 2 = the role-split kernel (attn_split_pp_kernel's header; bit-identical, FP_EXPERIMENTS builds)
-    if (a.variant != 2) {
-      hipLaunchKernelGGL(attn_split_kernel, grid, dim3(512), 0, st, a);
-    } else {
-#ifndef FP_EXPERIMENTS
-      fp_set_error("attention(f16x3): the role-split kernel (variant 2) exists in FP_EXPERIMENTS builds only");
+    if (a.variant == 2) {  // the role-split kernel, measured slower and removed (profiles/EXPERIMENTS.md)
+      fp_set_error("attention(f16x3): kernel variant 2 (the role-split kernel) no longer exists");
       return FP_ERR_UNSUPPORTED;
-#else
-      static FpDeviceOnce once;
-#ifndef SPP_TIMELINE
-      fp_allow_dynamic_lds(once, attn_split_pp_kernel, SPP_LDS);
-#endif
-#ifdef SPP_TIMELINE
-      if (!spp_tl_buf) (void)hipMalloc(&spp_tl_buf, 2 * 64 * sizeof(long long));
-      a.sat = reinterpret_cast<int*>(spp_tl_buf);
-      fp_allow_dynamic_lds(once, attn_split_pp_kernel, SPP_LDS + 4096);
-      hipLaunchKernelGGL(attn_split_pp_kernel, grid, dim3(512), SPP_LDS + 4096, st, a);
-#else
-      hipLaunchKernelGGL(attn_split_pp_kernel, grid, dim3(512), SPP_LDS, st, a);
-#endif
-#endif  // FP_EXPERIMENTS
     }
+    hipLaunchKernelGGL(attn_split_kernel, grid, dim3(512), 0, st, a);  // variant 0 / 1: the lock-step kernel
   } else if (dtype == FP_DTYPE_F32) {
     FP_REQUIRE(!a.sel_off, "attention: query selection exists in the bf16 and f16x3 kernels");
     if (a.variant == 1) {  // the thread-per-query VALU kernel (one fma chain per score, keys in order): the cross-check of the MFMA kernel

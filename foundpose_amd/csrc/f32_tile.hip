@@ -179,12 +179,10 @@ __global__ __launch_bounds__(256) void f32_tile_kernel(F32TileArgs a) {
     constexpr bool FULL = decltype(full_tag)::value;
     for (int t = 0; t < nk; ++t) {
       const int cur = t & 1;
-#ifndef FP_F32_NO_STAGE
       if (t + 1 < nk) {
         load_tile(fa, Ab, a.lda, m0, a_cnt, (t + 1) * BK, a.K, tid);
         load_tile(fb, Bb, a.ldb, n0, b_cnt, (t + 1) * BK, a.K, tid);
       }
-#endif
       const float* as0 = As + cur * STAGE_FLOATS + rb[0] + l31 + kh * LDS_STRIDE;
       const float* bs0 = Bs + cur * STAGE_FLOATS + cb[0] + l31 + kh * LDS_STRIDE;
       if constexpr (FULL) {
@@ -198,14 +196,10 @@ __global__ __launch_bounds__(256) void f32_tile_kernel(F32TileArgs a) {
             nb0 = bs0[krow]; nb1 = bs0[krow + 32];
           }
           __builtin_amdgcn_sched_barrier(0);  // keep the reads above the MFMAs (the scheduler sinks them to their first use)
-#ifndef FP_F32_NO_MFMA  // (measurement builds: tools/f32_ablate.sh)
           acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
           acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
           acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
           acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-#else
-          acc[0][0][kk] += a0 * b0 + a1 * b1;
-#endif
           __builtin_amdgcn_sched_barrier(0);
           a0 = na0; a1 = na1; b0 = nb0; b1 = nb1;
         }
@@ -229,24 +223,16 @@ __global__ __launch_bounds__(256) void f32_tile_kernel(F32TileArgs a) {
           a0 = na0; a1 = na1; b0 = nb0; b1 = nb1;
         }
       }
-#ifndef FP_F32_NO_STAGE
       if (t + 1 < nk) {
         store_tile(fa, As + (cur ^ 1) * STAGE_FLOATS, tid);
         store_tile(fb, Bs + (cur ^ 1) * STAGE_FLOATS, tid);
       }
       __syncthreads();
-#endif
     }
   };
   if (live_m == BM && live_n == BN) k_loop(std::true_type{});
   else k_loop(std::false_type{});
 
-#ifdef FP_F32_NO_EPI
-  if (a.K > 0) {
-    if (acc[0][0][0] + acc[0][1][1] + acc[1][0][2] + acc[1][1][3] == 12345.678f) a.out[0] = 1.f;
-    return;
-  }
-#endif
   // ---- epilogue.  acc[tm][tn][r] is C[i][j] with
   //   i = m0 + rb[tm] + (r&3) + 8*(r>>2) + 4*(lane>>5),  j = n0 + cb[tn] + (lane&31)      (block live iff lm[tm] && ln[tn])
   if constexpr (EPI == F32_EPI_DIST_ARGMIN) {

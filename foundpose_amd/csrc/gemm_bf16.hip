@@ -16,9 +16,6 @@
 //   * logical workgroup ids are remapped so that each XCD's L2 sees a contiguous run of tiles sharing A panels; wide
 //     outputs use an 8 x 4 super-tile raster per XCD that keeps a group of W panels resident in its L2.
 // What bounds it, and what was tried and did not help: DESIGN.md section 5 "GEMM analysis".
-#include <cstdlib>
-
-#include <cstring>
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -189,13 +186,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
   // DMA issue is asymmetric on the 8-wave tile: only the waves of row wm == 0 fetch (every SIMD hosts one wave of each
   // row).  A global/buffer_load..lds blocks its wave for ~60-180 issue cycles; when all eight waves issue their pieces
   // in lock step the matrix pipes idle meanwhile, when one wave per SIMD does it the other keeps its SIMD's pipe fed.
-#ifdef FP_GEMM_ALT  // measurement build: every wave issues half as many pieces, the two wave rows in alternating halves of the K-tile
-  constexpr bool ASYM = false;
-  constexpr bool ALT = NW == 8;
-#else
   constexpr bool ASYM = NW == 8;
-  constexpr bool ALT = false;
-#endif
   constexpr int NISSUE = ASYM ? NW / 2 : NW;
   constexpr int A_INSTR = BM / 8 / NISSUE, B_INSTR = BN / 8 / NISSUE;  // DMA instructions per issuing wave per K-tile
   constexpr int PIECES = A_INSTR + B_INSTR;
@@ -410,20 +401,14 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
               wl[j] = __builtin_bit_cast(f16x8, read_frag(Ws, row, ch + 4));
             }
             // the two cross terms first (small), then hi*hi; TM*TN independent accumulators between two MFMAs of one chain
-            // (FP_SP_ABLATE = 1 / 2: measurement builds that DROP one / both cross terms -- wrong results, same operand bytes -- to bound what
-            //  cross terms on the half-cost fp8 pipe could buy: tools/build_variant.sh, profiles/EXPERIMENTS.md round 5; never in the shipped library)
-#if !defined(FP_SP_ABLATE)
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
               for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[j], ah[i], acc[i][j], 0, 0, 0);
-#endif
-#if !defined(FP_SP_ABLATE) || FP_SP_ABLATE < 2
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
               for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[j], al[i], acc[i][j], 0, 0, 0);
-#endif
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -432,13 +417,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
         } else {
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-          if constexpr (ALT) {  // wave row 0 issues its pieces during k-steps 0, 1 -- row 1 during 2, 3
-            const int slot = ks - 2 * wm;
-            if (more && slot >= 0 && slot < 2) {
-#pragma unroll
-              for (int q = 0; q < PIECES / 2; ++q) stage_piece(slot * (PIECES / 2) + q, t + 1, nxt);
-            }
-          } else
           if (more) {
 #pragma unroll
             for (int q = (ks * PIECES) / 4; q < ((ks + 1) * PIECES) / 4; ++q) stage_piece(q, t + (NSTAGE - 1), nxt);
@@ -587,20 +565,12 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
             v0 *= gm.x; v1 *= gm.y; v2 *= gm.z; v3 *= gm.w;
           }
           if constexpr (EPI == GEMM_EPI_GELU_BF16) {
-#ifndef FP_F16_GELU_ERF   // (-DFP_F16_GELU_ERF, measurement build: the erf form in the fp16 epilogue -- fc1 468 instead of 426 us, the same index agreement)
-            if constexpr (H16) {
+            if constexpr (H16) {  // (the erf form here: fc1 468 instead of 426 us, the same index agreement -- profiles/EXPERIMENTS.md)
               const f32x2 g01 = gelu_pk9(f32x2{v0, v1}), g23 = gelu_pk9(f32x2{v2, v3});
               v0 = g01[0]; v1 = g01[1]; v2 = g23[0]; v3 = g23[1];
-            } else
-#endif
-            if constexpr (SP || H16) {  // the erf form at fp32 accuracy: the split modes do not approximate below the arithmetic they emulate
-#ifdef FP_SPLIT_GELU_OCML   // (measurement build: ocml's erff, the round-3 epilogue)
-              v0 = 0.5f * v0 * (1.f + erff(v0 * 0.70710678118654752440f)); v1 = 0.5f * v1 * (1.f + erff(v1 * 0.70710678118654752440f));
-              v2 = 0.5f * v2 * (1.f + erff(v2 * 0.70710678118654752440f)); v3 = 0.5f * v3 * (1.f + erff(v3 * 0.70710678118654752440f));
-#else
+            } else if constexpr (SP) {  // the erf form at fp32 accuracy: the split modes do not approximate below the arithmetic they emulate
               const f32x2 g01 = gelu_erf_pk(f32x2{v0, v1}), g23 = gelu_erf_pk(f32x2{v2, v3});
               v0 = g01[0]; v1 = g01[1]; v2 = g23[0]; v3 = g23[1];
-#endif
             } else {
               const f32x2 g01 = gelu_pk(f32x2{v0, v1}), g23 = gelu_pk(f32x2{v2, v3});
               v0 = g01[0]; v1 = g01[1]; v2 = g23[0]; v3 = g23[1];
@@ -804,22 +774,15 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
 }
 
 // The super-tile raster of a launch (0 x 0: none -- row-major tile ids in one contiguous chunk per XCD).
-// FP_GEMM_RAST (FP_EXPERIMENTS builds only): 0 = off, 1 = the default below, "RxG" = another super-tile of R m-tiles x G n-tiles (R * G = 32; measurements:
-// profiles/EXPERIMENTS.md "super-tile shapes" -- 4x8 / 2x16 / 16x2 all lose to 8x4: only a 4-n-tile W panel (2 MiB) survives in a 4-MiB L2
-// next to the streaming A slab, and the A re-fetch per n-group that remains is what a wider group would remove).
-// Default: 4 x 8 when the output is a multiple of 8 n-tiles wide (fc1: 16), else 8 x 4 (qkv: 12) -- same-box pipeline A/B, three
-// alternations: 1043.0 detections/s against 1038.2 with 8 x 4 everywhere (profiles/EXPERIMENTS.md)
+// Super-tiles of R m-tiles x G n-tiles, R * G = 32: 4 x 8 when the output is a multiple of 8 n-tiles wide (fc1: 16), else 8 x 4 (qkv: 12) --
+// same-box pipeline A/B, three alternations: 1043.0 detections/s against 1038.2 with 8 x 4 everywhere.  (profiles/EXPERIMENTS.md "super-tile
+// shapes": 2x16 / 16x2 lose too -- only a 4-n-tile W panel (2 MiB) survives in a 4-MiB L2 next to the streaming A slab, and the A re-fetch
+// per n-group that remains is what a wider group would remove.)
 struct GemmRaster { int r, gn; };
 static GemmRaster pick_raster(int bm, int n_tiles, unsigned grid) {
-#ifdef FP_EXPERIMENTS   // (measurement builds: the super-tile shape of the sweep, read once)
-  static const int env_rast = getenv("FP_GEMM_RAST") ? atoi(getenv("FP_GEMM_RAST")) : 1;
-  static const int env_gn = (getenv("FP_GEMM_RAST") && strchr(getenv("FP_GEMM_RAST"), 'x')) ? atoi(strchr(getenv("FP_GEMM_RAST"), 'x') + 1) : 0;
-#else
-  constexpr int env_rast = 1, env_gn = 0;
-#endif
   const int wide8 = n_tiles % 8 == 0;
-  const int rr = env_gn ? env_rast : (wide8 ? 4 : 8), gn = env_gn ? env_gn : (wide8 ? 8 : 4);
-  if (env_rast && rr * gn == 32 && bm >= 256 && n_tiles % gn == 0 && n_tiles > 4 && grid >= 512) return {rr, gn};
+  const int rr = wide8 ? 4 : 8, gn = wide8 ? 8 : 4;
+  if (bm >= 256 && n_tiles % gn == 0 && n_tiles > 4 && grid >= 512) return {rr, gn};
   return {0, 0};
 }
 
@@ -899,9 +862,6 @@ int launch(const GemmBf16Args& a, hipStream_t st) {
   if constexpr (!SP && (EPI == GEMM_EPI_RESID_HILO || EPI == GEMM_EPI_RESID_F32 || EPI == GEMM_EPI_LS_RESID_F32)) {
     const int tiles_128 = (a.M_valid > 0 ? (a.M_valid + 127) / 128 : a.M / 128) * (a.N / 128);
     if ((force == 64 && a.M % 64 == 0) || (force == 0 && a.M % 64 == 0 && tiles_128 <= cus / 2))
-#ifdef FP_GEMM_SMALL_2STAGE   // (measurement build: the double-buffered loop in the small tile)
-      return launch_cfg<EPI, 64, 128, 2, 2, false, false, SP, SPOUT, false, H16, 2>(a, st);
-#endif
       return launch_cfg<EPI, 64, 128, 2, 2, false, false, SP, SPOUT, false, H16, 4>(a, st);   // four K-tiles in flight: one workgroup per CU has nothing else to hide the fetch latency behind
   }
   return launch_cfg<EPI, 128, 128, 2, 2, false, false, SP, SPOUT, SX, H16>(a, st);

@@ -40,26 +40,6 @@ struct F32TileArgs {
 
 int f32_tile_launch(int epi, const F32TileArgs& a, int max_m, int max_n, int pairs, hipStream_t st);
 
-// ---------------------------------------------------------------- knn_cand.hip
-// Exact L2 k-NN (k <= 4, dimension 64 / 128 / 256) in two stages: fp16-MFMA candidate pass with a derived bound + exact fp32 chains
-// on the candidates -- the outputs of the all-pairs exact tile (DIST_TOPK / DIST_ARGMIN) bit for bit.  Segment tables as in F32TileArgs.
-struct KnnCandArgs {
-  const float* A; const float* B; int ld;   // [*, K] fp32, one row stride for both sides
-  const float* a_sqn; const float* b_sqn;   // squared norms (k-ascending fma chains) of the rows of A / B
-  int K, M, N;                              // unsegmented: rows of A, rows of B
-  const int* a_seg_off; int pair_a_div;     // pair -> A segment pair / pair_a_div (null: the whole of A)
-  const int* b_seg_off; const int* pair_b_seg; const int* pair_b_base;   // pair -> B segment pair_b_seg[pair] (+ base of the pair's group); < 0: empty pair
-  int swap;                                 // 0: rows = the A segment, database = the B segment; 1: rows = the B segment, database = the A segment
-  int k, pairs, row_stride;                 // neighbours per row; problems; rows reserved per pair in the per-row tables (>= the longest row segment)
-  unsigned long long* lists; int* counts;   // (set by the launcher from the scratch block)
-  unsigned long long* out_keys;             // [pairs * row_stride, k] (d2 bits << 32 | index) ascending, ~0 past the database; may be null
-  float* out_d2; int* out_idx;              // [pairs * row_stride, k]; may be null
-};
-size_t knn_cand_scratch_bytes(int k, long long rows);   // rows = pairs * row_stride
-constexpr int KNN_CAND_MAX_PAIRS = 65535;   // gridDim.y of the candidate pass; callers with more (detection, slot) pairs use the all-pairs tile
-bool knn_cand_supported(int k, int K);
-int knn_cand_launch(const KnnCandArgs& a, int max_rows, int max_db, void* scratch, hipStream_t st);   // max_db: the longest database segment (sizes the split)
-
 // ---------------------------------------------------------------- match.hip
 struct CyclicArgs {
   const int* q_off;        // [B+1] query-point segment per detection
@@ -202,7 +182,7 @@ struct AttnArgs {
   // the compact [num_sel, D] result belongs to sel_rows[r]
   const int* sel_rows; const int* sel_off; int max_sel;  // max_sel >= the largest per-image count (sizes the grid)
   // bf16 work split (bit-identical outputs): 0 = 64 queries per wave, K/V by LDS-DMA (default); 1 = 32 queries per wave, register
-  // staging (the cross-check); 2 = the DMA kernel with one 32-query block per wave, 8 waves per 256-query block
+  // staging (the cross-check)
   int variant;
   int tail_last;                 // set by the launcher (bf16 w64 kernel): the last (short) query tile of every (image, head) pair goes to the END of its XCD's block sequence
   float in_scale, out_scale;     // f16x3 kernel: power-of-two scale the split-fp16 q / k / v rows carry, and the one the output row gets

@@ -8,8 +8,6 @@
 //                      scatter_add_ in flattened order) + the query side of cosine_similarity (:167)
 //   cyclic_select .... utils/corresp_util.py:49-70,135-155
 //   sample_bilinear .. utils/feature_util.py:100-131 (grid_sample bilinear, zeros, align_corners=False)
-#include <cstdlib>
-
 #include "common.hpp"
 #include "kernels.hpp"
 #include "stl_order.hpp"
@@ -170,10 +168,7 @@ typedef __attribute__((address_space(3))) void cos_lds_void;
 typedef __attribute__((address_space(1))) const void cos_gbl_cvoid;
 constexpr int COS_NMAX = 8;          // candidates kept per thread / emitted per (workgroup, detection)
 constexpr int COS_RED_PITCH = 68;    // floats per 16-lane group of a wave's score tile (64 + 4: de-phases the groups across banks)
-#ifndef FP_COS_SLOTS
-#define FP_COS_SLOTS 3               // ring depth per wave, 4-KiB chunks (measurement builds: 2 / 4)
-#endif
-constexpr int COS_SLOTS = FP_COS_SLOTS;
+constexpr int COS_SLOTS = 3;         // ring depth per wave, 4-KiB chunks
 constexpr int COS_RED_BUFS = COS_SLOTS <= 3 ? 2 : 1;  // a 4-slot ring leaves LDS for one reduction buffer (second barrier per block)
 constexpr int COS_RING_BYTES = 8 * COS_SLOTS * 4096;
 
@@ -229,9 +224,6 @@ __global__ __launch_bounds__(512) void cosine_fused_kernel(CosineArgs a) {
   const char* slice_base = reinterpret_cast<const char*>(BF ? a.bank_bf16 : (const void*)a.bank_n) + ((size_t)tb * a.W + (size_t)wave * wslice) * ESZ;
   int it_blk = first, it_ch = 0, it_slot = 0;
   auto issue = [&]() {
-#ifdef FP_COS_NO_DMA
-    return;
-#endif
     const int t0 = it_blk * 16;
 #pragma unroll
     for (int q4 = 0; q4 < 4; ++q4) {
@@ -266,19 +258,16 @@ __global__ __launch_bounds__(512) void cosine_fused_kernel(CosineArgs a) {
         const int cc = task * nch + ch;
         // loads return in order: chunk cc has landed once at most the later chunks' DMAs are outstanding
         const int ahead = total - 1 - cc < COS_SLOTS - 1 ? total - 1 - cc : COS_SLOTS - 1;  // chunks issued after this one
-#ifndef FP_COS_NO_DMA  // (measurement builds: the kernel without its bank stream)
         if (ahead >= 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
         else if (ahead == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         else if (ahead == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
         const char* cs = ring + slot * 4096 + i * 256;
         f32x4 av[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) av[j] = *reinterpret_cast<const f32x4*>(cs + (((4 * j + g) ^ i) << 4));
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // fragments are in registers before the slot is handed back
         if (cc + COS_SLOTS < total) issue();
-#ifndef FP_COS_NO_MFMA  // (measurement builds, tools/cos_ablate.sh: the kernel without its matrix work)
         if constexpr (BF) {
 #pragma unroll
           for (int j = 0; j < 4; ++j)
@@ -297,20 +286,9 @@ __global__ __launch_bounds__(512) void cosine_fused_kernel(CosineArgs a) {
 #pragma unroll
           for (int q = 0; q < NQ; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[j][3], qv[ch * 4 + j][q].w, acc[q], 0, 0, 0);
         }
-#else
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int q = 0; q < NQ; ++q) acc[q] += av[j] * f32x4{qv[ch * 4 + j][q].x, qv[ch * 4 + j][q].y, qv[ch * 4 + j][q].z, qv[ch * 4 + j][q].w};
-#endif
         slot = slot == COS_SLOTS - 1 ? 0 : slot + 1;
       }
     }
-#ifdef FP_COS_NO_REDUCE  // (measurement builds: no slice reduction, no score store, no candidate lists)
-    if (acc[0][0] == 1234.5f) a.sims[tid] = acc[0][1];
-    blk += stride;
-    continue;
-#endif
     // ---- the block's eight slice sums meet in LDS: D[template 4g + r][detection q*16 + i] of this wave's slice
     float* mine = red + (buf * 8 + wave) * RED_SLICE;
 #pragma unroll
@@ -954,7 +932,7 @@ __global__ __launch_bounds__(256) void cyclic_select_kernel(CyclicArgs a) {
   const int f0 = a.tpl_off[tpl];
   // the distance tiles left one slice of nearest-neighbour keys per tile: the nearest over the whole template / crop is the
   // smallest key over the live tiles (keys order by distance, then index: the same winner an atomicMin would have kept)
-  // (row_parts / col_parts == 1: the two-stage search of knn_cand.hip left ONE finished key per row / column)
+  // (row_parts / col_parts == 1: one tile, one finished key per row / column)
   const int np = a.row_parts == 1 ? 1 : (a.tpl_off[tpl + 1] - f0 + 127) / 128, nq = a.col_parts == 1 ? 1 : (Q + 127) / 128;
   const unsigned long long* rb = a.row_best + (size_t)pair * a.row_parts * a.row_stride;
   const unsigned long long* cb = a.col_best + (size_t)pair * a.col_parts * a.col_stride;
@@ -1361,12 +1339,7 @@ int launch_cosine_topk(const CosineArgs& a_in, int num_det, int num_obj, int max
     else hipLaunchKernelGGL(cosine_fused_kernel<2>, grid, dim3(512), lds, st, a);
     FP_CHECK_LAUNCH("cosine_fused");
     if (want_cand) {
-#ifdef FP_EXPERIMENTS
-      static const bool two_launches = getenv("FP_COSINE_MERGE_REPLAY") && atoi(getenv("FP_COSINE_MERGE_REPLAY")) == 0;  // A/B switch of measurement builds
-#else
-      constexpr bool two_launches = false;
-#endif
-      if (tie_mode == 1 && !two_launches && n_top <= 32) {  // merge + the replay of tied rows in one launch (torch order)
+      if (tie_mode == 1 && n_top <= 32) {  // merge + the replay of tied rows in one launch (torch order)
         hipLaunchKernelGGL(cand_merge_replay_kernel, dim3(num_det), dim3(256), 0, st, a.cand, gx * n_emit, num_det, n_top, out_scores, out_ids,
                            a.need_replay, a.sims, a.ld_sims, det_num_templates, max_templates);
         FP_CHECK_LAUNCH("cand_merge_replay");

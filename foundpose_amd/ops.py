@@ -325,8 +325,8 @@ def gemm_split(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, acc_scale: 
 
 def attention_split(qkv: torch.Tensor, batch: int, n_tok: int, dim: int, heads: int, in_scale: float, out_scale: float, f16f8_out: bool = False,
                     variant: int = 0) -> torch.Tensor:
-    """qkv [B*N, 6D] split rows (q | k | v) -> [B*N, 2D] split rows (f16f8_out: f16f8 rows).  variant 0 = the kernel the pipeline runs, 1 = the lock-step
-    kernel, 2 = the role-split kernel (bit-identical)."""
+    """qkv [B*N, 6D] split rows (q | k | v) -> [B*N, 2D] split rows (f16f8_out: f16f8 rows).  variant 0 and 1 both run the lock-step kernel
+    (2 is refused: FP_ATTN_VARIANT in the header)."""
     require_cuda(qkv)
     out = torch.zeros(qkv.shape[0], 2 * dim, dtype=torch.float16, device=qkv.device)
     call("fp_attention_split", ptr(qkv), qkv.stride(0), ptr(out), 2 * dim, batch, n_tok, dim, heads, float(in_scale), float(out_scale),

@@ -8,7 +8,8 @@
  *   - every pointer is a DEVICE pointer unless it says "host"; the caller owns all memory (no allocation
  *     inside the library), including scratch; all work is enqueued on `stream` (a hipStream_t), nothing
  *     synchronises; the library keeps no mutable global state besides the thread-local error string and idempotent
- *     per-device caches (which kernels already had their dynamic-LDS limit raised on a device, its CU count)
+ *     per-device caches (which kernels already had their dynamic-LDS limit raised on a device, its CU count), and
+ *     reads no environment variable
  *   - return value: 0 = ok, 1 = invalid argument, 2 = unsupported, 3 = HIP failure; fp_last_error() gives text
  *   - indices on the device are int32; distances/scores fp32; L2 distances are SQUARED (faiss convention)
  *   - canonical ordering of every top-k: best value first, ties broken by the lowest index
@@ -64,13 +65,8 @@ enum { FP_F32 = 0, FP_BF16 = 1, FP_FP8 = 2, FP_F16X3 = 3, FP_F16F8 = 4, FP_F16 =
  * absolute error <= 3e-8 (fp16 subnormals, which the MFMA honours). */
 #define FP_GEMM_F16 (1 << 21) /* OR-ed into fp_gemm_bf16's / fp_gemm_bf16_ln's `epilogue`: A, W, the 16-bit outputs and the (xb, xl) stream are IEEE fp16 */
 
-#define FP_ABI_VERSION 18
+#define FP_ABI_VERSION 19
 int fp_abi_version(void);
-/* 1 if the library was compiled with -DFP_EXPERIMENTS (FP_EXPERIMENTS=1 python -m foundpose_amd.build): the measured-slower kernels kept for A/B runs -- the
- * role-split split-fp16 attention (fp_attention_split variant 2), the bf16 attention work splits 2 / 3 / 4, the two-stage k-NN of csrc/knn_cand.hip -- and
- * their environment switches (FP_KNN_CAND, FP_GEMM_RAST, FP_COSINE_MERGE_REPLAY) exist in such builds only.  The shipped library (0) reads NO environment
- * variable and keeps no mutable state beyond its idempotent per-device launch caches. */
-int fp_build_experiments(void);
 const char* fp_last_error(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -87,12 +83,7 @@ int fp_normalize_rows(const float* x, int64_t n, int d, float eps, float* out, f
 /* Exact brute-force L2 k-NN: KNN.fit + KNN.search with metric "l2" (utils/knn_util.py:38-106).
  * q [m,d], db [n,d], precomputed squared norms of both.  Scratch: FP_KNN_SCRATCH_BYTES(m, n, k): k == 1: m*8 bytes; 2 <= k <= 8:
  * m * max(ceil(n/128) * k * 8, 704) bytes (candidate keys, no distance matrix); k > 8: m*n*4 bytes.  out_d2 [m,k] (squared),
- * out_idx [m,k] int32, ascending, ties -> lowest index, (inf, -1) past the database size.
- * FP_EXPERIMENTS builds only (fp_build_experiments() == 1, there with FP_KNN_CAND=1 in the environment; measured slower than the all-pairs tile on the benchmark shapes): 2 <= k <= 4
- * with d = 64 / 128 / 256, n >= 256 (the visual-word search: k = 3, d = 256) runs in two stages -- an fp16-MFMA candidate pass whose
- * error bound is derived from the operands' norms (csrc/knn_cand.hip), then the exact fp32 chain on the candidates -- with outputs
- * bit-identical to the all-pairs exact-fp32 tile that serves every other case; rows the bound cannot cover (values beyond the fp16
- * range, more near-ties than a candidate list holds) are computed by exact brute force inside the second stage. */
+ * out_idx [m,k] int32, ascending, ties -> lowest index, (inf, -1) past the database size. */
 #define FP_KNN_SCRATCH_BYTES(m, n, k) \
   ((k) == 1 ? (size_t)(m) * 8 : ((k) <= 8 ? (size_t)(m) * ((size_t)(((n) + 127) / 128) * (k) * 8 > 704 ? (size_t)(((n) + 127) / 128) * (k) * 8 : 704) : (size_t)(m) * (n) * 4))
 int fp_knn_l2(const float* q, const float* q_sqnorm, int m, const float* db, const float* db_sqnorm, int n,
@@ -157,10 +148,8 @@ int fp_cosine_topk_prefiltered(const float* desc_n, const int32_t* det_seg_off, 
  *   tpl_ids [B*n_slots] template ids, <0 = empty slot: object-local (as fp_cosine_topk reports them) when tpl_base [B] = first
  *   template of each detection's object is given, GLOBAL ids when tpl_base is NULL
  *   feat_base [B]: first feature row of the detection's object (reported feature ids are object-local)
- *   scratch: FP_CYCLIC_SCRATCH_BYTES(B * n_slots, q_max, p_max) bytes (nearest-neighbour keys of both directions + the candidate
- *   lists of the two-stage search, or one slice of keys per 128 x 128 distance tile of the all-pairs form; nothing has to be preset)
- *   FP_EXPERIMENTS builds with FP_KNN_CAND=1 (see fp_knn_l2) and d = 64 / 128 / 256: the two 1-NN searches run as fp16-MFMA candidate pass + exact re-scoring
- *   (csrc/knn_cand.hip, same keys bit for bit); otherwise the all-pairs exact-fp32 tile
+ *   scratch: FP_CYCLIC_SCRATCH_BYTES(B * n_slots, q_max, p_max) bytes (nearest-neighbour keys of both directions, one slice of keys per
+ *   128 x 128 distance tile of the all-pairs exact-fp32 search; nothing has to be preset)
  * outputs, padded to k_max >= top_k per (detection, slot): count, query ids, object feature ids (= the
  * reference's nn_vertex_ids), cycle distances, confidences, coord_2d, coord_3d.  tie_mode as in fp_cosine_topk: 1 makes
  * the order (and the choice among tied distances at the top_k boundary) identical to the reference's
@@ -417,9 +406,8 @@ int fp_gemm_split(const void* A, int lda, const void* W, int ldw, int M, int N, 
                   void* out, int ldo, int epilogue, float acc_scale, float out_scale, fp_stream_t stream);
 /* Attention on split rows: qkv [B*N, 6D] halves (q | k | v, each 2D, split-fp16 rows of scale in_scale) -> out [B*N, 2D] halves (scale out_scale);
  * out_dtype FP_F16X3: a split-fp16 row, FP_F16F8: an f16f8 row (the f16f8 mode's proj operand); optionally OR-ed with FP_ATTN_VARIANT(v), test bits as in
- * fp_attention: 0 = the kernel the pipeline runs (the lock-step kernel), 1 = the lock-step kernel,
- * 2 = the role-split kernel (the two waves of a SIMD half a key tile apart; measured not faster, profiles/EXPERIMENTS.md section 0b: FP_EXPERIMENTS builds only, the shipped
- * library returns FP_ERR_UNSUPPORTED; in_scale >= 1).  All bit-identical. */
+ * fp_attention: 0 and 1 both run the lock-step kernel; 2 (the role-split kernel, removed after measuring not faster: profiles/EXPERIMENTS.md section 0b)
+ * returns FP_ERR_UNSUPPORTED.  in_scale >= 1. */
 int fp_attention_split(const void* qkv, int ld_qkv, void* out, int ld_out, int B, int n_tok, int dim, int heads, float in_scale, float out_scale,
                        int out_dtype, fp_stream_t stream);
 /* LayerNorm whose output carries a scale: out_dtype FP_FP8 (e4m3(y * out_scale) bytes), FP_F16X3 (split row of y * out_scale) or FP_F16F8 (f16f8 row) */
@@ -431,8 +419,8 @@ int fp_gemm_f32(const float* A, int lda, const float* W, int ldw, int M, int N, 
                 const float* gamma, float* out, int ldo, int epilogue, fp_stream_t stream);
 /* qkv [B*N, 3D] (q | k | v column blocks, head-major inside) -> out [B*N, D].
  * dtype: FP_F32 / FP_BF16 / FP_F16 (IEEE fp16 q | k | v and output: the "f16" mode's kernel, variant 0 only), optionally OR-ed with FP_ATTN_VARIANT(v) to pick a
- * bf16 work split (all bit-identical): 0 = 64 queries per wave, K/V by LDS-DMA (default), 1 = 32 queries per wave with register staging (the cross-check);
- * FP_EXPERIMENTS builds only (measured slower): 2 = the DMA kernel with 8 waves per 256-query block, 3 = 8 waves x 64 queries (512-query blocks), 4 = K prefetch.
+ * bf16 work split (bit-identical): 0 = 64 queries per wave, K/V by LDS-DMA (default), 1 = 32 queries per wave with register staging (the cross-check);
+ * any other value is FP_ERR_INVALID.
  * FP_F32: 0 = flash attention on the fp32 MFMA (default), 1 = one thread per query with one fma chain per score (its cross-check;
  * the two agree to fp32 rounding, not bit for bit). */
 #define FP_ATTN_VARIANT(v) ((v) << 8)

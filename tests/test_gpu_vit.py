@@ -129,8 +129,8 @@ def test_attention_bf16_lazy_rescale_staircase(step):
     """The exponent's reference moves only when a tile's maximum exceeds it by more than 8 (csrc/attn.hip, lazy rescale).  Keys whose
     scores climb by `step` (in the exponent, per 64-key tile) walk through every regime: never more than 8 above the reference for long
     stretches (p up to 2^8, no rescale), a rescale every few tiles, a rescale every tile; queries of different gain see different regimes
-    in one wave, so lanes that move and lanes that do not share the rescale branch.  The work splits (0 and its cross-check 1; 2 and 3 in FP_EXPERIMENTS
-    builds) stay bit-identical."""
+    in one wave, so lanes that move and lanes that do not share the rescale branch.  The work splits (0 and its cross-check 1) stay
+    bit-identical."""
     from foundpose_amd import ops
     N, D, heads = 64 * 9 + 17, 64, 1
     g = torch.Generator().manual_seed(int(step * 10))
@@ -142,8 +142,7 @@ def test_attention_bf16_lazy_rescale_staircase(step):
     q16 = qkv.to(torch.bfloat16)
     q, k, v = q16.double().reshape(1, N, 3, heads, 64).permute(2, 0, 3, 1, 4)
     ref = (torch.softmax(q @ k.transpose(-1, -2) * 0.125, -1) @ v).transpose(1, 2).reshape(N, D)
-    from tests.helpers import experiments_build
-    outs = [ops.attention(q16.cuda(), 1, N, D, heads, variant=v_).clone() for v_ in ((0, 1, 2, 3) if experiments_build() else (0, 1))]
+    outs = [ops.attention(q16.cuda(), 1, N, D, heads, variant=v_).clone() for v_ in (0, 1)]
     torch.cuda.synchronize()
     for o in outs[1:]:
         assert torch.equal(outs[0].view(torch.int16), o.view(torch.int16))
@@ -151,9 +150,10 @@ def test_attention_bf16_lazy_rescale_staircase(step):
 
 
 @pytest.mark.parametrize("B,N,heads", [(2, 77, 2), (1, 1374, 8), (3, 905, 2), (1, 256, 1), (2, 257, 4), (1, 321, 16)])
-def test_attention_bf16_work_splits_agree_bitwise(B, N, heads):
+def test_attention_bf16_variants_agree_bitwise_others_refused(B, N, heads):
     """The 64-queries-per-wave kernel (LDS-DMA staging) and the 32-queries-per-wave kernel issue the same MFMAs in the
-    same order for every query: their outputs must be bit-identical (ragged tails, idle waves, both block mappings)."""
+    same order for every query: their outputs must be bit-identical (ragged tails, idle waves, both block mappings).  Any other
+    variant is refused with FP_ERR_INVALID."""
     from foundpose_amd import ops
     D = heads * 64
     g = torch.Generator().manual_seed(N + heads)
@@ -161,14 +161,9 @@ def test_attention_bf16_work_splits_agree_bitwise(B, N, heads):
     o_a = ops.attention(q16, B, N, D, heads, variant=1).clone()   # 32 queries per wave, register staging
     o_b = ops.attention(q16, B, N, D, heads, variant=0).clone()   # the pipeline's kernel
     assert torch.equal(o_a.view(torch.int16), o_b.view(torch.int16))
-    from tests.helpers import experiments_build
-    if experiments_build():   # the measured-slower work splits of FP_EXPERIMENTS builds
-        o_c = ops.attention(q16, B, N, D, heads, variant=2)           # the DMA kernel with one 32-query block per wave, 8 waves per block
-        o_d = ops.attention(q16, B, N, D, heads, variant=3)           # 8 waves x 64 queries: 512-query blocks
-        assert torch.equal(o_a.view(torch.int16), o_d.view(torch.int16)) and torch.equal(o_a.view(torch.int16), o_c.view(torch.int16))
-    else:
-        with pytest.raises(_lib.FoundPoseNativeError, match="FP_EXPERIMENTS builds only"):
-            ops.attention(q16, B, N, D, heads, variant=2)
+    for v_ in (2, 3, 4):   # no other work split exists: FP_ERR_INVALID
+        with pytest.raises(_lib.FoundPoseNativeError, match=r"\(code 1\)"):
+            ops.attention(q16, B, N, D, heads, variant=v_)
 
 
 @pytest.mark.parametrize("precision,tol", [("fp32", 3e-5), ("f16x3", 3e-5), ("bf16", 3e-2)])

@@ -76,14 +76,14 @@ def main():
     if "attn" in what:
         qkv = (torch.randn(M, 3 * D, device=dev)).to(torch.bfloat16)
         for rep in range(2):
-            for variant in [int(v) for v in os.environ.get("BENCH_ATTN_VARIANTS", "0,3,2").split(",")]:
+            for variant in [int(v) for v in os.environ.get("BENCH_ATTN_VARIANTS", "0,1").split(",")]:
                 ms = timeit(lambda: ops.attention(qkv, B, N, D, H, variant=variant))
                 print(f"attn B={B} N={N} H={H} variant={variant}: {ms*1e3:8.1f} us  {4.0*B*N*N*D/ms/1e9:7.1f} TF/s", flush=True)
     if "attnsplit" in what:   # the f16x3 mode's attention (split-fp16 operands, three fp16 MFMAs per product)
         x = torch.randn(M, 3 * D, device=dev)
         packed = torch.cat([ops.split16_pack(x[:, i * D:(i + 1) * D].contiguous(), 16.0) for i in range(3)], dim=1)
         for rep in range(3):
-            for variant in (2, 1):   # 2 = the role-split kernel, 1 = the lock-step kernel
+            for variant in (1,):   # the lock-step kernel
                 ms = timeit(lambda: ops.attention_split(packed, B, N, D, H, 16.0, 16.0, variant=variant))
                 print(f"attn f16x3 B={B} N={N} H={H} variant={variant}: {ms*1e3:8.1f} us  {4.0*B*N*N*D/ms/1e9:7.1f} TF/s (fp32-product equivalent)", flush=True)
     if "attn32" in what:   # the exact-fp32 mode's attention: fp32 MFMA kernel (variant 0) vs the thread-per-query VALU kernel (variant 1)

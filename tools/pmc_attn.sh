@@ -1,6 +1,6 @@
 #!/bin/bash
 # Where the attention kernel's wave-cycles go: SQ wait / active / LDS-conflict counters (separate rocprofv3 --pmc passes, no trace domains)
-# over the kernel micro-benchmark, for the library in place and optionally a measurement variant (tools/attn_ablate.sh).
+# over the kernel micro-benchmark, for the library in place and optionally a measurement variant (tools/build_variant.sh).
 #   bash tools/pmc_attn.sh <tag> [variant.so ...]          (on the GPU box; writes gpurun_out/<tag>_pmc_attn.txt)
 tag=${1:-attn}; shift
 R=$GRAFT_REPO_ROOT

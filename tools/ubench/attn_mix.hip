@@ -1,4 +1,4 @@
-// What bounds the bf16 attention kernel at head_dim 64?  The kernel's own per-tile instruction stream (csrc/attn.hip, attn_bf16_w64_kernel<2>:
+// What bounds the bf16 attention kernel at head_dim 64?  The kernel's own per-tile instruction stream (csrc/attn.hip, attn_bf16_w64_kernel:
 // per wave and 64-key tile, two 32-query blocks: 16 score MFMAs + 16 P.V MFMAs, the fp32 online softmax, the bf16 packing) with everything
 // that touches memory removed -- operands are register values, no LDS, no DMA, no barrier -- at the kernel's occupancy (two waves per SIMD).
 //   mode 0  the 32 MFMAs alone                                  -> the matrix pipe's own pace under this dependency structure
@@ -10,7 +10,7 @@
 // no running maximum; row sum by v_dot2c over the packed probabilities) -- none of which is faster than the plain stream by more than 6 %.
 // Measured (MI355X, us per tile-round = one tile of each of the two waves of a SIMD; fraction of the 2.5 PFLOP/s dense bf16 peak):
 //   MFMAs alone 1.30 (0.66) | softmax alone 1.30 | real dataflow 1.84 (0.47) | launch shape 241 us (0.42) -- the same 240 us the real
-//   kernel takes with its DMA, barrier and LDS reads compiled out (tools/attn_ablate.sh).  The real kernel: 324 us (0.31).
+//   kernel takes with its DMA, barrier and LDS reads compiled out (a measurement build, profiles/EXPERIMENTS.md).  The real kernel: 324 us (0.31).
 // (The two 32-key halves of a tile must get different fragments: with one fragment the compiler merges them -- 24 MFMAs, half the softmax.)
 //   hipcc --offload-arch=gfx950 -O3 -mllvm -amdgpu-mfma-vgpr-form tools/ubench/attn_mix.hip -o tools/ubench/attn_mix && tools/ubench/attn_mix
 #include <hip/hip_runtime.h>
