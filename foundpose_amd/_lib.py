@@ -88,6 +88,7 @@ _PROTOS = {
     "fp_render_setup": [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "fp_render_raster": [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "fp_template_downsample": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+    "fp_pose_errors": [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp, vp],
 }
 
 _lib = None
@@ -148,6 +149,14 @@ def knn_scratch_bytes(m: int, n: int, k: int) -> int:
     if k <= 8:
         return m * max(((n + 127) // 128) * k * 8, 704)
     return m * n * 4
+
+
+POSE_ERR_TILE = 64 * 8  # FP_POSE_ERR_TILE of the header
+
+
+def pose_err_scratch_bytes(num_hyp: int, max_pts: int, max_syms: int) -> int:
+    """FP_POSE_ERR_SCRATCH_BYTES of include/foundpose_amd.h."""
+    return 32 * ((num_hyp + 7) // 8) * 8 + 24 * num_hyp * max_syms * ((max_pts + POSE_ERR_TILE - 1) // POSE_ERR_TILE)
 
 
 def exported_symbols():

@@ -1,9 +1,11 @@
 // C ABI of libfoundpose_amd.so (declared in include/foundpose_amd.h): argument checking, scratch carving
-// and kernel sequencing.  No allocation, no synchronisation, no global mutable state.
+// and kernel sequencing.  No device allocation, no global mutable state, no synchronisation except the table upload of
+// fp_pose_errors (which waits for its own copy).
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <vector>
 
 #include "../../include/foundpose_amd.h"
 #include "common.hpp"
@@ -490,6 +492,38 @@ int fp_template_downsample(const float* color, const float* depth, const uint8_t
   FP_REQUIRE(batch >= 1 && out_h >= 1 && out_w >= 1 && factor >= 1 && factor <= 16, "fp_template_downsample: bad shape");
   DownsampleArgs a{color, depth, mask, batch, out_h, out_w, factor, rgb, depth_u16, mask_out, boxes};
   return launch_template_downsample(a, ST(stream));
+}
+
+// ------------------------------------------------------------------ pose evaluation
+int fp_pose_errors(const double* pts, int total_pts, const double* est, const double* p_est, const double* gt_sym, const double* p_gt,
+                   int total_syms, const int32_t* ranges, int num_hyp, void* scratch, size_t scratch_bytes, double* err, int32_t* idx,
+                   fp_stream_t stream) {
+  FP_REQUIRE(pts && est && p_est && gt_sym && p_gt && ranges && scratch && err && idx, "fp_pose_errors: null pointer");
+  FP_REQUIRE(num_hyp >= 1 && num_hyp <= 65535, "fp_pose_errors: num_hyp %d outside [1, 65535]", num_hyp);
+  FP_REQUIRE(total_pts >= 1 && total_syms >= 1, "fp_pose_errors: empty vertex or symmetry array");
+  std::vector<PoseErrHyp> hyps(num_hyp);
+  long long parts = 0;
+  int max_tiles = 0, max_syms = 0;
+  for (int h = 0; h < num_hyp; ++h) {
+    const int32_t* r = ranges + 4 * (size_t)h;
+    FP_REQUIRE(r[1] >= 1 && r[3] >= 1, "fp_pose_errors: hypothesis %d has an empty vertex or symmetry range", h);
+    FP_REQUIRE(r[0] >= 0 && (long long)r[0] + r[1] <= total_pts, "fp_pose_errors: hypothesis %d: vertices [%d, +%d) outside [0, %d)", h, r[0], r[1], total_pts);
+    FP_REQUIRE(r[2] >= 0 && (long long)r[2] + r[3] <= total_syms, "fp_pose_errors: hypothesis %d: symmetries [%d, +%d) outside [0, %d)", h, r[2], r[3], total_syms);
+    const int tiles = (int)(((long long)r[1] + FP_POSE_ERR_TILE - 1) / FP_POSE_ERR_TILE);
+    hyps[h] = PoseErrHyp{r[0], r[1], r[2], r[3], tiles, 0, parts};
+    parts += (long long)tiles * r[3];
+    max_tiles = tiles > max_tiles ? tiles : max_tiles;
+    max_syms = r[3] > max_syms ? r[3] : max_syms;
+  }
+  const size_t table = 32 * (((size_t)num_hyp + 7) / 8) * 8;
+  FP_REQUIRE(scratch_bytes >= table + sizeof(PoseErrPart) * (size_t)parts, "fp_pose_errors: scratch holds %zu bytes, %zu needed", scratch_bytes,
+             table + sizeof(PoseErrPart) * (size_t)parts);
+  static_assert(sizeof(PoseErrHyp) == 32 && sizeof(PoseErrPart) == 24, "layout of FP_POSE_ERR_SCRATCH_BYTES");
+  // the one synchronous step of the library: the table lives in this frame, so the copy completes before it goes out of scope
+  HIP_TRY(hipMemcpyWithStream(scratch, hyps.data(), sizeof(PoseErrHyp) * (size_t)num_hyp, hipMemcpyHostToDevice, ST(stream)), "fp_pose_errors: table upload");
+  PoseErrArgs a{pts, est, p_est, gt_sym, p_gt, reinterpret_cast<const PoseErrHyp*>(scratch),
+                reinterpret_cast<PoseErrPart*>(static_cast<char*>(scratch) + table), err, idx};
+  return launch_pose_errors(a, num_hyp, max_tiles, max_syms, ST(stream));
 }
 
 // ------------------------------------------------------------------ ViT forward (launch sequence in C++)

@@ -254,6 +254,22 @@ int launch_cosine_topk_prefiltered(const CosineArgs& a, int num_det, int num_obj
 int launch_topn_rows(const float* sims, int ld, int rows, int max_len, const int* row_len, int n_top, float* out_scores,
                      int* out_ids, int tie_mode, hipStream_t st, const int* need_replay = nullptr);
 
+// ---------------------------------------------------------------- pose_eval.hip
+struct PoseErrHyp {        // one hypothesis, built on the host by fp_pose_errors
+  int pt_off, pt_cnt;      // vertex range in pts
+  int sym_off, sym_cnt;    // symmetry range in gt_sym / p_gt
+  int tiles, pad;          // ceil(pt_cnt / FP_POSE_ERR_TILE)
+  long long part_base;     // first partial of the hypothesis: partials [tiles, sym_cnt]
+};
+struct PoseErrPart { double sd, pd; int vsd, vpd; };  // per (hypothesis, tile, symmetry): max squared distances + first argmax
+struct PoseErrArgs {
+  const double* pts; const double* est; const double* p_est; const double* gt_sym; const double* p_gt;
+  const PoseErrHyp* hyps;  // [num_hyp] device copy
+  PoseErrPart* parts;
+  double* err; int* idx;
+};
+int launch_pose_errors(const PoseErrArgs& a, int num_hyp, int max_tiles, int max_syms, hipStream_t st);
+
 // ---------------------------------------------------------------- pnp.hip
 struct PnpArgs {
   const float* coord_2d;   // [pairs, k_max, 2] pixels

@@ -2,8 +2,9 @@
 reference's names and defaults, CNOS detections in, `estimated-poses.json` per object out.
 
 What differs from the reference loop, by design: the instances of an image go through the crop producer, the extractor,
-the matching and the PnP tail as ONE batch on the device (the reference handles them one at a time on the CPU), and the
-evaluation / rendering / visualisation branches (ground-truth errors, HTML) are not part of this path.
+the matching and the PnP tail as ONE batch on the device (the reference handles them one at a time on the CPU), the
+ground-truth evaluation (opt-in: eval_models / --eval-gt) is one fp_pose_errors launch per frame, and the rendering /
+visualisation branches (HTML) are not part of this path.
 
   python -m foundpose_amd.infer --opts configs/infer/lmo.json --dataset-dir <bop split dir> --detections <cnos json> \\
          --repre-dir <output>/object_repre --output-dir <output>/inference
@@ -70,9 +71,13 @@ def load_opts(path_or_dict) -> InferOpts:
 
 def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBasedObjectRepre, frames: Iterable[Dict[str, Any]],
                  detections: Dict[Any, Any], extractor=None, num_target_insts: Optional[Dict[Tuple[int, int], int]] = None,
-                 precision: str = "bf16", seed: int = 0, weights: Optional[str] = None) -> eval_util.PoseEvaluator:
+                 precision: str = "bf16", seed: int = 0, weights: Optional[str] = None,
+                 eval_model: Optional[eval_util.EvalModel] = None) -> eval_util.PoseEvaluator:
     """One object over a stream of frames (the body of infer.py's per-object loop).  A frame is
-    {"scene_id", "im_id", "image": HWC uint8 or float [0,1] (numpy or tensor), "camera": PinholePlaneCameraModel (c2w)}."""
+    {"scene_id", "im_id", "image": HWC uint8 or float [0,1] (numpy or tensor), "camera": PinholePlaneCameraModel (c2w)}.
+    eval_model (eval_util.load_eval_model): instances whose annotation carries a ground-truth `pose` (model -> world) are
+    evaluated against it (PoseEvaluator.update_batch, one launch per frame, inlier radius opts.pnp_inlier_thresh as in
+    infer.py:831); without it, or for annotations without a pose, the driver records what it always has."""
     if opts.match_template_type != "tfidf":
         raise ValueError(f"Unknown matching type '{opts.match_template_type}'.")
     if opts.match_feat_matching_type != "cyclic_buddies":
@@ -95,6 +100,9 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
     eng.record_stage_times = True
     evaluator = eval_util.PoseEvaluator()
     vertices = repre.vertices.cpu().numpy()
+
+    def annotated(inst):
+        return eval_model is not None and getattr(inst.get("gt_anno"), "pose", None) is not None
     for frame in frames:
         scene_id, im_id, cam = frame["scene_id"], frame["im_id"], frame["camera"]
         # number of target instances (infer.py:308-321): from the test targets when given -- frames that are not a target of
@@ -122,6 +130,10 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
         kept = []
         for inst_j, inst in enumerate(instances):
             evaluator.detection_times[(scene_id, im_id)] = inst.get("time", 0) if opts.use_detections else 0
+            # infer.py:770-777: a detection that hardly overlaps its ground-truth annotation is not evaluated (applied on the
+            # evaluation path only: the annotation-free entries stay what they were)
+            if opts.use_detections and annotated(inst) and infer_pose_util.mask_iou(inst["input_mask_modal"], inst["gt_anno"].masks_modal) < 0.05:
+                continue
             if inst["input_mask_modal"].sum() > cam.width * cam.height:  # infer.py:388-392
                 continue
             if inst["input_mask_modal"].sum() == 0:
@@ -172,32 +184,54 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
                  "feat_extract": (st.get("feat_extract", 0.0) + max(0.0, (t2 - t1) - dev_sum)) / n,
                  "grid_sample": st.get("grid_sample", 0.0) / n, "proj": st.get("proj", 0.0) / n, "corresp": st.get("corresp", 0.0) / n,
                  "pose_coarse": (t3 - t2) / n, "final_select": (t4 - t3) / n}
+        pending = []   # consecutive annotated hypotheses: evaluated in one launch, recorded in instance order
+
+        def flush():
+            if pending:
+                evaluator.update_batch(pending)
+                pending.clear()
         for b, (inst_j, inst) in enumerate(kept):
             if not found[b]:
                 continue
-            c = res.corresp_list(b)[cid[b]]
+            corr_all = res.corresp_list(b)
+            c = corr_all[cid[b]]
             corresp_np = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in c.items()}
             T_m2c = np.eye(4)
             T_m2c[:3, :3], T_m2c[:3, 3] = Rb[b], tb[b]
             T_m2w = cams[b].T_world_from_eye @ T_m2c  # infer.py:661-666
+            if annotated(inst):   # infer.py:806-835
+                bank_cams = repre.template_cameras_cam_from_model   # (a bank without template cameras: no template orientation error)
+                tpl_cams = [bank_cams[int(cc["template_id"])] for cc in corr_all] if len(bank_cams) else []
+                pending.append(dict(scene_id=scene_id, im_id=im_id, inst_id=inst_j, hypothesis_id=0, base_image=None, object_repre_vertices=vertices,
+                                    obj_lid=object_lid, object_pose_m2w=(T_m2w[:3, :3], T_m2w[:3, 3:]), object_pose_m2w_gt=inst["gt_anno"].pose,
+                                    orig_camera_c2w=cam, camera_c2w=cams[b], pred_mask=inst["input_mask_modal"], gt_mask=inst["gt_anno"].masks_modal,
+                                    corresp=corresp_np, retrieved_templates_camera_m2c=tpl_cams, time_per_inst=times,
+                                    object_mesh_vertices=eval_model.pts, object_syms=eval_model.syms, object_diameter=eval_model.diameter,
+                                    inlier_radius=opts.pnp_inlier_thresh))
+                continue
+            flush()
             evaluator.update_without_anno(scene_id, im_id, inst_j, 0, vertices, object_lid, T_m2w[:3, :3], T_m2w[:3, 3], cam, cams[b], times, corresp_np,
                                           inlier_radius=10)
+        flush()
     return evaluator
 
 
 def infer(opts: InferOpts, frames_by_object, detections, repres: Dict[int, repre_util.FeatureBasedObjectRepre], output_dir: str, extractor=None,
-          precision: str = "bf16", num_target_insts: Optional[Dict[int, Dict[Tuple[int, int], int]]] = None, weights: Optional[str] = None) -> List[str]:
+          precision: str = "bf16", num_target_insts: Optional[Dict[int, Dict[Tuple[int, int], int]]] = None, weights: Optional[str] = None,
+          eval_models: Optional[Dict[int, eval_util.EvalModel]] = None) -> List[str]:
     """All objects: `frames_by_object(lid)` yields the frames that show object `lid`; one estimated-poses.json per object
     under <output_dir>/<lid>/ (infer.py:813-816), then the BOP19 csv.
     num_target_insts: {object lid: {(scene_id, im_id): inst_count}} from test_targets_bop19.json -- the number of poses to
-    estimate per (image, object) is num_preds_factor x inst_count (infer.py:308-346); frames without an entry are skipped."""
+    estimate per (image, object) is num_preds_factor x inst_count (infer.py:308-346); frames without an entry are skipped.
+    eval_models: {object lid: eval_util.EvalModel} -- evaluate the hypotheses of frames whose annotations carry a pose."""
     lids = list(opts.object_lids) if opts.object_lids is not None else sorted(repres)
     if extractor is None:
         extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
     paths = []
     for lid in lids:
         ev = infer_object(opts, lid, repres[lid], frames_by_object(lid), detections, extractor,
-                          num_target_insts=None if num_target_insts is None else num_target_insts.get(lid, {}))
+                          num_target_insts=None if num_target_insts is None else num_target_insts.get(lid, {}),
+                          eval_model=None if eval_models is None else eval_models.get(lid))
         if opts.save_estimates:
             p = os.path.join(output_dir, str(lid), "estimated-poses.json")
             ev.save_results_json(p)
@@ -208,11 +242,51 @@ def infer(opts: InferOpts, frames_by_object, detections, repres: Dict[int, repre
 
 
 # ---------------------------------------------------------------------------------------------------- BOP split on disk
-def load_bop_frames(split_dir: str, targets: Sequence[Dict[str, int]], object_lid: int):
+class GtAnnotation(NamedTuple):
+    """structs.ObjectAnnotation, the fields data_util.prepare_sample fills (utils/data_util.py:105-151)."""
+    dataset: str
+    lid: int
+    pose: Any = None                # GtPose (model -> world) or None
+    masks_modal: Optional[np.ndarray] = None
+    boxes_amodal: Optional[np.ndarray] = None
+    visibilities: Optional[np.ndarray] = None
+
+
+class GtPose(NamedTuple):
+    R: np.ndarray   # 3x3
+    t: np.ndarray   # 3x1 (mm)
+
+
+def load_gt_annotations(scene_dir: str, im_id: int, camera, scene_gt: Dict[str, Any], scene_gt_info: Dict[str, Any], dataset: str = "") -> Optional[List[GtAnnotation]]:
+    """The annotations of one image as data_util.prepare_sample builds them: scene_gt.json (cam_R_m2c, cam_t_m2c, obj_id)
+    -> the m2w pose T_world_from_eye [R | t]; scene_gt_info.json bbox_obj (x, y, w, h) -> boxes_amodal (x1, y1, x2, y2),
+    visib_fract -> visibilities; mask_visib/<im>_<gt>.png / 255 -> masks_modal (uint8).  None when the image has none."""
+    from PIL import Image
+    gts = scene_gt.get(str(im_id), [])
+    if not len(gts) or not len(scene_gt_info):
+        return None
+    annos = []
+    for gt_id, gt in enumerate(gts):
+        info = scene_gt_info[str(im_id)][gt_id]
+        mask = np.asarray(Image.open(os.path.join(scene_dir, "mask_visib", f"{im_id:06d}_{gt_id:06d}.png"))) / 255.0
+        box = info["bbox_obj"]
+        T_m2c = np.eye(4)
+        T_m2c[:3, :3] = np.array(gt["cam_R_m2c"], np.float64).reshape(3, 3)
+        T_m2c[:3, 3] = np.array(gt["cam_t_m2c"], np.float64).reshape(3)
+        T_m2w = np.matmul(camera.T_world_from_eye, T_m2c)
+        annos.append(GtAnnotation(dataset=dataset, lid=int(gt["obj_id"]), pose=GtPose(T_m2w[:3, :3], T_m2w[:3, 3:]),
+                                  masks_modal=np.array(mask, dtype=np.uint8), boxes_amodal=np.array([box[0], box[1], box[0] + box[2], box[1] + box[3]]),
+                                  visibilities=np.asarray(info["visib_fract"])))
+    return annos
+
+
+def load_bop_frames(split_dir: str, targets: Sequence[Dict[str, int]], object_lid: int, with_gt: bool = False):
     """Frames of a BOP split that show `object_lid` according to test_targets_bop19.json entries
-    ({"scene_id", "im_id", "obj_id", "inst_count"}): <split>/<scene:06d>/rgb/<im:06d>.{png,jpg} + scene_camera.json (cam_K)."""
+    ({"scene_id", "im_id", "obj_id", "inst_count"}): <split>/<scene:06d>/rgb/<im:06d>.{png,jpg} + scene_camera.json (cam_K).
+    with_gt: each frame also carries "gt_annos" from scene_gt.json, scene_gt_info.json and mask_visib/ (load_gt_annotations)."""
     from PIL import Image
     cams: Dict[int, Dict[str, Any]] = {}
+    gts: Dict[int, Tuple[Dict[str, Any], Dict[str, Any]]] = {}
     for tgt in targets:
         if tgt["obj_id"] != object_lid:
             continue
@@ -226,7 +300,13 @@ def load_bop_frames(split_dir: str, targets: Sequence[Dict[str, int]], object_li
                                 os.path.join(sdir, "gray", f"{iid:06d}.tif")) if os.path.exists(p))
         image = np.asarray(Image.open(path).convert("RGB"))
         camera = crop_util.PinholePlaneCameraModel(image.shape[1], image.shape[0], (K[0, 0], K[1, 1]), (K[0, 2], K[1, 2]), np.eye(4))
-        yield {"scene_id": sid, "im_id": iid, "image": image, "camera": camera}
+        frame = {"scene_id": sid, "im_id": iid, "image": image, "camera": camera}
+        if with_gt:
+            if sid not in gts:
+                with open(os.path.join(sdir, "scene_gt.json")) as f, open(os.path.join(sdir, "scene_gt_info.json")) as g:
+                    gts[sid] = (json.load(f), json.load(g))
+            frame["gt_annos"] = load_gt_annotations(sdir, iid, camera, *gts[sid])
+        yield frame
 
 
 def main(argv: Optional[Sequence[str]] = None) -> None:
@@ -241,6 +321,9 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     ap.add_argument("--weights", default=None, help="DINOv2 checkpoint: a .pth with the upstream key names, or a directory holding the upstream file "
                     "(dinov2_vitl14_pretrain.pth, dinov2_vits14_reg4_pretrain.pth, ...); default $FOUNDPOSE_DINOV2_WEIGHTS, then the torch hub cache. "
                     "Without a checkpoint the run fails: there is no random-weight fallback")
+    ap.add_argument("--eval-gt", action="store_true", help="evaluate the poses against the split's ground truth (scene_gt.json, scene_gt_info.json, "
+                    "mask_visib/): MSSD, MSPD and the inlier counts go into estimated-poses.json")
+    ap.add_argument("--models-dir", default=None, help="with --eval-gt: models_info.json and obj_XXXXXX.ply (default: <dataset root>/models)")
     args = ap.parse_args(argv)
     opts = load_opts(args.opts)
     # the checkpoint is resolved before anything else is read: a missing one must fail in seconds, not after the banks are loaded
@@ -253,8 +336,14 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     n_inst: Dict[int, Dict[Tuple[int, int], int]] = {}
     for t in targets:
         n_inst.setdefault(t["obj_id"], {})[(t["scene_id"], t["im_id"])] = t["inst_count"]
-    out = infer(opts._replace(object_lids=list(lids)), lambda lid: load_bop_frames(args.dataset_dir, targets, lid), detections, repres, args.output_dir,
-                extractor=extractor.to("cuda"), precision=args.precision, num_target_insts=n_inst)
+    eval_models = None
+    if args.eval_gt:
+        models_dir = args.models_dir or os.path.join(os.path.dirname(os.path.abspath(args.dataset_dir)), "models")
+        with open(os.path.join(models_dir, "models_info.json")) as f:
+            models_info = json.load(f)
+        eval_models = {lid: eval_util.load_eval_model(models_dir, lid, opts.max_sym_disc_step, models_info) for lid in lids}
+    out = infer(opts._replace(object_lids=list(lids)), lambda lid: load_bop_frames(args.dataset_dir, targets, lid, with_gt=args.eval_gt), detections,
+                repres, args.output_dir, extractor=extractor.to("cuda"), precision=args.precision, num_target_insts=n_inst, eval_models=eval_models)
     print("\n".join(out))
 
 

@@ -340,3 +340,32 @@ def layernorm_split(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, o
     out = torch.empty(rows, 2 * D, dtype=torch.float16, device=x.device)
     call("fp_layernorm_scaled", ptr(x), x.stride(0), ptr(weight), ptr(bias), eps, ptr(out), 2 * D, _lib.FP_F16F8 if f16f8 else _lib.FP_F16X3, float(out_scale), D, rows, stream())
     return out
+
+
+def pose_errors(pts: torch.Tensor, est: torch.Tensor, p_est: torch.Tensor, gt_sym: torch.Tensor, p_gt: torch.Tensor,
+                ranges) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Symmetry-aware MSSD / MSPD of a ragged batch (fp_pose_errors): pts [V, 3], est / p_est [H, 12], gt_sym / p_gt [S, 12]
+    (fp64, on the device); ranges [H, 4] int (host) = (pt_off, pt_cnt, sym_off, sym_cnt) per hypothesis.
+    -> (err [H, 2] fp64 = (mssd, mspd), idx [H, 4] int32 = (mssd vertex, mssd symmetry, mspd vertex, mspd symmetry))."""
+    import numpy as np
+    require_cuda(pts, est, p_est, gt_sym, p_gt)
+    if isinstance(ranges, torch.Tensor):
+        if ranges.is_cuda:
+            raise ValueError("pose_errors: ranges is a host table (it is validated and sized on the host)")
+        ranges = ranges.numpy()
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 4))
+    if np.any(np.abs(r) > 2**31 - 1):
+        raise ValueError("pose_errors: range entries must fit int32")
+    r = r.astype(np.int32)
+    pts, est, p_est, gt_sym, p_gt = (t.to(torch.float64).contiguous() for t in (pts, est, p_est, gt_sym, p_gt))
+    h = r.shape[0]
+    if est.shape != (h, 12) or p_est.shape != (h, 12) or pts.dim() != 2 or pts.shape[1] != 3 or gt_sym.dim() != 2 or gt_sym.shape[1] != 12 \
+            or p_gt.shape != gt_sym.shape:
+        raise ValueError("pose_errors: shapes must be pts [V, 3], est / p_est [H, 12], gt_sym / p_gt [S, 12], ranges [H, 4]")
+    err = torch.empty(h, 2, dtype=torch.float64, device=pts.device)
+    idx = torch.empty(h, 4, dtype=torch.int32, device=pts.device)
+    nbytes = _lib.pose_err_scratch_bytes(h, int(r[:, 1].max()) if h else 0, int(r[:, 3].max()) if h else 0)
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=pts.device)
+    call("fp_pose_errors", ptr(pts), pts.shape[0], ptr(est), ptr(p_est), ptr(gt_sym), ptr(p_gt), gt_sym.shape[0],
+         r.ctypes.data_as(_lib.vp), h, ptr(scratch), nbytes, ptr(err), ptr(idx), stream())
+    return err, idx

@@ -17,6 +17,7 @@
 #ifndef FOUNDPOSE_AMD_H
 #define FOUNDPOSE_AMD_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -490,6 +491,31 @@ int fp_render_raster(const float* verts, const float* normals, const float* colo
 int fp_template_downsample(const float* color, const float* depth, const uint8_t* mask, int batch, int out_h, int out_w,
                            int factor, uint8_t* rgb, uint16_t* depth_u16, uint8_t* mask_out, int32_t* boxes,
                            fp_stream_t stream);
+
+/* ---- pose evaluation (utils/eval_errors.py:12-68) -----------------------------------------------
+ * Symmetry-aware BOP pose errors of num_hyp hypotheses, fp64 in and out.  Hypothesis h uses the vertices
+ * pts[pt_off .. pt_off + pt_cnt) and the symmetries [sym_off .. sym_off + sym_cnt) given by ranges[h] = (pt_off, pt_cnt,
+ * sym_off, sym_cnt) -- HOST memory, int32 [num_hyp, 4]: the call validates every range and copies a derived table into
+ * scratch on `stream`, waiting for that copy (and so for the work queued before it) before it returns.  Device arrays:
+ *   pts     [total_pts, 3]    model vertices (mm), objects concatenated
+ *   est     [num_hyp, 12]     R_est (row-major) | t_est, model -> camera
+ *   p_est   [num_hyp, 12]     K [R_est | t_est], row-major 3x4
+ *   gt_sym  [total_syms, 12]  R_gt S_R | R_gt S_t + t_gt  (composed by the caller)
+ *   p_gt    [total_syms, 12]  K [R_gt_sym | t_gt_sym]
+ *   err     [num_hyp, 2]      (mssd, mspd) = min over symmetries of the max over vertices of the 3D / projected distance
+ *   idx     [num_hyp, 4]      (mssd vertex, mssd symmetry, mspd vertex, mspd symmetry), relative to the hypothesis' ranges
+ * The vertex maximum compares squared distances (one sqrt per symmetry: same value, see csrc/pose_eval.hip); ties go to
+ * the lowest vertex / symmetry, NaN as numpy's max / argmax and np.argmin, the value across symmetries as Python's min().
+ * Results are bit-identical across runs and batch compositions.  scratch: at least
+ * FP_POSE_ERR_SCRATCH_BYTES(num_hyp, max pt_cnt, max sym_cnt) bytes (scratch_bytes says how many there are).
+ * num_hyp < 1, a count < 1, a range outside [0, total), a NULL pointer or too little scratch: FP_ERR_INVALID, nothing written. */
+#define FP_POSE_ERR_VERTS_PER_LANE 8
+#define FP_POSE_ERR_TILE (64 * FP_POSE_ERR_VERTS_PER_LANE)
+#define FP_POSE_ERR_SCRATCH_BYTES(num_hyp, max_pts, max_syms) \
+  (32 * (((size_t)(num_hyp) + 7) / 8) * 8 + 24 * (size_t)(num_hyp) * (size_t)(max_syms) * (((size_t)(max_pts) + FP_POSE_ERR_TILE - 1) / FP_POSE_ERR_TILE))
+int fp_pose_errors(const double* pts, int total_pts, const double* est, const double* p_est, const double* gt_sym, const double* p_gt,
+                   int total_syms, const int32_t* ranges, int num_hyp, void* scratch, size_t scratch_bytes, double* err, int32_t* idx,
+                   fp_stream_t stream);
 
 #ifdef __cplusplus
 }
