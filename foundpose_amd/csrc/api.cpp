@@ -1,6 +1,6 @@
 // C ABI of libfoundpose_amd.so (declared in include/foundpose_amd.h): argument checking, scratch carving
-// and kernel sequencing.  No device allocation, no global mutable state, no synchronisation except the table upload of
-// fp_pose_errors (which waits for its own copy).
+// and kernel sequencing.  No device allocation, no global mutable state, no synchronisation except the table uploads of
+// fp_pose_errors and fp_vsd_counts (each waits for its own copy).
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -524,6 +524,59 @@ int fp_pose_errors(const double* pts, int total_pts, const double* est, const do
   PoseErrArgs a{pts, est, p_est, gt_sym, p_gt, reinterpret_cast<const PoseErrHyp*>(scratch),
                 reinterpret_cast<PoseErrPart*>(static_cast<char*>(scratch) + table), err, idx};
   return launch_pose_errors(a, num_hyp, max_tiles, max_syms, ST(stream));
+}
+
+// ------------------------------------------------------------------ VSD
+int fp_vsd_counts(const float* depth_test, int num_test, const float* depth_est, int num_est, const float* depth_gt, int num_gt,
+                  int height, int width, const int32_t* pairs, const double* params, int num_pairs, const double* taus,
+                  int num_taus, void* scratch, size_t scratch_bytes, int64_t* counts, fp_stream_t stream) {
+  FP_REQUIRE(depth_test && depth_est && depth_gt && pairs && params && taus && scratch && counts, "fp_vsd_counts: null pointer");
+  FP_REQUIRE(num_pairs >= 1, "fp_vsd_counts: num_pairs %d < 1", num_pairs);
+  FP_REQUIRE(num_taus >= 1 && num_taus <= FP_VSD_MAX_TAUS, "fp_vsd_counts: num_taus %d outside [1, %d]", num_taus, FP_VSD_MAX_TAUS);
+  FP_REQUIRE(height >= 1 && width >= 1 && num_test >= 1 && num_est >= 1 && num_gt >= 1,
+             "fp_vsd_counts: empty image size or stack (%d x %d; %d, %d, %d images)", height, width, num_test, num_est, num_gt);
+  FP_REQUIRE(scratch_bytes >= FP_VSD_SCRATCH_BYTES(num_pairs), "fp_vsd_counts: scratch holds %zu bytes, %zu needed", scratch_bytes,
+             FP_VSD_SCRATCH_BYTES(num_pairs));
+  VsdArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int t = 0; t < num_taus; ++t) {
+    FP_REQUIRE(taus[t] == taus[t], "fp_vsd_counts: tau %d is NaN", t);
+    a.taus[t] = taus[t];
+  }
+  static_assert(sizeof(VsdPair) == 96, "layout of FP_VSD_SCRATCH_BYTES");
+  std::vector<VsdPair> tab(num_pairs);
+  const long long img = (long long)height * width;
+  long long blocks = 0;
+  for (int p = 0; p < num_pairs; ++p) {
+    const int32_t* r = pairs + 7 * (size_t)p;
+    const double* q = params + 6 * (size_t)p;
+    FP_REQUIRE(r[0] >= 0 && r[0] < num_test && r[1] >= 0 && r[1] < num_est && r[2] >= 0 && r[2] < num_gt,
+               "fp_vsd_counts: pair %d: indices (%d, %d, %d) outside (%d, %d, %d)", p, r[0], r[1], r[2], num_test, num_est, num_gt);
+    FP_REQUIRE(r[3] >= 0 && r[4] >= 0 && r[3] <= r[5] + 1 && r[4] <= r[6] + 1 && r[5] < width && r[6] < height,
+               "fp_vsd_counts: pair %d: box (%d, %d, %d, %d) outside the %d x %d image", p, r[3], r[4], r[5], r[6], width, height);
+    FP_REQUIRE(q[0] > 0 && q[1] > 0 && q[5] > 0, "fp_vsd_counts: pair %d: fx, fy and the diameter must be > 0", p);
+    FP_REQUIRE(q[4] == q[4], "fp_vsd_counts: pair %d: delta is NaN", p);
+    VsdPair& v = tab[p];
+    v.test_off = r[0] * img, v.est_off = r[1] * img, v.gt_off = r[2] * img;
+    v.x0 = r[3], v.y0 = r[4];
+    v.bw = r[5] - r[3] + 1, v.bh = r[6] - r[4] + 1;
+    if (v.bw == 0 || v.bh == 0) v.bw = v.bh = 0;
+    v.blk0 = blocks;
+    v.fx = q[0], v.fy = q[1], v.cx = q[2], v.cy = q[3], v.diameter = q[5];
+    v.delta = (float)q[4];
+    v.pad = 0;
+    blocks += ((long long)v.bw * v.bh + FP_VSD_BLOCK_PIXELS - 1) / FP_VSD_BLOCK_PIXELS;
+  }
+  FP_REQUIRE(blocks <= 0x7fffffffll, "fp_vsd_counts: %lld workgroups exceed the grid", blocks);
+  HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * (size_t)num_pairs * (2 + num_taus), ST(stream)), "fp_vsd_counts: zeroing");
+  if (blocks == 0) return FP_OK;
+  // the table lives in this frame, so the copy completes before it goes out of scope
+  HIP_TRY(hipMemcpyWithStream(scratch, tab.data(), sizeof(VsdPair) * (size_t)num_pairs, hipMemcpyHostToDevice, ST(stream)), "fp_vsd_counts: table upload");
+  a.depth_test = depth_test, a.depth_est = depth_est, a.depth_gt = depth_gt;
+  a.pairs = reinterpret_cast<const VsdPair*>(scratch);
+  a.num_pairs = num_pairs, a.width = width, a.num_taus = num_taus;
+  a.counts = reinterpret_cast<long long*>(counts);
+  return launch_vsd_counts(a, blocks, ST(stream));
 }
 
 // ------------------------------------------------------------------ ViT forward (launch sequence in C++)

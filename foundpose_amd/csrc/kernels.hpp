@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/foundpose_amd.h"
+
 // ---------------------------------------------------------------- f32_tile.hip
 enum : int {
   F32_EPI_STORE = 0,        // out = acc
@@ -269,6 +271,24 @@ struct PoseErrArgs {
   double* err; int* idx;
 };
 int launch_pose_errors(const PoseErrArgs& a, int num_hyp, int max_tiles, int max_syms, hipStream_t st);
+
+// ---------------------------------------------------------------- vsd.hip
+struct VsdPair {                         // one (estimate, GT) pair, built on the host by fp_vsd_counts
+  long long test_off, est_off, gt_off;   // element offsets of the three depth images (index * height * width)
+  int x0, y0, bw, bh;                    // the box scanned: bw x bh pixels from (x0, y0); 0 x 0 when empty
+  long long blk0;                        // first workgroup of the pair: ceil(bw * bh / FP_VSD_BLOCK_PIXELS) of them
+  double fx, fy, cx, cy, diameter;
+  float delta;                           // (float)delta: numpy compares the fp32 difference in fp32
+  int pad;
+};
+struct VsdArgs {
+  const float* depth_test; const float* depth_est; const float* depth_gt;
+  const VsdPair* pairs;                  // [num_pairs] device copy
+  int num_pairs, width, num_taus, pad;
+  double taus[FP_VSD_MAX_TAUS];
+  long long* counts;                     // [num_pairs, 2 + num_taus], zeroed by the host on the stream
+};
+int launch_vsd_counts(const VsdArgs& a, long long num_blocks, hipStream_t st);
 
 // ---------------------------------------------------------------- pnp.hip
 struct PnpArgs {

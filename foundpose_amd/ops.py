@@ -369,3 +369,35 @@ def pose_errors(pts: torch.Tensor, est: torch.Tensor, p_est: torch.Tensor, gt_sy
     call("fp_pose_errors", ptr(pts), pts.shape[0], ptr(est), ptr(p_est), ptr(gt_sym), ptr(p_gt), gt_sym.shape[0],
          r.ctypes.data_as(_lib.vp), h, ptr(scratch), nbytes, ptr(err), ptr(idx), stream())
     return err, idx
+
+
+def vsd_counts(depth_test: torch.Tensor, depth_est: torch.Tensor, depth_gt: torch.Tensor, pairs, params, taus) -> torch.Tensor:
+    """VSD counts of a batch of (estimate, GT) pairs (fp_vsd_counts): depth_test [N_test, H, W], depth_est [N_est, H, W],
+    depth_gt [N_gt, H, W] fp32 mm (on the device); pairs [P, 7] int (host) = (test, est, gt, x0, y0, x1, y1) with the inclusive
+    box of the two renders (x1 = x0 - 1: empty); params [P, 6] (host) = (fx, fy, cx, cy, delta, diameter); taus [T] (host).
+    -> counts [P, 2 + T] int64 = (|union|, |intersection|, intersection pixels with dist >= tau for each tau)."""
+    import numpy as np
+    require_cuda(depth_test, depth_est, depth_gt)
+    host = []
+    for name, a in (("pairs", pairs), ("params", params), ("taus", taus)):
+        if isinstance(a, torch.Tensor):
+            if a.is_cuda:
+                raise ValueError(f"vsd_counts: {name} is a host table (it is validated on the host)")
+            a = a.numpy()
+        host.append(a)
+    p = np.asarray(host[0], dtype=np.int64).reshape(-1, 7)
+    if np.any(np.abs(p) > 2**31 - 1):
+        raise ValueError("vsd_counts: pair entries must fit int32")
+    p = np.ascontiguousarray(p, np.int32)
+    q = np.ascontiguousarray(np.asarray(host[1], dtype=np.float64).reshape(-1, 6))
+    t = np.ascontiguousarray(np.asarray(host[2], dtype=np.float64).reshape(-1))
+    dt, de, dg = (x.to(torch.float32).contiguous() for x in (depth_test, depth_est, depth_gt))
+    if dt.dim() != 3 or de.dim() != 3 or dg.dim() != 3 or not (dt.shape[1:] == de.shape[1:] == dg.shape[1:]) or q.shape[0] != p.shape[0]:
+        raise ValueError("vsd_counts: shapes must be depth_test / depth_est / depth_gt [N, H, W] of one H x W, pairs [P, 7], params [P, 6]")
+    n = p.shape[0]
+    counts = torch.empty(max(n, 1), 2 + len(t), dtype=torch.int64, device=dt.device)[:n]
+    scratch = torch.empty(max(_lib.vsd_scratch_bytes(n), 1), dtype=torch.uint8, device=dt.device)
+    call("fp_vsd_counts", ptr(dt), dt.shape[0], ptr(de), de.shape[0], ptr(dg), dg.shape[0], dt.shape[1], dt.shape[2],
+         p.ctypes.data_as(_lib.vp), q.ctypes.data_as(_lib.vp), n, t.ctypes.data_as(_lib.vp), len(t), ptr(scratch),
+         _lib.vsd_scratch_bytes(n), ptr(counts), stream())
+    return counts

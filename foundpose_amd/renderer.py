@@ -58,9 +58,10 @@ def vertex_normals(vertices: np.ndarray, faces: np.ndarray) -> np.ndarray:
     return np.where(ln > 0, n / np.where(ln > 0, ln, 1.0), 0.0).astype(np.float32)
 
 
-def load_ply(path: str) -> Mesh:
+def load_ply(path: str, geometry_only: bool = False) -> Mesh:
     """BOP model PLY: ascii or binary_little_endian; x, y, z float / double; optional nx, ny, nz; red, green, blue[, alpha]
-    uchar; faces as `vertex_indices` lists, fanned into triangles.  Textured models raise NotImplementedError."""
+    uchar; faces as `vertex_indices` lists, fanned into triangles.  Textured models raise NotImplementedError, unless
+    `geometry_only` (depth-only uses such as VSD): then the texture is ignored and the colours are the fallback grey."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.find(b"end_header")
@@ -75,7 +76,7 @@ def load_ply(path: str) -> Mesh:
             continue
         if tok[0] == "format":
             fmt = tok[1]
-        elif tok[0] == "comment" and len(tok) > 1 and tok[1].lower() == "texturefile":
+        elif tok[0] == "comment" and len(tok) > 1 and tok[1].lower() == "texturefile" and not geometry_only:
             raise NotImplementedError("textured PLY models are not supported (vertex colours only)")
         elif tok[0] == "element":
             elements.append((tok[1], int(tok[2]), []))
@@ -88,7 +89,7 @@ def load_ply(path: str) -> Mesh:
         raise NotImplementedError(f"PLY format {fmt}")
     for name, _, props in elements:
         names = {p[0] for p in props}
-        if names & {"texture_u", "texture_v", "texcoord"}:
+        if names & {"texture_u", "texture_v", "texcoord"} and not geometry_only:
             raise NotImplementedError("textured PLY models are not supported (vertex colours only)")
     vert, faces = None, None
     pos = 0

@@ -196,3 +196,95 @@ def make_blob_mesh(num_lat: int = 50, num_lon: int = 50, radius: float = 60.0, s
     col = np.rint(np.clip(col, 0, 1) * 255.0).astype(np.float32) / np.float32(255.0)
     v = v.astype(np.float32)
     return Mesh(vertices=v, faces=faces, colors=col.astype(np.float32), normals=vertex_normals(v, faces))
+
+
+def make_bop_eval_scene(root: str, num_images: int = 4, num_objects: int = 2, width: int = 320, height: int = 240,
+                        mesh_res: int = 40, gts_per_image: int = 2, depth_scale: float = 0.1, seed: int = 0,
+                        device: str = "cuda"):
+    """A BOP split for evaluation, generated from a seed on the GPU: <root>/synth/{models/, test/000001/, test_targets_bop19.json}.
+    Objects are make_blob_mesh(mesh_res, mesh_res) blobs (about 2 mesh_res^2 triangles); every image shows gts_per_image
+    distinct objects, one instance each.  The test depth is the GT renders composited over a background plane at 1500 mm,
+    with a 40 mm occluder in front of the first instance and a hole (no measurement), stored as uint16 PNG in depth_scale
+    units.  -> dict: split_dir, models_dir, K, width, height, diameters, images [(im_id, [(obj_id, 4x4 m2c)])]."""
+    import json
+    import os
+
+    import numpy as np
+    from PIL import Image
+
+    from .renderer import HipRasterizer, save_ply
+    from .eval_bop19 import _Camera
+    rng = np.random.default_rng(seed)
+    ds = os.path.join(root, "synth")
+    split, models = os.path.join(ds, "test"), os.path.join(ds, "models")
+    sdir = os.path.join(split, "000001")
+    os.makedirs(os.path.join(sdir, "depth"), exist_ok=True)
+    os.makedirs(models, exist_ok=True)
+    ras = HipRasterizer(device)
+    diam, info = {}, {}
+    for lid in range(1, num_objects + 1):
+        m = make_blob_mesh(mesh_res, mesh_res, radius=float(rng.uniform(35, 55)), seed=seed * 100 + lid)
+        save_ply(os.path.join(models, f"obj_{lid:06d}.ply"), m)
+        diam[lid] = float(2.0 * np.linalg.norm(m.vertices.astype(np.float64), axis=1).max())
+        info[str(lid)] = {"diameter": diam[lid]}
+        ras.add_object_model(lid, mesh=m)
+    with open(os.path.join(models, "models_info.json"), "w") as f:
+        json.dump(info, f)
+    K = np.array([[572.4, 0.0, width / 2 + 5.3], [0.0, 573.6, height / 2 + 2.0], [0.0, 0.0, 1.0]])
+    images, cams, gts, infos, targets = [], {}, {}, {}, []
+    for im in range(num_images):
+        objs = rng.choice(np.arange(1, num_objects + 1), size=min(gts_per_image, num_objects), replace=False)
+        inst = []
+        for lid in objs:
+            a = rng.normal(size=3)
+            a /= np.linalg.norm(a)
+            ang = rng.uniform(-np.pi, np.pi)
+            Kx = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+            T = np.eye(4)
+            T[:3, :3] = np.eye(3) + np.sin(ang) * Kx + (1 - np.cos(ang)) * Kx @ Kx
+            z = rng.uniform(700, 1100)
+            T[:3, 3] = [rng.uniform(-0.3, 0.3) * z * width / K[0, 0], rng.uniform(-0.3, 0.3) * z * height / K[1, 1], z]
+            inst.append((int(lid), T))
+        renders = [ras.render_views(lid, [_Camera(K, width, height, np.linalg.inv(T))], with_color=False)["depth"][0].cpu().numpy()
+                   for lid, T in inst]
+        depth = np.full((height, width), 1500.0, np.float32)
+        for r in renders:
+            depth = np.where((r > 0) & (r < depth), r, depth)
+        m0 = renders[0] > 0
+        if m0.any():   # an occluder 40 mm in front of a strip of the first instance
+            ys, xs = np.nonzero(m0)
+            y0, x0 = int(np.median(ys)), int(np.median(xs))
+            depth[y0:y0 + 12, :x0] = np.where(m0[y0:y0 + 12, :x0], renders[0][y0:y0 + 12, :x0] - 40.0, depth[y0:y0 + 12, :x0])
+        hy, hx = int(rng.integers(0, height - 20)), int(rng.integers(0, width - 20))
+        depth[hy:hy + 20, hx:hx + 20] = 0.0
+        u16 = np.clip(np.rint(depth / depth_scale), 0, 65535).astype(np.uint16)
+        Image.fromarray(u16).save(os.path.join(sdir, "depth", f"{im:06d}.png"))
+        stored = u16.astype(np.float32) * np.float32(depth_scale)
+        cams[str(im)] = {"cam_K": K.ravel().tolist(), "depth_scale": depth_scale}
+        gts[str(im)] = [{"cam_R_m2c": T[:3, :3].ravel().tolist(), "cam_t_m2c": T[:3, 3].tolist(), "obj_id": lid} for lid, T in inst]
+        vis = []
+        for r in renders:
+            m = r > 0
+            vis.append(float(np.sum(m & ((np.abs(r - stored) <= 15.0) | (stored == 0))) / max(int(m.sum()), 1)))
+        infos[str(im)] = [{"visib_fract": v} for v in vis]
+        targets += [{"scene_id": 1, "im_id": im, "obj_id": lid, "inst_count": 1} for lid, _ in inst]
+        images.append((im, inst))
+    for name, obj in (("scene_camera.json", cams), ("scene_gt.json", gts), ("scene_gt_info.json", infos)):
+        with open(os.path.join(sdir, name), "w") as f:
+            json.dump(obj, f)
+    with open(os.path.join(ds, "test_targets_bop19.json"), "w") as f:
+        json.dump(targets, f)
+    return {"split_dir": split, "models_dir": models, "K": K, "width": width, "height": height, "diameters": diam, "images": images,
+            "targets": targets}
+
+
+def write_bop_results_csv(path: str, estimates) -> None:
+    """estimates: [(scene_id, im_id, obj_id, score, 4x4 m2c, time)] -> the BOP19 csv in eval_util.prepare_bop_submission's format."""
+    import numpy as np
+    lines = ["scene_id,im_id,obj_id,score,R,t,time"]
+    for s, im, lid, score, T, tm in estimates:
+        T = np.asarray(T, np.float64)
+        lines.append("{},{},{},{},{},{},{}".format(s, im, lid, score, " ".join(map(str, T[:3, :3].ravel().tolist())),
+                                                   " ".join(map(str, T[:3, 3].tolist())), tm))
+    with open(path, "w") as f:
+        f.write("\n".join(lines))

@@ -517,6 +517,36 @@ int fp_pose_errors(const double* pts, int total_pts, const double* est, const do
                    int total_syms, const int32_t* ranges, int num_hyp, void* scratch, size_t scratch_bytes, double* err, int32_t* idx,
                    fp_stream_t stream);
 
+/* ---- VSD (bop_toolkit_lib pose_error.vsd, `bop19` visibility, `step` cost) ----------------------
+ * Counts for the Visible Surface Discrepancy of num_pairs (estimate, GT) pairs.  Device arrays:
+ *   depth_test [num_test, height, width]  fp32 mm, 0 = no measurement (the test images)
+ *   depth_est  [num_est, height, width]   fp32 mm, 0 = background (renders of the estimates)
+ *   depth_gt   [num_gt, height, width]    fp32 mm, 0 = background (renders of the GT instances)
+ *   counts     [num_pairs, 2 + num_taus]  int64: |union|, |intersection|, then per tau the intersection pixels with
+ *                                         dist >= tau.  The call zeroes it on `stream`.
+ * HOST arrays (validated, then copied into scratch on `stream`; the call waits for that copy, as fp_pose_errors does):
+ *   pairs  int32 [num_pairs, 7]  (test index, est index, gt index, x0, y0, x1, y1): the inclusive pixel box scanned, the
+ *                                union of the two renders' boxes (x1 = x0 - 1 or y1 = y0 - 1: empty).  Every pixel outside it
+ *                                must have depth_est = depth_gt = 0.
+ *   params fp64 [num_pairs, 6]   (fx, fy, cx, cy, delta mm, diameter mm)
+ *   taus   fp64 [num_taus]       1 <= num_taus <= FP_VSD_MAX_TAUS
+ * Per pixel, fp64, every operation rounded on its own (no contraction, IEEE division, correctly rounded sqrt):
+ *   xs = (col - cx) / fx, ys = (row - cy) / fy  (integer pixel indices); dist = sqrt(((xs d)^2 + (ys d)^2) + d^2) for the
+ *   fp32 depth d of each image; visib(m) = ((float)dist_m - (float)dist_test <= (float)delta || dist_test == 0) && dist_m > 0
+ *   with the difference in fp32; visib_gt = visib(gt); visib_est = visib(est) || (visib_gt && dist_est > 0); on the
+ *   intersection e = |dist_gt - dist_est| / diameter, counted for each tau with e >= tau.
+ * The VSD error for tau is (count_tau + (|union| - |inter|)) / |union|, and 1 for every tau when |union| = 0 (host side).
+ * Results are bit-identical across runs and batch compositions (integer sums).  scratch: FP_VSD_SCRATCH_BYTES(num_pairs).
+ * num_pairs < 1, num_taus outside [1, FP_VSD_MAX_TAUS], a NaN tau or delta, height / width / image counts < 1, an index
+ * outside its stack, a box outside the image, fx, fy or diameter not > 0, a NULL pointer or too little scratch:
+ * FP_ERR_INVALID, nothing written. */
+#define FP_VSD_MAX_TAUS 16
+#define FP_VSD_BLOCK_PIXELS 1024
+#define FP_VSD_SCRATCH_BYTES(num_pairs) (96 * (size_t)(num_pairs))
+int fp_vsd_counts(const float* depth_test, int num_test, const float* depth_est, int num_est, const float* depth_gt, int num_gt,
+                  int height, int width, const int32_t* pairs, const double* params, int num_pairs, const double* taus,
+                  int num_taus, void* scratch, size_t scratch_bytes, int64_t* counts, fp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
