@@ -87,6 +87,9 @@ _PROTOS = {
     "fp_warp_depth": [vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp],
     "fp_render_setup": [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "fp_render_raster": [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "fp_texture_mips": [vp, i32, i32, vp, vp],
+    "fp_render_raster_textured": [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                  i32, i32, vp, vp],
     "fp_template_downsample": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
     "fp_pose_errors": [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp, vp],
     "fp_vsd_counts": [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp],
@@ -166,6 +169,20 @@ VSD_MAX_TAUS = 16  # FP_VSD_MAX_TAUS of the header
 def vsd_scratch_bytes(num_pairs: int) -> int:
     """FP_VSD_SCRATCH_BYTES of include/foundpose_amd.h."""
     return 96 * num_pairs
+
+
+TEXTURE_MAX_SIDE = 16384  # FP_TEXTURE_MAX_SIDE of the header
+
+
+def texture_levels(width: int, height: int):
+    """The pyramid layout of fp_texture_mips (include/foundpose_amd.h): [(texel offset, w, h)] per level, and the total."""
+    out, off, w, h = [], 0, int(width), int(height)
+    while True:
+        out.append((off, w, h))
+        off += w * h
+        if w == 1 and h == 1:
+            return out, off
+        w, h = max(1, w >> 1), max(1, h >> 1)
 
 
 def exported_symbols():

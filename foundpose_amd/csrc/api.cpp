@@ -485,6 +485,52 @@ int fp_render_raster(const float* verts, const float* normals, const float* colo
   return launch_render_raster(a, ST(stream));
 }
 
+// the level table of a pyramid (layout of include/foundpose_amd.h); sides already validated
+static void texture_levels(int width, int height, TexArgs* t) {
+  int w = width, h = height, off = 0, l = 0;
+  for (;; ++l) {
+    t->off[l] = off, t->w[l] = w, t->h[l] = h;
+    off += w * h;
+    if (w == 1 && h == 1) break;
+    w = w > 1 ? w >> 1 : 1, h = h > 1 ? h >> 1 : 1;
+  }
+  t->levels = l + 1;
+}
+
+int fp_texture_mips(const uint8_t* rgb, int width, int height, uint32_t* pyramid, fp_stream_t stream) {
+  FP_REQUIRE(rgb && pyramid, "fp_texture_mips: null pointer");
+  FP_REQUIRE(width >= 1 && height >= 1 && width <= FP_TEXTURE_MAX_SIDE && height <= FP_TEXTURE_MAX_SIDE,
+             "fp_texture_mips: texture %d x %d outside [1, %d]", width, height, FP_TEXTURE_MAX_SIDE);
+  TexArgs t;
+  memset(&t, 0, sizeof(t));
+  texture_levels(width, height, &t);
+  return launch_texture_mips(rgb, t, pyramid, ST(stream));
+}
+
+int fp_render_raster_textured(const float* verts, const float* normals, const float* colors, int num_verts, const int32_t* faces,
+                              int num_faces, const double* cams, int batch, int width, int height, void* vert_ws, void* tri_ws,
+                              int32_t* tile_counts, int64_t* tile_offsets, int32_t* lists, int64_t* status, float* color,
+                              float* depth, uint8_t* mask, int32_t* tri_id, int32_t* boxes, const float* uv,
+                              const uint32_t* pyramid, int tex_width, int tex_height, const float* material, fp_stream_t stream) {
+  RenderArgs a;
+  TRY(render_args(verts, normals, colors, num_verts, faces, num_faces, cams, batch, width, height, vert_ws, tri_ws,
+                  tile_counts, tile_offsets, lists, status, color, depth, mask, tri_id, boxes, &a));
+  FP_REQUIRE(lists && depth && mask && uv && pyramid && material, "fp_render_raster_textured: null pointer");
+  FP_REQUIRE(tex_width >= 1 && tex_height >= 1 && tex_width <= FP_TEXTURE_MAX_SIDE && tex_height <= FP_TEXTURE_MAX_SIDE,
+             "fp_render_raster_textured: texture %d x %d outside [1, %d]", tex_width, tex_height, FP_TEXTURE_MAX_SIDE);
+  for (int k = 0; k < 6; ++k)
+    FP_REQUIRE(material[k] >= 0.f && material[k] <= 1.f, "fp_render_raster_textured: material[%d] = %g is NaN or outside [0, 1]", k,
+               (double)material[k]);
+  TexArgs t;
+  memset(&t, 0, sizeof(t));
+  texture_levels(tex_width, tex_height, &t);
+  t.uv = uv, t.texels = pyramid;
+  t.metallic = material[0], t.roughness = material[1];
+  t.factor[0] = material[2], t.factor[1] = material[3], t.factor[2] = material[4];
+  t.srgb = material[5] != 0.f;
+  return launch_render_raster_textured(a, t, ST(stream));
+}
+
 int fp_template_downsample(const float* color, const float* depth, const uint8_t* mask, int batch, int out_h, int out_w,
                            int factor, uint8_t* rgb, uint16_t* depth_u16, uint8_t* mask_out, int32_t* boxes,
                            fp_stream_t stream) {

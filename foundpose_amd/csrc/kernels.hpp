@@ -94,8 +94,18 @@ struct RenderArgs {
   void* vert_ws; void* tri_ws; int* tile_counts; long long* tile_offsets; int* lists; long long* status;
   float* color; float* depth; unsigned char* mask; int* tri_id; int* boxes;
 };
+struct TexArgs {                  // a textured model (fp_render_raster_textured); zero for the vertex-coloured raster
+  const float* uv;                 // [num_verts, 2]
+  const unsigned* texels;          // packed RGBA8 pyramid (fp_texture_mips)
+  int levels;                      // level l: texels [off[l], off[l] + w[l] h[l])
+  int off[FP_TEXTURE_MAX_LEVELS], w[FP_TEXTURE_MAX_LEVELS], h[FP_TEXTURE_MAX_LEVELS];
+  float metallic, roughness, factor[3];
+  int srgb;
+};
 int launch_render_setup(const RenderArgs& a, hipStream_t st);
 int launch_render_raster(const RenderArgs& a, hipStream_t st);
+int launch_render_raster_textured(const RenderArgs& a, const TexArgs& t, hipStream_t st);
+int launch_texture_mips(const unsigned char* rgb, const TexArgs& t, unsigned* pyramid, hipStream_t st);
 
 struct DownsampleArgs {
   const float* color; const float* depth; const unsigned char* mask; int batch, out_h, out_w, factor;

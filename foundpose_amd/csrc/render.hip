@@ -11,7 +11,9 @@
 //                          arbitrary; the raster's total order makes the result independent of it)
 //   render_raster_kernel   one 256-thread workgroup per (view, 32 x 32 tile), 4 pixels per thread; triangle records staged
 //                          through LDS; nearest z (fp32), ties to the lower triangle id; then the winners are shaded and
-//                          the per-view box of covered pixels is reduced (integer atomics)
+//                          the per-view box of covered pixels is reduced (integer atomics).  <false>: vertex colours;
+//                          <true>: a trilinear sample of the texture pyramid at the interpolated uv, analytic LOD
+//   texture_*_kernel       the mip pyramid of a texture (packed RGBA8, integer box filter, one launch per level)
 //   downsample_kernel      ssaa x ssaa blocks -> template pixels: colour block mean -> trunc(255 c), depth / mask top-left
 //
 // Coverage, depth, mask and triangle id are exact functions of the inputs (integer edge functions, individually rounded
@@ -221,8 +223,10 @@ __global__ __launch_bounds__(256) void render_init_kernel(RenderArgs a) {
 
 // Lighting of one covered pixel ("unpinned"): pyrender's metallic-roughness shader with the
 // reference's spot light at the camera and its ambient term, evaluated in eye space (metres).
-FP_DEVICE float shade_channel(float base, float nl, float nv, float nh, float vh, float radiance, float F90) {
-  constexpr float kPi = 3.14159265358979f, kMetallic = 0.2f, kAlpha = 0.64f /* roughness 0.8 squared */, kF0 = 0.04f;
+// metallic / alpha (= roughness^2): the material; the vertex-coloured path passes the constants 0.2 / 0.64.
+FP_DEVICE float shade_channel(float base, float nl, float nv, float nh, float vh, float radiance, float F90, float kMetallic,
+                              float kAlpha) {
+  constexpr float kPi = 3.14159265358979f, kF0 = 0.04f;
   const float diffuse_color = fm(fm(base, fsub(1.f, kF0)), fsub(1.f, kMetallic));
   const float spec_color = fa(fm(kF0, fsub(1.f, kMetallic)), fm(base, kMetallic));
   const float one_vh = fclamp(fsub(1.f, vh), 0.f, 1.f);
@@ -240,7 +244,77 @@ FP_DEVICE float shade_channel(float base, float nl, float nv, float nh, float vh
   return fclamp(c, 0.f, 1.f);
 }
 
-__global__ __launch_bounds__(256) void render_raster_kernel(RenderArgs a) {
+// GL REPEAT on an integer texel index, then a clamp: the result is inside [0, n) for every int i
+FP_DEVICE int wrap_index(int i, int n) { return min(max(((i % n) + n) % n, 0), n - 1); }
+
+// GL LINEAR on level l: s = u w - 1/2, t = (1 - v) h - 1/2 (row 0 of the image is v = 1), texels k / 255, fixed blend order
+FP_DEVICE void sample_bilinear(const TexArgs& t, int l, float u, float v, float out[3]) {
+  const int w = t.w[l], h = t.h[l];
+  const float s = fsub(fm(u, (float)w), 0.5f), r = fsub(fm(fsub(1.f, v), (float)h), 0.5f);
+  const float fs = floorf(s), fr = floorf(r);
+  const float al = fsub(s, fs), be = fsub(r, fr);
+  const int i0 = (int)fclamp(fs, -1073741824.f, 1073741824.f), j0 = (int)fclamp(fr, -1073741824.f, 1073741824.f);
+  const int x0 = wrap_index(i0, w), x1 = wrap_index(i0 + 1, w), y0 = wrap_index(j0, h), y1 = wrap_index(j0 + 1, h);
+  const unsigned* lv = t.texels + t.off[l];
+  const unsigned p00 = lv[y0 * w + x0], p10 = lv[y0 * w + x1], p01 = lv[y1 * w + x0], p11 = lv[y1 * w + x1];
+  const float a1 = fsub(1.f, al), b1 = fsub(1.f, be);
+  for (int ch = 0; ch < 3; ++ch) {
+    const int sh = 8 * ch;
+    const float t00 = fdv((float)((p00 >> sh) & 255u), 255.f), t10 = fdv((float)((p10 >> sh) & 255u), 255.f);
+    const float t01 = fdv((float)((p01 >> sh) & 255u), 255.f), t11 = fdv((float)((p11 >> sh) & 255u), 255.f);
+    out[ch] = fa(fm(b1, fa(fm(a1, t00), fm(al, t10))), fm(be, fa(fm(a1, t01), fm(al, t11))));
+  }
+}
+
+// Base colour of a textured winner: uv at the pixel centre (w_k as the colour path), its screen derivatives from the
+// analytic d q_k / dx = ((256 A_k) / area) / z_k (fp64), GL's isotropic LOD, LINEAR / LINEAR_MIPMAP_LINEAR, sRGB decode,
+// base factor.
+FP_DEVICE void textured_base(const TexArgs& t, const TriRec& r, const double q[3], float w0, float w1, float w2, float base[3]) {
+  const float2 t0 = reinterpret_cast<const float2*>(t.uv)[r.vid[0]], t1 = reinterpret_cast<const float2*>(t.uv)[r.vid[1]],
+               t2 = reinterpret_cast<const float2*>(t.uv)[r.vid[2]];
+  const float u = fa(fa(fm(w0, t0.x), fm(w1, t1.x)), fm(w2, t2.x)), v = fa(fa(fm(w0, t0.y), fm(w1, t1.y)), fm(w2, t2.y));
+  const double ar = (double)r.area;
+  double qx[3], qy[3];
+  for (int e = 0; e < 3; ++e) {
+    qx[e] = ddiv(ddiv(dmul(256.0, (double)r.A[e]), ar), r.z[e]);
+    qy[e] = ddiv(ddiv(dmul(256.0, (double)r.B[e]), ar), r.z[e]);
+  }
+  const double D = dadd(dadd(q[0], q[1]), q[2]), Dx = dadd(dadd(qx[0], qx[1]), qx[2]), Dy = dadd(dadd(qy[0], qy[1]), qy[2]);
+  const double u0 = t0.x, u1 = t1.x, u2 = t2.x, v0 = t0.y, v1 = t1.y, v2 = t2.y, ud = u, vd = v;
+  const double ux = ddiv(dadd(dot3(qx[0], qx[1], qx[2], u0, u1, u2), -dmul(ud, Dx)), D);
+  const double vx = ddiv(dadd(dot3(qx[0], qx[1], qx[2], v0, v1, v2), -dmul(vd, Dx)), D);
+  const double uy = ddiv(dadd(dot3(qy[0], qy[1], qy[2], u0, u1, u2), -dmul(ud, Dy)), D);
+  const double vy = ddiv(dadd(dot3(qy[0], qy[1], qy[2], v0, v1, v2), -dmul(vd, Dy)), D);
+  const double W = t.w[0], H = t.h[0];
+  const double ax = dmul(ux, W), bx = dmul(vx, H), ay = dmul(uy, W), by = dmul(vy, H);
+  const double rho2 = fmax(dadd(dmul(ax, ax), dmul(bx, bx)), dadd(dmul(ay, ay), dmul(by, by)));
+  const float lod = fm(0.5f, log2f((float)rho2));
+  const int q_top = t.levels - 1;
+  float c[3];
+  if (!(lod > 0.f)) {  // magnification (and a degenerate uv map): LINEAR on level 0
+    sample_bilinear(t, 0, u, v, c);
+  } else {
+    const bool top = lod >= (float)q_top;
+    const float fl = floorf(lod);
+    const int d1 = top ? q_top : (int)fl;
+    const float f = top ? 0.f : fsub(lod, fl);
+    sample_bilinear(t, d1, u, v, c);
+    if (d1 < q_top) {  // d2 = d1 + 1; at the top level d2 = d1 and f = 0: the blend is c exactly
+      float c2[3];
+      sample_bilinear(t, d1 + 1, u, v, c2);
+      const float f1 = fsub(1.f, f);
+      for (int ch = 0; ch < 3; ++ch) c[ch] = fa(fm(f1, c[ch]), fm(f, c2[ch]));
+    }
+  }
+  for (int ch = 0; ch < 3; ++ch) {
+    float x = c[ch];
+    if (t.srgb) x = x <= 0.04045f ? fdv(x, 12.92f) : powf(fdv(fa(x, 0.055f), 1.055f), 2.4f);
+    base[ch] = fm(t.factor[ch], x);
+  }
+}
+
+template <bool kTextured>
+__global__ __launch_bounds__(256) void render_raster_kernel(RenderArgs a, TexArgs tex) {
   __shared__ TriRec lds[CHUNK];
   const int tiles_x = (a.width + TILE - 1) / TILE, tiles = tiles_x * ((a.height + TILE - 1) / TILE);
   const int tile = blockIdx.x, b = blockIdx.y;
@@ -322,14 +396,20 @@ __global__ __launch_bounds__(256) void render_raster_kernel(RenderArgs a) {
       float sa = fclamp(fa(fm(cd, spot_scale), spot_offset), 0.f, 1.f);
       sa = fm(sa, sa);
       const float radiance = fdv(fm(2.4f, sa), d2);
-      float base[3];
-      for (int ch = 0; ch < 3; ++ch) base[ch] = fa(fa(fm(w0, c0[ch]), fm(w1, c1[ch])), fm(w2, c2[ch]));
-      // reflectance at 90 degrees from the largest specular colour component (metallic 0.2 mix of 0.04 and the base)
+      float base[3], metallic, alpha;
+      if constexpr (kTextured) {
+        textured_base(tex, r, q, w0, w1, w2, base);
+        metallic = tex.metallic, alpha = fm(tex.roughness, tex.roughness);
+      } else {
+        for (int ch = 0; ch < 3; ++ch) base[ch] = fa(fa(fm(w0, c0[ch]), fm(w1, c1[ch])), fm(w2, c2[ch]));
+        metallic = 0.2f, alpha = 0.64f;  // roughness 0.8 squared
+      }
+      // reflectance at 90 degrees from the largest specular colour component (the metallic mix of 0.04 and the base)
       float refl = 0.f;
-      for (int ch = 0; ch < 3; ++ch) refl = fmaxf(refl, fa(fm(0.04f, 0.8f), fm(base[ch], 0.2f)));
+      for (int ch = 0; ch < 3; ++ch) refl = fmaxf(refl, fa(fm(0.04f, fsub(1.f, metallic)), fm(base[ch], metallic)));
       const float F90 = fclamp(fm(refl, 25.f), 0.f, 1.f);
       for (int ch = 0; ch < 3; ++ch) {
-        const float c = shade_channel(base[ch], nl, nv, nh, vh, radiance, F90);
+        const float c = shade_channel(base[ch], nl, nv, nh, vh, radiance, F90, metallic, alpha);
         rgb[ch] = fdv((float)__float2int_rn(fm(c, 255.f)), 255.f);  // unorm8 framebuffer, then / 255
       }
       bx0 = min(bx0, px), bx1 = max(bx1, px), by0 = min(by0, py), by1 = max(by1, py);
@@ -350,6 +430,28 @@ __global__ __launch_bounds__(256) void render_raster_kernel(RenderArgs a) {
       atomicMax(a.boxes + 4 * b + 2, bx1), atomicMax(a.boxes + 4 * b + 3, by1);
     }
   }
+}
+
+// level 0 of a pyramid: RGB bytes -> packed RGBA8, A = 255
+__global__ __launch_bounds__(256) void texture_pack_kernel(const unsigned char* rgb, int n, unsigned* out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = (unsigned)rgb[3 * i] | ((unsigned)rgb[3 * i + 1] << 8) | ((unsigned)rgb[3 * i + 2] << 16) | 0xff000000u;
+}
+
+// level l + 1 from level l: the rounded mean of a 2 x 2 block, indices clamped to the source (integer, exact)
+__global__ __launch_bounds__(256) void texture_reduce_kernel(const unsigned* src, int sw, int sh, unsigned* dst, int dw, int dh) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= dw * dh) return;
+  const int x = i % dw, y = i / dw;
+  const int xa = min(2 * x, sw - 1), xb = min(2 * x + 1, sw - 1), ya = min(2 * y, sh - 1), yb = min(2 * y + 1, sh - 1);
+  const unsigned p[4] = {src[ya * sw + xa], src[ya * sw + xb], src[yb * sw + xa], src[yb * sw + xb]};
+  unsigned out = 0xff000000u;
+  for (int ch = 0; ch < 3; ++ch) {
+    const int sh8 = 8 * ch;
+    const unsigned s = ((p[0] >> sh8) & 255u) + ((p[1] >> sh8) & 255u) + ((p[2] >> sh8) & 255u) + ((p[3] >> sh8) & 255u);
+    out |= ((s + 2u) >> 2) << sh8;
+  }
+  dst[i] = out;
 }
 
 __global__ __launch_bounds__(256) void box_init_kernel(int* boxes, int batch) {
@@ -422,8 +524,30 @@ int launch_render_raster(const RenderArgs& a, hipStream_t st) {
   const long long nf = (long long)a.batch * a.num_faces;
   hipLaunchKernelGGL(render_setup_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, a, 1);
   FP_CHECK_LAUNCH("render_scatter");
-  hipLaunchKernelGGL(render_raster_kernel, dim3(tiles, a.batch), dim3(256), 0, st, a);
+  TexArgs none{};
+  hipLaunchKernelGGL(render_raster_kernel<false>, dim3(tiles, a.batch), dim3(256), 0, st, a, none);
   FP_CHECK_LAUNCH("render_raster");
+  return FP_OK;
+}
+
+int launch_render_raster_textured(const RenderArgs& a, const TexArgs& t, hipStream_t st) {
+  const int tiles = cdiv(a.width, TILE) * cdiv(a.height, TILE);
+  const long long nf = (long long)a.batch * a.num_faces;
+  hipLaunchKernelGGL(render_setup_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, a, 1);
+  FP_CHECK_LAUNCH("render_scatter");
+  hipLaunchKernelGGL(render_raster_kernel<true>, dim3(tiles, a.batch), dim3(256), 0, st, a, t);
+  FP_CHECK_LAUNCH("render_raster_textured");
+  return FP_OK;
+}
+
+int launch_texture_mips(const unsigned char* rgb, const TexArgs& t, unsigned* pyramid, hipStream_t st) {
+  hipLaunchKernelGGL(texture_pack_kernel, dim3(cdiv(t.w[0] * t.h[0], 256)), dim3(256), 0, st, rgb, t.w[0] * t.h[0], pyramid);
+  FP_CHECK_LAUNCH("texture_pack");
+  for (int l = 1; l < t.levels; ++l) {
+    hipLaunchKernelGGL(texture_reduce_kernel, dim3(cdiv(t.w[l] * t.h[l], 256)), dim3(256), 0, st, pyramid + t.off[l - 1],
+                       t.w[l - 1], t.h[l - 1], pyramid + t.off[l], t.w[l], t.h[l]);
+    FP_CHECK_LAUNCH("texture_reduce");
+  }
   return FP_OK;
 }
 

@@ -84,7 +84,7 @@ def load_eval_model(models_dir: str, lid: int, max_sym_disc_step: float = 0.01, 
         with open(os.path.join(models_dir, "models_info.json")) as f:
             models_info = json.load(f)
     info = models_info[str(lid)] if str(lid) in models_info else models_info[lid]
-    pts = load_ply(os.path.join(models_dir, f"obj_{lid:06d}.ply")).vertices.astype(np.float64)
+    pts = load_ply(os.path.join(models_dir, f"obj_{lid:06d}.ply"), geometry_only=True).vertices.astype(np.float64)  # textured models too
     return EvalModel(pts, get_symmetry_transformations(info, max_sym_disc_step), float(info["diameter"]))
 
 

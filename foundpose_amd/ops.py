@@ -401,3 +401,18 @@ def vsd_counts(depth_test: torch.Tensor, depth_est: torch.Tensor, depth_gt: torc
          p.ctypes.data_as(_lib.vp), q.ctypes.data_as(_lib.vp), n, t.ctypes.data_as(_lib.vp), len(t), ptr(scratch),
          _lib.vsd_scratch_bytes(n), ptr(counts), stream())
     return counts
+
+
+def texture_mips(rgb: torch.Tensor) -> torch.Tensor:
+    """The mip pyramid of a texture (fp_texture_mips): rgb uint8 [H, W, 3] on the device -> int32 [total] holding packed RGBA8
+    texels (view as uint32), the levels back to back in the layout of _lib.texture_levels(W, H)."""
+    require_cuda(rgb)
+    if rgb.dim() != 3 or rgb.shape[2] != 3 or rgb.dtype != torch.uint8:
+        raise ValueError("texture_mips: rgb must be uint8 [H, W, 3]")
+    h, w = int(rgb.shape[0]), int(rgb.shape[1])
+    if not (1 <= h <= _lib.TEXTURE_MAX_SIDE and 1 <= w <= _lib.TEXTURE_MAX_SIDE):
+        raise ValueError(f"texture_mips: texture {w} x {h} outside [1, {_lib.TEXTURE_MAX_SIDE}]")
+    rgb = rgb.contiguous()
+    out = torch.empty(_lib.texture_levels(w, h)[1], dtype=torch.int32, device=rgb.device)
+    call("fp_texture_mips", ptr(rgb), w, h, ptr(out), stream())
+    return out

@@ -198,6 +198,48 @@ def make_blob_mesh(num_lat: int = 50, num_lon: int = 50, radius: float = 60.0, s
     return Mesh(vertices=v, faces=faces, colors=col.astype(np.float32), normals=vertex_normals(v, faces))
 
 
+def make_texture(size: int = 256, seed: int = 0):
+    """A procedural RGB texture, uint8 [size, size, 3]: colour ramps along both axes, a checker of size / 16 cells, an
+    off-centre disc and an L-shaped bar (no symmetry), and bright stripes along the left and right borders (the seam)."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:size, 0:size].astype(np.float64) / size
+    cell = max(size // 16, 1)
+    chk = ((np.arange(size)[:, None] // cell + np.arange(size)[None, :] // cell) % 2).astype(np.float64)
+    img = np.stack([x, 0.3 + 0.5 * y, 0.25 + 0.5 * chk], -1)
+    cx, cy = rng.uniform(0.55, 0.75, 2)
+    img[(x - cx) ** 2 + (y - cy) ** 2 < 0.01] = (1.0, 0.9, 0.1)
+    img[(x > 0.15) & (x < 0.2) & (y > 0.1) & (y < 0.45)] = (0.1, 0.1, 0.9)
+    img[(x > 0.15) & (x < 0.35) & (y > 0.4) & (y < 0.45)] = (0.1, 0.1, 0.9)
+    img[(x < 0.02) | (x > 0.98)] = (1.0, 0.2, 0.6)
+    return np.rint(np.clip(img, 0, 1) * 255.0).astype(np.uint8)
+
+
+def make_textured_blob_mesh(num_lat: int = 50, num_lon: int = 50, radius: float = 60.0, seed: int = 0, tex_size: int = 256):
+    """make_blob_mesh's geometry with a spherical UV map and make_texture(tex_size): per-corner UVs, unmerged (every
+    triangle corner its own vertex, the merged mesh's normals, face order kept).  u = azimuth / 2 pi, v = 1 - polar / pi;
+    a triangle across the seam gets u > 1 on its wrapped corners (REPEAT makes that the same texels), a pole corner the
+    mean u of the other two."""
+    import numpy as np
+
+    from .renderer import Mesh
+    m = make_blob_mesh(num_lat, num_lon, radius, seed)
+    d = m.vertices.astype(np.float64) / (np.array([1.4, 1.0, 0.8]) * radius)
+    u = (np.arctan2(d[:, 1], d[:, 0]) % (2 * np.pi)) / (2 * np.pi)
+    v = 1.0 - np.arccos(np.clip(d[:, 2] / np.linalg.norm(d, axis=1), -1, 1)) / np.pi
+    cu, cv = u[m.faces], v[m.faces]                                   # [F, 3]
+    lo = cu.max(1, keepdims=True) - cu > 0.5
+    cu = np.where(lo, cu + 1.0, cu)                                   # the seam: wrap the low corners past 1
+    pole = (m.faces == 0) | (m.faces == len(m.vertices) - 1)
+    other = np.where(pole, np.nan, cu)
+    cu = np.where(pole, np.nanmean(other, 1, keepdims=True), cu)
+    idx = m.faces.reshape(-1)
+    F = len(m.faces)
+    uv = np.stack([cu.reshape(-1), cv.reshape(-1)], 1).astype(np.float32)
+    return Mesh(m.vertices[idx], np.arange(3 * F, dtype=np.int32).reshape(F, 3), m.colors[idx], m.normals[idx], uv,
+                make_texture(tex_size, seed))
+
+
 def make_bop_eval_scene(root: str, num_images: int = 4, num_objects: int = 2, width: int = 320, height: int = 240,
                         mesh_res: int = 40, gts_per_image: int = 2, depth_scale: float = 0.1, seed: int = 0,
                         device: str = "cuda"):

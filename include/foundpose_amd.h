@@ -483,6 +483,28 @@ int fp_render_raster(const float* verts, const float* normals, const float* colo
                      int32_t* tile_counts, int64_t* tile_offsets, int32_t* lists, int64_t* status, float* color,
                      float* depth, uint8_t* mask, int32_t* tri_id, int32_t* boxes, fp_stream_t stream);
 
+/* ---- textured models ("Textured models") ------------------------------------------------------
+ * fp_texture_mips  rgb u8 [height, width, 3] (device; row 0 is the top of the image) -> pyramid: packed RGBA8 uint32 texels
+ *                  (byte 0 red, 1 green, 2 blue, 3 = 255), every level row-major and the levels back to back.  Level 0 is
+ *                  the image; level l + 1 is max(1, w_l >> 1) x max(1, h_l >> 1) and its texel (x, y) is, per channel,
+ *                  (sum over i, j in {0, 1} of level_l(min(2x + i, w_l - 1), min(2y + j, h_l - 1)) + 2) >> 2; the levels
+ *                  run down to 1 x 1.  Level l starts at texel offset sum_{k < l} w_k h_k; the total is that sum over all
+ *                  levels (at most FP_TEXTURE_MAX_LEVELS).  Sides in [1, FP_TEXTURE_MAX_SIDE].
+ * fp_render_raster_textured  fp_render_raster (after the same fp_render_setup) for a textured model: coverage, depth, mask,
+ *                  tri_id and boxes are fp_render_raster's bit for bit; the colour samples the pyramid at the perspective-
+ *                  correct uv (uv fp32 [num_verts, 2], device; v = 1 is row 0 of the image) with trilinear filtering (GL
+ *                  LINEAR / LINEAR_MIPMAP_LINEAR, REPEAT wrap, analytic level of detail) and shades it with `material`
+ *                  (HOST float[6]: metallic, roughness, base factor r, g, b, sRGB decode flag 0 / 1; every entry in [0, 1]).
+ *                  tex_width x tex_height is level 0 of `pyramid`.  The colours argument is not read. */
+#define FP_TEXTURE_MAX_SIDE 16384
+#define FP_TEXTURE_MAX_LEVELS 15
+int fp_texture_mips(const uint8_t* rgb, int width, int height, uint32_t* pyramid, fp_stream_t stream);
+int fp_render_raster_textured(const float* verts, const float* normals, const float* colors, int num_verts, const int32_t* faces,
+                              int num_faces, const double* cams, int batch, int width, int height, void* vert_ws, void* tri_ws,
+                              int32_t* tile_counts, int64_t* tile_offsets, int32_t* lists, int64_t* status, float* color,
+                              float* depth, uint8_t* mask, int32_t* tri_id, int32_t* boxes, const float* uv,
+                              const uint32_t* pyramid, int tex_width, int tex_height, const float* material, fp_stream_t stream);
+
 /* SSAA downsample by an integer factor (gen_templates.py:373-386 with the output casts of :389-480): color fp32
  * [batch, 3, out_h * factor, out_w * factor] (fp_warp_crops' layout), depth fp32 and mask u8 [batch, out_h * factor,
  * out_w * factor] -> rgb u8 [batch, 3, out_h, out_w] = trunc(255 * block mean), depth_u16 = round-half-even of the block's

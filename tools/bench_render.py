@@ -2,7 +2,10 @@
 vertex-coloured mesh of ~20k triangles, the lmo camera (630 x 630 templates, SSAA 4 -> 2520 x 2520 renders), 420 x 420
 crops, 57 views x 14 in-plane rotations = 798 templates, 32 views per launch chain.
 
-    python tools/bench_render.py [--templates N] [--batch 32] [--png]
+    python tools/bench_render.py [--templates N] [--batch 32] [--png] [--textured]
+
+--textured: the same geometry as a textured model (per-corner spherical UVs, unmerged; a 2048 x 2048 procedural texture
+with its mip pyramid, the default material), rendered by render_raster_kernel<true>.
 
 Reports templates/s of the device chain (render -> boxes -> crop cameras -> warps -> downsample, wall clock between
 device synchronisations, host work for the crop cameras included) with the device time of each stage from HIP events,
@@ -27,16 +30,20 @@ def main():
     ap.add_argument("--templates", type=int, default=798)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--png", action="store_true")
+    ap.add_argument("--textured", action="store_true")
     args = ap.parse_args()
     opts = gen_templates.GenTemplatesOpts(version="bench", object_dataset="lmo")
     K = np.array([[572.4114, 0.0, 325.2611], [0.0, 573.57043, 242.04899], [0.0, 0.0, 1.0]])
     _, render_cam = gen_templates.base_cameras(K, (640, 480), opts)
     views = gen_templates.template_views(opts, (346.31, 1499.84))[:args.templates]
-    mesh = synthetic.make_blob_mesh(100, 100, radius=70.0, seed=0)
+    if args.textured:
+        mesh = synthetic.make_textured_blob_mesh(100, 100, radius=70.0, seed=0, tex_size=2048)
+    else:
+        mesh = synthetic.make_blob_mesh(100, 100, radius=70.0, seed=0)
     r = HipRasterizer()
     r.add_object_model(1, mesh=mesh)
     print(f"mesh: {len(mesh.faces)} triangles, {len(mesh.vertices)} vertices; render {render_cam.width}^2, crop {opts.crop_size[0]}, "
-          f"{len(views)} templates, batch {args.batch}", flush=True)
+          f"{len(views)} templates, batch {args.batch}" + (f", texture {mesh.texture.shape[1]}^2" if args.textured else ""), flush=True)
     gen_templates.render_templates(r, 1, views[:args.batch], render_cam, opts)     # warm-up (code objects, allocator)
     torch.cuda.synchronize()
     # stage split from HIP events on one batch
