@@ -2,13 +2,14 @@
 """Headline benchmark: detections/sec (ViT + descriptor matching) on 518x518 crops against a 10k-template
 bank, one process per GPU.  Contract: see the task prompt / DESIGN.md "Measurement".
 
-  python bench.py                       # 1 GPU, finishes in a few minutes
+  python bench.py                       # 1 GPU: set-up, warm-up, the timed steps and the headline keys, nothing else
+  python bench.py --full                # ... then every other measurement and check (roofline, parity, CPU baseline, other configs): a few minutes
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
   python bench.py --gpus N ...          # no launcher: starts the line above itself (self_launch) and returns its exit code
 
 The workload is PLANTED (foundpose_amd/workload.py): every crop's fp32 features sit, with graded noise, in five
-consecutive templates of the bank, so the expected output of a step is known and the line carries index-agreement
+consecutive templates of the bank, so the expected output of a step is known and the --full line carries index-agreement
 numbers ("parity") next to the throughput: against oracle A (the fp32 CPU restatement, on the detections the
 cpu_baseline leg runs anyway) and against the library's own fp32 mode on every detection of the batch.
 """
@@ -159,8 +160,13 @@ def main():
     ap.add_argument("--parity-steps", type=int, default=5)
     ap.add_argument("--no-parity-fast", action="store_true", help="skip `parity_mode_fast` (the f16f8 mode timed next to the f16x3 parity mode)")
     ap.add_argument("--no-mode-f16", action="store_true", help="skip `mode_f16` (the fp16-operand mode timed next to the bf16 headline)")
-    ap.add_argument("--skip-probes", action="store_true", help="time the steps and stop: no roofline probe launches, no parity passes (tools/pmc_bench.sh: every "
-                                                                "launch the counters see then belongs to a step of the pipeline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures and checks: the other tie order, token selection, the near-exact and fp16 "
+                         "modes, the roofline probes, parity against the fp32 mode and the oracles, the CPU baseline, the margin-free workload, latency_b1, "
+                         "pipeline, other_configs and (N > 1) gather_ms.  --parity-precision, --parity-steps, --cpu-detections, --other-configs and "
+                         "the --no-* options shape this part only.  Without it the run sets up, warms up, times the steps, dumps and prints the headline keys")
+    ap.add_argument("--skip-probes", action="store_true", help="time the steps and stop, even with --full: what a run without --full does (tools/pmc_bench.sh: "
+                                                                "every launch the counters see then belongs to a step of the pipeline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the fp32-mode agreement pass (the oracle comparison rides on the cpu baseline)")
     ap.add_argument("--cpu-detections", type=int, default=5, help="detections of the CPU baseline sample (BASELINE.md section 2: median of >= 5)")
@@ -176,6 +182,7 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    full = args.full and not args.skip_probes
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -286,23 +293,38 @@ def main():
     rank_ms = [1e3 * v / args.steps for v in per_rank_s]
     multi = None
     if world > 1:   # diagnosability of the scaling run (the driver computes the efficiency itself from the per-N values)
-        g_ms = torch.tensor([gather_ms()], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
-        g_all = torch.empty(world, dtype=torch.float64, device=g_ms.device)
-        dist.all_gather_into_tensor(g_all, g_ms)
-        multi = {"per_rank_ms_per_step": {"min": round(min(rank_ms), 3), "max": round(max(rank_ms), 3), "all": [round(v, 3) for v in rank_ms]},
-                 "gather_ms": {"mean_over_ranks": round(float(g_all.mean()), 4), "max_over_ranks": round(float(g_all.max()), 4),
-                               "what": "HIP events around the one all-gather of result records, 5 extra untimed steps", "record_bytes_per_rank": None}}
-    if world > 1:
-        multi["gather_ms"]["record_bytes_per_rank"] = int(gathered.shape[0] // world * gathered.shape[1] * 4)
+        multi = {"per_rank_ms_per_step": {"min": round(min(rank_ms), 3), "max": round(max(rank_ms), 3), "all": [round(v, 3) for v in rank_ms]}}
+        if full:    # the exchange step alone: 5 extra steps
+            g_ms = torch.tensor([gather_ms()], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
+            g_all = torch.empty(world, dtype=torch.float64, device=g_ms.device)
+            dist.all_gather_into_tensor(g_all, g_ms)
+            multi["gather_ms"] = {"mean_over_ranks": round(float(g_all.mean()), 4), "max_over_ranks": round(float(g_all.max()), 4),
+                                  "what": "HIP events around the one all-gather of result records, 5 extra untimed steps",
+                                  "record_bytes_per_rank": int(gathered.shape[0] // world * gathered.shape[1] * 4)}
         ranks_seen = int(gathered.shape[0] // B)
         cnt = torch.ones(1, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(cnt)
         assert int(cnt.item()) == world == ranks_seen, "every rank must contribute its records to the gather"
-    if args.skip_probes:
+    # the headline keys: all a run without --full computes and prints
+    headline = {
+        "metric": "detections/sec (ViT+kNN match) on 518^2 crops vs 10k-template bank",
+        "value": round(det_per_s, 2), "unit": "detections/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": args.precision, "data": "synthetic (seeded crops assembled from 682 noise patch textures, disc masks, random-init ViT weights, planted bank: each crop's "
+                                         "fp32 features sit with graded noise in 5 consecutive templates, the rest are random texture sets; words = instances of the textures, see config.workload)",
+        "config": {"workload": f"{args.version} layer {args.layer} ({args.layer + 1} of {arch.depth} blocks executed, early exit after the hooked block" + (", the hooked block on the sampled tokens only" if select_on else "") + "), "
+                               f"{args.size}x{args.size} crops, batch {B}/GPU, {args.objects} object(s) x {args.templates} templates "
+                               f"(N_f={bank.feats.shape[0]}), {W_words} words ({wpt} per texture), PCA {arch.dim}->256, top-5 templates, top-300 buddies, {args.mask} mask Q={int(masks[0, 7::14, 7::14].sum())}, "
+                               f"tie order '{args.tie_order}'" + (" (the reference's torch.topk order, replayed on the device)" if args.tie_order == "torch" else ""),
+                   "parallelism": f"detections sharded over {world} GPU(s), one RCCL all-gather of result records per step",
+                   "tie_order": args.tie_order},
+        "ranks_seen": ranks_seen,
+        **({"multi_gpu": multi} if multi is not None else {}),
+        "full": full,
+    }
+    if not full:
         if rank == 0:
-            print(result_line({"metric": "detections/sec (ViT+kNN match) on 518^2 crops vs 10k-template bank", "value": round(det_per_s, 2), "unit": "detections/s",
-                               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "probes": "skipped", "ranks_seen": ranks_seen,
-                               **({"multi_gpu": multi} if multi is not None else {})}), flush=True)
+            print(result_line(headline), flush=True)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
@@ -481,19 +503,7 @@ def main():
         # proj is the one block GEMM whose floor is HBM, not the matrix pipe: fp32 residual read + write, bf16 copy, operands
         proj_bytes = mv * arch.dim * (2 + ((2 + 2) * 2 if hilo else 4 + 4 + (2 if fold else 0))) + arch.dim * arch.dim * 2   # A + stream read + stream write (+ bf16 copy)
         result = {
-            "metric": "detections/sec (ViT+kNN match) on 518^2 crops vs 10k-template bank",
-            "value": round(det_per_s, 2), "unit": "detections/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": args.precision, "data": "synthetic (seeded crops assembled from 682 noise patch textures, disc masks, random-init ViT weights, planted bank: each crop's "
-                                             "fp32 features sit with graded noise in 5 consecutive templates, the rest are random texture sets; words = instances of the textures, see config.workload)",
-            "config": {"workload": f"{args.version} layer {args.layer} ({args.layer + 1} of {arch.depth} blocks executed, early exit after the hooked block" + (", the hooked block on the sampled tokens only" if select_on else "") + "), "
-                                   f"{args.size}x{args.size} crops, batch {B}/GPU, {args.objects} object(s) x {args.templates} templates "
-                                   f"(N_f={bank.feats.shape[0]}), {W_words} words ({wpt} per texture), PCA {arch.dim}->256, top-5 templates, top-300 buddies, {args.mask} mask Q={int(masks[0, 7::14, 7::14].sum())}, "
-                                   f"tie order '{args.tie_order}'" + (" (the reference's torch.topk order, replayed on the device)" if args.tie_order == "torch" else ""),
-                       "parallelism": f"detections sharded over {world} GPU(s), one RCCL all-gather of result records per step",
-                       "tie_order": args.tie_order},
-            "ranks_seen": ranks_seen,
-            **({"multi_gpu": multi} if multi is not None else {}),
+            **headline,
             "tie_order_cost": {args.tie_order + "_ms_per_step": round(ms_per_step, 3), other + "_ms_per_step": round(ms_other, 3)},
             "roofline": {"kernel": ("gemm_bf16_kernel<RESID_HILO> (attn.proj + mlp.fc2 of one ViT block, residual update on the (hi, lo) bf16 stream + LayerNorm row sums: the largest time bucket of a step)"
                                     if hilo else "gemm_bf16_kernel<RESID> (attn.proj + mlp.fc2 of one ViT block, residual update + bf16 copy + LayerNorm row sums: the largest time bucket of a step)"

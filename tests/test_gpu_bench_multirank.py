@@ -16,7 +16,7 @@ def test_bench_two_ranks_dry_run():
     env = dict(os.environ, FP_BENCH_ONE_DEVICE="1", FP_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--templates", "600", "--batch", "8", "--version", "vits14-reg", "--layer", "9", "--size", "224"]
+           "--templates", "600", "--batch", "8", "--version", "vits14-reg", "--layer", "9", "--size", "224", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
