@@ -93,6 +93,8 @@ _PROTOS = {
     "fp_template_downsample": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
     "fp_pose_errors": [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp, vp],
     "fp_vsd_counts": [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp],
+    "fp_featuremetric_refine": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32,
+                                vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
 }
 
 _lib = None
@@ -169,6 +171,15 @@ VSD_MAX_TAUS = 16  # FP_VSD_MAX_TAUS of the header
 def vsd_scratch_bytes(num_pairs: int) -> int:
     """FP_VSD_SCRATCH_BYTES of include/foundpose_amd.h."""
     return 96 * num_pairs
+
+
+REFINE_CHUNK, REFINE_RECORD, REFINE_STATE_BYTES = 32, 32, 512  # FP_REFINE_* of the header
+
+
+def refine_scratch_bytes(num_det: int, max_points: int) -> int:
+    """FP_REFINE_SCRATCH_BYTES of include/foundpose_amd.h."""
+    chunks = (max_points + REFINE_CHUNK - 1) // REFINE_CHUNK
+    return REFINE_STATE_BYTES * num_det + 8 * REFINE_RECORD * num_det * chunks + ((num_det * max_points + 7) // 8) * 8 + 8
 
 
 TEXTURE_MAX_SIDE = 16384  # FP_TEXTURE_MAX_SIDE of the header

@@ -282,6 +282,26 @@ struct PoseErrArgs {
 };
 int launch_pose_errors(const PoseErrArgs& a, int num_hyp, int max_tiles, int max_syms, hipStream_t st);
 
+// ---------------------------------------------------------------- refine.hip
+struct RefineState {       // Levenberg-Marquardt state of one detection (scratch, FP_REFINE_STATE_BYTES)
+  double R[9], t[3];       // current pose
+  double Rt[9], tt[3];     // trial pose (the next pass evaluates it)
+  double H[21], g[6];      // system at the current pose
+  double E, E_in, lam, sigma2;
+  int p0, np;              // bank rows [p0, p0 + np)
+  int it, active, pending, accepted, skipped, nvalid;
+};
+struct RefineArgs {
+  const float* map; long long sb, sy, sx, sc; int gh, gw, C, pad0; double W, H;
+  const double* cam; const double* R_in; const double* t_in;
+  const int32_t* row_begin; const int32_t* row_end; const float* feats; const float* verts; long long num_rows;
+  const int32_t* has_pose; int num_det, max_points, iters, chunks;
+  double* R_out; double* t_out; double* cost_in; double* cost_out; int32_t* num_points; int32_t* iters_used; int32_t* status;
+  double* normal_eq;       // [num_det, 28] or null
+  RefineState* state; double* part; uint8_t* valid; int32_t* err;
+};
+int launch_featuremetric_refine(const RefineArgs& a, hipStream_t st);
+
 // ---------------------------------------------------------------- vsd.hip
 struct VsdPair {                         // one (estimate, GT) pair, built on the host by fp_vsd_counts
   long long test_off, est_off, gt_off;   // element offsets of the three depth images (index * height * width)

@@ -19,6 +19,7 @@
 // the kernel is latency / fp64-VALU bound.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "rot.hpp"
 
 namespace {
 
@@ -37,12 +38,6 @@ FP_DEVICE unsigned long long mix64(unsigned long long z) {  // splitmix64 finali
   return z ^ (z >> 31);
 }
 
-FP_DEVICE void cross3(const double* a, const double* b, double* c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-FP_DEVICE double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 FP_DEVICE bool normalize3(double* a) {
   const double n = sqrt(dot3(a, a));
   if (!(n > 1e-300)) return false;
@@ -209,21 +204,6 @@ FP_DEVICE double block_sum(double v, double* red, int tid) {
   if ((tid & 63) == 0) red[tid >> 6] = v;
   __syncthreads();
   return red[0] + red[1] + red[2] + red[3];
-}
-
-// exp of a rotation vector times R (left perturbation)
-FP_DEVICE void rot_update(const double* w, const double* R, double* Rn) {
-  const double th2 = dot3(w, w), th = sqrt(th2);
-  double a, b;  // exp([w]x) = I + a [w]x + b [w]x^2
-  if (th < 1e-8) { a = 1.0 - th2 / 6.0; b = 0.5 - th2 / 24.0; }
-  else { a = sin(th) / th; b = (1.0 - cos(th)) / th2; }
-  const double K[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-  double K2[9], E[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) K2[i * 3 + j] = K[i * 3 + 0] * K[0 * 3 + j] + K[i * 3 + 1] * K[1 * 3 + j] + K[i * 3 + 2] * K[2 * 3 + j];
-  for (int i = 0; i < 9; ++i) E[i] = (i % 4 == 0 ? 1.0 : 0.0) + a * K[i] + b * K2[i];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) Rn[i * 3 + j] = E[i * 3 + 0] * R[0 * 3 + j] + E[i * 3 + 1] * R[1 * 3 + j] + E[i * 3 + 2] * R[2 * 3 + j];
 }
 
 // RANSACUpdateNumIters of OpenCV's point-set registrator

@@ -598,6 +598,15 @@ class DinoFeatureExtractor(torch.nn.Module):
                  ptr(point_img), points.shape[0], ptr(row_map), ptr(out), stream())
         return out
 
+    def hidden_feature_map(self) -> torch.Tensor:
+        """The whole feature map of the batch forward_hidden (prefix_only=False) just ran: final norm of every patch token -> [B, gh * gw, D]
+        fp32, what forward_tokens returns (featuremetric refinement samples it anywhere, not only under the mask)."""
+        B, gh, gw, H, W = self._hidden
+        ws, _ = self._workspace(B, gh, gw)
+        fmap = torch.empty(B, gh * gw, self.arch.dim, dtype=torch.float32, device=self._device)
+        call("fp_vit_features", C.byref(self._model), C.byref(ws), B, gh * gw, int(self.apply_norm), ptr(fmap), None, stream())
+        return fmap
+
     def _forward_facet(self, images, B, H, W, gh, gw):
         """key / query / value facet (dinov2_utils.py:176-194, 294-311 in the reference): the qkv projection of
         blocks[layer] is what the forward leaves in the workspace; per token the reference orders the vector (d, head)."""

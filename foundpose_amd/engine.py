@@ -147,14 +147,18 @@ class FoundPoseEngine:
         return out + ((sel[0], sel[1], sel[2], sum(sel_counts), max(sel_counts)),)
 
     def infer_batch(self, images: torch.Tensor, masks: torch.Tensor, det_obj: Optional[Sequence[int]] = None,
-                    keep_debug: bool = False) -> MatchResult:
+                    keep_debug: bool = False, keep_feature_map: bool = False) -> MatchResult:
+        """keep_feature_map: also return the projected patch-feature map of every detection (MatchResult.feature_map [B, gh, gw, C] fp32,
+        each through its own object's projector chain) for the featuremetric refinement (refine_util).  The hooked block then runs on all
+        tokens -- the refinement samples outside the mask -- and the correspondences are the same bit for bit."""
         B, _, H, W = images.shape
         det_obj = [0] * B if det_obj is None else list(det_obj)
         fused = self.extractor.facet == "token" and not self.extractor.use_graph and self.fused_sample
         # The reference samples the hooked block's feature map at the query points and nowhere else (infer.py:452-466), so
         # that block only has to produce the patch tokens under the sampling taps: its attention queries, proj and MLP run on
         # those tokens (keys / values: all tokens).  Same sampled features bit for bit; engine.select_tokens = False is the A/B switch.
-        select = fused and self.extractor.supports_token_selection and self.select_tokens
+        select = fused and self.extractor.supports_token_selection and self.select_tokens and not keep_feature_map
+        fmap = None
         self._stage_events = []
         self._mark("start")
         # f16x3 / fp8: clamped activations are reported per BATCH -- the sticky device counters are snapshotted before and after the backbone
@@ -174,8 +178,12 @@ class FoundPoseEngine:
             q_pts, q_img, counts = self._query_points_end(*pending)
             self._mark("feat_extract")
             raw = self.extractor.sample_patch_features(q_pts, q_img)
+            if keep_feature_map:
+                fmap = self.extractor.hidden_feature_map()
         else:
             fmap, _ = self.extractor.forward_tokens(images)
+            if keep_feature_map and self.extractor.use_graph:
+                fmap = fmap.clone()   # the graph's static output buffer: the next batch overwrites it
             q_pts, q_img, counts = self._query_points_end(*pending)
             self._mark("feat_extract")
             gh, gw = self.extractor.num_patches
@@ -190,10 +198,12 @@ class FoundPoseEngine:
             sat_delta = sat1 if sat0 is None else (sat1 - sat0).clamp_min_(0)
         if not self.overlap_matching:
             feats = self._project(raw, counts, det_obj)
+            fmap_proj = self._project_map(fmap, det_obj) if keep_feature_map else None
             self._mark("proj")
             res = match_batch(self.bank, feats, q_pts, counts, det_obj, self.top_n, self.top_k, keep_debug, self.tie_order,
                               mark=self._submark if self.record_stage_times else None, prefilter=self.prefilter)
             self._mark("corresp")
+            res.feature_map = fmap_proj
             if track_sat:
                 res.extractor, res.sat_delta = self.extractor, sat_delta   # corresp_list() reads the verdict of this batch
             return res
@@ -202,13 +212,15 @@ class FoundPoseEngine:
         produced.record(main)
         with torch.cuda.stream(side):
             side.wait_event(produced)
-            for t in (raw, q_pts, q_img):       # allocated on the caller's stream, consumed here
+            for t in (raw, q_pts, q_img) + ((fmap,) if keep_feature_map else ()):       # allocated on the caller's stream, consumed here
                 t.record_stream(side)
             feats = self._project(raw, counts, det_obj)
+            fmap_proj = self._project_map(fmap, det_obj) if keep_feature_map else None
             self._mark("proj")
             res = match_batch(self.bank, feats, q_pts, counts, det_obj, self.top_n, self.top_k, keep_debug, self.tie_order,
                               mark=self._submark if self.record_stage_times else None, prefilter=self.prefilter)
             self._mark("corresp")
+            res.feature_map = fmap_proj
             res.ready = torch.cuda.Event()
             res.ready.record(side)
         if track_sat:
@@ -229,6 +241,13 @@ class FoundPoseEngine:
         from . import crop_util
         crops, crop_masks, cams = crop_util.crop_detections(image_hwc, masks_modal, boxes_amodal, camera_c2w, crop_size, crop_rel_pad)
         return self.infer_batch(crops, crop_masks, det_obj, keep_debug), cams
+
+    def _project_map(self, fmap: torch.Tensor, det_obj: Sequence[int]) -> torch.Tensor:
+        """[B, gh * gw, D] token-major map -> [B, gh, gw, C]: every detection's rows through its own object's projector chain."""
+        B, n, D = fmap.shape
+        gh, gw = self.extractor.num_patches
+        out = self._project(fmap.reshape(B * n, D), [n] * B, det_obj)
+        return out.reshape(B, gh, gw, out.shape[-1])
 
     def _project(self, raw: torch.Tensor, counts: Sequence[int], det_obj: Sequence[int]) -> torch.Tensor:
         if raw.shape[1] == self.bank.feat_dim:

@@ -19,7 +19,7 @@ from typing import Any, Dict, Iterable, List, NamedTuple, Optional, Sequence, Tu
 import numpy as np
 import torch
 
-from . import crop_util, engine as fe, eval_util, feature_util, infer_pose_util, pnp_util, repre_util
+from . import crop_util, engine as fe, eval_util, feature_util, infer_pose_util, pnp_util, refine_util, repre_util
 from .bank import DeviceBank
 
 
@@ -55,6 +55,10 @@ class InferOpts(NamedTuple):
     vis_feat_map: bool = True
     vis_for_paper: bool = True
     debug: bool = True
+    refine_iters: int = 30          # final_pose_type="featuremetric": Levenberg-Marquardt iterations (refine_util)
+
+
+FINAL_POSE_TYPES = ("best_coarse", "featuremetric")
 
 
 def load_opts(path_or_dict) -> InferOpts:
@@ -82,8 +86,11 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
         raise ValueError(f"Unknown matching type '{opts.match_template_type}'.")
     if opts.match_feat_matching_type != "cyclic_buddies":
         raise ValueError(f"Unknown feature matching type ({opts.match_feat_matching_type}).")
-    if opts.final_pose_type != "best_coarse":
+    if opts.final_pose_type not in FINAL_POSE_TYPES:
         raise ValueError(f"Unknown final pose type {opts.final_pose_type}")
+    refine = opts.final_pose_type == "featuremetric"   # the best coarse pose refined featuremetrically (refine_util)
+    if refine and (not isinstance(opts.refine_iters, int) or opts.refine_iters < 0):
+        raise ValueError(f"refine_iters must be an integer >= 0, got {opts.refine_iters!r}")
     # scripts/infer.py:482-485 subsamples the query points with torch.randperm when a mask yields more than max_num_queries of them
     # (default 1 000 000: never for a crop).  The batched path keeps every point; an option value that could trigger the subsampling
     # is refused instead of being ignored (crop=False: checked per frame against the image's own grid).
@@ -163,7 +170,7 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
             crop_masks, cams = masks, [cam] * len(kept)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        res = eng.infer_batch(crops, crop_masks, [0] * len(kept))
+        res = eng.infer_batch(crops, crop_masks, [0] * len(kept), keep_feature_map=refine)
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
@@ -174,6 +181,10 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
         found, cid = best["found"].cpu().tolist(), best["corresp_id"].cpu().tolist()
         Rb, tb = best["R"].cpu().numpy(), best["t"].cpu().numpy()
         t4 = time.perf_counter()
+        if refine:   # infer.py:619: the refined pose of the best coarse pose is the final pose
+            ref = refine_util.refine_best_coarse(res, best, bank, [0] * len(kept), cams, (crops.shape[-1], crops.shape[-2]), opts.refine_iters)
+            Rb, tb = ref["R"].cpu().numpy(), ref["t"].cpu().numpy()
+            t5 = time.perf_counter()
         n = len(kept)
         # The reference's per-detection `times` keys (infer.py:464-633, persisted by eval_util.py:327).  The instances of a frame
         # run as ONE batch here, so every instance is charged its share of the batch; the four stages inside infer_batch come
@@ -184,6 +195,8 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
                  "feat_extract": (st.get("feat_extract", 0.0) + max(0.0, (t2 - t1) - dev_sum)) / n,
                  "grid_sample": st.get("grid_sample", 0.0) / n, "proj": st.get("proj", 0.0) / n, "corresp": st.get("corresp", 0.0) / n,
                  "pose_coarse": (t3 - t2) / n, "final_select": (t4 - t3) / n}
+        if refine:
+            times["pose_refine"] = (t5 - t4) / n
         pending = []   # consecutive annotated hypotheses: evaluated in one launch, recorded in instance order
 
         def flush():

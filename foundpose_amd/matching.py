@@ -38,6 +38,8 @@ class MatchResult:
     _sat_error: Optional[Exception] = None      # the saturation verdict of this result, once read (see corresp_list)
     ready: Optional["torch.cuda.Event"] = None  # set when the matching ran on the engine's side stream (overlap_matching): the tensors are
                                                 # complete once this event has fired; wait() makes the current stream wait for it
+    feature_map: Optional[torch.Tensor] = None  # [B, gh, gw, C] f32 (infer_batch(keep_feature_map=True)): the projected patch-feature map of
+                                                # each detection, through its own object's projector chain (featuremetric refinement)
 
     def wait(self) -> "MatchResult":
         """Makes the current stream wait for the matching stream, and tells the caching allocator that the result tensors
@@ -48,7 +50,7 @@ class MatchResult:
             cur = torch.cuda.current_stream()
             cur.wait_event(self.ready)
             for t in (self.template_ids, self.template_scores, self.counts, self.q_ids, self.feat_ids, self.dists, self.conf, self.coord_2d,
-                      self.coord_3d, self.query_tfidf, self.word_ids):
+                      self.coord_3d, self.query_tfidf, self.word_ids, self.feature_map):
                 if t is not None and t.is_cuda:
                     t.record_stream(cur)
         return self

@@ -1,0 +1,102 @@
+"""Featuremetric refinement of the best coarse pose on the MI355X.
+
+The FoundPose paper's third stage, which the released reference leaves as hooks only (scripts/infer.py:619, `final_pose_type`):
+Levenberg-Marquardt on the 6-DoF pose that aligns the per-point features of the template behind the best coarse pose with the
+query's projected patch-feature map.  One fp_featuremetric_refine call (csrc/refine.hip) refines a whole batch; the contract is
+restated in numpy fp64 by tests/featuremetric_ref.py.
+"""
+
+from typing import Any, Dict, Optional, Sequence, Tuple
+
+import torch
+
+from ._lib import call, ptr, refine_scratch_bytes, require_cuda, stream, upload_async
+from .bank import DeviceBank
+from .matching import MatchResult
+from .pnp_util import _intrinsics
+
+STATUS_REFINED, STATUS_NOT_IMPROVED, STATUS_SKIPPED = 0, 1, 2
+
+
+def refine_featuremetric(feature_map: torch.Tensor, image_size: Tuple[int, int], cameras: Sequence[Any], R: torch.Tensor, t: torch.Tensor,
+                         row_begin: torch.Tensor, row_end: torch.Tensor, feats: torch.Tensor, vertices: torch.Tensor, has_pose: torch.Tensor,
+                         iters: int = 30, return_normal_equations: bool = False, max_points: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """feature_map [B, gh, gw, C] fp32 (any strides), image_size (W, H) of the camera the poses live in, cameras: one pinhole
+    camera per detection (what pnp_util accepts), R [B, 3, 3] / t [B, 3] model -> camera (mm), row_begin / row_end [B] int:
+    each detection's rows of feats [N, C] / vertices [N, 3], has_pose [B] bool.  max_points bounds row_end - row_begin (None:
+    read back from the device).  -> dict of device tensors: R [B, 3, 3] f64, t [B, 3] f64, cost_in, cost_out [B] f64,
+    num_points, iters_used, status [B] i32 (0 refined, 1 no step accepted, 2 skipped), + normal_eq [B, 28] f64 (H upper
+    triangle row-major | g | E at the input pose) with return_normal_equations."""
+    require_cuda(feature_map, R, t, row_begin, row_end, feats, vertices, has_pose)
+    if feature_map.dim() != 4:
+        raise ValueError("feature_map must be [B, gh, gw, C]")
+    B, gh, gw, C = feature_map.shape
+    if gh < 2 or gw < 2:
+        raise ValueError(f"the feature map is {gh} x {gw}: refinement needs at least 2 x 2 cells")
+    if int(iters) < 0:
+        raise ValueError("iters must be >= 0")
+    if feats.dim() != 2 or feats.shape[1] != C or vertices.shape != (feats.shape[0], 3):
+        raise ValueError(f"feats {tuple(feats.shape)} / vertices {tuple(vertices.shape)} do not match a C = {C} map")
+    if len(cameras) != B:
+        raise ValueError(f"{len(cameras)} cameras for {B} detections")
+    dev = feature_map.device
+    fmap = feature_map if feature_map.dtype == torch.float32 else feature_map.float()
+    W, H = int(image_size[0]), int(image_size[1])
+    cam = upload_async(torch.tensor([_intrinsics(c) for c in cameras], dtype=torch.float64).reshape(B, 4), dev)
+    Rin = R.to(torch.float64).reshape(B, 9).contiguous()
+    tin = t.to(torch.float64).reshape(B, 3).contiguous()
+    rb = row_begin.to(torch.int32).contiguous()
+    re = row_end.to(torch.int32).contiguous()
+    hp = has_pose.to(torch.int32).contiguous()
+    f32 = feats.float().contiguous()
+    v32 = vertices.float().contiguous()
+    if max_points is None:
+        max_points = int(torch.where(hp != 0, re - rb, torch.zeros_like(re)).max().item()) if B else 0
+    max_points = max(1, int(max_points))
+    scratch = torch.empty(refine_scratch_bytes(B, max_points), dtype=torch.uint8, device=dev)
+    Ro = torch.empty(B, 9, dtype=torch.float64, device=dev)
+    to = torch.empty(B, 3, dtype=torch.float64, device=dev)
+    cin = torch.empty(B, dtype=torch.float64, device=dev)
+    cout = torch.empty(B, dtype=torch.float64, device=dev)
+    npts = torch.empty(B, dtype=torch.int32, device=dev)
+    used = torch.empty(B, dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    neq = torch.empty(B, 28, dtype=torch.float64, device=dev) if return_normal_equations else None
+    sb, sy, sx, sc = fmap.stride()
+    call("fp_featuremetric_refine", ptr(fmap), sb, sy, sx, sc, gh, gw, C, W, H, ptr(cam), ptr(Rin), ptr(tin), ptr(rb), ptr(re), ptr(f32), ptr(v32),
+         int(f32.shape[0]), ptr(hp), B, max_points, int(iters), ptr(scratch), scratch.numel(), ptr(Ro), ptr(to), ptr(cin), ptr(cout), ptr(npts),
+         ptr(used), ptr(status), ptr(neq), stream())
+    out = {"R": Ro.reshape(B, 3, 3), "t": to, "cost_in": cin, "cost_out": cout, "num_points": npts, "iters_used": used, "status": status}
+    if neq is not None:
+        out["normal_eq"] = neq
+    return out
+
+
+def best_template_rows(res: MatchResult, best: Dict[str, torch.Tensor], bank: DeviceBank, det_obj: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The bank rows of the template behind each detection's best coarse pose, on the device: global template
+    g = tpl_base[object] + template_ids[b, corresp_id[b]] -> rows [tpl_off[g], tpl_off[g + 1]).  -> (row_begin, row_end,
+    has_pose): has_pose is false where no coarse pose was found or the slot holds no template (id -1)."""
+    dev = res.template_ids.device
+    B = res.template_ids.shape[0]
+    base = upload_async(torch.tensor([bank.objects[o].tpl_base for o in det_obj], dtype=torch.int64), dev)
+    cid = best["corresp_id"].to(torch.int64).reshape(B, 1)
+    tid = res.template_ids.gather(1, cid)[:, 0].to(torch.int64)
+    ok = best["found"].bool() & (tid >= 0)
+    g = torch.where(ok, base + tid, torch.zeros_like(tid))
+    off = bank.tpl_off.to(torch.int64)
+    return off[g].to(torch.int32), off[g + 1].to(torch.int32), ok
+
+
+def refine_best_coarse(res: MatchResult, best: Dict[str, torch.Tensor], bank: DeviceBank, det_obj: Optional[Sequence[int]], cameras: Sequence[Any],
+                       image_size: Tuple[int, int], iters: int = 30, return_normal_equations: bool = False) -> Dict[str, torch.Tensor]:
+    """Refines pnp_util.select_best_coarse's pose of every detection of an infer_batch(..., keep_feature_map=True) result
+    against that result's projected feature map.  cameras / image_size: the cameras PnP solved in (the crop cameras) and
+    their image size (the crop size).  -> refine_featuremetric's dict."""
+    if res.feature_map is None:
+        raise ValueError("the MatchResult carries no feature map: run infer_batch(..., keep_feature_map=True)")
+    res.wait()
+    B = res.template_ids.shape[0]
+    det_obj = [0] * B if det_obj is None else list(det_obj)
+    rb, re, ok = best_template_rows(res, best, bank, det_obj)
+    return refine_featuremetric(res.feature_map, image_size, cameras, best["R"], best["t"], rb, re, bank.feats, bank.vertices, ok, iters,
+                                return_normal_equations, max_points=bank.p_max)

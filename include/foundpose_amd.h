@@ -569,6 +569,36 @@ int fp_vsd_counts(const float* depth_test, int num_test, const float* depth_est,
                   int height, int width, const int32_t* pairs, const double* params, int num_pairs, const double* taus,
                   int num_taus, void* scratch, size_t scratch_bytes, int64_t* counts, fp_stream_t stream);
 
+/* ---- featuremetric refinement of the best coarse pose (tests/featuremetric_ref.py restates it) ----
+ * Levenberg-Marquardt on the 6-DoF pose of each of num_det detections, aligning a template's per-point features with the
+ * query's projected patch-feature map.  Device arrays:
+ *   map        fp32 [num_det, gh, gw, C] at element strides (sb, sy, sx, sc): the projected query feature map (gh, gw >= 2)
+ *   cameras    fp64 [num_det, 4]  (fx, fy, cx, cy) of the camera the pose lives in; W x H its image size (map x_m = u gw / W - 1/2)
+ *   R_in, t_in fp64 [num_det, 9], [num_det, 3]  the input pose, model -> camera (mm)
+ *   row_begin, row_end int32 [num_det]  the template's rows [row_begin, row_end) of feats [num_rows, C] fp32 and vertices
+ *              [num_rows, 3] fp32; at most max_points rows.  A range outside [0, num_rows] or longer than max_points is never read:
+ *              the call then returns FP_ERR_INVALID naming the detection (it waits for the work queued on `stream` to learn this)
+ *   has_pose   int32 [num_det]  0: skipped (status 2)
+ * Outputs: R_out [num_det, 9], t_out [num_det, 3], cost_in, cost_out fp64 [num_det], num_points (valid points), iters_used and
+ * status int32 [num_det] (0 refined, 1 no step accepted, 2 skipped: no pose, empty range or < 6 valid points; for 1 and 2 the
+ * pose is the input bit for bit); normal_eq fp64 [num_det, 28] may be null: H (upper triangle, row-major), g, E at the input pose.
+ * Valid set frozen at the input pose (z > 1 mm, inside the map), Cauchy loss with sigma^2 = mean squared residual there,
+ * lambda from 1e-3, at most `iters` (0..1000) iterations; all of them are enqueued at once.  Deterministic and bit-identical
+ * across batch compositions; no float atomics.  scratch: FP_REFINE_SCRATCH_BYTES(num_det, max_points). */
+#define FP_REFINE_CHUNK 32
+#define FP_REFINE_RECORD 32
+#define FP_REFINE_STATE_BYTES 512
+#define FP_REFINE_SCRATCH_BYTES(num_det, max_points)                                                                   \
+  ((size_t)FP_REFINE_STATE_BYTES * (size_t)(num_det) +                                                                  \
+   8 * FP_REFINE_RECORD * (size_t)(num_det) * (((size_t)(max_points) + FP_REFINE_CHUNK - 1) / FP_REFINE_CHUNK) +       \
+   (((size_t)(num_det) * (size_t)(max_points) + 7) / 8) * 8 + 8)
+int fp_featuremetric_refine(const float* map, int64_t sb, int64_t sy, int64_t sx, int64_t sc, int gh, int gw, int C, int W, int H,
+                            const double* cameras, const double* R_in, const double* t_in, const int32_t* row_begin,
+                            const int32_t* row_end, const float* feats, const float* vertices, int64_t num_rows,
+                            const int32_t* has_pose, int num_det, int max_points, int iters, void* scratch, size_t scratch_bytes,
+                            double* R_out, double* t_out, double* cost_in, double* cost_out, int32_t* num_points,
+                            int32_t* iters_used, int32_t* status, double* normal_eq, fp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
