@@ -323,23 +323,18 @@ int fp_gemm_bf16_timeline(const void* A, int lda, const void* W, int ldw, int M,
 }
 #endif
 
-static int gemm_fp8_impl(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int M_valid, const float* bias,
-                         const float* col_scale, void* out, int ldo, int epilogue, float out_scale, int* sat, fp_stream_t stream, int no_tall = 0) {
+int fp_gemm_fp8(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int M_valid, const float* bias,
+                const float* col_scale, void* out, int ldo, int epilogue, float out_scale, fp_stream_t stream) {
   FP_REQUIRE(A && W && out, "fp_gemm_fp8: null pointer");
   FP_REQUIRE(out_scale >= 0.f, "fp_gemm_fp8: out_scale must be >= 0");
   GemmBf16Args a;
   memset(&a, 0, sizeof(a));
   a.A = reinterpret_cast<const __bf16*>(A); a.lda = lda; a.W = reinterpret_cast<const __bf16*>(W); a.ldw = ldw;
   a.M = M; a.N = N; a.K = K; a.M_valid = M_valid; a.bias = bias; a.gamma = col_scale; a.out = out; a.ldo = ldo;
-  a.out_scale = out_scale; a.sat = sat; a.no_tall = no_tall;
+  a.out_scale = out_scale;
   a.tile_override = (epilogue >> 8) & 0xfff;  // tuning bits: 256 / 320 force that block tile (benchmarks, tests)
   FP_REQUIRE(a.tile_override == 0 || a.tile_override == 256 || a.tile_override == 320, "fp_gemm_fp8: bad tile override %d", a.tile_override);
   return gemm_fp8_launch(epilogue & 0xff, a, ST(stream));
-}
-
-int fp_gemm_fp8(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int M_valid, const float* bias,
-                const float* col_scale, void* out, int ldo, int epilogue, float out_scale, fp_stream_t stream) {
-  return gemm_fp8_impl(A, lda, W, ldw, M, N, K, M_valid, bias, col_scale, out, ldo, epilogue, out_scale, nullptr, stream);
 }
 
 int fp_gemm_split(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int M_valid, const float* bias, const float* gamma,
@@ -675,289 +670,206 @@ int fp_vsd_counts(const float* depth_test, int num_test, const float* depth_est,
 namespace {
 enum { VIT_FULL = 0, VIT_PREFIX = 1, VIT_LAST_SELECTED = 2 };
 struct VitSelection { const int32_t* rows; const int32_t* off; int num, max_per_img; };
+enum { QKV = 0, PROJ = 1, FC1 = 2, FC2 = 3 };   // the GEMMs of a block, in order; also the index of fp_vit_block.act_scale
+enum { VK_F32, VK_BF16, VK_F16, VK_SPLIT, VK_SPLITX, VK_FP8 };   // GEMM launchers of the forward
+struct VitEpilogues { int tokens, bias, gelu, swiglu, resid; };
+constexpr VitEpilogues kF32Epi{F32_EPI_TOKENS, F32_EPI_BIAS, F32_EPI_BIAS_GELU, F32_EPI_SWIGLU, F32_EPI_LS_RESID};
+constexpr VitEpilogues kGemmEpi{GEMM_EPI_TOKENS_F32, GEMM_EPI_BIAS_BF16, GEMM_EPI_GELU_BF16, GEMM_EPI_SWIGLU_BF16, GEMM_EPI_LS_RESID_F32};
+// folded LayerNorms: LayerScale is in the matrices; the residual GEMMs also emit the next GEMM's 16-bit operand and row sums (RESID_HILO in front
+// of the hooked block)
+constexpr VitEpilogues kFoldEpi{GEMM_EPI_TOKENS_F32, GEMM_EPI_BIAS_BF16, GEMM_EPI_GELU_BF16, GEMM_EPI_SWIGLU_BF16, GEMM_EPI_RESID_F32};
 
-// VIT_FULL: embedding + blocks 0..layer.  VIT_PREFIX: embedding + blocks 0..layer-1, leaving what block `layer` starts from:
-// the fp32 stream ws->x, its bf16 copy and the LayerNorm row sums -- or, with ws->xl set (the extractor's default, resid_hilo=True) and layer > 0,
-// the (xb, xl) pair and the row sums ONLY: ws->x is then stale (it holds the token embedding) and must not be read by a caller.  VIT_LAST_SELECTED: block `layer` alone, computed for the selected
-// tokens only (queries of the attention, rows of proj / fc1 / fc2) on top of a VIT_PREFIX run -- keys and values are all tokens.
-// first_block > 0 (precision schedules, fp_vit_forward_blocks): no embedding -- the fp32 stream of blocks 0..first_block-1 is already in ws->x (another model's
-// blocks left it there) and blocks first_block..layer of THIS model continue from it (a folded-LayerNorm model starts its chain -- 16-bit copy, row sums -- from that stream).
+GemmBf16Args zero_gemm_args() {
+  GemmBf16Args g;
+  memset(&g, 0, sizeof(g));
+  return g;
+}
+
+// VIT_FULL: embedding + blocks 0..layer.  VIT_PREFIX: embedding + blocks 0..layer-1, leaving what block `layer` starts from: the fp32
+// stream ws->x -- or, for a folded-LayerNorm model with layer > 0, the (xb, xl) pair and the LayerNorm row sums ONLY: ws->x is then stale (it
+// holds the token embedding) and must not be read by a caller.  VIT_LAST_SELECTED: block `layer` alone, computed for the selected tokens only
+// (queries of the attention, rows of proj / fc1 / fc2) on top of a VIT_PREFIX run -- keys and values are all tokens.
+//
+// Every block runs the same steps: norm 1 -> qkv -> attention -> (the selected rows) -> proj -> norm 2 -> fc1 -> fc2.  The model's family decides
+// how a step normalises, which GEMM launcher runs and what the epilogues take:
+//   fp32, bf16  LayerNorm kernel, LayerScale in the residual epilogue;
+//   folded      (bf16 / f16 with ln_fold) the LayerNorms folded into the GEMMs around them: qkv / fc1 read the 16-bit copy of the stream and
+//               normalise in their epilogue from the row sums the residual GEMMs emit (ln_finalize turns them into per-row constants);
+//   split       (f16x3 / f16f8) every GEMM / attention operand is a split-fp16 (or f16f8) row written by the kernel in front of it with a fixed
+//               power-of-two scale; b.act_scale[j] = 1 / (scale of the input x scale of the matrix) undoes both in the epilogue of GEMM j;
+//   fp8         every GEMM input is produced as e4m3 bytes (ws->a8; the hidden activations reuse ws->h) by the kernel in front of it with the
+//               block's static scales; the matrices carry a per-column dequantisation scale (gamma).
+// Residual stream, LayerNorm and softmax are fp32 in every family.
 int vit_forward_impl(const fp_vit_model* m, const fp_vit_workspace* ws, const float* images, int B, int H, int W, int layer, int mode,
-                     const VitSelection* sel, fp_stream_t stream, int first_block = 0) {
-  FP_REQUIRE(m && ws && (images || mode == VIT_LAST_SELECTED || first_block > 0) && m->blocks, "fp_vit_forward: null pointer");
-  FP_REQUIRE(first_block == 0 || (first_block >= 1 && first_block <= layer), "fp_vit_forward_blocks: first_block %d out of range (layer %d)", first_block, layer);
+                     const VitSelection* sel, fp_stream_t stream) {
+  FP_REQUIRE(m && ws && (images || mode == VIT_LAST_SELECTED) && m->blocks, "fp_vit_forward: null pointer");
   FP_REQUIRE(layer >= -1 && layer < m->depth, "fp_vit_forward: layer %d out of range (depth %d)", layer, m->depth);  // -1: token embedding only
   const int pstride = m->patch_stride > 0 ? m->patch_stride : m->patch;  // the conv stride of the patch embedding (dinov2_utils.py:364-389)
   FP_REQUIRE(pstride != m->patch || (H % m->patch == 0 && W % m->patch == 0), "fp_vit_forward: image size must be a multiple of the patch size");
   FP_REQUIRE(H >= m->patch && W >= m->patch && (pstride == m->patch || mode == VIT_FULL), "fp_vit_forward: image smaller than a patch, or token selection with stride != patch size");
-  const int D = m->dim, np = (1 + (H - m->patch) / pstride) * (1 + (W - m->patch) / pstride), ntok = 1 + m->registers + np;
+  const int D = m->dim, hid = m->hidden, np = (1 + (H - m->patch) / pstride) * (1 + (W - m->patch) / pstride), ntok = 1 + m->registers + np;
   const int Mtok = B * ntok, Mp = B * np;
   FP_REQUIRE(ws->m_pad >= Mtok && ws->m_pad % 128 == 0, "fp_vit_forward: workspace m_pad (%d) too small for %d tokens or not a multiple of 128", ws->m_pad, Mtok);
   FP_REQUIRE(ws->m_patch_pad >= Mp && ws->m_patch_pad % 128 == 0, "fp_vit_forward: workspace m_patch_pad too small");
   FP_REQUIRE(ws->patches && ws->x && ws->y && ws->qkv && ws->h, "fp_vit_forward: workspace buffer missing");
   hipStream_t st = ST(stream);
-  const bool f8 = m->weight_dtype == FP_DTYPE_FP8;  // e4m3 block matrices; activations and patch embed stay bf16
-  const bool sx = m->weight_dtype == FP_DTYPE_F16F8;  // f16f8 rows (common.hpp): the split mode with the cross terms on the fp8 pipe
-  const bool sp = m->weight_dtype == FP_DTYPE_F16X3 || sx;  // split-fp16 operands everywhere (near-exact modes): rows of 2 x halves
-  const bool h16 = m->weight_dtype == FP_DTYPE_F16;  // the "f16" mode: the bf16 pipeline (folded LayerNorms, (hi, lo) stream) on IEEE fp16 operands
-  const bool bf = m->weight_dtype == FP_DTYPE_BF16 || f8 || h16;
-  const int adt = sx ? FP_DTYPE_F16F8 : (sp ? FP_DTYPE_F16X3 : (h16 ? FP_DTYPE_F16 : (bf ? FP_DTYPE_BF16 : FP_DTYPE_F32)));
-  const int attn_dt = h16 ? FP_DTYPE_F16 : FP_DTYPE_BF16;
-  FP_REQUIRE(!h16 || m->ln_fold, "fp_vit_forward: weight_dtype FP_F16 runs the folded-LayerNorm pipeline only (ln_fold = 1, dim %% 128 == 0)");
-  FP_REQUIRE(!sx || (D % 64 == 0 && m->hidden % 64 == 0 && m->patch_k_pad % 64 == 0), "fp_vit_forward: the f16f8 mode needs dim, hidden and patch_k_pad to be multiples of 64");
-  const int em = sp ? 2 : 1;                          // stored elements per logical element of an operand row
-  FP_REQUIRE(!sp || m->patch_acc_scale > 0.f, "fp_vit_forward: the f16x3 mode needs patch_acc_scale");
-  FP_REQUIRE(!f8 || (ws->a8 && ws->m_pad % 256 == 0), "fp_vit_forward: the fp8 mode needs workspace a8 and m_pad %% 256 == 0");
-  FP_REQUIRE(!f8 || ((ws->ld_y == 0 || (ws->ld_y >= m->dim && ws->ld_y % 16 == 0)) && (ws->ld_h == 0 || (ws->ld_h >= m->hidden && ws->ld_h % 16 == 0)) &&
-                     (m->ld_w_dim == 0 || (m->ld_w_dim >= m->dim && m->ld_w_dim % 16 == 0)) && (m->ld_w_hidden == 0 || (m->ld_w_hidden >= m->hidden && m->ld_w_hidden % 16 == 0))),
-             "fp_vit_forward: fp8 row strides (bytes) must cover the row and keep 16-byte alignment");
 
-  // tokens: [cls + pos0 | registers | patch_embed(x) + pos]
-  if (mode != VIT_LAST_SELECTED && first_block == 0) {
-  if (pstride == m->patch) TRY(patchify_launch(images, B, H, W, m->patch, ws->patches, em * m->patch_k_pad, adt, st, FP_SPLIT_SCALE_ACT));
-  else TRY(patchify_strided_launch(images, B, H, W, m->patch, pstride, ws->patches, em * m->patch_k_pad, adt, st, FP_SPLIT_SCALE_ACT));
-  TRY(prefix_tokens_launch(m->prefix, 1 + m->registers, D, ws->x, B, ntok, st));
-  if (sp) {
-    GemmBf16Args g;
-    memset(&g, 0, sizeof(g));
-    g.A = reinterpret_cast<const __bf16*>(ws->patches); g.lda = 2 * m->patch_k_pad;
-    g.W = reinterpret_cast<const __bf16*>(m->patch_w); g.ldw = 2 * m->patch_k_pad;
-    g.M = ws->m_patch_pad; g.N = D; g.K = m->patch_k_pad; g.M_valid = Mp; g.bias = m->patch_b;
-    g.out = ws->x; g.ldo = D; g.pos = m->pos_patch; g.tok_np = np; g.tok_n = ntok; g.tok_skip = 1 + m->registers;
-    g.acc_scale = m->patch_acc_scale;
-    TRY(sx ? gemm_splitx_launch(GEMM_EPI_TOKENS_F32, g, st) : gemm_split_launch(GEMM_EPI_TOKENS_F32, g, st));
-  } else if (bf) {
-    GemmBf16Args g;
-    memset(&g, 0, sizeof(g));
-    g.A = reinterpret_cast<const __bf16*>(ws->patches); g.lda = m->patch_k_pad;
-    g.W = reinterpret_cast<const __bf16*>(m->patch_w); g.ldw = m->patch_k_pad;
-    g.M = ws->m_patch_pad; g.N = D; g.K = m->patch_k_pad; g.M_valid = Mp; g.bias = m->patch_b;
-    g.out = ws->x; g.ldo = D; g.pos = m->pos_patch; g.tok_np = np; g.tok_n = ntok; g.tok_skip = 1 + m->registers;
-    TRY(h16 ? gemm_f16_launch(GEMM_EPI_TOKENS_F32, g, st) : gemm_bf16_launch(GEMM_EPI_TOKENS_F32, g, st));
-  } else {
-    F32TileArgs a = zero_tile_args();
-    a.A = reinterpret_cast<const float*>(ws->patches); a.lda = m->patch_k_pad;
-    a.B = reinterpret_cast<const float*>(m->patch_w); a.ldb = m->patch_k_pad; a.K = m->patch_k_pad; a.M = Mp; a.N = D;
-    a.out = ws->x; a.ldo = D; a.bias = m->patch_b; a.pos = m->pos_patch; a.tok_np = np; a.tok_n = ntok;
-    a.tok_skip = 1 + m->registers;
-    TRY(f32_tile_launch(F32_EPI_TOKENS, a, Mp, D, 1, st));
-  }
-  }
-
-  // row strides of the bf16 / fp32 operands (fp8 mode: dense)
-  const int ldy = (!f8 && ws->ld_y) ? ws->ld_y : em * D, ldh = (!f8 && ws->ld_h) ? ws->ld_h : em * m->hidden;
-  const int ldq = ws->ld_qkv ? ws->ld_qkv : em * 3 * D;
-  const int ldwd = (!f8 && m->ld_w_dim) ? m->ld_w_dim : em * D, ldwh = (!f8 && m->ld_w_hidden) ? m->ld_w_hidden : em * m->hidden;
-  FP_REQUIRE(ldy >= em * D && ldh >= em * m->hidden && ldwd >= em * D && ldwh >= em * m->hidden && ldy % 8 == 0 && ldh % 8 == 0 && ldwd % 8 == 0 && ldwh % 8 == 0 &&
-                 ldq >= em * 3 * D && ldq % 8 == 0,
-             "fp_vit_forward: operand row strides must cover the row and keep 16-byte alignment");
-  LayerNormArgs ln;
-  memset(&ln, 0, sizeof(ln));
-  ln.sat = ws->sat;
-  ln.x = ws->x; ln.ld_x = D; ln.eps = 1e-6f; ln.out = ws->y; ln.ld_out = ldy; ln.out_dtype = adt;
-  ln.dim = D; ln.out_rows = Mtok; ln.out_rows_per_img = Mtok; ln.in_rows_per_img = Mtok; ln.in_skip = 0;
-  AttnArgs at;
-  memset(&at, 0, sizeof(at));
-  at.qkv = ws->qkv; at.ld_qkv = ldq; at.out = ws->y; at.ld_out = ldy;
-  at.batch = B; at.n_tok = ntok; at.dim = D; at.heads = m->heads;
-  at.sat = ws->sat;
-
-  // LayerNorm folded into the GEMMs (bf16 blocks): see fp_vit_model.ln_fold.  The chain starts from the token embedding.
+  // ---- the plan of this call: family, operand type, row strides, launchers
+  const int wdt = m->weight_dtype;
+  const bool f8 = wdt == FP_DTYPE_FP8;      // e4m3 block matrices; activations and patch embed stay bf16
+  const bool sx = wdt == FP_DTYPE_F16F8;    // f16f8 rows (common.hpp): the split mode with the cross terms on the fp8 pipe
+  const bool sp = wdt == FP_DTYPE_F16X3 || sx;
+  const bool h16 = wdt == FP_DTYPE_F16;     // the "f16" mode: the folded bf16 pipeline (folded LayerNorms, (hi, lo) stream) on IEEE fp16 operands
+  const bool bf = wdt == FP_DTYPE_BF16 || f8 || h16;
   const bool fold = m->ln_fold && bf && !f8;
-  int ln_parts = 1;
-  float2* stats = reinterpret_cast<float2*>(ws->stats);
-  if (fold) {
-    FP_REQUIRE(ws->xb && ws->stats, "fp_vit_forward: ln_fold needs workspace xb and stats");
-    FP_REQUIRE(D % 128 == 0, "fp_vit_forward: ln_fold needs dim %% 128 == 0");
-    ln_parts = D / 128;  // one partial sum per 128-column group of the residual GEMMs, whatever tile they run with
-    if (layer >= 0 && mode != VIT_LAST_SELECTED) TRY(rowstats_cast_launch(ws->x, Mtok, D, ws->xb, ldy, stats, ws->m_pad, ln_parts, st, ws->xl, h16));
-  }
-  // Blocks in FRONT of the hooked one keep the residual stream as (hi, lo) bf16 arrays (ws->xb, ws->xl) instead of fp32 + a bf16 copy: the
-  // residual GEMMs then read 4 and write 4 bytes per element instead of 4 + 6 (hi IS the next GEMM's A operand).  16 mantissa bits per update
-  // against the 8 of the bf16 operands everything is multiplied in.  The hooked block itself runs on an fp32 stream rebuilt from the pair
-  // (all rows, or the selected rows only), so the engine's token-selected form and the full form stay bit-identical.
-  const bool hilo = fold && ws->xl != nullptr;
+  const int adt = sx ? FP_DTYPE_F16F8 : (sp ? FP_DTYPE_F16X3 : (h16 ? FP_DTYPE_F16 : (bf ? FP_DTYPE_BF16 : FP_DTYPE_F32)));
+  const int em = sp ? 2 : 1;                // stored elements per logical element of an operand row
+  // row strides of the operands and matrices, 0 = dense: elements (split rows: halves); the fp8 family's e4m3 operands and matrices: bytes
+  const int ldy = ws->ld_y ? ws->ld_y : em * D, ldh = ws->ld_h ? ws->ld_h : em * hid, ldq = ws->ld_qkv ? ws->ld_qkv : em * 3 * D;
+  const int ldwd = m->ld_w_dim ? m->ld_w_dim : em * D, ldwh = m->ld_w_hidden ? m->ld_w_hidden : em * hid;
+  FP_REQUIRE(!h16 || m->ln_fold, "fp_vit_forward: weight_dtype FP_F16 runs the folded-LayerNorm pipeline only (ln_fold = 1, dim %% 128 == 0)");
+  FP_REQUIRE(!sx || (D % 64 == 0 && hid % 64 == 0 && m->patch_k_pad % 64 == 0), "fp_vit_forward: the f16f8 mode needs dim, hidden and patch_k_pad to be multiples of 64");
+  FP_REQUIRE(!sp || m->patch_acc_scale > 0.f, "fp_vit_forward: the f16x3 mode needs patch_acc_scale");
+  FP_REQUIRE(!f8 || (ws->a8 && ws->m_pad % 256 == 0 && D % 128 == 0 && hid % 128 == 0), "fp_vit_forward: the fp8 mode needs workspace a8, m_pad %% 256 == 0 and dim, hidden multiples of 128");
+  FP_REQUIRE(!f8 || (ldy % 16 == 0 && ldh % 16 == 0 && ldwd % 16 == 0 && ldwh % 16 == 0), "fp_vit_forward: fp8 row strides (bytes) must keep 16-byte alignment");
+  FP_REQUIRE(ldy >= em * D && ldh >= em * hid && ldq >= em * 3 * D && ldwd >= em * D && ldwh >= em * hid &&
+                 ldy % 8 == 0 && ldh % 8 == 0 && ldq % 8 == 0 && ldwd % 8 == 0 && ldwh % 8 == 0,
+             "fp_vit_forward: operand row strides must cover the row and keep 16-byte alignment");
+  FP_REQUIRE(!fold || (ws->xb && ws->xl && ws->stats), "fp_vit_forward: ln_fold needs workspace xb, xl and stats");
+  FP_REQUIRE(!fold || D % 128 == 0, "fp_vit_forward: ln_fold needs dim %% 128 == 0");
   FP_REQUIRE(mode == VIT_FULL || fold || sp || f8, "fp_vit_forward_prefix / fp_vit_block_selected: bf16 model with ln_fold, an fp8 or an f16x3 model");
-  float2* ln_row = stats + (size_t)ln_parts * ws->m_pad;  // (rstd, mean * rstd) per row, behind the partial-sum slots
-  int rows_valid = Mtok, rows_pad = ws->m_pad;  // the selected tail of the hooked block narrows these to the compact rows
-  // (the residual GEMM files its partial sums with a stride of ITS row count: rows_pad)
-  auto finalize = [&]() -> int { return ln_finalize_launch(stats, ln_parts, rows_pad, rows_valid, D, 1e-6f, ln_row, st); };
-  auto gemm = [&](const void* A, int lda, const void* Wt, int ldw, int N, int K, const float* bias, const float* gamma, void* out, int ldo, int epi,
-                  const float* colsum, bool produce, float w_inv_scale = 0.f) -> int {
-    GemmBf16Args g;
-    memset(&g, 0, sizeof(g));
-    g.A = reinterpret_cast<const __bf16*>(A); g.lda = lda; g.W = reinterpret_cast<const __bf16*>(Wt); g.ldw = ldw;
-    g.M = rows_pad; g.N = N; g.K = K; g.M_valid = rows_valid; g.bias = bias; g.gamma = gamma; g.out = out; g.ldo = ldo;
-    g.no_tall = (m->flags & FP_VIT_NO_TALL_TILES) ? 1 : 0;
-    g.acc_scale = h16 ? w_inv_scale : 0.f;   // FP_F16: 1 / (power-of-two scale of this weight matrix), fp_vit_block.act_scale[j]; 0 = unscaled
-    if (colsum) { g.ln_stats = ln_row; g.ln_parts = ln_parts; g.ln_eps = 1e-6f; g.colsum = colsum; }
-    if (produce) { g.xb = reinterpret_cast<__bf16*>(ws->xb); g.ld_xb = ldy; g.stats_out = stats; g.xl = reinterpret_cast<__bf16*>(ws->xl); }
-    return h16 ? gemm_f16_launch(epi, g, st) : gemm_bf16_launch(epi, g, st);
+  const int kernel = fold ? (h16 ? VK_F16 : VK_BF16) : sp ? (sx ? VK_SPLITX : VK_SPLIT) : f8 ? VK_FP8 : bf ? VK_BF16 : VK_F32;
+  const VitEpilogues& epi = kernel == VK_F32 ? kF32Epi : fold ? kFoldEpi : kGemmEpi;
+  const int role_epi[4] = {epi.bias, epi.resid, m->ffn_swiglu ? epi.swiglu : epi.gelu, epi.resid};  // fc1 with SwiGLU: fc1_w rows interleaved (x1_j, x2_j)
+  void* const norm_out = fold ? ws->xb : f8 ? ws->a8 : ws->y;   // the A operand of qkv and fc1
+  void* const attn_out = f8 ? ws->a8 : ws->y;                    // the A operand of proj
+  const int attn_dt = kernel == VK_F32 ? FP_DTYPE_F32 : sp ? FP_DTYPE_F16X3 : h16 ? FP_DTYPE_F16 : FP_DTYPE_BF16;
+  // folded LayerNorms: one partial sum per 128-column group of the residual GEMMs, whatever tile they run with; then (rstd, mean * rstd) per row
+  const int ln_parts = D / 128;
+  float2* stats = reinterpret_cast<float2*>(ws->stats);
+  float2* ln_row = fold ? stats + (size_t)ln_parts * ws->m_pad : nullptr;
+
+  // the rows every GEMM and norm runs on: the patch rows of the embedding, then all tokens, then (VIT_LAST_SELECTED) the selected ones
+  int rows_valid = Mp, rows_pad = ws->m_patch_pad;
+  auto gemm = [&](int k, int e, GemmBf16Args g) -> int {
+    g.M = rows_pad; g.M_valid = rows_valid;
+    switch (k) {
+      case VK_BF16: return gemm_bf16_launch(e, g, st);
+      case VK_F16: return gemm_f16_launch(e, g, st);
+      case VK_SPLIT: return gemm_split_launch(e, g, st);
+      case VK_SPLITX: return gemm_splitx_launch(e, g, st);
+      case VK_FP8: return gemm_fp8_launch(e, g, st);
+    }
+    F32TileArgs a = zero_tile_args();   // the fp32 tile takes the valid rows only
+    a.A = reinterpret_cast<const float*>(g.A); a.lda = g.lda; a.B = reinterpret_cast<const float*>(g.W); a.ldb = g.ldw;
+    a.K = g.K; a.M = rows_valid; a.N = g.N; a.out = static_cast<float*>(g.out); a.ldo = g.ldo; a.bias = g.bias; a.gamma = g.gamma;
+    a.pos = g.pos; a.tok_np = g.tok_np; a.tok_n = g.tok_n; a.tok_skip = g.tok_skip;
+    return f32_tile_launch(e, a, rows_valid, g.N, 1, st);
   };
 
-  const int i_first = mode == VIT_LAST_SELECTED ? layer : first_block, i_last = mode == VIT_PREFIX ? layer - 1 : layer;
+  // tokens: [cls + pos0 | registers | patch_embed(x) + pos]
+  if (mode != VIT_LAST_SELECTED) {
+    if (pstride == m->patch) TRY(patchify_launch(images, B, H, W, m->patch, ws->patches, em * m->patch_k_pad, adt, st, FP_SPLIT_SCALE_ACT));
+    else TRY(patchify_strided_launch(images, B, H, W, m->patch, pstride, ws->patches, em * m->patch_k_pad, adt, st, FP_SPLIT_SCALE_ACT));
+    TRY(prefix_tokens_launch(m->prefix, 1 + m->registers, D, ws->x, B, ntok, st));
+    GemmBf16Args g = zero_gemm_args();
+    g.A = reinterpret_cast<const __bf16*>(ws->patches); g.lda = em * m->patch_k_pad;
+    g.W = reinterpret_cast<const __bf16*>(m->patch_w); g.ldw = em * m->patch_k_pad;
+    g.N = D; g.K = m->patch_k_pad; g.bias = m->patch_b; g.out = ws->x; g.ldo = D;
+    g.pos = m->pos_patch; g.tok_np = np; g.tok_n = ntok; g.tok_skip = 1 + m->registers;
+    g.acc_scale = sp ? m->patch_acc_scale : 0.f;
+    TRY(gemm(f8 ? VK_BF16 : kernel, epi.tokens, g));   // (the fp8 family embeds in bf16)
+    // the folded chain starts from the token embedding: its 16-bit copy (hi, lo) and row sums
+    if (fold && layer >= 0) TRY(rowstats_cast_launch(ws->x, Mtok, D, ws->xb, ldy, stats, ws->m_pad, ln_parts, st, ws->xl, h16));
+  }
+  rows_valid = Mtok, rows_pad = ws->m_pad;
+
+  // x (rows xr) -> the A operand of qkv (j = QKV) or fc1 (j = FC1).  Folded: the row constants of the GEMM's normalising epilogue (the residual
+  // GEMM filed its partial sums with a stride of ITS row count: rows_pad).
+  auto norm = [&](const fp_vit_block& b, int j, const float* xr) -> int {
+    if (fold) return ln_finalize_launch(stats, ln_parts, rows_pad, rows_valid, D, 1e-6f, ln_row, st);
+    LayerNormArgs ln;
+    memset(&ln, 0, sizeof(ln));
+    ln.x = xr; ln.ld_x = D; ln.weight = j == QKV ? b.ln1_w : b.ln2_w; ln.bias = j == QKV ? b.ln1_b : b.ln2_b; ln.eps = 1e-6f;
+    ln.out = norm_out; ln.ld_out = ldy; ln.out_dtype = f8 ? FP_DTYPE_FP8 : adt;
+    ln.out_scale = sp ? FP_SPLIT_SCALE_ACT : f8 ? b.act_scale[j] : 0.f;
+    ln.dim = D; ln.out_rows = ln.out_rows_per_img = ln.in_rows_per_img = rows_valid;
+    ln.sat = ws->sat;
+    return layernorm_launch(ln, st);
+  };
+  auto attention = [&](const fp_vit_block& b) -> int {
+    AttnArgs at;
+    memset(&at, 0, sizeof(at));
+    at.qkv = ws->qkv; at.ld_qkv = ldq; at.out = attn_out; at.ld_out = ldy;
+    at.batch = B; at.n_tok = ntok; at.dim = D; at.heads = m->heads;
+    at.sat = ws->sat;
+    // f16f8: q | k | v stay split-fp16 rows (the attention's own three-MFMA products), its output is proj's f16f8 operand
+    if (sp) at.in_scale = FP_SPLIT_SCALE_QKV, at.out_scale = FP_SPLIT_SCALE_ACT, at.out_fmt = sx ? 1 : 0;
+    if (f8) at.out_fp8_scale = b.act_scale[PROJ];
+    if (sel) at.sel_rows = sel->rows, at.sel_off = sel->off, at.max_sel = sel->max_per_img;
+    return attn_launch(at, attn_dt, st);
+  };
+  // The hooked block for the selected tokens only.  K and V need every token: norm 1 and the qkv GEMM run on all rows (its Q columns of
+  // unselected rows are the only wasted work); attention takes its queries through the index list and writes compact rows; from there on every
+  // operand has num_sel rows, and row r of every compact buffer is token sel->rows[r].  The per-row arithmetic (GEMM chains, 128-column stat
+  // groups, static scales) does not depend on where a row sits, so the selected rows carry the bits the full block would have given them.
+  auto select_rows = [&](float*& xr) -> int {
+    xr = reinterpret_cast<float*>(ws->qkv);   // qkv is dead after the attention: [num_sel, D] fp32 rows of the stream
+    if (fold && layer > 0) TRY(hilo_rows_launch(ws->xb, ws->xl, ldy, sel->rows, sel->num, D, xr, st, h16));   // the blocks in front left (hi, lo) pairs
+    else TRY(gather_rows_launch(ws->x, sel->rows, sel->num, D, xr, st));
+    const int pad = (sel->num + 255) / 256 * 256;
+    rows_valid = sel->num, rows_pad = pad < ws->m_pad ? pad : ws->m_pad;
+    return FP_OK;
+  };
+  // GEMM j of block b; xr: the residual rows; pair: a folded block in front of the hooked one (the stream is the (hi, lo) pair)
+  auto block_gemm = [&](const fp_vit_block& b, int j, float* xr, bool pair) -> int {
+    const void* const Wt[4] = {b.qkv_w, b.proj_w, b.fc1_w, b.fc2_w};
+    const float* const bias[4] = {b.qkv_b, b.proj_b, b.fc1_b, b.fc2_b};
+    const float* const col_scale[4] = {b.qkv_s, b.proj_s, b.fc1_s, b.fc2_s};
+    const bool resid = j == PROJ || j == FC2;
+    GemmBf16Args g = zero_gemm_args();
+    g.A = reinterpret_cast<const __bf16*>(j == FC2 ? ws->h : j == PROJ ? attn_out : norm_out); g.lda = j == FC2 ? ldh : ldy;
+    g.W = reinterpret_cast<const __bf16*>(Wt[j]); g.ldw = j == FC2 ? ldwh : ldwd;
+    g.N = j == QKV ? 3 * D : j == FC1 ? (m->ffn_swiglu ? 2 : 1) * hid : D; g.K = j == FC2 ? hid : D;
+    g.bias = bias[j];
+    g.out = j == QKV ? ws->qkv : j == FC1 ? ws->h : xr; g.ldo = j == QKV ? ldq : j == FC1 ? ldh : D;
+    if (f8) g.gamma = col_scale[j];
+    else if (!fold && resid) g.gamma = j == PROJ ? b.ls1 : b.ls2;
+    if (sp || h16) g.acc_scale = b.act_scale[j];   // f16: 1 / (power-of-two scale of the matrix)
+    if (sp) g.out_scale = j == QKV ? FP_SPLIT_SCALE_QKV : j == FC1 ? FP_SPLIT_SCALE_HID : 0.f;
+    if (f8 && j == FC1) g.out_scale = b.act_scale[FC2];   // the hidden activations leave as fc2's e4m3 input
+    if (sp || f8) g.sat = ws->sat;
+    if (fold && !resid) {
+      g.ln_stats = ln_row; g.ln_parts = ln_parts; g.ln_eps = 1e-6f; g.colsum = j == QKV ? b.qkv_colsum : b.fc1_colsum;
+    }
+    if (fold && resid && (j == PROJ || pair)) {   // the next norm's row sums and 16-bit operand (fc2 of the hooked block feeds no norm)
+      g.xb = reinterpret_cast<__bf16*>(ws->xb); g.ld_xb = ldy; g.stats_out = stats; g.xl = reinterpret_cast<__bf16*>(ws->xl);
+    }
+    FP_REQUIRE(g.W && (g.gamma || fold || !resid) && g.out_scale >= 0.f, "fp_vit_forward: GEMM %d: matrix or LayerScale missing, or a negative output scale", j);
+    return gemm(kernel, resid && pair ? GEMM_EPI_RESID_HILO : role_epi[j], g);
+  };
+
+  const int i_first = mode == VIT_LAST_SELECTED ? layer : 0, i_last = mode == VIT_PREFIX ? layer - 1 : layer;
   for (int i = i_first; i <= i_last; ++i) {
     const fp_vit_block& b = m->blocks[i];
-    if (fold && mode == VIT_LAST_SELECTED) {
-      // The hooked block for the selected tokens only.  K and V need every token: LayerNorm constants and the qkv GEMM run on
-      // all rows (its Q columns of unselected rows are the only wasted work); attention takes its queries through the index
-      // list and writes compact rows; from there on every operand has num_sel rows.  Row r of every compact buffer is
-      // token sel->rows[r]; the per-row arithmetic (GEMM chains, 128-column stat groups) does not depend on where a row sits,
-      // so the selected rows carry the bits the full block would have given them.
-      FP_REQUIRE(b.qkv_colsum && b.fc1_colsum, "fp_vit_forward: ln_fold needs the column sums of qkv_w / fc1_w");
-      TRY(finalize());
-      TRY(gemm(ws->xb, ldy, b.qkv_w, ldwd, 3 * D, D, b.qkv_b, nullptr, ws->qkv, ldq, GEMM_EPI_BIAS_BF16, b.qkv_colsum, false, b.act_scale[0]));
-      AttnArgs as = at;
-      as.sel_rows = sel->rows; as.sel_off = sel->off; as.max_sel = sel->max_per_img;
-      TRY(attn_launch(as, attn_dt, st));
-      float* xs = reinterpret_cast<float*>(ws->qkv);  // qkv is dead after the attention: [num_sel, D] fp32 rows of the stream
-      if (hilo && layer > 0) TRY(hilo_rows_launch(ws->xb, ws->xl, ldy, sel->rows, sel->num, D, xs, st, h16));   // the blocks in front left (hi, lo) pairs
-      else TRY(gather_rows_launch(ws->x, sel->rows, sel->num, D, xs, st));
-      rows_valid = sel->num;
-      rows_pad = (sel->num + 255) / 256 * 256 < ws->m_pad ? (sel->num + 255) / 256 * 256 : ws->m_pad;
-      TRY(gemm(ws->y, ldy, b.proj_w, ldwd, D, D, b.proj_b, nullptr, xs, D, GEMM_EPI_RESID_F32, nullptr, true, b.act_scale[1]));
-      TRY(finalize());
-      if (m->ffn_swiglu)
-        TRY(gemm(ws->xb, ldy, b.fc1_w, ldwd, 2 * m->hidden, D, b.fc1_b, nullptr, ws->h, ldh, GEMM_EPI_SWIGLU_BF16, b.fc1_colsum, false, b.act_scale[2]));
-      else
-        TRY(gemm(ws->xb, ldy, b.fc1_w, ldwd, m->hidden, D, b.fc1_b, nullptr, ws->h, ldh, GEMM_EPI_GELU_BF16, b.fc1_colsum, false, b.act_scale[2]));
-      TRY(gemm(ws->h, ldh, b.fc2_w, ldwh, D, m->hidden, b.fc2_b, nullptr, xs, D, GEMM_EPI_RESID_F32, nullptr, false, b.act_scale[3]));
-      continue;
-    }
-    if (fold) {
-      // x += ls1 * proj(attn(ln1(x))): qkv reads bf16(x) and normalises in its epilogue; proj refreshes bf16(x) + row sums
-      FP_REQUIRE(b.qkv_colsum && b.fc1_colsum, "fp_vit_forward: ln_fold needs the column sums of qkv_w / fc1_w");
-      const bool pair = hilo && i < layer;            // a block in front of the hooked one: (hi, lo) stream
-      const int resid = pair ? GEMM_EPI_RESID_HILO : GEMM_EPI_RESID_F32;
-      if (hilo && i == layer && i > 0) TRY(hilo_rows_launch(ws->xb, ws->xl, ldy, nullptr, Mtok, D, ws->x, st, h16));   // VIT_FULL: the hooked block's fp32 stream, all rows
-      TRY(finalize());
-      TRY(gemm(ws->xb, ldy, b.qkv_w, ldwd, 3 * D, D, b.qkv_b, nullptr, ws->qkv, ldq, GEMM_EPI_BIAS_BF16, b.qkv_colsum, false, b.act_scale[0]));
-      TRY(attn_launch(at, attn_dt, st));
-      TRY(gemm(ws->y, ldy, b.proj_w, ldwd, D, D, b.proj_b, nullptr, ws->x, D, resid, nullptr, true, b.act_scale[1]));
-      // x += ls2 * fc2(act(fc1(ln2(x))))
-      TRY(finalize());
-      if (m->ffn_swiglu)
-        TRY(gemm(ws->xb, ldy, b.fc1_w, ldwd, 2 * m->hidden, D, b.fc1_b, nullptr, ws->h, ldh, GEMM_EPI_SWIGLU_BF16, b.fc1_colsum, false, b.act_scale[2]));
-      else
-        TRY(gemm(ws->xb, ldy, b.fc1_w, ldwd, m->hidden, D, b.fc1_b, nullptr, ws->h, ldh, GEMM_EPI_GELU_BF16, b.fc1_colsum, false, b.act_scale[2]));
-      TRY(gemm(ws->h, ldh, b.fc2_w, ldwh, D, m->hidden, b.fc2_b, nullptr, ws->x, D, resid, nullptr, i < layer, b.act_scale[3]));
-      continue;
-    }
+    FP_REQUIRE(!fold || (b.qkv_colsum && b.fc1_colsum), "fp_vit_forward: ln_fold needs the column sums of qkv_w / fc1_w");
+    // Folded blocks in FRONT of the hooked one keep the residual stream as (hi, lo) 16-bit arrays (ws->xb, ws->xl) instead of fp32 + a 16-bit
+    // copy: the residual GEMMs then read 4 and write 4 bytes per element instead of 4 + 6 (hi IS the next GEMM's A operand), 16 mantissa bits
+    // per update.  The hooked block itself runs on an fp32 stream rebuilt from the pair (all rows, or the selected rows only), so the engine's
+    // token-selected form and the full form stay bit-identical.
+    const bool pair = fold && i < layer;
+    float* xr = ws->x;   // the residual rows the block updates
+    if (fold && mode == VIT_FULL && i == layer && i > 0) TRY(hilo_rows_launch(ws->xb, ws->xl, ldy, nullptr, Mtok, D, ws->x, st, h16));
     // x += ls1 * proj(attn(ln1(x)))
-    ln.weight = b.ln1_w; ln.bias = b.ln1_b;
-    if (sp) {
-      // f16x3 block: every GEMM / attention operand is a split-fp16 row written by the kernel in front of it (LayerNorm, the
-      // qkv / GELU / SwiGLU epilogues, the attention kernel) with a fixed power-of-two scale; b.act_scale[j] = 1 / (scale of the
-      // input x scale of the matrix) undoes both in the epilogue of GEMM j.  The residual stream, LayerNorm and softmax are fp32.
-      // mode VIT_LAST_SELECTED (the hooked block for the selected tokens only, as in the bf16 branch above): LayerNorm 1 and the qkv
-      // GEMM on all rows (keys / values need every token), attention takes its queries through the index list and writes compact
-      // rows, and from there on every operand has num_sel rows: the residual rows are gathered into the dead qkv buffer, proj /
-      // LayerNorm 2 / fc1 / fc2 run on them.  Per-row arithmetic does not depend on where a row sits: the same bits as the full block.
-      const bool selected = mode == VIT_LAST_SELECTED;
-      auto sgemm = [&](const void* A, int lda, const void* Wt, int ldw, int N, int K, const float* bias, const float* gamma, void* out, int ldo, int epi,
-                       float acc_scale, float out_scale) -> int {
-        GemmBf16Args g;
-        memset(&g, 0, sizeof(g));
-        g.A = reinterpret_cast<const __bf16*>(A); g.lda = lda; g.W = reinterpret_cast<const __bf16*>(Wt); g.ldw = ldw;
-        g.M = rows_pad; g.N = N; g.K = K; g.M_valid = rows_valid; g.bias = bias; g.gamma = gamma; g.out = out; g.ldo = ldo;
-        g.acc_scale = acc_scale; g.out_scale = out_scale; g.sat = ws->sat;
-        return sx ? gemm_splitx_launch(epi, g, st) : gemm_split_launch(epi, g, st);
-      };
-      ln.out_scale = FP_SPLIT_SCALE_ACT;
-      TRY(layernorm_launch(ln, st));
-      TRY(sgemm(ws->y, ldy, b.qkv_w, ldwd, 3 * D, D, b.qkv_b, nullptr, ws->qkv, ldq, GEMM_EPI_BIAS_BF16, b.act_scale[0], FP_SPLIT_SCALE_QKV));
-      AttnArgs as = at;
-      as.in_scale = FP_SPLIT_SCALE_QKV; as.out_scale = FP_SPLIT_SCALE_ACT;
-      as.out_fmt = sx ? 1 : 0;   // f16f8: q | k | v stay split-fp16 rows (the attention's own three-MFMA products), its output is proj's f16f8 operand
-      float* xr = ws->x;  // the residual rows the rest of the block updates
-      if (selected) {
-        as.sel_rows = sel->rows; as.sel_off = sel->off; as.max_sel = sel->max_per_img;
-        TRY(attn_launch(as, FP_DTYPE_F16X3, st));
-        xr = reinterpret_cast<float*>(ws->qkv);  // qkv is dead after the attention: [num_sel, D] fp32 rows of the stream
-        TRY(gather_rows_launch(ws->x, sel->rows, sel->num, D, xr, st));
-        rows_valid = sel->num;
-        rows_pad = (sel->num + 255) / 256 * 256 < ws->m_pad ? (sel->num + 255) / 256 * 256 : ws->m_pad;
-        ln.x = xr; ln.out_rows = rows_valid; ln.out_rows_per_img = rows_valid; ln.in_rows_per_img = rows_valid;
-      } else {
-        TRY(attn_launch(as, FP_DTYPE_F16X3, st));
-      }
-      TRY(sgemm(ws->y, ldy, b.proj_w, ldwd, D, D, b.proj_b, b.ls1, xr, D, GEMM_EPI_LS_RESID_F32, b.act_scale[1], 0.f));
-      ln.weight = b.ln2_w; ln.bias = b.ln2_b;
-      TRY(layernorm_launch(ln, st));
-      if (m->ffn_swiglu)
-        TRY(sgemm(ws->y, ldy, b.fc1_w, ldwd, 2 * m->hidden, D, b.fc1_b, nullptr, ws->h, ldh, GEMM_EPI_SWIGLU_BF16, b.act_scale[2], FP_SPLIT_SCALE_HID));
-      else
-        TRY(sgemm(ws->y, ldy, b.fc1_w, ldwd, m->hidden, D, b.fc1_b, nullptr, ws->h, ldh, GEMM_EPI_GELU_BF16, b.act_scale[2], FP_SPLIT_SCALE_HID));
-      TRY(sgemm(ws->h, ldh, b.fc2_w, ldwh, D, m->hidden, b.fc2_b, b.ls2, xr, D, GEMM_EPI_LS_RESID_F32, b.act_scale[3], 0.f));
-      continue;
-    }
-    if (f8) {
-      // fp8 block: every GEMM input is produced as e4m3 bytes by the kernel in front of it -- LayerNorm, attention and
-      // the GELU / SwiGLU epilogue quantise with the block's static scales on their way out (ws->a8; the hidden
-      // activations reuse ws->h as a byte buffer) -- so the four GEMMs run on the fp8 MFMA with no extra pass.
-      // row strides in bytes (= fp8 elements): a8 [m_pad, ld8y], hidden bytes [m_pad, ld8h], matrices [N, ld8wd / ld8wh]
-      const int ld8y = ws->ld_y ? ws->ld_y : D, ld8h = ws->ld_h ? ws->ld_h : m->hidden;
-      const int ld8wd = m->ld_w_dim ? m->ld_w_dim : D, ld8wh = m->ld_w_hidden ? m->ld_w_hidden : m->hidden;
-      // mode VIT_LAST_SELECTED (the hooked block for the selected tokens only, as in the bf16 and f16x3 branches): LayerNorm 1 and the qkv GEMM on
-      // all rows (keys / values need every token), attention takes its queries through the index list and writes compact e4m3 rows, the residual
-      // rows are gathered into the dead qkv buffer, and proj / LayerNorm 2 / fc1 / fc2 run on num_sel rows.  Per-row arithmetic (static scales,
-      // k-ordered GEMM chains) does not depend on where a row sits: the selected rows carry the bits the full block would have given them.
-      const bool selected = mode == VIT_LAST_SELECTED;
-      LayerNormArgs l8 = ln;
-      l8.out = ws->a8; l8.ld_out = ld8y; l8.out_dtype = FP_DTYPE_FP8; l8.out_scale = b.act_scale[0];
-      TRY(layernorm_launch(l8, st));
-      TRY(gemm_fp8_impl(ws->a8, ld8y, b.qkv_w, ld8wd, ws->m_pad, 3 * D, D, Mtok, b.qkv_b, b.qkv_s, ws->qkv, ldq, GEMM_EPI_BIAS_BF16, 0.f, ws->sat, stream, (m->flags & FP_VIT_NO_TALL_TILES) ? 1 : 0));
-      AttnArgs a8 = at;
-      a8.out = ws->a8; a8.ld_out = ld8y; a8.out_fp8_scale = b.act_scale[1];
-      float* xr = ws->x;  // the residual rows the rest of the block updates
-      int rv = Mtok, rp = ws->m_pad;
-      if (selected) {
-        a8.sel_rows = sel->rows; a8.sel_off = sel->off; a8.max_sel = sel->max_per_img;
-        TRY(attn_launch(a8, FP_DTYPE_BF16, st));
-        xr = reinterpret_cast<float*>(ws->qkv);  // qkv is dead after the attention: [num_sel, D] fp32 rows of the stream
-        TRY(gather_rows_launch(ws->x, sel->rows, sel->num, D, xr, st));
-        rv = sel->num;
-        rp = (sel->num + 255) / 256 * 256 < ws->m_pad ? (sel->num + 255) / 256 * 256 : ws->m_pad;
-        l8.x = xr; l8.out_rows = rv; l8.out_rows_per_img = rv; l8.in_rows_per_img = rv;
-      } else {
-        TRY(attn_launch(a8, FP_DTYPE_BF16, st));
-      }
-      TRY(gemm_fp8_impl(ws->a8, ld8y, b.proj_w, ld8wd, rp, D, D, rv, b.proj_b, b.proj_s, xr, D, GEMM_EPI_LS_RESID_F32, 0.f, ws->sat, stream, (m->flags & FP_VIT_NO_TALL_TILES) ? 1 : 0));
-      l8.weight = b.ln2_w; l8.bias = b.ln2_b; l8.out_scale = b.act_scale[2];
-      TRY(layernorm_launch(l8, st));
-      if (m->ffn_swiglu)
-        TRY(gemm_fp8_impl(ws->a8, ld8y, b.fc1_w, ld8wd, rp, 2 * m->hidden, D, rv, b.fc1_b, b.fc1_s, ws->h, ld8h, GEMM_EPI_SWIGLU_BF16, b.act_scale[3], ws->sat, stream, (m->flags & FP_VIT_NO_TALL_TILES) ? 1 : 0));
-      else
-        TRY(gemm_fp8_impl(ws->a8, ld8y, b.fc1_w, ld8wd, rp, m->hidden, D, rv, b.fc1_b, b.fc1_s, ws->h, ld8h, GEMM_EPI_GELU_BF16, b.act_scale[3], ws->sat, stream, (m->flags & FP_VIT_NO_TALL_TILES) ? 1 : 0));
-      TRY(gemm_fp8_impl(ws->h, ld8h, b.fc2_w, ld8wh, rp, D, m->hidden, rv, b.fc2_b, b.fc2_s, xr, D, GEMM_EPI_LS_RESID_F32, 0.f, ws->sat, stream, (m->flags & FP_VIT_NO_TALL_TILES) ? 1 : 0));
-      continue;
-    }
-    TRY(layernorm_launch(ln, st));
-    if (bf) {
-      TRY(fp_gemm_bf16(ws->y, ldy, b.qkv_w, ldwd, ws->m_pad, 3 * D, D, Mtok, b.qkv_b, nullptr, ws->qkv, ldq, GEMM_EPI_BIAS_BF16, stream));
-      TRY(attn_launch(at, FP_DTYPE_BF16, st));
-      TRY(fp_gemm_bf16(ws->y, ldy, b.proj_w, ldwd, ws->m_pad, D, D, Mtok, b.proj_b, b.ls1, ws->x, D, GEMM_EPI_LS_RESID_F32, stream));
-    } else {
-      TRY(fp_gemm_f32((const float*)ws->y, ldy, (const float*)b.qkv_w, ldwd, Mtok, 3 * D, D, b.qkv_b, nullptr, (float*)ws->qkv, ldq, F32_EPI_BIAS, stream));
-      TRY(attn_launch(at, FP_DTYPE_F32, st));
-      TRY(fp_gemm_f32((const float*)ws->y, ldy, (const float*)b.proj_w, ldwd, Mtok, D, D, b.proj_b, b.ls1, ws->x, D, F32_EPI_LS_RESID, stream));
-    }
-    // x += ls2 * fc2(gelu(fc1(ln2(x))))
-    ln.weight = b.ln2_w; ln.bias = b.ln2_b;
-    TRY(layernorm_launch(ln, st));
-    if (bf) {
-      if (m->ffn_swiglu)  // fc1_w = w12 with rows interleaved (x1_j, x2_j); h = silu(x1) * x2
-        TRY(fp_gemm_bf16(ws->y, ldy, b.fc1_w, ldwd, ws->m_pad, 2 * m->hidden, D, Mtok, b.fc1_b, nullptr, ws->h, ldh, GEMM_EPI_SWIGLU_BF16, stream));
-      else
-        TRY(fp_gemm_bf16(ws->y, ldy, b.fc1_w, ldwd, ws->m_pad, m->hidden, D, Mtok, b.fc1_b, nullptr, ws->h, ldh, GEMM_EPI_GELU_BF16, stream));
-      TRY(fp_gemm_bf16(ws->h, ldh, b.fc2_w, ldwh, ws->m_pad, D, m->hidden, Mtok, b.fc2_b, b.ls2, ws->x, D, GEMM_EPI_LS_RESID_F32, stream));
-    } else {
-      if (m->ffn_swiglu)
-        TRY(fp_gemm_f32((const float*)ws->y, ldy, (const float*)b.fc1_w, ldwd, Mtok, 2 * m->hidden, D, b.fc1_b, nullptr, (float*)ws->h, ldh, F32_EPI_SWIGLU, stream));
-      else
-        TRY(fp_gemm_f32((const float*)ws->y, ldy, (const float*)b.fc1_w, ldwd, Mtok, m->hidden, D, b.fc1_b, nullptr, (float*)ws->h, ldh, F32_EPI_BIAS_GELU, stream));
-      TRY(fp_gemm_f32((const float*)ws->h, ldh, (const float*)b.fc2_w, ldwh, Mtok, D, m->hidden, b.fc2_b, b.ls2, ws->x, D, F32_EPI_LS_RESID, stream));
-    }
+    TRY(norm(b, QKV, xr));
+    TRY(block_gemm(b, QKV, xr, pair));
+    TRY(attention(b));
+    if (sel) TRY(select_rows(xr));
+    TRY(block_gemm(b, PROJ, xr, pair));
+    // x += ls2 * fc2(act(fc1(ln2(x))))
+    TRY(norm(b, FC1, xr));
+    TRY(block_gemm(b, FC1, xr, pair));
+    TRY(block_gemm(b, FC2, xr, pair));
   }
   return FP_OK;
 }
@@ -974,22 +886,6 @@ int fp_vit_forward_prefix(const fp_vit_model* m, const fp_vit_workspace* ws, con
                           int layer, fp_stream_t stream) {
   FP_REQUIRE(layer >= 0, "fp_vit_forward_prefix: layer must be >= 0");
   return vit_forward_impl(m, ws, images, B, H, W, layer, VIT_PREFIX, nullptr, stream);
-}
-
-int fp_vit_forward_blocks(const fp_vit_model* m, const fp_vit_workspace* ws, int B, int H, int W, int first_block, int layer, int prefix_only, fp_stream_t stream) {
-  FP_REQUIRE(first_block >= 1, "fp_vit_forward_blocks: first_block must be >= 1 (fp_vit_forward runs the embedding and every block)");
-  return vit_forward_impl(m, ws, nullptr, B, H, W, layer, prefix_only ? VIT_PREFIX : VIT_FULL, nullptr, stream, first_block);
-}
-
-int fp_vit_stream_f32(const fp_vit_model* m, const fp_vit_workspace* ws, int B, int H, int W, int layer, float* out, fp_stream_t stream) {
-  FP_REQUIRE(m && ws && out && layer >= 0, "fp_vit_stream_f32: null pointer");
-  const int pstride = m->patch_stride > 0 ? m->patch_stride : m->patch;
-  const int np = (1 + (H - m->patch) / pstride) * (1 + (W - m->patch) / pstride), rows = B * (1 + m->registers + np), D = m->dim;
-  const bool h16 = m->weight_dtype == FP_DTYPE_F16;
-  const bool pair = m->ln_fold && (m->weight_dtype == FP_DTYPE_BF16 || h16) && ws->xl != nullptr && layer > 0;   // what fp_vit_forward_prefix(layer) left behind
-  if (pair) return hilo_rows_launch(ws->xb, ws->xl, ws->ld_y ? ws->ld_y : D, nullptr, rows, D, out, ST(stream), h16);
-  if (out != ws->x) HIP_TRY(hipMemcpyAsync(out, ws->x, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, ST(stream)), "fp_vit_stream_f32: copy");
-  return FP_OK;
 }
 
 int fp_vit_block_selected(const fp_vit_model* m, const fp_vit_workspace* ws, int B, int H, int W, int layer,

@@ -826,7 +826,7 @@ int launch_cfg(const GemmBf16Args& a_in, hipStream_t st) {
 // "320 x 256 block tiles") shows steps exactly at these counts: qkv at the bench batch, 256^2: 22 x 3 = 66 super-tiles = 9 rounds of 31 us;
 // 320 x 256: 18 x 3 = 54 = 7 rounds of 37.5 us.  A round of the taller tile takes 1.21x (not 1.25x) the time: cost = rounds x height x 0.97.
 // The estimate picks the faster tile in 32 of the 36 cases of the recorded sweep (profiles/r4_gemm_tile_sweep.txt; three misses within 1 %, one
-// of 3 %) and 256 rows for the residual GEMMs of the bench batch (3 rounds either way).  GemmBf16Args.no_tall (fp_vit_model.flags & FP_VIT_NO_TALL_TILES) is the A/B switch.
+// of 3 %) and 256 rows for the residual GEMMs of the bench batch (3 rounds either way).
 static int xcd_rounds(int bm, int m_valid, int n_tiles) {
   const int m_tiles = (m_valid + bm - 1) / bm, xcds = 8, per_xcd = fp_num_cus() / xcds > 0 ? fp_num_cus() / xcds : 32;
   const GemmRaster ra = pick_raster(bm, n_tiles, (unsigned)(m_tiles * n_tiles));
@@ -835,7 +835,7 @@ static int xcd_rounds(int bm, int m_valid, int n_tiles) {
   return (chunk + per_xcd - 1) / per_xcd;
 }
 static bool tall_tile_wins(const GemmBf16Args& a) {
-  if (a.no_tall || a.M % 320 != 0 || a.M % 256 != 0 || a.N % 256 != 0) return false;
+  if (a.M % 320 != 0 || a.M % 256 != 0 || a.N % 256 != 0) return false;
   return (float)(xcd_rounds(320, a.M_valid, a.N / 256) * 320) * 0.97f < (float)(xcd_rounds(256, a.M_valid, a.N / 256) * 256);
 }
 

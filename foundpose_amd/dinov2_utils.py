@@ -58,19 +58,30 @@ def _interpolate_pos_embed_strided(pos_embed: torch.Tensor, patch: int, stride: 
     return torch.cat([pos_embed[:, :1], grid.permute(0, 2, 3, 1).reshape(1, -1, dim)], dim=1)
 
 
+def _swiglu_interleave(t: torch.Tensor) -> torch.Tensor:
+    """SwiGLU (ViT-g): the rows of mlp.w12 (its weight [2 hidden, D] or bias [2 hidden]) interleaved as (x1_j, x2_j), so the gate and the value of a
+    hidden unit land in adjacent GEMM columns and silu(x1) * x2 is a per-lane epilogue."""
+    h = t.shape[0] // 2
+    return torch.stack([t[:h], t[h:]], 1).reshape(2 * h, *t.shape[1:])
+
+
+# Row strides of the block matrices and of the y / h / xb / xl activation buffers are padded by this many elements so that a stride is never a
+# multiple of 2 KiB: the 8 rows one staging instruction of the GEMM fetches then spread over the L2 channels instead of queueing on one.  The fp8
+# operands and the qkv buffer stay dense (measured: fp8 padding had no effect, 1425 detections/s either way; qkv padding gains 5-9 % for the
+# attention kernel and the qkv GEMM in isolation, nothing inside the pipeline).
+_LD_PAD = 64
+
+
 class DinoFeatureExtractor(torch.nn.Module):
     def __init__(self, model_name: str, state_dict: Optional[Dict[str, torch.Tensor]] = None, weights: Optional[str] = None,
                  random_init_seed: Optional[int] = None, precision: str = "bf16", arch: Optional[VitArch] = None, use_graph: bool = False,
-                 act_scales: Optional[torch.Tensor] = None, fold_layernorm: bool = True, head_blocks: int = 0, head_precision: str = "f16",
-                 resid_hilo: bool = True, ld_pad: int = 64, ld_pad_qkv: int = 0, ld_pad8: int = 0, tall_tiles: bool = True, sat_check: bool = True) -> None:
+                 act_scales: Optional[torch.Tensor] = None, fold_layernorm: bool = True, sat_check: bool = True) -> None:
         """Weights (the reference: hub model with pretrained=True, dinov2_utils.py:81-84): `state_dict=` (upstream key names), `weights=` (checkpoint
         file, or directory holding the upstream file name), else $FOUNDPOSE_DINOV2_WEIGHTS, else the torch hub cache the reference's own call fills;
         none of them -> FoundPoseWeightsError.  Random weights only on an explicit `random_init_seed=` (tests, benchmarks).  Every dict is checked
         like load_state_dict(strict=True) (weights.validate_state_dict).
-        Tuning arguments (A/B switches of measurements; none changes what is computed beyond rounding points, the defaults are what the benchmarks run):
-        fold_layernorm (bf16: the block LayerNorms folded into the GEMMs), resid_hilo (the residual stream in front of the hooked block as a (hi, lo) 16-bit
-        pair), ld_pad / ld_pad_qkv / ld_pad8 (row-stride padding of the operands, elements / bytes), tall_tiles (320-row GEMM tiles), sat_check (forward()
-        raises on a saturation report: one host sync per call).  No environment variable is read."""
+        Switches: fold_layernorm (bf16: the block LayerNorms folded into the GEMMs; False keeps a LayerNorm kernel per norm, the reference of the
+        tests), sat_check (forward() raises on a saturation report: one host sync per call).  No environment variable is read."""
         super().__init__()
         self.use_graph = use_graph  # replay the forward's launch sequence as one hipGraph (static buffers per batch shape)
         if arch is not None:  # non-hub architecture (unit tests use a tiny one)
@@ -126,23 +137,9 @@ class DinoFeatureExtractor(torch.nn.Module):
         # qkv / fc1 matrices, shift into their biases, LayerScale into the proj / fc2 matrices -- no LayerNorm kernel runs
         # inside the blocks (they were 6.5 % of a step).  fold_layernorm=False keeps the kernel-per-LayerNorm sequence.
         self.fold_layernorm = (bool(fold_layernorm) and precision == "bf16") or precision == "f16"
-        self.resid_hilo = bool(resid_hilo) or precision == "f16"
-        self.tall_tiles, self.sat_check = bool(tall_tiles), bool(sat_check)
-        self._ld_pad_arg, self._ld_pad_qkv_arg, self._ld_pad8_arg = int(ld_pad), int(ld_pad_qkv), int(ld_pad8)
+        self.resid_hilo = True   # a folded model keeps the residual stream in front of the hooked block as a (hi, lo) 16-bit pair (fp_vit_workspace.xl)
+        self.sat_check = bool(sat_check)
         self._sd, self.weights_source = _weights.resolve(self.model_base_name, self.arch, state_dict, weights, random_init_seed)
-        # Precision schedule: blocks 0 .. head_blocks-1 run in `head_precision`, blocks head_blocks .. layer in this extractor's own precision, over one
-        # fp32 stream (fp_vit_stream_f32 / fp_vit_forward_blocks): the fast "f16" pipeline in front of a near-exact tail, or the other way round.
-        # Measured and NOT a shipped default: see profiles/EXPERIMENTS.md "precision schedules" (tools/schedule_sweep.py).
-        self.head_blocks = int(head_blocks)
-        self._head: Optional["DinoFeatureExtractor"] = None
-        if self.head_blocks:
-            modes = ("f16", "f16x3", "f16f8", "fp32")
-            if precision not in modes or head_precision not in modes or not 0 < self.head_blocks <= self.layer or self.facet != "token" or use_graph:
-                raise ValueError("head_blocks: 1 .. layer blocks in one of 'f16' / 'f16x3' / 'f16f8' / 'fp32' in front of an extractor of another of them (token facet, no graph replay)")
-            # a folded-LayerNorm head stops BEFORE block k (fp_vit_forward_prefix, layer = k); the others run blocks 0 .. k-1 in full (fp_vit_forward, layer = k - 1)
-            self._head_fold = head_precision == "f16"
-            head_name = f"dinov2_version={self.version}_stride={self.stride}_facet=token_layer={self.head_blocks if self._head_fold else self.head_blocks - 1}_norm=1"
-            self._head = DinoFeatureExtractor(head_name, state_dict=self._sd, precision=head_precision, arch=arch)
         self._device: Optional[torch.device] = None
         self._w: Dict[str, torch.Tensor] = {}
         self._model = None
@@ -162,8 +159,6 @@ class DinoFeatureExtractor(torch.nn.Module):
         if dev.type != "cuda":
             raise _lib.FoundPoseNativeError("DinoFeatureExtractor runs on the MI355X only (device must be 'cuda'); no CPU path exists")
         self._prepare(dev)
-        if self._head is not None:
-            self._head.to(dev)
         return self
 
     def cuda(self, device=None):  # type: ignore[override]
@@ -175,18 +170,7 @@ class DinoFeatureExtractor(torch.nn.Module):
             return self._prepare_split(dev)
         wdt = torch.float32 if self.precision == "fp32" else (torch.float16 if self.precision == "f16" else torch.bfloat16)
         w: Dict[str, torch.Tensor] = {}
-
-        # Row strides of the block matrices and of the y / h activation buffers are padded by `pad` elements so that a
-        # stride is never a multiple of 2 KiB: the 8 rows one staging instruction of the GEMM fetches then spread over
-        # the L2 channels instead of queueing on one (ld_pad; 0 = dense; fp8 mode stays dense).
-        pad = self._ld_pad_arg if self.precision != "fp8" else 0
-        self._ld_pad8 = self._ld_pad8_arg if self.precision == "fp8" else 0  # bytes, fp8 operands (measured: no effect at 128, 1425 detections/s either way)
-        if pad % 8:
-            raise ValueError("ld_pad must be a multiple of 8")
-        self._ld_pad = pad
-        # the qkv buffer's stride can be padded too (ld_pad_qkv): in isolation the attention kernel and the qkv GEMM gain
-        # 5-9 % from +64..128 elements, inside the pipeline nothing (998 detections/s at 0 / 64 / 128 / 256) -> dense
-        self._ld_pad_qkv = self._ld_pad_qkv_arg
+        self._ld_pad = pad = 0 if self.precision == "fp8" else _LD_PAD
 
         def padded(t2d):  # [N, K] -> view of an [N, K + pad] buffer
             if pad == 0:
@@ -203,10 +187,7 @@ class DinoFeatureExtractor(torch.nn.Module):
             w[key] = sd[key].to(dev, torch.float32).reshape(-1).contiguous()
             return w[key]
 
-        kp = 3 * a.patch * a.patch
-        kpad = (kp + 63) // 64 * 64
-        pw = torch.zeros(a.dim, kpad, dtype=torch.float32, device=dev)
-        pw[:, :kp] = sd["patch_embed.proj.weight"].to(dev, torch.float32).reshape(a.dim, kp)
+        pw, kpad = self._patch_weight(dev)
         w["patch_w"] = pw.to(wdt).contiguous()
         vec("patch_embed.proj.bias")
         vec("norm.weight")
@@ -254,11 +235,8 @@ class DinoFeatureExtractor(torch.nn.Module):
                 if a.ffn == "mlp":
                     w[p + "fc1.wf"], w[p + "fc1.bf"], w[p + "fc1.cs"] = folded_in(p + "mlp.fc1.weight", p + "mlp.fc1.bias", p + "norm2", name=2)
                     w[p + "fc2.wf"], w[p + "fc2.bf"] = folded_out(p + "mlp.fc2.weight", p + "mlp.fc2.bias", p + "ls2.gamma", name=3)
-                else:  # SwiGLU: rows of w12 interleaved (x1_j, x2_j), see below
-                    w12, b12 = f32(p + "mlp.w12.weight"), f32(p + "mlp.w12.bias")
-                    hdn = w12.shape[0] // 2
-                    w12i = torch.stack([w12[:hdn], w12[hdn:]], 1).reshape(2 * hdn, -1)
-                    b12i = torch.stack([b12[:hdn], b12[hdn:]], 1).reshape(-1)
+                else:
+                    w12i, b12i = _swiglu_interleave(f32(p + "mlp.w12.weight")), _swiglu_interleave(f32(p + "mlp.w12.bias"))
                     w[p + "fc1.wf"], w[p + "fc1.bf"], w[p + "fc1.cs"] = folded_in(None, None, p + "norm2", w12i, b12i, name=2)
                     w[p + "fc2.wf"], w[p + "fc2.bf"] = folded_out(p + "mlp.w3.weight", p + "mlp.w3.bias", p + "ls2.gamma", name=3)
                 b.qkv_w, b.qkv_b, b.qkv_colsum = ptr(w[p + "qkv.wf"]), ptr(w[p + "qkv.bf"]), ptr(w[p + "qkv.cs"])
@@ -277,30 +255,12 @@ class DinoFeatureExtractor(torch.nn.Module):
                 b.fc1_w, b.fc1_b = ptr(mat(p + "mlp.fc1.weight")), ptr(vec(p + "mlp.fc1.bias"))
                 b.fc2_w, b.fc2_b = ptr(mat(p + "mlp.fc2.weight")), ptr(vec(p + "mlp.fc2.bias"))
             else:
-                # SwiGLU (ViT-g): interleave the rows of w12 as (x1_j, x2_j) so the gate and the value of a hidden unit
-                # land in adjacent GEMM columns and silu(x1) * x2 is a per-lane epilogue
-                w12 = sd[p + "mlp.w12.weight"].to(dev, torch.float32)
-                b12 = sd[p + "mlp.w12.bias"].to(dev, torch.float32)
-                hdn = w12.shape[0] // 2
-                w[p + "w12i"] = padded(torch.stack([w12[:hdn], w12[hdn:]], 1).reshape(2 * hdn, -1).to(wdt))
-                w[p + "b12i"] = torch.stack([b12[:hdn], b12[hdn:]], 1).reshape(-1).contiguous()
+                w[p + "w12i"] = padded(_swiglu_interleave(f32(p + "mlp.w12.weight")).to(wdt))
+                w[p + "b12i"] = _swiglu_interleave(f32(p + "mlp.w12.bias"))
                 b.fc1_w, b.fc1_b = ptr(w[p + "w12i"]), ptr(w[p + "b12i"])
                 b.fc2_w, b.fc2_b = ptr(mat(p + "mlp.w3.weight")), ptr(vec(p + "mlp.w3.bias"))
-        m = _lib.VitModel()
-        m.dim, m.depth, m.heads, m.hidden, m.registers, m.patch = a.dim, a.depth, a.heads, a.hidden, a.registers, a.patch
-        m.ffn_swiglu = int(a.ffn != "mlp")
-        m.patch_stride = 0 if self.stride == self.patch_size else self.stride
-        m.weight_dtype = _lib.FP_F32 if self.precision == "fp32" else (_lib.FP_F16 if self.precision == "f16" else _lib.FP_BF16)  # "fp8": bf16 until calibrated (_to_fp8)
-        m.patch_w, m.patch_k_pad, m.patch_b = ptr(w["patch_w"]), kpad, ptr(w["patch_embed.proj.bias"])
-        m.norm_w, m.norm_b = ptr(w["norm.weight"]), ptr(w["norm.bias"])
-        m.blocks = C.cast(blocks, C.POINTER(_lib.VitBlock))
-        m.ld_w_dim, m.ld_w_hidden = (a.dim + pad, a.hidden + pad) if pad else (0, 0)  # fp8: set by _to_fp8
-        m.ln_fold = int(fold)
-        m.flags = 0 if self.tall_tiles else _lib.VIT_NO_TALL_TILES
-        self._w, self._model, self._blocks, self._device = w, m, blocks, dev
-        self._grids.clear()
-        self._ws.clear()
-        self._graphs.clear()
+        wdt_abi = _lib.FP_F32 if self.precision == "fp32" else (_lib.FP_F16 if self.precision == "f16" else _lib.FP_BF16)  # "fp8": bf16 until calibrated (_to_fp8)
+        self._install(dev, w, blocks, kpad, wdt_abi, em=1, ln_fold=fold)
         if self.precision == "fp8" and self.act_scales is not None:
             self._to_fp8()
 
@@ -310,10 +270,7 @@ class DinoFeatureExtractor(torch.nn.Module):
         from . import ops
         a, sd = self.arch, self._sd
         w: Dict[str, torch.Tensor] = {}
-        pad = self._ld_pad_arg
-        if pad % 8:
-            raise ValueError("ld_pad must be a multiple of 8")
-        self._ld_pad, self._ld_pad8, self._ld_pad_qkv = pad, 0, 0
+        self._ld_pad = pad = _LD_PAD
 
         def f32(key):
             return sd[key].to(dev, torch.float32)
@@ -330,10 +287,7 @@ class DinoFeatureExtractor(torch.nn.Module):
             w[name] = pack(W, sw, pad)
             return w[name], sw
 
-        kp = 3 * a.patch * a.patch
-        kpad = (kp + 63) // 64 * 64
-        pw = torch.zeros(a.dim, kpad, dtype=torch.float32, device=dev)
-        pw[:, :kp] = f32("patch_embed.proj.weight").reshape(a.dim, kp)
+        pw, kpad = self._patch_weight(dev)
         spw = ops.pow2_scale(pw)
         w["patch_w"] = pack(pw, spw)
         vec("patch_embed.proj.bias")
@@ -350,11 +304,9 @@ class DinoFeatureExtractor(torch.nn.Module):
             if a.ffn == "mlp":
                 fc1_w, fc1_b = f32(p + "mlp.fc1.weight"), vec(p + "mlp.fc1.bias")
                 fc2_w, fc2_b = f32(p + "mlp.fc2.weight"), vec(p + "mlp.fc2.bias")
-            else:  # SwiGLU: rows of w12 interleaved (x1_j, x2_j) like the other modes
-                w12, b12 = f32(p + "mlp.w12.weight"), f32(p + "mlp.w12.bias")
-                hdn = w12.shape[0] // 2
-                fc1_w = torch.stack([w12[:hdn], w12[hdn:]], 1).reshape(2 * hdn, -1)
-                w[p + "b12i"] = fc1_b = torch.stack([b12[:hdn], b12[hdn:]], 1).reshape(-1).contiguous()
+            else:
+                fc1_w = _swiglu_interleave(f32(p + "mlp.w12.weight"))
+                w[p + "b12i"] = fc1_b = _swiglu_interleave(f32(p + "mlp.w12.bias"))
                 fc2_w, fc2_b = f32(p + "mlp.w3.weight"), vec(p + "mlp.w3.bias")
             mats = [("qkv", f32(p + "attn.qkv.weight"), vec(p + "attn.qkv.bias"), S_ACT), ("proj", f32(p + "attn.proj.weight"), vec(p + "attn.proj.bias"), S_ACT),
                     ("fc1", fc1_w, fc1_b, S_ACT), ("fc2", fc2_w, fc2_b, S_HID)]
@@ -363,39 +315,35 @@ class DinoFeatureExtractor(torch.nn.Module):
                 setattr(b, field + "_w", ptr(ws_))
                 setattr(b, field + "_b", ptr(bias))
                 b.act_scale[j] = 1.0 / (s_in * sw)
-        m = _lib.VitModel()
+        self._install(dev, w, blocks, kpad, _lib.FP_F16F8 if sx else _lib.FP_F16X3, em=2, patch_acc_scale=1.0 / (S_ACT * spw))
+
+    def _patch_weight(self, dev: torch.device) -> Tuple[torch.Tensor, int]:
+        """-> the patch-embedding conv weight flattened (c, py, px) as fp32 [D, patch_k_pad], zero padded to a multiple of 64, and patch_k_pad."""
+        a = self.arch
+        kp = 3 * a.patch * a.patch
+        kpad = (kp + 63) // 64 * 64
+        pw = torch.zeros(a.dim, kpad, dtype=torch.float32, device=dev)
+        pw[:, :kp] = self._sd["patch_embed.proj.weight"].to(dev, torch.float32).reshape(a.dim, kp)
+        return pw, kpad
+
+    def _install(self, dev: torch.device, w: Dict[str, torch.Tensor], blocks, kpad: int, weight_dtype: int, em: int, ln_fold: bool = False,
+                 patch_acc_scale: float = 0.0) -> None:
+        """The fp_vit_model over prepared weights w (em: stored elements per logical element of a matrix row); drops what was cached for the last ones."""
+        a, m, pad = self.arch, _lib.VitModel(), self._ld_pad
         m.dim, m.depth, m.heads, m.hidden, m.registers, m.patch = a.dim, a.depth, a.heads, a.hidden, a.registers, a.patch
         m.ffn_swiglu = int(a.ffn != "mlp")
         m.patch_stride = 0 if self.stride == self.patch_size else self.stride
-        m.weight_dtype = _lib.FP_F16F8 if sx else _lib.FP_F16X3
+        m.weight_dtype = weight_dtype
         m.patch_w, m.patch_k_pad, m.patch_b = ptr(w["patch_w"]), kpad, ptr(w["patch_embed.proj.bias"])
-        m.patch_acc_scale = 1.0 / (S_ACT * spw)
+        m.patch_acc_scale = patch_acc_scale
         m.norm_w, m.norm_b = ptr(w["norm.weight"]), ptr(w["norm.bias"])
         m.blocks = C.cast(blocks, C.POINTER(_lib.VitBlock))
-        m.ld_w_dim, m.ld_w_hidden = (2 * a.dim + pad, 2 * a.hidden + pad) if pad else (0, 0)
-        m.ln_fold = 0
+        m.ld_w_dim, m.ld_w_hidden = (em * a.dim + pad, em * a.hidden + pad) if pad else (0, 0)
+        m.ln_fold = int(ln_fold)
         self._w, self._model, self._blocks, self._device = w, m, blocks, dev
         self._grids.clear()
         self._ws.clear()
         self._graphs.clear()
-
-    def _run_backbone(self, images, ws, B: int, H: int, W: int, prefix_only: bool) -> None:
-        """fp_vit_forward / fp_vit_forward_prefix, or -- with a precision schedule -- the head's blocks in the f16 mode, its stream as fp32 into this
-        workspace, and this model's blocks behind it."""
-        if self._head is None:
-            call("fp_vit_forward_prefix" if prefix_only else "fp_vit_forward", C.byref(self._model), C.byref(ws), ptr(images), B, H, W, self.layer, stream())
-            return
-        hd, k = self._head, self.head_blocks
-        gh, gw = hd._grid(H, W)
-        pos_patch, prefix = hd._grid_tables(gh, gw, H, W)
-        hd._model.pos_patch, hd._model.prefix = ptr(pos_patch), ptr(prefix)
-        hws, _ = hd._workspace(B, gh, gw)
-        if self._head_fold:
-            call("fp_vit_forward_prefix", C.byref(hd._model), C.byref(hws), ptr(images), B, H, W, k, stream())      # embedding + blocks 0 .. k-1, the stream as the (hi, lo) pair
-        else:
-            call("fp_vit_forward", C.byref(hd._model), C.byref(hws), ptr(images), B, H, W, k - 1, stream())         # embedding + blocks 0 .. k-1, the stream in its ws.x
-        call("fp_vit_stream_f32", C.byref(hd._model), C.byref(hws), B, H, W, k, ws.x, stream())                      # -> this workspace's fp32 stream
-        call("fp_vit_forward_blocks", C.byref(self._model), C.byref(ws), B, H, W, k, self.layer, int(prefix_only), stream())
 
     def _grid(self, H: int, W: int) -> Tuple[int, int]:
         """Patch tokens per axis (dinov2_utils.py:266-269): 1 + (size - patch) // stride; at stride == patch size the image must tile."""
@@ -445,26 +393,21 @@ class DinoFeatureExtractor(torch.nn.Module):
                 torch.zeros(mp_pad, em * self._model.patch_k_pad, dtype=adt, device=dev),
                 torch.zeros(m_pad, a.dim, dtype=torch.float32, device=dev),
                 torch.zeros(m_pad, em * a.dim + self._ld_pad, dtype=adt, device=dev),
-                torch.zeros(m_pad, em * 3 * a.dim + self._ld_pad_qkv, dtype=adt, device=dev),
+                torch.zeros(m_pad, em * 3 * a.dim, dtype=adt, device=dev),
                 torch.zeros(m_pad, em * a.hidden + self._ld_pad, dtype=adt, device=dev),
             ]
             if self.precision == "fp8":
-                p8 = self._ld_pad8
-                bufs.append(torch.zeros(m_pad, max(a.dim, a.hidden) + p8, dtype=torch.uint8, device=dev))
+                bufs.append(torch.zeros(m_pad, max(a.dim, a.hidden), dtype=torch.uint8, device=dev))
             ws = _lib.VitWorkspace()
-            if self.fold_layernorm:  # bf16 copy of the residual stream + partial row sums per 128-column tile
+            if self.fold_layernorm:  # 16-bit copy of the residual stream (its high halves), partial row sums per 128-column tile, low halves
                 bufs.append(torch.zeros(m_pad, a.dim + self._ld_pad, dtype=adt, device=dev))
                 bufs.append(torch.zeros(a.dim // 128 + 1, m_pad, 2, dtype=torch.float32, device=dev))
-                ws.xb, ws.stats = ptr(bufs[-2]), ptr(bufs[-1])
-                if self.resid_hilo:   # low halves of the (hi, lo) residual stream of the blocks in front of the hooked one (A/B switch)
-                    bufs.append(torch.zeros(m_pad, a.dim + self._ld_pad, dtype=adt, device=dev))
-                    ws.xl = ptr(bufs[-1])
+                bufs.append(torch.zeros(m_pad, a.dim + self._ld_pad, dtype=adt, device=dev))
+                ws.xb, ws.stats, ws.xl = (ptr(t) for t in bufs[-3:])
             ws.patches, ws.x, ws.y, ws.qkv, ws.h = (ptr(t) for t in bufs[:5])
             ws.a8 = ptr(bufs[5]) if self.precision == "fp8" else None
             ws.ld_y, ws.ld_h = (em * a.dim + self._ld_pad, em * a.hidden + self._ld_pad) if self._ld_pad else (0, 0)
-            if self.precision == "fp8" and self._ld_pad8:  # byte strides of a8 and of the hidden bytes kept in h
-                ws.ld_y, ws.ld_h = a.dim + self._ld_pad8, a.hidden + self._ld_pad8
-            ws.ld_qkv = em * 3 * a.dim + self._ld_pad_qkv
+            ws.ld_qkv = em * 3 * a.dim
             ws.m_pad, ws.m_patch_pad = m_pad, mp_pad
             if self._sat is None:
                 self._sat = torch.zeros(2, dtype=torch.int32, device=dev)
@@ -514,10 +457,9 @@ class DinoFeatureExtractor(torch.nn.Module):
             warnings.warn(f"precision='fp8': {n8} kernel thread(s) clamped an activation at +-448 (inputs beyond the static calibration scales)")
 
     # ---- forward
-    def forward_tokens(self, images: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """-> (fmap [B, Np, D] fp32 token-major, cls [B, D] fp32); the batched fast-path entry."""
-        if self._model is None:
-            raise _lib.FoundPoseNativeError("call extractor.to('cuda') before running it")
+    def _batch(self, images: torch.Tensor):
+        """What a forward over `images` needs: the grid tables in the model and the workspace of the batch shape.
+        -> (images as contiguous fp32, B, H, W, gh, gw, workspace)."""
         _lib.require_cuda(images)
         if images.dim() != 4 or images.shape[1] != 3:
             raise ValueError("images must be [B, 3, H, W]")
@@ -531,6 +473,13 @@ class DinoFeatureExtractor(torch.nn.Module):
             raise _lib.FoundPoseNativeError(
                 "precision='fp8' needs its static activation scales before the first forward: construct the extractor with "
                 "act_scales= (the table stored with the bank) or call calibrate_fp8(calibration_images) once")
+        return images, B, H, W, gh, gw, ws
+
+    def forward_tokens(self, images: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (fmap [B, Np, D] fp32 token-major, cls [B, D] fp32); the batched fast-path entry."""
+        if self._model is None:
+            raise _lib.FoundPoseNativeError("call extractor.to('cuda') before running it")
+        images, B, H, W, gh, gw, ws = self._batch(images)
         if self.facet != "token":
             fmap, cls = self._forward_facet(images, B, H, W, gh, gw)
         elif self.use_graph:
@@ -560,16 +509,8 @@ class DinoFeatureExtractor(torch.nn.Module):
             raise NotImplementedError("forward_hidden serves the eager token path")
         if prefix_only and not self.supports_token_selection:
             raise NotImplementedError("token selection needs the bf16 mode with folded LayerNorms, the fp8 or the f16x3 mode")
-        _lib.require_cuda(images)
-        images = images.float().contiguous()
-        B, _, H, W = images.shape
-        gh, gw = self._grid(H, W)
-        pos_patch, prefix = self._grid_tables(gh, gw, H, W)
-        self._model.pos_patch, self._model.prefix = ptr(pos_patch), ptr(prefix)
-        ws, _ = self._workspace(B, gh, gw)
-        if self.precision == "fp8" and self._model.weight_dtype != _lib.FP_FP8:
-            raise _lib.FoundPoseNativeError("precision='fp8' needs its static activation scales before the first forward (act_scales= / calibrate_fp8)")
-        self._run_backbone(images, ws, B, H, W, prefix_only)
+        images, B, H, W, gh, gw, ws = self._batch(images)
+        call("fp_vit_forward_prefix" if prefix_only else "fp_vit_forward", C.byref(self._model), C.byref(ws), ptr(images), B, H, W, self.layer, stream())
         self.num_patches = (gh, gw)
         self._hidden = (B, gh, gw, H, W)
         return B, gh, gw
@@ -690,10 +631,6 @@ class DinoFeatureExtractor(torch.nn.Module):
                 sw = 448.0 / wt.abs().amax(dim=1).clamp_min(1e-12)
                 deq = 1.0 / (float(self.act_scales[i, j]) * sw)
                 q8 = ops.quantize_fp8((wt * sw[:, None]).contiguous(), 1.0)
-                if self._ld_pad8:  # rows K + pad bytes apart (L2 channel spread, as for the bf16 operands)
-                    buf = torch.zeros(q8.shape[0], q8.shape[1] + self._ld_pad8, dtype=torch.uint8, device=q8.device)
-                    buf[:, :q8.shape[1]] = q8.view(torch.uint8)
-                    q8 = buf
                 w[p + wk + ".f8"] = q8
                 w[p + wk + ".b8"] = (w[p + bk] / deq).contiguous()
                 w[p + wk + ".s8"] = (deq * w[p + gk] if gk else deq).contiguous()
@@ -702,21 +639,17 @@ class DinoFeatureExtractor(torch.nn.Module):
                 setattr(b, field + "_s", ptr(w[p + wk + ".s8"]))
                 b.act_scale[j] = float(self.act_scales[i, j])
         self._model.weight_dtype = _lib.FP_FP8
-        p8 = self._ld_pad8
-        self._model.ld_w_dim, self._model.ld_w_hidden = (a.dim + p8, a.hidden + p8) if p8 else (0, 0)
         self._graphs.clear()
 
     def _fp32_matrix(self, p: str, wk: str) -> torch.Tensor:
         sd, dev = self._sd, self._device
         if wk == "w12i":  # SwiGLU: rows interleaved (x1_j, x2_j) like the bf16 operand
-            w12 = sd[p + "mlp.w12.weight"].to(dev, torch.float32)
-            hdn = w12.shape[0] // 2
-            return torch.stack([w12[:hdn], w12[hdn:]], 1).reshape(2 * hdn, -1).contiguous()
+            return _swiglu_interleave(sd[p + "mlp.w12.weight"].to(dev, torch.float32)).contiguous()
         return sd[p + wk].to(dev, torch.float32).contiguous()
 
     def _launch(self, images, ws, B, H, W, gh, gw, fmap, cls) -> None:
         """The ~125 kernel launches of one forward (C++ launch sequence) on the current stream."""
-        self._run_backbone(images, ws, B, H, W, False)
+        call("fp_vit_forward", C.byref(self._model), C.byref(ws), ptr(images), B, H, W, self.layer, stream())
         call("fp_vit_features", C.byref(self._model), C.byref(ws), B, gh * gw, int(self.apply_norm), ptr(fmap), ptr(cls), stream())
 
     def _forward_graph(self, images, ws, B, H, W, gh, gw):

@@ -66,7 +66,7 @@ enum { FP_F32 = 0, FP_BF16 = 1, FP_FP8 = 2, FP_F16X3 = 3, FP_F16F8 = 4, FP_F16 =
  * absolute error <= 3e-8 (fp16 subnormals, which the MFMA honours). */
 #define FP_GEMM_F16 (1 << 21) /* OR-ed into fp_gemm_bf16's / fp_gemm_bf16_ln's `epilogue`: A, W, the 16-bit outputs and the (xb, xl) stream are IEEE fp16 */
 
-#define FP_ABI_VERSION 19
+#define FP_ABI_VERSION 20
 int fp_abi_version(void);
 const char* fp_last_error(void);
 
@@ -257,10 +257,8 @@ typedef struct {
                               qkv_b / fc1_b hold b + W ln_bias, *_colsum the row sums of those matrices; proj_w / fc2_w hold
                               diag(LayerScale) W and proj_b / fc2_b hold LayerScale * b (ls1 / ls2 are then unused); the
                               residual GEMMs (proj, fc2) also emit bf16(x) and per-row (sum x, sum x^2), and the qkv / fc1
-                              epilogues compute rstd * (acc - mean * colsum) + bias.  Needs workspace xb / stats. */
-  int flags;               /* tuning bits of a whole forward (results are bit-identical either way): FP_VIT_NO_TALL_TILES */
+                              epilogues compute rstd * (acc - mean * colsum) + bias.  Needs workspace xb / stats / xl. */
 } fp_vit_model;
-#define FP_VIT_NO_TALL_TILES 1 /* the wide bf16 / f16 GEMMs never take their 320-row block tile (A/B switch; the tiles walk k in the same order) */
 
 typedef struct {
   void* patches; /* [m_patch_pad, patch_k_pad] activation dtype */
@@ -288,10 +286,10 @@ typedef struct {
                     Counted per reporting thread, not per element: non-zero means "at least one live output row clamped".
                     The attention output and the softmax probabilities of the f16x3 mode cannot clamp (a convex combination of v rows
                     that fit their scale; p <= 2) and do not report; padding rows never report. */
-  void* xl;      /* ln_fold only, may be NULL: [m_pad, D] bf16 (row stride ld_y), the LOW halves of the residual stream.  When given, the blocks in
-                    front of the hooked one keep the stream as the pair (xb, xl) -- x = hi + lo, hi' = bf16(x'), lo' = bf16(x' - hi'): 16 mantissa
-                    bits per update -- and their residual GEMMs read 4 + write 4 bytes per element instead of 4 + 6 (no fp32 read-modify-write
-                    beside a separate bf16 copy); the hooked block runs on an fp32 stream rebuilt from the pair.  NULL: fp32 stream throughout. */
+  void* xl;      /* ln_fold only (required): [m_pad, D] bf16 (row stride ld_y), the LOW halves of the residual stream.  The blocks in front of
+                    the hooked one keep the stream as the pair (xb, xl) -- x = hi + lo, hi' = bf16(x'), lo' = bf16(x' - hi'): 16 mantissa bits per
+                    update -- and their residual GEMMs read 4 + write 4 bytes per element instead of 4 + 6 (no fp32 read-modify-write beside a
+                    separate bf16 copy); the hooked block runs on an fp32 stream rebuilt from the pair. */
 } fp_vit_workspace;
 
 /* images [B,3,H,W] fp32 in [0,1] -> ws->x holds the output of blocks[layer] for every token
@@ -321,7 +319,7 @@ int fp_vit_sample_features(const fp_vit_model* model, const fp_vit_workspace* ws
  * fp_vit_sample_features with identical sampled features (bit for bit: a token's row never depends on which rows share its
  * GEMM tile or attention block):
  *   fp_vit_forward_prefix   embedding + blocks 0..layer-1 (what block `layer` starts from stays in the workspace).  The workspace
- *                           state between the calls is PRIVATE to them: with ws->xl set (the (hi, lo) residual stream) and layer > 0 the
+ *                           state between the calls is PRIVATE to them: for a folded-LayerNorm model (the (hi, lo) residual stream) and layer > 0 the
  *                           stream lives in the (ws->xb, ws->xl) pair only and ws->x is UNDEFINED (it still holds the token
  *                           embedding); do not read ws->x after a prefix run -- fp_vit_block_selected rebuilds the rows it needs;
  *   fp_vit_block_selected   block `layer`: LayerNorm constants and the qkv projection for all tokens, then attention
@@ -350,15 +348,6 @@ int fp_vit_forward_prefix(const fp_vit_model* model, const fp_vit_workspace* ws,
                           fp_stream_t stream);
 int fp_vit_block_selected(const fp_vit_model* model, const fp_vit_workspace* ws, int B, int H, int W, int layer, const int32_t* sel_rows,
                           const int32_t* sel_off, int num_sel, int max_sel_per_img, fp_stream_t stream);
-/* Precision schedules: blocks 0..k-1 in one model (e.g. FP_F16), blocks k..layer in another (FP_F16X3 / FP_F16F8 / FP_F32) over the same fp32 stream.
- *   fp_vit_stream_f32      the residual stream fp_vit_forward_prefix(model, ws, .., layer = k) -- or, for a model without folded LayerNorms, fp_vit_forward(.., layer =
- *                          k - 1) -- left in its workspace (the (xb, xl) pair of a folded-LayerNorm model, else ws->x), as fp32 rows out [B * n_tok, D]: the `x` buffer
- *                          of the second model's workspace;
- *   fp_vit_forward_blocks  blocks first_block..layer (prefix_only: ..layer-1) of `model` on the stream already in ws->x: no embedding; 1 <= first_block <= layer.
- *                          fp_vit_block_selected / fp_vit_features / fp_vit_sample_features* follow as after fp_vit_forward_prefix / fp_vit_forward. */
-int fp_vit_stream_f32(const fp_vit_model* model, const fp_vit_workspace* ws, int B, int H, int W, int layer, float* out, fp_stream_t stream);
-int fp_vit_forward_blocks(const fp_vit_model* model, const fp_vit_workspace* ws, int B, int H, int W, int first_block, int layer, int prefix_only,
-                          fp_stream_t stream);
 int fp_vit_sample_features_selected(const fp_vit_model* model, const fp_vit_workspace* ws, int B, int grid_h, int grid_w, int apply_norm,
                                     int img_w, int img_h, const float* points, const int32_t* point_img, int num_points,
                                     const int32_t* row_map, float* out, fp_stream_t stream);

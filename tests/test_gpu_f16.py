@@ -322,35 +322,6 @@ def test_f16_mode_loud_failures():
         ops.gemm_bf16(a, w, torch.zeros(128, device="cuda"))
 
 
-@pytest.mark.parametrize("head,tail", [("f16", "f16x3"), ("f16f8", "f16")])
-def test_precision_schedule_runs_two_models_over_one_stream(head, tail):
-    """head_blocks = k: blocks 0..k-1 in one precision, blocks k..layer in another, over one fp32 stream (fp_vit_stream_f32 / fp_vit_forward_blocks) -- a
-    measurement device (tools/schedule_sweep.py), not a shipped default.  The composition is exact at its seams: with the SAME precision on both sides
-    of the cut (fp32 | fp32) the features equal the single model's to the last bit; mixed precisions land between the two pure modes' distances from the fp32
-    oracle; the engine's token-selected path equals the full path bit for bit."""
-    from foundpose_amd import engine as fe, feature_util, workload
-    from foundpose_amd.bank import DeviceBank
-    arch = ARCHS["vits14-reg"]
-    name = "dinov2_version=vits14-reg_stride=14_facet=token_layer=6_norm=1"
-    sd = synthetic.make_vit_state_dict(arch, seed=4)
-    imgs = synthetic.make_crops(3, 224, seed=1)
-    ref = ov.extractor_forward(sd, arch, imgs, 6, True)["feature_maps"]
-    mk = lambda prec, **kw: feature_util.make_feature_extractor(name, state_dict=sd, precision=prec, **kw).to("cuda")
-    whole = mk("fp32")(imgs.cuda())["feature_maps"]
-    cut = mk("fp32", head_blocks=3, head_precision="fp32")(imgs.cuda())["feature_maps"]
-    assert torch.equal(whole, cut)
-    e = {p: rel_err(mk(p)(imgs.cuda())["feature_maps"].cpu(), ref) for p in (head, tail)}
-    ex = mk(tail, head_blocks=3, head_precision=head)
-    got = rel_err(ex(imgs.cuda())["feature_maps"].cpu(), ref)
-    assert got < 1.5 * max(e.values()) + 1e-5, (got, e)
-    wl = workload.build_planted_workload(mk("fp32"), 3, 224, 1, 60, seed=3, crop_seed=2)
-    bank = DeviceBank(wl.repres)
-    outs = [fe.FoundPoseEngine(ex, bank, 14.0, 5, 300, tie_order="torch", select_tokens=sel).infer_batch(wl.crops, wl.masks, wl.det_obj) for sel in (True, False)]
-    for f in ("template_ids", "counts", "q_ids", "feat_ids", "dists", "coord_3d"):
-        x, y = getattr(outs[0], f), getattr(outs[1], f)
-        assert torch.equal(x, y) or bool(((x == y) | (x.isnan() & y.isnan())).all()), f
-
-
 def test_f16_weight_matrices_carry_power_of_two_scales():
     """LayerScale is folded into proj / fc2 (fp_vit_model.ln_fold): with the small gammas DINOv2 starts from, diag(gamma) W would sit in fp16's subnormal range,
     where the format has FEWER significant bits than bf16.  Every folded matrix is therefore stored times a power of two that brings its largest entry to
