@@ -41,6 +41,18 @@ static F32TileArgs zero_tile_args() {
   return a;
 }
 
+int gemm_launch(GemmFmt fmt, int epi, const GemmBf16Args& a, hipStream_t st) {
+  switch (fmt) {
+    case GemmFmt::BF16: return gemm_launch_fmt<GemmFmt::BF16>(epi, a, st);
+    case GemmFmt::F16: return gemm_launch_fmt<GemmFmt::F16>(epi, a, st);
+    case GemmFmt::FP8: return gemm_launch_fmt<GemmFmt::FP8>(epi, a, st);
+    case GemmFmt::F16X3: return gemm_launch_fmt<GemmFmt::F16X3>(epi, a, st);
+    case GemmFmt::F16F8: return gemm_launch_fmt<GemmFmt::F16F8>(epi, a, st);
+  }
+  fp_set_error("gemm: unknown operand format %d", (int)fmt);
+  return FP_ERR_INVALID;
+}
+
 extern "C" {
 
 int fp_abi_version(void) { return FP_ABI_VERSION; }
@@ -269,7 +281,7 @@ int fp_gemm_bf16(const void* A, int lda, const void* W, int ldw, int M, int N, i
   a.A = reinterpret_cast<const __bf16*>(A); a.lda = lda; a.W = reinterpret_cast<const __bf16*>(W); a.ldw = ldw;
   a.M = M; a.N = N; a.K = K; a.M_valid = M_valid; a.bias = bias; a.gamma = gamma; a.out = out; a.ldo = ldo;
   a.tile_override = tile;
-  return f16 ? gemm_f16_launch(epilogue, a, ST(stream)) : gemm_bf16_launch(epilogue, a, ST(stream));
+  return gemm_launch(f16 ? GemmFmt::F16 : GemmFmt::BF16, epilogue, a, ST(stream));
 }
 
 int fp_gemm_bf16_ln(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int M_valid, const float* bias, void* out, int ldo,
@@ -297,7 +309,7 @@ int fp_gemm_bf16_ln(const void* A, int lda, const void* W, int ldw, int M, int N
     FP_REQUIRE(colsum && ln_row, "fp_gemm_bf16_ln: colsum and ln_row are required");
     a.colsum = colsum; a.ln_stats = reinterpret_cast<const float2*>(ln_row); a.ln_eps = 1e-6f;
   }
-  return f16 ? gemm_f16_launch(epilogue, a, ST(stream)) : gemm_bf16_launch(epilogue, a, ST(stream));
+  return gemm_launch(f16 ? GemmFmt::F16 : GemmFmt::BF16, epilogue, a, ST(stream));
 }
 
 int fp_ln_finalize(const float* stats, int parts, int stats_stride, int rows, int dim, float eps, float* ln_row, fp_stream_t stream) {
@@ -319,7 +331,7 @@ int fp_gemm_bf16_timeline(const void* A, int lda, const void* W, int ldw, int M,
   a.M = M; a.N = N; a.K = K; a.M_valid = M_valid; a.bias = bias; a.gamma = gamma; a.out = out; a.ldo = ldo;
   a.tile_override = (epilogue >> 8) & 0xfff;
   a.dbg = dbg;
-  return gemm_bf16_launch(epilogue & 0xff, a, ST(stream));
+  return gemm_launch(GemmFmt::BF16, epilogue & 0xff, a, ST(stream));
 }
 #endif
 
@@ -334,7 +346,7 @@ int fp_gemm_fp8(const void* A, int lda, const void* W, int ldw, int M, int N, in
   a.out_scale = out_scale;
   a.tile_override = (epilogue >> 8) & 0xfff;  // tuning bits: 256 / 320 force that block tile (benchmarks, tests)
   FP_REQUIRE(a.tile_override == 0 || a.tile_override == 256 || a.tile_override == 320, "fp_gemm_fp8: bad tile override %d", a.tile_override);
-  return gemm_fp8_launch(epilogue & 0xff, a, ST(stream));
+  return gemm_launch(GemmFmt::FP8, epilogue & 0xff, a, ST(stream));
 }
 
 int fp_gemm_split(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int M_valid, const float* bias, const float* gamma,
@@ -352,7 +364,7 @@ int fp_gemm_split(const void* A, int lda, const void* W, int ldw, int M, int N, 
   a.A = reinterpret_cast<const __bf16*>(A); a.lda = lda; a.W = reinterpret_cast<const __bf16*>(W); a.ldw = ldw;
   a.M = M; a.N = N; a.K = K; a.M_valid = M_valid; a.bias = bias; a.gamma = gamma; a.out = out; a.ldo = ldo;
   a.tile_override = tile; a.acc_scale = acc_scale; a.out_scale = out_scale;
-  return f16f8 ? gemm_splitx_launch(epilogue, a, ST(stream)) : gemm_split_launch(epilogue, a, ST(stream));
+  return gemm_launch(f16f8 ? GemmFmt::F16F8 : GemmFmt::F16X3, epilogue, a, ST(stream));
 }
 
 int fp_attention_split(const void* qkv, int ld_qkv, void* out, int ld_out, int B, int n_tok, int dim, int heads, float in_scale, float out_scale,
@@ -671,7 +683,6 @@ namespace {
 enum { VIT_FULL = 0, VIT_PREFIX = 1, VIT_LAST_SELECTED = 2 };
 struct VitSelection { const int32_t* rows; const int32_t* off; int num, max_per_img; };
 enum { QKV = 0, PROJ = 1, FC1 = 2, FC2 = 3 };   // the GEMMs of a block, in order; also the index of fp_vit_block.act_scale
-enum { VK_F32, VK_BF16, VK_F16, VK_SPLIT, VK_SPLITX, VK_FP8 };   // GEMM launchers of the forward
 struct VitEpilogues { int tokens, bias, gelu, swiglu, resid; };
 constexpr VitEpilogues kF32Epi{F32_EPI_TOKENS, F32_EPI_BIAS, F32_EPI_BIAS_GELU, F32_EPI_SWIGLU, F32_EPI_LS_RESID};
 constexpr VitEpilogues kGemmEpi{GEMM_EPI_TOKENS_F32, GEMM_EPI_BIAS_BF16, GEMM_EPI_GELU_BF16, GEMM_EPI_SWIGLU_BF16, GEMM_EPI_LS_RESID_F32};
@@ -738,12 +749,13 @@ int vit_forward_impl(const fp_vit_model* m, const fp_vit_workspace* ws, const fl
   FP_REQUIRE(!fold || (ws->xb && ws->xl && ws->stats), "fp_vit_forward: ln_fold needs workspace xb, xl and stats");
   FP_REQUIRE(!fold || D % 128 == 0, "fp_vit_forward: ln_fold needs dim %% 128 == 0");
   FP_REQUIRE(mode == VIT_FULL || fold || sp || f8, "fp_vit_forward_prefix / fp_vit_block_selected: bf16 model with ln_fold, an fp8 or an f16x3 model");
-  const int kernel = fold ? (h16 ? VK_F16 : VK_BF16) : sp ? (sx ? VK_SPLITX : VK_SPLIT) : f8 ? VK_FP8 : bf ? VK_BF16 : VK_F32;
-  const VitEpilogues& epi = kernel == VK_F32 ? kF32Epi : fold ? kFoldEpi : kGemmEpi;
+  const bool f32 = !bf && !sp;             // the fp32 family: its GEMMs run on the fp32 tile (fmt unused)
+  const GemmFmt fmt = sx ? GemmFmt::F16F8 : sp ? GemmFmt::F16X3 : f8 ? GemmFmt::FP8 : h16 ? GemmFmt::F16 : GemmFmt::BF16;
+  const VitEpilogues& epi = f32 ? kF32Epi : fold ? kFoldEpi : kGemmEpi;
   const int role_epi[4] = {epi.bias, epi.resid, m->ffn_swiglu ? epi.swiglu : epi.gelu, epi.resid};  // fc1 with SwiGLU: fc1_w rows interleaved (x1_j, x2_j)
   void* const norm_out = fold ? ws->xb : f8 ? ws->a8 : ws->y;   // the A operand of qkv and fc1
   void* const attn_out = f8 ? ws->a8 : ws->y;                    // the A operand of proj
-  const int attn_dt = kernel == VK_F32 ? FP_DTYPE_F32 : sp ? FP_DTYPE_F16X3 : h16 ? FP_DTYPE_F16 : FP_DTYPE_BF16;
+  const int attn_dt = f32 ? FP_DTYPE_F32 : sp ? FP_DTYPE_F16X3 : h16 ? FP_DTYPE_F16 : FP_DTYPE_BF16;
   // folded LayerNorms: one partial sum per 128-column group of the residual GEMMs, whatever tile they run with; then (rstd, mean * rstd) per row
   const int ln_parts = D / 128;
   float2* stats = reinterpret_cast<float2*>(ws->stats);
@@ -751,15 +763,9 @@ int vit_forward_impl(const fp_vit_model* m, const fp_vit_workspace* ws, const fl
 
   // the rows every GEMM and norm runs on: the patch rows of the embedding, then all tokens, then (VIT_LAST_SELECTED) the selected ones
   int rows_valid = Mp, rows_pad = ws->m_patch_pad;
-  auto gemm = [&](int k, int e, GemmBf16Args g) -> int {
+  auto gemm = [&](GemmFmt k, int e, GemmBf16Args g) -> int {
     g.M = rows_pad; g.M_valid = rows_valid;
-    switch (k) {
-      case VK_BF16: return gemm_bf16_launch(e, g, st);
-      case VK_F16: return gemm_f16_launch(e, g, st);
-      case VK_SPLIT: return gemm_split_launch(e, g, st);
-      case VK_SPLITX: return gemm_splitx_launch(e, g, st);
-      case VK_FP8: return gemm_fp8_launch(e, g, st);
-    }
+    if (!f32) return gemm_launch(k, e, g, st);
     F32TileArgs a = zero_tile_args();   // the fp32 tile takes the valid rows only
     a.A = reinterpret_cast<const float*>(g.A); a.lda = g.lda; a.B = reinterpret_cast<const float*>(g.W); a.ldb = g.ldw;
     a.K = g.K; a.M = rows_valid; a.N = g.N; a.out = static_cast<float*>(g.out); a.ldo = g.ldo; a.bias = g.bias; a.gamma = g.gamma;
@@ -778,7 +784,7 @@ int vit_forward_impl(const fp_vit_model* m, const fp_vit_workspace* ws, const fl
     g.N = D; g.K = m->patch_k_pad; g.bias = m->patch_b; g.out = ws->x; g.ldo = D;
     g.pos = m->pos_patch; g.tok_np = np; g.tok_n = ntok; g.tok_skip = 1 + m->registers;
     g.acc_scale = sp ? m->patch_acc_scale : 0.f;
-    TRY(gemm(f8 ? VK_BF16 : kernel, epi.tokens, g));   // (the fp8 family embeds in bf16)
+    TRY(gemm(f8 ? GemmFmt::BF16 : fmt, epi.tokens, g));   // (the fp8 family embeds in bf16)
     // the folded chain starts from the token embedding: its 16-bit copy (hi, lo) and row sums
     if (fold && layer >= 0) TRY(rowstats_cast_launch(ws->x, Mtok, D, ws->xb, ldy, stats, ws->m_pad, ln_parts, st, ws->xl, h16));
   }
@@ -846,7 +852,7 @@ int vit_forward_impl(const fp_vit_model* m, const fp_vit_workspace* ws, const fl
       g.xb = reinterpret_cast<__bf16*>(ws->xb); g.ld_xb = ldy; g.stats_out = stats; g.xl = reinterpret_cast<__bf16*>(ws->xl);
     }
     FP_REQUIRE(g.W && (g.gamma || fold || !resid) && g.out_scale >= 0.f, "fp_vit_forward: GEMM %d: matrix or LayerScale missing, or a negative output scale", j);
-    return gemm(kernel, resid && pair ? GEMM_EPI_RESID_HILO : role_epi[j], g);
+    return gemm(fmt, resid && pair ? GEMM_EPI_RESID_HILO : role_epi[j], g);
   };
 
   const int i_first = mode == VIT_LAST_SELECTED ? layer : 0, i_last = mode == VIT_PREFIX ? layer - 1 : layer;

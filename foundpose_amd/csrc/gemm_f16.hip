@@ -1,3 +1,4 @@
-// Translation unit 5 of the GEMM template: IEEE fp16 operands (the "f16" mode) -- see the end of gemm_bf16.hip.
-#define FP_GEMM_TU 5
-#include "gemm_bf16.hip"
+// The GEMM kernel template (gemm_kernel.hpp) on IEEE fp16 operands: the "f16" mode.
+#include "gemm_kernel.hpp"
+
+template int gemm_launch_fmt<GemmFmt::F16>(int epi, const GemmBf16Args& a, hipStream_t st);

@@ -1,3 +1,4 @@
-// fp8 (e4m3) instantiations of the GEMM kernel template (gemm_bf16.hip): their own translation unit, see the note above gemm_fp8_launch there.
-#define FP_GEMM_TU 2
-#include "gemm_bf16.hip"
+// The GEMM kernel template (gemm_kernel.hpp) on fp8 (e4m3) operands.
+#include "gemm_kernel.hpp"
+
+template int gemm_launch_fmt<GemmFmt::FP8>(int epi, const GemmBf16Args& a, hipStream_t st);

@@ -1,3 +1,4 @@
-// split-fp16 (f16x3 mode) instantiations of the GEMM kernel template (gemm_bf16.hip): their own translation unit, see the note above gemm_fp8_launch there.
-#define FP_GEMM_TU 3
-#include "gemm_bf16.hip"
+// The GEMM kernel template (gemm_kernel.hpp) on split-fp16 operands: the f16x3 mode.
+#include "gemm_kernel.hpp"
+
+template int gemm_launch_fmt<GemmFmt::F16X3>(int epi, const GemmBf16Args& a, hipStream_t st);

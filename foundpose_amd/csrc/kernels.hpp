@@ -124,7 +124,7 @@ int launch_cyclic_select(const CyclicArgs& a, int num_pairs, hipStream_t st);
 int launch_sample_bilinear(const SampleArgs& a, hipStream_t st);
 int launch_sqrt_inplace(float* x, long long n, hipStream_t st);
 
-// ---------------------------------------------------------------- gemm_bf16.hip
+// ---------------------------------------------------------------- gemm_kernel.hpp (one gemm_*.hip per operand format)
 enum : int {
   GEMM_EPI_BIAS_BF16 = 0,     // out(bf16) = acc + bias
   GEMM_EPI_GELU_BF16 = 1,     // out(bf16) = gelu_erf(acc + bias)
@@ -165,18 +165,23 @@ struct GemmBf16Args {
   int* sat;                   // may be null; else [2] sticky saturation counters (common.hpp report_saturation): the split-fp16 / e4m3 epilogues report clamped outputs
 };
 
-int gemm_bf16_launch(int epi, const GemmBf16Args& a, hipStream_t st);
-// f16x3 mode: A [M, 2K] and W [N, 2K] split-fp16 rows (common.hpp) behind the __bf16 pointers, a.K = the logical K (multiple of 32),
-// lda / ldw in halves; out = epi(acc * a.acc_scale + bias); the BIAS / GELU (exact erf) / SwiGLU epilogues write split-fp16 rows
-// again ([M, 2N] halves, values scaled by a.out_scale), LS_RESID / TOKENS / BIAS_F32 write fp32
-int gemm_split_launch(int epi, const GemmBf16Args& a, hipStream_t st);
-// f16f8 mode: the same with A and W as f16f8 rows (common.hpp; K a multiple of 64): hi*hi on the fp16 MFMA, the two cross terms on the fp8 MFMA;
-// the GELU / SwiGLU outputs are f16f8 rows, the BIAS output (q | k | v) stays a split-fp16 row for the attention kernel
-int gemm_splitx_launch(int epi, const GemmBf16Args& a, hipStream_t st);
-int gemm_fp8_launch(int epi, const GemmBf16Args& a, hipStream_t st);  // A, W: OCP fp8 e4m3 bytes behind the __bf16 pointers
-// "f16" mode: gemm_bf16_launch's kernels with IEEE fp16 operands and fp16 outputs behind the __bf16 pointers (A, W, out of the 16-bit epilogues, xb / xl
-// of the residual epilogues); v_mfma_f32_32x32x16_f16, the nine-coefficient GELU polynomial; an fp16 output beyond +-65504 becomes inf (no report here: see common.hpp)
-int gemm_f16_launch(int epi, const GemmBf16Args& a, hipStream_t st);
+// The operand format of a GEMM; A and W (and the 16-bit outputs) sit behind the __bf16 pointers whatever it is.
+enum class GemmFmt {
+  BF16,
+  // IEEE fp16 operands and fp16 outputs (out of the 16-bit epilogues, xb / xl of the residual epilogues): the "f16" mode; v_mfma_f32_32x32x16_f16, the
+  // nine-coefficient GELU polynomial; an fp16 output beyond +-65504 becomes inf (no report here: see common.hpp)
+  F16,
+  FP8,  // OCP fp8 e4m3 bytes
+  // A [M, 2K] and W [N, 2K] split-fp16 rows (common.hpp), a.K = the logical K (multiple of 32), lda / ldw in halves: the f16x3 mode;
+  // out = epi(acc * a.acc_scale + bias); the BIAS / GELU (exact erf) / SwiGLU epilogues write split-fp16 rows again ([M, 2N] halves, values
+  // scaled by a.out_scale), LS_RESID / TOKENS / BIAS_F32 write fp32
+  F16X3,
+  // the same with A and W as f16f8 rows (common.hpp; K a multiple of 64): hi*hi on the fp16 MFMA, the two cross terms on the fp8 MFMA; the
+  // GELU / SwiGLU outputs are f16f8 rows, the BIAS output (q | k | v) stays a split-fp16 row for the attention kernel
+  F16F8,
+};
+template <GemmFmt FMT> int gemm_launch_fmt(int epi, const GemmBf16Args& a, hipStream_t st);   // instantiated by the format's gemm_*.hip
+int gemm_launch(GemmFmt fmt, int epi, const GemmBf16Args& a, hipStream_t st);   // (api.cpp) the one entry point: gemm_launch_fmt<fmt>
 
 // ---------------------------------------------------------------- dtypes of the C ABI
 enum : int { FP_DTYPE_F32 = 0, FP_DTYPE_BF16 = 1, FP_DTYPE_FP8 = 2, FP_DTYPE_F16X3 = 3, FP_DTYPE_F16F8 = 4,   // F16F8: common.hpp "f16f8 rows"

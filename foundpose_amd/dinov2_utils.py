@@ -372,7 +372,7 @@ class DinoFeatureExtractor(torch.nn.Module):
 
     def padded_rows(self, rows: int) -> int:
         """Rows of the activation buffers for `rows` tokens: whole 256-row GEMM tiles, and whole 320-row tiles as well (the taller tile of the
-        wide bf16 / fp8 GEMMs, csrc/gemm_bf16.hip) when that costs < 3 % more rows.  Row tiles without live rows are never launched."""
+        wide bf16 / fp8 GEMMs, csrc/gemm_kernel.hpp) when that costs < 3 % more rows.  Row tiles without live rows are never launched."""
         m_pad = (rows + 255) // 256 * 256
         m1280 = (rows + 1279) // 1280 * 1280
         if (self.fold_layernorm or self.precision == "fp8") and m1280 * 100 <= m_pad * 103:
