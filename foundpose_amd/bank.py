@@ -104,7 +104,7 @@ class DeviceBank:
         return self._descs_f16
 
     def prefilter_applies(self, max_det_per_obj: int, tie_mode: int) -> bool:
-        """Mirrors launch_cosine_topk_prefiltered's own gate (csrc/match.hip): the two-stage form pays off once the single-pass kernel
+        """Mirrors launch_cosine_topk_prefiltered's own gate (csrc/retrieve.hip): the two-stage form pays off once the single-pass kernel
         would stream more than ~250 MB of fp32 bank; word counts the fp16 pass (and, in the torch order, the exact fallback) handles."""
         w = self.num_words
         w_ok = w % 1024 == 0 and (w <= 2048 if tie_mode == 1 else w <= 4096)

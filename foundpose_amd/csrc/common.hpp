@@ -194,12 +194,6 @@ FP_DEVICE unsigned long long wave_min_u64(unsigned long long v) {
   return v;
 }
 
-// Non-negative floats order like their bit patterns: (d2, index) -> one u64 key whose
-// unsigned order is "smaller distance first, ties -> lower index".
-FP_DEVICE unsigned long long pack_dist_idx(float d2, unsigned idx) {
-  return ((unsigned long long)__float_as_uint(d2) << 32) | idx;
-}
-
 // XCD-aware bijective block remap (guide section 5.5 T1): consecutive logical tiles share an XCD's L2.
 FP_DEVICE unsigned xcd_remap(unsigned bid, unsigned nwg) {
   const unsigned nx = 8;

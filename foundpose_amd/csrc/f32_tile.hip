@@ -18,6 +18,7 @@
 #include <type_traits>
 #include "common.hpp"
 #include "kernels.hpp"
+#include "select.hpp"
 
 namespace {
 
@@ -59,17 +60,6 @@ FP_DEVICE void store_tile(const Frag& f, float* __restrict__ lds, int tid) {
 // image keeping KMAX sorted (d2, column) keys, one shuffle merges the halves, thread `half == 0` emits k keys.  Columns past
 // the live part of the tile are never turned into keys.
 template <int KMAX>
-FP_DEVICE void topk_insert(unsigned long long (&best)[KMAX], unsigned long long key) {
-#pragma unroll
-  for (int s = 0; s < KMAX; ++s) {  // one compare per slot: the smaller key stays, the larger moves on
-    const bool lt = key < best[s];
-    const unsigned long long lo = lt ? key : best[s], hi = lt ? best[s] : key;
-    best[s] = lo;
-    key = hi;
-  }
-}
-
-template <int KMAX>
 FP_DEVICE void tile_topk_rows(const float* dt, int k, int tid, int n0, int live_n, bool row_live, unsigned long long* out) {
   const int row = tid >> 1, half = tid & 1;
   // two independent sorted lists per thread (even / odd steps of the scan): the insertion is a chain of dependent
@@ -81,19 +71,19 @@ FP_DEVICE void tile_topk_rows(const float* dt, int k, int tid, int n0, int live_
     for (int c = 0; c < 64; c += 2) {
       const int ja = half * 64 + ((c + 32 * half) & 63), jb = half * 64 + ((c + 1 + 32 * half) & 63);  // the halves walk 32 columns apart: different LDS banks
       const float da = dt[row * LDS_STRIDE + ja], db = dt[row * LDS_STRIDE + jb];
-      topk_insert<KMAX>(best, ja >= live_n ? ~0ull : pack_dist_idx(da, (unsigned)(n0 + ja)));
-      topk_insert<KMAX>(bestb, jb >= live_n ? ~0ull : pack_dist_idx(db, (unsigned)(n0 + jb)));
+      sorted_insert(best, ja >= live_n ? ~0ull : pack_dist_idx(da, (unsigned)(n0 + ja)));
+      sorted_insert(bestb, jb >= live_n ? ~0ull : pack_dist_idx(db, (unsigned)(n0 + jb)));
     }
 #pragma unroll
     for (int s = 0; s < KMAX; ++s)
-      if (s < k) topk_insert<KMAX>(best, bestb[s]);
+      if (s < k) sorted_insert(best, bestb[s]);
   }
   unsigned long long other[KMAX];
 #pragma unroll
   for (int s = 0; s < KMAX; ++s) other[s] = __shfl_xor(best[s], 1, 64);
 #pragma unroll
   for (int s = 0; s < KMAX; ++s)
-    if (s < k) topk_insert<KMAX>(best, other[s]);
+    if (s < k) sorted_insert(best, other[s]);
   if (half == 0 && row_live) {
 #pragma unroll
     for (int s = 0; s < KMAX; ++s)

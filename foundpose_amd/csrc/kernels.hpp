@@ -42,7 +42,7 @@ struct F32TileArgs {
 
 int f32_tile_launch(int epi, const F32TileArgs& a, int max_m, int max_n, int pairs, hipStream_t st);
 
-// ---------------------------------------------------------------- match.hip
+// ---------------------------------------------------------------- match.hip, retrieve.hip
 struct CyclicArgs {
   const int* q_off;        // [B+1] query-point segment per detection
   const int* tpl_ids;      // [B*n_slots] template id per (detection, slot); <0 = empty slot; global, or object-local with tpl_base

@@ -61,7 +61,7 @@ FP_HD int lg2(int n) {  // floor(log2(n)), n >= 1
 
 // ---- heap primitives (max-heap w.r.t. `gt` as "less": the root is the WORST of the kept elements).  Written over an
 // accessor (get / set by index) so the same moves run on an array in memory and on a heap whose element j lives in the
-// registers of lane j of a wavefront (match.hip: the strict top-n keeps its n-element heap there).
+// registers of lane j of a wavefront (retrieve.hip: the strict top-n keeps its n-element heap there).
 struct PtrAcc {
   Elem* p;
   FP_HD Elem get(int i) const { return p[i]; }
