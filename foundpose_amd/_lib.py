@@ -92,6 +92,12 @@ _PROTOS = {
     "fp_vsd_counts": [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp],
     "fp_featuremetric_refine": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32,
                                 vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "fp_vis_pca_colorize": [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
+    "fp_vis_mask_tint": [vp, vp, i32, i32, i32, vp, vp],
+    "fp_vis_contour": [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp],
+    "fp_vis_resize_area": [vp, i32, i32, i32, i32, i32, vp, vp],
+    "fp_vis_draw_matches": [vp, vp, i32, i32, i32, i32, vp, f32, f32, f32, vp, vp],
+    "fp_vis_scene_composite": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
 }
 
 _lib = None
@@ -180,6 +186,7 @@ def refine_scratch_bytes(num_det: int, max_points: int) -> int:
 
 
 TEXTURE_MAX_SIDE = 16384  # FP_TEXTURE_MAX_SIDE of the header
+VIS_MAX_MATCHES, VIS_MAX_DILATE = 1024, 8  # FP_VIS_MAX_MATCHES / FP_VIS_MAX_DILATE of the header
 
 
 def texture_levels(width: int, height: int):

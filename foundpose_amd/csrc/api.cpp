@@ -960,4 +960,62 @@ int fp_vit_sample_features_selected(const fp_vit_model* m, const fp_vit_workspac
                           grid_h, grid_w, img_w, img_h, points, point_img, num_points, out, ST(stream), row_map, m->weight_dtype == FP_DTYPE_F16 ? ws->sat : nullptr);
 }
 
+// ------------------------------------------------------------------ result pictures (vis.hip)
+static bool vis_side(int v) { return v >= 1 && v <= FP_VIS_MAX_SIDE; }
+
+int fp_vis_pca_colorize(const float* map, int batch, int gh, int gw, int C, int out_h, int out_w, int dim_num, int dim_den, float* range,
+                        uint8_t* out, fp_stream_t stream) {
+  FP_REQUIRE(map && range && out, "fp_vis_pca_colorize: null pointer");
+  FP_REQUIRE(batch >= 1 && batch <= 65535 && vis_side(gh) && vis_side(gw) && vis_side(out_h) && vis_side(out_w),
+             "fp_vis_pca_colorize: bad sizes (batch %d, map %d x %d, picture %d x %d)", batch, gh, gw, out_h, out_w);
+  FP_REQUIRE(C >= 3, "fp_vis_pca_colorize: the map needs at least 3 channels, got %d", C);
+  FP_REQUIRE(dim_num >= 0 && dim_num <= dim_den && dim_den >= 1 && dim_den <= 255, "fp_vis_pca_colorize: dimming %d / %d outside 0 <= num <= den <= 255",
+             dim_num, dim_den);
+  return launch_vis_pca_colorize(map, batch, gh, gw, C, out_h, out_w, dim_num, dim_den, range, out, ST(stream));
+}
+
+int fp_vis_mask_tint(const uint8_t* img, const uint8_t* mask, int batch, int h, int w, uint8_t* out, fp_stream_t stream) {
+  FP_REQUIRE(img && mask && out, "fp_vis_mask_tint: null pointer");
+  FP_REQUIRE(batch >= 1 && batch <= 65535 && vis_side(h) && vis_side(w), "fp_vis_mask_tint: bad sizes (batch %d, %d x %d)", batch, h, w);
+  return launch_vis_mask_tint(img, mask, (long long)batch * h * w, out, ST(stream));
+}
+
+int fp_vis_contour(const uint8_t* mask, int batch, int h, int w, int dilate_iterations, int r, int g, int b, uint8_t* img,
+                   fp_stream_t stream) {
+  FP_REQUIRE(mask && img, "fp_vis_contour: null pointer");
+  FP_REQUIRE(batch >= 1 && batch <= 65535 && vis_side(h) && vis_side(w), "fp_vis_contour: bad sizes (batch %d, %d x %d)", batch, h, w);
+  FP_REQUIRE(dilate_iterations >= 0 && dilate_iterations <= FP_VIS_MAX_DILATE, "fp_vis_contour: dilate_iterations %d outside [0, %d]",
+             dilate_iterations, FP_VIS_MAX_DILATE);
+  FP_REQUIRE(r >= 0 && r <= 255 && g >= 0 && g <= 255 && b >= 0 && b <= 255, "fp_vis_contour: colour (%d, %d, %d) outside [0, 255]", r, g, b);
+  return launch_vis_contour(mask, batch, h, w, dilate_iterations, r, g, b, img, ST(stream));
+}
+
+int fp_vis_resize_area(const uint8_t* src, int batch, int h, int w, int out_h, int out_w, uint8_t* out, fp_stream_t stream) {
+  FP_REQUIRE(src && out, "fp_vis_resize_area: null pointer");
+  FP_REQUIRE(batch >= 1 && batch <= 65535 && vis_side(h) && vis_side(w) && out_h >= 1 && out_w >= 1, "fp_vis_resize_area: bad sizes");
+  FP_REQUIRE(out_h <= h && out_w <= w, "fp_vis_resize_area: %d x %d -> %d x %d is not a downscaling", w, h, out_w, out_h);
+  return launch_vis_resize_area(src, batch, h, w, out_h, out_w, out, ST(stream));
+}
+
+int fp_vis_draw_matches(const float* segments, const int32_t* counts, int batch, int max_matches, int h, int w, const float* colour,
+                        float alpha, float lw, float radius, uint8_t* tile, fp_stream_t stream) {
+  FP_REQUIRE(segments && counts && colour && tile, "fp_vis_draw_matches: null pointer");
+  FP_REQUIRE(batch >= 1 && batch <= 65535 && vis_side(h) && vis_side(w), "fp_vis_draw_matches: bad sizes (batch %d, %d x %d)", batch, h, w);
+  FP_REQUIRE(max_matches >= 1 && max_matches <= FP_VIS_MAX_MATCHES, "fp_vis_draw_matches: max_matches %d outside [1, %d]", max_matches,
+             FP_VIS_MAX_MATCHES);
+  FP_REQUIRE((reinterpret_cast<uintptr_t>(segments) & 15) == 0, "fp_vis_draw_matches: segments must be 16-byte aligned");
+  FP_REQUIRE(alpha >= 0.f && alpha <= 1.f && lw >= 0.f && lw <= 64.f && radius >= 0.f && radius <= 64.f,
+             "fp_vis_draw_matches: alpha in [0, 1], lw and radius in [0, 64]");
+  for (int c = 0; c < 3; ++c) FP_REQUIRE(colour[c] >= 0.f && colour[c] <= 255.f, "fp_vis_draw_matches: colour outside [0, 255]");
+  return launch_vis_draw_matches(segments, counts, batch, max_matches, h, w, colour, alpha, lw, radius, tile, ST(stream));
+}
+
+int fp_vis_scene_composite(const float* depth, const uint8_t* colours, int layers, int h, int w, const uint8_t* img, uint8_t* out,
+                           int32_t* ids, fp_stream_t stream) {
+  FP_REQUIRE(depth && colours && img && out && ids, "fp_vis_scene_composite: null pointer");
+  FP_REQUIRE(layers >= 1 && layers <= FP_VIS_MAX_LAYERS && vis_side(h) && vis_side(w), "fp_vis_scene_composite: bad sizes (%d layers, %d x %d)",
+             layers, h, w);
+  return launch_vis_scene_composite(depth, colours, layers, h, w, img, out, ids, ST(stream));
+}
+
 }  // extern "C"

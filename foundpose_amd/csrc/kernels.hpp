@@ -324,6 +324,17 @@ struct VsdArgs {
 };
 int launch_vsd_counts(const VsdArgs& a, long long num_blocks, hipStream_t st);
 
+// ---------------------------------------------------------------- vis.hip
+int launch_vis_mask_tint(const uint8_t* img, const uint8_t* mask, long long pixels, uint8_t* out, hipStream_t st);
+int launch_vis_contour(const uint8_t* mask, int batch, int h, int w, int dil, int r, int g, int b, uint8_t* img, hipStream_t st);
+int launch_vis_scene_composite(const float* depth, const uint8_t* colours, int layers, int h, int w, const uint8_t* img, uint8_t* out,
+                               int* ids, hipStream_t st);
+int launch_vis_resize_area(const uint8_t* src, int batch, int h, int w, int oh, int ow, uint8_t* out, hipStream_t st);
+int launch_vis_pca_colorize(const float* map, int batch, int gh, int gw, int C, int h, int w, int num, int den, float* range, uint8_t* out,
+                            hipStream_t st);
+int launch_vis_draw_matches(const float* segs, const int* counts, int batch, int max_matches, int h, int w, const float* colour, float alpha,
+                            float lw, float radius, uint8_t* tile, hipStream_t st);
+
 // ---------------------------------------------------------------- pnp.hip
 struct PnpArgs {
   const float* coord_2d;   // [pairs, k_max, 2] pixels

@@ -3,11 +3,12 @@ reference's names and defaults, CNOS detections in, `estimated-poses.json` per o
 
 What differs from the reference loop, by design: the instances of an image go through the crop producer, the extractor,
 the matching and the PnP tail as ONE batch on the device (the reference handles them one at a time on the CPU), the
-ground-truth evaluation (opt-in: eval_models / --eval-gt) is one fp_pose_errors launch per frame, and the rendering /
-visualisation branches (HTML) are not part of this path.
+ground-truth evaluation (opt-in: eval_models / --eval-gt) is one fp_pose_errors launch per frame, and the result pictures
+(opt-in: renderer= / --vis, with vis_results; vis_util) are composited on the device, one tile per
+estimated pose and one summary per frame; the HTML branches are not part of this path.
 
   python -m foundpose_amd.infer --opts configs/infer/lmo.json --dataset-dir <bop split dir> --detections <cnos json> \\
-         --repre-dir <output>/object_repre --output-dir <output>/inference
+         --repre-dir <output>/object_repre --output-dir <output>/inference [--vis [--models-dir <models>]]
 """
 
 import argparse
@@ -19,7 +20,7 @@ from typing import Any, Dict, Iterable, List, NamedTuple, Optional, Sequence, Tu
 import numpy as np
 import torch
 
-from . import crop_util, engine as fe, eval_util, feature_util, infer_pose_util, pnp_util, refine_util, repre_util
+from . import crop_util, engine as fe, eval_util, feature_util, infer_pose_util, pnp_util, refine_util, repre_util, vis_util
 from .bank import DeviceBank
 
 
@@ -76,12 +77,22 @@ def load_opts(path_or_dict) -> InferOpts:
 def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBasedObjectRepre, frames: Iterable[Dict[str, Any]],
                  detections: Dict[Any, Any], extractor=None, num_target_insts: Optional[Dict[Tuple[int, int], int]] = None,
                  precision: str = "bf16", seed: int = 0, weights: Optional[str] = None,
-                 eval_model: Optional[eval_util.EvalModel] = None) -> eval_util.PoseEvaluator:
+                 eval_model: Optional[eval_util.EvalModel] = None, renderer=None, output_dir: Optional[str] = None,
+                 frame_poses: Optional[Dict[Tuple[int, int], List[Tuple[int, np.ndarray]]]] = None) -> eval_util.PoseEvaluator:
     """One object over a stream of frames (the body of infer.py's per-object loop).  A frame is
     {"scene_id", "im_id", "image": HWC uint8 or float [0,1] (numpy or tensor), "camera": PinholePlaneCameraModel (c2w)}.
     eval_model (eval_util.load_eval_model): instances whose annotation carries a ground-truth `pose` (model -> world) are
     evaluated against it (PoseEvaluator.update_batch, one launch per frame, inlier radius opts.pnp_inlier_thresh as in
-    infer.py:831); without it, or for annotations without a pose, the driver records what it always has."""
+    infer.py:831); without it, or for annotations without a pose, the driver records what it always has.
+    renderer (a HipRasterizer holding this object's mesh under `object_lid`) together with opts.vis_results: one picture per estimated
+    pose is written to vis_util.tile_path(output_dir, ...) and its share of the time recorded as times["vis"]; frame_poses, when
+    given, collects (object_lid, T_m2c in the frame's own camera) per (scene_id, im_id) for the frame summaries.  Without a renderer
+    nothing of this runs, whatever vis_results says."""
+    vis = renderer is not None and bool(opts.vis_results)
+    if vis:   # refused before any device work
+        vis_util.check_opts(opts)
+        if output_dir is None:
+            raise ValueError("pictures need an output_dir")
     if opts.match_template_type != "tfidf":
         raise ValueError(f"Unknown matching type '{opts.match_template_type}'.")
     if opts.match_feat_matching_type != "cyclic_buddies":
@@ -107,6 +118,7 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
     eng.record_stage_times = True
     evaluator = eval_util.PoseEvaluator()
     vertices = repre.vertices.cpu().numpy()
+    vis_templates = repre.templates.cuda() if vis else None
 
     def annotated(inst):
         return eval_model is not None and getattr(inst.get("gt_anno"), "pose", None) is not None
@@ -170,7 +182,7 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
             crop_masks, cams = masks, [cam] * len(kept)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        res = eng.infer_batch(crops, crop_masks, [0] * len(kept), keep_feature_map=refine)
+        res = eng.infer_batch(crops, crop_masks, [0] * len(kept), keep_feature_map=refine or vis)
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
@@ -197,6 +209,24 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
                  "pose_coarse": (t3 - t2) / n, "final_select": (t4 - t3) / n}
         if refine:
             times["pose_refine"] = (t5 - t4) / n
+        if vis:   # compositing on the device, one copy of the batch's tiles to pinned memory, PNG encoding on the host
+            tv = time.perf_counter()
+            to_T = lambda R, t: np.block([[np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3, 1)], [np.array([[0.0, 0.0, 0.0, 1.0]])]])
+            coarse = [to_T(best["R"][b].cpu().numpy(), best["t"][b].cpu().numpy()) if found[b] else None for b in range(n)] if refine else [None] * n
+            final = [to_T(Rb[b], tb[b]) if found[b] else None for b in range(n)]
+            gt_pose = [getattr(inst.get("gt_anno"), "pose", None) for _, inst in kept]
+            gt = [None if p is None else np.linalg.inv(cams[b].T_world_from_eye) @ to_T(p.R, p.t) for b, p in enumerate(gt_pose)]
+            tiles, vis_records = vis_util.vis_inference_results_batch(
+                crops, crop_masks, cams, res, found, cid, coarse, final, repre, renderer, object_lid, extractor=extractor,
+                poses_gt=gt if any(g is not None for g in gt) else None, draw_coarse=refine, vis_corresp_top_n=opts.vis_corresp_top_n,
+                vis_feat_map=opts.vis_feat_map, vis_for_paper=opts.vis_for_paper, templates=vis_templates)
+            host = vis_util.tiles_to_host(tiles)
+            for b, (inst_j, _) in enumerate(kept):
+                if found[b]:
+                    vis_util.write_png(vis_util.tile_path(output_dir, scene_id, im_id, object_lid, inst_j, 0), host[b])
+                    for note in vis_records[b]["notes"]:
+                        print(f"vis: scene {scene_id} image {im_id} object {object_lid} instance {inst_j}: {note}")
+            times["vis"] = (time.perf_counter() - tv) / n
         pending = []   # consecutive annotated hypotheses: evaluated in one launch, recorded in instance order
 
         def flush():
@@ -212,6 +242,8 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
             T_m2c = np.eye(4)
             T_m2c[:3, :3], T_m2c[:3, 3] = Rb[b], tb[b]
             T_m2w = cams[b].T_world_from_eye @ T_m2c  # infer.py:661-666
+            if vis and frame_poses is not None:
+                frame_poses.setdefault((scene_id, im_id), []).append((object_lid, np.linalg.inv(cam.T_world_from_eye) @ T_m2w))
             if annotated(inst):   # infer.py:806-835
                 bank_cams = repre.template_cameras_cam_from_model   # (a bank without template cameras: no template orientation error)
                 tpl_cams = [bank_cams[int(cc["template_id"])] for cc in corr_all] if len(bank_cams) else []
@@ -231,26 +263,50 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
 
 def infer(opts: InferOpts, frames_by_object, detections, repres: Dict[int, repre_util.FeatureBasedObjectRepre], output_dir: str, extractor=None,
           precision: str = "bf16", num_target_insts: Optional[Dict[int, Dict[Tuple[int, int], int]]] = None, weights: Optional[str] = None,
-          eval_models: Optional[Dict[int, eval_util.EvalModel]] = None) -> List[str]:
+          eval_models: Optional[Dict[int, eval_util.EvalModel]] = None, renderer=None) -> List[str]:
     """All objects: `frames_by_object(lid)` yields the frames that show object `lid`; one estimated-poses.json per object
     under <output_dir>/<lid>/ (infer.py:813-816), then the BOP19 csv.
     num_target_insts: {object lid: {(scene_id, im_id): inst_count}} from test_targets_bop19.json -- the number of poses to
     estimate per (image, object) is num_preds_factor x inst_count (infer.py:308-346); frames without an entry are skipped.
-    eval_models: {object lid: eval_util.EvalModel} -- evaluate the hypotheses of frames whose annotations carry a pose."""
+    eval_models: {object lid: eval_util.EvalModel} -- evaluate the hypotheses of frames whose annotations carry a pose.
+    renderer: a HipRasterizer holding the mesh of every object under its lid -- with opts.vis_results, one picture per estimated pose
+    (<output_dir>/<lid>/<scene>_<im>_<lid>_<inst>_0.png) and, after all objects, one summary per frame (<output_dir>/vis/<scene>_<im>.png)
+    with every final pose in the frame's own camera.  Without it no picture is made and nothing else changes."""
     lids = list(opts.object_lids) if opts.object_lids is not None else sorted(repres)
+    if renderer is not None and not opts.vis_results:
+        print("vis_results is false in the options: no pictures are written")
+        renderer = None
+    if renderer is not None:
+        vis_util.check_opts(opts)
+    frame_poses: Dict[Tuple[int, int], List[Tuple[int, np.ndarray]]] = {}
     if extractor is None:
         extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
     paths = []
     for lid in lids:
         ev = infer_object(opts, lid, repres[lid], frames_by_object(lid), detections, extractor,
                           num_target_insts=None if num_target_insts is None else num_target_insts.get(lid, {}),
-                          eval_model=None if eval_models is None else eval_models.get(lid))
+                          eval_model=None if eval_models is None else eval_models.get(lid), renderer=renderer, output_dir=output_dir,
+                          frame_poses=frame_poses if renderer is not None else None)
         if opts.save_estimates:
             p = os.path.join(output_dir, str(lid), "estimated-poses.json")
             ev.save_results_json(p)
             paths.append(p)
     if opts.save_estimates:
         paths.append(eval_util.prepare_bop_submission(output_dir, opts.object_dataset, lids))
+    if renderer is not None and frame_poses:   # the frames are read again rather than kept: one image in memory at a time
+        done = set()
+        for lid in lids:
+            for frame in frames_by_object(lid):
+                key = (frame["scene_id"], frame["im_id"])
+                if key in done or key not in frame_poses:
+                    continue
+                done.add(key)
+                pic, _, notes = vis_util.vis_frame_summary(frame["image"], frame["camera"], [(o, T, None) for o, T in frame_poses[key]], renderer)
+                for note in notes:
+                    print(f"vis: scene {key[0]} image {key[1]}: {note}")
+                p = vis_util.summary_path(output_dir, *key)
+                vis_util.write_png(p, vis_util.tiles_to_host(pic))
+                paths.append(p)
     return paths
 
 
@@ -336,7 +392,10 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
                     "Without a checkpoint the run fails: there is no random-weight fallback")
     ap.add_argument("--eval-gt", action="store_true", help="evaluate the poses against the split's ground truth (scene_gt.json, scene_gt_info.json, "
                     "mask_visib/): MSSD, MSPD and the inlier counts go into estimated-poses.json")
-    ap.add_argument("--models-dir", default=None, help="with --eval-gt: models_info.json and obj_XXXXXX.ply (default: <dataset root>/models)")
+    ap.add_argument("--models-dir", default=None, help="with --eval-gt / --vis: models_info.json and obj_XXXXXX.ply (default: <dataset root>/models)")
+    ap.add_argument("--vis", action="store_true", help="write the result pictures (when vis_results is true in the options): one tile per estimated pose, "
+                    "<output-dir>/<lid>/<scene>_<im>_<lid>_<inst>_0.png (pose contours, retrieved templates, matches), and one summary per frame, "
+                    "<output-dir>/vis/<scene>_<im>.png; the object meshes come from --models-dir")
     args = ap.parse_args(argv)
     opts = load_opts(args.opts)
     # the checkpoint is resolved before anything else is read: a missing one must fail in seconds, not after the banks are loaded
@@ -350,13 +409,23 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     for t in targets:
         n_inst.setdefault(t["obj_id"], {})[(t["scene_id"], t["im_id"])] = t["inst_count"]
     eval_models = None
+    models_dir = args.models_dir or os.path.join(os.path.dirname(os.path.abspath(args.dataset_dir)), "models")
+    renderer = None
+    if args.vis and opts.vis_results:
+        from .renderer import HipRasterizer
+        vis_util.check_opts(opts)
+        renderer = HipRasterizer("cuda")
+        for lid in lids:
+            renderer.add_object_model(lid, os.path.join(models_dir, f"obj_{lid:06d}.ply"))
+    elif args.vis:
+        print("vis_results is false in the options: no pictures are written")
     if args.eval_gt:
-        models_dir = args.models_dir or os.path.join(os.path.dirname(os.path.abspath(args.dataset_dir)), "models")
         with open(os.path.join(models_dir, "models_info.json")) as f:
             models_info = json.load(f)
         eval_models = {lid: eval_util.load_eval_model(models_dir, lid, opts.max_sym_disc_step, models_info) for lid in lids}
     out = infer(opts._replace(object_lids=list(lids)), lambda lid: load_bop_frames(args.dataset_dir, targets, lid, with_gt=args.eval_gt), detections,
-                repres, args.output_dir, extractor=extractor.to("cuda"), precision=args.precision, num_target_insts=n_inst, eval_models=eval_models)
+                repres, args.output_dir, extractor=extractor.to("cuda"), precision=args.precision, num_target_insts=n_inst, eval_models=eval_models,
+                renderer=renderer)
     print("\n".join(out))
 
 

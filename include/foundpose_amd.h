@@ -588,6 +588,46 @@ int fp_featuremetric_refine(const float* map, int64_t sb, int64_t sy, int64_t sx
                             double* R_out, double* t_out, double* cost_in, double* cost_out, int32_t* num_points,
                             int32_t* iters_used, int32_t* status, double* normal_eq, fp_stream_t stream);
 
+/* ---- result pictures (utils/vis_util.py:179-687 vis_inference_results in its vis_for_paper layout; DESIGN.md section 12;
+ * tests/vis_ref.py restates every entry) ---------------------------------------------------------------------------------
+ * Images are uint8 HWC (3 channels), contiguous, with a leading batch dimension; sides lie in [1, FP_VIS_MAX_SIDE].  One thread
+ * produces one output pixel from a gather in a fixed order (no atomics): a detection's picture is bit-identical across runs
+ * and batch compositions.  cv2 and matplotlib are not restated: the contract is this project's own (edge pixels are not
+ * Canny's, the anti-aliasing is not Agg's).  Bad sizes or NULL pointers: FP_ERR_INVALID, nothing written. */
+#define FP_VIS_MAX_SIDE 16384
+#define FP_VIS_MAX_MATCHES 1024
+#define FP_VIS_MAX_DILATE 8
+#define FP_VIS_MAX_LAYERS 4096
+/* normalize_data (vis_base_util.py:26) + nearest upsampling: map fp32 [batch, gh, gw, C] (C >= 3, channels 0..2 are used);
+ * lo / hi = min / max over the gh gw 3 values of a detection (ONE range for the three channels), written to range fp32
+ * [batch, 2] (scratch and output); out [batch, out_h, out_w, 3] = trunc(255 ((x - lo) / (hi - lo))) in fp32, the quotient first so that hi maps to 255 (0 when hi == lo), of
+ * the cell (floor(y gh / out_h), floor(x gw / out_w)), then dimmed in integers: (v dim_num) / dim_den with 0 <= dim_num <= dim_den
+ * <= 255 (1 / 1: unchanged; 9 / 10 for the query side of the match picture, vis_util.py's 0.9 factor). */
+int fp_vis_pca_colorize(const float* map, int batch, int gh, int gw, int C, int out_h, int out_w, int dim_num, int dim_den, float* range,
+                        uint8_t* out, fp_stream_t stream);
+/* vis_util.py:286-292 with the white accent colour: out = (img + 255) >> 1 per channel where mask [batch, h, w] != 0, img elsewhere. */
+int fp_vis_mask_tint(const uint8_t* img, const uint8_t* mask, int batch, int h, int w, uint8_t* out, fp_stream_t stream);
+/* Replaces add_contour_overlay (cv2.Canny + cv2.dilate; unpinned).  A pixel of mask [batch, h, w] is an edge when it is set and
+ * one of its 4 neighbours inside the image is unset; the edge map is dilated dilate_iterations (0..FP_VIS_MAX_DILATE) times by a
+ * 3 x 3 square; those pixels of img [batch, h, w, 3] are overwritten with (r, g, b), each in [0, 255].  In place. */
+int fp_vis_contour(const uint8_t* mask, int batch, int h, int w, int dilate_iterations, int r, int g, int b, uint8_t* img,
+                   fp_stream_t stream);
+/* Area-average downscaling of src [batch, h, w, 3] to out [batch, out_h, out_w, 3] (out_h <= h, out_w <= w, else FP_ERR_INVALID):
+ * the footprint of output pixel x is [x w / out_w, (x + 1) w / out_w), likewise in y; the value is the footprint-area-weighted mean,
+ * computed exactly in integers and rounded to nearest (half up). */
+int fp_vis_resize_area(const uint8_t* src, int batch, int h, int w, int out_h, int out_w, uint8_t* out, fp_stream_t stream);
+/* plot_matches: counts[b] <= max_matches <= FP_VIS_MAX_MATCHES segments (x0, y0, x1, y1) fp32 [batch, max_matches, 4] with a disc at both
+ * ends, drawn in place onto tile [batch, h, w, 3].  Per pixel, centre p = (x + 1/2, y + 1/2), the matches in input order, for each its
+ * segment (coverage clamp(1/2 + lw / 2 - dist(p, segment), 0, 1)) and then its two discs (clamp(1/2 + radius - |p - c|, 0, 1)):
+ * out = out (1 - alpha cov) + colour alpha cov in fp32, rounded to nearest once at the end.  colour: HOST fp32 [3] in [0, 255]. */
+int fp_vis_draw_matches(const float* segments, const int32_t* counts, int batch, int max_matches, int h, int w, const float* colour,
+                        float alpha, float lw, float radius, uint8_t* tile, fp_stream_t stream);
+/* One frame with several posed objects: depth fp32 [layers, h, w] in mm, 0 = background (fp_render_raster's output), colours uint8
+ * [layers, 3].  ids int32 [h, w] = the layer with the smallest positive depth (ties: the lowest layer), -1 where none;
+ * out [h, w, 3] = (img + colours[id]) >> 1 where a layer covers the pixel, img elsewhere.  1 <= layers <= FP_VIS_MAX_LAYERS. */
+int fp_vis_scene_composite(const float* depth, const uint8_t* colours, int layers, int h, int w, const uint8_t* img, uint8_t* out,
+                           int32_t* ids, fp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
