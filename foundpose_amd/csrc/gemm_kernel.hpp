@@ -3,7 +3,9 @@
 // This is the arithmetic the reference delegates to the DINOv2 backbone's nn.Linear layers
 // (call site /root/reference/utils/dinov2_utils.py:257).  MI355X design:
 //   * block tile 256x256x64, 512 threads = 2x4 waves, each wave 128x64 = 4x2 v_mfma_f32_32x32x16_bf16
-//     (128x128, 4 waves for small shapes)
+//     (128x128, 4 waves for small shapes; 64x128 for the residual GEMMs of one or two crops; 320x256 = waves of 5x2 tiles for wide outputs whose round
+//     count favours it; 352x256 = wave rows of 6x2 and 5x2 tiles, 192 + 160 rows, for the residual GEMMs on the (hi, lo) stream where two rounds of it
+//     replace three of 256 rows -- every shape gives the same bits)
 //   * A and W tiles go HBM/L2 -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds, 16 B/lane, no VGPR round trip), double
 //     buffered, one barrier per K-tile, next tile's DMA in flight under the MFMAs; on the 8-wave tile only ONE wave
 //     row issues the DMA (each SIMD hosts a wave of either row: the partner keeps the matrix pipe fed while the
@@ -23,6 +25,7 @@
 #pragma once
 #include "common.hpp"
 #include "kernels.hpp"
+#include <type_traits>
 
 namespace {
 
@@ -182,7 +185,11 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
   constexpr bool SPOUT = SP && (EPI == GEMM_EPI_BIAS_BF16 || EPI == GEMM_EPI_GELU_BF16 || EPI == GEMM_EPI_SWIGLU_BF16);
   static_assert(NSTAGE == 2 || (NSTAGE == 4 && !F8 && !SP && WM * WN != 8), "the deep pipeline exists for the small bf16 / fp16 tiles");
   static_assert(!F8OUT || (F8 && (EPI == GEMM_EPI_GELU_BF16 || EPI == GEMM_EPI_SWIGLU_BF16)), "fp8 output: GELU / SwiGLU epilogues of the fp8 kernels");
-  constexpr int NW = WM * WN, NT = NW * 64, TM = BM / WM / 32, TN = BN / WN / 32;
+  // Wave row wm owns the TM 32-row tiles from row wm * WROWS on.  Where BM / 32 does not split evenly over the wave rows (352 = 11 tiles over two rows:
+  // 192 + 160) the last wave row holds one tile fewer: tile_on(i) is wave-uniform, and an absent tile is neither multiplied nor stored.
+  constexpr int NW = WM * WN, NT = NW * 64, MT = BM / 32, TM = (MT + WM - 1) / WM, WROWS = TM * 32, TN = BN / WN / 32;
+  constexpr bool UNEVEN = MT % WM != 0;
+  static_assert(BM % 32 == 0 && (!UNEVEN || (WM == 2 && FMT != GemmFmt::FP8 && FMT != GemmFmt::F16X3 && FMT != GemmFmt::F16F8)), "uneven wave rows: the bf16 / fp16 loop of the 2 x 4 wave grid");
   constexpr bool HILO = EPI == GEMM_EPI_RESID_HILO;  // the residual stream as (hi, lo) bf16 arrays: hi IS the next GEMM's A operand
   constexpr bool RESID = EPI == GEMM_EPI_LS_RESID_F32 || EPI == GEMM_EPI_RESID_F32 || HILO;  // residual read-modify-write epilogues
   constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2, STAGE = A_BYTES + B_BYTES;
@@ -193,10 +200,11 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
   constexpr int NISSUE = ASYM ? NW / 2 : NW;
   constexpr int A_INSTR = BM / 8 / NISSUE, B_INSTR = BN / 8 / NISSUE;  // DMA instructions per issuing wave per K-tile
   constexpr int PIECES = A_INSTR + B_INSTR;
-  static_assert(PIECES % 2 == 0, "staging split");  // quarters of the piece list per k-step (uneven for the 320-row tile: 18 pieces), halves in the fp8 / f16x3 loops
+  static_assert(PIECES % 2 == 0 || !(F8 || SP), "staging split");  // quarters of the piece list per k-step (uneven for the 320- and 352-row tiles: 18 and 19 pieces), halves in the fp8 / f16x3 loops
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 stages][A | B]
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN, l31 = lane & 31, kh = lane >> 5;
+  auto tile_on = [&](int i) { return !UNEVEN || wm * TM + i < MT; };
 
   const unsigned nwg = gridDim.x;
   const unsigned lid = xcd_remap(blockIdx.x, nwg);
@@ -232,7 +240,10 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     // DMA piece q (0 .. PIECES-1) of this wave for K-tile t into stage buffer `buf`
-    static_assert(A_INSTR % 2 == 0 && B_INSTR % 2 == 0, "row-group parity of a piece must be a compile-time property");
+    // (an odd number of A pieces per wave -- 11 for the 352-row tile -- deals the row groups out round-robin instead: piece q of issuing wave iw is row group
+    //  q * NISSUE + iw, whose parity is that of iw: one lane offset per wave)
+    constexpr bool A_ILV = A_INSTR % 2 != 0;
+    static_assert((A_INSTR % 2 == 0 || (NISSUE % 2 == 0 && BM / 8 % NISSUE == 0)) && B_INSTR % 2 == 0, "row-group parity of a piece must be a compile-time (or per-wave) property");
     // the resources start at this tile's first row (32-bit offsets then never exceed one tile's extent, whatever the
     // size of the matrix) and end at the end of the matrix, clipped to the 4-GiB range of a buffer resource
     auto tile_rsrc = [](const __bf16* base, int row0, int rows, int ld) {
@@ -244,9 +255,14 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
     const unsigned voff_w[2] = {stage_lane_offset(a.ldw, lane, 0), stage_lane_offset(a.ldw, lane, 1)};
     const bool issuer = !ASYM || wm == 0;  // wave-uniform
     const int iw = ASYM ? wave % NISSUE : wave;
+    const unsigned voff_a_w = voff_a[iw & 1];
+    // one VM instruction per call and issuing wave: the vmcnt immediates of the deep pipeline count on it
     auto stage_piece = [&](int q, int t, char* buf) {
       if (!issuer) return;
-      if (q < A_INSTR) stage_rows(rsrc_a, voff_a[q & 1], a.lda, 0, t * BK, buf, iw * A_INSTR + q);
+      if (q < A_INSTR) {
+        if constexpr (A_ILV) stage_rows(rsrc_a, voff_a_w, a.lda, 0, t * BK, buf, q * NISSUE + iw);
+        else stage_rows(rsrc_a, voff_a[q & 1], a.lda, 0, t * BK, buf, iw * A_INSTR + q);
+      }
       else stage_rows(rsrc_w, voff_w[(q - A_INSTR) & 1], a.ldw, 0, t * BK, buf + A_BYTES, iw * B_INSTR + (q - A_INSTR));
     };
 #pragma unroll
@@ -270,7 +286,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
       if (a.ln_stats) {
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-          const float2 st = a.ln_stats[m0 + wm * (BM / WM) + i * 32 + l31];
+          if (!tile_on(i)) continue;
+          const float2 st = a.ln_stats[m0 + wm * WROWS + i * 32 + l31];
           ln_rs[i] = st.x;
           ln_mrs[i] = st.y;
           if constexpr (H16) {  // W (and with it acc and colsum) carries the matrix's power-of-two scale: rstd (acc - mean colsum) / s_w, exactly
@@ -281,7 +298,44 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
       }
     }
 
-    {
+    if constexpr (UNEVEN) {
+      // ---- main loop of the uneven wave rows: the loop below for the bf16 / fp16 formats at two stages, once per tile count (TMW tiles in this wave's row) --
+      // a wave takes one of the two copies whole, so each is a plain loop over its own accumulators (one loop with a branch per K-tile spilled them)
+      static_assert(NSTAGE == 2 && !F8 && !SP, "uneven wave rows: the two-stage bf16 / fp16 loop");
+      auto k_loop = [&](auto tmw) {
+        constexpr int TMW = decltype(tmw)::value;
+        for (int t = kb; t < ke; ++t) {
+          const int cur = (t - kb) & 1;
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          __syncthreads();
+          char* nxt = smem + (cur ^ 1) * STAGE;
+          const bool more = t + 1 < ke;
+          const char* As = smem + cur * STAGE;
+          const char* Ws = As + A_BYTES;
+#pragma unroll
+          for (int ks = 0; ks < 4; ++ks) {
+            if (more) {
+#pragma unroll
+              for (int q = (ks * PIECES) / 4; q < ((ks + 1) * PIECES) / 4; ++q) stage_piece(q, t + 1, nxt);
+            }
+            const int chunk = ks * 2 + kh;
+            __builtin_amdgcn_iglp_opt(1);
+            bf16x8 af[TMW], wf[TN];
+#pragma unroll
+            for (int i = 0; i < TMW; ++i) af[i] = read_frag(As, wm * WROWS + i * 32 + l31, chunk);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) wf[j] = read_frag(Ws, wn * (BN / WN) + j * 32 + l31, chunk);
+#pragma unroll
+            for (int i = 0; i < TMW; ++i)
+#pragma unroll
+              for (int j = 0; j < TN; ++j) acc[i][j] = mfma_h<H16>(wf[j], af[i], acc[i][j]);
+          }
+        }
+      };
+      if (tile_on(TM - 1)) k_loop(std::integral_constant<int, TM>{});
+      else k_loop(std::integral_constant<int, TM - 1>{});
+      __syncthreads();
+    } else {
       // ---- main loop: one barrier per K-tile, the next tile's DMA issued in four slices ahead of each k-step's MFMAs
       for (int t = kb; t < ke; ++t) {
         const int cur = NSTAGE == 2 ? ((t - kb) & 1) : ((t - kb) % NSTAGE);
@@ -291,6 +345,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
           // tiles t + 1 .. t + NSTAGE - 2 may still be in flight behind tile t (loads retire in order): PIECES instructions each.  In the tail fewer are
           // outstanding than the count would allow, so it waits for everything (conservative for the last NSTAGE - 2 tiles)
           static_assert((NSTAGE - 2) * PIECES == 12, "s_waitcnt immediate below");
+          static_assert(!ASYM || NSTAGE == 2, "with issuer-only staging a non-issuing wave has no pieces in flight: the count below would be wrong for it");
           if (t + NSTAGE - 2 < ke) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
           else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -318,7 +373,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
               return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
             };
 #pragma unroll
-            for (int i = 0; i < TM; ++i) af[i] = frag8(As, wm * (BM / WM) + i * 32 + l31);
+            for (int i = 0; i < TM; ++i) af[i] = frag8(As, wm * WROWS + i * 32 + l31);
 #pragma unroll
             for (int j = 0; j < TN; ++j) wf[j] = frag8(Ws, wn * (BN / WN) + j * 32 + l31);
 #pragma unroll
@@ -340,7 +395,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
               __builtin_amdgcn_iglp_opt(1);
               f16x8 ah[TM], wh[TN];
 #pragma unroll
-              for (int i = 0; i < TM; ++i) ah[i] = __builtin_bit_cast(f16x8, read_frag(As, wm * (BM / WM) + i * 32 + l31, chunk));
+              for (int i = 0; i < TM; ++i) ah[i] = __builtin_bit_cast(f16x8, read_frag(As, wm * WROWS + i * 32 + l31, chunk));
 #pragma unroll
               for (int j = 0; j < TN; ++j) wh[j] = __builtin_bit_cast(f16x8, read_frag(Ws, wn * (BN / WN) + j * 32 + l31, chunk));
 #pragma unroll
@@ -370,7 +425,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
                 return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
               };
 #pragma unroll
-              for (int i = 0; i < TM; ++i) af[i] = frag8(As1, wm * (BM / WM) + i * 32 + l31, ca);
+              for (int i = 0; i < TM; ++i) af[i] = frag8(As1, wm * WROWS + i * 32 + l31, ca);
 #pragma unroll
               for (int j = 0; j < TN; ++j) wf[j] = frag8(Ws1, wn * (BN / WN) + j * 32 + l31, cw);
 #pragma unroll
@@ -393,7 +448,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
             f16x8 ah[TM], al[TM], wh[TN], wl[TN];
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
-              const int row = wm * (BM / WM) + i * 32 + l31;
+              const int row = wm * WROWS + i * 32 + l31;
               ah[i] = __builtin_bit_cast(f16x8, read_frag(As, row, ch));
               al[i] = __builtin_bit_cast(f16x8, read_frag(As, row, ch + 4));
             }
@@ -430,7 +485,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
           if constexpr (TM * TN >= 4) __builtin_amdgcn_iglp_opt(1);   // (the 64 x 128 tile's two MFMAs per k-step: the strategy's search does not terminate in reasonable memory)
           bf16x8 af[TM], wf[TN];
 #pragma unroll
-          for (int i = 0; i < TM; ++i) af[i] = read_frag(As, wm * (BM / WM) + i * 32 + l31, chunk);
+          for (int i = 0; i < TM; ++i) af[i] = read_frag(As, wm * WROWS + i * 32 + l31, chunk);
 #pragma unroll
           for (int j = 0; j < TN; ++j) wf[j] = read_frag(Ws, wn * (BN / WN) + j * 32 + l31, chunk);
 #pragma unroll
@@ -473,13 +528,15 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
     // epilogue applies out = rstd_r * (acc - mean_r * colsum_n) + bias_n before the non-linearity
     constexpr bool LN_FOLD_OK = !F8 && (EPI == GEMM_EPI_BIAS_BF16 || EPI == GEMM_EPI_GELU_BF16 || EPI == GEMM_EPI_SWIGLU_BF16);
     const bool fold = LN_FOLD_OK && a.ln_stats != nullptr;
+    // (192 accumulator registers -- the 352-row tile -- leave no room to hold the bias over the bands: it is fetched again per band, from L1 / L2)
+    constexpr bool BIAS_LATE = TM * TN * 16 > 160;
     float4 bias[TN][4], gam[TN][4];
   #pragma unroll
     for (int tn = 0; tn < TN; ++tn)
   #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int n = n0 + wn * (BN / WN) + tn * 32 + 8 * g + 4 * kh;
-        bias[tn][g] = *reinterpret_cast<const float4*>(a.bias + n);
+        if constexpr (!BIAS_LATE) bias[tn][g] = *reinterpret_cast<const float4*>(a.bias + n);
         if constexpr (EPI == GEMM_EPI_LS_RESID_F32 || F8) gam[tn][g] = *reinterpret_cast<const float4*>(a.gamma + n);
         if constexpr (LN_FOLD_OK) {
           if (fold) gam[tn][g] = *reinterpret_cast<const float4*>(a.colsum + n);  // (gam is free in these epilogues)
@@ -489,7 +546,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
     float sat_amax = 0.f;  // largest |scale * value| of a LIVE row packed into a split-fp16 / e4m3 output (saturation report)
   #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
-      const int m = m0 + wm * (BM / WM) + tm * 32 + l31;
+      const int m = m0 + wm * WROWS + tm * 32 + l31;
       float band_amax = 0.f;
       // Global reads of this band (residual / pos-embed rows, whole rows, all passes) are issued FIRST, ahead of the
       // register -> slab pass and its barrier, so their latency hides under that pass (proj -4 %, fc2 -1.5 %).
@@ -509,8 +566,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
         for (int it = 0; it < PASS8; ++it) {
           const int id = tid + it * NT;
           const int r = id / CPR8, c = id - r * CPR8;
-          const int gm_row = m0 + (r >> 5) * (BM / WM) + tm * 32 + (r & 31);
-          const bool okr = gm_row < a.M_valid;
+          const int gm_row = m0 + (r >> 5) * WROWS + tm * 32 + (r & 31);
+          const bool okr = gm_row < a.M_valid && (!UNEVEN || (r >> 5) * TM + tm < MT);  // (an absent tile of the last wave row: the next tile's rows)
           if (okr) {
             exh[it] = *reinterpret_cast<const uint4*>(a.xb + (size_t)gm_row * a.ld_xb + n0 + c * 8);
             exl[it] = *reinterpret_cast<const uint4*>(a.xl + (size_t)gm_row * a.ld_xb + n0 + c * 8);
@@ -522,8 +579,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
       for (int it = 0; it < (HILO ? 0 : PASSES); ++it) {
         const int id = tid + it * NT;
         const int r = id / CHUNKS_PER_ROW, c = id - r * CHUNKS_PER_ROW;
-        const int gm_row = m0 + (r >> 5) * (BM / WM) + tm * 32 + (r & 31);
-        const bool okr = gm_row < a.M_valid;
+        const int gm_row = m0 + (r >> 5) * WROWS + tm * 32 + (r & 31);
+        const bool okr = gm_row < a.M_valid && (!UNEVEN || (r >> 5) * TM + tm < MT);  // (an absent tile of the last wave row: the next tile's rows)
         int orow = gm_row;
         if constexpr (EPI == GEMM_EPI_TOKENS_F32) {
           const int b = gm_row / a.tok_np, pidx = gm_row - b * a.tok_np;
@@ -544,7 +601,9 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
   #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int col = wn * (BN / WN) + tn * 32 + 8 * g + 4 * kh;
-          const float4 bs = bias[tn][g];
+          float4 bs;
+          if constexpr (BIAS_LATE) bs = *reinterpret_cast<const float4*>(a.bias + n0 + col);
+          else bs = bias[tn][g];
           float v0 = acc[tm][tn][4 * g + 0] + bs.x, v1 = acc[tm][tn][4 * g + 1] + bs.y;
           float v2 = acc[tm][tn][4 * g + 2] + bs.z, v3 = acc[tm][tn][4 * g + 3] + bs.w;
           if constexpr (SP || H16) {  // undo the power-of-two operand scales (exact), then the bias  (H16: the weight matrix's scale, 1 when the caller gave none)
@@ -706,7 +765,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
       }
   #pragma unroll
     for (int tm = 0; tm < TM; ++tm) {
-      const int m = m0 + wm * (BM / WM) + tm * 32 + l31;
+      const int m = m0 + wm * WROWS + tm * 32 + l31;
       if (m >= a.M_valid) continue;
       size_t out_row = m;
       int pidx = 0;
@@ -782,7 +841,7 @@ int launch_cfg(const GemmBf16Args& a_in, hipStream_t st) {
   }
   // M is padded to whole tiles of every shape in use; tiles of padding rows only are not launched (they would all sit at the end of the
   // tile order, i.e. in the last XCD's chunk, and leave that XCD short of work)
-  a.m_tiles = a.M / BM;
+  a.m_tiles = (a.M + BM - 1) / BM;   // (352 rows divide no padded M: the last tile's rows past M read as zeros through the buffer resource and are never stored)
   if (a.M_valid > 0 && (a.M_valid + BM - 1) / BM < a.m_tiles) a.m_tiles = (a.M_valid + BM - 1) / BM;
   unsigned grid = a.m_tiles * (a.N / BN);
   a.rast_r = a.rast_gn = 0;
@@ -815,8 +874,8 @@ int launch_cfg(const GemmBf16Args& a_in, hipStream_t st) {
 // 320 x 256: 18 x 3 = 54 = 7 rounds of 37.5 us.  A round of the taller tile takes 1.21x (not 1.25x) the time: cost = rounds x height x 0.97.
 // The estimate picks the faster tile in 32 of the 36 cases of the recorded sweep (profiles/r4_gemm_tile_sweep.txt; three misses within 1 %, one
 // of 3 %) and 256 rows for the residual GEMMs of the bench batch (3 rounds either way).
-static int xcd_rounds(int bm, int m_valid, int n_tiles) {
-  const int m_tiles = (m_valid + bm - 1) / bm, xcds = 8, per_xcd = fp_num_cus() / xcds > 0 ? fp_num_cus() / xcds : 32;
+static int xcd_rounds(int bm, int m_valid, int n_tiles, int cus) {
+  const int m_tiles = (m_valid + bm - 1) / bm, xcds = 8, per_xcd = cus / xcds > 0 ? cus / xcds : 32;
   const GemmRaster ra = pick_raster(bm, n_tiles, (unsigned)(m_tiles * n_tiles));
   if (ra.r) return (((m_tiles + ra.r - 1) / ra.r) * (n_tiles / ra.gn) + xcds - 1) / xcds;
   const int chunk = (m_tiles * n_tiles + xcds - 1) / xcds;
@@ -824,7 +883,17 @@ static int xcd_rounds(int bm, int m_valid, int n_tiles) {
 }
 static bool tall_tile_wins(const GemmBf16Args& a) {
   if (a.M % 320 != 0 || a.M % 256 != 0 || a.N % 256 != 0) return false;
-  return (float)(xcd_rounds(320, a.M_valid, a.N / 256) * 320) * 0.97f < (float)(xcd_rounds(256, a.M_valid, a.N / 256) * 256);
+  const int cus = fp_num_cus();
+  return (float)(xcd_rounds(320, a.M_valid, a.N / 256, cus) * 320) * 0.97f < (float)(xcd_rounds(256, a.M_valid, a.N / 256, cus) * 256);
+}
+
+// 352 x 256 tiles for the residual GEMMs on the (hi, lo) stream (proj, fc2: N = 4 n-tiles, no raster): 11 MFMA row tiles over two wave rows of 192 + 160 rows,
+// 152 KiB of LDS.  A pure function of the shape and the CU count: the taller tile where it needs fewer rounds AND fewer tile rows per CU -- the bench batch
+// (43 968 rows x 1024 on 256 CUs): 2 rounds of 352 = 704 rows against 3 of 256 = 768; a 256-crop batch: 16 x 352 = 22 x 256, stays; one round either way, stays.
+static int resid_tile_rows(int m_valid, int n, int cus) {
+  if (m_valid <= 0 || n <= 0 || n % 256 != 0 || cus <= 0) return 256;
+  const int r352 = xcd_rounds(352, m_valid, n / 256, cus), r256 = xcd_rounds(256, m_valid, n / 256, cus);
+  return r352 < r256 && r352 * 352 < r256 * 256 ? 352 : 256;
 }
 
 // Tile selection: 256x256 (8 waves, 1 block/CU, 128 KiB LDS) when the shape allows it and fills the chip,
@@ -843,6 +912,12 @@ int launch(const GemmBf16Args& a, hipStream_t st) {
   if constexpr (!SP && (EPI == GEMM_EPI_BIAS_BF16 || EPI == GEMM_EPI_GELU_BF16 || EPI == GEMM_EPI_RESID_HILO)) {
     if ((force == 320 && a.M % 320 == 0 && a.N % 256 == 0) || (force == 0 && use_big && tall_tile_wins(a)))
       return launch_cfg<EPI, 320, 256, 2, 4, FMT>(a, st);
+  }
+  if constexpr (!SP && EPI == GEMM_EPI_RESID_HILO) {
+    const bool ok352 = a.N % 256 == 0 && a.M_valid > 0 && a.M_valid <= a.M;
+    if (ok352 && (force == 352 || (force == 0 && use_big && resid_tile_rows(a.M_valid, a.N, cus) == 352)))
+      return launch_cfg<EPI, 352, 256, 2, 4, FMT>(a, st);
+    FP_REQUIRE(force != 352, "gemm_bf16: the 352-row tile needs N %% 256 == 0 and 0 < M_valid <= M (N %d, M_valid %d, M %d)", a.N, a.M_valid, a.M);
   }
   if (use_big) return launch_cfg<EPI, 256, 256, 2, 4, FMT>(a, st);
   // Small M (a batch of one or two crops -- the reference loop's shape, one detection at a time, scripts/infer.py:368): the N = D outputs (proj,

@@ -375,6 +375,10 @@ int fp_gemm_bf16(const void* A, int lda, const void* W, int ldw, int M, int N, i
  *   fp_ln_finalize, colsum [N] = row sums of W.  Tuning bits as in fp_gemm_bf16. */
 int fp_gemm_bf16_ln(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int M_valid, const float* bias, void* out, int ldo,
                     int epilogue, const float* colsum, const float* ln_row, void* xb, int ld_xb, float* stats, fp_stream_t stream);
+/* Block-tile height (256 or 352 rows) the launcher gives an epilogue-8 launch of M_valid live rows x N columns that fills a device of num_cus compute units:
+ * 352 where it takes fewer rounds of tiles and fewer tile rows per compute unit.  Pure host arithmetic (no device needed); `352 << 8` in the tuning bits of
+ * fp_gemm_bf16_ln forces that tile for epilogue 8 (N a multiple of 256, 0 < M_valid <= M; every tile gives the same bits). */
+int fp_gemm_resid_tile_rows(int M_valid, int N, int num_cus);
 /* stats [parts, stats_stride, 2] partial row sums over `dim` columns in total -> ln_row [rows, 2] = (rstd, mean * rstd). */
 int fp_ln_finalize(const float* stats, int parts, int stats_stride, int rows, int dim, float eps, float* ln_row, fp_stream_t stream);
 
