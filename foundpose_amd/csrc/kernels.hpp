@@ -345,6 +345,7 @@ struct PnpArgs {
   int n_slots, k_max, iters, lm_iters, min_corresp;
   double thresh, conf;
   unsigned long long seed;
+  const unsigned long long* pair_keys;  // [pairs] sampler key of each pair, or null: the pair's index in the launch
   int* success;            // [pairs]
   double* R;               // [pairs, 9] row-major model -> camera
   double* t;               // [pairs, 3]

@@ -250,7 +250,9 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_ransac_kernel(PnpArgs a) {
   for (int i = tid; i < N * 2; i += PNP_THREADS) UV[i] = a.coord_2d[(size_t)pair * a.k_max * 2 + i];
   __syncthreads();
   const double thr2 = a.thresh * a.thresh;
-  const unsigned long long base = mix64(a.seed ^ ((unsigned long long)pair * 0xD6E8FEB86659FD93ull));
+  // the sampler key: the caller's (a pair then draws the same hypotheses wherever it sits in a launch) or the pair's index in this launch
+  const unsigned long long key = a.pair_keys ? a.pair_keys[pair] : (unsigned long long)pair;
+  const unsigned long long base = mix64(a.seed ^ (key * 0xD6E8FEB86659FD93ull));
 
   // ---- all hypotheses, scored in parallel
   for (int h = tid; h < a.iters; h += PNP_THREADS) {

@@ -8,7 +8,10 @@ ground-truth evaluation (opt-in: eval_models / --eval-gt) is one fp_pose_errors 
 estimated pose and one summary per frame; the HTML branches are not part of this path.
 
   python -m foundpose_amd.infer --opts configs/infer/lmo.json --dataset-dir <bop split dir> --detections <cnos json> \\
-         --repre-dir <output>/object_repre --output-dir <output>/inference [--vis [--models-dir <models>]]
+         --repre-dir <output>/object_repre --output-dir <output>/inference [--vis [--models-dir <models>]] [--batch-detections 32]
+
+--batch-detections N (N >= 1) runs infer_batched instead: one pass over the images, N detections per batch across frames and objects, the
+same poses.
 """
 
 import argparse
@@ -74,6 +77,133 @@ def load_opts(path_or_dict) -> InferOpts:
     return InferOpts(**d)
 
 
+def _check_driver_opts(opts: InferOpts):
+    """The options both drivers refuse, before any device work.  -> (refine, check_max_queries)."""
+    if opts.match_template_type != "tfidf":
+        raise ValueError(f"Unknown matching type '{opts.match_template_type}'.")
+    if opts.match_feat_matching_type != "cyclic_buddies":
+        raise ValueError(f"Unknown feature matching type ({opts.match_feat_matching_type}).")
+    if opts.final_pose_type not in FINAL_POSE_TYPES:
+        raise ValueError(f"Unknown final pose type {opts.final_pose_type}")
+    refine = opts.final_pose_type == "featuremetric"   # the best coarse pose refined featuremetrically (refine_util)
+    if refine and (not isinstance(opts.refine_iters, int) or opts.refine_iters < 0):
+        raise ValueError(f"refine_iters must be an integer >= 0, got {opts.refine_iters!r}")
+    # scripts/infer.py:482-485 subsamples the query points with torch.randperm when a mask yields more than max_num_queries of them
+    # (default 1 000 000: never for a crop).  The batched path keeps every point; an option value that could trigger the subsampling
+    # is refused instead of being ignored (crop=False: checked per frame against the image's own grid).
+    def check_max_queries(size_wh):
+        max_points = int(size_wh[0] // opts.grid_cell_size) * int(size_wh[1] // opts.grid_cell_size)
+        if opts.max_num_queries < max_points:
+            raise NotImplementedError(f"max_num_queries={opts.max_num_queries} could subsample the {max_points} grid points of a {size_wh[0]}x{size_wh[1]} input: not on the batched path")
+    if opts.crop:
+        check_max_queries(opts.crop_size)
+    return refine, check_max_queries
+
+
+def _annotated(inst, eval_model) -> bool:
+    return eval_model is not None and getattr(inst.get("gt_anno"), "pose", None) is not None
+
+
+def select_instances(opts: InferOpts, object_lid: int, frame: Dict[str, Any], detections: Dict[Any, Any],
+                     num_target_insts: Optional[Dict[Tuple[int, int], int]], eval_model: Optional[eval_util.EvalModel],
+                     detection_times: Dict[Tuple[int, int], float]) -> List[Tuple[int, Dict[str, Any]]]:
+    """The instances of `object_lid` in one frame that get a pose: [(instance id, instance)] in instance order, empty when the frame is not
+    one of this object's.  Both drivers select with this function.  detection_times (PoseEvaluator.detection_times) receives the
+    detector's time of the frame."""
+    scene_id, im_id, cam = frame["scene_id"], frame["im_id"], frame["camera"]
+    # number of target instances (infer.py:308-321): from the test targets when given -- frames that are not a target of
+    # this object, or whose count is 0, are skipped -- otherwise the number of ground-truth annotations of the frame
+    # ground-truth annotations of this object that are sufficiently visible (infer.py:286-305): a frame that HAS annotations but
+    # none of them qualifies is skipped; a frame without annotations (sample.objects_anno is None) goes on with an empty list
+    object_annos = []
+    if frame.get("gt_annos") is not None:
+        object_annos = [a for a in frame["gt_annos"]
+                        if getattr(a, "lid", object_lid) == object_lid and not np.isnan(getattr(a, "visibilities", 1.0))
+                        and getattr(a, "visibilities", 1.0) > opts.min_visibility]
+        if len(object_annos) == 0:
+            return []
+    if num_target_insts is not None:
+        if (scene_id, im_id) not in num_target_insts:
+            return []
+        n_target = int(num_target_insts[(scene_id, im_id)])
+    else:
+        n_target = len(object_annos)     # infer.py:317: no targets and no annotations -> 0 -> the frame is skipped
+    if n_target == 0:
+        return []
+    instances = infer_pose_util.get_instances_for_pose_estimation(
+        scene_id, im_id, object_lid, opts.use_detections, detections, int(opts.num_preds_factor * n_target), object_annos,
+        (cam.width, cam.height))
+    kept = []
+    for inst_j, inst in enumerate(instances):
+        detection_times[(scene_id, im_id)] = inst.get("time", 0) if opts.use_detections else 0
+        # infer.py:770-777: a detection that hardly overlaps its ground-truth annotation is not evaluated (applied on the
+        # evaluation path only: the annotation-free entries stay what they were)
+        if opts.use_detections and _annotated(inst, eval_model) and infer_pose_util.mask_iou(inst["input_mask_modal"], inst["gt_anno"].masks_modal) < 0.05:
+            continue
+        if inst["input_mask_modal"].sum() > cam.width * cam.height:  # infer.py:388-392
+            continue
+        if inst["input_mask_modal"].sum() == 0:
+            continue
+        kept.append((inst_j, inst))
+    return kept
+
+
+def _to_device_image(img) -> torch.Tensor:
+    """A frame's image (HWC uint8 or float [0,1], numpy or tensor) -> float32 [H, W, 3] in [0,1] on the device."""
+    if not isinstance(img, torch.Tensor):
+        arr = np.asarray(img)
+        img = torch.from_numpy(arr if arr.flags.writeable else arr.copy())   # (PIL hands out read-only arrays)
+    return (img.to("cuda", torch.float32) / 255.0) if img.dtype == torch.uint8 else img.to("cuda", torch.float32)
+
+
+def _stage_times(eng, n: int, t0: float, t1: float, t2: float, t3: float, t4: float, t5: Optional[float]) -> Dict[str, float]:
+    """The reference's per-detection `times` keys (infer.py:464-633, persisted by eval_util.py:327).  The detections between t0 and t5
+    ran as ONE batch of n, so every instance is charged its share of the batch; the four stages inside infer_batch come
+    from HIP events on the stream (their sum is the device time of t1..t2, the host-side remainder is in feat_extract)."""
+    st = eng.stage_times()
+    dev_sum = sum(st.values())
+    times = {"prep": (t1 - t0) / n,
+             "feat_extract": (st.get("feat_extract", 0.0) + max(0.0, (t2 - t1) - dev_sum)) / n,
+             "grid_sample": st.get("grid_sample", 0.0) / n, "proj": st.get("proj", 0.0) / n, "corresp": st.get("corresp", 0.0) / n,
+             "pose_coarse": (t3 - t2) / n, "final_select": (t4 - t3) / n}
+    if t5 is not None:
+        times["pose_refine"] = (t5 - t4) / n
+    return times
+
+
+def _record_poses(evaluator: eval_util.PoseEvaluator, opts: InferOpts, object_lid: int, repre, vertices: np.ndarray,
+                  eval_model: Optional[eval_util.EvalModel], res, records, times: Dict[str, float]) -> None:
+    """The found poses of ONE object out of a batch into its evaluator, in the order given.  records: (row of the detection in `res`,
+    scene_id, im_id, instance id, instance, the frame's camera, the camera PnP solved in, id of the best correspondence set, R, t)."""
+    pending = []   # consecutive annotated hypotheses: evaluated in one launch, recorded in instance order
+
+    def flush():
+        if pending:
+            evaluator.update_batch(pending)
+            pending.clear()
+    for b, scene_id, im_id, inst_j, inst, cam, crop_cam, cid, R, t in records:
+        corr_all = res.corresp_list(b)
+        c = corr_all[cid]
+        corresp_np = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in c.items()}
+        T_m2c = np.eye(4)
+        T_m2c[:3, :3], T_m2c[:3, 3] = R, t
+        T_m2w = crop_cam.T_world_from_eye @ T_m2c  # infer.py:661-666
+        if _annotated(inst, eval_model):   # infer.py:806-835
+            bank_cams = repre.template_cameras_cam_from_model   # (a bank without template cameras: no template orientation error)
+            tpl_cams = [bank_cams[int(cc["template_id"])] for cc in corr_all] if len(bank_cams) else []
+            pending.append(dict(scene_id=scene_id, im_id=im_id, inst_id=inst_j, hypothesis_id=0, base_image=None, object_repre_vertices=vertices,
+                                obj_lid=object_lid, object_pose_m2w=(T_m2w[:3, :3], T_m2w[:3, 3:]), object_pose_m2w_gt=inst["gt_anno"].pose,
+                                orig_camera_c2w=cam, camera_c2w=crop_cam, pred_mask=inst["input_mask_modal"], gt_mask=inst["gt_anno"].masks_modal,
+                                corresp=corresp_np, retrieved_templates_camera_m2c=tpl_cams, time_per_inst=times,
+                                object_mesh_vertices=eval_model.pts, object_syms=eval_model.syms, object_diameter=eval_model.diameter,
+                                inlier_radius=opts.pnp_inlier_thresh))
+            continue
+        flush()
+        evaluator.update_without_anno(scene_id, im_id, inst_j, 0, vertices, object_lid, T_m2w[:3, :3], T_m2w[:3, 3], cam, crop_cam, times, corresp_np,
+                                      inlier_radius=10)
+    flush()
+
+
 def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBasedObjectRepre, frames: Iterable[Dict[str, Any]],
                  detections: Dict[Any, Any], extractor=None, num_target_insts: Optional[Dict[Tuple[int, int], int]] = None,
                  precision: str = "bf16", seed: int = 0, weights: Optional[str] = None,
@@ -93,24 +223,7 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
         vis_util.check_opts(opts)
         if output_dir is None:
             raise ValueError("pictures need an output_dir")
-    if opts.match_template_type != "tfidf":
-        raise ValueError(f"Unknown matching type '{opts.match_template_type}'.")
-    if opts.match_feat_matching_type != "cyclic_buddies":
-        raise ValueError(f"Unknown feature matching type ({opts.match_feat_matching_type}).")
-    if opts.final_pose_type not in FINAL_POSE_TYPES:
-        raise ValueError(f"Unknown final pose type {opts.final_pose_type}")
-    refine = opts.final_pose_type == "featuremetric"   # the best coarse pose refined featuremetrically (refine_util)
-    if refine and (not isinstance(opts.refine_iters, int) or opts.refine_iters < 0):
-        raise ValueError(f"refine_iters must be an integer >= 0, got {opts.refine_iters!r}")
-    # scripts/infer.py:482-485 subsamples the query points with torch.randperm when a mask yields more than max_num_queries of them
-    # (default 1 000 000: never for a crop).  The batched path keeps every point; an option value that could trigger the subsampling
-    # is refused instead of being ignored (crop=False: checked per frame against the image's own grid).
-    def check_max_queries(size_wh):
-        max_points = int(size_wh[0] // opts.grid_cell_size) * int(size_wh[1] // opts.grid_cell_size)
-        if opts.max_num_queries < max_points:
-            raise NotImplementedError(f"max_num_queries={opts.max_num_queries} could subsample the {max_points} grid points of a {size_wh[0]}x{size_wh[1]} input: not on the batched path")
-    if opts.crop:
-        check_max_queries(opts.crop_size)
+    refine, check_max_queries = _check_driver_opts(opts)
     if extractor is None:  # infer.py:125-128; the checkpoint: weights=, $FOUNDPOSE_DINOV2_WEIGHTS or the torch hub cache, else this raises
         extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
     bank = DeviceBank([repre])
@@ -120,52 +233,13 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
     vertices = repre.vertices.cpu().numpy()
     vis_templates = repre.templates.cuda() if vis else None
 
-    def annotated(inst):
-        return eval_model is not None and getattr(inst.get("gt_anno"), "pose", None) is not None
     for frame in frames:
         scene_id, im_id, cam = frame["scene_id"], frame["im_id"], frame["camera"]
-        # number of target instances (infer.py:308-321): from the test targets when given -- frames that are not a target of
-        # this object, or whose count is 0, are skipped -- otherwise the number of ground-truth annotations of the frame
-        # ground-truth annotations of this object that are sufficiently visible (infer.py:286-305): a frame that HAS annotations but
-        # none of them qualifies is skipped; a frame without annotations (sample.objects_anno is None) goes on with an empty list
-        object_annos = []
-        if frame.get("gt_annos") is not None:
-            object_annos = [a for a in frame["gt_annos"]
-                            if getattr(a, "lid", object_lid) == object_lid and not np.isnan(getattr(a, "visibilities", 1.0))
-                            and getattr(a, "visibilities", 1.0) > opts.min_visibility]
-            if len(object_annos) == 0:
-                continue
-        if num_target_insts is not None:
-            if (scene_id, im_id) not in num_target_insts:
-                continue
-            n_target = int(num_target_insts[(scene_id, im_id)])
-        else:
-            n_target = len(object_annos)     # infer.py:317: no targets and no annotations -> 0 -> the frame is skipped
-        if n_target == 0:
-            continue
-        instances = infer_pose_util.get_instances_for_pose_estimation(
-            scene_id, im_id, object_lid, opts.use_detections, detections, int(opts.num_preds_factor * n_target), object_annos,
-            (cam.width, cam.height))
-        kept = []
-        for inst_j, inst in enumerate(instances):
-            evaluator.detection_times[(scene_id, im_id)] = inst.get("time", 0) if opts.use_detections else 0
-            # infer.py:770-777: a detection that hardly overlaps its ground-truth annotation is not evaluated (applied on the
-            # evaluation path only: the annotation-free entries stay what they were)
-            if opts.use_detections and annotated(inst) and infer_pose_util.mask_iou(inst["input_mask_modal"], inst["gt_anno"].masks_modal) < 0.05:
-                continue
-            if inst["input_mask_modal"].sum() > cam.width * cam.height:  # infer.py:388-392
-                continue
-            if inst["input_mask_modal"].sum() == 0:
-                continue
-            kept.append((inst_j, inst))
+        kept = select_instances(opts, object_lid, frame, detections, num_target_insts, eval_model, evaluator.detection_times)
         if not kept:
             continue
         t0 = time.perf_counter()
-        img = frame["image"]
-        if not isinstance(img, torch.Tensor):
-            arr = np.asarray(img)
-            img = torch.from_numpy(arr if arr.flags.writeable else arr.copy())   # (PIL hands out read-only arrays)
-        img = (img.to("cuda", torch.float32) / 255.0) if img.dtype == torch.uint8 else img.to("cuda", torch.float32)
+        img = _to_device_image(frame["image"])
         masks = torch.from_numpy(np.stack([i["input_mask_modal"] for _, i in kept]).astype(np.uint8)).cuda()
         boxes = [i["input_box_amodal"].tolist() for _, i in kept]
         if opts.crop:
@@ -198,17 +272,7 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
             Rb, tb = ref["R"].cpu().numpy(), ref["t"].cpu().numpy()
             t5 = time.perf_counter()
         n = len(kept)
-        # The reference's per-detection `times` keys (infer.py:464-633, persisted by eval_util.py:327).  The instances of a frame
-        # run as ONE batch here, so every instance is charged its share of the batch; the four stages inside infer_batch come
-        # from HIP events on the stream (their sum is the device time of t1..t2, the host-side remainder is in feat_extract).
-        st = eng.stage_times()
-        dev_sum = sum(st.values())
-        times = {"prep": (t1 - t0) / n,
-                 "feat_extract": (st.get("feat_extract", 0.0) + max(0.0, (t2 - t1) - dev_sum)) / n,
-                 "grid_sample": st.get("grid_sample", 0.0) / n, "proj": st.get("proj", 0.0) / n, "corresp": st.get("corresp", 0.0) / n,
-                 "pose_coarse": (t3 - t2) / n, "final_select": (t4 - t3) / n}
-        if refine:
-            times["pose_refine"] = (t5 - t4) / n
+        times = _stage_times(eng, n, t0, t1, t2, t3, t4, t5 if refine else None)
         if vis:   # compositing on the device, one copy of the batch's tiles to pinned memory, PNG encoding on the host
             tv = time.perf_counter()
             to_T = lambda R, t: np.block([[np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3, 1)], [np.array([[0.0, 0.0, 0.0, 1.0]])]])
@@ -227,37 +291,16 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
                     for note in vis_records[b]["notes"]:
                         print(f"vis: scene {scene_id} image {im_id} object {object_lid} instance {inst_j}: {note}")
             times["vis"] = (time.perf_counter() - tv) / n
-        pending = []   # consecutive annotated hypotheses: evaluated in one launch, recorded in instance order
-
-        def flush():
-            if pending:
-                evaluator.update_batch(pending)
-                pending.clear()
+        records = []
         for b, (inst_j, inst) in enumerate(kept):
             if not found[b]:
                 continue
-            corr_all = res.corresp_list(b)
-            c = corr_all[cid[b]]
-            corresp_np = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in c.items()}
-            T_m2c = np.eye(4)
-            T_m2c[:3, :3], T_m2c[:3, 3] = Rb[b], tb[b]
-            T_m2w = cams[b].T_world_from_eye @ T_m2c  # infer.py:661-666
             if vis and frame_poses is not None:
-                frame_poses.setdefault((scene_id, im_id), []).append((object_lid, np.linalg.inv(cam.T_world_from_eye) @ T_m2w))
-            if annotated(inst):   # infer.py:806-835
-                bank_cams = repre.template_cameras_cam_from_model   # (a bank without template cameras: no template orientation error)
-                tpl_cams = [bank_cams[int(cc["template_id"])] for cc in corr_all] if len(bank_cams) else []
-                pending.append(dict(scene_id=scene_id, im_id=im_id, inst_id=inst_j, hypothesis_id=0, base_image=None, object_repre_vertices=vertices,
-                                    obj_lid=object_lid, object_pose_m2w=(T_m2w[:3, :3], T_m2w[:3, 3:]), object_pose_m2w_gt=inst["gt_anno"].pose,
-                                    orig_camera_c2w=cam, camera_c2w=cams[b], pred_mask=inst["input_mask_modal"], gt_mask=inst["gt_anno"].masks_modal,
-                                    corresp=corresp_np, retrieved_templates_camera_m2c=tpl_cams, time_per_inst=times,
-                                    object_mesh_vertices=eval_model.pts, object_syms=eval_model.syms, object_diameter=eval_model.diameter,
-                                    inlier_radius=opts.pnp_inlier_thresh))
-                continue
-            flush()
-            evaluator.update_without_anno(scene_id, im_id, inst_j, 0, vertices, object_lid, T_m2w[:3, :3], T_m2w[:3, 3], cam, cams[b], times, corresp_np,
-                                          inlier_radius=10)
-        flush()
+                T_m2c = np.eye(4)
+                T_m2c[:3, :3], T_m2c[:3, 3] = Rb[b], tb[b]
+                frame_poses.setdefault((scene_id, im_id), []).append((object_lid, np.linalg.inv(cam.T_world_from_eye) @ (cams[b].T_world_from_eye @ T_m2c)))
+            records.append((b, scene_id, im_id, inst_j, inst, cam, cams[b], cid[b], Rb[b], tb[b]))
+        _record_poses(evaluator, opts, object_lid, repre, vertices, eval_model, res, records, times)
     return evaluator
 
 
@@ -310,6 +353,150 @@ def infer(opts: InferOpts, frames_by_object, detections, repres: Dict[int, repre
     return paths
 
 
+# ---------------------------------------------------------------------------------------------------- frame-major, cross-object batches
+class QueuedDetection(NamedTuple):
+    """One kept instance waiting for its batch."""
+    frame_no: int                   # running number of its frame in the stream
+    size: Tuple[int, int]           # (width, height) of that frame's image
+    obj: int                        # object index: the position of its lid in the sorted lids = its object in the DeviceBank
+    group_index: int                # its index among the kept instances of its own (frame, object) group
+    inst_id: int = 0
+    inst: Optional[Dict[str, Any]] = None
+    frame: Optional[Dict[str, Any]] = None   # the frame itself: alive as long as a queued detection refers to it
+
+
+def iter_batches(entries: Iterable[QueuedDetection], batch_detections: int):
+    """The flush rule: a batch goes out when `batch_detections` are queued, when the next detection's frame has another image size than the
+    queued ones (one batch is one stack of images), and when the stream ends.  Lazy: nothing is read ahead of the batch being filled."""
+    if batch_detections < 1:
+        raise ValueError(f"batch_detections must be >= 1, got {batch_detections}")
+    queue: List[QueuedDetection] = []
+    for e in entries:
+        if queue and e.size != queue[0].size:
+            yield queue
+            queue = []
+        queue.append(e)
+        if len(queue) == batch_detections:
+            yield queue
+            queue = []
+    if queue:
+        yield queue
+
+
+class FlushPlan(NamedTuple):
+    order: List[int]             # batch row -> position in the queue: the queue stable-sorted by object index
+    det_obj: List[int]           # batch row -> object index (ascending)
+    image_index: List[int]       # batch row -> position of its frame in `frames`
+    pair_group_index: List[int]  # batch row -> group_index of the detection (the RANSAC sampler key of slot j is group_index * n + j)
+    frames: List[int]            # frame_no of the images to stack, in queue order
+
+
+def plan_flush(queue: Sequence[QueuedDetection]) -> FlushPlan:
+    """Rows of one batch: the engine takes detections grouped by object, so the queue is stable-sorted by object index (within an object
+    the order stays frame, then instance); every row remembers which of the batch's stacked images it reads and its sampler key group."""
+    order = sorted(range(len(queue)), key=lambda i: queue[i].obj)   # sorted() is stable
+    frames = list(dict.fromkeys(e.frame_no for e in queue))
+    slot = {f: i for i, f in enumerate(frames)}
+    return FlushPlan(order, [queue[i].obj for i in order], [slot[queue[i].frame_no] for i in order], [queue[i].group_index for i in order], frames)
+
+
+def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections, repres: Dict[int, repre_util.FeatureBasedObjectRepre],
+                  output_dir: str, *, batch_detections: int = 32, extractor=None, precision: str = "bf16",
+                  num_target_insts: Optional[Dict[int, Dict[Tuple[int, int], int]]] = None, weights: Optional[str] = None,
+                  eval_models: Optional[Dict[int, eval_util.EvalModel]] = None, seed: int = 0, renderer=None) -> List[str]:
+    """infer() for a whole split in ONE pass over its frames: the kept instances of every (frame, object) are queued and go through the
+    crop producer, the engine and the PnP tail `batch_detections` at a time, across frames and objects (one DeviceBank of all objects).
+    `frames` yields each image once (load_bop_frames_all); `gt_annos` may hold annotations of several objects.  The poses, scores and
+    files are those of infer(): the instances are selected by the same function, the crops are the same bits, the engine's results do not
+    depend on the batch, and RANSAC's sampler is keyed by the pair's index in its own (frame, object) group -- what the per-object driver's
+    launch gives it -- instead of its place in the batch.  Pictures are not made here: infer() / infer_object() write them."""
+    if batch_detections < 1:
+        raise ValueError(f"batch_detections must be >= 1, got {batch_detections}")
+    if renderer is not None:
+        raise NotImplementedError("result pictures are written by the per-object driver (infer.infer / infer.infer_object, batch_detections=0): "
+                                  "the batched driver makes none")
+    refine, check_max_queries = _check_driver_opts(opts)
+    lids = sorted(opts.object_lids) if opts.object_lids is not None else sorted(repres)
+    if extractor is None:
+        extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
+    bank = DeviceBank([repres[l] for l in lids])
+    eng = fe.FoundPoseEngine(extractor, bank, opts.grid_cell_size, opts.match_top_n_templates, opts.match_top_k_buddies, tie_order="torch")
+    eng.record_stage_times = True
+    evaluators = [eval_util.PoseEvaluator() for _ in lids]
+    vertices = [repres[l].vertices.cpu().numpy() for l in lids]
+    models = [None if eval_models is None else eval_models.get(l) for l in lids]
+
+    def entries():
+        for frame_no, frame in enumerate(frames):
+            cam, checked = frame["camera"], False
+            for o, lid in enumerate(lids):
+                kept = select_instances(opts, lid, frame, detections, None if num_target_insts is None else num_target_insts.get(lid, {}),
+                                        models[o], evaluators[o].detection_times)
+                if kept and not opts.crop and not checked:   # (as in infer_object: only a frame that has work is checked)
+                    h, w = frame["image"].shape[:2]
+                    ps = extractor.patch_size
+                    if h % ps or w % ps:
+                        raise AssertionError(f"Input image height {h} / width {w} is not a multiple of patch size {ps} (crop=False)")
+                    check_max_queries((cam.width, cam.height))
+                    checked = True
+                for i, (inst_j, inst) in enumerate(kept):
+                    yield QueuedDetection(frame_no, (cam.width, cam.height), o, i, inst_j, inst, frame)
+
+    for queue in iter_batches(entries(), batch_detections):
+        t0 = time.perf_counter()
+        plan = plan_flush(queue)
+        dets = [queue[i] for i in plan.order]
+        n = len(dets)
+        by_no = {e.frame_no: e.frame for e in queue}
+        images = torch.stack([_to_device_image(by_no[f]["image"]) for f in plan.frames])
+        masks = torch.from_numpy(np.stack([e.inst["input_mask_modal"] for e in dets]).astype(np.uint8)).cuda()
+        src_cams = [e.frame["camera"] for e in dets]
+        if opts.crop:
+            cams = []
+            for e in dets:
+                b = e.inst["input_box_amodal"].tolist()
+                box = crop_util.calc_crop_box(crop_util.AlignedBox2f(b[0], b[1], b[2], b[3]), make_square=True)
+                cams.append(crop_util.construct_crop_camera(box, e.frame["camera"], tuple(opts.crop_size), opts.crop_rel_pad))
+            crops, crop_masks = crop_util.warp_crops(images, masks, src_cams, cams, plan.image_index)
+        else:   # crop=False: every detection gets its frame's whole image and solves in the frame's own camera (see infer_object)
+            crops = images[torch.as_tensor(plan.image_index, device=images.device)].permute(0, 3, 1, 2).contiguous()
+            crop_masks, cams = masks, src_cams
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        res = eng.infer_batch(crops, crop_masks, plan.det_obj, keep_feature_map=refine)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        n_slots = int(res.counts.shape[1])
+        keys = [[g * n_slots + j for j in range(n_slots)] for g in plan.pair_group_index]
+        poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
+                                        opts.pnp_refine_lm, seed=seed, pair_keys=keys)
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        best = pnp_util.select_best_coarse(poses)
+        found, cid = best["found"].cpu().tolist(), best["corresp_id"].cpu().tolist()
+        Rb, tb = best["R"].cpu().numpy(), best["t"].cpu().numpy()
+        t4 = time.perf_counter()
+        t5 = None
+        if refine:
+            ref = refine_util.refine_best_coarse(res, best, bank, plan.det_obj, cams, (crops.shape[-1], crops.shape[-2]), opts.refine_iters)
+            Rb, tb = ref["R"].cpu().numpy(), ref["t"].cpu().numpy()
+            t5 = time.perf_counter()
+        times = _stage_times(eng, n, t0, t1, t2, t3, t4, t5)
+        for o, lid in enumerate(lids):   # rows are grouped by object, and within an object in frame, then instance order
+            records = [(b, e.frame["scene_id"], e.frame["im_id"], e.inst_id, e.inst, e.frame["camera"], cams[b], cid[b], Rb[b], tb[b])
+                       for b, e in enumerate(dets) if e.obj == o and found[b]]
+            if records:
+                _record_poses(evaluators[o], opts, lid, repres[lid], vertices[o], models[o], res, records, times)
+    paths = []
+    if opts.save_estimates:
+        for o, lid in enumerate(lids):
+            p = os.path.join(output_dir, str(lid), "estimated-poses.json")
+            evaluators[o].save_results_json(p)
+            paths.append(p)
+        paths.append(eval_util.prepare_bop_submission(output_dir, opts.object_dataset, lids))
+    return paths
+
+
 # ---------------------------------------------------------------------------------------------------- BOP split on disk
 class GtAnnotation(NamedTuple):
     """structs.ObjectAnnotation, the fields data_util.prepare_sample fills (utils/data_util.py:105-151)."""
@@ -349,33 +536,54 @@ def load_gt_annotations(scene_dir: str, im_id: int, camera, scene_gt: Dict[str, 
     return annos
 
 
-def load_bop_frames(split_dir: str, targets: Sequence[Dict[str, int]], object_lid: int, with_gt: bool = False):
-    """Frames of a BOP split that show `object_lid` according to test_targets_bop19.json entries
-    ({"scene_id", "im_id", "obj_id", "inst_count"}): <split>/<scene:06d>/rgb/<im:06d>.{png,jpg} + scene_camera.json (cam_K).
-    with_gt: each frame also carries "gt_annos" from scene_gt.json, scene_gt_info.json and mask_visib/ (load_gt_annotations)."""
-    from PIL import Image
-    cams: Dict[int, Dict[str, Any]] = {}
-    gts: Dict[int, Tuple[Dict[str, Any], Dict[str, Any]]] = {}
-    for tgt in targets:
-        if tgt["obj_id"] != object_lid:
-            continue
-        sid, iid = tgt["scene_id"], tgt["im_id"]
-        sdir = os.path.join(split_dir, f"{sid:06d}")
-        if sid not in cams:
+class _SplitReader:
+    """The images of a BOP split with their cameras (and annotations): <split>/<scene:06d>/rgb/<im:06d>.{png,jpg} + scene_camera.json (cam_K)."""
+
+    def __init__(self, split_dir: str, with_gt: bool) -> None:
+        self.split_dir, self.with_gt = split_dir, with_gt
+        self.cams: Dict[int, Dict[str, Any]] = {}
+        self.gts: Dict[int, Tuple[Dict[str, Any], Dict[str, Any]]] = {}
+
+    def frame(self, sid: int, iid: int) -> Dict[str, Any]:
+        from PIL import Image
+        sdir = os.path.join(self.split_dir, f"{sid:06d}")
+        if sid not in self.cams:
             with open(os.path.join(sdir, "scene_camera.json")) as f:
-                cams[sid] = json.load(f)
-        K = np.array(cams[sid][str(iid)]["cam_K"], np.float64).reshape(3, 3)
+                self.cams[sid] = json.load(f)
+        K = np.array(self.cams[sid][str(iid)]["cam_K"], np.float64).reshape(3, 3)
         path = next(p for p in (os.path.join(sdir, "rgb", f"{iid:06d}.png"), os.path.join(sdir, "rgb", f"{iid:06d}.jpg"),
                                 os.path.join(sdir, "gray", f"{iid:06d}.tif")) if os.path.exists(p))
         image = np.asarray(Image.open(path).convert("RGB"))
         camera = crop_util.PinholePlaneCameraModel(image.shape[1], image.shape[0], (K[0, 0], K[1, 1]), (K[0, 2], K[1, 2]), np.eye(4))
         frame = {"scene_id": sid, "im_id": iid, "image": image, "camera": camera}
-        if with_gt:
-            if sid not in gts:
+        if self.with_gt:
+            if sid not in self.gts:
                 with open(os.path.join(sdir, "scene_gt.json")) as f, open(os.path.join(sdir, "scene_gt_info.json")) as g:
-                    gts[sid] = (json.load(f), json.load(g))
-            frame["gt_annos"] = load_gt_annotations(sdir, iid, camera, *gts[sid])
-        yield frame
+                    self.gts[sid] = (json.load(f), json.load(g))
+            frame["gt_annos"] = load_gt_annotations(sdir, iid, camera, *self.gts[sid])
+        return frame
+
+
+def load_bop_frames(split_dir: str, targets: Sequence[Dict[str, int]], object_lid: int, with_gt: bool = False):
+    """Frames of a BOP split that show `object_lid` according to test_targets_bop19.json entries
+    ({"scene_id", "im_id", "obj_id", "inst_count"}): <split>/<scene:06d>/rgb/<im:06d>.{png,jpg} + scene_camera.json (cam_K).
+    with_gt: each frame also carries "gt_annos" from scene_gt.json, scene_gt_info.json and mask_visib/ (load_gt_annotations)."""
+    reader = _SplitReader(split_dir, with_gt)
+    for tgt in targets:
+        if tgt["obj_id"] == object_lid:
+            yield reader.frame(tgt["scene_id"], tgt["im_id"])
+
+
+def load_bop_frames_all(split_dir: str, targets: Sequence[Dict[str, int]], with_gt: bool = False):
+    """Every image the targets name, ONCE, whatever the number of objects targeted in it, in the order of its first entry (the stream of
+    infer_batched).  with_gt: "gt_annos" holds the annotations of all objects of the image."""
+    reader = _SplitReader(split_dir, with_gt)
+    seen = set()
+    for tgt in targets:
+        key = (tgt["scene_id"], tgt["im_id"])
+        if key not in seen:
+            seen.add(key)
+            yield reader.frame(*key)
 
 
 def main(argv: Optional[Sequence[str]] = None) -> None:
@@ -396,7 +604,13 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     ap.add_argument("--vis", action="store_true", help="write the result pictures (when vis_results is true in the options): one tile per estimated pose, "
                     "<output-dir>/<lid>/<scene>_<im>_<lid>_<inst>_0.png (pose contours, retrieved templates, matches), and one summary per frame, "
                     "<output-dir>/vis/<scene>_<im>.png; the object meshes come from --models-dir")
+    ap.add_argument("--batch-detections", type=int, default=0, help="N >= 1: one pass over the split's images, N detections per batch across frames and "
+                    "objects (infer_batched; same poses, no pictures); 0 (default): one object after the other, one batch per (image, object)")
     args = ap.parse_args(argv)
+    if args.batch_detections < 0:
+        ap.error("--batch-detections must be >= 0")
+    if args.batch_detections >= 1 and args.vis:
+        ap.error("--vis needs the per-object driver: drop --batch-detections (or pass 0)")
     opts = load_opts(args.opts)
     # the checkpoint is resolved before anything else is read: a missing one must fail in seconds, not after the banks are loaded
     extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=args.precision, weights=args.weights)
@@ -423,6 +637,12 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         with open(os.path.join(models_dir, "models_info.json")) as f:
             models_info = json.load(f)
         eval_models = {lid: eval_util.load_eval_model(models_dir, lid, opts.max_sym_disc_step, models_info) for lid in lids}
+    if args.batch_detections >= 1:
+        out = infer_batched(opts._replace(object_lids=list(lids)), load_bop_frames_all(args.dataset_dir, targets, with_gt=args.eval_gt), detections, repres,
+                            args.output_dir, batch_detections=args.batch_detections, extractor=extractor.to("cuda"), precision=args.precision,
+                            num_target_insts=n_inst, eval_models=eval_models)
+        print("\n".join(out))
+        return
     out = infer(opts._replace(object_lids=list(lids)), lambda lid: load_bop_frames(args.dataset_dir, targets, lid, with_gt=args.eval_gt), detections,
                 repres, args.output_dir, extractor=extractor.to("cuda"), precision=args.precision, num_target_insts=n_inst, eval_models=eval_models,
                 renderer=renderer)

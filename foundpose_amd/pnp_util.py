@@ -39,11 +39,13 @@ def _intrinsics(camera) -> Tuple[float, float, float, float]:
 def solve_pnp_ransac_batch(coord_2d: torch.Tensor, coord_3d: torch.Tensor, counts: torch.Tensor, cameras: Sequence[Any],
                            pnp_ransac_iter: int = 1000, pnp_inlier_thresh: float = 3.0, pnp_required_ransac_conf: float = 0.99,
                            pnp_refine_lm: bool = True, seed: int = 0, return_ransac_pose: bool = False,
-                           min_corresp: int = 6) -> Dict[str, torch.Tensor]:
+                           min_corresp: int = 6, pair_keys=None) -> Dict[str, torch.Tensor]:
     """coord_2d [B, n, K, 2], coord_3d [B, n, K, 3], counts [B, n] (MatchResult's padded layout); cameras: one per detection.
     -> dict of device tensors: success [B, n] bool, R [B, n, 3, 3] f64, t [B, n, 3] f64, quality [B, n] (RANSAC inliers),
     inliers [B, n, K] bool (+ ransac_pose [B, n, 12]).  min_corresp: sets with fewer correspondences fail without being tried --
-    6 in the driver's loop (scripts/infer.py:555-559), 4 for a bare estimate_pose call (what cv2.solvePnPRansac needs)."""
+    6 in the driver's loop (scripts/infer.py:555-559), 4 for a bare estimate_pose call (what cv2.solvePnPRansac needs).
+    pair_keys: [B, n] int64 tensor or nested sequence, the sampler key of every pair (fp_pnp_ransac_keyed): a pair's hypotheses then depend on
+    (seed, its key) and not on where it sits in this batch.  None: the pair's index b * n + j (fp_pnp_ransac)."""
     require_cuda(coord_2d, coord_3d, counts)
     B, n, K = coord_2d.shape[:3]
     dev = coord_2d.device
@@ -60,7 +62,18 @@ def solve_pnp_ransac_batch(coord_2d: torch.Tensor, coord_3d: torch.Tensor, count
     mask = torch.zeros(P, K, dtype=torch.uint8, device=dev)
     rp = torch.zeros(P, 12, dtype=torch.float64, device=dev) if return_ransac_pose else None
     lm_iters = 20 + (20 if pnp_refine_lm else 0)
-    call("fp_pnp_ransac", ptr(c2), ptr(c3), ptr(cnt), ptr(cam), P, n, K, int(pnp_ransac_iter), float(pnp_inlier_thresh),
+    keys = None
+    if pair_keys is not None:
+        if isinstance(pair_keys, torch.Tensor):
+            if pair_keys.dtype != torch.int64:
+                raise ValueError(f"pair_keys must be int64, got {pair_keys.dtype}")
+        else:
+            pair_keys = torch.tensor(pair_keys, dtype=torch.int64)
+        if tuple(pair_keys.shape) != (B, n):
+            raise ValueError(f"pair_keys must have shape [{B}, {n}], got {list(pair_keys.shape)}")
+        keys = pair_keys.contiguous() if pair_keys.is_cuda else upload_async(pair_keys, dev)   # (the int64 bits are the uint64 keys)
+    entry, key_arg = ("fp_pnp_ransac", ()) if keys is None else ("fp_pnp_ransac_keyed", (ptr(keys),))
+    call(entry, ptr(c2), ptr(c3), ptr(cnt), ptr(cam), *key_arg, P, n, K, int(pnp_ransac_iter), float(pnp_inlier_thresh),
          float(pnp_required_ransac_conf), lm_iters, int(min_corresp), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(success), ptr(R), ptr(t), ptr(ninl), ptr(mask), ptr(rp), stream())
     out = {"success": success.reshape(B, n).bool(), "R": R.reshape(B, n, 3, 3), "t": t.reshape(B, n, 3),
            "quality": ninl.reshape(B, n).to(torch.float64), "inliers": mask.reshape(B, n, K).bool()}
@@ -70,13 +83,13 @@ def solve_pnp_ransac_batch(coord_2d: torch.Tensor, coord_3d: torch.Tensor, count
 
 
 def estimate_poses(res: MatchResult, cameras: Sequence[Any], pnp_type: str = "opencv", pnp_ransac_iter: int = 1000,
-                   pnp_inlier_thresh: float = 3.0, pnp_required_ransac_conf: float = 0.99, pnp_refine_lm: bool = True, seed: int = 0):
-    """All coarse poses of a batch (the loop of infer.py:552-580 for every detection at once)."""
+                   pnp_inlier_thresh: float = 3.0, pnp_required_ransac_conf: float = 0.99, pnp_refine_lm: bool = True, seed: int = 0, pair_keys=None):
+    """All coarse poses of a batch (the loop of infer.py:552-580 for every detection at once).  pair_keys: see solve_pnp_ransac_batch."""
     if pnp_type != "opencv":
         raise ValueError("Unsupported PnP type")
     counts = torch.where(res.template_ids >= 0, res.counts, torch.zeros_like(res.counts))
     return solve_pnp_ransac_batch(res.coord_2d, res.coord_3d, counts, cameras, pnp_ransac_iter, pnp_inlier_thresh,
-                                  pnp_required_ransac_conf, pnp_refine_lm, seed)
+                                  pnp_required_ransac_conf, pnp_refine_lm, seed, pair_keys=pair_keys)
 
 
 def select_best_coarse(poses: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:

@@ -195,6 +195,15 @@ int fp_pnp_ransac(const float* coord_2d, const float* coord_3d, const int32_t* c
                   int32_t* out_success, double* out_R, double* out_t, int32_t* out_num_inliers, uint8_t* out_inlier_mask,
                   double* out_ransac_pose, fp_stream_t stream);
 
+/* fp_pnp_ransac with the sampler key of every pair given by the caller: pair_keys [num_pairs].  fp_pnp_ransac draws the hypotheses of a
+ * pair from (seed, the pair's index in the launch), so a pair's hypotheses change with its neighbours in the batch; here they are drawn
+ * from (seed, pair_keys[pair]) and a pair's result is the same in whatever launch and at whatever position it runs.  With
+ * pair_keys[i] == i the results are those of fp_pnp_ransac bit for bit (same kernel). */
+int fp_pnp_ransac_keyed(const float* coord_2d, const float* coord_3d, const int32_t* counts, const double* cameras, const uint64_t* pair_keys,
+                        int num_pairs, int n_slots, int k_max, int ransac_iters, double inlier_thresh, double confidence, int lm_iters,
+                        int min_corresp, uint64_t seed, int32_t* out_success, double* out_R, double* out_t, int32_t* out_num_inliers,
+                        uint8_t* out_inlier_mask, double* out_ransac_pose, fp_stream_t stream);
+
 /* sample_feature_map_at_points (utils/feature_util.py:100-131): bilinear grid_sample, zeros padding,
  * align_corners=False.  fmap addressed by element strides (image, channel, y, x); point_img (may be null)
  * maps each point to its image.  out [num_points, C]. */
