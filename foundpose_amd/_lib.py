@@ -94,6 +94,7 @@ _PROTOS = {
     "fp_vsd_counts": [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp],
     "fp_featuremetric_refine": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32,
                                 vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "fp_depth_refine": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "fp_vis_pca_colorize": [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
     "fp_vis_mask_tint": [vp, vp, i32, i32, i32, vp, vp],
     "fp_vis_contour": [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp],
@@ -185,6 +186,12 @@ def refine_scratch_bytes(num_det: int, max_points: int) -> int:
     """FP_REFINE_SCRATCH_BYTES of include/foundpose_amd.h."""
     chunks = (max_points + REFINE_CHUNK - 1) // REFINE_CHUNK
     return REFINE_STATE_BYTES * num_det + 8 * REFINE_RECORD * num_det * chunks + ((num_det * max_points + 7) // 8) * 8 + 8
+
+
+def depth_refine_scratch_bytes(num_det: int, max_points: int) -> int:
+    """FP_DEPTH_REFINE_SCRATCH_BYTES of include/foundpose_amd.h."""
+    chunks = (max_points + REFINE_CHUNK - 1) // REFINE_CHUNK
+    return REFINE_STATE_BYTES * num_det + 8 * REFINE_RECORD * num_det * chunks + 8
 
 
 TEXTURE_MAX_SIDE = 16384  # FP_TEXTURE_MAX_SIDE of the header

@@ -307,6 +307,18 @@ struct RefineArgs {
 };
 int launch_featuremetric_refine(const RefineArgs& a, hipStream_t st);
 
+// ---------------------------------------------------------------- depth_refine.hip (the LM state is refine.hip's RefineState)
+struct DepthRefineArgs {
+  const float* depth; int num_images, H, W, pad0; const int32_t* image_index;   // [num_images, H, W] mm, 0 = no measurement
+  const double* cam; const double* R_in; const double* t_in;
+  const int32_t* row_begin; const int32_t* row_end; const float* verts; long long num_rows;
+  const int32_t* has_pose; const double* tau; int num_det, max_points, iters, chunks;
+  double* R_out; double* t_out; double* cost_in; double* cost_out; int32_t* num_points; int32_t* iters_used; int32_t* status;
+  double* normal_eq;       // [num_det, 28] or null
+  RefineState* state; double* part; int32_t* err;
+};
+int launch_depth_refine(const DepthRefineArgs& a, hipStream_t st);
+
 // ---------------------------------------------------------------- vsd.hip
 struct VsdPair {                         // one (estimate, GT) pair, built on the host by fp_vsd_counts
   long long test_off, est_off, gt_off;   // element offsets of the three depth images (index * height * width)

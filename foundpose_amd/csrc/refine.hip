@@ -7,13 +7,14 @@
 //   refine_pass      (chunk of FP_REFINE_CHUNK points, detection): bilinear taps + six C-length dot products per point (fp32), the
 //                    per-point Jacobian, cost and normal-equation terms (fp64), one partial record per workgroup
 //   refine_solve     one wave per detection: folds the partials in chunk order, then accepts / rejects the trial pose and
-//                    solves the damped 6x6 system for the next one (fp64 Cholesky)
+//                    solves the damped 6x6 system for the next one (fp64 Cholesky; lm_step.hpp)
 //   refine_finalize  one thread per detection: the outputs
 // The pass/solve pair runs `iters` times.  Detections that have stopped leave both kernels at their first instruction.
 // Every sum has a fixed order (lanes: butterfly; waves: 0..3; chunks: ascending), no atomics, and a detection's chunk
 // decomposition depends only on its own point count: results are bit-identical across runs and batch compositions.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "lm_step.hpp"
 #include "rot.hpp"
 
 namespace {
@@ -157,62 +158,6 @@ __global__ void __launch_bounds__(64 * RF_WAVES) refine_pass_kernel(RefineArgs a
   }
 }
 
-// (H + lam diag(H)) d = -g by Cholesky; false if a pivot is not > 0 (or not finite)
-FP_DEVICE bool lm_solve(const double* H, const double* g, double lam, double* d) {
-  double L[6][6];
-  int k = 0;
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j, ++k) { L[j][i] = H[k]; L[i][j] = H[k]; }
-  for (int i = 0; i < 6; ++i) L[i][i] = L[i][i] + lam * L[i][i];
-  for (int j = 0; j < 6; ++j) {
-    double dj = L[j][j];
-    for (int m = 0; m < j; ++m) dj -= L[j][m] * L[j][m];
-    if (!(dj > 0.0) || !(dj < INFINITY)) return false;
-    const double ljj = sqrt(dj);
-    L[j][j] = ljj;
-    for (int i = j + 1; i < 6; ++i) {
-      double v = L[i][j];
-      for (int m = 0; m < j; ++m) v -= L[i][m] * L[j][m];
-      L[i][j] = v / ljj;
-    }
-  }
-  double y[6];
-  for (int i = 0; i < 6; ++i) {
-    double v = -g[i];
-    for (int m = 0; m < i; ++m) v -= L[i][m] * y[m];
-    y[i] = v / L[i][i];
-  }
-  for (int i = 5; i >= 0; --i) {
-    double v = y[i];
-    for (int m = i + 1; m < 6; ++m) v -= L[m][i] * d[m];
-    d[i] = v / L[i][i];
-  }
-  return true;
-}
-
-FP_DEVICE void stop(RefineState& s) { s.active = 0; s.pending = 0; }
-
-// next trial pose from the current system; a failed factorisation is a rejected step (one iteration, lam x 10)
-FP_DEVICE void propose(RefineState& s, int iters) {
-  for (int k = 0; k <= iters && s.active; ++k) {
-    if (s.it >= iters) { stop(s); return; }
-    double d[6];
-    const bool ok = lm_solve(s.H, s.g, s.lam, d);
-    s.it += 1;
-    if (ok) {
-      double E[9];
-      rot_exp(d, E);
-      for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) s.Rt[i * 3 + j] = E[i * 3 + 0] * s.R[0 * 3 + j] + E[i * 3 + 1] * s.R[1 * 3 + j] + E[i * 3 + 2] * s.R[2 * 3 + j];
-      for (int i = 0; i < 3; ++i) s.tt[i] = E[i * 3 + 0] * s.t[0] + E[i * 3 + 1] * s.t[1] + E[i * 3 + 2] * s.t[2] + d[3 + i];
-      s.pending = 1;
-      return;
-    }
-    s.lam *= 10.0;
-    if (s.lam > 1e12) { stop(s); return; }
-  }
-}
-
 __global__ void __launch_bounds__(64) refine_solve_kernel(RefineArgs a, int mode) {
   __shared__ double tot[RF_REC];
   const int b = blockIdx.x;
@@ -230,7 +175,7 @@ __global__ void __launch_bounds__(64) refine_solve_kernel(RefineArgs a, int mode
   if (lane != 0) return;
   if (mode == SOLVE_SIGMA) {
     s.nvalid = (int)tot[29];
-    if (s.nvalid < 6) { stop(s); return; }
+    if (s.nvalid < 6) { lm_stop(s); return; }
     s.skipped = 0;
     s.sigma2 = fmax(tot[28] / s.nvalid, 1e-12);
     return;   // pending stays 1: the next pass evaluates the input pose
@@ -242,7 +187,7 @@ __global__ void __launch_bounds__(64) refine_solve_kernel(RefineArgs a, int mode
     if (a.normal_eq)
       for (int i = 0; i < 28; ++i) a.normal_eq[28 * b + i] = tot[i];
     s.pending = 0;
-    propose(s, a.iters);
+    lm_propose(s, a.iters);
     return;
   }
   // SOLVE_STEP: the pass evaluated the trial pose
@@ -257,12 +202,12 @@ __global__ void __launch_bounds__(64) refine_solve_kernel(RefineArgs a, int mode
     s.E = Et;
     s.lam = fmax(s.lam / 10.0, 1e-12);
     s.accepted = 1;
-    if (rel < 1e-10) { stop(s); return; }
+    if (rel < 1e-10) { lm_stop(s); return; }
   } else {
     s.lam *= 10.0;
-    if (s.lam > 1e12) { stop(s); return; }
+    if (s.lam > 1e12) { lm_stop(s); return; }
   }
-  propose(s, a.iters);
+  lm_propose(s, a.iters);
 }
 
 __global__ void __launch_bounds__(64) refine_finalize_kernel(RefineArgs a) {

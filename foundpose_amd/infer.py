@@ -60,9 +60,12 @@ class InferOpts(NamedTuple):
     vis_for_paper: bool = True
     debug: bool = True
     refine_iters: int = 30          # final_pose_type="featuremetric": Levenberg-Marquardt iterations (refine_util)
+    depth_refine_iters: int = 30    # final_pose_type="depth" / "featuremetric_depth": iterations against the frame's depth
+    depth_refine_max_dist: float = 0.0   # ... its truncation distance tau in mm; 0: a tenth of the diagonal of the bounding box of repre.vertices
 
 
-FINAL_POSE_TYPES = ("best_coarse", "featuremetric")
+FINAL_POSE_TYPES = ("best_coarse", "featuremetric", "depth", "featuremetric_depth")
+DEPTH_POSE_TYPES = ("depth", "featuremetric_depth")   # the final pose is refined against the frame's "depth" (refine_util.refine_best_coarse_depth)
 
 
 def load_opts(path_or_dict) -> InferOpts:
@@ -85,9 +88,13 @@ def _check_driver_opts(opts: InferOpts):
         raise ValueError(f"Unknown feature matching type ({opts.match_feat_matching_type}).")
     if opts.final_pose_type not in FINAL_POSE_TYPES:
         raise ValueError(f"Unknown final pose type {opts.final_pose_type}")
-    refine = opts.final_pose_type == "featuremetric"   # the best coarse pose refined featuremetrically (refine_util)
+    refine = opts.final_pose_type in ("featuremetric", "featuremetric_depth")   # the best coarse pose refined featuremetrically (refine_util)
     if refine and (not isinstance(opts.refine_iters, int) or opts.refine_iters < 0):
         raise ValueError(f"refine_iters must be an integer >= 0, got {opts.refine_iters!r}")
+    if opts.final_pose_type in DEPTH_POSE_TYPES and (not isinstance(opts.depth_refine_iters, int) or opts.depth_refine_iters < 0):
+        raise ValueError(f"depth_refine_iters must be an integer >= 0, got {opts.depth_refine_iters!r}")
+    if not opts.depth_refine_max_dist >= 0:
+        raise ValueError(f"depth_refine_max_dist must be >= 0 (mm; 0: a tenth of the model's bounding-box diagonal), got {opts.depth_refine_max_dist!r}")
     # scripts/infer.py:482-485 subsamples the query points with torch.randperm when a mask yields more than max_num_queries of them
     # (default 1 000 000: never for a crop).  The batched path keeps every point; an option value that could trigger the subsampling
     # is refused instead of being ignored (crop=False: checked per frame against the image's own grid).
@@ -156,6 +163,34 @@ def _to_device_image(img) -> torch.Tensor:
     return (img.to("cuda", torch.float32) / 255.0) if img.dtype == torch.uint8 else img.to("cuda", torch.float32)
 
 
+def depth_refine_tau(opts: InferOpts, repre) -> float:
+    """The truncation distance of the depth refinement for one object (mm), computed once per object on the host."""
+    if opts.depth_refine_max_dist > 0:
+        return float(opts.depth_refine_max_dist)
+    v = repre.vertices.detach().cpu().numpy().astype(np.float64)
+    return 0.1 * float(np.linalg.norm(v.max(0) - v.min(0)))
+
+
+def _check_frame_depth(frame: Dict[str, Any]) -> None:
+    """A frame that has work under a depth pose type must carry "depth" of the camera's size: refused by name otherwise."""
+    cam, d = frame["camera"], frame.get("depth")
+    where = f"scene {frame['scene_id']} image {frame['im_id']}"
+    if d is None:
+        raise ValueError(f"{where}: the final pose type refines against depth, but the frame carries no \"depth\"")
+    if tuple(d.shape) != (cam.height, cam.width):
+        raise ValueError(f"{where}: depth is {tuple(d.shape)}, the camera's image is ({cam.height}, {cam.width})")
+
+
+def _frame_depth(frame: Dict[str, Any]) -> torch.Tensor:
+    """A frame's "depth" (float32 mm [H, W], numpy or tensor, 0 = no measurement) on the device."""
+    _check_frame_depth(frame)
+    d = frame["depth"]
+    if not isinstance(d, torch.Tensor):
+        arr = np.asarray(d)
+        d = torch.from_numpy(arr if arr.flags.writeable else arr.copy())
+    return d.to("cuda", torch.float32)
+
+
 def _stage_times(eng, n: int, t0: float, t1: float, t2: float, t3: float, t4: float, t5: Optional[float]) -> Dict[str, float]:
     """The reference's per-detection `times` keys (infer.py:464-633, persisted by eval_util.py:327).  The detections between t0 and t5
     ran as ONE batch of n, so every instance is charged its share of the batch; the four stages inside infer_batch come
@@ -169,6 +204,18 @@ def _stage_times(eng, n: int, t0: float, t1: float, t2: float, t3: float, t4: fl
     if t5 is not None:
         times["pose_refine"] = (t5 - t4) / n
     return times
+
+
+def _refine_final(opts: InferOpts, res, best, bank: DeviceBank, det_obj, frame_cams, cams, crop_size, depth, image_index, taus):
+    """The final pose of a batch for the refining pose types: featuremetric in the cameras PnP solved in, then / or against the frames' depth
+    in the frames' own cameras (refine_util).  Its time is times["pose_refine"].  -> (R [n, 3, 3], t [n, 3]) numpy, in the solve cameras."""
+    pose = best
+    if opts.final_pose_type in ("featuremetric", "featuremetric_depth"):
+        ref = refine_util.refine_best_coarse(res, best, bank, det_obj, cams, crop_size, opts.refine_iters)
+        pose = dict(best, R=ref["R"], t=ref["t"])
+    if opts.final_pose_type in DEPTH_POSE_TYPES:
+        pose = refine_util.refine_best_coarse_depth(res, pose, bank, det_obj, frame_cams, cams, depth, image_index, taus, opts.depth_refine_iters)
+    return pose["R"].cpu().numpy(), pose["t"].cpu().numpy()
 
 
 def _record_poses(evaluator: eval_util.PoseEvaluator, opts: InferOpts, object_lid: int, repre, vertices: np.ndarray,
@@ -210,7 +257,8 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
                  eval_model: Optional[eval_util.EvalModel] = None, renderer=None, output_dir: Optional[str] = None,
                  frame_poses: Optional[Dict[Tuple[int, int], List[Tuple[int, np.ndarray]]]] = None) -> eval_util.PoseEvaluator:
     """One object over a stream of frames (the body of infer.py's per-object loop).  A frame is
-    {"scene_id", "im_id", "image": HWC uint8 or float [0,1] (numpy or tensor), "camera": PinholePlaneCameraModel (c2w)}.
+    {"scene_id", "im_id", "image": HWC uint8 or float [0,1] (numpy or tensor), "camera": PinholePlaneCameraModel (c2w)} and, for the
+    final pose types "depth" / "featuremetric_depth", "depth": float32 mm [H, W] (numpy or tensor, 0 = no measurement).
     eval_model (eval_util.load_eval_model): instances whose annotation carries a ground-truth `pose` (model -> world) are
     evaluated against it (PoseEvaluator.update_batch, one launch per frame, inlier radius opts.pnp_inlier_thresh as in
     infer.py:831); without it, or for annotations without a pose, the driver records what it always has.
@@ -224,6 +272,7 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
         if output_dir is None:
             raise ValueError("pictures need an output_dir")
     refine, check_max_queries = _check_driver_opts(opts)
+    use_depth = opts.final_pose_type in DEPTH_POSE_TYPES
     if extractor is None:  # infer.py:125-128; the checkpoint: weights=, $FOUNDPOSE_DINOV2_WEIGHTS or the torch hub cache, else this raises
         extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
     bank = DeviceBank([repre])
@@ -232,12 +281,15 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
     evaluator = eval_util.PoseEvaluator()
     vertices = repre.vertices.cpu().numpy()
     vis_templates = repre.templates.cuda() if vis else None
+    tau = depth_refine_tau(opts, repre) if use_depth else None
 
     for frame in frames:
         scene_id, im_id, cam = frame["scene_id"], frame["im_id"], frame["camera"]
         kept = select_instances(opts, object_lid, frame, detections, num_target_insts, eval_model, evaluator.detection_times)
         if not kept:
             continue
+        if use_depth:
+            _check_frame_depth(frame)
         t0 = time.perf_counter()
         img = _to_device_image(frame["image"])
         masks = torch.from_numpy(np.stack([i["input_mask_modal"] for _, i in kept]).astype(np.uint8)).cuda()
@@ -267,22 +319,24 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
         found, cid = best["found"].cpu().tolist(), best["corresp_id"].cpu().tolist()
         Rb, tb = best["R"].cpu().numpy(), best["t"].cpu().numpy()
         t4 = time.perf_counter()
-        if refine:   # infer.py:619: the refined pose of the best coarse pose is the final pose
-            ref = refine_util.refine_best_coarse(res, best, bank, [0] * len(kept), cams, (crops.shape[-1], crops.shape[-2]), opts.refine_iters)
-            Rb, tb = ref["R"].cpu().numpy(), ref["t"].cpu().numpy()
+        t5 = None
+        if refine or use_depth:   # infer.py:619: the refined pose of the best coarse pose is the final pose
+            depth = _frame_depth(frame) if use_depth else None   # (the upload is part of pose_refine)
+            Rb, tb = _refine_final(opts, res, best, bank, [0] * len(kept), [cam] * len(kept), cams, (crops.shape[-1], crops.shape[-2]), depth,
+                                   [0] * len(kept), [tau] * len(kept))
             t5 = time.perf_counter()
         n = len(kept)
-        times = _stage_times(eng, n, t0, t1, t2, t3, t4, t5 if refine else None)
+        times = _stage_times(eng, n, t0, t1, t2, t3, t4, t5)
         if vis:   # compositing on the device, one copy of the batch's tiles to pinned memory, PNG encoding on the host
             tv = time.perf_counter()
             to_T = lambda R, t: np.block([[np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3, 1)], [np.array([[0.0, 0.0, 0.0, 1.0]])]])
-            coarse = [to_T(best["R"][b].cpu().numpy(), best["t"][b].cpu().numpy()) if found[b] else None for b in range(n)] if refine else [None] * n
+            coarse = [to_T(best["R"][b].cpu().numpy(), best["t"][b].cpu().numpy()) if found[b] else None for b in range(n)] if t5 is not None else [None] * n
             final = [to_T(Rb[b], tb[b]) if found[b] else None for b in range(n)]
             gt_pose = [getattr(inst.get("gt_anno"), "pose", None) for _, inst in kept]
             gt = [None if p is None else np.linalg.inv(cams[b].T_world_from_eye) @ to_T(p.R, p.t) for b, p in enumerate(gt_pose)]
             tiles, vis_records = vis_util.vis_inference_results_batch(
                 crops, crop_masks, cams, res, found, cid, coarse, final, repre, renderer, object_lid, extractor=extractor,
-                poses_gt=gt if any(g is not None for g in gt) else None, draw_coarse=refine, vis_corresp_top_n=opts.vis_corresp_top_n,
+                poses_gt=gt if any(g is not None for g in gt) else None, draw_coarse=t5 is not None, vis_corresp_top_n=opts.vis_corresp_top_n,
                 vis_feat_map=opts.vis_feat_map, vis_for_paper=opts.vis_for_paper, templates=vis_templates)
             host = vis_util.tiles_to_host(tiles)
             for b, (inst_j, _) in enumerate(kept):
@@ -416,6 +470,7 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
         raise NotImplementedError("result pictures are written by the per-object driver (infer.infer / infer.infer_object, batch_detections=0): "
                                   "the batched driver makes none")
     refine, check_max_queries = _check_driver_opts(opts)
+    use_depth = opts.final_pose_type in DEPTH_POSE_TYPES
     lids = sorted(opts.object_lids) if opts.object_lids is not None else sorted(repres)
     if extractor is None:
         extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
@@ -425,6 +480,7 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
     evaluators = [eval_util.PoseEvaluator() for _ in lids]
     vertices = [repres[l].vertices.cpu().numpy() for l in lids]
     models = [None if eval_models is None else eval_models.get(l) for l in lids]
+    taus = [depth_refine_tau(opts, repres[l]) for l in lids] if use_depth else None
 
     def entries():
         for frame_no, frame in enumerate(frames):
@@ -432,6 +488,8 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
             for o, lid in enumerate(lids):
                 kept = select_instances(opts, lid, frame, detections, None if num_target_insts is None else num_target_insts.get(lid, {}),
                                         models[o], evaluators[o].detection_times)
+                if kept and use_depth:
+                    _check_frame_depth(frame)
                 if kept and not opts.crop and not checked:   # (as in infer_object: only a frame that has work is checked)
                     h, w = frame["image"].shape[:2]
                     ps = extractor.patch_size
@@ -477,9 +535,11 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
         Rb, tb = best["R"].cpu().numpy(), best["t"].cpu().numpy()
         t4 = time.perf_counter()
         t5 = None
-        if refine:
-            ref = refine_util.refine_best_coarse(res, best, bank, plan.det_obj, cams, (crops.shape[-1], crops.shape[-2]), opts.refine_iters)
-            Rb, tb = ref["R"].cpu().numpy(), ref["t"].cpu().numpy()
+        if refine or use_depth:
+            # the depth images of the flush, stacked like its RGB images and read through plan.image_index (the upload is part of pose_refine)
+            depth = torch.stack([_frame_depth(by_no[f]) for f in plan.frames]) if use_depth else None
+            Rb, tb = _refine_final(opts, res, best, bank, plan.det_obj, src_cams, cams, (crops.shape[-1], crops.shape[-2]), depth, plan.image_index,
+                                   [taus[o] for o in plan.det_obj] if use_depth else None)
             t5 = time.perf_counter()
         times = _stage_times(eng, n, t0, t1, t2, t3, t4, t5)
         for o, lid in enumerate(lids):   # rows are grouped by object, and within an object in frame, then instance order
@@ -539,8 +599,8 @@ def load_gt_annotations(scene_dir: str, im_id: int, camera, scene_gt: Dict[str, 
 class _SplitReader:
     """The images of a BOP split with their cameras (and annotations): <split>/<scene:06d>/rgb/<im:06d>.{png,jpg} + scene_camera.json (cam_K)."""
 
-    def __init__(self, split_dir: str, with_gt: bool) -> None:
-        self.split_dir, self.with_gt = split_dir, with_gt
+    def __init__(self, split_dir: str, with_gt: bool, with_depth: bool = False) -> None:
+        self.split_dir, self.with_gt, self.with_depth = split_dir, with_gt, with_depth
         self.cams: Dict[int, Dict[str, Any]] = {}
         self.gts: Dict[int, Tuple[Dict[str, Any], Dict[str, Any]]] = {}
 
@@ -556,6 +616,9 @@ class _SplitReader:
         image = np.asarray(Image.open(path).convert("RGB"))
         camera = crop_util.PinholePlaneCameraModel(image.shape[1], image.shape[0], (K[0, 0], K[1, 1]), (K[0, 2], K[1, 2]), np.eye(4))
         frame = {"scene_id": sid, "im_id": iid, "image": image, "camera": camera}
+        if self.with_depth:   # depth/<im>.png in depth_scale units -> float32 mm, what the BOP evaluation reads (eval_bop19.load_depth)
+            from .eval_bop19 import load_depth
+            frame["depth"] = load_depth(os.path.join(sdir, "depth", f"{iid:06d}.png"), float(self.cams[sid][str(iid)].get("depth_scale", 1.0)))
         if self.with_gt:
             if sid not in self.gts:
                 with open(os.path.join(sdir, "scene_gt.json")) as f, open(os.path.join(sdir, "scene_gt_info.json")) as g:
@@ -564,20 +627,21 @@ class _SplitReader:
         return frame
 
 
-def load_bop_frames(split_dir: str, targets: Sequence[Dict[str, int]], object_lid: int, with_gt: bool = False):
+def load_bop_frames(split_dir: str, targets: Sequence[Dict[str, int]], object_lid: int, with_gt: bool = False, with_depth: bool = False):
     """Frames of a BOP split that show `object_lid` according to test_targets_bop19.json entries
     ({"scene_id", "im_id", "obj_id", "inst_count"}): <split>/<scene:06d>/rgb/<im:06d>.{png,jpg} + scene_camera.json (cam_K).
-    with_gt: each frame also carries "gt_annos" from scene_gt.json, scene_gt_info.json and mask_visib/ (load_gt_annotations)."""
-    reader = _SplitReader(split_dir, with_gt)
+    with_gt: each frame also carries "gt_annos" from scene_gt.json, scene_gt_info.json and mask_visib/ (load_gt_annotations).
+    with_depth: and "depth", float32 mm [H, W], from depth/<im:06d>.png and the frame's depth_scale (eval_bop19.load_depth)."""
+    reader = _SplitReader(split_dir, with_gt, with_depth)
     for tgt in targets:
         if tgt["obj_id"] == object_lid:
             yield reader.frame(tgt["scene_id"], tgt["im_id"])
 
 
-def load_bop_frames_all(split_dir: str, targets: Sequence[Dict[str, int]], with_gt: bool = False):
+def load_bop_frames_all(split_dir: str, targets: Sequence[Dict[str, int]], with_gt: bool = False, with_depth: bool = False):
     """Every image the targets name, ONCE, whatever the number of objects targeted in it, in the order of its first entry (the stream of
-    infer_batched).  with_gt: "gt_annos" holds the annotations of all objects of the image."""
-    reader = _SplitReader(split_dir, with_gt)
+    infer_batched).  with_gt: "gt_annos" holds the annotations of all objects of the image.  with_depth: "depth" as in load_bop_frames."""
+    reader = _SplitReader(split_dir, with_gt, with_depth)
     seen = set()
     for tgt in targets:
         key = (tgt["scene_id"], tgt["im_id"])
@@ -612,6 +676,7 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     if args.batch_detections >= 1 and args.vis:
         ap.error("--vis needs the per-object driver: drop --batch-detections (or pass 0)")
     opts = load_opts(args.opts)
+    with_depth = opts.final_pose_type in DEPTH_POSE_TYPES   # the depth pose types read depth/<im>.png beside every image
     # the checkpoint is resolved before anything else is read: a missing one must fail in seconds, not after the banks are loaded
     extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=args.precision, weights=args.weights)
     with open(args.targets or os.path.join(os.path.dirname(os.path.abspath(args.dataset_dir)), "test_targets_bop19.json")) as f:
@@ -638,12 +703,12 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
             models_info = json.load(f)
         eval_models = {lid: eval_util.load_eval_model(models_dir, lid, opts.max_sym_disc_step, models_info) for lid in lids}
     if args.batch_detections >= 1:
-        out = infer_batched(opts._replace(object_lids=list(lids)), load_bop_frames_all(args.dataset_dir, targets, with_gt=args.eval_gt), detections, repres,
+        out = infer_batched(opts._replace(object_lids=list(lids)), load_bop_frames_all(args.dataset_dir, targets, with_gt=args.eval_gt, with_depth=with_depth), detections, repres,
                             args.output_dir, batch_detections=args.batch_detections, extractor=extractor.to("cuda"), precision=args.precision,
                             num_target_insts=n_inst, eval_models=eval_models)
         print("\n".join(out))
         return
-    out = infer(opts._replace(object_lids=list(lids)), lambda lid: load_bop_frames(args.dataset_dir, targets, lid, with_gt=args.eval_gt), detections,
+    out = infer(opts._replace(object_lids=list(lids)), lambda lid: load_bop_frames(args.dataset_dir, targets, lid, with_gt=args.eval_gt, with_depth=with_depth), detections,
                 repres, args.output_dir, extractor=extractor.to("cuda"), precision=args.precision, num_target_insts=n_inst, eval_models=eval_models,
                 renderer=renderer)
     print("\n".join(out))

@@ -1,16 +1,19 @@
-"""Featuremetric refinement of the best coarse pose on the MI355X.
+"""Refinement of the best coarse pose on the MI355X: featuremetric and against the frame's depth (section 14).
 
 The FoundPose paper's third stage, which the released reference leaves as hooks only (scripts/infer.py:619, `final_pose_type`):
 Levenberg-Marquardt on the 6-DoF pose that aligns the per-point features of the template behind the best coarse pose with the
 query's projected patch-feature map.  One fp_featuremetric_refine call (csrc/refine.hip) refines a whole batch; the contract is
-restated in numpy fp64 by tests/featuremetric_ref.py.
+restated in numpy fp64 by tests/featuremetric_ref.py.  The depth term is this project's own: Levenberg-Marquardt on the truncated
+quadratic of (measured depth at a template point's projection) - (the point's depth), in the frame's own camera; one
+fp_depth_refine call (csrc/depth_refine.hip) per batch, restated by tests/depth_refine_ref.py.
 """
 
 from typing import Any, Dict, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
-from ._lib import call, ptr, refine_scratch_bytes, require_cuda, stream, upload_async
+from ._lib import call, depth_refine_scratch_bytes, ptr, refine_scratch_bytes, require_cuda, stream, upload_async
 from .bank import DeviceBank
 from .matching import MatchResult
 from .pnp_util import _intrinsics
@@ -100,3 +103,103 @@ def refine_best_coarse(res: MatchResult, best: Dict[str, torch.Tensor], bank: De
     rb, re, ok = best_template_rows(res, best, bank, det_obj)
     return refine_featuremetric(res.feature_map, image_size, cameras, best["R"], best["t"], rb, re, bank.feats, bank.vertices, ok, iters,
                                 return_normal_equations, max_points=bank.p_max)
+
+
+def refine_depth(depth: torch.Tensor, image_index: torch.Tensor, cameras: Sequence[Any], R: torch.Tensor, t: torch.Tensor, row_begin: torch.Tensor,
+                 row_end: torch.Tensor, vertices: torch.Tensor, has_pose: torch.Tensor, tau, iters: int = 30, return_normal_equations: bool = False,
+                 max_points: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """depth [N, H, W] (or [H, W]) fp32 mm, 0 = no measurement: the frames' full depth images; image_index [B] int: the image of each
+    detection; cameras: the FRAME's pinhole camera per detection (what pnp_util accepts); R [B, 3, 3] / t [B, 3] model -> that camera
+    (mm); row_begin / row_end [B] int: each detection's rows of vertices [N, 3]; has_pose [B] bool; tau: the truncation distance in mm,
+    a number or one per detection.  max_points bounds row_end - row_begin (None: read back from the device).
+    -> refine_featuremetric's dict; num_points counts the inliers at the input pose, cost = sum min(r^2, tau^2) / points."""
+    require_cuda(depth, image_index, R, t, row_begin, row_end, vertices, has_pose)
+    if depth.dim() == 2:
+        depth = depth[None]
+    if depth.dim() != 3:
+        raise ValueError("depth must be [N, H, W] or [H, W]")
+    N, H, W = depth.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"the depth image is {H} x {W}: refinement needs at least 2 x 2 pixels")
+    if int(iters) < 0:
+        raise ValueError("iters must be >= 0")
+    B = int(R.shape[0])
+    if len(cameras) != B:
+        raise ValueError(f"{len(cameras)} cameras for {B} detections")
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"vertices {tuple(vertices.shape)} are not [N, 3]")
+    dev = depth.device
+    tau_h = torch.as_tensor(tau, dtype=torch.float64).reshape(-1).cpu()
+    if tau_h.numel() == 1:
+        tau_h = tau_h.expand(B)
+    if tau_h.numel() != B:
+        raise ValueError(f"{tau_h.numel()} tau values for {B} detections")
+    d32 = depth.float().contiguous()
+    cam = upload_async(torch.tensor([_intrinsics(c) for c in cameras], dtype=torch.float64).reshape(B, 4), dev)
+    tau_d = upload_async(tau_h.contiguous(), dev)
+    ii = image_index.to(torch.int32).contiguous()
+    Rin = R.to(torch.float64).reshape(B, 9).contiguous()
+    tin = t.to(torch.float64).reshape(B, 3).contiguous()
+    rb = row_begin.to(torch.int32).contiguous()
+    re = row_end.to(torch.int32).contiguous()
+    hp = has_pose.to(torch.int32).contiguous()
+    v32 = vertices.float().contiguous()
+    if max_points is None:
+        max_points = int(torch.where(hp != 0, re - rb, torch.zeros_like(re)).max().item()) if B else 0
+    max_points = max(1, int(max_points))
+    scratch = torch.empty(depth_refine_scratch_bytes(B, max_points), dtype=torch.uint8, device=dev)
+    Ro = torch.empty(B, 9, dtype=torch.float64, device=dev)
+    to = torch.empty(B, 3, dtype=torch.float64, device=dev)
+    cin = torch.empty(B, dtype=torch.float64, device=dev)
+    cout = torch.empty(B, dtype=torch.float64, device=dev)
+    npts = torch.empty(B, dtype=torch.int32, device=dev)
+    used = torch.empty(B, dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    neq = torch.empty(B, 28, dtype=torch.float64, device=dev) if return_normal_equations else None
+    call("fp_depth_refine", ptr(d32), N, H, W, ptr(ii), ptr(cam), ptr(Rin), ptr(tin), ptr(rb), ptr(re), ptr(v32), int(v32.shape[0]), ptr(hp), ptr(tau_d),
+         B, max_points, int(iters), ptr(scratch), scratch.numel(), ptr(Ro), ptr(to), ptr(cin), ptr(cout), ptr(npts), ptr(used), ptr(status), ptr(neq),
+         stream())
+    out = {"R": Ro.reshape(B, 3, 3), "t": to, "cost_in": cin, "cost_out": cout, "num_points": npts, "iters_used": used, "status": status}
+    if neq is not None:
+        out["normal_eq"] = neq
+    return out
+
+
+def _pose_matrices(R, t) -> np.ndarray:
+    R = R.detach().cpu().numpy() if isinstance(R, torch.Tensor) else np.asarray(R)
+    t = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    T = np.tile(np.eye(4), (len(R), 1, 1))
+    T[:, :3, :3], T[:, :3, 3] = R.astype(np.float64).reshape(-1, 3, 3), t.astype(np.float64).reshape(-1, 3)
+    return T
+
+
+def refine_best_coarse_depth(res: MatchResult, pose: Dict[str, torch.Tensor], bank: DeviceBank, det_obj: Optional[Sequence[int]],
+                             frame_cameras: Sequence[Any], solve_cameras: Sequence[Any], depth: torch.Tensor, image_index, tau,
+                             iters: int = 30) -> Dict[str, torch.Tensor]:
+    """Refines a pose of every detection (pose: select_best_coarse's dict, its "R" / "t" possibly replaced by a featuremetric
+    refinement's) against the frames' depth.  The poses live in solve_cameras (the cameras PnP solved in: the crop cameras); they are
+    moved into frame_cameras (the frames' own), inv(frame.T_world_from_eye) @ solve.T_world_from_eye @ T_m2c in fp64, refined there
+    on the unwarped depth [N, H, W] (image_index: the image of each detection), and moved back.  Where both cameras are the same
+    object (crop=False) nothing is converted.  -> refine_depth's dict, R / t in the solve cameras."""
+    res.wait()
+    B = res.template_ids.shape[0]
+    det_obj = [0] * B if det_obj is None else list(det_obj)
+    rb, re, ok = best_template_rows(res, pose, bank, det_obj)
+    dev = res.template_ids.device
+    same = all(f is s for f, s in zip(frame_cameras, solve_cameras))
+    R, t = pose["R"], pose["t"]
+    if not same:
+        rel = np.stack([np.linalg.inv(np.asarray(f.T_world_from_eye, np.float64)) @ np.asarray(s.T_world_from_eye, np.float64)
+                        for f, s in zip(frame_cameras, solve_cameras)])
+        T = rel @ _pose_matrices(R, t)
+        R, t = upload_async(torch.from_numpy(T[:, :3, :3].copy()), dev), upload_async(torch.from_numpy(T[:, :3, 3].copy()), dev)
+    ii = image_index if isinstance(image_index, torch.Tensor) else upload_async(torch.tensor(list(image_index), dtype=torch.int32), dev)
+    out = refine_depth(depth, ii, frame_cameras, R, t, rb, re, bank.vertices, ok, tau, iters, max_points=bank.p_max)
+    if not same:
+        # detections whose pose did not move keep the solve-camera pose they came with, bit for bit
+        moved = (out["status"] == STATUS_REFINED).cpu().numpy()
+        T = np.linalg.inv(rel) @ _pose_matrices(out["R"], out["t"])
+        T0 = _pose_matrices(pose["R"], pose["t"])
+        T[~moved] = T0[~moved]
+        out["R"], out["t"] = torch.from_numpy(T[:, :3, :3].copy()).to(dev), torch.from_numpy(T[:, :3, 3].copy()).to(dev)
+    return out

@@ -601,6 +601,34 @@ int fp_featuremetric_refine(const float* map, int64_t sb, int64_t sy, int64_t sx
                             double* R_out, double* t_out, double* cost_in, double* cost_out, int32_t* num_points,
                             int32_t* iters_used, int32_t* status, double* normal_eq, fp_stream_t stream);
 
+/* ---- depth refinement of the final pose (tests/depth_refine_ref.py restates it) ----------------------------
+ * Levenberg-Marquardt on the 6-DoF pose of each of num_det detections against the frame's measured depth, in the frame's own
+ * camera (never a crop camera; the depth is not warped or resampled).  Device arrays:
+ *   depth       fp32 [num_images, H, W] mm, 0 = no measurement (H, W >= 2); image_index int32 [num_det]: the image a detection reads.
+ *               An index outside [0, num_images) is never used: the call then returns FP_ERR_INVALID naming the detection
+ *   cameras     fp64 [num_det, 4]  (fx, fy, cx, cy) of the frame's camera; pixel centres lie at integer coordinates
+ *   R_in, t_in  fp64 [num_det, 9], [num_det, 3]  the input pose, model -> camera (mm)
+ *   row_begin, row_end int32 [num_det]  the template's rows [row_begin, row_end) of vertices [num_rows, 3] fp32, at most max_points
+ *               rows; a bad range is reported like a bad image index, and the rows are never read
+ *   has_pose    int32 [num_det]  0: skipped (status 2);  tau fp64 [num_det]: the truncation distance (mm).  tau is not validated: a NaN
+ *               or a value <= 0 leaves no inlier, so that detection is skipped (status 2) with its pose untouched
+ * Per point: Xc = R X + t, (u, v) its projection, d the bilinear depth at (u, v) from the taps (x0, y0) = floor(u, v) and their +1
+ * neighbours, r = d - z.  Measurable: z > 1 mm, the four taps inside the image and > 0.  rho = r^2 for an inlier (measurable, |r| < tau),
+ * tau^2 otherwise (no gradient); cost = sum rho / (row_end - row_begin); H, g over the inliers.  The LM loop, lambda schedule and
+ * stopping rules are fp_featuremetric_refine's, at most `iters` (0..1000) iterations, all enqueued at once.
+ * Outputs: R_out, t_out, cost_in, cost_out, num_points (inliers at the input pose), iters_used, status (0 refined, 1 no step
+ * accepted, 2 skipped: no pose, empty range or < 6 inliers at the input pose; for 1 and 2 the pose is the input bit for bit);
+ * normal_eq fp64 [num_det, 28] may be null: H (upper triangle, row-major), g, cost at the input pose.  cost_out <= cost_in always.
+ * Deterministic and bit-identical across batch compositions; no float atomics.  scratch: FP_DEPTH_REFINE_SCRATCH_BYTES. */
+#define FP_DEPTH_REFINE_SCRATCH_BYTES(num_det, max_points)                                                             \
+  ((size_t)FP_REFINE_STATE_BYTES * (size_t)(num_det) +                                                                  \
+   8 * FP_REFINE_RECORD * (size_t)(num_det) * (((size_t)(max_points) + FP_REFINE_CHUNK - 1) / FP_REFINE_CHUNK) + 8)
+int fp_depth_refine(const float* depth, int num_images, int H, int W, const int32_t* image_index, const double* cameras,
+                    const double* R_in, const double* t_in, const int32_t* row_begin, const int32_t* row_end, const float* vertices,
+                    int64_t num_rows, const int32_t* has_pose, const double* tau, int num_det, int max_points, int iters,
+                    void* scratch, size_t scratch_bytes, double* R_out, double* t_out, double* cost_in, double* cost_out,
+                    int32_t* num_points, int32_t* iters_used, int32_t* status, double* normal_eq, fp_stream_t stream);
+
 /* ---- result pictures (utils/vis_util.py:179-687 vis_inference_results in its vis_for_paper layout; DESIGN.md section 12;
  * tests/vis_ref.py restates every entry) ---------------------------------------------------------------------------------
  * Images are uint8 HWC (3 channels), contiguous, with a leading batch dimension; sides lie in [1, FP_VIS_MAX_SIDE].  One thread
