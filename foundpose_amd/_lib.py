@@ -95,6 +95,8 @@ _PROTOS = {
     "fp_featuremetric_refine": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32,
                                 vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "fp_depth_refine": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "fp_rgbd_refine": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, C.c_double,
+                       i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "fp_vis_pca_colorize": [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
     "fp_vis_mask_tint": [vp, vp, i32, i32, i32, vp, vp],
     "fp_vis_contour": [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp],
@@ -192,6 +194,12 @@ def depth_refine_scratch_bytes(num_det: int, max_points: int) -> int:
     """FP_DEPTH_REFINE_SCRATCH_BYTES of include/foundpose_amd.h."""
     chunks = (max_points + REFINE_CHUNK - 1) // REFINE_CHUNK
     return REFINE_STATE_BYTES * num_det + 8 * REFINE_RECORD * num_det * chunks + 8
+
+
+def rgbd_refine_scratch_bytes(num_det: int, max_points: int) -> int:
+    """FP_RGBD_REFINE_SCRATCH_BYTES of include/foundpose_amd.h."""
+    chunks = (max_points + REFINE_CHUNK - 1) // REFINE_CHUNK
+    return REFINE_STATE_BYTES * num_det + 16 * REFINE_RECORD * num_det * chunks + ((num_det * max_points + 7) // 8) * 8 + 8
 
 
 TEXTURE_MAX_SIDE = 16384  # FP_TEXTURE_MAX_SIDE of the header

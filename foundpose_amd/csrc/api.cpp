@@ -1,6 +1,7 @@
 // C ABI of libfoundpose_amd.so (declared in include/foundpose_amd.h): argument checking, scratch carving
 // and kernel sequencing.  No device allocation, no global mutable state, no synchronisation except the table uploads of
 // fp_pose_errors and fp_vsd_counts (each waits for its own copy) and the range check read back by fp_featuremetric_refine / fp_depth_refine.
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -679,6 +680,58 @@ int fp_depth_refine(const float* depth, int num_images, int H, int W, const int3
   FP_REQUIRE(bad <= 0, "fp_depth_refine: detection %d: bank rows outside [0, %lld) or more than max_points %d", bad - 1,
              (long long)num_rows, max_points);
   FP_REQUIRE(bad == 0, "fp_depth_refine: detection %d: image index outside [0, %d)", -bad - 1, num_images);
+  return FP_OK;
+}
+
+// ------------------------------------------------------------------ joint refinement on features and depth
+int fp_rgbd_refine(const float* map, int64_t sb, int64_t sy, int64_t sx, int64_t sc, int gh, int gw, int C, int W, int H,
+                   const double* feature_cameras, const double* A, const double* a_vec, const float* depth, int num_images, int Hd, int Wd,
+                   const int32_t* image_index, const double* frame_cameras, const double* R_in, const double* t_in,
+                   const int32_t* row_begin, const int32_t* row_end, const float* feats, const float* vertices, int64_t num_rows,
+                   const int32_t* has_pose, const double* tau, double depth_weight, int num_det, int max_points, int iters,
+                   void* scratch, size_t scratch_bytes, double* R_out, double* t_out, double* cost_in, double* cost_out,
+                   int32_t* num_points, int32_t* num_depth_inliers, int32_t* iters_used, int32_t* status, double* normal_eq,
+                   fp_stream_t stream) {
+  FP_REQUIRE(map && feature_cameras && A && a_vec && depth && image_index && frame_cameras && R_in && t_in && row_begin && row_end && feats &&
+             vertices && has_pose && tau && scratch && R_out && t_out && cost_in && cost_out && num_points && num_depth_inliers && iters_used &&
+             status, "fp_rgbd_refine: null pointer");
+  FP_REQUIRE(gh >= 2 && gw >= 2, "fp_rgbd_refine: the feature map is %d x %d, at least 2 x 2 needed", gh, gw);
+  FP_REQUIRE(C >= 1 && W >= 1 && H >= 1, "fp_rgbd_refine: C %d, image %d x %d", C, W, H);
+  FP_REQUIRE(sb >= 0 && sy >= 0 && sx >= 0 && sc >= 0, "fp_rgbd_refine: negative map stride");
+  FP_REQUIRE(num_images >= 1 && Hd >= 2 && Wd >= 2, "fp_rgbd_refine: %d depth images of %d x %d, at least one of 2 x 2 needed", num_images, Wd, Hd);
+  FP_REQUIRE(depth_weight >= 0.0 && depth_weight < INFINITY, "fp_rgbd_refine: depth_weight %g is not a finite number >= 0", depth_weight);
+  FP_REQUIRE(num_det >= 1 && num_det <= 65535, "fp_rgbd_refine: num_det %d outside [1, 65535]", num_det);
+  FP_REQUIRE(max_points >= 1 && num_rows >= 0, "fp_rgbd_refine: max_points %d, num_rows %lld", max_points, (long long)num_rows);
+  FP_REQUIRE(iters >= 0 && iters <= 1000, "fp_rgbd_refine: iters %d outside [0, 1000]", iters);
+  const size_t need = FP_RGBD_REFINE_SCRATCH_BYTES(num_det, max_points);
+  FP_REQUIRE(scratch_bytes >= need, "fp_rgbd_refine: scratch holds %zu bytes, %zu needed", scratch_bytes, need);
+  static_assert(sizeof(RgbdState) <= FP_REFINE_STATE_BYTES, "FP_REFINE_STATE_BYTES");
+  const int chunks = (max_points + FP_REFINE_CHUNK - 1) / FP_REFINE_CHUNK;
+  char* sp = static_cast<char*>(scratch);
+  RgbdRefineArgs a;
+  memset(&a, 0, sizeof(a));
+  a.map = map; a.sb = sb; a.sy = sy; a.sx = sx; a.sc = sc; a.gh = gh; a.gw = gw; a.C = C; a.W = W; a.H = H;
+  a.fcam = feature_cameras; a.A = A; a.a = a_vec; a.depth = depth; a.num_images = num_images; a.Hd = Hd; a.Wd = Wd; a.image_index = image_index;
+  a.cam = frame_cameras; a.R_in = R_in; a.t_in = t_in; a.row_begin = row_begin; a.row_end = row_end; a.feats = feats; a.verts = vertices;
+  a.num_rows = num_rows; a.has_pose = has_pose; a.tau = tau; a.wd = depth_weight; a.num_det = num_det; a.max_points = max_points;
+  a.iters = iters; a.chunks = chunks;
+  a.R_out = R_out; a.t_out = t_out; a.cost_in = cost_in; a.cost_out = cost_out; a.num_points = num_points; a.num_depth_inliers = num_depth_inliers;
+  a.iters_used = iters_used; a.status = status; a.normal_eq = normal_eq;
+  a.state = reinterpret_cast<RgbdState*>(sp);
+  sp += (size_t)FP_REFINE_STATE_BYTES * num_det;
+  a.part = reinterpret_cast<double*>(sp);
+  sp += 16 * (size_t)FP_REFINE_RECORD * num_det * chunks;
+  a.valid = reinterpret_cast<uint8_t*>(sp);
+  sp += (((size_t)num_det * max_points + 7) / 8) * 8;
+  a.err = reinterpret_cast<int32_t*>(sp);
+  HIP_TRY(hipMemsetAsync(a.err, 0, sizeof(int32_t), ST(stream)), "fp_rgbd_refine: clear");
+  TRY(launch_rgbd_refine(a, ST(stream)));
+  // the one wait of this call, after every iteration is enqueued: a bad row range or image index is reported here, never read
+  int32_t bad = 0;
+  HIP_TRY(hipMemcpyWithStream(&bad, a.err, sizeof(int32_t), hipMemcpyDeviceToHost, ST(stream)), "fp_rgbd_refine: status read");
+  FP_REQUIRE(bad <= 0, "fp_rgbd_refine: detection %d: bank rows outside [0, %lld) or more than max_points %d", bad - 1,
+             (long long)num_rows, max_points);
+  FP_REQUIRE(bad == 0, "fp_rgbd_refine: detection %d: image index outside [0, %d)", -bad - 1, num_images);
   return FP_OK;
 }
 

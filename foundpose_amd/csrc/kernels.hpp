@@ -319,6 +319,26 @@ struct DepthRefineArgs {
 };
 int launch_depth_refine(const DepthRefineArgs& a, hipStream_t st);
 
+// ---------------------------------------------------------------- rgbd_refine.hip (features and depth in one objective)
+struct RgbdState {         // scratch, FP_REFINE_STATE_BYTES: the shared LM state (H, g, E are those of the mixed objective) and the depth decision
+  RefineState s;
+  int ninl, use_depth;     // depth inliers at the input pose; whether the depth term takes part (depth_weight > 0 and ninl >= 6)
+};
+struct RgbdRefineArgs {
+  const float* map; long long sb, sy, sx, sc; int gh, gw, C, pad0; double W, H;    // the feature map and its (crop) camera's image size
+  const double* fcam;      // [num_det, 4] the feature camera
+  const double* A; const double* a;    // [num_det, 9], [num_det, 3]: X_f = A X_c + a, frame camera -> feature camera
+  const float* depth; int num_images, Hd, Wd, pad1; const int32_t* image_index;
+  const double* cam;       // [num_det, 4] the frame camera, in which the pose lives
+  const double* R_in; const double* t_in;
+  const int32_t* row_begin; const int32_t* row_end; const float* feats; const float* verts; long long num_rows;
+  const int32_t* has_pose; const double* tau; double wd; int num_det, max_points, iters, chunks;
+  double* R_out; double* t_out; double* cost_in; double* cost_out; int32_t* num_points; int32_t* num_depth_inliers; int32_t* iters_used; int32_t* status;
+  double* normal_eq;       // [num_det, 57] or null
+  RgbdState* state; double* part; uint8_t* valid; int32_t* err;
+};
+int launch_rgbd_refine(const RgbdRefineArgs& a, hipStream_t st);
+
 // ---------------------------------------------------------------- vsd.hip
 struct VsdPair {                         // one (estimate, GT) pair, built on the host by fp_vsd_counts
   long long test_off, est_off, gt_off;   // element offsets of the three depth images (index * height * width)

@@ -62,10 +62,12 @@ class InferOpts(NamedTuple):
     refine_iters: int = 30          # final_pose_type="featuremetric": Levenberg-Marquardt iterations (refine_util)
     depth_refine_iters: int = 30    # final_pose_type="depth" / "featuremetric_depth": iterations against the frame's depth
     depth_refine_max_dist: float = 0.0   # ... its truncation distance tau in mm; 0: a tenth of the diagonal of the bounding box of repre.vertices
+    depth_refine_weight: float = 1.0     # final_pose_type="featuremetric_depth_joint": w_d of E_f + w_d E_d (refine_iters iterations)
 
 
 FINAL_POSE_TYPES = ("best_coarse", "featuremetric", "depth", "featuremetric_depth")
-DEPTH_POSE_TYPES = ("depth", "featuremetric_depth")   # the final pose is refined against the frame's "depth" (refine_util.refine_best_coarse_depth)
+JOINT_POSE_TYPES = ("featuremetric_depth_joint",)   # features and depth in one objective (refine_util.refine_best_coarse_rgbd); a final pose type too
+DEPTH_POSE_TYPES = ("depth", "featuremetric_depth") + JOINT_POSE_TYPES   # the final pose is refined against the frame's "depth"
 
 
 def load_opts(path_or_dict) -> InferOpts:
@@ -86,15 +88,19 @@ def _check_driver_opts(opts: InferOpts):
         raise ValueError(f"Unknown matching type '{opts.match_template_type}'.")
     if opts.match_feat_matching_type != "cyclic_buddies":
         raise ValueError(f"Unknown feature matching type ({opts.match_feat_matching_type}).")
-    if opts.final_pose_type not in FINAL_POSE_TYPES:
+    if opts.final_pose_type not in FINAL_POSE_TYPES + JOINT_POSE_TYPES:
         raise ValueError(f"Unknown final pose type {opts.final_pose_type}")
-    refine = opts.final_pose_type in ("featuremetric", "featuremetric_depth")   # the best coarse pose refined featuremetrically (refine_util)
+    # the best coarse pose refined on the projected feature map (refine_util): the engine keeps the map
+    refine = opts.final_pose_type in ("featuremetric", "featuremetric_depth") + JOINT_POSE_TYPES
     if refine and (not isinstance(opts.refine_iters, int) or opts.refine_iters < 0):
         raise ValueError(f"refine_iters must be an integer >= 0, got {opts.refine_iters!r}")
     if opts.final_pose_type in DEPTH_POSE_TYPES and (not isinstance(opts.depth_refine_iters, int) or opts.depth_refine_iters < 0):
         raise ValueError(f"depth_refine_iters must be an integer >= 0, got {opts.depth_refine_iters!r}")
     if not opts.depth_refine_max_dist >= 0:
         raise ValueError(f"depth_refine_max_dist must be >= 0 (mm; 0: a tenth of the model's bounding-box diagonal), got {opts.depth_refine_max_dist!r}")
+    if isinstance(opts.depth_refine_weight, bool) or not isinstance(opts.depth_refine_weight, (int, float)) \
+            or not 0 <= opts.depth_refine_weight < float("inf"):
+        raise ValueError(f"depth_refine_weight must be a finite number >= 0, got {opts.depth_refine_weight!r}")
     # scripts/infer.py:482-485 subsamples the query points with torch.randperm when a mask yields more than max_num_queries of them
     # (default 1 000 000: never for a crop).  The batched path keeps every point; an option value that could trigger the subsampling
     # is refused instead of being ignored (crop=False: checked per frame against the image's own grid).
@@ -208,8 +214,12 @@ def _stage_times(eng, n: int, t0: float, t1: float, t2: float, t3: float, t4: fl
 
 def _refine_final(opts: InferOpts, res, best, bank: DeviceBank, det_obj, frame_cams, cams, crop_size, depth, image_index, taus):
     """The final pose of a batch for the refining pose types: featuremetric in the cameras PnP solved in, then / or against the frames' depth
-    in the frames' own cameras (refine_util).  Its time is times["pose_refine"].  -> (R [n, 3, 3], t [n, 3]) numpy, in the solve cameras."""
+    in the frames' own cameras, or on both in one objective in the frames' cameras (refine_util).  Its time is times["pose_refine"].  -> (R [n, 3, 3], t [n, 3]) numpy, in the solve cameras."""
     pose = best
+    if opts.final_pose_type in JOINT_POSE_TYPES:
+        pose = refine_util.refine_best_coarse_rgbd(res, best, bank, det_obj, frame_cams, cams, crop_size, depth, image_index, taus,
+                                                   opts.depth_refine_weight, opts.refine_iters)
+        return pose["R"].cpu().numpy(), pose["t"].cpu().numpy()
     if opts.final_pose_type in ("featuremetric", "featuremetric_depth"):
         ref = refine_util.refine_best_coarse(res, best, bank, det_obj, cams, crop_size, opts.refine_iters)
         pose = dict(best, R=ref["R"], t=ref["t"])

@@ -1,11 +1,13 @@
-"""Refinement of the best coarse pose on the MI355X: featuremetric and against the frame's depth (section 14).
+"""Refinement of the best coarse pose on the MI355X: featuremetric, against the frame's depth (section 14), and on
+both in one objective (section 15).
 
 The FoundPose paper's third stage, which the released reference leaves as hooks only (scripts/infer.py:619, `final_pose_type`):
 Levenberg-Marquardt on the 6-DoF pose that aligns the per-point features of the template behind the best coarse pose with the
 query's projected patch-feature map.  One fp_featuremetric_refine call (csrc/refine.hip) refines a whole batch; the contract is
 restated in numpy fp64 by tests/featuremetric_ref.py.  The depth term is this project's own: Levenberg-Marquardt on the truncated
 quadratic of (measured depth at a template point's projection) - (the point's depth), in the frame's own camera; one
-fp_depth_refine call (csrc/depth_refine.hip) per batch, restated by tests/depth_refine_ref.py.
+fp_depth_refine call (csrc/depth_refine.hip) per batch, restated by tests/depth_refine_ref.py.  The joint objective E_f + w_d E_d puts
+both terms into one normal equation: one fp_rgbd_refine call (csrc/rgbd_refine.hip) per batch, restated by tests/rgbd_refine_ref.py.
 """
 
 from typing import Any, Dict, Optional, Sequence, Tuple
@@ -13,7 +15,7 @@ from typing import Any, Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ._lib import call, depth_refine_scratch_bytes, ptr, refine_scratch_bytes, require_cuda, stream, upload_async
+from ._lib import call, depth_refine_scratch_bytes, ptr, refine_scratch_bytes, require_cuda, rgbd_refine_scratch_bytes, stream, upload_async
 from .bank import DeviceBank
 from .matching import MatchResult
 from .pnp_util import _intrinsics
@@ -200,6 +202,124 @@ def refine_best_coarse_depth(res: MatchResult, pose: Dict[str, torch.Tensor], ba
         moved = (out["status"] == STATUS_REFINED).cpu().numpy()
         T = np.linalg.inv(rel) @ _pose_matrices(out["R"], out["t"])
         T0 = _pose_matrices(pose["R"], pose["t"])
+        T[~moved] = T0[~moved]
+        out["R"], out["t"] = torch.from_numpy(T[:, :3, :3].copy()).to(dev), torch.from_numpy(T[:, :3, 3].copy()).to(dev)
+    return out
+
+
+def refine_rgbd(feature_map: torch.Tensor, image_size: Tuple[int, int], feature_cameras: Sequence[Any], A: torch.Tensor, a: torch.Tensor,
+                depth: torch.Tensor, image_index: torch.Tensor, frame_cameras: Sequence[Any], R: torch.Tensor, t: torch.Tensor,
+                row_begin: torch.Tensor, row_end: torch.Tensor, feats: torch.Tensor, vertices: torch.Tensor, has_pose: torch.Tensor, tau,
+                depth_weight: float = 1.0, iters: int = 30, return_normal_equations: bool = False,
+                max_points: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """Features and depth in one Levenberg-Marquardt objective E_f + depth_weight E_d.  feature_map [B, gh, gw, C],
+    image_size (W, H) and feature_cameras: refine_featuremetric's map arguments (the crop cameras); A [B, 3, 3] / a [B, 3] fp64: the rigid
+    transform frame camera -> feature camera, X_f = A X_c + a; depth [N, Hd, Wd], image_index, frame_cameras, tau: refine_depth's;
+    R [B, 3, 3] / t [B, 3]: model -> FRAME camera (mm); rows, feats, vertices, has_pose as in the two calls above.
+    -> refine_depth's dict (num_points: the valid points of the feature term) + num_depth_inliers [B] i32, the depth inliers at the input
+    pose; with return_normal_equations normal_eq [B, 57] f64: H_f | g_f | E_f, H_d | g_d | E_d, E at the input pose."""
+    require_cuda(feature_map, A, a, depth, image_index, R, t, row_begin, row_end, feats, vertices, has_pose)
+    if feature_map.dim() != 4:
+        raise ValueError("feature_map must be [B, gh, gw, C]")
+    B, gh, gw, C = feature_map.shape
+    if gh < 2 or gw < 2:
+        raise ValueError(f"the feature map is {gh} x {gw}: refinement needs at least 2 x 2 cells")
+    if depth.dim() == 2:
+        depth = depth[None]
+    if depth.dim() != 3:
+        raise ValueError("depth must be [N, H, W] or [H, W]")
+    N, Hd, Wd = depth.shape
+    if Hd < 2 or Wd < 2:
+        raise ValueError(f"the depth image is {Hd} x {Wd}: refinement needs at least 2 x 2 pixels")
+    if int(iters) < 0:
+        raise ValueError("iters must be >= 0")
+    if not (float(depth_weight) >= 0.0 and float(depth_weight) < float("inf")):
+        raise ValueError(f"depth_weight must be a finite number >= 0, got {depth_weight!r}")
+    if feats.dim() != 2 or feats.shape[1] != C or vertices.shape != (feats.shape[0], 3):
+        raise ValueError(f"feats {tuple(feats.shape)} / vertices {tuple(vertices.shape)} do not match a C = {C} map")
+    if len(feature_cameras) != B or len(frame_cameras) != B:
+        raise ValueError(f"{len(feature_cameras)} feature cameras and {len(frame_cameras)} frame cameras for {B} detections")
+    if tuple(A.shape) != (B, 3, 3) or tuple(a.shape) != (B, 3):
+        raise ValueError(f"A {tuple(A.shape)} / a {tuple(a.shape)} are not [{B}, 3, 3] / [{B}, 3]")
+    dev = feature_map.device
+    tau_h = torch.as_tensor(tau, dtype=torch.float64).reshape(-1).cpu()
+    if tau_h.numel() == 1:
+        tau_h = tau_h.expand(B)
+    if tau_h.numel() != B:
+        raise ValueError(f"{tau_h.numel()} tau values for {B} detections")
+    fmap = feature_map if feature_map.dtype == torch.float32 else feature_map.float()
+    W, H = int(image_size[0]), int(image_size[1])
+    fcam = upload_async(torch.tensor([_intrinsics(c) for c in feature_cameras], dtype=torch.float64).reshape(B, 4), dev)
+    cam = upload_async(torch.tensor([_intrinsics(c) for c in frame_cameras], dtype=torch.float64).reshape(B, 4), dev)
+    tau_d = upload_async(tau_h.contiguous(), dev)
+    Ain = A.to(torch.float64).reshape(B, 9).contiguous()
+    ain = a.to(torch.float64).reshape(B, 3).contiguous()
+    d32 = depth.float().contiguous()
+    ii = image_index.to(torch.int32).contiguous()
+    Rin = R.to(torch.float64).reshape(B, 9).contiguous()
+    tin = t.to(torch.float64).reshape(B, 3).contiguous()
+    rb = row_begin.to(torch.int32).contiguous()
+    re = row_end.to(torch.int32).contiguous()
+    hp = has_pose.to(torch.int32).contiguous()
+    f32 = feats.float().contiguous()
+    v32 = vertices.float().contiguous()
+    if max_points is None:
+        max_points = int(torch.where(hp != 0, re - rb, torch.zeros_like(re)).max().item()) if B else 0
+    max_points = max(1, int(max_points))
+    scratch = torch.empty(rgbd_refine_scratch_bytes(B, max_points), dtype=torch.uint8, device=dev)
+    Ro = torch.empty(B, 9, dtype=torch.float64, device=dev)
+    to = torch.empty(B, 3, dtype=torch.float64, device=dev)
+    cin = torch.empty(B, dtype=torch.float64, device=dev)
+    cout = torch.empty(B, dtype=torch.float64, device=dev)
+    npts = torch.empty(B, dtype=torch.int32, device=dev)
+    ninl = torch.empty(B, dtype=torch.int32, device=dev)
+    used = torch.empty(B, dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    neq = torch.empty(B, 57, dtype=torch.float64, device=dev) if return_normal_equations else None
+    sb, sy, sx, sc = fmap.stride()
+    call("fp_rgbd_refine", ptr(fmap), sb, sy, sx, sc, gh, gw, C, W, H, ptr(fcam), ptr(Ain), ptr(ain), ptr(d32), N, Hd, Wd, ptr(ii), ptr(cam), ptr(Rin),
+         ptr(tin), ptr(rb), ptr(re), ptr(f32), ptr(v32), int(f32.shape[0]), ptr(hp), ptr(tau_d), float(depth_weight), B, max_points, int(iters),
+         ptr(scratch), scratch.numel(), ptr(Ro), ptr(to), ptr(cin), ptr(cout), ptr(npts), ptr(ninl), ptr(used), ptr(status), ptr(neq), stream())
+    out = {"R": Ro.reshape(B, 3, 3), "t": to, "cost_in": cin, "cost_out": cout, "num_points": npts, "num_depth_inliers": ninl, "iters_used": used,
+           "status": status}
+    if neq is not None:
+        out["normal_eq"] = neq
+    return out
+
+
+def refine_best_coarse_rgbd(res: MatchResult, best: Dict[str, torch.Tensor], bank: DeviceBank, det_obj: Optional[Sequence[int]],
+                            frame_cameras: Sequence[Any], solve_cameras: Sequence[Any], image_size: Tuple[int, int], depth: torch.Tensor,
+                            image_index, tau, depth_weight: float = 1.0, iters: int = 30) -> Dict[str, torch.Tensor]:
+    """Refines select_best_coarse's pose of every detection of an infer_batch(..., keep_feature_map=True) result on that result's
+    projected feature map and the frames' depth in one objective.  The poses live in solve_cameras (the crop cameras, image_size
+    their size); they are moved into frame_cameras as in refine_best_coarse_depth, refined there -- the feature term reaches its crop
+    camera through (A, a) = the inverse of that move -- and moved back.  Where both cameras are the same object (crop=False) nothing is
+    converted and (A, a) is the identity.  -> refine_rgbd's dict, R / t in the solve cameras."""
+    if res.feature_map is None:
+        raise ValueError("the MatchResult carries no feature map: run infer_batch(..., keep_feature_map=True)")
+    res.wait()
+    B = res.template_ids.shape[0]
+    det_obj = [0] * B if det_obj is None else list(det_obj)
+    rb, re, ok = best_template_rows(res, best, bank, det_obj)
+    dev = res.template_ids.device
+    same = all(f is s for f, s in zip(frame_cameras, solve_cameras))
+    R, t = best["R"], best["t"]
+    Aa = np.tile(np.eye(4), (B, 1, 1))
+    if not same:
+        rel = np.stack([np.linalg.inv(np.asarray(f.T_world_from_eye, np.float64)) @ np.asarray(s.T_world_from_eye, np.float64)
+                        for f, s in zip(frame_cameras, solve_cameras)])
+        Aa = np.linalg.inv(rel)
+        T = rel @ _pose_matrices(R, t)
+        R, t = upload_async(torch.from_numpy(T[:, :3, :3].copy()), dev), upload_async(torch.from_numpy(T[:, :3, 3].copy()), dev)
+    A, a = upload_async(torch.from_numpy(Aa[:, :3, :3].copy()), dev), upload_async(torch.from_numpy(Aa[:, :3, 3].copy()), dev)
+    ii = image_index if isinstance(image_index, torch.Tensor) else upload_async(torch.tensor(list(image_index), dtype=torch.int32), dev)
+    out = refine_rgbd(res.feature_map, image_size, solve_cameras, A, a, depth, ii, frame_cameras, R, t, rb, re, bank.feats, bank.vertices, ok, tau,
+                      depth_weight, iters, max_points=bank.p_max)
+    if not same:
+        # detections whose pose did not move keep the solve-camera pose they came with, bit for bit
+        moved = (out["status"] == STATUS_REFINED).cpu().numpy()
+        T = Aa @ _pose_matrices(out["R"], out["t"])
+        T0 = _pose_matrices(best["R"], best["t"])
         T[~moved] = T0[~moved]
         out["R"], out["t"] = torch.from_numpy(T[:, :3, :3].copy()).to(dev), torch.from_numpy(T[:, :3, 3].copy()).to(dev)
     return out

@@ -629,6 +629,38 @@ int fp_depth_refine(const float* depth, int num_images, int H, int W, const int3
                     void* scratch, size_t scratch_bytes, double* R_out, double* t_out, double* cost_in, double* cost_out,
                     int32_t* num_points, int32_t* iters_used, int32_t* status, double* normal_eq, fp_stream_t stream);
 
+/* ---- joint refinement on features and depth (tests/rgbd_refine_ref.py restates it) --------------------------
+ * One Levenberg-Marquardt objective E = E_f + depth_weight E_d per detection.  The pose (R, t) is model -> FRAME camera (mm).
+ *   map, strides, gh, gw, C, W, H, feature_cameras   the featuremetric call's map arguments: the projected feature map and the camera
+ *               (fx, fy, cx, cy; image W x H) it belongs to, the crop camera
+ *   A, a        fp64 [num_det, 9], [num_det, 3]  the rigid transform frame camera -> feature camera, X_f = A X_c + a
+ *   depth, num_images, Hd, Wd, image_index, frame_cameras, tau   the depth call's arguments: the frames' depth images and cameras
+ *   R_in, t_in, row_begin, row_end, feats, vertices, num_rows, has_pose   as in the two calls above; a bad row range or image index is
+ *               reported by FP_ERR_INVALID naming the detection, and such rows and images are never read
+ *   depth_weight  w_d >= 0 (a negative or NaN value: FP_ERR_INVALID before any device work)
+ * Feature term: the featuremetric call's, evaluated at X_f: valid set V frozen at the input pose, sigma^2 the mean squared residual
+ * over V there (floored at 1e-12), weight 1 / (1 + s / sigma^2), E_f = sum_V log(1 + s / sigma^2) / |V|; the Jacobian carries A, the
+ * twist is left-multiplied on the frame-camera pose.  Depth term: the depth call's at X_c, and a point is measurable only if also
+ * max(taps) - min(taps) <= tau; E_d = sum min(r^2, tau^2) / (N tau^2) over the N rows of the range.
+ * H = H_f / (|V| sigma^2) + w_d H_d / (N tau^2), g likewise.  The LM loop is the featuremetric call's (a trial that puts a point of
+ * V at z_f <= 1 mm is rejected).  A detection with w_d = 0 or fewer than 6 depth inliers at the input pose runs on E_f alone.
+ * Outputs as above: num_points = |V|, num_depth_inliers = the inliers at the input pose, status 0 refined, 1 no step accepted,
+ * 2 skipped (no pose, empty range, |V| < 6); for 1 and 2 the pose is the input bit for bit; cost_out <= cost_in always.
+ * normal_eq fp64 [num_det, 57] may be null: H_f (21) | g_f (6) | E_f, H_d (21) | g_d (6) | E_d, E, at the input pose.
+ * Deterministic and bit-identical across batch compositions; no float atomics.  scratch: FP_RGBD_REFINE_SCRATCH_BYTES. */
+#define FP_RGBD_REFINE_SCRATCH_BYTES(num_det, max_points)                                                              \
+  ((size_t)FP_REFINE_STATE_BYTES * (size_t)(num_det) +                                                                  \
+   16 * FP_REFINE_RECORD * (size_t)(num_det) * (((size_t)(max_points) + FP_REFINE_CHUNK - 1) / FP_REFINE_CHUNK) +      \
+   (((size_t)(num_det) * (size_t)(max_points) + 7) / 8) * 8 + 8)
+int fp_rgbd_refine(const float* map, int64_t sb, int64_t sy, int64_t sx, int64_t sc, int gh, int gw, int C, int W, int H,
+                   const double* feature_cameras, const double* A, const double* a, const float* depth, int num_images, int Hd, int Wd,
+                   const int32_t* image_index, const double* frame_cameras, const double* R_in, const double* t_in,
+                   const int32_t* row_begin, const int32_t* row_end, const float* feats, const float* vertices, int64_t num_rows,
+                   const int32_t* has_pose, const double* tau, double depth_weight, int num_det, int max_points, int iters,
+                   void* scratch, size_t scratch_bytes, double* R_out, double* t_out, double* cost_in, double* cost_out,
+                   int32_t* num_points, int32_t* num_depth_inliers, int32_t* iters_used, int32_t* status, double* normal_eq,
+                   fp_stream_t stream);
+
 /* ---- result pictures (utils/vis_util.py:179-687 vis_inference_results in its vis_for_paper layout; DESIGN.md section 12;
  * tests/vis_ref.py restates every entry) ---------------------------------------------------------------------------------
  * Images are uint8 HWC (3 channels), contiguous, with a leading batch dimension; sides lie in [1, FP_VIS_MAX_SIDE].  One thread
