@@ -262,6 +262,26 @@ int fp_pnp_ransac_keyed(const float* coord_2d, const float* coord_3d, const int3
                           confidence, lm_iters, min_corresp, seed, out_success, out_R, out_t, out_num_inliers, out_inlier_mask, out_ransac_pose, stream);
 }
 
+int fp_kabsch_ransac(const float* coord_2d, const float* coord_3d, const int32_t* counts, const double* solve_cameras, const double* frame_cameras,
+                     const double* A, const int32_t* image_index, const double* inlier_thresh_mm, const float* depth, int num_images, int H, int W,
+                     const uint64_t* pair_keys, int num_pairs, int n_slots, int k_max, int ransac_iters, double confidence, int refit,
+                     int min_corresp, uint64_t seed, int32_t* out_success, double* out_R, double* out_t, int32_t* out_num_inliers,
+                     int32_t* out_num_valid, uint8_t* out_inlier_mask, double* out_ransac_pose, fp_stream_t stream) {
+  FP_REQUIRE(coord_2d && coord_3d && counts && solve_cameras && frame_cameras && A && image_index && inlier_thresh_mm && depth && out_success &&
+             out_R && out_t && out_num_inliers && out_num_valid && out_inlier_mask, "fp_kabsch_ransac: null pointer");
+  FP_REQUIRE(num_pairs >= 0 && n_slots >= 1 && num_pairs % n_slots == 0, "fp_kabsch_ransac: num_pairs must be a multiple of n_slots");
+  KabschArgs a;
+  memset(&a, 0, sizeof(a));
+  a.coord_2d = coord_2d; a.coord_3d = coord_3d; a.counts = counts; a.cam = solve_cameras; a.frame_cam = frame_cameras; a.A = A;
+  a.image_index = image_index; a.tau = inlier_thresh_mm; a.depth = depth; a.num_images = num_images; a.H = H; a.W = W;
+  a.n_slots = n_slots; a.k_max = k_max; a.iters = ransac_iters; a.refit = refit ? 1 : 0; a.min_corresp = min_corresp;
+  a.conf = confidence; a.seed = seed;
+  a.pair_keys = reinterpret_cast<const unsigned long long*>(pair_keys);
+  a.success = out_success; a.R = out_R; a.t = out_t; a.n_inliers = out_num_inliers; a.num_valid = out_num_valid;
+  a.inlier_mask = out_inlier_mask; a.ransac_pose = out_ransac_pose;
+  return launch_kabsch_ransac(a, num_pairs, ST(stream));
+}
+
 // ------------------------------------------------------------------ ViT building blocks
 int fp_patchify(const float* images, int B, int H, int W, int patch, void* out, int ld_out, int out_dtype,
                 fp_stream_t stream) {

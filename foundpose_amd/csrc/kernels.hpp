@@ -386,3 +386,29 @@ struct PnpArgs {
   double* ransac_pose;     // [pairs, 12] the winning model before refinement (R | t), may be null
 };
 int launch_pnp_ransac(const PnpArgs& a, int num_pairs, hipStream_t st);
+
+// ---------------------------------------------------------------- kabsch.hip
+struct KabschArgs {
+  const float* coord_2d;   // [pairs, k_max, 2] pixels in the solve camera
+  const float* coord_3d;   // [pairs, k_max, 3] model space (mm)
+  const int* counts;       // [pairs] correspondences per pair (clamped to [0, k_max])
+  const double* cam;       // [dets, 4] fx, fy, cx, cy of each detection's solve camera (dets = pairs / n_slots)
+  const double* frame_cam; // [dets, 4] ... of its frame's camera
+  const double* A;         // [dets, 9] row-major rotation solve camera -> frame camera
+  const int* image_index;  // [dets] the detection's image in `depth`
+  const double* tau;       // [dets] inlier threshold (mm)
+  const float* depth;      // [num_images, H, W] mm, 0 = no measurement
+  int num_images, H, W;
+  int n_slots, k_max, iters, refit, min_corresp;
+  double conf;
+  unsigned long long seed;
+  const unsigned long long* pair_keys;  // [pairs] sampler key of each pair, or null: the pair's index in the launch
+  int* success;            // [pairs] 1, 0 (no pose), -1 (image index outside the stack / threshold not positive: nothing read)
+  double* R;               // [pairs, 9] row-major model -> solve camera
+  double* t;               // [pairs, 3]
+  int* n_inliers;          // [pairs] inliers of the winning hypothesis
+  int* num_valid;          // [pairs] correspondences with a depth measurement
+  unsigned char* inlier_mask;  // [pairs, k_max]
+  double* ransac_pose;     // [pairs, 12] the winning hypothesis before the refit (R | t), may be null
+};
+int launch_kabsch_ransac(const KabschArgs& a, int num_pairs, hipStream_t st);

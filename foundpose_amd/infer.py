@@ -63,11 +63,13 @@ class InferOpts(NamedTuple):
     depth_refine_iters: int = 30    # final_pose_type="depth" / "featuremetric_depth": iterations against the frame's depth
     depth_refine_max_dist: float = 0.0   # ... its truncation distance tau in mm; 0: a tenth of the diagonal of the bounding box of repre.vertices
     depth_refine_weight: float = 1.0     # final_pose_type="featuremetric_depth_joint": w_d of E_f + w_d E_d (refine_iters iterations)
+    depth_pnp_inlier_thresh: float = 0.0   # pnp_type="kabsch_depth": the 3D inlier threshold in mm; 0: 0.05 x the diagonal of the bounding box of repre.vertices
 
 
 FINAL_POSE_TYPES = ("best_coarse", "featuremetric", "depth", "featuremetric_depth")
 JOINT_POSE_TYPES = ("featuremetric_depth_joint",)   # features and depth in one objective (refine_util.refine_best_coarse_rgbd); a final pose type too
 DEPTH_POSE_TYPES = ("depth", "featuremetric_depth") + JOINT_POSE_TYPES   # the final pose is refined against the frame's "depth"
+DEPTH_PNP_TYPES = ("kabsch_depth",)   # the coarse poses are solved on the frame's "depth" (pnp_util.solve_kabsch_ransac_batch)
 
 
 def load_opts(path_or_dict) -> InferOpts:
@@ -90,6 +92,12 @@ def _check_driver_opts(opts: InferOpts):
         raise ValueError(f"Unknown feature matching type ({opts.match_feat_matching_type}).")
     if opts.final_pose_type not in FINAL_POSE_TYPES + JOINT_POSE_TYPES:
         raise ValueError(f"Unknown final pose type {opts.final_pose_type}")
+    if opts.pnp_type not in pnp_util.PNP_TYPES:
+        raise ValueError(f"Unknown PnP type '{opts.pnp_type}' (one of {', '.join(pnp_util.PNP_TYPES)})")
+    if isinstance(opts.depth_pnp_inlier_thresh, bool) or not isinstance(opts.depth_pnp_inlier_thresh, (int, float)) \
+            or not 0 <= opts.depth_pnp_inlier_thresh < float("inf"):
+        raise ValueError(f"depth_pnp_inlier_thresh must be a finite number >= 0 (mm; 0: a twentieth of the model's bounding-box diagonal), "
+                         f"got {opts.depth_pnp_inlier_thresh!r}")
     # the best coarse pose refined on the projected feature map (refine_util): the engine keeps the map
     refine = opts.final_pose_type in ("featuremetric", "featuremetric_depth") + JOINT_POSE_TYPES
     if refine and (not isinstance(opts.refine_iters, int) or opts.refine_iters < 0):
@@ -177,19 +185,33 @@ def depth_refine_tau(opts: InferOpts, repre) -> float:
     return 0.1 * float(np.linalg.norm(v.max(0) - v.min(0)))
 
 
-def _check_frame_depth(frame: Dict[str, Any]) -> None:
-    """A frame that has work under a depth pose type must carry "depth" of the camera's size: refused by name otherwise."""
+def depth_pnp_tau(opts: InferOpts, repre) -> float:
+    """The 3D inlier threshold of pnp_type "kabsch_depth" for one object (mm), computed once per object on the host."""
+    if opts.depth_pnp_inlier_thresh > 0:
+        return float(opts.depth_pnp_inlier_thresh)
+    v = repre.vertices.detach().cpu().numpy().astype(np.float64)
+    return 0.05 * float(np.linalg.norm(v.max(0) - v.min(0)))
+
+
+def _check_frame_depth(frame: Dict[str, Any], why: str = "the final pose type refines against depth") -> None:
+    """A frame that has work under a depth pose type or a depth PnP type must carry "depth" of the camera's size: refused by name otherwise."""
     cam, d = frame["camera"], frame.get("depth")
     where = f"scene {frame['scene_id']} image {frame['im_id']}"
     if d is None:
-        raise ValueError(f"{where}: the final pose type refines against depth, but the frame carries no \"depth\"")
+        raise ValueError(f"{where}: {why}, but the frame carries no \"depth\"")
     if tuple(d.shape) != (cam.height, cam.width):
         raise ValueError(f"{where}: depth is {tuple(d.shape)}, the camera's image is ({cam.height}, {cam.width})")
 
 
-def _frame_depth(frame: Dict[str, Any]) -> torch.Tensor:
+def _depth_reason(opts: InferOpts) -> str:
+    if opts.pnp_type in DEPTH_PNP_TYPES:
+        return f"pnp_type '{opts.pnp_type}' solves the coarse poses on depth"
+    return "the final pose type refines against depth"
+
+
+def _frame_depth(frame: Dict[str, Any], why: str = "the final pose type refines against depth") -> torch.Tensor:
     """A frame's "depth" (float32 mm [H, W], numpy or tensor, 0 = no measurement) on the device."""
-    _check_frame_depth(frame)
+    _check_frame_depth(frame, why)
     d = frame["depth"]
     if not isinstance(d, torch.Tensor):
         arr = np.asarray(d)
@@ -283,6 +305,7 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
             raise ValueError("pictures need an output_dir")
     refine, check_max_queries = _check_driver_opts(opts)
     use_depth = opts.final_pose_type in DEPTH_POSE_TYPES
+    depth_pnp = opts.pnp_type in DEPTH_PNP_TYPES
     if extractor is None:  # infer.py:125-128; the checkpoint: weights=, $FOUNDPOSE_DINOV2_WEIGHTS or the torch hub cache, else this raises
         extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
     bank = DeviceBank([repre])
@@ -292,14 +315,15 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
     vertices = repre.vertices.cpu().numpy()
     vis_templates = repre.templates.cuda() if vis else None
     tau = depth_refine_tau(opts, repre) if use_depth else None
+    pnp_tau = depth_pnp_tau(opts, repre) if depth_pnp else None
 
     for frame in frames:
         scene_id, im_id, cam = frame["scene_id"], frame["im_id"], frame["camera"]
         kept = select_instances(opts, object_lid, frame, detections, num_target_insts, eval_model, evaluator.detection_times)
         if not kept:
             continue
-        if use_depth:
-            _check_frame_depth(frame)
+        if use_depth or depth_pnp:
+            _check_frame_depth(frame, _depth_reason(opts))
         t0 = time.perf_counter()
         img = _to_device_image(frame["image"])
         masks = torch.from_numpy(np.stack([i["input_mask_modal"] for _, i in kept]).astype(np.uint8)).cuda()
@@ -321,8 +345,15 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
         res = eng.infer_batch(crops, crop_masks, [0] * len(kept), keep_feature_map=refine or vis)
         torch.cuda.synchronize()
         t2 = time.perf_counter()
-        poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
-                                        opts.pnp_refine_lm, seed=seed)
+        depth = None
+        if depth_pnp:   # one stack per frame, shared with the depth refiners below (the upload is part of pose_coarse)
+            depth = _frame_depth(frame, _depth_reason(opts))
+            poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
+                                            opts.pnp_refine_lm, seed=seed, frame_cameras=[cam] * len(kept), depth=depth[None],
+                                            image_index=[0] * len(kept), depth_inlier_thresh_mm=pnp_tau)
+        else:
+            poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
+                                            opts.pnp_refine_lm, seed=seed)
         torch.cuda.synchronize()
         t3 = time.perf_counter()
         best = pnp_util.select_best_coarse(poses)
@@ -331,9 +362,10 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
         t4 = time.perf_counter()
         t5 = None
         if refine or use_depth:   # infer.py:619: the refined pose of the best coarse pose is the final pose
-            depth = _frame_depth(frame) if use_depth else None   # (the upload is part of pose_refine)
-            Rb, tb = _refine_final(opts, res, best, bank, [0] * len(kept), [cam] * len(kept), cams, (crops.shape[-1], crops.shape[-2]), depth,
-                                   [0] * len(kept), [tau] * len(kept))
+            if use_depth and depth is None:   # (the upload is part of pose_refine)
+                depth = _frame_depth(frame)
+            Rb, tb = _refine_final(opts, res, best, bank, [0] * len(kept), [cam] * len(kept), cams, (crops.shape[-1], crops.shape[-2]),
+                                   depth if use_depth else None, [0] * len(kept), [tau] * len(kept))
             t5 = time.perf_counter()
         n = len(kept)
         times = _stage_times(eng, n, t0, t1, t2, t3, t4, t5)
@@ -481,6 +513,7 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
                                   "the batched driver makes none")
     refine, check_max_queries = _check_driver_opts(opts)
     use_depth = opts.final_pose_type in DEPTH_POSE_TYPES
+    depth_pnp = opts.pnp_type in DEPTH_PNP_TYPES
     lids = sorted(opts.object_lids) if opts.object_lids is not None else sorted(repres)
     if extractor is None:
         extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
@@ -491,6 +524,7 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
     vertices = [repres[l].vertices.cpu().numpy() for l in lids]
     models = [None if eval_models is None else eval_models.get(l) for l in lids]
     taus = [depth_refine_tau(opts, repres[l]) for l in lids] if use_depth else None
+    pnp_taus = [depth_pnp_tau(opts, repres[l]) for l in lids] if depth_pnp else None
 
     def entries():
         for frame_no, frame in enumerate(frames):
@@ -498,8 +532,8 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
             for o, lid in enumerate(lids):
                 kept = select_instances(opts, lid, frame, detections, None if num_target_insts is None else num_target_insts.get(lid, {}),
                                         models[o], evaluators[o].detection_times)
-                if kept and use_depth:
-                    _check_frame_depth(frame)
+                if kept and (use_depth or depth_pnp):
+                    _check_frame_depth(frame, _depth_reason(opts))
                 if kept and not opts.crop and not checked:   # (as in infer_object: only a frame that has work is checked)
                     h, w = frame["image"].shape[:2]
                     ps = extractor.patch_size
@@ -536,8 +570,15 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
         t2 = time.perf_counter()
         n_slots = int(res.counts.shape[1])
         keys = [[g * n_slots + j for j in range(n_slots)] for g in plan.pair_group_index]
-        poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
-                                        opts.pnp_refine_lm, seed=seed, pair_keys=keys)
+        depth = None
+        if depth_pnp:   # the depth images of the flush, stacked once and shared with the depth refiners below (the upload is part of pose_coarse)
+            depth = torch.stack([_frame_depth(by_no[f], _depth_reason(opts)) for f in plan.frames])
+            poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
+                                            opts.pnp_refine_lm, seed=seed, pair_keys=keys, frame_cameras=src_cams, depth=depth,
+                                            image_index=plan.image_index, depth_inlier_thresh_mm=[pnp_taus[o] for o in plan.det_obj])
+        else:
+            poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
+                                            opts.pnp_refine_lm, seed=seed, pair_keys=keys)
         torch.cuda.synchronize()
         t3 = time.perf_counter()
         best = pnp_util.select_best_coarse(poses)
@@ -547,8 +588,10 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
         t5 = None
         if refine or use_depth:
             # the depth images of the flush, stacked like its RGB images and read through plan.image_index (the upload is part of pose_refine)
-            depth = torch.stack([_frame_depth(by_no[f]) for f in plan.frames]) if use_depth else None
-            Rb, tb = _refine_final(opts, res, best, bank, plan.det_obj, src_cams, cams, (crops.shape[-1], crops.shape[-2]), depth, plan.image_index,
+            if use_depth and depth is None:
+                depth = torch.stack([_frame_depth(by_no[f]) for f in plan.frames])
+            Rb, tb = _refine_final(opts, res, best, bank, plan.det_obj, src_cams, cams, (crops.shape[-1], crops.shape[-2]),
+                                   depth if use_depth else None, plan.image_index,
                                    [taus[o] for o in plan.det_obj] if use_depth else None)
             t5 = time.perf_counter()
         times = _stage_times(eng, n, t0, t1, t2, t3, t4, t5)
@@ -686,7 +729,7 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     if args.batch_detections >= 1 and args.vis:
         ap.error("--vis needs the per-object driver: drop --batch-detections (or pass 0)")
     opts = load_opts(args.opts)
-    with_depth = opts.final_pose_type in DEPTH_POSE_TYPES   # the depth pose types read depth/<im>.png beside every image
+    with_depth = opts.final_pose_type in DEPTH_POSE_TYPES or opts.pnp_type in DEPTH_PNP_TYPES   # the depth pose / PnP types read depth/<im>.png beside every image
     # the checkpoint is resolved before anything else is read: a missing one must fail in seconds, not after the banks are loaded
     extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=args.precision, weights=args.weights)
     with open(args.targets or os.path.join(os.path.dirname(os.path.abspath(args.dataset_dir)), "test_targets_bop19.json")) as f:

@@ -82,12 +82,118 @@ def solve_pnp_ransac_batch(coord_2d: torch.Tensor, coord_3d: torch.Tensor, count
     return out
 
 
+PNP_TYPES = ("opencv", "kabsch_depth")
+
+
+def _pair_keys_tensor(pair_keys, B: int, n: int, dev):
+    if pair_keys is None:
+        return None
+    if isinstance(pair_keys, torch.Tensor):
+        if pair_keys.dtype != torch.int64:
+            raise ValueError(f"pair_keys must be int64, got {pair_keys.dtype}")
+    else:
+        pair_keys = torch.tensor(pair_keys, dtype=torch.int64)
+    if tuple(pair_keys.shape) != (B, n):
+        raise ValueError(f"pair_keys must have shape [{B}, {n}], got {list(pair_keys.shape)}")
+    return pair_keys.contiguous() if pair_keys.is_cuda else upload_async(pair_keys, dev)   # (the int64 bits are the uint64 keys)
+
+
+def solve_to_frame_rotations(solve_cameras: Sequence[Any], frame_cameras: Sequence[Any]) -> np.ndarray:
+    """A [B, 3, 3] fp64: the rotation solve camera -> frame camera of every detection, from rel = inv(frame.T_world_from_eye) @
+    solve.T_world_from_eye.  The crop camera looks at its box from the frame camera's own position, so rel has no translation; one whose
+    translation exceeds 1e-6 (1 + |eye position|) is refused (a depth pixel then could not be found from a ray alone).  The same camera
+    object on both sides (crop=False) gives the identity."""
+    A = np.empty((len(solve_cameras), 3, 3), np.float64)
+    for i, (s, f) in enumerate(zip(solve_cameras, frame_cameras)):
+        if s is f:
+            A[i] = np.eye(3)
+            continue
+        Tf, Ts = np.asarray(f.T_world_from_eye, np.float64), np.asarray(s.T_world_from_eye, np.float64)
+        rel = np.linalg.inv(Tf) @ Ts
+        off, bound = float(np.linalg.norm(rel[:3, 3])), 1e-6 * (1.0 + float(np.linalg.norm(Tf[:3, 3])))
+        if not off <= bound:
+            raise ValueError(f"detection {i}: the solve camera's centre is {off:.3g} away from the frame camera's (more than {bound:.3g}): "
+                             "kabsch_depth needs cameras that share their centre")
+        A[i] = rel[:3, :3]
+    return A
+
+
+def solve_kabsch_ransac_batch(coord_2d: torch.Tensor, coord_3d: torch.Tensor, counts: torch.Tensor, solve_cameras: Sequence[Any],
+                              frame_cameras: Sequence[Any], depth: torch.Tensor, image_index, inlier_thresh_mm, ransac_iter: int = 1000,
+                              required_conf: float = 0.99, refit: bool = True, seed: int = 0, return_ransac_pose: bool = False,
+                              min_corresp: int = 6, pair_keys=None) -> Dict[str, torch.Tensor]:
+    """Coarse poses from depth-lifted correspondences: 3D-3D RANSAC + Horn's closed-form refit (csrc/kabsch.hip).
+    coord_2d / coord_3d / counts / pair_keys / min_corresp: as in solve_pnp_ransac_batch, the pixels in solve_cameras (one per detection);
+    frame_cameras: the frames' own cameras (the same objects with crop=False); depth [N, H, W] fp32 mm on the device, 0 = no measurement;
+    image_index: B host integers, the image of each detection; inlier_thresh_mm: one number or one per detection (> 0).
+    -> solve_pnp_ransac_batch's dict (poses model -> solve camera, quality = 3D inliers) + num_valid [B, n], the correspondences that
+    found a depth measurement.  A bad image index, threshold or camera pair raises ValueError before anything is launched."""
+    require_cuda(coord_2d, coord_3d, counts, depth)
+    B, n, K = coord_2d.shape[:3]
+    dev = coord_2d.device
+    if len(solve_cameras) != B or len(frame_cameras) != B:
+        raise ValueError(f"{len(solve_cameras)} solve cameras and {len(frame_cameras)} frame cameras for {B} detections")
+    if depth.dim() != 3 or depth.dtype != torch.float32:
+        raise ValueError(f"depth must be a float32 stack [N, H, W], got {depth.dtype} {list(depth.shape)}")
+    N, H, W = (int(s) for s in depth.shape)
+    if isinstance(image_index, torch.Tensor):
+        image_index = image_index.cpu().tolist()
+    ii = [int(i) for i in image_index]
+    if len(ii) != B:
+        raise ValueError(f"{len(ii)} image indices for {B} detections")
+    for b, i in enumerate(ii):
+        if not 0 <= i < N:
+            raise ValueError(f"detection {b}: image index {i} outside [0, {N})")
+    tau = np.broadcast_to(np.asarray(inlier_thresh_mm, np.float64), (B,)) if np.ndim(inlier_thresh_mm) == 0 else np.asarray(inlier_thresh_mm, np.float64).reshape(-1)
+    if tau.shape != (B,) or not np.all(tau > 0) or not np.all(np.isfinite(tau)):
+        raise ValueError(f"inlier_thresh_mm must be one finite number > 0 or {B} of them, got {inlier_thresh_mm!r}")
+    A = solve_to_frame_rotations(solve_cameras, frame_cameras)
+    table = torch.cat([torch.tensor([_intrinsics(c) for c in solve_cameras], dtype=torch.float64).reshape(B, 4),
+                       torch.tensor([_intrinsics(c) for c in frame_cameras], dtype=torch.float64).reshape(B, 4),
+                       torch.from_numpy(A.reshape(B, 9)), torch.from_numpy(np.ascontiguousarray(tau)).reshape(B, 1)], dim=1)   # [B, 18]: one upload
+    table = upload_async(table, dev)
+    cam, fcam, Ad, taud = table[:, :4].contiguous(), table[:, 4:8].contiguous(), table[:, 8:17].contiguous(), table[:, 17].contiguous()
+    iid = upload_async(torch.tensor(ii, dtype=torch.int32), dev)
+    keys = _pair_keys_tensor(pair_keys, B, n, dev)
+    c2, c3 = coord_2d.float().contiguous(), coord_3d.float().contiguous()
+    cnt = counts.to(torch.int32).contiguous()
+    dimg = depth.contiguous()
+    P = B * n
+    success = torch.zeros(P, dtype=torch.int32, device=dev)
+    R = torch.zeros(P, 9, dtype=torch.float64, device=dev)
+    t = torch.zeros(P, 3, dtype=torch.float64, device=dev)
+    ninl = torch.zeros(P, dtype=torch.int32, device=dev)
+    nval = torch.zeros(P, dtype=torch.int32, device=dev)
+    mask = torch.zeros(P, K, dtype=torch.uint8, device=dev)
+    rp = torch.zeros(P, 12, dtype=torch.float64, device=dev) if return_ransac_pose else None
+    call("fp_kabsch_ransac", ptr(c2), ptr(c3), ptr(cnt), ptr(cam), ptr(fcam), ptr(Ad), ptr(iid), ptr(taud), ptr(dimg), N, H, W, ptr(keys), P, n, K,
+         int(ransac_iter), float(required_conf), int(bool(refit)), int(min_corresp), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(success), ptr(R), ptr(t),
+         ptr(ninl), ptr(nval), ptr(mask), ptr(rp), stream())
+    out = {"success": (success.reshape(B, n) > 0), "R": R.reshape(B, n, 3, 3), "t": t.reshape(B, n, 3),
+           "quality": ninl.reshape(B, n).to(torch.float64), "inliers": mask.reshape(B, n, K).bool(), "num_valid": nval.reshape(B, n)}
+    if rp is not None:
+        out["ransac_pose"] = rp.reshape(B, n, 12)
+    return out
+
+
 def estimate_poses(res: MatchResult, cameras: Sequence[Any], pnp_type: str = "opencv", pnp_ransac_iter: int = 1000,
-                   pnp_inlier_thresh: float = 3.0, pnp_required_ransac_conf: float = 0.99, pnp_refine_lm: bool = True, seed: int = 0, pair_keys=None):
-    """All coarse poses of a batch (the loop of infer.py:552-580 for every detection at once).  pair_keys: see solve_pnp_ransac_batch."""
-    if pnp_type != "opencv":
+                   pnp_inlier_thresh: float = 3.0, pnp_required_ransac_conf: float = 0.99, pnp_refine_lm: bool = True, seed: int = 0, pair_keys=None,
+                   *, frame_cameras: Optional[Sequence[Any]] = None, depth: Optional[torch.Tensor] = None, image_index=None,
+                   depth_inlier_thresh_mm=None):
+    """All coarse poses of a batch (the loop of infer.py:552-580 for every detection at once).  pair_keys: see solve_pnp_ransac_batch.
+    pnp_type "kabsch_depth": 3D-3D RANSAC on depth-lifted correspondences (solve_kabsch_ransac_batch) -- needs the four keyword
+    arguments (the frames' cameras, the depth stack, each detection's image in it, the inlier threshold in mm); pnp_inlier_thresh
+    (pixels) is not used by it."""
+    if pnp_type not in PNP_TYPES:
         raise ValueError("Unsupported PnP type")
     counts = torch.where(res.template_ids >= 0, res.counts, torch.zeros_like(res.counts))
+    if pnp_type == "kabsch_depth":
+        missing = [k for k, v in (("frame_cameras", frame_cameras), ("depth", depth), ("image_index", image_index),
+                                  ("depth_inlier_thresh_mm", depth_inlier_thresh_mm)) if v is None]
+        if missing:
+            raise ValueError(f"pnp_type 'kabsch_depth' needs {', '.join(missing)}")
+        return solve_kabsch_ransac_batch(res.coord_2d, res.coord_3d, counts, cameras, frame_cameras, depth, image_index, depth_inlier_thresh_mm,
+                                         pnp_ransac_iter, pnp_required_ransac_conf, pnp_refine_lm, seed, pair_keys=pair_keys)
     return solve_pnp_ransac_batch(res.coord_2d, res.coord_3d, counts, cameras, pnp_ransac_iter, pnp_inlier_thresh,
                                   pnp_required_ransac_conf, pnp_refine_lm, seed, pair_keys=pair_keys)
 

@@ -204,6 +204,28 @@ int fp_pnp_ransac_keyed(const float* coord_2d, const float* coord_3d, const int3
                         int min_corresp, uint64_t seed, int32_t* out_success, double* out_R, double* out_t, int32_t* out_num_inliers,
                         uint8_t* out_inlier_mask, double* out_ransac_pose, fp_stream_t stream);
 
+/* Coarse pose of every (detection, template slot) pair from its 2D-3D correspondences and the frame's depth image: a rigid 3D-3D RANSAC
+ * on depth-lifted correspondences (this project's own stage, the reference has none).  coord_2d / coord_3d / counts
+ * as in fp_pnp_ransac (counts clamped to [0, k_max]).  Per detection (num_pairs / n_slots of them): solve_cameras [., 4] f64 = (fx, fy, cx,
+ * cy) of the camera the pixels are in, frame_cameras [., 4] of the frame's own camera, A [., 9] f64 the row-major rotation solve camera ->
+ * frame camera (the two share their centre), image_index [.] into depth [num_images, H, W] fp32 mm (0 = no measurement), inlier_thresh_mm
+ * [.] f64 (> 0).  A pixel (u, v) is lifted in fp64: d = ((u - cx) / fx, (v - cy) / fy, 1), d_f = A d, invalid if d_f.z <= 1e-9; the depth
+ * pixel (rint(fx_f d_f.x / d_f.z + cx_f), rint(...)) (half to even), invalid outside the image or where the depth is <= 0 (never read
+ * outside); Y = depth / d_f.z * d, stored as fp32, is the measured point in the SOLVE camera.  num_valid counts the valid ones; fewer than
+ * min_corresp (>= 3) fail the pair.  Hypothesis h: 3 distinct valid indices from fp_pnp_ransac's sampler (seed, pair_keys[pair] or, with
+ * pair_keys null, the pair's index; an invalid or repeated draw is redrawn, at most 64 times per index), rejected unless every edge has
+ * | |X_i - X_j| - |Y_i - Y_j| | <= 2 tau, fitted in closed form from the two triangle frames; its score is the number of valid
+ * correspondences with |R X + t - Y| <= tau.  The first hypothesis with the most (> 2) inliers inside the adaptively shortened budget
+ * (confidence, 3 model points) wins; with refit != 0 the output pose is Horn's closed-form least-squares fit on its inliers, otherwise the
+ * hypothesis itself.  Outputs as fp_pnp_ransac's (model -> solve camera) plus out_num_valid [num_pairs]; out_success is 1, 0, or -1 for a
+ * detection whose image_index is outside [0, num_images) or whose threshold is not positive (nothing of the stack is read for it).
+ * k_max <= 4096, ransac_iters <= 4096.  Every sum has a fixed order: a pair's result depends on (seed, its key, its own data) only. */
+int fp_kabsch_ransac(const float* coord_2d, const float* coord_3d, const int32_t* counts, const double* solve_cameras, const double* frame_cameras,
+                     const double* A, const int32_t* image_index, const double* inlier_thresh_mm, const float* depth, int num_images, int H, int W,
+                     const uint64_t* pair_keys, int num_pairs, int n_slots, int k_max, int ransac_iters, double confidence, int refit,
+                     int min_corresp, uint64_t seed, int32_t* out_success, double* out_R, double* out_t, int32_t* out_num_inliers,
+                     int32_t* out_num_valid, uint8_t* out_inlier_mask, double* out_ransac_pose, fp_stream_t stream);
+
 /* sample_feature_map_at_points (utils/feature_util.py:100-131): bilinear grid_sample, zeros padding,
  * align_corners=False.  fmap addressed by element strides (image, channel, y, x); point_img (may be null)
  * maps each point to its image.  out [num_points, C]. */
