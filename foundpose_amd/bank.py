@@ -13,8 +13,9 @@ retrieved template (utils/corresp_util.py:110-113). Here the bank of ALL objects
 """
 
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import ops
@@ -41,6 +42,39 @@ class ObjectEntry:
             wn = ops.normalize_rows(self.words, 0.0)
             self._unit = (wn, ops.sqnorm_rows(wn))
         return self._unit
+
+
+class VerifyPoints(NamedTuple):
+    """DeviceBank.verify_points: the objects' compact samples."""
+    points: torch.Tensor              # [M_total, 3] f32 on the device
+    ranges: List[Tuple[int, int]]     # per object [begin, end) in points
+    centers: np.ndarray               # [objects, 3] f64
+    radii: np.ndarray                 # [objects] f64
+
+
+def sample_verify_points(vertices: torch.Tensor, row_ranges: Sequence[Tuple[int, int]], max_points: int):
+    """Rows begin, begin + s, ... (s = ceil(rows / max_points)) of every [begin, end) of `vertices`, concatenated.
+    -> (points [M_total, 3] f32, the new [begin, end) of each range)."""
+    parts, ranges, at = [], [], 0
+    for begin, end in row_ranges:
+        rows = end - begin
+        step = max(1, -(-rows // max_points))
+        part = vertices[begin:end:step].to(torch.float32)
+        parts.append(part)
+        ranges.append((at, at + int(part.shape[0])))
+        at += int(part.shape[0])
+    return (torch.cat(parts, 0) if parts else torch.zeros(0, 3)).contiguous(), ranges
+
+
+def sample_spheres(points: torch.Tensor, ranges: Sequence[Tuple[int, int]]):
+    """Per range: the midpoint of the bounding box of its points and the largest distance of a point from it, fp64 (an empty range: 0, 0)."""
+    P = points.cpu().numpy().astype(np.float64)
+    centers, radii = np.zeros((len(ranges), 3)), np.zeros(len(ranges))
+    for i, (b, e) in enumerate(ranges):
+        if e > b:
+            centers[i] = (P[b:e].min(0) + P[b:e].max(0)) / 2.0
+            radii[i] = np.sqrt(((P[b:e] - centers[i]) ** 2).sum(1).max())
+    return centers, radii
 
 
 class DeviceBank:
@@ -94,6 +128,7 @@ class DeviceBank:
         self.obj_tpl_off = torch.tensor([o.tpl_base for o in self.objects] + [tpl_base], dtype=torch.int32, device=dev)
         self.num_templates_total = tpl_base
         self.max_templates = max(o.num_templates for o in self.objects)
+        self._verify_points: Dict[int, VerifyPoints] = {}   # by max_points (verify_points())
 
     def descs_f16(self) -> torch.Tensor:
         """fp16 image (round to nearest even) of `descs_n` for the candidate pass of the two-stage retrieval
@@ -109,6 +144,21 @@ class DeviceBank:
         w = self.num_words
         w_ok = w % 1024 == 0 and (w <= 2048 if tie_mode == 1 else w <= 4096)
         return w_ok and self.max_templates * ((max_det_per_obj + 31) // 32) >= 30000
+
+    def verify_points(self, max_points: int) -> "VerifyPoints":
+        """The compact point samples hypothesis verification places at a pose (pnp_util.verify_poses_depth): of every
+        object the rows begin, begin + s, begin + 2 s, ... of its range of `vertices`, s = ceil(rows / max_points), all in one contiguous
+        tensor; the centre of each sample (the midpoint of its bounding box) and its radius about that centre in fp64.  Built on the host
+        once per max_points and kept."""
+        max_points = int(max_points)
+        if max_points < 1:
+            raise ValueError(f"max_points must be >= 1, got {max_points}")
+        if max_points not in self._verify_points:
+            host = self.vertices.cpu()
+            pts, ranges = sample_verify_points(host, [(o.feat_base, o.feat_base + o.num_feats) for o in self.objects], max_points)
+            centers, radii = sample_spheres(pts, ranges)
+            self._verify_points[max_points] = VerifyPoints(pts.to(self.device).contiguous(), ranges, centers, radii)
+        return self._verify_points[max_points]
 
     @property
     def num_objects(self) -> int:

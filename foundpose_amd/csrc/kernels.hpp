@@ -412,3 +412,26 @@ struct KabschArgs {
   double* ransac_pose;     // [pairs, 12] the winning hypothesis before the refit (R | t), may be null
 };
 int launch_kabsch_ransac(const KabschArgs& a, int num_pairs, hipStream_t st);
+
+// ---------------------------------------------------------------- verify.hip
+struct VerifyArgs {
+  const int* success;      // [pairs] > 0: the pair has a pose
+  const double* R;         // [pairs, 9] row-major model -> solve camera
+  const double* t;         // [pairs, 3]
+  const double* cam;       // [dets, 4] fx, fy, cx, cy of each detection's frame camera (dets = pairs / n_slots)
+  const double* A;         // [dets, 9] row-major rotation solve camera -> frame camera
+  const int* image_index;  // [dets] the detection's image in `depth`
+  const double* tau;       // [dets] tolerance (mm)
+  const int* ranges;       // [dets, 2] the detection's object in `points`: [begin, end), clamped to [0, m_total]
+  const double* center;    // [dets, 3] centre of the object's sample
+  const double* radius;    // [dets] its radius about that centre
+  const float* points;     // [m_total, 3] the compact samples of all objects
+  int m_total;
+  const float* depth;      // [num_images, H, W] mm, 0 = no measurement
+  int num_images, H, W;
+  int n_slots, grid, min_visible;
+  int* counts;             // [pairs, 6] n_vis, n_in, n_occ, n_free, n_hole, n_out
+  double* score;           // [pairs] n_in / n_vis, 0 below min_visible
+  int* status;             // [pairs] 0 scored, 1 too few visible points, 2 skipped, -1 bad image index / tolerance (nothing read)
+};
+int launch_pose_verify_depth(const VerifyArgs& a, int num_pairs, hipStream_t st);

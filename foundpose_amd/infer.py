@@ -64,12 +64,17 @@ class InferOpts(NamedTuple):
     depth_refine_max_dist: float = 0.0   # ... its truncation distance tau in mm; 0: a tenth of the diagonal of the bounding box of repre.vertices
     depth_refine_weight: float = 1.0     # final_pose_type="featuremetric_depth_joint": w_d of E_f + w_d E_d (refine_iters iterations)
     depth_pnp_inlier_thresh: float = 0.0   # pnp_type="kabsch_depth": the 3D inlier threshold in mm; 0: 0.05 x the diagonal of the bounding box of repre.vertices
+    coarse_select_type: str = "inliers"    # which coarse hypothesis goes on: "inliers" (the most correspondence inliers) or "depth_verify" (every hypothesis checked against the frame's depth)
+    depth_verify_thresh: float = 0.0       # coarse_select_type="depth_verify": the tolerance tau in mm; 0: 0.02 x the diagonal of the bounding box of repre.vertices
+    depth_verify_max_points: int = 16384   # ... and the number of model points placed at each hypothesis, at most
 
 
 FINAL_POSE_TYPES = ("best_coarse", "featuremetric", "depth", "featuremetric_depth")
 JOINT_POSE_TYPES = ("featuremetric_depth_joint",)   # features and depth in one objective (refine_util.refine_best_coarse_rgbd); a final pose type too
 DEPTH_POSE_TYPES = ("depth", "featuremetric_depth") + JOINT_POSE_TYPES   # the final pose is refined against the frame's "depth"
 DEPTH_PNP_TYPES = ("kabsch_depth",)   # the coarse poses are solved on the frame's "depth" (pnp_util.solve_kabsch_ransac_batch)
+COARSE_SELECT_TYPES = ("inliers", "depth_verify")
+DEPTH_SELECT_TYPES = ("depth_verify",)   # the coarse hypotheses are checked against the frame's "depth" (pnp_util.verify_poses_depth)
 
 
 def load_opts(path_or_dict) -> InferOpts:
@@ -98,6 +103,14 @@ def _check_driver_opts(opts: InferOpts):
             or not 0 <= opts.depth_pnp_inlier_thresh < float("inf"):
         raise ValueError(f"depth_pnp_inlier_thresh must be a finite number >= 0 (mm; 0: a twentieth of the model's bounding-box diagonal), "
                          f"got {opts.depth_pnp_inlier_thresh!r}")
+    if opts.coarse_select_type not in COARSE_SELECT_TYPES:
+        raise ValueError(f"Unknown coarse select type '{opts.coarse_select_type}' (one of {', '.join(COARSE_SELECT_TYPES)})")
+    if isinstance(opts.depth_verify_thresh, bool) or not isinstance(opts.depth_verify_thresh, (int, float)) \
+            or not 0 <= opts.depth_verify_thresh < float("inf"):
+        raise ValueError(f"depth_verify_thresh must be a finite number >= 0 (mm; 0: a fiftieth of the model's bounding-box diagonal), "
+                         f"got {opts.depth_verify_thresh!r}")
+    if isinstance(opts.depth_verify_max_points, bool) or not isinstance(opts.depth_verify_max_points, int) or opts.depth_verify_max_points < 1:
+        raise ValueError(f"depth_verify_max_points must be an integer >= 1, got {opts.depth_verify_max_points!r}")
     # the best coarse pose refined on the projected feature map (refine_util): the engine keeps the map
     refine = opts.final_pose_type in ("featuremetric", "featuremetric_depth") + JOINT_POSE_TYPES
     if refine and (not isinstance(opts.refine_iters, int) or opts.refine_iters < 0):
@@ -193,8 +206,16 @@ def depth_pnp_tau(opts: InferOpts, repre) -> float:
     return 0.05 * float(np.linalg.norm(v.max(0) - v.min(0)))
 
 
+def depth_verify_tau(opts: InferOpts, repre) -> float:
+    """The tolerance of coarse_select_type "depth_verify" for one object (mm), computed once per object on the host."""
+    if opts.depth_verify_thresh > 0:
+        return float(opts.depth_verify_thresh)
+    v = repre.vertices.detach().cpu().numpy().astype(np.float64)
+    return 0.02 * float(np.linalg.norm(v.max(0) - v.min(0)))
+
+
 def _check_frame_depth(frame: Dict[str, Any], why: str = "the final pose type refines against depth") -> None:
-    """A frame that has work under a depth pose type or a depth PnP type must carry "depth" of the camera's size: refused by name otherwise."""
+    """A frame that has work under a depth pose type, a depth PnP type or a depth select type must carry "depth" of the camera's size: refused by name otherwise."""
     cam, d = frame["camera"], frame.get("depth")
     where = f"scene {frame['scene_id']} image {frame['im_id']}"
     if d is None:
@@ -206,6 +227,8 @@ def _check_frame_depth(frame: Dict[str, Any], why: str = "the final pose type re
 def _depth_reason(opts: InferOpts) -> str:
     if opts.pnp_type in DEPTH_PNP_TYPES:
         return f"pnp_type '{opts.pnp_type}' solves the coarse poses on depth"
+    if opts.coarse_select_type in DEPTH_SELECT_TYPES:
+        return f"coarse_select_type '{opts.coarse_select_type}' checks the coarse poses against depth"
     return "the final pose type refines against depth"
 
 
@@ -290,7 +313,8 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
                  frame_poses: Optional[Dict[Tuple[int, int], List[Tuple[int, np.ndarray]]]] = None) -> eval_util.PoseEvaluator:
     """One object over a stream of frames (the body of infer.py's per-object loop).  A frame is
     {"scene_id", "im_id", "image": HWC uint8 or float [0,1] (numpy or tensor), "camera": PinholePlaneCameraModel (c2w)} and, for the
-    final pose types "depth" / "featuremetric_depth", "depth": float32 mm [H, W] (numpy or tensor, 0 = no measurement).
+    depth-reading options (the final pose types of DEPTH_POSE_TYPES, pnp_type "kabsch_depth", coarse_select_type "depth_verify"), "depth":
+    float32 mm [H, W] (numpy or tensor, 0 = no measurement).
     eval_model (eval_util.load_eval_model): instances whose annotation carries a ground-truth `pose` (model -> world) are
     evaluated against it (PoseEvaluator.update_batch, one launch per frame, inlier radius opts.pnp_inlier_thresh as in
     infer.py:831); without it, or for annotations without a pose, the driver records what it always has.
@@ -306,6 +330,7 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
     refine, check_max_queries = _check_driver_opts(opts)
     use_depth = opts.final_pose_type in DEPTH_POSE_TYPES
     depth_pnp = opts.pnp_type in DEPTH_PNP_TYPES
+    verify = opts.coarse_select_type in DEPTH_SELECT_TYPES
     if extractor is None:  # infer.py:125-128; the checkpoint: weights=, $FOUNDPOSE_DINOV2_WEIGHTS or the torch hub cache, else this raises
         extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
     bank = DeviceBank([repre])
@@ -316,13 +341,14 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
     vis_templates = repre.templates.cuda() if vis else None
     tau = depth_refine_tau(opts, repre) if use_depth else None
     pnp_tau = depth_pnp_tau(opts, repre) if depth_pnp else None
+    verify_tau = depth_verify_tau(opts, repre) if verify else None
 
     for frame in frames:
         scene_id, im_id, cam = frame["scene_id"], frame["im_id"], frame["camera"]
         kept = select_instances(opts, object_lid, frame, detections, num_target_insts, eval_model, evaluator.detection_times)
         if not kept:
             continue
-        if use_depth or depth_pnp:
+        if use_depth or depth_pnp or verify:
             _check_frame_depth(frame, _depth_reason(opts))
         t0 = time.perf_counter()
         img = _to_device_image(frame["image"])
@@ -354,9 +380,15 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
         else:
             poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
                                             opts.pnp_refine_lm, seed=seed)
+        checked = None
+        if verify:   # every hypothesis against the frame's depth (the stack of kabsch_depth when that built one); part of pose_coarse
+            if depth is None:
+                depth = _frame_depth(frame, _depth_reason(opts))
+            checked = pnp_util.verify_poses_depth(poses, bank, [0] * len(kept), cams, [cam] * len(kept), depth[None], [0] * len(kept), verify_tau,
+                                                  max_points=opts.depth_verify_max_points)
         torch.cuda.synchronize()
         t3 = time.perf_counter()
-        best = pnp_util.select_best_coarse(poses)
+        best = pnp_util.select_best_coarse(poses) if checked is None else pnp_util.select_best_verified(poses, checked)
         found, cid = best["found"].cpu().tolist(), best["corresp_id"].cpu().tolist()
         Rb, tb = best["R"].cpu().numpy(), best["t"].cpu().numpy()
         t4 = time.perf_counter()
@@ -514,6 +546,7 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
     refine, check_max_queries = _check_driver_opts(opts)
     use_depth = opts.final_pose_type in DEPTH_POSE_TYPES
     depth_pnp = opts.pnp_type in DEPTH_PNP_TYPES
+    verify = opts.coarse_select_type in DEPTH_SELECT_TYPES
     lids = sorted(opts.object_lids) if opts.object_lids is not None else sorted(repres)
     if extractor is None:
         extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
@@ -525,6 +558,7 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
     models = [None if eval_models is None else eval_models.get(l) for l in lids]
     taus = [depth_refine_tau(opts, repres[l]) for l in lids] if use_depth else None
     pnp_taus = [depth_pnp_tau(opts, repres[l]) for l in lids] if depth_pnp else None
+    verify_taus = [depth_verify_tau(opts, repres[l]) for l in lids] if verify else None
 
     def entries():
         for frame_no, frame in enumerate(frames):
@@ -532,7 +566,7 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
             for o, lid in enumerate(lids):
                 kept = select_instances(opts, lid, frame, detections, None if num_target_insts is None else num_target_insts.get(lid, {}),
                                         models[o], evaluators[o].detection_times)
-                if kept and (use_depth or depth_pnp):
+                if kept and (use_depth or depth_pnp or verify):
                     _check_frame_depth(frame, _depth_reason(opts))
                 if kept and not opts.crop and not checked:   # (as in infer_object: only a frame that has work is checked)
                     h, w = frame["image"].shape[:2]
@@ -579,9 +613,15 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
         else:
             poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
                                             opts.pnp_refine_lm, seed=seed, pair_keys=keys)
+        checked = None
+        if verify:   # every hypothesis against its frame's depth (the stack of kabsch_depth when that built one); part of pose_coarse
+            if depth is None:
+                depth = torch.stack([_frame_depth(by_no[f], _depth_reason(opts)) for f in plan.frames])
+            checked = pnp_util.verify_poses_depth(poses, bank, plan.det_obj, cams, src_cams, depth, plan.image_index,
+                                                  [verify_taus[o] for o in plan.det_obj], max_points=opts.depth_verify_max_points)
         torch.cuda.synchronize()
         t3 = time.perf_counter()
-        best = pnp_util.select_best_coarse(poses)
+        best = pnp_util.select_best_coarse(poses) if checked is None else pnp_util.select_best_verified(poses, checked)
         found, cid = best["found"].cpu().tolist(), best["corresp_id"].cpu().tolist()
         Rb, tb = best["R"].cpu().numpy(), best["t"].cpu().numpy()
         t4 = time.perf_counter()
@@ -729,7 +769,8 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     if args.batch_detections >= 1 and args.vis:
         ap.error("--vis needs the per-object driver: drop --batch-detections (or pass 0)")
     opts = load_opts(args.opts)
-    with_depth = opts.final_pose_type in DEPTH_POSE_TYPES or opts.pnp_type in DEPTH_PNP_TYPES   # the depth pose / PnP types read depth/<im>.png beside every image
+    with_depth = (opts.final_pose_type in DEPTH_POSE_TYPES or opts.pnp_type in DEPTH_PNP_TYPES
+                  or opts.coarse_select_type in DEPTH_SELECT_TYPES)   # the depth pose / PnP / select types read depth/<im>.png beside every image
     # the checkpoint is resolved before anything else is read: a missing one must fail in seconds, not after the banks are loaded
     extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=args.precision, weights=args.weights)
     with open(args.targets or os.path.join(os.path.dirname(os.path.abspath(args.dataset_dir)), "test_targets_bop19.json")) as f:

@@ -98,11 +98,11 @@ def _pair_keys_tensor(pair_keys, B: int, n: int, dev):
     return pair_keys.contiguous() if pair_keys.is_cuda else upload_async(pair_keys, dev)   # (the int64 bits are the uint64 keys)
 
 
-def solve_to_frame_rotations(solve_cameras: Sequence[Any], frame_cameras: Sequence[Any]) -> np.ndarray:
+def solve_to_frame_rotations(solve_cameras: Sequence[Any], frame_cameras: Sequence[Any], what: str = "kabsch_depth") -> np.ndarray:
     """A [B, 3, 3] fp64: the rotation solve camera -> frame camera of every detection, from rel = inv(frame.T_world_from_eye) @
     solve.T_world_from_eye.  The crop camera looks at its box from the frame camera's own position, so rel has no translation; one whose
     translation exceeds 1e-6 (1 + |eye position|) is refused (a depth pixel then could not be found from a ray alone).  The same camera
-    object on both sides (crop=False) gives the identity."""
+    object on both sides (crop=False) gives the identity.  what: the stage the refusal names."""
     A = np.empty((len(solve_cameras), 3, 3), np.float64)
     for i, (s, f) in enumerate(zip(solve_cameras, frame_cameras)):
         if s is f:
@@ -113,7 +113,7 @@ def solve_to_frame_rotations(solve_cameras: Sequence[Any], frame_cameras: Sequen
         off, bound = float(np.linalg.norm(rel[:3, 3])), 1e-6 * (1.0 + float(np.linalg.norm(Tf[:3, 3])))
         if not off <= bound:
             raise ValueError(f"detection {i}: the solve camera's centre is {off:.3g} away from the frame camera's (more than {bound:.3g}): "
-                             "kabsch_depth needs cameras that share their centre")
+                             f"{what} needs cameras that share their centre")
         A[i] = rel[:3, :3]
     return A
 
@@ -210,6 +210,99 @@ def select_best_coarse(poses: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor
     return {"found": best_q >= 0, "corresp_id": first,
             "R": poses["R"].gather(1, idx[..., None].expand(-1, 1, 3, 3))[:, 0], "t": poses["t"].gather(1, idx.expand(-1, 1, 3))[:, 0],
             "quality": best_q}
+
+
+VERIFY_MIN_GRID, VERIFY_MAX_GRID = 8, 128   # the z-buffer's side in cells (csrc/verify.hip: G * G words of LDS)
+
+
+def verify_poses_depth(poses: Dict[str, torch.Tensor], bank, det_obj: Sequence[int], solve_cameras: Sequence[Any], frame_cameras: Sequence[Any],
+                       depth: torch.Tensor, image_index, thresh_mm, max_points: int = 16384, grid: int = 64,
+                       min_visible: int = 16) -> Dict[str, torch.Tensor]:
+    """Every coarse pose of a batch checked against the frame's depth (csrc/verify.hip): the point sample of the
+    whole model (bank.verify_points(max_points)) placed at the pose, its self-occlusion decided by a grid x grid z-buffer, each visible point
+    counted as confirmed by the depth image, occluded, in free space, on a hole or outside the image.
+    poses: estimate_poses' dict (success [B, n], R [B, n, 3, 3], t [B, n, 3], model -> solve camera); det_obj: the object of each detection
+    in `bank`; solve_cameras / frame_cameras / depth [N, H, W] fp32 mm / image_index: as in solve_kabsch_ransac_batch; thresh_mm: one
+    number or one per detection (> 0).
+    -> counts [B, n, 6] int32 = (n_vis, n_in, n_occ, n_free, n_hole, n_out), score [B, n] f64 = n_in / n_vis (0 below min_visible visible
+    points), status [B, n] int32 (0 scored, 1 too few visible points, 2 skipped: no pose, no points, or the model's sphere reaches the
+    camera).  B = 0 or n = 0 returns empty tensors without a launch.  A bad image index, threshold, camera pair or grid raises ValueError before anything is launched."""
+    success, R, t = poses["success"], poses["R"], poses["t"]
+    require_cuda(success, R, t, depth)
+    B, n = (int(s) for s in success.shape)
+    dev = success.device
+    if len(solve_cameras) != B or len(frame_cameras) != B or len(det_obj) != B:
+        raise ValueError(f"{len(solve_cameras)} solve cameras, {len(frame_cameras)} frame cameras and {len(det_obj)} objects for {B} detections")
+    if depth.dim() != 3 or depth.dtype != torch.float32:
+        raise ValueError(f"depth must be a float32 stack [N, H, W], got {depth.dtype} {list(depth.shape)}")
+    if isinstance(grid, bool) or not isinstance(grid, int) or not VERIFY_MIN_GRID <= grid <= VERIFY_MAX_GRID:
+        raise ValueError(f"grid must be an integer in [{VERIFY_MIN_GRID}, {VERIFY_MAX_GRID}], got {grid!r}")
+    if isinstance(min_visible, bool) or not isinstance(min_visible, int) or min_visible < 1:
+        raise ValueError(f"min_visible must be an integer >= 1, got {min_visible!r}")
+    N, H, W = (int(s) for s in depth.shape)
+    if isinstance(image_index, torch.Tensor):
+        image_index = image_index.cpu().tolist()
+    ii = [int(i) for i in image_index]
+    if len(ii) != B:
+        raise ValueError(f"{len(ii)} image indices for {B} detections")
+    for b, i in enumerate(ii):
+        if not 0 <= i < N:
+            raise ValueError(f"detection {b}: image index {i} outside [0, {N})")
+    tau = np.full(B, thresh_mm, np.float64) if np.ndim(thresh_mm) == 0 else np.array(thresh_mm, np.float64).reshape(-1)
+    if tau.shape != (B,) or not np.all(tau > 0) or not np.all(np.isfinite(tau)):
+        raise ValueError(f"thresh_mm must be one finite number > 0 or {B} of them, got {thresh_mm!r}")
+    vp = bank.verify_points(max_points)
+    objs = [int(o) for o in det_obj]
+    for b, o in enumerate(objs):
+        if not 0 <= o < len(vp.ranges):
+            raise ValueError(f"detection {b}: object {o} outside the bank's [0, {len(vp.ranges)})")
+    A = solve_to_frame_rotations(solve_cameras, frame_cameras, "depth verification")
+    P = B * n
+    counts = torch.zeros(P, 6, dtype=torch.int32, device=dev)
+    score = torch.zeros(P, dtype=torch.float64, device=dev)
+    status = torch.zeros(P, dtype=torch.int32, device=dev)
+    if P == 0:   # nothing to launch
+        return {"counts": counts.reshape(B, n, 6), "score": score.reshape(B, n), "status": status.reshape(B, n)}
+    # one byte buffer, one upload: the fp64 table [B, 18] followed by the int32 table [B, 3] (image, begin, end), each read back as its own type
+    reals = torch.cat([torch.tensor([_intrinsics(c) for c in frame_cameras], dtype=torch.float64).reshape(B, 4), torch.from_numpy(A.reshape(B, 9)),
+                       torch.from_numpy(tau).reshape(B, 1), torch.from_numpy(vp.centers[objs].reshape(B, 3)),
+                       torch.from_numpy(vp.radii[objs].reshape(B, 1))], dim=1).contiguous()
+    ints = torch.tensor([[i, *vp.ranges[o]] for i, o in zip(ii, objs)], dtype=torch.int32).reshape(B, 3)
+    raw = upload_async(torch.cat([reals.view(torch.uint8).reshape(-1), ints.view(torch.uint8).reshape(-1)]), dev)
+    table = raw[:B * 18 * 8].view(torch.float64).reshape(B, 18)   # (the int32 part starts at a multiple of 8 bytes)
+    idev = raw[B * 18 * 8:].view(torch.int32).reshape(B, 3)
+    cam, Ad, taud = table[:, :4].contiguous(), table[:, 4:13].contiguous(), table[:, 13].contiguous()
+    cen, rad = table[:, 14:17].contiguous(), table[:, 17].contiguous()
+    iid, rng = idev[:, 0].contiguous(), idev[:, 1:3].contiguous()
+    ok = success.to(torch.int32).contiguous()
+    Rd, td = R.to(torch.float64).contiguous(), t.to(torch.float64).contiguous()
+    dimg = depth.contiguous()
+    call("fp_pose_verify_depth", ptr(ok), ptr(Rd), ptr(td), ptr(cam), ptr(Ad), ptr(iid), ptr(taud), ptr(rng), ptr(cen), ptr(rad), ptr(vp.points),
+         int(vp.points.shape[0]), ptr(dimg), N, H, W, P, n, grid, min_visible, ptr(counts), ptr(score), ptr(status), stream())
+    return {"counts": counts.reshape(B, n, 6), "score": score.reshape(B, n), "status": status.reshape(B, n)}
+
+
+def select_best_verified(poses: Dict[str, torch.Tensor], verify: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """select_best_coarse with the hypotheses ranked by verify_poses_depth's result: among a detection's successful coarse poses the scored
+    ones (status 0) before the others, then the higher score, then the higher coarse quality, then the first slot.
+    -> select_best_coarse's dict (quality: the chosen hypothesis's coarse quality, -1 where nothing was found) + verify_score [B]."""
+    ok, quality = poses["success"], poses["quality"]
+    n = ok.shape[1]
+    scored = ok & (verify["status"] == 0)
+    cand = torch.where(scored.any(dim=1, keepdim=True), scored, ok)
+    neg = torch.full_like(quality, -float("inf"))
+    for key in (torch.where(scored, verify["score"].to(quality.dtype), torch.zeros_like(quality)), quality):
+        k = torch.where(cand, key, neg)
+        cand = cand & (k == k.max(dim=1, keepdim=True).values)
+    first = torch.where(cand, torch.arange(n, device=ok.device)[None, :], torch.full_like(cand, n, dtype=torch.int64)).min(dim=1).values
+    found = first < n
+    first = first.clamp_max(n - 1)
+    idx = first[:, None, None]
+    pick = lambda v: v.gather(1, first[:, None])[:, 0]
+    return {"found": found, "corresp_id": first,
+            "R": poses["R"].gather(1, idx[..., None].expand(-1, 1, 3, 3))[:, 0], "t": poses["t"].gather(1, idx.expand(-1, 1, 3))[:, 0],
+            "quality": torch.where(found, pick(quality), torch.full_like(pick(quality), -1.0)),
+            "verify_score": torch.where(found, pick(verify["score"]), torch.zeros_like(pick(verify["score"])))}
 
 
 def estimate_pose(corresp: Dict[str, Any], camera_c2w: Any, pnp_type: str, pnp_ransac_iter: int, pnp_inlier_thresh: float,

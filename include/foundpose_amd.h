@@ -226,6 +226,31 @@ int fp_kabsch_ransac(const float* coord_2d, const float* coord_3d, const int32_t
                      int min_corresp, uint64_t seed, int32_t* out_success, double* out_R, double* out_t, int32_t* out_num_inliers,
                      int32_t* out_num_valid, uint8_t* out_inlier_mask, double* out_ransac_pose, fp_stream_t stream);
 
+/* Hypothesis verification against depth (this project's own stage): the point sample of the whole model placed at
+ * the pose of every (detection, template slot) pair, its self-occlusion decided by a G x G z-buffer of the sample, each visible point
+ * classified against the frame's depth image.  Per pair: success [num_pairs] (> 0: the pair has a pose), R [., 9] / t [., 3] f64 row-major
+ * model -> solve camera (fp_pnp_ransac's / fp_kabsch_ransac's outputs).  Per detection (num_pairs / n_slots of them): frame_cameras [., 4]
+ * f64 = (fx, fy, cx, cy), A [., 9] f64 the rotation solve camera -> frame camera, image_index [.] into depth [num_images, H, W] fp32 mm
+ * (0 = no measurement), thresh_mm [.] f64 (tau), point_ranges [., 2] = [begin, end) of the detection's object in points [num_points, 3]
+ * fp32 (clamped to [0, num_points]), centers [., 3] / radii [.] f64: the sample's centre c and its radius rho about c.  All arithmetic is
+ * fp64, every step one rounded operation in this order (no FMA contraction), sums of products with k ascending:
+ *   R_f = A R, t_f = A t;  C = R_f c + t_f; status 2 unless C.z > rho + 1;  u_c = fx C.x / C.z + cx, v_c alike;
+ *   r_px = max(fx, fy) rho / (C.z - rho), cell side h = 2 r_px / G; a pixel (u, v) lies in cell
+ *   (clamp(floor((u - (u_c - r_px)) / h), 0, G - 1), clamp(floor((v - (v_c - r_px)) / h), 0, G - 1)) (the clamp is part of the contract);
+ *   pass 1: X_c = R_f X + t_f, ignored when X_c.z <= 1; u = fx x / z + cx, v alike; zbuf[cell] = min(zbuf[cell], (float)z), cells start at +inf;
+ *   pass 2: a point with z > 1 is visible iff z <= (double)zbuf[cell] + tau; a visible point adds 1 to n_vis and to exactly one of
+ *     n_out (px = rint(u), py = rint(v), half to even, outside [0, W-1] x [0, H-1]: never read), n_hole (D[py, px] <= 0), and with
+ *     r = D - z: n_in (|r| <= tau), n_occ (r < -tau), n_free (r > tau).
+ * out_counts [num_pairs, 6] = (n_vis, n_in, n_occ, n_free, n_hole, n_out); out_score [num_pairs] f64 = n_in / n_vis when n_vis >=
+ * min_visible (>= 1), else 0; out_status [num_pairs]: 0 scored, 1 fewer than min_visible visible points, 2 skipped (success <= 0, an empty
+ * point range, or C.z <= rho + 1; counts and score 0), -1 for a detection whose image_index is outside [0, num_images) or whose tau is not
+ * positive and finite (nothing of the stack is read for it; counts and score 0).  grid G in [8, 128].  A pair's result depends on its own
+ * data only: it is the same bits alone, in any batch and at any position. */
+int fp_pose_verify_depth(const int32_t* success, const double* R, const double* t, const double* frame_cameras, const double* A,
+                         const int32_t* image_index, const double* thresh_mm, const int32_t* point_ranges, const double* centers, const double* radii,
+                         const float* points, int num_points, const float* depth, int num_images, int H, int W, int num_pairs, int n_slots, int grid,
+                         int min_visible, int32_t* out_counts, double* out_score, int32_t* out_status, fp_stream_t stream);
+
 /* sample_feature_map_at_points (utils/feature_util.py:100-131): bilinear grid_sample, zeros padding,
  * align_corners=False.  fmap addressed by element strides (image, channel, y, x); point_img (may be null)
  * maps each point to its image.  out [num_points, C]. */
