@@ -299,6 +299,23 @@ int fp_pose_verify_depth(const int32_t* success, const double* R, const double* 
   return launch_pose_verify_depth(a, num_pairs, ST(stream));
 }
 
+int fp_pose_verify_mask(const int32_t* success, const double* R, const double* t, const double* frame_cameras, const double* A,
+                        const int32_t* point_ranges, const double* centers, const double* radii, const float* points, int num_points,
+                        const uint8_t* masks, const int32_t* mask_areas, int H, int W, int num_pairs, int n_slots, int grid, int min_pixels,
+                        int32_t* out_counts, double* out_score, int32_t* out_status, fp_stream_t stream) {
+  FP_REQUIRE(success && R && t && frame_cameras && A && point_ranges && centers && radii && masks && mask_areas && out_counts && out_score &&
+             out_status, "fp_pose_verify_mask: null pointer");
+  FP_REQUIRE(points || num_points == 0, "fp_pose_verify_mask: null points");
+  FP_REQUIRE(num_pairs >= 0 && n_slots >= 1 && num_pairs % n_slots == 0, "fp_pose_verify_mask: num_pairs must be a multiple of n_slots");
+  MaskVerifyArgs a;
+  memset(&a, 0, sizeof(a));
+  a.success = success; a.R = R; a.t = t; a.cam = frame_cameras; a.A = A;
+  a.ranges = point_ranges; a.center = centers; a.radius = radii; a.points = points; a.m_total = num_points;
+  a.masks = masks; a.area = mask_areas; a.H = H; a.W = W; a.n_slots = n_slots; a.grid = grid; a.min_pixels = min_pixels;
+  a.counts = out_counts; a.score = out_score; a.status = out_status;
+  return launch_pose_verify_mask(a, num_pairs, ST(stream));
+}
+
 // ------------------------------------------------------------------ ViT building blocks
 int fp_patchify(const float* images, int B, int H, int W, int patch, void* out, int ld_out, int out_dtype,
                 fp_stream_t stream) {

@@ -435,3 +435,25 @@ struct VerifyArgs {
   int* status;             // [pairs] 0 scored, 1 too few visible points, 2 skipped, -1 bad image index / tolerance (nothing read)
 };
 int launch_pose_verify_depth(const VerifyArgs& a, int num_pairs, hipStream_t st);
+
+// ---------------------------------------------------------------- mask_verify.hip
+struct MaskVerifyArgs {
+  const int* success;      // [pairs] > 0: the pair has a pose
+  const double* R;         // [pairs, 9] row-major model -> solve camera
+  const double* t;         // [pairs, 3]
+  const double* cam;       // [dets, 4] fx, fy, cx, cy of each detection's frame camera (dets = pairs / n_slots)
+  const double* A;         // [dets, 9] row-major rotation solve camera -> frame camera
+  const int* ranges;       // [dets, 2] the detection's object in `points`: [begin, end), clamped to [0, m_total]
+  const double* center;    // [dets, 3] centre of the object's sample
+  const double* radius;    // [dets] its radius about that centre
+  const float* points;     // [m_total, 3] the compact samples of all objects
+  int m_total;
+  const unsigned char* masks;  // [dets, H, W] each detection's mask in the frame camera's image, non-zero = set
+  const int* area;         // [dets] the number of set pixels of the detection's mask
+  int H, W;
+  int n_slots, grid, min_pixels;
+  int* counts;             // [pairs, 4] n_both, n_model_only, n_mask_only, n_cells
+  double* score;           // [pairs] n_both / (n_both + n_model_only + n_mask_only), 0 below min_pixels model pixels
+  int* status;             // [pairs] 0 scored, 1 too few model pixels, 2 skipped
+};
+int launch_pose_verify_mask(const MaskVerifyArgs& a, int num_pairs, hipStream_t st);

@@ -12,41 +12,11 @@
 // stored as fp32.  The outputs are integer counts and one quotient of two of them: a pair's result depends on its own data only.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "verify_grid.hpp"  // FramePose, CellGrid, to_camera, project: shared with mask_verify.hip
 
 namespace {
 
-constexpr int PV_THREADS = 256;
-constexpr int PV_MIN_GRID = 8;
-constexpr int PV_MAX_GRID = 128;
 constexpr int PV_COUNTS = 6;  // n_vis, n_in, n_occ, n_free, n_hole, n_out
-
-struct FramePose {
-  double R[9];
-  double t[3];
-};
-
-struct CellGrid {
-  double fx, fy, cx, cy;
-  double u0, v0, h;  // the square's corner (u_c - r_px, v_c - r_px) and the cell side
-  int G;
-};
-
-// X -> the frame camera: products summed k ascending, then + t
-FP_DEVICE void to_camera(const FramePose& P, const double* X, double* Xc) {
-#pragma clang fp contract(off)
-  for (int i = 0; i < 3; ++i) Xc[i] = ((P.R[i * 3 + 0] * X[0] + P.R[i * 3 + 1] * X[1]) + P.R[i * 3 + 2] * X[2]) + P.t[i];
-}
-
-// a point with z > 1 -> its pixel coordinates and its cell (a NaN coordinate lands in cell 0: fmax / fmin drop it)
-FP_DEVICE int project(const CellGrid& g, const double* Xc, double* u, double* v) {
-#pragma clang fp contract(off)
-  *u = g.fx * Xc[0] / Xc[2] + g.cx;
-  *v = g.fy * Xc[1] / Xc[2] + g.cy;
-  const double top = (double)(g.G - 1);
-  const int ix = (int)fmin(fmax(floor((*u - g.u0) / g.h), 0.0), top);
-  const int iy = (int)fmin(fmax(floor((*v - g.v0) / g.h), 0.0), top);
-  return iy * g.G + ix;
-}
 
 __global__ __launch_bounds__(PV_THREADS) void pose_verify_depth_kernel(VerifyArgs a) {
 #pragma clang fp contract(off)

@@ -64,17 +64,20 @@ class InferOpts(NamedTuple):
     depth_refine_max_dist: float = 0.0   # ... its truncation distance tau in mm; 0: a tenth of the diagonal of the bounding box of repre.vertices
     depth_refine_weight: float = 1.0     # final_pose_type="featuremetric_depth_joint": w_d of E_f + w_d E_d (refine_iters iterations)
     depth_pnp_inlier_thresh: float = 0.0   # pnp_type="kabsch_depth": the 3D inlier threshold in mm; 0: 0.05 x the diagonal of the bounding box of repre.vertices
-    coarse_select_type: str = "inliers"    # which coarse hypothesis goes on: "inliers" (the most correspondence inliers) or "depth_verify" (every hypothesis checked against the frame's depth)
+    coarse_select_type: str = "inliers"    # which coarse hypothesis goes on: "inliers" (the most correspondence inliers), "depth_verify" (every hypothesis checked against the frame's depth) or "mask_verify" (... against the detection's mask, no depth needed; section 18)
     depth_verify_thresh: float = 0.0       # coarse_select_type="depth_verify": the tolerance tau in mm; 0: 0.02 x the diagonal of the bounding box of repre.vertices
     depth_verify_max_points: int = 16384   # ... and the number of model points placed at each hypothesis, at most
+    mask_verify_grid: int = 64             # coarse_select_type="mask_verify": the side G of the silhouette's cell grid, in [8, 128]
+    mask_verify_max_points: int = 16384    # ... and the number of model points placed at each hypothesis, at most
 
 
 FINAL_POSE_TYPES = ("best_coarse", "featuremetric", "depth", "featuremetric_depth")
 JOINT_POSE_TYPES = ("featuremetric_depth_joint",)   # features and depth in one objective (refine_util.refine_best_coarse_rgbd); a final pose type too
 DEPTH_POSE_TYPES = ("depth", "featuremetric_depth") + JOINT_POSE_TYPES   # the final pose is refined against the frame's "depth"
 DEPTH_PNP_TYPES = ("kabsch_depth",)   # the coarse poses are solved on the frame's "depth" (pnp_util.solve_kabsch_ransac_batch)
-COARSE_SELECT_TYPES = ("inliers", "depth_verify")
+COARSE_SELECT_TYPES = ("inliers", "depth_verify", "mask_verify")
 DEPTH_SELECT_TYPES = ("depth_verify",)   # the coarse hypotheses are checked against the frame's "depth" (pnp_util.verify_poses_depth)
+MASK_SELECT_TYPES = ("mask_verify",)     # ... against the detection's own mask (pnp_util.verify_poses_mask): no depth
 
 
 def load_opts(path_or_dict) -> InferOpts:
@@ -111,6 +114,11 @@ def _check_driver_opts(opts: InferOpts):
                          f"got {opts.depth_verify_thresh!r}")
     if isinstance(opts.depth_verify_max_points, bool) or not isinstance(opts.depth_verify_max_points, int) or opts.depth_verify_max_points < 1:
         raise ValueError(f"depth_verify_max_points must be an integer >= 1, got {opts.depth_verify_max_points!r}")
+    if isinstance(opts.mask_verify_grid, bool) or not isinstance(opts.mask_verify_grid, int) \
+            or not pnp_util.VERIFY_MIN_GRID <= opts.mask_verify_grid <= pnp_util.VERIFY_MAX_GRID:
+        raise ValueError(f"mask_verify_grid must be an integer in [{pnp_util.VERIFY_MIN_GRID}, {pnp_util.VERIFY_MAX_GRID}], got {opts.mask_verify_grid!r}")
+    if isinstance(opts.mask_verify_max_points, bool) or not isinstance(opts.mask_verify_max_points, int) or opts.mask_verify_max_points < 1:
+        raise ValueError(f"mask_verify_max_points must be an integer >= 1, got {opts.mask_verify_max_points!r}")
     # the best coarse pose refined on the projected feature map (refine_util): the engine keeps the map
     refine = opts.final_pose_type in ("featuremetric", "featuremetric_depth") + JOINT_POSE_TYPES
     if refine and (not isinstance(opts.refine_iters, int) or opts.refine_iters < 0):
@@ -331,6 +339,7 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
     use_depth = opts.final_pose_type in DEPTH_POSE_TYPES
     depth_pnp = opts.pnp_type in DEPTH_PNP_TYPES
     verify = opts.coarse_select_type in DEPTH_SELECT_TYPES
+    mask_verify = opts.coarse_select_type in MASK_SELECT_TYPES
     if extractor is None:  # infer.py:125-128; the checkpoint: weights=, $FOUNDPOSE_DINOV2_WEIGHTS or the torch hub cache, else this raises
         extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
     bank = DeviceBank([repre])
@@ -386,6 +395,9 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
                 depth = _frame_depth(frame, _depth_reason(opts))
             checked = pnp_util.verify_poses_depth(poses, bank, [0] * len(kept), cams, [cam] * len(kept), depth[None], [0] * len(kept), verify_tau,
                                                   max_points=opts.depth_verify_max_points)
+        elif mask_verify:   # ... or against its detection's mask in the frame's image; part of pose_coarse
+            checked = pnp_util.verify_poses_mask(poses, bank, [0] * len(kept), cams, [cam] * len(kept), masks,
+                                                 max_points=opts.mask_verify_max_points, grid=opts.mask_verify_grid)
         torch.cuda.synchronize()
         t3 = time.perf_counter()
         best = pnp_util.select_best_coarse(poses) if checked is None else pnp_util.select_best_verified(poses, checked)
@@ -547,6 +559,7 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
     use_depth = opts.final_pose_type in DEPTH_POSE_TYPES
     depth_pnp = opts.pnp_type in DEPTH_PNP_TYPES
     verify = opts.coarse_select_type in DEPTH_SELECT_TYPES
+    mask_verify = opts.coarse_select_type in MASK_SELECT_TYPES
     lids = sorted(opts.object_lids) if opts.object_lids is not None else sorted(repres)
     if extractor is None:
         extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
@@ -619,6 +632,9 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
                 depth = torch.stack([_frame_depth(by_no[f], _depth_reason(opts)) for f in plan.frames])
             checked = pnp_util.verify_poses_depth(poses, bank, plan.det_obj, cams, src_cams, depth, plan.image_index,
                                                   [verify_taus[o] for o in plan.det_obj], max_points=opts.depth_verify_max_points)
+        elif mask_verify:   # ... or against its detection's mask in its frame's image; part of pose_coarse
+            checked = pnp_util.verify_poses_mask(poses, bank, plan.det_obj, cams, src_cams, masks,
+                                                 max_points=opts.mask_verify_max_points, grid=opts.mask_verify_grid)
         torch.cuda.synchronize()
         t3 = time.perf_counter()
         best = pnp_util.select_best_coarse(poses) if checked is None else pnp_util.select_best_verified(poses, checked)

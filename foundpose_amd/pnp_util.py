@@ -282,6 +282,65 @@ def verify_poses_depth(poses: Dict[str, torch.Tensor], bank, det_obj: Sequence[i
     return {"counts": counts.reshape(B, n, 6), "score": score.reshape(B, n), "status": status.reshape(B, n)}
 
 
+def verify_poses_mask(poses: Dict[str, torch.Tensor], bank, det_obj: Sequence[int], solve_cameras: Sequence[Any], frame_cameras: Sequence[Any],
+                      masks: torch.Tensor, max_points: int = 16384, grid: int = 64, min_pixels: int = 16) -> Dict[str, torch.Tensor]:
+    """Every coarse pose of a batch checked against its detection's mask (csrc/mask_verify.hip): the point sample of
+    the whole model (bank.verify_points(max_points)) placed at the pose, the cells of a grid x grid square its points project into taken as
+    the model's silhouette, and the silhouette's pixels compared with the mask's.
+    poses / bank / det_obj / solve_cameras / frame_cameras: as in verify_poses_depth; masks: uint8 [B, H, W] on the device, each detection's
+    own mask in its frame camera's image (non-zero = set).
+    -> counts [B, n, 4] int32 = (n_both, n_model_only, n_mask_only, n_cells), score [B, n] f64 = n_both / (n_both + n_model_only +
+    n_mask_only) (0 below min_pixels model pixels), status [B, n] int32 (0 scored, 1 too few model pixels, 2 skipped: no pose, no points,
+    or the model's sphere reaches the camera).  B = 0 or n = 0 returns empty tensors without a launch.  Masks of another type or shape,
+    lengths that do not match, a bad object index, grid, min_pixels or camera pair raise ValueError before anything is launched."""
+    success, R, t = poses["success"], poses["R"], poses["t"]
+    if isinstance(grid, bool) or not isinstance(grid, int) or not VERIFY_MIN_GRID <= grid <= VERIFY_MAX_GRID:
+        raise ValueError(f"grid must be an integer in [{VERIFY_MIN_GRID}, {VERIFY_MAX_GRID}], got {grid!r}")
+    if isinstance(min_pixels, bool) or not isinstance(min_pixels, int) or min_pixels < 1:
+        raise ValueError(f"min_pixels must be an integer >= 1, got {min_pixels!r}")
+    if not isinstance(masks, torch.Tensor) or masks.dtype != torch.uint8 or masks.dim() != 3:
+        raise ValueError(f"masks must be a uint8 tensor [B, H, W] on the device, got "
+                         f"{(masks.dtype, list(masks.shape)) if isinstance(masks, torch.Tensor) else type(masks).__name__}")
+    B, n = (int(s) for s in success.shape)
+    if len(solve_cameras) != B or len(frame_cameras) != B or len(det_obj) != B or int(masks.shape[0]) != B:
+        raise ValueError(f"{len(solve_cameras)} solve cameras, {len(frame_cameras)} frame cameras, {len(det_obj)} objects and {int(masks.shape[0])} masks "
+                         f"for {B} detections")
+    H, W = int(masks.shape[1]), int(masks.shape[2])
+    if B and not 1 <= H * W <= 1 << 30:
+        raise ValueError(f"masks of {W} x {H}: between 1 and 2^30 pixels")
+    if not masks.is_cuda:
+        raise ValueError(f"masks must be a uint8 tensor [B, H, W] on the device, got one on {masks.device}")
+    require_cuda(success, R, t)
+    dev = success.device
+    vp = bank.verify_points(max_points)
+    objs = [int(o) for o in det_obj]
+    for b, o in enumerate(objs):
+        if not 0 <= o < len(vp.ranges):
+            raise ValueError(f"detection {b}: object {o} outside the bank's [0, {len(vp.ranges)})")
+    A = solve_to_frame_rotations(solve_cameras, frame_cameras, "mask verification")
+    P = B * n
+    counts = torch.zeros(P, 4, dtype=torch.int32, device=dev)
+    score = torch.zeros(P, dtype=torch.float64, device=dev)
+    status = torch.zeros(P, dtype=torch.int32, device=dev)
+    if P == 0:   # nothing to launch
+        return {"counts": counts.reshape(B, n, 4), "score": score.reshape(B, n), "status": status.reshape(B, n)}
+    # one byte buffer, one upload: the fp64 table [B, 17] followed by the int32 table [B, 2] (begin, end), each read back as its own type
+    reals = torch.cat([torch.tensor([_intrinsics(c) for c in frame_cameras], dtype=torch.float64).reshape(B, 4), torch.from_numpy(A.reshape(B, 9)),
+                       torch.from_numpy(vp.centers[objs].reshape(B, 3)), torch.from_numpy(vp.radii[objs].reshape(B, 1))], dim=1).contiguous()
+    ints = torch.tensor([vp.ranges[o] for o in objs], dtype=torch.int32).reshape(B, 2)
+    raw = upload_async(torch.cat([reals.view(torch.uint8).reshape(-1), ints.view(torch.uint8).reshape(-1)]), dev)
+    table = raw[:B * 17 * 8].view(torch.float64).reshape(B, 17)   # (the int32 part starts at a multiple of 8 bytes)
+    rng = raw[B * 17 * 8:].view(torch.int32).reshape(B, 2)
+    cam, Ad, cen, rad = table[:, :4].contiguous(), table[:, 4:13].contiguous(), table[:, 13:16].contiguous(), table[:, 16].contiguous()
+    ok = success.to(torch.int32).contiguous()
+    Rd, td = R.to(torch.float64).contiguous(), t.to(torch.float64).contiguous()
+    mk = masks.contiguous()
+    area = mk.ne(0).flatten(1).sum(1, dtype=torch.int32)   # plumbing on the device, no synchronisation: the set pixels of each mask
+    call("fp_pose_verify_mask", ptr(ok), ptr(Rd), ptr(td), ptr(cam), ptr(Ad), ptr(rng), ptr(cen), ptr(rad), ptr(vp.points), int(vp.points.shape[0]),
+         ptr(mk), ptr(area), H, W, P, n, grid, min_pixels, ptr(counts), ptr(score), ptr(status), stream())
+    return {"counts": counts.reshape(B, n, 4), "score": score.reshape(B, n), "status": status.reshape(B, n)}
+
+
 def select_best_verified(poses: Dict[str, torch.Tensor], verify: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """select_best_coarse with the hypotheses ranked by verify_poses_depth's result: among a detection's successful coarse poses the scored
     ones (status 0) before the others, then the higher score, then the higher coarse quality, then the first slot.

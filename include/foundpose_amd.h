@@ -251,6 +251,27 @@ int fp_pose_verify_depth(const int32_t* success, const double* R, const double* 
                          const float* points, int num_points, const float* depth, int num_images, int H, int W, int num_pairs, int n_slots, int grid,
                          int min_visible, int32_t* out_counts, double* out_score, int32_t* out_status, fp_stream_t stream);
 
+/* Hypothesis verification against the detection's mask (this project's own stage): the point sample of the whole
+ * model placed at the pose of every (detection, template slot) pair, the cells of a G x G grid its points project into taken as the model's
+ * silhouette, and that silhouette compared with the detection's mask.  success, R, t, frame_cameras, A, point_ranges, centers, radii, points
+ * and num_points are fp_pose_verify_depth's.  masks [num_pairs / n_slots, H, W] uint8: each detection's own mask in the frame camera's image
+ * (non-zero = set); mask_areas [.] int32: the number of set pixels of each.  All arithmetic is fp64, every step one rounded operation in
+ * this order (no FMA contraction):
+ *   R_f, t_f, C, status 2 unless C.z > rho + 1, u_c, v_c, r_px, u0 = u_c - r_px, v0 = v_c - r_px, h = 2 r_px / G: fp_pose_verify_depth's;
+ *   pass 1: every sampled point with X_c.z > 1 sets the bit of its cell (fp_pose_verify_depth's cell, the clamp included) in a bitmap;
+ *   pass 2: a pixel (px, py), integers in [0, W-1] x [0, H-1], has ix = floor((px - u0) / h), iy alike (no clamp); it is a model pixel iff
+ *     0 <= ix < G, 0 <= iy < G and the bit of cell iy G + ix is set; n_both counts the model pixels whose mask byte is non-zero,
+ *     n_model_only the others.  No byte outside the image is read, whatever the pose.
+ * out_counts [num_pairs, 4] = (n_both, n_model_only, n_mask_only = area - n_both, n_cells = set bits of the bitmap); out_score [num_pairs]
+ * f64 = n_both / (n_both + n_model_only + n_mask_only), one division of two integers converted to double, when n_both + n_model_only >=
+ * min_pixels (>= 1), else 0; out_status [num_pairs]: 0 scored, 1 fewer than min_pixels model pixels (counts reported), 2 skipped (success
+ * <= 0, an empty point range, or C.z <= rho + 1; counts and score 0).  grid G in [8, 128]; H W at most 2^30.  A pair's result depends on
+ * its own data only: it is the same bits alone, in any batch and at any position. */
+int fp_pose_verify_mask(const int32_t* success, const double* R, const double* t, const double* frame_cameras, const double* A,
+                        const int32_t* point_ranges, const double* centers, const double* radii, const float* points, int num_points,
+                        const uint8_t* masks, const int32_t* mask_areas, int H, int W, int num_pairs, int n_slots, int grid, int min_pixels,
+                        int32_t* out_counts, double* out_score, int32_t* out_status, fp_stream_t stream);
+
 /* sample_feature_map_at_points (utils/feature_util.py:100-131): bilinear grid_sample, zeros padding,
  * align_corners=False.  fmap addressed by element strides (image, channel, y, x); point_img (may be null)
  * maps each point to its image.  out [num_points, C]. */
