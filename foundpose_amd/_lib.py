@@ -76,6 +76,7 @@ _PROTOS = {
     "fp_gemm_bf16": [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp],
     "fp_gemm_bf16_ln": [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp],
     "fp_gemm_resid_tile_rows": [i32, i32, i32],
+    "fp_gemm_wide_tile_rows": [i32, i32, i32, i32],
     "fp_ln_finalize": [vp, i32, i32, i32, i32, f32, vp, vp],
     "fp_gemm_fp8": [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, f32, vp],
     "fp_quantize_fp8": [vp, i32, i64, f32, vp, vp],

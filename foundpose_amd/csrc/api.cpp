@@ -343,7 +343,8 @@ int fp_gemm_bf16(const void* A, int lda, const void* W, int ldw, int M, int N, i
   const int tile = (epilogue >> 8) & 0xfff;  // tuning bits: force the 128 or 256 block tile
   const bool f16 = (epilogue >> 21) & 1;     // FP_GEMM_F16: IEEE fp16 operands and 16-bit outputs
   epilogue &= 0xff;
-  FP_REQUIRE(tile == 0 || tile == 64 || tile == 128 || tile == 256 || tile == 320, "fp_gemm_bf16: bad tile override %d", tile);
+  FP_REQUIRE(tile == 0 || tile == 64 || tile == 128 || tile == 256 || tile == 320 || (tile == 352 && (epilogue == GEMM_EPI_BIAS_BF16 || epilogue == GEMM_EPI_GELU_BF16)),
+             "fp_gemm_bf16: bad tile override %d", tile);
 
   FP_REQUIRE(epilogue == GEMM_EPI_BIAS_BF16 || epilogue == GEMM_EPI_GELU_BF16 || epilogue == GEMM_EPI_LS_RESID_F32 ||
                  epilogue == GEMM_EPI_BIAS_F32 || epilogue == GEMM_EPI_SWIGLU_BF16,
@@ -363,7 +364,9 @@ int fp_gemm_bf16_ln(const void* A, int lda, const void* W, int ldw, int M, int N
   const int tile = (epilogue >> 8) & 0xfff;
   const bool f16 = (epilogue >> 21) & 1;     // FP_GEMM_F16: IEEE fp16 operands, 16-bit outputs and (hi, lo) stream
   epilogue &= 0xff;
-  FP_REQUIRE(tile == 0 || tile == 64 || tile == 128 || tile == 256 || tile == 320 || (tile == 352 && epilogue == GEMM_EPI_RESID_HILO), "fp_gemm_bf16_ln: bad tile override %d", tile);
+  FP_REQUIRE(tile == 0 || tile == 64 || tile == 128 || tile == 256 || tile == 320 ||
+                 (tile == 352 && (epilogue == GEMM_EPI_RESID_HILO || epilogue == GEMM_EPI_BIAS_BF16 || epilogue == GEMM_EPI_GELU_BF16)),
+             "fp_gemm_bf16_ln: bad tile override %d", tile);
   GemmBf16Args a;
   memset(&a, 0, sizeof(a));
   a.A = reinterpret_cast<const __bf16*>(A); a.lda = lda; a.W = reinterpret_cast<const __bf16*>(W); a.ldw = ldw;
@@ -386,6 +389,7 @@ int fp_gemm_bf16_ln(const void* A, int lda, const void* W, int ldw, int M, int N
 }
 
 int fp_gemm_resid_tile_rows(int M_valid, int N, int num_cus) { return gemm_resid_tile_rows(M_valid, N, num_cus); }
+int fp_gemm_wide_tile_rows(int M, int M_valid, int N, int num_cus) { return gemm_wide_tile_rows(M, M_valid, N, num_cus); }
 
 int fp_ln_finalize(const float* stats, int parts, int stats_stride, int rows, int dim, float eps, float* ln_row, fp_stream_t stream) {
   FP_REQUIRE(stats && ln_row && parts >= 1 && dim >= 1, "fp_ln_finalize: bad arguments");

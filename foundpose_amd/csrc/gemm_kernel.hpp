@@ -5,7 +5,7 @@
 //   * block tile 256x256x64, 512 threads = 2x4 waves, each wave 128x64 = 4x2 v_mfma_f32_32x32x16_bf16
 //     (128x128, 4 waves for small shapes; 64x128 for the residual GEMMs of one or two crops; 320x256 = waves of 5x2 tiles for wide outputs whose round
 //     count favours it; 352x256 = wave rows of 6x2 and 5x2 tiles, 192 + 160 rows, for the residual GEMMs on the (hi, lo) stream where two rounds of it
-//     replace three of 256 rows -- every shape gives the same bits)
+//     replace three of 256 rows, and for the wide outputs where whole rounds of it cost less (qkv of the bench batch) -- every shape gives the same bits)
 //   * A and W tiles go HBM/L2 -> LDS by LDS-DMA (buffer_load_dwordx4 ... lds, 16 B/lane, no VGPR round trip), double
 //     buffered, one barrier per K-tile, next tile's DMA in flight under the MFMAs; on the 8-wave tile only ONE wave
 //     row issues the DMA (each SIMD hosts a wave of either row: the partner keeps the matrix pipe fed while the
@@ -48,6 +48,11 @@ FP_DEVICE unsigned stage_lane_offset(int ld, int lane, int parity) {
 }
 FP_DEVICE void stage_rows(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, int ld, int row0, int k0, char* lds, int rblk) {
   const unsigned soff = (unsigned)((row0 + rblk * 8) * ld + k0) * 2u;  // uniform
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)(lds + rblk * 1024), 16, voff, soff, 0, 0);
+}
+// ... with the source row group given apart from the LDS one (a tile whose rows pass the end of the matrix, below)
+FP_DEVICE void stage_rows_from(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, int ld, int src_row, int k0, char* lds, int rblk) {
+  const unsigned soff = (unsigned)(src_row * ld + k0) * 2u;  // uniform
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)(lds + rblk * 1024), 16, voff, soff, 0, 0);
 }
 
@@ -201,7 +206,12 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
   constexpr int A_INSTR = BM / 8 / NISSUE, B_INSTR = BN / 8 / NISSUE;  // DMA instructions per issuing wave per K-tile
   constexpr int PIECES = A_INSTR + B_INSTR;
   static_assert(PIECES % 2 == 0 || !(F8 || SP), "staging split");  // quarters of the piece list per k-step (uneven for the 320- and 352-row tiles: 18 and 19 pieces), halves in the fp8 / f16x3 loops
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 stages][A | B]
+  // 192 accumulator registers -- the 352-row tile -- leave no room to hold the bias, or the column sums of the folded LayerNorm, over the bands of the epilogue:
+  // the tile's BN values of each sit in LDS behind the stages.  (Fetched per band from L1 / L2 instead, the wait for them is also a wait for every load issued
+  // before them -- the residual rows of the band, which are meant to land under the register -> slab pass -- and in the bias / GELU epilogues nothing hides it.)
+  constexpr bool BIAS_LDS = TM * TN * 16 > 160;
+  static_assert(!BIAS_LDS || (!F8 && !SP && NT == 2 * BN && NSTAGE == 2), "one thread per stashed value, behind two stages");
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2 stages][A | B] (+ [bias BN | colsum BN] fp32 with BIAS_LDS)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN, l31 = lane & 31, kh = lane >> 5;
   auto tile_on = [&](int i) { return !UNEVEN || wm * TM + i < MT; };
@@ -256,11 +266,18 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
     const bool issuer = !ASYM || wm == 0;  // wave-uniform
     const int iw = ASYM ? wave % NISSUE : wave;
     const unsigned voff_a_w = voff_a[iw & 1];
+    // 352 rows divide no padded M, so the last m-tile of a launch can pass the end of A.  The row part of a piece's address travels in the scalar offset,
+    // which the buffer's range check does not cover: a row group past the end is fetched from the matrix's last row group instead (rows >= M_valid are never
+    // stored, and a row of the output depends on its own row of A only).  M and m0 are multiples of 32: a row group lies whole on one side.
+    const int a_last_grp = (a.M - m0 < BM ? a.M - m0 : BM) - 8;
     // one VM instruction per call and issuing wave: the vmcnt immediates of the deep pipeline count on it
     auto stage_piece = [&](int q, int t, char* buf) {
       if (!issuer) return;
       if (q < A_INSTR) {
-        if constexpr (A_ILV) stage_rows(rsrc_a, voff_a_w, a.lda, 0, t * BK, buf, q * NISSUE + iw);
+        if constexpr (A_ILV) {
+          const int rblk = q * NISSUE + iw;
+          stage_rows_from(rsrc_a, voff_a_w, a.lda, rblk * 8 < a_last_grp ? rblk * 8 : a_last_grp, t * BK, buf, rblk);
+        }
         else stage_rows(rsrc_a, voff_a[q & 1], a.lda, 0, t * BK, buf, iw * A_INSTR + q);
       }
       else stage_rows(rsrc_w, voff_w[(q - A_INSTR) & 1], a.ldw, 0, t * BK, buf + A_BYTES, iw * B_INSTR + (q - A_INSTR));
@@ -276,6 +293,11 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
         }
     }
 
+    if constexpr (BIAS_LDS) {   // (published by the main loop's first barrier, read after its last)
+      float* stash = reinterpret_cast<float*>(smem + 2 * STAGE);
+      if (tid < BN) stash[tid] = a.bias[n0 + tid];
+      else if (a.colsum) stash[tid] = a.colsum[n0 + tid - BN];
+    }
     // Folded LayerNorm (consumer side): (rstd, mean * rstd) of the TM rows this lane will finish (ln_finalize's table).
     // Loaded here, behind the first K-tile's DMA, so the round trip hides under the main loop (fetched in the epilogue it
     // cost ~3.5 us per band).
@@ -287,7 +309,11 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
           if (!tile_on(i)) continue;
-          const float2 st = a.ln_stats[m0 + wm * WROWS + i * 32 + l31];
+          const int row = m0 + wm * WROWS + i * 32 + l31;
+          if constexpr (UNEVEN) {  // the last 352-row tile passes M_valid and can pass M, the end of the table: such a row keeps (1, 0), its address is never formed
+            if (row >= a.M_valid) continue;
+          }
+          const float2 st = a.ln_stats[row];
           ln_rs[i] = st.x;
           ln_mrs[i] = st.y;
           if constexpr (H16) {  // W (and with it acc and colsum) carries the matrix's power-of-two scale: rstd (acc - mean colsum) / s_w, exactly
@@ -528,17 +554,15 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
     // epilogue applies out = rstd_r * (acc - mean_r * colsum_n) + bias_n before the non-linearity
     constexpr bool LN_FOLD_OK = !F8 && (EPI == GEMM_EPI_BIAS_BF16 || EPI == GEMM_EPI_GELU_BF16 || EPI == GEMM_EPI_SWIGLU_BF16);
     const bool fold = LN_FOLD_OK && a.ln_stats != nullptr;
-    // (192 accumulator registers -- the 352-row tile -- leave no room to hold the bias over the bands: it is fetched again per band, from L1 / L2)
-    constexpr bool BIAS_LATE = TM * TN * 16 > 160;
     float4 bias[TN][4], gam[TN][4];
   #pragma unroll
     for (int tn = 0; tn < TN; ++tn)
   #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int n = n0 + wn * (BN / WN) + tn * 32 + 8 * g + 4 * kh;
-        if constexpr (!BIAS_LATE) bias[tn][g] = *reinterpret_cast<const float4*>(a.bias + n);
+        if constexpr (!BIAS_LDS) bias[tn][g] = *reinterpret_cast<const float4*>(a.bias + n);
         if constexpr (EPI == GEMM_EPI_LS_RESID_F32 || F8) gam[tn][g] = *reinterpret_cast<const float4*>(a.gamma + n);
-        if constexpr (LN_FOLD_OK) {
+        if constexpr (LN_FOLD_OK && !BIAS_LDS) {
           if (fold) gam[tn][g] = *reinterpret_cast<const float4*>(a.colsum + n);  // (gam is free in these epilogues)
         }
       }
@@ -602,7 +626,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
         for (int g = 0; g < 4; ++g) {
           const int col = wn * (BN / WN) + tn * 32 + 8 * g + 4 * kh;
           float4 bs;
-          if constexpr (BIAS_LATE) bs = *reinterpret_cast<const float4*>(a.bias + n0 + col);
+          if constexpr (BIAS_LDS) bs = *reinterpret_cast<const float4*>(smem + 2 * STAGE + col * 4);
           else bs = bias[tn][g];
           float v0 = acc[tm][tn][4 * g + 0] + bs.x, v1 = acc[tm][tn][4 * g + 1] + bs.y;
           float v2 = acc[tm][tn][4 * g + 2] + bs.z, v3 = acc[tm][tn][4 * g + 3] + bs.w;
@@ -613,7 +637,9 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
           }
           if constexpr (LN_FOLD_OK) {
             if (fold) {  // rstd * acc - (mean * rstd) * colsum + bias, two columns per v_pk_fma_f32
-              const float4 cs = gam[tn][g];
+              float4 cs;
+              if constexpr (BIAS_LDS) cs = *reinterpret_cast<const float4*>(smem + 2 * STAGE + (BN + col) * 4);
+              else cs = gam[tn][g];
               const f32x2 rs2 = {rs, rs}, nm2 = {-mrs, -mrs};
               const f32x2 t01 = __builtin_elementwise_fma(nm2, f32x2{cs.x, cs.y}, f32x2{bs.x, bs.y});
               const f32x2 t23 = __builtin_elementwise_fma(nm2, f32x2{cs.z, cs.w}, f32x2{bs.z, bs.w});
@@ -841,7 +867,7 @@ int launch_cfg(const GemmBf16Args& a_in, hipStream_t st) {
   }
   // M is padded to whole tiles of every shape in use; tiles of padding rows only are not launched (they would all sit at the end of the
   // tile order, i.e. in the last XCD's chunk, and leave that XCD short of work)
-  a.m_tiles = (a.M + BM - 1) / BM;   // (352 rows divide no padded M: the last tile's rows past M read as zeros through the buffer resource and are never stored)
+  a.m_tiles = (a.M + BM - 1) / BM;   // (352 rows divide no padded M: the last tile's rows past M are fetched from the matrix's last row group instead, stage_piece, and are never stored)
   if (a.M_valid > 0 && (a.M_valid + BM - 1) / BM < a.m_tiles) a.m_tiles = (a.M_valid + BM - 1) / BM;
   unsigned grid = a.m_tiles * (a.N / BN);
   a.rast_r = a.rast_gn = 0;
@@ -855,7 +881,8 @@ int launch_cfg(const GemmBf16Args& a_in, hipStream_t st) {
     a.rast_r = ra.r; a.rast_gn = ra.gn;
     grid = ((a.m_tiles + ra.r - 1) / ra.r) * ((a.N / BN) / ra.gn) * 32;
   }
-  const size_t lds = (size_t)(BM + BN) * BK * 2 * NSTAGE;
+  constexpr bool BIAS_LDS = (BM / 32 + WM - 1) / WM * (BN / WN / 32) * 16 > 160;   // the kernel's BIAS_LDS: bias and column sums of the tile behind the stages
+  const size_t lds = (size_t)(BM + BN) * BK * 2 * NSTAGE + (BIAS_LDS ? 2 * BN * 4 : 0);
   // (Measured and dropped: asking for > 80 KiB of LDS when a launch has no more tiles than CUs, so that every workgroup takes a CU of its own -- the dispatcher
   //  already spreads them: fc2 of a two-crop batch 51.4 us either way, tools/b1_gemm_probe.py.)
   static FpDeviceOnce attr;
@@ -896,6 +923,31 @@ static int resid_tile_rows(int m_valid, int n, int cus) {
   return r352 < r256 && r352 * 352 < r256 * 256 ? 352 : 256;
 }
 
+// ... and for the wide outputs (qkv, fc1: the BIAS / GELU epilogues, plain or with the folded LayerNorm; bf16 and fp16): 256, 320 or 352 rows by
+// cost = rounds x height x factor, the estimate of tall_tile_wins with one more candidate.  352 rows turn the bench batch's 125 m-tiles into whole rounds -- qkv
+// (8 x 4 raster) 16 super-rows x 3 = 48 super-tiles = 6 rounds for the 7 of 320 rows, fc1 (4 x 8) 32 x 2 = 64 = 8 for 9 -- with every tile equal.  320 rows need M to
+// be a whole number of tiles of both heights, 352 rows only 0 < M_valid <= M.  A pure function of the shape and the CU count.  The 352 factors are measured
+// (profiles/EXPERIMENTS.md section 0.8, profiles/r7_gemm_tile_sweep.txt): a round of 352 rows costs more per row than one of 256 -- six epilogue bands for five
+// and a half bands of rows, more so under fc1's GELU -- so one factor per raster, each set between the launches where the forced 352-row tile measured faster
+// than the pick without it by more than the spread of the repetitions and those where it did not: qkv at the bench batch takes it (6 rounds for 7), fc1 does not.
+constexpr float WIDE_FACTOR_320 = 0.97f, WIDE_FACTOR_352_R8X4 = 1.02f, WIDE_FACTOR_352_R4X8 = 1.05f;
+static int wide_tile_rows(int m, int m_valid, int n, int cus) {
+  if (m <= 0 || m % 256 != 0 || m_valid <= 0 || m_valid > m || n <= 0 || n % 256 != 0 || cus <= 0) return 256;
+  const int tiles_big = (m / 256) * (n / 256);
+  if (tiles_big < cus || (tiles_big > cus && tiles_big < cus + cus / 2)) return 256;   // does not fill the chip with 256^2 tiles (launch() below: 128^2 then)
+  int best = 256;
+  float cost = (float)(xcd_rounds(256, m_valid, n / 256, cus) * 256);
+  if (m % 320 == 0) {
+    const float c320 = (float)(xcd_rounds(320, m_valid, n / 256, cus) * 320) * WIDE_FACTOR_320;
+    if (c320 < cost) { best = 320; cost = c320; }
+  }
+  // (352 rows only for a launch on the super-tile raster: what the factor was measured on)
+  const GemmRaster ra = pick_raster(352, n / 256, (unsigned)((m_valid + 351) / 352 * (n / 256)));
+  const float c352 = (float)(xcd_rounds(352, m_valid, n / 256, cus) * 352) * (ra.gn == 8 ? WIDE_FACTOR_352_R4X8 : WIDE_FACTOR_352_R8X4);
+  if (ra.r && c352 < cost) best = 352;
+  return best;
+}
+
 // Tile selection: 256x256 (8 waves, 1 block/CU, 128 KiB LDS) when the shape allows it and fills the chip,
 // otherwise 128x128 (4 waves, 2 blocks/CU).
 template <int EPI, GemmFmt FMT>
@@ -909,7 +961,14 @@ int launch(const GemmBf16Args& a, hipStream_t st) {
   const bool use_big = big_ok && (force == 256 || (force == 0 && tiles_big >= cus && !(tiles_big > cus && tiles_big < cus + cus / 2)));
   // (Measured and dropped, round 3: sending the m-tiles that hold the few tiles beyond a whole number of rounds -- qkv at the bench batch:
   //  2064 = 8 x 256 + 16 -- as 128^2 tiles in a second launch: 334 vs 289 us; a dependent second launch costs its own latency.)
-  if constexpr (!SP && (EPI == GEMM_EPI_BIAS_BF16 || EPI == GEMM_EPI_GELU_BF16 || EPI == GEMM_EPI_RESID_HILO)) {
+  if constexpr (!SP && (EPI == GEMM_EPI_BIAS_BF16 || EPI == GEMM_EPI_GELU_BF16)) {
+    const int pick = force == 0 && use_big ? wide_tile_rows(a.M, a.M_valid, a.N, cus) : 0;
+    const bool ok352 = a.N % 256 == 0 && a.M_valid > 0 && a.M_valid <= a.M;
+    if (ok352 && (force == 352 || pick == 352)) return launch_cfg<EPI, 352, 256, 2, 4, FMT>(a, st);
+    FP_REQUIRE(force != 352, "gemm_bf16: the 352-row tile needs N %% 256 == 0 and 0 < M_valid <= M (N %d, M_valid %d, M %d)", a.N, a.M_valid, a.M);
+    if ((force == 320 && a.M % 320 == 0 && a.N % 256 == 0) || pick == 320) return launch_cfg<EPI, 320, 256, 2, 4, FMT>(a, st);
+  }
+  if constexpr (!SP && EPI == GEMM_EPI_RESID_HILO) {
     if ((force == 320 && a.M % 320 == 0 && a.N % 256 == 0) || (force == 0 && use_big && tall_tile_wins(a)))
       return launch_cfg<EPI, 320, 256, 2, 4, FMT>(a, st);
   }

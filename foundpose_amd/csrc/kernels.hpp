@@ -146,7 +146,7 @@ struct GemmBf16Args {
   void* out; int ldo;
   const float* pos;           // [Np, ldo] fp32 pos-embed rows of the patch tokens
   int tok_np, tok_n, tok_skip;  // patches / tokens per image, first patch token index (1 + registers)
-  int tile_override;          // 0 = auto, 64 (x 128) / 128 / 256 / 320 / 352 (RESID_HILO) = force that block tile (benchmarks, tests)
+  int tile_override;          // 0 = auto, 64 (x 128) / 128 / 256 / 320 / 352 (BIAS, GELU, RESID_HILO) = force that block tile (benchmarks, tests)
   int m_tiles;                // set by the launcher: row tiles that hold live rows (tiles of padding rows only are not launched)
   unsigned rast_r, rast_gn;
   float out_scale;            // fp8 kernels: > 0 -> the GELU / SwiGLU result leaves as e4m3(value * out_scale) bytes; f16x3: scale of a split-fp16 output
@@ -182,6 +182,7 @@ enum class GemmFmt {
 };
 template <GemmFmt FMT> int gemm_launch_fmt(int epi, const GemmBf16Args& a, hipStream_t st);   // instantiated by the format's gemm_*.hip
 int gemm_resid_tile_rows(int m_valid, int n, int cus);   // (gemm_bf16.hip) block-tile height the launcher picks for a RESID_HILO launch that fills the chip: 256 or 352
+int gemm_wide_tile_rows(int m, int m_valid, int n, int cus);   // (gemm_bf16.hip) ... and for a BIAS / GELU launch (qkv, fc1) of m padded rows: 256, 320 or 352
 int gemm_launch(GemmFmt fmt, int epi, const GemmBf16Args& a, hipStream_t st);   // (api.cpp) the one entry point: gemm_launch_fmt<fmt>
 
 // ---------------------------------------------------------------- dtypes of the C ABI

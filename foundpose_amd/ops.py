@@ -130,7 +130,7 @@ def _h16_bit(a: torch.Tensor, w: torch.Tensor) -> int:
 
 
 def gemm_bf16(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, gamma=None, out=None, epilogue: int = 0,
-              m_valid: Optional[int] = None) -> torch.Tensor:
+              m_valid: Optional[int] = None, tile: int = 0) -> torch.Tensor:
     """bf16 operands, or fp16 ones (the "f16" mode: same kernels on v_mfma_f32_32x32x16_f16; 16-bit outputs are then fp16)."""
     require_cuda(a, w, bias)
     M, K = a.shape
@@ -139,7 +139,7 @@ def gemm_bf16(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, gamma=None, 
         dt = torch.float32 if (epilogue & 0xff) in (3, 5) else a.dtype
         out = torch.zeros(M, N // 2 if (epilogue & 0xff) == 6 else N, dtype=dt, device=a.device)
     call("fp_gemm_bf16", ptr(a), a.stride(0), ptr(w), w.stride(0), M, N, K, M if m_valid is None else m_valid,
-         ptr(bias), ptr(gamma), ptr(out), out.stride(0), epilogue | _h16_bit(a, w), stream())
+         ptr(bias), ptr(gamma), ptr(out), out.stride(0), epilogue | (tile << 8) | _h16_bit(a, w), stream())
     return out
 
 

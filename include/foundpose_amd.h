@@ -437,8 +437,9 @@ int fp_layernorm(const float* x, int ld_x, const float* weight, const float* bia
                  fp_stream_t stream);
 /* epilogue: 0 bias->bf16, 1 bias+gelu->bf16, 3 LayerScale*(.)+residual (fp32 in place), 5 bias->f32,
  * 6 SwiGLU (interleaved column pairs -> [M, N/2] bf16);
- * tuning bits: epilogue | (128 << 8), | (256 << 8) or | (320 << 8) forces that block tile (default: chosen from the shape; 320 = the 320 x 256
- * tile of the bias / GELU epilogues, M a multiple of 320; every tile gives the same bits).  Row tiles without live rows (>= M_valid) are not launched. */
+ * tuning bits: epilogue | (128 << 8), | (256 << 8), | (320 << 8) or | (352 << 8) forces that block tile (default: chosen from the shape; 320 = the 320 x 256
+ * tile of the bias / GELU epilogues, M a multiple of 320; 352 = their 352 x 256 tile, N a multiple of 256 and 0 < M_valid <= M; every tile gives the same
+ * bits).  Row tiles without live rows (>= M_valid) are not launched. */
 int fp_gemm_bf16(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int M_valid, const float* bias,
                  const float* gamma, void* out, int ldo, int epilogue, fp_stream_t stream);
 /* The GEMMs of a block with the LayerNorm folded in (fp_vit_model.ln_fold), exported for unit tests and benchmarks.
@@ -456,6 +457,10 @@ int fp_gemm_bf16_ln(const void* A, int lda, const void* W, int ldw, int M, int N
  * 352 where it takes fewer rounds of tiles and fewer tile rows per compute unit.  Pure host arithmetic (no device needed); `352 << 8` in the tuning bits of
  * fp_gemm_bf16_ln forces that tile for epilogue 8 (N a multiple of 256, 0 < M_valid <= M; every tile gives the same bits). */
 int fp_gemm_resid_tile_rows(int M_valid, int N, int num_cus);
+/* ... and the height (256, 320 or 352 rows) it gives an epilogue-0 or -1 launch (plain or folded form, bf16 or fp16 operands) of M padded rows, M_valid of them
+ * live, x N columns: the least of rounds of tiles x tile height x a measured factor per height; 320 only where M is a whole number of 256- and 320-row tiles.
+ * Pure host arithmetic; degenerate arguments give 256.  (Added without a change of FP_ABI_VERSION: no existing entry point changed.) */
+int fp_gemm_wide_tile_rows(int M, int M_valid, int N, int num_cus);
 /* stats [parts, stats_stride, 2] partial row sums over `dim` columns in total -> ln_row [rows, 2] = (rstd, mean * rstd). */
 int fp_ln_finalize(const float* stats, int parts, int stats_stride, int rows, int dim, float eps, float* ln_row, fp_stream_t stream);
 
