@@ -229,7 +229,10 @@ __global__ __launch_bounds__(256, 4) void attn_bf16_kernel(AttnArgs a) {
 //   K image  [64 keys][128 B], 16-B chunk p of row r holds chunk p ^ ((r >> 1) & 7)            (b128 fragment reads)
 //   V image  [64 keys][128 B], 64-B half  g of row r holds half  g ^ ((r >> 1) & 1)            (transpose reads: the
 //            four keys x 64 B a half-wave touches then fall into four different bank quarters)
-// Rows past the last token read as zeros (buffer range check) and are masked exactly like before.
+// Rows past the last token read as zeros and are masked exactly like before.  A tile's row offset travels in the SCALAR offset of the load (soff_k + t below); on
+// gfx950 the range check of a raw buffer covers it -- an access is dropped when lane offset + scalar offset reaches the resource's size -- which the device showed:
+// NaN or an attractor (K = 8 x the mean query, V = 1000) in the rows behind an image, where 0 x NaN would poison the P V MFMA, leaves every output bit unchanged
+// (tests/test_gpu_attention_edges.py, this kernel and attn_split_kernel; the qkv workspace of a launch with m_pad = B N ends at the last token and relies on it).
 typedef __attribute__((address_space(3))) void lds_void_t;
 
 // QB = 2 32-query blocks per wave, 4 waves: 208 VGPRs, 2 waves/SIMD.  Each wave stages two of the tile's eight 8-key row groups.

@@ -266,9 +266,12 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void gemm_bf16_kernel(GemmBf16Args
     const bool issuer = !ASYM || wm == 0;  // wave-uniform
     const int iw = ASYM ? wave % NISSUE : wave;
     const unsigned voff_a_w = voff_a[iw & 1];
-    // 352 rows divide no padded M, so the last m-tile of a launch can pass the end of A.  The row part of a piece's address travels in the scalar offset,
-    // which the buffer's range check does not cover: a row group past the end is fetched from the matrix's last row group instead (rows >= M_valid are never
-    // stored, and a row of the output depends on its own row of A only).  M and m0 are multiples of 32: a row group lies whole on one side.
+    // 352 rows divide no padded M, so the last m-tile of a launch can pass the end of A.  The row part of a piece's address travels in the scalar offset.
+    // This clamp was written on the assumption that the buffer's range check leaves the scalar offset out; measured on gfx950 it does NOT (the attention kernels
+    // carry their key tile's rows the same way and return zeros behind the operand: csrc/attn.hip, tests/test_gpu_attention_edges.py), so such a row group would
+    // read as zeros either way.  The fetch stays as it is -- it depends on no property of the range check: a row group past the end is fetched from the matrix's
+    // last row group instead (rows >= M_valid are never stored, and a row of the output depends on its own row of A only; tests/test_gpu_gemm_guard.py).  M and
+    // m0 are multiples of 32: a row group lies whole on one side.
     const int a_last_grp = (a.M - m0 < BM ? a.M - m0 : BM) - 8;
     // one VM instruction per call and issuing wave: the vmcnt immediates of the deep pipeline count on it
     auto stage_piece = [&](int q, int t, char* buf) {

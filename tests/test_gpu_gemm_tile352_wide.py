@@ -6,7 +6,7 @@ order of an accumulator, the folded-LayerNorm correction, the bias and the GELU 
 past m_valid, the padding columns of a row stride wider than N) keeps the sentinel the output was filled with.
 
 352 divides no padded M: the last m-tile of a launch passes m_valid and can pass M.  The folded form's `ln_row` has exactly M rows, so the row guard of that
-table is the code that runs here; a read past it is not something this test can see.
+table is the code that runs here; a read past it is not something this test can see (tests/test_gpu_gemm_guard.py puts NaN behind every operand for that).
 The launcher's pick is host arithmetic on (padded rows, live rows, columns, compute units) and is checked without a device.
 """
 
