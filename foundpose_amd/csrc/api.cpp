@@ -316,6 +316,21 @@ int fp_pose_verify_mask(const int32_t* success, const double* R, const double* t
   return launch_pose_verify_mask(a, num_pairs, ST(stream));
 }
 
+int fp_detection_masks(const int32_t* counts, const int32_t* run_off, int num_runs, int num_det, int hc, int wc, int H, int W, int open3x3,
+                       int32_t* scratch_prefix, uint8_t* out_masks, int32_t* out_area, fp_stream_t stream) {
+  FP_REQUIRE(num_det >= 0 && num_runs >= 0, "fp_detection_masks: %d detections with %d runs", num_det, num_runs);
+  FP_REQUIRE(H >= 1 && W >= 1 && H <= hc && W <= wc, "fp_detection_masks: an image of %d x %d out of a canvas of %d x %d (1 <= W <= wc, 1 <= H <= hc)", W, H, wc, hc);
+  FP_REQUIRE((long long)hc * wc <= (1ll << 30), "fp_detection_masks: a canvas of %d x %d (at most 2^30 pixels: the pixel index is an int)", wc, hc);
+  if (num_det == 0) return FP_OK;
+  FP_REQUIRE(run_off && out_masks && out_area, "fp_detection_masks: null pointer");
+  FP_REQUIRE((counts && scratch_prefix) || num_runs == 0, "fp_detection_masks: null counts / scratch_prefix");
+  DetMaskArgs a;
+  memset(&a, 0, sizeof(a));
+  a.counts = counts; a.run_off = run_off; a.num_runs = num_runs; a.hc = hc; a.wc = wc; a.H = H; a.W = W;
+  a.prefix = scratch_prefix; a.masks = out_masks; a.area = out_area;
+  return launch_detection_masks(a, num_det, open3x3, ST(stream));
+}
+
 // ------------------------------------------------------------------ ViT building blocks
 int fp_patchify(const float* images, int B, int H, int W, int patch, void* out, int ld_out, int out_dtype,
                 fp_stream_t stream) {

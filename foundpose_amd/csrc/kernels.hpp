@@ -458,3 +458,18 @@ struct MaskVerifyArgs {
   int* status;             // [pairs] 0 scored, 1 too few model pixels, 2 skipped
 };
 int launch_pose_verify_mask(const MaskVerifyArgs& a, int num_pairs, hipStream_t st);
+
+// ---------------------------------------------------------------- det_masks.hip
+constexpr int DM_TILE_W = 64, DM_TILE_H = 16;  // one workgroup per tile of the output image
+struct DetMaskArgs {
+  const int* counts;       // [num_runs] the concatenated run lengths of the detections
+  const int* run_off;      // [num_det + 1] where each detection's runs start (clamped to [0, num_runs] by the kernels)
+  int num_runs;
+  int hc, wc;              // the detector's canvas
+  int H, W;                // the image, centre-cropped out of the canvas
+  int* prefix;             // [num_runs] scratch: the inclusive prefix sums of each detection's runs
+  unsigned char* masks;    // [num_det, H, W] 0 / 1
+  int* area;               // [num_det] set pixels of each mask
+  int tiles_x, tiles_y;    // filled in by the launcher
+};
+int launch_detection_masks(DetMaskArgs a, int num_det, int open3x3, hipStream_t st);

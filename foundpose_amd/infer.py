@@ -8,10 +8,10 @@ ground-truth evaluation (opt-in: eval_models / --eval-gt) is one fp_pose_errors 
 estimated pose and one summary per frame; the HTML branches are not part of this path.
 
   python -m foundpose_amd.infer --opts configs/infer/lmo.json --dataset-dir <bop split dir> --detections <cnos json> \\
-         --repre-dir <output>/object_repre --output-dir <output>/inference [--vis [--models-dir <models>]] [--batch-detections 32]
+         --repre-dir <output>/object_repre --output-dir <output>/inference [--vis [--models-dir <models>]] [--batch-detections 32 [--device-masks]]
 
 --batch-detections N (N >= 1) runs infer_batched instead: one pass over the images, N detections per batch across frames and objects, the
-same poses.
+same poses; --device-masks with it makes the detections' masks on the device instead of on the host (section 19).
 """
 
 import argparse
@@ -146,13 +146,10 @@ def _annotated(inst, eval_model) -> bool:
     return eval_model is not None and getattr(inst.get("gt_anno"), "pose", None) is not None
 
 
-def select_instances(opts: InferOpts, object_lid: int, frame: Dict[str, Any], detections: Dict[Any, Any],
-                     num_target_insts: Optional[Dict[Tuple[int, int], int]], eval_model: Optional[eval_util.EvalModel],
-                     detection_times: Dict[Tuple[int, int], float]) -> List[Tuple[int, Dict[str, Any]]]:
-    """The instances of `object_lid` in one frame that get a pose: [(instance id, instance)] in instance order, empty when the frame is not
-    one of this object's.  Both drivers select with this function.  detection_times (PoseEvaluator.detection_times) receives the
-    detector's time of the frame."""
-    scene_id, im_id, cam = frame["scene_id"], frame["im_id"], frame["camera"]
+def _frame_targets(opts: InferOpts, object_lid: int, frame: Dict[str, Any],
+                   num_target_insts: Optional[Dict[Tuple[int, int], int]]) -> Optional[Tuple[List[Any], int]]:
+    """(the object's annotations in the frame, its number of target instances), or None when the frame is not one of this object's."""
+    scene_id, im_id = frame["scene_id"], frame["im_id"]
     # number of target instances (infer.py:308-321): from the test targets when given -- frames that are not a target of
     # this object, or whose count is 0, are skipped -- otherwise the number of ground-truth annotations of the frame
     # ground-truth annotations of this object that are sufficiently visible (infer.py:286-305): a frame that HAS annotations but
@@ -163,15 +160,30 @@ def select_instances(opts: InferOpts, object_lid: int, frame: Dict[str, Any], de
                         if getattr(a, "lid", object_lid) == object_lid and not np.isnan(getattr(a, "visibilities", 1.0))
                         and getattr(a, "visibilities", 1.0) > opts.min_visibility]
         if len(object_annos) == 0:
-            return []
+            return None
     if num_target_insts is not None:
         if (scene_id, im_id) not in num_target_insts:
-            return []
+            return None
         n_target = int(num_target_insts[(scene_id, im_id)])
     else:
         n_target = len(object_annos)     # infer.py:317: no targets and no annotations -> 0 -> the frame is skipped
     if n_target == 0:
+        return None
+    return object_annos, n_target
+
+
+def select_instances(opts: InferOpts, object_lid: int, frame: Dict[str, Any], detections: Dict[Any, Any],
+                     num_target_insts: Optional[Dict[Tuple[int, int], int]], eval_model: Optional[eval_util.EvalModel],
+                     detection_times: Dict[Tuple[int, int], float]) -> List[Tuple[int, Dict[str, Any]]]:
+    """The instances of `object_lid` in one frame that get a pose: [(instance id, instance)] in instance order, empty when the frame is not
+    one of this object's.  Both drivers select with this function (infer_batched's device_masks path: with
+    select_instances_device, the same rules).  detection_times (PoseEvaluator.detection_times) receives the
+    detector's time of the frame."""
+    scene_id, im_id, cam = frame["scene_id"], frame["im_id"], frame["camera"]
+    tgt = _frame_targets(opts, object_lid, frame, num_target_insts)
+    if tgt is None:
         return []
+    object_annos, n_target = tgt
     instances = infer_pose_util.get_instances_for_pose_estimation(
         scene_id, im_id, object_lid, opts.use_detections, detections, int(opts.num_preds_factor * n_target), object_annos,
         (cam.width, cam.height))
@@ -187,6 +199,42 @@ def select_instances(opts: InferOpts, object_lid: int, frame: Dict[str, Any], de
         if inst["input_mask_modal"].sum() == 0:
             continue
         kept.append((inst_j, inst))
+    return kept
+
+
+def select_instances_device(opts: InferOpts, lids: Sequence[int], frame: Dict[str, Any], detections: Dict[Any, Any],
+                            num_target_insts: Optional[Dict[int, Dict[Tuple[int, int], int]]],
+                            eval_models: Optional[Dict[int, Optional[eval_util.EvalModel]]],
+                            detection_times_by_lid: Dict[int, Dict[Tuple[int, int], float]]) -> Dict[int, List[Tuple[int, Dict[str, Any]]]]:
+    """select_instances for ALL objects of a frame at once, the detections' masks decoded and opened on the device
+    (infer_pose_util.instances_on_device): {lid: [(instance id, instance)]}, for every lid what select_instances
+    returns -- the same targets, the same detections in the same order, the same three filters, evaluated from the masks' areas and their
+    overlap counts instead of the masks -- except that "input_mask_modal" is a uint8 [H, W] tensor on the device.  use_detections=False
+    keeps the host path: those masks are annotations, not run lengths."""
+    if not opts.use_detections:
+        return {lid: select_instances(opts, lid, frame, detections, None if num_target_insts is None else num_target_insts.get(lid, {}),
+                                      None if eval_models is None else eval_models.get(lid), detection_times_by_lid[lid]) for lid in lids}
+    scene_id, im_id, cam = frame["scene_id"], frame["im_id"], frame["camera"]
+    preds_by_lid, annos_by_lid = {}, {}
+    for lid in lids:
+        tgt = _frame_targets(opts, lid, frame, None if num_target_insts is None else num_target_insts.get(lid, {}))
+        preds = None if tgt is None else detections.get((scene_id, im_id, lid))
+        if preds is not None:
+            annos_by_lid[lid] = tgt[0]
+            preds_by_lid[lid] = infer_pose_util._top_predictions(preds, int(opts.num_preds_factor * tgt[1]))
+    instances = infer_pose_util.instances_on_device(preds_by_lid, (cam.width, cam.height), annos_by_lid)
+    kept = {lid: [] for lid in lids}
+    for lid, insts in instances.items():
+        eval_model = None if eval_models is None else eval_models.get(lid)
+        for inst_j, inst in enumerate(insts):
+            detection_times_by_lid[lid][(scene_id, im_id)] = inst.get("time", 0)
+            if _annotated(inst, eval_model) and inst["gt_iou"] < 0.05:   # (gt_iou is mask_iou with the chosen annotation: one quotient of the same integers)
+                continue
+            if inst["mask_area"] > cam.width * cam.height:
+                continue
+            if inst["mask_area"] == 0:
+                continue
+            kept[lid].append((inst_j, inst))
     return kept
 
 
@@ -299,11 +347,14 @@ def _record_poses(evaluator: eval_util.PoseEvaluator, opts: InferOpts, object_li
         T_m2c[:3, :3], T_m2c[:3, 3] = R, t
         T_m2w = crop_cam.T_world_from_eye @ T_m2c  # infer.py:661-666
         if _annotated(inst, eval_model):   # infer.py:806-835
+            pred_mask = inst["input_mask_modal"]
+            if isinstance(pred_mask, torch.Tensor):   # infer_batched's device_masks path: only an evaluated mask ever reaches the host
+                pred_mask = pred_mask.cpu().numpy()
             bank_cams = repre.template_cameras_cam_from_model   # (a bank without template cameras: no template orientation error)
             tpl_cams = [bank_cams[int(cc["template_id"])] for cc in corr_all] if len(bank_cams) else []
             pending.append(dict(scene_id=scene_id, im_id=im_id, inst_id=inst_j, hypothesis_id=0, base_image=None, object_repre_vertices=vertices,
                                 obj_lid=object_lid, object_pose_m2w=(T_m2w[:3, :3], T_m2w[:3, 3:]), object_pose_m2w_gt=inst["gt_anno"].pose,
-                                orig_camera_c2w=cam, camera_c2w=crop_cam, pred_mask=inst["input_mask_modal"], gt_mask=inst["gt_anno"].masks_modal,
+                                orig_camera_c2w=cam, camera_c2w=crop_cam, pred_mask=pred_mask, gt_mask=inst["gt_anno"].masks_modal,
                                 corresp=corresp_np, retrieved_templates_camera_m2c=tpl_cams, time_per_inst=times,
                                 object_mesh_vertices=eval_model.pts, object_syms=eval_model.syms, object_diameter=eval_model.diameter,
                                 inlier_radius=opts.pnp_inlier_thresh))
@@ -543,13 +594,16 @@ def plan_flush(queue: Sequence[QueuedDetection]) -> FlushPlan:
 def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections, repres: Dict[int, repre_util.FeatureBasedObjectRepre],
                   output_dir: str, *, batch_detections: int = 32, extractor=None, precision: str = "bf16",
                   num_target_insts: Optional[Dict[int, Dict[Tuple[int, int], int]]] = None, weights: Optional[str] = None,
-                  eval_models: Optional[Dict[int, eval_util.EvalModel]] = None, seed: int = 0, renderer=None) -> List[str]:
+                  eval_models: Optional[Dict[int, eval_util.EvalModel]] = None, seed: int = 0, renderer=None,
+                  device_masks: bool = False) -> List[str]:
     """infer() for a whole split in ONE pass over its frames: the kept instances of every (frame, object) are queued and go through the
     crop producer, the engine and the PnP tail `batch_detections` at a time, across frames and objects (one DeviceBank of all objects).
     `frames` yields each image once (load_bop_frames_all); `gt_annos` may hold annotations of several objects.  The poses, scores and
     files are those of infer(): the instances are selected by the same function, the crops are the same bits, the engine's results do not
     depend on the batch, and RANSAC's sampler is keyed by the pair's index in its own (frame, object) group -- what the per-object driver's
-    launch gives it -- instead of its place in the batch.  Pictures are not made here: infer() / infer_object() write them."""
+    launch gives it -- instead of its place in the batch.  Pictures are not made here: infer() / infer_object() write them.
+    device_masks: the detections' run lengths are decoded, opened and cropped on the device (select_instances_device)
+    instead of on the host; the masks are the same bits and so is everything written."""
     if batch_detections < 1:
         raise ValueError(f"batch_detections must be >= 1, got {batch_detections}")
     if renderer is not None:
@@ -576,9 +630,16 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
     def entries():
         for frame_no, frame in enumerate(frames):
             cam, checked = frame["camera"], False
+            kept_by_lid = None
+            if device_masks:
+                kept_by_lid = select_instances_device(opts, lids, frame, detections, num_target_insts, dict(zip(lids, models)),
+                                                      {lid: evaluators[o].detection_times for o, lid in enumerate(lids)})
             for o, lid in enumerate(lids):
-                kept = select_instances(opts, lid, frame, detections, None if num_target_insts is None else num_target_insts.get(lid, {}),
-                                        models[o], evaluators[o].detection_times)
+                if kept_by_lid is not None:
+                    kept = kept_by_lid[lid]
+                else:
+                    kept = select_instances(opts, lid, frame, detections, None if num_target_insts is None else num_target_insts.get(lid, {}),
+                                            models[o], evaluators[o].detection_times)
                 if kept and (use_depth or depth_pnp or verify):
                     _check_frame_depth(frame, _depth_reason(opts))
                 if kept and not opts.crop and not checked:   # (as in infer_object: only a frame that has work is checked)
@@ -598,7 +659,10 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
         n = len(dets)
         by_no = {e.frame_no: e.frame for e in queue}
         images = torch.stack([_to_device_image(by_no[f]["image"]) for f in plan.frames])
-        masks = torch.from_numpy(np.stack([e.inst["input_mask_modal"] for e in dets]).astype(np.uint8)).cuda()
+        if device_masks and opts.use_detections:   # views into their frames' stacks: nothing is uploaded
+            masks = torch.stack([e.inst["input_mask_modal"] for e in dets])
+        else:
+            masks = torch.from_numpy(np.stack([e.inst["input_mask_modal"] for e in dets]).astype(np.uint8)).cuda()
         src_cams = [e.frame["camera"] for e in dets]
         if opts.crop:
             cams = []
@@ -779,11 +843,15 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
                     "<output-dir>/vis/<scene>_<im>.png; the object meshes come from --models-dir")
     ap.add_argument("--batch-detections", type=int, default=0, help="N >= 1: one pass over the split's images, N detections per batch across frames and "
                     "objects (infer_batched; same poses, no pictures); 0 (default): one object after the other, one batch per (image, object)")
+    ap.add_argument("--device-masks", action="store_true", help="with --batch-detections N >= 1: decode, open and crop the detections' masks on the "
+                    "device instead of on the host (same masks, same poses)")
     args = ap.parse_args(argv)
     if args.batch_detections < 0:
         ap.error("--batch-detections must be >= 0")
     if args.batch_detections >= 1 and args.vis:
         ap.error("--vis needs the per-object driver: drop --batch-detections (or pass 0)")
+    if args.device_masks and args.batch_detections < 1:
+        ap.error("--device-masks needs the batched driver: pass --batch-detections N (N >= 1)")
     opts = load_opts(args.opts)
     with_depth = (opts.final_pose_type in DEPTH_POSE_TYPES or opts.pnp_type in DEPTH_PNP_TYPES
                   or opts.coarse_select_type in DEPTH_SELECT_TYPES)   # the depth pose / PnP / select types read depth/<im>.png beside every image
@@ -815,7 +883,7 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     if args.batch_detections >= 1:
         out = infer_batched(opts._replace(object_lids=list(lids)), load_bop_frames_all(args.dataset_dir, targets, with_gt=args.eval_gt, with_depth=with_depth), detections, repres,
                             args.output_dir, batch_detections=args.batch_detections, extractor=extractor.to("cuda"), precision=args.precision,
-                            num_target_insts=n_inst, eval_models=eval_models)
+                            num_target_insts=n_inst, eval_models=eval_models, device_masks=args.device_masks)
         print("\n".join(out))
         return
     out = infer(opts._replace(object_lids=list(lids)), lambda lid: load_bop_frames(args.dataset_dir, targets, lid, with_gt=args.eval_gt, with_depth=with_depth), detections,

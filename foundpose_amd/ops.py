@@ -416,3 +416,26 @@ def texture_mips(rgb: torch.Tensor) -> torch.Tensor:
     out = torch.empty(_lib.texture_levels(w, h)[1], dtype=torch.int32, device=rgb.device)
     call("fp_texture_mips", ptr(rgb), w, h, ptr(out), stream())
     return out
+
+
+def detection_masks(counts: torch.Tensor, run_off: torch.Tensor, canvas_hw: Tuple[int, int], image_hw: Tuple[int, int],
+                    open3x3: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Detection masks from their COCO run lengths (fp_detection_masks).  counts int32 [R_total]: the runs of N
+    detections, concatenated; run_off int32 [N + 1]: where each detection's runs start (infer_pose_util.pack_rle builds and validates both;
+    the kernels clamp the offsets to the array, so a wrong table gives a wrong mask and never a wild read); canvas_hw = (hc, wc) of the
+    detector, image_hw = (H, W) of the image centre-cropped out of it.  -> (masks uint8 [N, H, W] of 0 / 1, area int32 [N]), the bits of
+    rle_to_binary_mask, open_mask_3x3 (when open3x3) and the [dy : hc - dy, dx : wc - dx] slice."""
+    require_cuda(counts, run_off)
+    if counts.dtype != torch.int32 or run_off.dtype != torch.int32 or counts.dim() != 1 or run_off.dim() != 1 or run_off.shape[0] < 1:
+        raise ValueError("detection_masks: counts must be int32 [R_total] and run_off int32 [N + 1]")
+    (hc, wc), (h, w) = (int(v) for v in canvas_hw), (int(v) for v in image_hw)
+    if not (1 <= h <= hc and 1 <= w <= wc and hc * wc <= 1 << 30):
+        raise ValueError(f"detection_masks: an image of {w} x {h} out of a canvas of {wc} x {hc} (1 <= W <= wc, 1 <= H <= hc, hc wc <= 2^30)")
+    counts, run_off = counts.contiguous(), run_off.contiguous()
+    n = int(run_off.shape[0]) - 1
+    masks = torch.empty(n, h, w, dtype=torch.uint8, device=counts.device)
+    area = torch.empty(n, dtype=torch.int32, device=counts.device)
+    prefix = torch.empty(max(int(counts.shape[0]), 1), dtype=torch.int32, device=counts.device)
+    call("fp_detection_masks", ptr(counts), ptr(run_off), int(counts.shape[0]), n, hc, wc, h, w, int(bool(open3x3)), ptr(prefix), ptr(masks), ptr(area),
+         stream())
+    return masks, area

@@ -272,6 +272,23 @@ int fp_pose_verify_mask(const int32_t* success, const double* R, const double* t
                         const uint8_t* masks, const int32_t* mask_areas, int H, int W, int num_pairs, int n_slots, int grid, int min_pixels,
                         int32_t* out_counts, double* out_score, int32_t* out_status, fp_stream_t stream);
 
+/* Detection masks from their COCO run lengths (the device_masks path of infer_batched): what
+ * infer_pose_util.rle_to_binary_mask, open_mask_3x3 and the centre crop of the host path compute, for num_det detections in one call.
+ * counts [num_runs] int32: the run lengths of all detections, concatenated; run_off [num_det + 1] int32: detection n owns the R =
+ * run_off[n + 1] - run_off[n] runs from run_off[n] on (offsets are clamped to [0, num_runs], nothing outside counts is read).  hc, wc: the
+ * detector's canvas, shared by the call; H <= hc, W <= wc: the image; hc wc at most 2^30.
+ *   decode: with s_i the inclusive prefix sums of the detection's runs (a negative count counts as 0, the sums saturate at 2^31 - 1), canvas
+ *     pixel (x, y) has the column-major index p = x hc + y and k = the number of s_i <= p; it is set iff k < R and k is odd (runs alternate
+ *     0 / 1 starting with 0; a total short of hc wc leaves the rest 0, what lies beyond hc wc is ignored);
+ *   opening (open3x3 != 0), on the canvas: an eroded pixel is 1 iff every pixel of its 3 x 3 that lies inside the canvas is 1, a dilated
+ *     pixel is 1 iff any pixel of its 3 x 3 of the eroded image that lies inside the canvas is 1;
+ *   crop: dx = (wc - W) / 2, dy = (hc - H) / 2 (integer division); out_masks[n, y, x] = canvas pixel (x + dx, y + dy), 0 or 1.
+ * out_masks [num_det, H, W] uint8, every byte written; out_area [num_det] int32: the set pixels of each mask.  scratch_prefix: num_runs
+ * int32.  num_det = 0 returns without a launch.  A detection's result depends on its own runs only: it is the same bits alone, in any
+ * batch and at any position.  (Added without a change of FP_ABI_VERSION: no existing entry point changed.) */
+int fp_detection_masks(const int32_t* counts, const int32_t* run_off, int num_runs, int num_det, int hc, int wc, int H, int W, int open3x3,
+                       int32_t* scratch_prefix, uint8_t* out_masks, int32_t* out_area, fp_stream_t stream);
+
 /* sample_feature_map_at_points (utils/feature_util.py:100-131): bilinear grid_sample, zeros padding,
  * align_corners=False.  fmap addressed by element strides (image, channel, y, x); point_img (may be null)
  * maps each point to its image.  out [num_points, C]. */

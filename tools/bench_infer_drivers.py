@@ -11,7 +11,12 @@ spent loading frames, in select_instances (detection masks: RLE decoding and the
 correspondences of every pose to the host, scores, evaluator) -- host work outside the stage clocks -- and the mean of every per-detection
 `times` stage of estimated-poses.json.
 
+--device-masks: after the runs above, infer_batched(<first of --batches>) with the host masks and with device_masks=True
+on the same split in the same process, in the order host, device, host, device; the report gains "device_masks": the four runs (the device
+ones with select_instances_device_s), the mean and the spread of the two repeats of each path, and the ratios device / host.
+
   python tools/bench_infer_drivers.py [--out profiles/infer_drivers.json]
+  python tools/bench_infer_drivers.py --batches 32 --device-masks --out profiles/infer_drivers_device_masks.json
 """
 import argparse
 import json
@@ -121,6 +126,7 @@ def main():
     ap.add_argument("--size", type=int, default=518)
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--batches", default="32,256", help="batch_detections values of infer_batched")
+    ap.add_argument("--device-masks", action="store_true", help="also run infer_batched(first of --batches) host, device, host, device (see above)")
     ap.add_argument("--out", default=None, help="also write the JSON report here")
     args = ap.parse_args()
     name = f"dinov2_version={args.version}_stride=14_facet=token_layer={args.layer}_norm=1"
@@ -144,18 +150,20 @@ def main():
         def per_object(out_dir, timer):
             infer.infer(opts, lambda lid: timer(infer.load_bop_frames(split, targets, lid)), detections, repres, out_dir, extractor=ex, num_target_insts=n_inst)
 
-        def batched(n):
+        def batched(n, **kw):
             def run(out_dir, timer):
                 infer.infer_batched(opts, timer(infer.load_bop_frames_all(split, targets)), detections, repres, out_dir, batch_detections=n, extractor=ex,
-                                    num_target_insts=n_inst)
+                                    num_target_insts=n_inst, **kw)
             return run
         select, record = TimedCalls("select_instances"), TimedCalls("_record_poses")
+        select_dev = TimedCalls("select_instances_device")
         drivers = [("infer", per_object)] + [(f"infer_batched({int(n)})", batched(int(n))) for n in args.batches.split(",")]
-        for label, run in drivers:
+
+        def measure(label, run, tag=""):
             for phase in ("warmup", "timed"):
-                out_dir = os.path.join(root, "out", label.replace("(", "_").replace(")", ""), phase)
+                out_dir = os.path.join(root, "out", label.replace("(", "_").replace(")", "").replace(", ", "_") + tag, phase)
                 timer = TimedFrames()
-                select.seconds = record.seconds = 0.0
+                select.seconds = record.seconds = select_dev.seconds = 0.0
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 run(out_dir, timer)
@@ -167,8 +175,28 @@ def main():
                  "frame_loading_s": timer.seconds, "frames_loaded": timer.frames, "detections_per_s_without_loading": n_det / (wall - timer.seconds),
                  "select_instances_s": select.seconds, "record_poses_s": record.seconds,
                  "stage_means_ms": {k: 1e3 * v for k, v in means.items()}}
-            report["runs"].append(r)
+            if select_dev.seconds:   # a device_masks run: the selection ran in select_instances_device (select_instances is not called there)
+                r["select_instances_device_s"] = select_dev.seconds
             print(json.dumps(r), flush=True)
+            return r
+        for label, run in drivers:
+            report["runs"].append(measure(label, run))
+        if args.device_masks:
+            n = int(args.batches.split(",")[0])
+            runs = []
+            for rep_no in (0, 1):
+                for label, kw in ((f"infer_batched({n})", {}), (f"infer_batched({n}, device_masks)", {"device_masks": True})):
+                    r = measure(label, batched(n, **kw), tag=f"_rep{rep_no}")
+                    r["repeat"] = rep_no
+                    runs.append(r)
+            summary = {}
+            for path, key in (("host", "select_instances_s"), ("device", "select_instances_device_s")):
+                mine = [r for r in runs if ("device_masks" in r["driver"]) == (path == "device")]
+                summary[path] = {out: {"mean": float(np.mean([r[k] for r in mine])), "spread": float(abs(mine[0][k] - mine[1][k]))}
+                                 for out, k in (("select_s", key), ("record_poses_s", "record_poses_s"), ("wall_s", "wall_s"), ("detections_per_s", "detections_per_s"))}
+            summary["device_over_host"] = {k: summary["device"][k]["mean"] / summary["host"][k]["mean"] for k in summary["host"]}
+            report["device_masks"] = {"runs": runs, "summary": summary}
+            print(json.dumps(summary), flush=True)
     base = report["runs"][0]["detections_per_s"]
     report["speedup_vs_infer"] = {r["driver"]: r["detections_per_s"] / base for r in report["runs"][1:]}
     print(json.dumps(report["speedup_vs_infer"]))
