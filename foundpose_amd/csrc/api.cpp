@@ -331,6 +331,37 @@ int fp_detection_masks(const int32_t* counts, const int32_t* run_off, int num_ru
   return launch_detection_masks(a, num_det, open3x3, ST(stream));
 }
 
+int fp_pose_overlap(const float* points, int num_points, const int32_t* point_ranges, const double* centers, const double* radii,
+                    int num_objects, const int32_t* pose_obj, const int32_t* valid, const double* R, const double* t, int num_poses,
+                    const int32_t* pairs, int num_pairs, int grid, int32_t* out_counts, double* out_overlap, int32_t* out_status,
+                    fp_stream_t stream) {
+  FP_REQUIRE(num_pairs >= 0 && num_poses >= 0 && num_objects >= 0, "fp_pose_overlap: negative count");
+  if (num_pairs == 0) return FP_OK;
+  FP_REQUIRE(point_ranges && centers && radii && pose_obj && valid && R && t && pairs && out_counts && out_overlap && out_status,
+             "fp_pose_overlap: null pointer");
+  FP_REQUIRE(points || num_points == 0, "fp_pose_overlap: null points");
+  PoseOverlapArgs a;
+  memset(&a, 0, sizeof(a));
+  a.points = points; a.m_total = num_points; a.ranges = point_ranges; a.center = centers; a.radius = radii; a.n_objects = num_objects;
+  a.pose_obj = pose_obj; a.valid = valid; a.R = R; a.t = t; a.n_poses = num_poses; a.pairs = pairs; a.grid = grid;
+  a.counts = out_counts; a.overlap = out_overlap; a.status = out_status;
+  return launch_pose_overlap(a, num_pairs, ST(stream));
+}
+
+int fp_pose_nms_greedy(const int32_t* group_off, const int32_t* pair_off, int num_groups, const int32_t* pairs, const double* overlap,
+                       const int32_t* status, int num_poses, int num_pairs, double thresh, int32_t* out_keep, int32_t* out_suppressed_by,
+                       fp_stream_t stream) {
+  FP_REQUIRE(num_groups >= 0 && num_poses >= 0 && num_pairs >= 0, "fp_pose_nms_greedy: negative count");
+  if (num_groups == 0) return FP_OK;
+  FP_REQUIRE(group_off && pair_off && out_keep && out_suppressed_by, "fp_pose_nms_greedy: null pointer");
+  FP_REQUIRE((pairs && overlap && status) || num_pairs == 0, "fp_pose_nms_greedy: null pairs / overlap / status");
+  PoseNmsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.group_off = group_off; a.pair_off = pair_off; a.pairs = pairs; a.overlap = overlap; a.status = status; a.thresh = thresh;
+  a.n_poses = num_poses; a.n_pairs = num_pairs; a.keep = out_keep; a.suppressed_by = out_suppressed_by;
+  return launch_pose_nms_greedy(a, num_groups, ST(stream));
+}
+
 // ------------------------------------------------------------------ ViT building blocks
 int fp_patchify(const float* images, int B, int H, int W, int patch, void* out, int ld_out, int out_dtype,
                 fp_stream_t stream) {

@@ -473,3 +473,39 @@ struct DetMaskArgs {
   int tiles_x, tiles_y;    // filled in by the launcher
 };
 int launch_detection_masks(DetMaskArgs a, int num_det, int open3x3, hipStream_t st);
+
+// ---------------------------------------------------------------- pose_nms.hip
+constexpr int PN_MIN_GRID = 8, PN_MAX_GRID = 32;  // the side of the occupancy grid: at most 32^3 bits = 4 KB of LDS
+constexpr int PN_MAX_GROUP = 256;                 // poses of one frame: one thread each
+struct PoseOverlapArgs {
+  const float* points;     // [m_total, 3] the compact samples of all objects
+  int m_total;
+  const int* ranges;       // [objects, 2] each object in `points`: [begin, end), clamped to [0, m_total]
+  const double* center;    // [objects, 3] centre of the object's sample
+  const double* radius;    // [objects] its radius about that centre
+  int n_objects;
+  const int* pose_obj;     // [poses] the pose's object
+  const int* valid;        // [poses] > 0: the pose takes part
+  const double* R;         // [poses, 9] row-major model -> the frame's common coordinates
+  const double* t;         // [poses, 3]
+  int n_poses;
+  const int* pairs;        // [pairs, 2] (i, j): how much of i's sample lies in j's occupied cells
+  int grid;
+  int* counts;             // [pairs, 2] n_in, n_cells
+  double* overlap;         // [pairs] n_in / n_i
+  int* status;             // [pairs] 0 scored, 1 disjoint spheres, 2 skipped
+};
+int launch_pose_overlap(const PoseOverlapArgs& a, int num_pairs, hipStream_t st);
+
+struct PoseNmsArgs {
+  const int* group_off;    // [groups + 1] the poses of each frame, in rank order
+  const int* pair_off;     // [groups + 1] the pairs of each frame
+  const int* pairs;        // [n_pairs, 2] pose indices
+  const double* overlap;   // [n_pairs]
+  const int* status;       // [n_pairs] 0: the overlap counts
+  double thresh;
+  int n_poses, n_pairs;
+  int* keep;               // [n_poses] 1 kept, 0 suppressed
+  int* suppressed_by;      // [n_poses] the pose that suppressed it, or -1
+};
+int launch_pose_nms_greedy(const PoseNmsArgs& a, int num_groups, hipStream_t st);

@@ -16,6 +16,7 @@ same poses; --device-masks with it makes the detections' 
 
 import argparse
 import json
+import math
 import os
 import time
 from typing import Any, Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
@@ -23,7 +24,7 @@ from typing import Any, Dict, Iterable, List, NamedTuple, Optional, Sequence, Tu
 import numpy as np
 import torch
 
-from . import crop_util, engine as fe, eval_util, feature_util, infer_pose_util, pnp_util, refine_util, repre_util, vis_util
+from . import crop_util, engine as fe, eval_bop19, eval_util, feature_util, infer_pose_util, pnp_util, pose_nms, refine_util, repre_util, vis_util
 from .bank import DeviceBank
 
 
@@ -69,6 +70,11 @@ class InferOpts(NamedTuple):
     depth_verify_max_points: int = 16384   # ... and the number of model points placed at each hypothesis, at most
     mask_verify_grid: int = 64             # coarse_select_type="mask_verify": the side G of the silhouette's cell grid, in [8, 128]
     mask_verify_max_points: int = 16384    # ... and the number of model points placed at each hypothesis, at most
+    frame_select_type: str = "none"        # what is done with the poses of a frame TOGETHER once all are estimated: "none" or "pose_nms" (duplicate poses suppressed by their 3D overlap)
+    pose_nms_thresh: float = 0.3           # frame_select_type="pose_nms": two poses conflict when either's sample lies in the other's occupied cells by this fraction, in (0, 1]
+    pose_nms_grid: int = 16                # ... the side G of the occupancy grid over the model's bounding sphere, in [8, 32]
+    pose_nms_max_points: int = 4096        # ... the number of model points of each sample, at most
+    pose_nms_cross_object: bool = False    # ... compare poses of different objects too
 
 
 FINAL_POSE_TYPES = ("best_coarse", "featuremetric", "depth", "featuremetric_depth")
@@ -78,6 +84,7 @@ DEPTH_PNP_TYPES = ("kabsch_depth",)   # the coarse poses are solved on the frame
 COARSE_SELECT_TYPES = ("inliers", "depth_verify", "mask_verify")
 DEPTH_SELECT_TYPES = ("depth_verify",)   # the coarse hypotheses are checked against the frame's "depth" (pnp_util.verify_poses_depth)
 MASK_SELECT_TYPES = ("mask_verify",)     # ... against the detection's own mask (pnp_util.verify_poses_mask): no depth
+FRAME_SELECT_TYPES = ("none", "pose_nms")
 
 
 def load_opts(path_or_dict) -> InferOpts:
@@ -119,6 +126,18 @@ def _check_driver_opts(opts: InferOpts):
         raise ValueError(f"mask_verify_grid must be an integer in [{pnp_util.VERIFY_MIN_GRID}, {pnp_util.VERIFY_MAX_GRID}], got {opts.mask_verify_grid!r}")
     if isinstance(opts.mask_verify_max_points, bool) or not isinstance(opts.mask_verify_max_points, int) or opts.mask_verify_max_points < 1:
         raise ValueError(f"mask_verify_max_points must be an integer >= 1, got {opts.mask_verify_max_points!r}")
+    if opts.frame_select_type not in FRAME_SELECT_TYPES:
+        raise ValueError(f"Unknown frame select type '{opts.frame_select_type}' (one of {', '.join(FRAME_SELECT_TYPES)})")
+    if isinstance(opts.pose_nms_thresh, bool) or not isinstance(opts.pose_nms_thresh, (int, float)) \
+            or not (math.isfinite(opts.pose_nms_thresh) and 0 < opts.pose_nms_thresh <= 1):
+        raise ValueError(f"pose_nms_thresh must be a finite number in (0, 1], got {opts.pose_nms_thresh!r}")
+    if isinstance(opts.pose_nms_grid, bool) or not isinstance(opts.pose_nms_grid, int) \
+            or not pose_nms.MIN_GRID <= opts.pose_nms_grid <= pose_nms.MAX_GRID:
+        raise ValueError(f"pose_nms_grid must be an integer in [{pose_nms.MIN_GRID}, {pose_nms.MAX_GRID}], got {opts.pose_nms_grid!r}")
+    if isinstance(opts.pose_nms_max_points, bool) or not isinstance(opts.pose_nms_max_points, int) or opts.pose_nms_max_points < 1:
+        raise ValueError(f"pose_nms_max_points must be an integer >= 1, got {opts.pose_nms_max_points!r}")
+    if not isinstance(opts.pose_nms_cross_object, bool):
+        raise ValueError(f"pose_nms_cross_object must be true or false, got {opts.pose_nms_cross_object!r}")
     # the best coarse pose refined on the projected feature map (refine_util): the engine keeps the map
     refine = opts.final_pose_type in ("featuremetric", "featuremetric_depth") + JOINT_POSE_TYPES
     if refine and (not isinstance(opts.refine_iters, int) or opts.refine_iters < 0):
@@ -495,6 +514,27 @@ def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBase
     return evaluator
 
 
+def _select_frame_poses(opts: InferOpts, repres: Dict[int, repre_util.FeatureBasedObjectRepre], lids: Sequence[int], csv_path: str) -> List[str]:
+    """frame_select_type "pose_nms" (DESIGN.md section 20), after the per-object estimated-poses.json files and the csv of every pose are
+    written: the poses of each frame compared with each other (pose_nms.suppress_duplicates, samples from the repres' vertices), the csv
+    written again with the kept rows only -- the stage's wall time, divided equally over the images that have rows, added to their `time`
+    -- and every row's decision written to pose-nms.json beside it.  -> the paths written besides the csv."""
+    _check_driver_opts(opts)
+    rows = eval_bop19.load_results_csv(csv_path)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    samples = pose_nms.samples_from_vertices({lid: repres[lid].vertices for lid in lids}, opts.pose_nms_max_points)
+    result = pose_nms.suppress_duplicates(rows, samples, opts.pose_nms_thresh, opts.pose_nms_grid, opts.pose_nms_cross_object)
+    torch.cuda.synchronize()
+    images = {(r["scene_id"], r["im_id"]) for r in rows}
+    share = (time.perf_counter() - t0) / max(len(images), 1)
+    pose_nms.write_results_csv(csv_path, [dict(r, time=r["time"] + share) for i, r in enumerate(rows) if result["keep"][i]])
+    path = os.path.join(os.path.dirname(csv_path), "pose-nms.json")
+    with open(path, "w") as f:
+        json.dump(pose_nms.decision_records(rows, result), f, indent=1)
+    return [path]
+
+
 def infer(opts: InferOpts, frames_by_object, detections, repres: Dict[int, repre_util.FeatureBasedObjectRepre], output_dir: str, extractor=None,
           precision: str = "bf16", num_target_insts: Optional[Dict[int, Dict[Tuple[int, int], int]]] = None, weights: Optional[str] = None,
           eval_models: Optional[Dict[int, eval_util.EvalModel]] = None, renderer=None) -> List[str]:
@@ -527,6 +567,8 @@ def infer(opts: InferOpts, frames_by_object, detections, repres: Dict[int, repre
             paths.append(p)
     if opts.save_estimates:
         paths.append(eval_util.prepare_bop_submission(output_dir, opts.object_dataset, lids))
+        if opts.frame_select_type == "pose_nms":
+            paths.extend(_select_frame_poses(opts, repres, lids, paths[-1]))
     if renderer is not None and frame_poses:   # the frames are read again rather than kept: one image in memory at a time
         done = set()
         for lid in lids:
@@ -727,6 +769,8 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
             evaluators[o].save_results_json(p)
             paths.append(p)
         paths.append(eval_util.prepare_bop_submission(output_dir, opts.object_dataset, lids))
+        if opts.frame_select_type == "pose_nms":
+            paths.extend(_select_frame_poses(opts, repres, lids, paths[-1]))
     return paths
 
 

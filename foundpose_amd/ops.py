@@ -439,3 +439,44 @@ def detection_masks(counts: torch.Tensor, run_off: torch.Tensor, canvas_hw: Tupl
     call("fp_detection_masks", ptr(counts), ptr(run_off), int(counts.shape[0]), n, hc, wc, h, w, int(bool(open3x3)), ptr(prefix), ptr(masks), ptr(area),
          stream())
     return masks, area
+
+
+def pose_overlap(points: torch.Tensor, ranges: torch.Tensor, centers: torch.Tensor, radii: torch.Tensor, pose_obj: torch.Tensor,
+                 valid: torch.Tensor, R: torch.Tensor, t: torch.Tensor, pairs: torch.Tensor, grid: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fp_pose_overlap on device tables that have been validated already (pose_nms.pose_overlaps checks them on the
+    host before it uploads them): points f32 [M, 3], ranges int32 [O, 2], centers f64 [O, 3], radii f64 [O], pose_obj / valid int32 [N],
+    R f64 [N, 9] or [N, 3, 3], t f64 [N, 3], pairs int32 [P, 2].  -> (counts int32 [P, 2], overlap f64 [P], status int32 [P])."""
+    require_cuda(points, ranges, centers, radii, pose_obj, valid, R, t, pairs)
+    for x, dt in ((points, torch.float32), (ranges, torch.int32), (centers, torch.float64), (radii, torch.float64), (pose_obj, torch.int32),
+                  (valid, torch.int32), (R, torch.float64), (t, torch.float64), (pairs, torch.int32)):
+        if x.dtype != dt or not x.is_contiguous():
+            raise ValueError(f"pose_overlap: a contiguous {dt} table is needed, got {x.dtype}{'' if x.is_contiguous() else ' (strided)'}")
+    O, N, P = int(ranges.shape[0]), int(pose_obj.shape[0]), int(pairs.shape[0])
+    if centers.numel() != 3 * O or radii.numel() != O or valid.numel() != N or R.numel() != 9 * N or t.numel() != 3 * N or pairs.numel() != 2 * P:
+        raise ValueError("pose_overlap: table sizes do not match")
+    dev = points.device
+    counts = torch.empty(P, 2, dtype=torch.int32, device=dev)
+    overlap = torch.empty(P, dtype=torch.float64, device=dev)
+    status = torch.empty(P, dtype=torch.int32, device=dev)
+    call("fp_pose_overlap", ptr(points), int(points.shape[0]), ptr(ranges), ptr(centers), ptr(radii), O, ptr(pose_obj), ptr(valid), ptr(R), ptr(t), N,
+         ptr(pairs), P, int(grid), ptr(counts), ptr(overlap), ptr(status), stream())
+    return counts, overlap, status
+
+
+def pose_nms_greedy(group_off: torch.Tensor, pair_off: torch.Tensor, pairs: torch.Tensor, overlap: torch.Tensor, status: torch.Tensor,
+                    num_poses: int, thresh: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp_pose_nms_greedy on device tables validated already (pose_nms.nms_greedy): group_off / pair_off int32
+    [F + 1], pairs int32 [P, 2], overlap f64 [P], status int32 [P].  -> (keep int32 [num_poses], suppressed_by int32 [num_poses]); a pose
+    of no frame is kept."""
+    require_cuda(group_off, pair_off, pairs, overlap, status)
+    for x, dt in ((group_off, torch.int32), (pair_off, torch.int32), (pairs, torch.int32), (overlap, torch.float64), (status, torch.int32)):
+        if x.dtype != dt or not x.is_contiguous():
+            raise ValueError(f"pose_nms_greedy: a contiguous {dt} table is needed, got {x.dtype}{'' if x.is_contiguous() else ' (strided)'}")
+    F, P = int(group_off.shape[0]) - 1, int(overlap.shape[0])
+    if F < 0 or int(pair_off.shape[0]) != F + 1 or pairs.numel() != 2 * P or status.numel() != P:
+        raise ValueError("pose_nms_greedy: table sizes do not match")
+    keep = torch.ones(num_poses, dtype=torch.int32, device=overlap.device)
+    by = torch.full((num_poses,), -1, dtype=torch.int32, device=overlap.device)
+    call("fp_pose_nms_greedy", ptr(group_off), ptr(pair_off), F, ptr(pairs), ptr(overlap), ptr(status), int(num_poses), P, float(thresh), ptr(keep), ptr(by),
+         stream())
+    return keep, by

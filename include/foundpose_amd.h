@@ -289,6 +289,46 @@ int fp_pose_verify_mask(const int32_t* success, const double* R, const double* t
 int fp_detection_masks(const int32_t* counts, const int32_t* run_off, int num_runs, int num_det, int hc, int wc, int H, int W, int open3x3,
                        int32_t* scratch_prefix, uint8_t* out_masks, int32_t* out_area, fp_stream_t stream);
 
+/* Duplicate suppression between the poses of one frame (this project's own stage), first half: for every ordered
+ * pair (i, j) = pairs[p] of poses given in ONE common coordinate frame, the fraction of i's model sample that lies in space occupied by j's
+ * model.  points [num_points, 3] f32, point_ranges [num_objects, 2] ([begin, end), clamped to [0, num_points]), centers [num_objects, 3]
+ * and radii [num_objects] f64: the compact samples fp_pose_verify_depth uses, per OBJECT here; pose_obj [num_poses] int32: each pose's
+ * object; valid [num_poses] int32 (> 0: the pose takes part); R [num_poses, 9] row-major and t [num_poses, 3] f64; pairs [num_pairs, 2]
+ * int32.  All arithmetic is fp64, every step one rounded operation in this order (no FMA contraction), products summed k ascending:
+ *   skip: status 2 if either pose is not valid, either point range is empty or !(rho_j > 0);
+ *   spheres: C_p = R_p c_p + t_p (fp_pose_verify_depth's order), d2 = ((dx dx + dy dy) + dz dz) of C_i - C_j, s = rho_i + rho_j; status 1
+ *     if !(d2 <= s s) (disjoint spheres, or a NaN): no point is read;
+ *   grid of j in j's own model frame: x0 = c_j - rho_j per axis, h = 2 rho_j / G;
+ *   pass 1: every point x of j's sample sets bit (iz G + iy) G + ix of a bitmap, per axis i = (int) fmin(fmax(floor((x - x0) / h), 0),
+ *     G - 1) (fmax / fmin drop a NaN: cell 0);
+ *   pass 2: every point x of i's sample: X = R_i x + t_i, d = X - t_j, y_k = (R_j[0,k] d_0 + R_j[1,k] d_1) + R_j[2,k] d_2, q_k =
+ *     floor((y_k - x0_k) / h) without a clamp; the point is inside the cube iff 0 <= q_k < G on all three axes, decided in fp64 before
+ *     any conversion to an integer; n_in counts the inside points whose cell's bit is set.
+ * out_counts [num_pairs, 2] = (n_in, n_cells = set bits of the bitmap); out_overlap [num_pairs] f64 = n_in / n_i, one division of two
+ * integers converted to double, n_i the number of points of i's sample; out_status [num_pairs]: 0 scored, 1 disjoint spheres, 2 skipped
+ * (counts and overlap 0 for both).  grid G in [8, 32].  The caller validates pose_obj and pairs (device arrays the entry point cannot
+ * read); an index outside its table that arrives all the same gives status 2 and nothing is read through it.  A pair's result depends on
+ * its own data only: it is the same bits alone, in any batch and at any position.  (Added without a change of FP_ABI_VERSION: no existing
+ * entry point changed.) */
+int fp_pose_overlap(const float* points, int num_points, const int32_t* point_ranges, const double* centers, const double* radii,
+                    int num_objects, const int32_t* pose_obj, const int32_t* valid, const double* R, const double* t, int num_poses,
+                    const int32_t* pairs, int num_pairs, int grid, int32_t* out_counts, double* out_overlap, int32_t* out_status,
+                    fp_stream_t stream);
+
+/* ... second half: greedy suppression per frame.  group_off [num_groups + 1] int32: frame g owns the poses [group_off[g], group_off[g + 1]),
+ * at most 256 of them, laid out IN RANK ORDER (the caller sorts by score descending, equal scores in input order); pair_off
+ * [num_groups + 1] int32: frame g owns the pairs [pair_off[g], pair_off[g + 1]) of pairs [num_pairs, 2] (pose indices in that layout),
+ * overlap [num_pairs] f64 and status [num_pairs] int32 (the three as the first half takes and writes them).  Poses a and b of a frame
+ * conflict iff some pair (a, b) or (b, a) has status 0 and overlap >= thresh.  For r = 0, 1, ...: if the pose of rank r is still alive,
+ * every alive pose of a later rank that conflicts with it is suppressed by it.  out_keep [num_poses] int32 (1 kept, 0 suppressed);
+ * out_suppressed_by [num_poses] int32: the pose index of the suppressor (the first kept pose in rank order that conflicts), -1 for a kept
+ * pose.  An empty frame and a frame of one pose are legal; offsets are clamped to their arrays and a frame to 256 poses (the caller
+ * refuses larger ones); a pair that names a pose outside its frame is ignored.  Only poses of some frame are written.  (Added without a
+ * change of FP_ABI_VERSION.) */
+int fp_pose_nms_greedy(const int32_t* group_off, const int32_t* pair_off, int num_groups, const int32_t* pairs, const double* overlap,
+                       const int32_t* status, int num_poses, int num_pairs, double thresh, int32_t* out_keep, int32_t* out_suppressed_by,
+                       fp_stream_t stream);
+
 /* sample_feature_map_at_points (utils/feature_util.py:100-131): bilinear grid_sample, zeros padding,
  * align_corners=False.  fmap addressed by element strides (image, channel, y, x); point_img (may be null)
  * maps each point to its image.  out [num_points, C]. */
