@@ -64,6 +64,8 @@ _PROTOS = {
     "fp_pose_verify_mask": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "fp_pose_overlap": [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp],
     "fp_pose_nms_greedy": [vp, vp, i32, vp, vp, vp, i32, i32, f64, vp, vp, vp],
+    "fp_detection_match": [vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp],
+    "fp_detection_ap": [vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp],
     "fp_detection_masks": [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "fp_sample_bilinear": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp],
     "fp_pca_project": [vp, i32, i32, vp, i32, vp, vp, vp],

@@ -362,6 +362,37 @@ int fp_pose_nms_greedy(const int32_t* group_off, const int32_t* pair_off, int nu
   return launch_pose_nms_greedy(a, num_groups, ST(stream));
 }
 
+int fp_detection_match(const int32_t* est_off, const int32_t* gt_off, const int32_t* pair_off, int num_groups, const double* err,
+                       int num_pairs, const int32_t* gt_valid, int num_gt, const int32_t* group_tab, const double* ths, int num_tabs,
+                       int num_ths, int num_est, int8_t* out_flag, int32_t* out_matched_gt, fp_stream_t stream) {
+  FP_REQUIRE(num_groups >= 0 && num_pairs >= 0 && num_gt >= 0 && num_est >= 0 && num_tabs >= 0, "fp_detection_match: negative count");
+  if (num_groups == 0) return FP_OK;
+  FP_REQUIRE(est_off && gt_off && pair_off && group_tab && ths, "fp_detection_match: null pointer");
+  FP_REQUIRE((out_flag && out_matched_gt) || num_est == 0, "fp_detection_match: null output");
+  FP_REQUIRE(err || num_pairs == 0, "fp_detection_match: null err");
+  FP_REQUIRE(gt_valid || num_gt == 0, "fp_detection_match: null gt_valid");
+  DetMatchArgs a;
+  memset(&a, 0, sizeof(a));
+  a.est_off = est_off; a.gt_off = gt_off; a.pair_off = pair_off; a.err = err; a.gt_valid = gt_valid; a.group_tab = group_tab; a.ths = ths;
+  a.n_groups = num_groups; a.n_est = num_est; a.n_gt = num_gt; a.n_pairs = num_pairs; a.n_tab = num_tabs; a.T = num_ths;
+  a.flag = (signed char*)out_flag; a.matched_gt = out_matched_gt;
+  return launch_detection_match(a, ST(stream));
+}
+
+int fp_detection_ap(const int32_t* obj_off, int num_objects, const int32_t* order, int num_order, const int8_t* flag, int num_est,
+                    int num_ths, const int32_t* n_valid, const double* rec_thr, int num_rec, double* out_ap, double* out_q,
+                    int32_t* out_totals, fp_stream_t stream) {
+  FP_REQUIRE(num_objects >= 0 && num_order >= 0 && num_est >= 0, "fp_detection_ap: negative count");
+  if (num_objects == 0) return FP_OK;
+  FP_REQUIRE(obj_off && n_valid && rec_thr && out_ap && out_q && out_totals, "fp_detection_ap: null pointer");
+  FP_REQUIRE((order && flag) || num_order == 0, "fp_detection_ap: null order / flag");
+  DetApArgs a;
+  memset(&a, 0, sizeof(a));
+  a.obj_off = obj_off; a.order = order; a.flag = (const signed char*)flag; a.n_valid = n_valid; a.rec_thr = rec_thr;
+  a.n_order = num_order; a.n_est = num_est; a.T = num_ths; a.R = num_rec; a.ap = out_ap; a.q = out_q; a.totals = out_totals;
+  return launch_detection_ap(a, num_objects, ST(stream));
+}
+
 // ------------------------------------------------------------------ ViT building blocks
 int fp_patchify(const float* images, int B, int H, int W, int patch, void* out, int ld_out, int out_dtype,
                 fp_stream_t stream) {

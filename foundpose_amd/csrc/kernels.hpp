@@ -509,3 +509,35 @@ struct PoseNmsArgs {
   int* suppressed_by;      // [n_poses] the pose that suppressed it, or -1
 };
 int launch_pose_nms_greedy(const PoseNmsArgs& a, int num_groups, hipStream_t st);
+
+// ---------------------------------------------------------------- detection_ap.hip
+constexpr int DA_THREADS = 256;        // a workgroup: 4 (group, column) waves of the matching, one (object, column) of the AP
+constexpr int DA_MAX_GROUP_GT = 256;   // GT instances of one (image, object): 4 per lane
+constexpr int DA_MAX_THS = 16;         // thresholds per error type
+constexpr int DA_MAX_REC = 128;        // recall thresholds: one thread each
+struct DetMatchArgs {
+  const int* est_off;      // [groups + 1] the estimates of each group, in rank order
+  const int* gt_off;       // [groups + 1] its GT instances
+  const int* pair_off;     // [groups + 1] its rows of err: E_g x G_g, row-major
+  const double* err;       // [n_pairs, 2] (mssd, mspd), what fp_pose_errors wrote
+  const int* gt_valid;     // [n_gt] > 0: a valid GT
+  const int* group_tab;    // [groups] the group's row of ths
+  const double* ths;       // [n_tab, 2, T]
+  int n_groups, n_est, n_gt, n_pairs, n_tab, T;
+  signed char* flag;       // [n_est, 2 T] 1 true positive, 0 false positive, 2 ignored
+  int* matched_gt;         // [n_est, 2 T] the group-local GT index or -1
+};
+int launch_detection_match(const DetMatchArgs& a, hipStream_t st);
+
+struct DetApArgs {
+  const int* obj_off;      // [objects + 1] each object's stretch of order
+  const int* order;        // [n_order] rows of flag, per object in global rank order
+  const signed char* flag; // [n_est, 2 T]
+  const int* n_valid;      // [objects] valid GT instances over all target images
+  const double* rec_thr;   // [R]
+  int n_order, n_est, T, R;
+  double* ap;              // [objects, 2 T]
+  double* q;               // [objects, 2 T, R] the interpolated precision at each recall threshold
+  int* totals;             // [objects, 2 T, 3] tp, fp, ignored
+};
+int launch_detection_ap(const DetApArgs& a, int num_objects, hipStream_t st);

@@ -167,11 +167,18 @@ def _inlier_ratio(corr_dist: np.ndarray, ids: np.ndarray, radius: float):
 
 
 def pose_errors_batch(items: Sequence[Dict[str, Any]], device: str = "cuda"):
+    """pose_errors_device read back: -> (err [H, 2] numpy = (mssd, mspd), idx [H, 4] numpy int = (mssd vertex, mssd sym, mspd vertex, mspd
+    sym))."""
+    err, idx = pose_errors_device(items, device)
+    return err.cpu().numpy(), idx.cpu().numpy().astype(np.int64)
+
+
+def pose_errors_device(items: Sequence[Dict[str, Any]], device: str = "cuda"):
     """MSSD / MSPD of several hypotheses in ONE fp_pose_errors launch.  Each item: R_est, t_est, R_gt, t_gt (model ->
     original camera), K (3x3), pts (the mesh vertices, numpy fp64 or a device tensor), syms (list of {"R", "t"}).
     Objects shared by several items are uploaded once.  The symmetry stack of each item is composed on the host,
     vectorised: R_gt_sym = R_gt S_R, t_gt_sym = R_gt S_t + t_gt (eval_errors.py:22-23), P = K [R | t] (project_pts).
-    -> (err [H, 2] numpy = (mssd, mspd), idx [H, 4] numpy int = (mssd vertex, mssd sym, mspd vertex, mspd sym))."""
+    -> (err [H, 2] fp64 = (mssd, mspd), idx [H, 4] int32 = (mssd vertex, mssd sym, mspd vertex, mspd sym)), both left on the device."""
     import torch
     from . import ops
     pts_keys, pts_list, pts_off = {}, [], 0
@@ -208,7 +215,7 @@ def pose_errors_batch(items: Sequence[Dict[str, Any]], device: str = "cuda"):
     pts_d = torch.cat([dev(p).reshape(-1, 3) for p in pts_list])
     err, idx = ops.pose_errors(pts_d, dev(np.stack(est)), dev(np.stack(p_est)), dev(np.concatenate(gt_rows)), dev(np.concatenate(pgt_rows)),
                                np.array(ranges, np.int64))
-    return err.cpu().numpy(), idx.cpu().numpy().astype(np.int64)
+    return err, idx
 
 
 class PoseEvaluator:

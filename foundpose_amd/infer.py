@@ -12,6 +12,9 @@ estimated pose and one summary per frame; the HTML branches are not part of this
 
 --batch-detections N (N >= 1) runs infer_batched instead: one pass over the images, N detections per batch across frames and objects, the
 same poses; --device-masks with it makes the detections' masks on the device instead of on the host (section 19).
+
+"task": "detection" in the options runs the BOP24 6D detection task instead of 6D localization (section 21): the targets (default
+test_targets_bop24.json) name images only, and every detection of every object gets a pose; eval_bop24 scores the csv.
 """
 
 import argparse
@@ -75,6 +78,9 @@ class InferOpts(NamedTuple):
     pose_nms_grid: int = 16                # ... the side G of the occupancy grid over the model's bounding sphere, in [8, 32]
     pose_nms_max_points: int = 4096        # ... the number of model points of each sample, at most
     pose_nms_cross_object: bool = False    # ... compare poses of different objects too
+    task: str = "localization"             # "localization": the targets say how many instances each (image, object) has and num_preds_factor x that many detections get a pose; "detection": the targets name images only and every detection of every object gets one (BOP24 6D detection)
+    detection_min_score: float = 0.0       # task="detection": detections scored below this get no pose
+    detection_max_per_object: int = 16     # ... and at most this many of one (image, object), best first; >= 1
 
 
 FINAL_POSE_TYPES = ("best_coarse", "featuremetric", "depth", "featuremetric_depth")
@@ -85,6 +91,7 @@ COARSE_SELECT_TYPES = ("inliers", "depth_verify", "mask_verify")
 DEPTH_SELECT_TYPES = ("depth_verify",)   # the coarse hypotheses are checked against the frame's "depth" (pnp_util.verify_poses_depth)
 MASK_SELECT_TYPES = ("mask_verify",)     # ... against the detection's own mask (pnp_util.verify_poses_mask): no depth
 FRAME_SELECT_TYPES = ("none", "pose_nms")
+TASKS = ("localization", "detection")
 
 
 def load_opts(path_or_dict) -> InferOpts:
@@ -138,6 +145,18 @@ def _check_driver_opts(opts: InferOpts):
         raise ValueError(f"pose_nms_max_points must be an integer >= 1, got {opts.pose_nms_max_points!r}")
     if not isinstance(opts.pose_nms_cross_object, bool):
         raise ValueError(f"pose_nms_cross_object must be true or false, got {opts.pose_nms_cross_object!r}")
+    if opts.task not in TASKS:
+        raise ValueError(f"Unknown task '{opts.task}' (one of {', '.join(TASKS)})")
+    if isinstance(opts.detection_min_score, bool) or not isinstance(opts.detection_min_score, (int, float)) or not math.isfinite(opts.detection_min_score):
+        raise ValueError(f"detection_min_score must be a finite number, got {opts.detection_min_score!r}")
+    if isinstance(opts.detection_max_per_object, bool) or not isinstance(opts.detection_max_per_object, int) or opts.detection_max_per_object < 1:
+        raise ValueError(f"detection_max_per_object must be an integer >= 1, got {opts.detection_max_per_object!r}")
+    if opts.task == "detection":
+        if opts.num_preds_factor != 1.0:
+            raise ValueError(f"task 'detection' has no instance counts to multiply: num_preds_factor must be 1.0, got {opts.num_preds_factor!r} "
+                             f"(detection_max_per_object bounds the poses of an (image, object))")
+        if not opts.use_detections:
+            raise ValueError("task 'detection' estimates a pose for every detection: use_detections must be true")
     # the best coarse pose refined on the projected feature map (refine_util): the engine keeps the map
     refine = opts.final_pose_type in ("featuremetric", "featuremetric_depth") + JOINT_POSE_TYPES
     if refine and (not isinstance(opts.refine_iters, int) or opts.refine_iters < 0):
@@ -167,8 +186,18 @@ def _annotated(inst, eval_model) -> bool:
 
 def _frame_targets(opts: InferOpts, object_lid: int, frame: Dict[str, Any],
                    num_target_insts: Optional[Dict[Tuple[int, int], int]]) -> Optional[Tuple[List[Any], int]]:
-    """(the object's annotations in the frame, its number of target instances), or None when the frame is not one of this object's."""
+    """(the object's annotations in the frame, its number of target instances), or None when the frame is not one of this object's.
+    task "detection": a frame is every object's when the targets name it (or there are none); the count is not read (0 is returned) and a
+    frame whose annotations show none of this object goes on with an empty list -- a pose estimated there is a false positive that must
+    reach the csv."""
     scene_id, im_id = frame["scene_id"], frame["im_id"]
+    if opts.task == "detection":
+        if num_target_insts is not None and (scene_id, im_id) not in num_target_insts:
+            return None
+        annos = [a for a in (frame.get("gt_annos") or [])
+                 if getattr(a, "lid", object_lid) == object_lid and not np.isnan(getattr(a, "visibilities", 1.0))
+                 and getattr(a, "visibilities", 1.0) > opts.min_visibility]
+        return annos, 0
     # number of target instances (infer.py:308-321): from the test targets when given -- frames that are not a target of
     # this object, or whose count is 0, are skipped -- otherwise the number of ground-truth annotations of the frame
     # ground-truth annotations of this object that are sufficiently visible (infer.py:286-305): a frame that HAS annotations but
@@ -191,6 +220,28 @@ def _frame_targets(opts: InferOpts, object_lid: int, frame: Dict[str, Any],
     return object_annos, n_target
 
 
+def detection_predictions(opts: InferOpts, preds: Optional[Sequence[Dict[str, Any]]]) -> List[Dict[str, Any]]:
+    """task "detection": the detections of one (scene, image, object) that get a pose -- those with score >= detection_min_score, best first
+    (equal scores in file order), at most detection_max_per_object.  No instance count is involved."""
+    preds = preds or []
+    order = sorted((i for i in range(len(preds)) if preds[i]["score"] >= opts.detection_min_score), key=lambda i: preds[i]["score"], reverse=True)
+    return [preds[i] for i in order[:opts.detection_max_per_object]]
+
+
+def detection_targets(num_target_insts, lids: Sequence[int]) -> Optional[Dict[int, Dict[Tuple[int, int], int]]]:
+    """task "detection": the drivers' num_target_insts -- None, a collection of (scene_id, im_id), or the localization task's {lid:
+    {(scene_id, im_id): count}}, whose counts and object ids are not read -- as {lid: {(scene_id, im_id): 0}} with EVERY target image under
+    EVERY object of the run."""
+    if num_target_insts is None:
+        return None
+    if isinstance(num_target_insts, dict) and all(isinstance(v, dict) for v in num_target_insts.values()):
+        images = [k for v in num_target_insts.values() for k in v]
+    else:
+        images = list(num_target_insts)
+    images = list(dict.fromkeys((int(s), int(i)) for s, i in images))
+    return {lid: dict.fromkeys(images, 0) for lid in lids}
+
+
 def select_instances(opts: InferOpts, object_lid: int, frame: Dict[str, Any], detections: Dict[Any, Any],
                      num_target_insts: Optional[Dict[Tuple[int, int], int]], eval_model: Optional[eval_util.EvalModel],
                      detection_times: Dict[Tuple[int, int], float]) -> List[Tuple[int, Dict[str, Any]]]:
@@ -203,12 +254,18 @@ def select_instances(opts: InferOpts, object_lid: int, frame: Dict[str, Any], de
     if tgt is None:
         return []
     object_annos, n_target = tgt
+    if opts.task == "detection":   # the chosen detections stand in for the file's: get_instances_for_pose_estimation keeps all of them, in this order
+        chosen = detection_predictions(opts, detections.get((scene_id, im_id, object_lid)))
+        detections, max_num_preds = ({(scene_id, im_id, object_lid): chosen} if chosen else {}), len(chosen)
+    else:
+        max_num_preds = int(opts.num_preds_factor * n_target)
     instances = infer_pose_util.get_instances_for_pose_estimation(
-        scene_id, im_id, object_lid, opts.use_detections, detections, int(opts.num_preds_factor * n_target), object_annos,
-        (cam.width, cam.height))
+        scene_id, im_id, object_lid, opts.use_detections, detections, max_num_preds, object_annos, (cam.width, cam.height))
     kept = []
     for inst_j, inst in enumerate(instances):
         detection_times[(scene_id, im_id)] = inst.get("time", 0) if opts.use_detections else 0
+        if opts.task == "detection" and _annotated(inst, eval_model) and inst["gt_iou"] < 0.05:
+            inst = dict(inst, gt_anno=None)   # no annotation is this detection's: it is kept and recorded without one, not dropped
         # infer.py:770-777: a detection that hardly overlaps its ground-truth annotation is not evaluated (applied on the
         # evaluation path only: the annotation-free entries stay what they were)
         if opts.use_detections and _annotated(inst, eval_model) and infer_pose_util.mask_iou(inst["input_mask_modal"], inst["gt_anno"].masks_modal) < 0.05:
@@ -238,15 +295,19 @@ def select_instances_device(opts: InferOpts, lids: Sequence[int], frame: Dict[st
     for lid in lids:
         tgt = _frame_targets(opts, lid, frame, None if num_target_insts is None else num_target_insts.get(lid, {}))
         preds = None if tgt is None else detections.get((scene_id, im_id, lid))
+        if opts.task == "detection":
+            preds = detection_predictions(opts, preds) or None
         if preds is not None:
             annos_by_lid[lid] = tgt[0]
-            preds_by_lid[lid] = infer_pose_util._top_predictions(preds, int(opts.num_preds_factor * tgt[1]))
+            preds_by_lid[lid] = preds if opts.task == "detection" else infer_pose_util._top_predictions(preds, int(opts.num_preds_factor * tgt[1]))
     instances = infer_pose_util.instances_on_device(preds_by_lid, (cam.width, cam.height), annos_by_lid)
     kept = {lid: [] for lid in lids}
     for lid, insts in instances.items():
         eval_model = None if eval_models is None else eval_models.get(lid)
         for inst_j, inst in enumerate(insts):
             detection_times_by_lid[lid][(scene_id, im_id)] = inst.get("time", 0)
+            if opts.task == "detection" and _annotated(inst, eval_model) and inst["gt_iou"] < 0.05:
+                inst = dict(inst, gt_anno=None)
             if _annotated(inst, eval_model) and inst["gt_iou"] < 0.05:   # (gt_iou is mask_iou with the chosen annotation: one quotient of the same integers)
                 continue
             if inst["mask_area"] > cam.width * cam.height:
@@ -545,8 +606,14 @@ def infer(opts: InferOpts, frames_by_object, detections, repres: Dict[int, repre
     eval_models: {object lid: eval_util.EvalModel} -- evaluate the hypotheses of frames whose annotations carry a pose.
     renderer: a HipRasterizer holding the mesh of every object under its lid -- with opts.vis_results, one picture per estimated pose
     (<output_dir>/<lid>/<scene>_<im>_<lid>_<inst>_0.png) and, after all objects, one summary per frame (<output_dir>/vis/<scene>_<im>.png)
-    with every final pose in the frame's own camera.  Without it no picture is made and nothing else changes."""
+    with every final pose in the frame's own camera.  Without it no picture is made and nothing else changes.
+    opts.task "detection" (DESIGN.md section 21): num_target_insts only names the target images -- a collection of (scene_id, im_id), or
+    the dict above with its counts and object ids unread (detection_targets) -- and in each of them every detection of every object with
+    score >= detection_min_score gets a pose, at most detection_max_per_object per object; `frames_by_object(lid)` then yields every
+    target image."""
     lids = list(opts.object_lids) if opts.object_lids is not None else sorted(repres)
+    if opts.task == "detection":
+        num_target_insts = detection_targets(num_target_insts, lids)
     if renderer is not None and not opts.vis_results:
         print("vis_results is false in the options: no pictures are written")
         renderer = None
@@ -657,6 +724,8 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
     verify = opts.coarse_select_type in DEPTH_SELECT_TYPES
     mask_verify = opts.coarse_select_type in MASK_SELECT_TYPES
     lids = sorted(opts.object_lids) if opts.object_lids is not None else sorted(repres)
+    if opts.task == "detection":   # the targets name images only (infer()'s note): every target image under every object
+        num_target_insts = detection_targets(num_target_insts, lids)
     if extractor is None:
         extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
     bank = DeviceBank([repres[l] for l in lids])
@@ -851,7 +920,7 @@ def load_bop_frames(split_dir: str, targets: Sequence[Dict[str, int]], object_li
     with_depth: and "depth", float32 mm [H, W], from depth/<im:06d>.png and the frame's depth_scale (eval_bop19.load_depth)."""
     reader = _SplitReader(split_dir, with_gt, with_depth)
     for tgt in targets:
-        if tgt["obj_id"] == object_lid:
+        if tgt.get("obj_id", object_lid) == object_lid:   # an entry without obj_id (test_targets_bop24.json) is every object's
             yield reader.frame(tgt["scene_id"], tgt["im_id"])
 
 
@@ -871,7 +940,8 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--opts", required=True, help="options JSON ({'infer_opts': {...}}, e.g. the reference's configs/infer/lmo.json)")
     ap.add_argument("--dataset-dir", required=True, help="BOP split directory (<datasets>/<dataset>/<split>)")
-    ap.add_argument("--targets", default=None, help="test_targets_bop19.json (default: <dataset-dir>/../test_targets_bop19.json)")
+    ap.add_argument("--targets", default=None, help="test_targets_bop19.json (default: <dataset-dir>/../test_targets_bop19.json); with \"task\": "
+                    "\"detection\" in the options: test_targets_bop24.json (the default then), of which only scene_id / im_id are read")
     ap.add_argument("--detections", required=True, help="CNOS detections in the BOP format")
     ap.add_argument("--repre-dir", required=True, help="<output>/object_repre (repre.pth under <version>/<dataset>/<lid>/)")
     ap.add_argument("--output-dir", required=True)
@@ -901,14 +971,26 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
                   or opts.coarse_select_type in DEPTH_SELECT_TYPES)   # the depth pose / PnP / select types read depth/<im>.png beside every image
     # the checkpoint is resolved before anything else is read: a missing one must fail in seconds, not after the banks are loaded
     extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=args.precision, weights=args.weights)
-    with open(args.targets or os.path.join(os.path.dirname(os.path.abspath(args.dataset_dir)), "test_targets_bop19.json")) as f:
+    detection_task = opts.task == "detection"
+    with open(args.targets or os.path.join(os.path.dirname(os.path.abspath(args.dataset_dir)),
+                                           "test_targets_bop24.json" if detection_task else "test_targets_bop19.json")) as f:
         targets = json.load(f)
     detections = infer_pose_util.load_detections_in_bop_format(args.detections)
-    lids = opts.object_lids or sorted({t["obj_id"] for t in targets})
+    if detection_task:   # an image list: each image once, object ids and instance counts dropped; the objects come from the options or the detections
+        targets = [{"scene_id": s, "im_id": i} for s, i in dict.fromkeys((int(t["scene_id"]), int(t["im_id"])) for t in targets)]
+        lids = opts.object_lids or sorted({k[2] for k in detections})
+        if not lids:
+            ap.error("task 'detection': no object_lids in the options and no detection to take the objects from")
+    else:
+        lids = opts.object_lids or sorted({t["obj_id"] for t in targets})
     repres = {lid: repre_util.load_object_repre(repre_util.get_object_repre_dir_path(args.repre_dir, opts.repre_version, opts.object_dataset, lid)) for lid in lids}
     n_inst: Dict[int, Dict[Tuple[int, int], int]] = {}
     for t in targets:
-        n_inst.setdefault(t["obj_id"], {})[(t["scene_id"], t["im_id"])] = t["inst_count"]
+        if detection_task:
+            for lid in lids:
+                n_inst.setdefault(lid, {})[(t["scene_id"], t["im_id"])] = 0
+        else:
+            n_inst.setdefault(t["obj_id"], {})[(t["scene_id"], t["im_id"])] = t["inst_count"]
     eval_models = None
     models_dir = args.models_dir or os.path.join(os.path.dirname(os.path.abspath(args.dataset_dir)), "models")
     renderer = None

@@ -480,3 +480,58 @@ def pose_nms_greedy(group_off: torch.Tensor, pair_off: torch.Tensor, pairs: torc
     call("fp_pose_nms_greedy", ptr(group_off), ptr(pair_off), F, ptr(pairs), ptr(overlap), ptr(status), int(num_poses), P, float(thresh), ptr(keep), ptr(by),
          stream())
     return keep, by
+
+
+DETECTION_MAX_THS, DETECTION_MAX_GROUP_GT, DETECTION_MAX_REC = 16, 256, 128  # FP_DETECTION_* of the header
+
+
+def _detection_tables(name: str, tables) -> None:
+    for x, dt in tables:
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise ValueError(f"{name}: every table is a device tensor (got {'a CPU tensor' if isinstance(x, torch.Tensor) else type(x).__name__}); there is no CPU path")
+        if x.dtype != dt or not x.is_contiguous():
+            raise ValueError(f"{name}: a contiguous {dt} table is needed, got {x.dtype}{'' if x.is_contiguous() else ' (strided)'}")
+
+
+def detection_match(est_off: torch.Tensor, gt_off: torch.Tensor, pair_off: torch.Tensor, err: torch.Tensor, gt_valid: torch.Tensor,
+                    group_tab: torch.Tensor, ths: torch.Tensor, num_est: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp_detection_match on device tables whose CONTENTS have been validated already (eval_bop24.match_groups checks
+    the offsets on the host before it uploads them): est_off / gt_off / pair_off int32 [NG + 1], err f64 [P, 2] (ops.pose_errors' first
+    output, not read back), gt_valid int32 [G], group_tab int32 [NG], ths f64 [NTAB, 2, T].  -> (flag int8 [num_est, 2 T], matched_gt int32
+    [num_est, 2 T]); an estimate of no group keeps flag 0 and matched_gt -1."""
+    _detection_tables("detection_match", ((est_off, torch.int32), (gt_off, torch.int32), (pair_off, torch.int32), (err, torch.float64),
+                                          (gt_valid, torch.int32), (group_tab, torch.int32), (ths, torch.float64)))
+    NG = int(est_off.shape[0]) - 1
+    if ths.dim() != 3 or ths.shape[1] != 2 or not 1 <= int(ths.shape[2]) <= DETECTION_MAX_THS or (NG > 0 and ths.shape[0] < 1):
+        raise ValueError(f"detection_match: ths must be [NTAB >= 1, 2, T] with 1 <= T <= {DETECTION_MAX_THS}, got {tuple(ths.shape)}")
+    if NG < 0 or int(gt_off.shape[0]) != NG + 1 or int(pair_off.shape[0]) != NG + 1 or group_tab.numel() != NG or err.dim() != 2 or err.shape[1] != 2 \
+            or num_est < 0:
+        raise ValueError("detection_match: table sizes do not match")
+    T = int(ths.shape[2])
+    flag = torch.zeros(num_est, 2 * T, dtype=torch.int8, device=err.device)
+    matched = torch.full((num_est, 2 * T), -1, dtype=torch.int32, device=err.device)
+    call("fp_detection_match", ptr(est_off), ptr(gt_off), ptr(pair_off), NG, ptr(err), int(err.shape[0]), ptr(gt_valid), int(gt_valid.shape[0]),
+         ptr(group_tab), ptr(ths), int(ths.shape[0]), T, int(num_est), ptr(flag), ptr(matched), stream())
+    return flag, matched
+
+
+def detection_ap(obj_off: torch.Tensor, order: torch.Tensor, flag: torch.Tensor, n_valid: torch.Tensor,
+                 rec_thr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fp_detection_ap on device tables validated already (eval_bop24.ap_objects): obj_off int32 [O + 1], order int32
+    [N], flag int8 [N_est, C] as detection_match wrote it, n_valid int32 [O], rec_thr f64 [R].  -> (ap f64 [O, C], q f64 [O, C, R], totals
+    int32 [O, C, 3])."""
+    _detection_tables("detection_ap", ((obj_off, torch.int32), (order, torch.int32), (flag, torch.int8), (n_valid, torch.int32), (rec_thr, torch.float64)))
+    O, R = int(obj_off.shape[0]) - 1, int(rec_thr.numel())
+    if flag.dim() != 2 or flag.shape[1] % 2 or not 1 <= int(flag.shape[1]) // 2 <= DETECTION_MAX_THS:
+        raise ValueError(f"detection_ap: flag must be [N_est, 2 T] with 1 <= T <= {DETECTION_MAX_THS}, got {tuple(flag.shape)}")
+    if not 1 <= R <= DETECTION_MAX_REC:
+        raise ValueError(f"detection_ap: 1 <= R <= {DETECTION_MAX_REC} recall thresholds are needed, got {R}")
+    if O < 0 or n_valid.numel() != O or order.dim() != 1:
+        raise ValueError("detection_ap: table sizes do not match")
+    C = int(flag.shape[1])
+    ap = torch.empty(O, C, dtype=torch.float64, device=flag.device)
+    q = torch.empty(O, C, R, dtype=torch.float64, device=flag.device)
+    totals = torch.empty(O, C, 3, dtype=torch.int32, device=flag.device)
+    call("fp_detection_ap", ptr(obj_off), O, ptr(order), int(order.shape[0]), ptr(flag), int(flag.shape[0]), C // 2, ptr(n_valid), ptr(rec_thr), R,
+         ptr(ap), ptr(q), ptr(totals), stream())
+    return ap, q, totals

@@ -329,6 +329,42 @@ int fp_pose_nms_greedy(const int32_t* group_off, const int32_t* pair_off, int nu
                        const int32_t* status, int num_poses, int num_pairs, double thresh, int32_t* out_keep, int32_t* out_suppressed_by,
                        fp_stream_t stream);
 
+/* The score of the BOP 6D detection task (restates the published behaviour of bop_toolkit's detection scores), first
+ * half: greedy matching of every estimate group, once per column.  A group is the estimates of one (image, object); a column is
+ * c = type * num_ths + k, type 0 = MSSD, 1 = MSPD, k < num_ths, 1 <= num_ths <= FP_DETECTION_MAX_THS, so there are C = 2 num_ths columns.
+ * est_off / gt_off / pair_off [num_groups + 1] int32: group g owns the estimates [est_off[g], est_off[g + 1]) -- E_g of them, laid out IN
+ * RANK ORDER (the caller sorts by score descending, equal scores in input order) --, the GT instances [gt_off[g], gt_off[g + 1]) -- G_g
+ * <= FP_DETECTION_MAX_GROUP_GT of them, 0 is legal -- and the rows [pair_off[g], pair_off[g] + E_g G_g) of err [num_pairs, 2] f64 =
+ * (mssd, mspd), row-major [E_g x G_g]: fp_pose_errors' out_err as it lies on the device.  gt_valid [num_gt] int32 (> 0: valid);
+ * group_tab [num_groups] int32: the group's row of ths [num_tabs, 2, num_ths] f64 (the caller multiplies the thresholds out).
+ * Rule per (group, column): for e = 0 .. E_g - 1 the estimate takes the not yet matched GT with the lowest error STRICTLY below the
+ * threshold, ties to the lower GT index; a NaN error never matches; the matched GT is used up whether valid or not.
+ * out_flag [num_est, C] int8: 1 matched to a valid GT (true positive), 2 matched to an invalid GT (ignored), 0 unmatched (false positive);
+ * out_matched_gt [num_est, C] int32: the group-local GT index or -1.  Only estimates of some group are written.  Offsets are clamped to
+ * their arrays, a group to 256 GT instances (the caller refuses more) and to the rows err has.  A group's result depends on its own data
+ * only: the same bytes alone, in any batch and at any position.  (Added without a change of FP_ABI_VERSION: no existing entry point
+ * changed.) */
+#define FP_DETECTION_MAX_THS 16
+#define FP_DETECTION_MAX_GROUP_GT 256
+#define FP_DETECTION_MAX_REC 128
+int fp_detection_match(const int32_t* est_off, const int32_t* gt_off, const int32_t* pair_off, int num_groups, const double* err,
+                       int num_pairs, const int32_t* gt_valid, int num_gt, const int32_t* group_tab, const double* ths, int num_tabs,
+                       int num_ths, int num_est, int8_t* out_flag, int32_t* out_matched_gt, fp_stream_t stream);
+
+/* ... second half: the average precision per (object, column).  obj_off [num_objects + 1] int32: object o owns order[obj_off[o],
+ * obj_off[o + 1]) of order [num_order] int32, the rows of flag [num_est, C] of its estimates over ALL images in global rank order (score
+ * descending, equal scores in input order; sorted by the caller); n_valid [num_objects] int32: its valid GT instances over all target
+ * images; rec_thr [num_rec] f64, 1 <= num_rec <= FP_DETECTION_MAX_REC.  Rule per (o, c): the estimates with flag 2 are dropped; over the
+ * kept ones tp_k / fp_k are the inclusive running counts of flags 1 / 0, p_k = (double) tp_k / (double) (tp_k + fp_k), r_k = (double) tp_k
+ * / (double) n_valid[o], pe_k = max over j >= k of p_j; q_i = pe_k* with k* the first kept k whose r_k >= rec_thr[i], 0 when there is
+ * none; ap = (((q_0 + q_1) + q_2) + ...) / (double) num_rec, one rounded add each (no FMA contraction).  n_valid[o] <= 0: ap = -1, q = 0.
+ * out_ap [num_objects, C] f64, out_q [num_objects, C, num_rec] f64, out_totals [num_objects, C, 3] int32 = (tp, fp, ignored).  All but
+ * the divisions is integer arithmetic and maxima.  Offsets and rows are clamped to their arrays.  (Added without a change of
+ * FP_ABI_VERSION.) */
+int fp_detection_ap(const int32_t* obj_off, int num_objects, const int32_t* order, int num_order, const int8_t* flag, int num_est,
+                    int num_ths, const int32_t* n_valid, const double* rec_thr, int num_rec, double* out_ap, double* out_q,
+                    int32_t* out_totals, fp_stream_t stream);
+
 /* sample_feature_map_at_points (utils/feature_util.py:100-131): bilinear grid_sample, zeros padding,
  * align_corners=False.  fmap addressed by element strides (image, channel, y, x); point_img (may be null)
  * maps each point to its image.  out [num_points, C]. */
