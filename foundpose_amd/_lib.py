@@ -100,6 +100,7 @@ _PROTOS = {
                                   i32, i32, vp, vp],
     "fp_template_downsample": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
     "fp_pose_errors": [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp, vp],
+    "fp_pose_add_errors": [vp, i32, vp, vp, vp, i32, vp, C.c_size_t, vp, vp],
     "fp_vsd_counts": [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp],
     "fp_featuremetric_refine": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32,
                                 vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
@@ -180,6 +181,14 @@ POSE_ERR_TILE = 64 * 8  # FP_POSE_ERR_TILE of the header
 def pose_err_scratch_bytes(num_hyp: int, max_pts: int, max_syms: int) -> int:
     """FP_POSE_ERR_SCRATCH_BYTES of include/foundpose_amd.h."""
     return 32 * ((num_hyp + 7) // 8) * 8 + 24 * num_hyp * max_syms * ((max_pts + POSE_ERR_TILE - 1) // POSE_ERR_TILE)
+
+
+POSE_ADD_TILE = 256  # FP_POSE_ADD_TILE of the header
+
+
+def pose_add_scratch_bytes(num_pairs: int, max_pts: int) -> int:
+    """FP_POSE_ADD_SCRATCH_BYTES of include/foundpose_amd.h."""
+    return 32 * ((num_pairs + 7) // 8) * 8 + 16 * num_pairs * ((max_pts + POSE_ADD_TILE - 1) // POSE_ADD_TILE)
 
 
 VSD_MAX_TAUS = 16  # FP_VSD_MAX_TAUS of the header

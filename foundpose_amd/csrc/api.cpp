@@ -735,6 +735,33 @@ int fp_pose_errors(const double* pts, int total_pts, const double* est, const do
   return launch_pose_errors(a, num_hyp, max_tiles, max_syms, ST(stream));
 }
 
+int fp_pose_add_errors(const double* pts, int total_pts, const double* est, const double* gt, const int32_t* ranges, int num_pairs,
+                       void* scratch, size_t scratch_bytes, double* err, fp_stream_t stream) {
+  FP_REQUIRE(pts && est && gt && ranges && scratch && err, "fp_pose_add_errors: null pointer");
+  FP_REQUIRE(num_pairs >= 1 && num_pairs <= 65535, "fp_pose_add_errors: num_pairs %d outside [1, 65535]", num_pairs);
+  FP_REQUIRE(total_pts >= 1, "fp_pose_add_errors: empty point array");
+  std::vector<PoseAddPair> pairs(num_pairs);
+  long long parts = 0;
+  int max_tiles = 0;
+  for (int h = 0; h < num_pairs; ++h) {
+    const int32_t* r = ranges + 2 * (size_t)h;
+    FP_REQUIRE(r[1] >= 1, "fp_pose_add_errors: pair %d has an empty point range", h);
+    FP_REQUIRE(r[0] >= 0 && (long long)r[0] + r[1] <= total_pts, "fp_pose_add_errors: pair %d: points [%d, +%d) outside [0, %d)", h, r[0], r[1], total_pts);
+    const int tiles = (int)(((long long)r[1] + FP_POSE_ADD_TILE - 1) / FP_POSE_ADD_TILE);
+    pairs[h] = PoseAddPair{r[0], r[1], tiles, 0, parts, 0};
+    parts += tiles;
+    max_tiles = tiles > max_tiles ? tiles : max_tiles;
+  }
+  const size_t table = 32 * (((size_t)num_pairs + 7) / 8) * 8;
+  FP_REQUIRE(scratch_bytes >= table + 16 * (size_t)parts, "fp_pose_add_errors: scratch holds %zu bytes, %zu needed", scratch_bytes, table + 16 * (size_t)parts);
+  static_assert(sizeof(PoseAddPair) == 32, "layout of FP_POSE_ADD_SCRATCH_BYTES");
+  // synchronous as in fp_pose_errors: the table lives in this frame
+  HIP_TRY(hipMemcpyWithStream(scratch, pairs.data(), sizeof(PoseAddPair) * (size_t)num_pairs, hipMemcpyHostToDevice, ST(stream)), "fp_pose_add_errors: table upload");
+  PoseAddArgs a{pts, est, gt, reinterpret_cast<const PoseAddPair*>(scratch), reinterpret_cast<double*>(static_cast<char*>(scratch) + table), err, total_pts};
+  const int tiles_per_block = FP_POSE_ADD_BLOCK / FP_POSE_ADD_TILE;
+  return launch_pose_add_errors(a, num_pairs, (max_tiles + tiles_per_block - 1) / tiles_per_block, ST(stream));
+}
+
 // ------------------------------------------------------------------ featuremetric refinement
 int fp_featuremetric_refine(const float* map, int64_t sb, int64_t sy, int64_t sx, int64_t sc, int gh, int gw, int C, int W, int H,
                             const double* cameras, const double* R_in, const double* t_in, const int32_t* row_begin,

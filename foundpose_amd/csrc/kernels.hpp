@@ -288,6 +288,22 @@ struct PoseErrArgs {
 };
 int launch_pose_errors(const PoseErrArgs& a, int num_hyp, int max_tiles, int max_syms, hipStream_t st);
 
+// ---------------------------------------------------------------- pose_add.hip
+struct PoseAddPair {       // one (estimate, GT) pair, built on the host by fp_pose_add_errors
+  int pt_off, pt_cnt;      // point range in pts
+  int tiles, pad;          // ceil(pt_cnt / FP_POSE_ADD_TILE)
+  long long part_base;     // first tile partial of the pair: partials [tiles] of (sum_a, sum_n)
+  long long pad2;
+};
+struct PoseAddArgs {
+  const double* pts; const double* est; const double* gt;
+  const PoseAddPair* pairs;  // [num_pairs] device copy
+  double* parts;             // [total tiles, 2]
+  double* err;               // [num_pairs, 2] (add, adi)
+  int total_pts;
+};
+int launch_pose_add_errors(const PoseAddArgs& a, int num_pairs, int max_blocks, hipStream_t st);
+
 // ---------------------------------------------------------------- refine.hip
 struct RefineState {       // Levenberg-Marquardt state of one detection (scratch, FP_REFINE_STATE_BYTES)
   double R[9], t[3];       // current pose

@@ -371,6 +371,43 @@ def pose_errors(pts: torch.Tensor, est: torch.Tensor, p_est: torch.Tensor, gt_sy
     return err, idx
 
 
+def pose_add_errors(pts: torch.Tensor, est: torch.Tensor, gt: torch.Tensor, ranges) -> torch.Tensor:
+    """ADD / ADI of a ragged batch of (estimate, GT) pairs (fp_pose_add_errors): pts [V, 3], est / gt [H, 12] = R row-major | t (fp64, on the
+    device); ranges [H, 2] int (host) = (pt_off, pt_cnt) per pair.  -> err [H, 2] fp64 = (add, adi).  The table is checked here, before any
+    launch: ValueError, nothing written."""
+    import numpy as np
+    for name, t in (("pts", pts), ("est", est), ("gt", gt)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"pose_add_errors: {name} is a device tensor; there is no CPU path")
+    if isinstance(ranges, torch.Tensor):
+        if ranges.is_cuda:
+            raise ValueError("pose_add_errors: ranges is a host table (it is validated and sized on the host)")
+        ranges = ranges.numpy()
+    r = np.asarray(ranges)
+    if r.ndim != 2 or r.shape[1] != 2 or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError(f"pose_add_errors: ranges must be an integer [H, 2] table, got {r.dtype} {r.shape}")
+    r = np.ascontiguousarray(r.astype(np.int64))
+    h = r.shape[0]
+    if h < 1 or h > 65535:
+        raise ValueError(f"pose_add_errors: {h} pairs, 1 .. 65535 per call")
+    if np.any(np.abs(r) > 2**31 - 1) or pts.shape[0] > 2**31 - 1:
+        raise ValueError("pose_add_errors: range entries must fit int32")
+    if pts.dim() != 2 or pts.shape[1] != 3 or est.shape != (h, 12) or gt.shape != (h, 12):
+        raise ValueError("pose_add_errors: shapes must be pts [V, 3], est / gt [H, 12], ranges [H, 2]")
+    if int(r[:, 1].min()) < 1:
+        raise ValueError(f"pose_add_errors: pair {int(np.argmin(r[:, 1]))} has an empty point range")
+    bad = np.nonzero((r[:, 0] < 0) | (r[:, 0] + r[:, 1] > pts.shape[0]))[0]
+    if bad.size:
+        raise ValueError(f"pose_add_errors: pair {int(bad[0])}: points [{int(r[bad[0], 0])}, +{int(r[bad[0], 1])}) outside [0, {pts.shape[0]})")
+    r = r.astype(np.int32)
+    pts, est, gt = (t.to(torch.float64).contiguous() for t in (pts, est, gt))
+    err = torch.empty(h, 2, dtype=torch.float64, device=pts.device)
+    nbytes = _lib.pose_add_scratch_bytes(h, int(r[:, 1].max()))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
+    call("fp_pose_add_errors", ptr(pts), pts.shape[0], ptr(est), ptr(gt), r.ctypes.data_as(_lib.vp), h, ptr(scratch), nbytes, ptr(err), stream())
+    return err
+
+
 def vsd_counts(depth_test: torch.Tensor, depth_est: torch.Tensor, depth_gt: torch.Tensor, pairs, params, taus) -> torch.Tensor:
     """VSD counts of a batch of (estimate, GT) pairs (fp_vsd_counts): depth_test [N_test, H, W], depth_est [N_est, H, W],
     depth_gt [N_gt, H, W] fp32 mm (on the device); pairs [P, 7] int (host) = (test, est, gt, x0, y0, x1, y1) with the inclusive

@@ -707,6 +707,31 @@ int fp_pose_errors(const double* pts, int total_pts, const double* est, const do
                    int total_syms, const int32_t* ranges, int num_hyp, void* scratch, size_t scratch_bytes, double* err, int32_t* idx,
                    fp_stream_t stream);
 
+/* ---- ADD / ADI (bop_toolkit_lib pose_error.add / adi; DESIGN.md section 22, tests/pose_add_ref.py restates it) -----------
+ * The average distance of model points (ADD) and to the closest model point (ADI, "ADD-S") of num_pairs (estimate, GT) pairs,
+ * fp64 in and out.  Pair h uses the points pts[pt_off .. pt_off + pt_cnt) given by ranges[h] = (pt_off, pt_cnt) -- HOST memory,
+ * int32 [num_pairs, 2]: the call validates every range and copies a derived table into scratch on `stream`, waiting for that
+ * copy as fp_pose_errors does.  Device arrays:
+ *   pts  [total_pts, 3]   model points (mm), objects concatenated
+ *   est  [num_pairs, 12]  R_est (row-major) | t_est, model -> camera
+ *   gt   [num_pairs, 12]  R_gt | t_gt
+ *   err  [num_pairs, 2]   (add, adi)
+ * With E_v = ((r0 x + r1 y) + r2 z) + t per row of the estimate and G_v the same with the GT pose:
+ *   add = mean_v sqrt((dx dx + dy dy) + dz dz), d = G_v - E_v
+ *   adi = mean_v sqrt(min_u ((dx dx + dy dy) + dz dz)), d = G_v - E_u, u over the pair's whole range (brute force): the minimum
+ *         starts at +inf and takes a candidate only when it is strictly smaller (a NaN never wins)
+ * every operation rounded on its own (no contraction, correctly rounded sqrt, IEEE division).  The means have one summation
+ * order: tiles of FP_POSE_ADD_TILE consecutive points are summed in ascending point order, the tile sums in ascending tile order,
+ * and the sum is divided by (double)pt_cnt.  Results are bit-identical across runs, batch compositions and batch orders.
+ * scratch: at least FP_POSE_ADD_SCRATCH_BYTES(num_pairs, max pt_cnt) bytes.  num_pairs outside [1, 65535], a pt_cnt < 1, a range
+ * outside [0, total_pts], a NULL pointer or too little scratch: FP_ERR_INVALID, nothing written. */
+#define FP_POSE_ADD_TILE 256
+#define FP_POSE_ADD_BLOCK (4 * FP_POSE_ADD_TILE) /* query points of one workgroup */
+#define FP_POSE_ADD_SCRATCH_BYTES(num_pairs, max_pts) \
+  (32 * (((size_t)(num_pairs) + 7) / 8) * 8 + 16 * (size_t)(num_pairs) * (((size_t)(max_pts) + FP_POSE_ADD_TILE - 1) / FP_POSE_ADD_TILE))
+int fp_pose_add_errors(const double* pts, int total_pts, const double* est, const double* gt, const int32_t* ranges, int num_pairs,
+                       void* scratch, size_t scratch_bytes, double* err, fp_stream_t stream);
+
 /* ---- VSD (bop_toolkit_lib pose_error.vsd, `bop19` visibility, `step` cost) ----------------------
  * Counts for the Visible Surface Discrepancy of num_pairs (estimate, GT) pairs.  Device arrays:
  *   depth_test [num_test, height, width]  fp32 mm, 0 = no measurement (the test images)
