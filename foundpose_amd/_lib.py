@@ -67,6 +67,11 @@ _PROTOS = {
     "fp_detection_match": [vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp],
     "fp_detection_ap": [vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp],
     "fp_detection_masks": [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "fp_mask_boxes": [vp, i32, i32, i32, vp, vp, vp],
+    "fp_proposal_crops": [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp],
+    "fp_proposal_scores": [vp, i32, i32, vp, i32, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp],
+    "fp_proposal_rank": [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+    "fp_box_iou": [vp, i32, vp, i32, vp, vp, vp],
     "fp_sample_bilinear": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp],
     "fp_pca_project": [vp, i32, i32, vp, i32, vp, vp, vp],
     "fp_vit_forward": [C.POINTER(VitModel), C.POINTER(VitWorkspace), vp, i32, i32, i32, i32, vp],
@@ -218,6 +223,18 @@ def rgbd_refine_scratch_bytes(num_det: int, max_points: int) -> int:
     """FP_RGBD_REFINE_SCRATCH_BYTES of include/foundpose_amd.h."""
     chunks = (max_points + REFINE_CHUNK - 1) // REFINE_CHUNK
     return REFINE_STATE_BYTES * num_det + 16 * REFINE_RECORD * num_det * chunks + ((num_det * max_points + 7) // 8) * 8 + 8
+
+
+PROPOSAL_MAX_SIZE, PROPOSAL_MAX_K, PROPOSAL_MAX_RANKED = 1024, 16, 4096  # FP_PROPOSAL_MAX_* of the header
+PROPOSAL_DECISIONS = ("candidate", "small", "empty", "no_object", "low_score", "group_limit")  # FP_PROPOSAL_CANDIDATE .. _GROUP_LIMIT
+
+
+def proposal_score_scratch_bytes(num_prop: int, num_obj: int, dim: int, max_templates: int, k: int) -> int:
+    """FP_PROPOSAL_SCORE_SCRATCH_BYTES of include/foundpose_amd.h."""
+    up16 = lambda b: (b + 15) // 16 * 16
+    rows = num_obj * num_prop
+    return (up16(4 * cosine_scratch_floats(rows, max_templates)) + up16(4 * rows * dim) + 2 * up16(4 * (num_obj + 1)) + up16(4 * rows)
+            + 2 * up16(4 * rows * k))
 
 
 TEXTURE_MAX_SIDE = 16384  # FP_TEXTURE_MAX_SIDE of the header

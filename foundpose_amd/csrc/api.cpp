@@ -393,6 +393,96 @@ int fp_detection_ap(const int32_t* obj_off, int num_objects, const int32_t* orde
   return launch_detection_ap(a, num_objects, ST(stream));
 }
 
+// ------------------------------------------------------------------ proposal labelling
+int fp_mask_boxes(const uint8_t* masks, int num_prop, int H, int W, int32_t* out_box, int32_t* out_area, fp_stream_t stream) {
+  FP_REQUIRE(num_prop >= 0, "fp_mask_boxes: %d proposals", num_prop);
+  if (num_prop == 0) return FP_OK;
+  FP_REQUIRE(masks && out_box && out_area, "fp_mask_boxes: null pointer");
+  MaskBoxArgs a;
+  memset(&a, 0, sizeof(a));
+  a.masks = masks; a.H = H; a.W = W; a.box = out_box; a.area = out_area;
+  return launch_mask_boxes(a, num_prop, ST(stream));
+}
+
+int fp_proposal_crops(const float* images, int n_img, int H, int W, const uint8_t* masks, const int32_t* image_index, const int32_t* boxes,
+                      int num_prop, int S, float* out, int32_t* out_status, fp_stream_t stream) {
+  FP_REQUIRE(num_prop >= 0, "fp_proposal_crops: %d proposals", num_prop);
+  if (num_prop == 0) return FP_OK;
+  FP_REQUIRE(images && masks && boxes && out && out_status, "fp_proposal_crops: null pointer");
+  ProposalCropArgs a;
+  memset(&a, 0, sizeof(a));
+  a.images = images; a.masks = masks; a.image_index = image_index; a.boxes = boxes; a.n_img = n_img; a.H = H; a.W = W; a.S = S;
+  a.out = out; a.status = out_status;
+  return launch_proposal_crops(a, num_prop, ST(stream));
+}
+
+int fp_proposal_scores(const float* desc_n, int num_prop, int dim, const float* bank_n, int num_bank, const int32_t* obj_off, int num_obj,
+                       int max_templates, int k, void* scratch, size_t scratch_bytes, float* out_scores, int32_t* out_best_obj,
+                       float* out_best_score, int32_t* out_best_template, fp_stream_t stream) {
+  FP_REQUIRE(num_prop >= 0 && num_bank >= 0, "fp_proposal_scores: negative count");
+  FP_REQUIRE(num_obj >= 1 && dim >= 1 && max_templates >= 1, "fp_proposal_scores: %d objects of at most %d templates, %d words", num_obj, max_templates, dim);
+  FP_REQUIRE(k >= 1 && k <= FP_PROPOSAL_MAX_K, "fp_proposal_scores: k = %d outside [1, %d]", k, FP_PROPOSAL_MAX_K);
+  FP_REQUIRE((long long)num_obj * num_prop <= (1ll << 20), "fp_proposal_scores: %d proposals x %d objects (at most 2^20 rows in one call)", num_prop, num_obj);
+  if (num_prop == 0) return FP_OK;
+  FP_REQUIRE(desc_n && obj_off && scratch && out_scores && out_best_obj && out_best_score && out_best_template, "fp_proposal_scores: null pointer");
+  FP_REQUIRE(bank_n || num_bank == 0, "fp_proposal_scores: null bank");
+  FP_REQUIRE((reinterpret_cast<size_t>(scratch) & 15) == 0, "fp_proposal_scores: scratch must be 16-byte aligned");
+  FP_REQUIRE(scratch_bytes >= FP_PROPOSAL_SCORE_SCRATCH_BYTES(num_prop, num_obj, dim, max_templates, k),
+             "fp_proposal_scores: scratch of %zu bytes, %zu needed", scratch_bytes,
+             (size_t)FP_PROPOSAL_SCORE_SCRATCH_BYTES(num_prop, num_obj, dim, max_templates, k));
+  const size_t rows = (size_t)num_obj * num_prop;
+  auto up16 = [](size_t b) { return (b + 15) / 16 * 16; };
+  char* s = static_cast<char*>(scratch);
+  float* cos_scratch = reinterpret_cast<float*>(s);  s += up16(4 * FP_COSINE_SCRATCH_FLOATS(rows, max_templates));
+  ProposalScoreArgs a;
+  memset(&a, 0, sizeof(a));
+  a.desc_n = desc_n; a.obj_off = obj_off; a.P = num_prop; a.D = dim; a.N = num_bank; a.O = num_obj; a.k = k; a.max_templates = max_templates;
+  a.rep = reinterpret_cast<float*>(s);      s += up16(4 * rows * dim);
+  a.seg_off = reinterpret_cast<int*>(s);    s += up16(4 * ((size_t)num_obj + 1));
+  a.tpl_off = reinterpret_cast<int*>(s);    s += up16(4 * ((size_t)num_obj + 1));
+  a.det_nt = reinterpret_cast<int*>(s);     s += up16(4 * rows);
+  float* top_val = reinterpret_cast<float*>(s);  s += up16(4 * rows * k);
+  int* top_idx = reinterpret_cast<int*>(s);
+  a.top_val = top_val; a.top_idx = top_idx;
+  a.scores = out_scores; a.best_obj = out_best_obj; a.best_score = out_best_score; a.best_template = out_best_template;
+  TRY(launch_proposal_prep(a, ST(stream)));
+  // the library's own retrieval, canonical tie order: its kernels, its summation order, its bits (a bank of no rows is never read: every
+  // object then has no template)
+  TRY(fp_cosine_topk(a.rep, a.seg_off, a.det_nt, (int)rows, num_prop, bank_n ? bank_n : desc_n, a.tpl_off, num_obj, max_templates, dim, k, cos_scratch,
+                     top_val, top_idx, 0, stream));
+  return launch_proposal_aggregate(a, ST(stream));
+}
+
+int fp_proposal_rank(const int32_t* best_obj, const float* best_score, const int32_t* area, const int32_t* crop_status, const int32_t* boxes,
+                     int num_prop, int num_obj, int min_area, float min_score, int max_group, int max_pairs, int32_t* out_decision,
+                     int32_t* out_order, int32_t* out_group_off, int32_t* out_pair_off, int32_t* out_pairs, int32_t* out_boxes_ranked,
+                     fp_stream_t stream) {
+  FP_REQUIRE(num_prop >= 0 && max_pairs >= 0, "fp_proposal_rank: negative count");
+  FP_REQUIRE(out_group_off && out_pair_off, "fp_proposal_rank: null pointer");
+  FP_REQUIRE((best_obj && best_score && area && crop_status && boxes && out_decision && out_order && out_boxes_ranked) || num_prop == 0,
+             "fp_proposal_rank: null pointer");
+  FP_REQUIRE(out_pairs || max_pairs == 0, "fp_proposal_rank: null pairs");
+  ProposalRankArgs a;
+  memset(&a, 0, sizeof(a));
+  a.best_obj = best_obj; a.best_score = best_score; a.area = area; a.crop_status = crop_status; a.boxes = boxes;
+  a.P = num_prop; a.O = num_obj; a.min_area = min_area; a.max_group = max_group; a.max_pairs = max_pairs; a.min_score = min_score;
+  a.decision = out_decision; a.order = out_order; a.group_off = out_group_off; a.pair_off = out_pair_off; a.pairs = out_pairs;
+  a.boxes_ranked = out_boxes_ranked;
+  return launch_proposal_rank(a, ST(stream));
+}
+
+int fp_box_iou(const int32_t* boxes, int num_boxes, const int32_t* pairs, int num_pairs, double* out_overlap, int32_t* out_status,
+               fp_stream_t stream) {
+  FP_REQUIRE(num_boxes >= 0 && num_pairs >= 0, "fp_box_iou: negative count");
+  if (num_pairs == 0) return FP_OK;
+  FP_REQUIRE(pairs && out_overlap && out_status, "fp_box_iou: null pointer");
+  FP_REQUIRE(boxes || num_boxes == 0, "fp_box_iou: null boxes");
+  BoxIouArgs a;
+  memset(&a, 0, sizeof(a));
+  a.boxes = boxes; a.pairs = pairs; a.n_boxes = num_boxes; a.n_pairs = num_pairs; a.overlap = out_overlap; a.status = out_status;
+  return launch_box_iou(a, ST(stream));
+}
+
 // ------------------------------------------------------------------ ViT building blocks
 int fp_patchify(const float* images, int B, int H, int W, int patch, void* out, int ld_out, int out_dtype,
                 fp_stream_t stream) {

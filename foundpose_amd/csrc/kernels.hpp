@@ -557,3 +557,72 @@ struct DetApArgs {
   int* totals;             // [objects, 2 T, 3] tp, fp, ignored
 };
 int launch_detection_ap(const DetApArgs& a, int num_objects, hipStream_t st);
+
+// ---------------------------------------------------------------- proposals.hip
+constexpr int PC_MAX_SIZE = 1024;      // the crop's side: the axis tables and three rows of it fit the 64 KiB of a workgroup's LDS
+constexpr int PS_MAX_K = 16;           // similarities averaged per (proposal, object)
+struct MaskBoxArgs {
+  const unsigned char* masks;  // [P, H, W] 0 / non-zero
+  int H, W;
+  int* box;                // [P, 4] x1, y1, x2, y2 (x2, y2 exclusive); all 0 for an empty mask
+  int* area;               // [P] set pixels
+};
+int launch_mask_boxes(const MaskBoxArgs& a, int num_prop, hipStream_t st);
+
+struct ProposalCropArgs {
+  const float* images;     // [n_img, H, W, 3] HWC
+  const unsigned char* masks;  // [P, H, W]
+  const int* image_index;  // [P] or null: proposal p reads image p
+  const int* boxes;        // [P, 4] as mask_boxes writes them
+  int n_img, H, W, S;
+  float* out;              // [P, 3, S, S] CHW, every element written
+  int* status;             // [P] 0 cropped, 2 empty box / box outside the image / image_index outside its table (all-zero crop)
+  int band_rows, chunk_rows;  // filled in by the launcher: output rows per workgroup, source rows per pass through LDS
+};
+int launch_proposal_crops(ProposalCropArgs a, int num_prop, hipStream_t st);
+
+struct ProposalScoreArgs {
+  const float* desc_n;     // [P, D]
+  const int* obj_off;      // [O + 1] over the N bank rows, as the caller gave it
+  int P, D, N, O, k, max_templates;
+  float* rep;              // [O, P, D] scratch: the descriptors, once per object
+  int* seg_off;            // [O + 1] scratch: o P
+  int* tpl_off;            // [O + 1] scratch: obj_off clamped into the bank and to max_templates rows per object
+  int* det_nt;             // [O P] scratch: the template count of each listed row's object
+  const float* top_val;    // [O P, k] what the retrieval wrote: the best k similarities, best first, ties to the lower template
+  const int* top_idx;      // [O P, k] their object-local template ids
+  float* scores;           // [P, O]
+  int* best_obj;           // [P]
+  float* best_score;       // [P]
+  int* best_template;      // [P]
+};
+int launch_proposal_prep(const ProposalScoreArgs& a, hipStream_t st);
+int launch_proposal_aggregate(const ProposalScoreArgs& a, hipStream_t st);
+
+constexpr int PR_MAX_PROPOSALS = 4096, PR_MAX_OBJECTS = 4096;  // of one image: one workgroup ranks them
+enum { PR_CANDIDATE = 0, PR_SMALL = 1, PR_EMPTY = 2, PR_NO_OBJECT = 3, PR_LOW_SCORE = 4, PR_GROUP_LIMIT = 5 };  // FP_PROPOSAL_* of the header
+struct ProposalRankArgs {
+  const int* best_obj;     // [P] as proposal_scores wrote it
+  const float* best_score; // [P]
+  const int* area;         // [P] as mask_boxes wrote it
+  const int* crop_status;  // [P] as proposal_crops wrote it
+  const int* boxes;        // [P, 4]
+  int P, O, min_area, max_group, max_pairs;
+  float min_score;
+  int* decision;           // [P] PR_*
+  int* order;              // [P] the proposal at each place of the layout, -1 behind the last candidate
+  int* group_off;          // [O + 1] the places of each object's candidates, in rank order
+  int* pair_off;           // [O + 1] the pairs of each object
+  int* pairs;              // [max_pairs, 2] places (a, b), a < b; (-1, -1) behind the last pair
+  int* boxes_ranked;       // [P, 4] the boxes in layout order, zeros behind the last candidate
+};
+int launch_proposal_rank(const ProposalRankArgs& a, hipStream_t st);
+
+struct BoxIouArgs {
+  const int* boxes;        // [n_boxes, 4] x1, y1, x2, y2 (x2, y2 exclusive)
+  const int* pairs;        // [n_pairs, 2] box indices
+  int n_boxes, n_pairs;
+  double* overlap;         // [n_pairs] intersection / union
+  int* status;             // [n_pairs] 0 scored, 2 union 0 or an index outside the table
+};
+int launch_box_iou(const BoxIouArgs& a, hipStream_t st);

@@ -572,3 +572,104 @@ def detection_ap(obj_off: torch.Tensor, order: torch.Tensor, flag: torch.Tensor,
     call("fp_detection_ap", ptr(obj_off), O, ptr(order), int(order.shape[0]), ptr(flag), int(flag.shape[0]), C // 2, ptr(n_valid), ptr(rec_thr), R,
          ptr(ap), ptr(q), ptr(totals), stream())
     return ap, q, totals
+
+
+# ---------------------------------------------------------------- proposal labelling
+def mask_boxes(masks: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp_mask_boxes: masks uint8 [P, H, W] (0 / non-zero) -> (boxes int32 [P, 4] = (x1, y1, x2, y2), x2 / y2 exclusive; area int32 [P]); an
+    empty mask gives (0, 0, 0, 0) and 0."""
+    _detection_tables("mask_boxes", ((masks, torch.uint8),))
+    if masks.dim() != 3 or masks.shape[1] < 1 or masks.shape[2] < 1:
+        raise ValueError(f"mask_boxes: masks must be uint8 [P, H, W] with H, W >= 1, got {tuple(masks.shape)}")
+    P, H, W = (int(v) for v in masks.shape)
+    boxes = torch.empty(P, 4, dtype=torch.int32, device=masks.device)
+    area = torch.empty(P, dtype=torch.int32, device=masks.device)
+    call("fp_mask_boxes", ptr(masks), P, H, W, ptr(boxes), ptr(area), stream())
+    return boxes, area
+
+
+def proposal_crops(images: torch.Tensor, masks: torch.Tensor, boxes: torch.Tensor, size: int,
+                   image_index: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp_proposal_crops: images f32 [n_img, H, W, 3] in [0, 1], masks uint8 [P, H, W], boxes int32 [P, 4] as mask_boxes writes them,
+    image_index int32 [P] or None (proposal p reads image p).  -> (crops f32 [P, 3, size, size], status int32 [P]: 0 cropped, 2 all zero)."""
+    tables = [(images, torch.float32), (masks, torch.uint8), (boxes, torch.int32)] + ([(image_index, torch.int32)] if image_index is not None else [])
+    _detection_tables("proposal_crops", tables)
+    if images.dim() != 4 or images.shape[3] != 3 or masks.dim() != 3 or tuple(masks.shape[1:]) != tuple(images.shape[1:3]):
+        raise ValueError(f"proposal_crops: images [n_img, H, W, 3] and masks [P, H, W] of one H x W are needed, got {tuple(images.shape)} and {tuple(masks.shape)}")
+    P = int(masks.shape[0])
+    if tuple(boxes.shape) != (P, 4) or (image_index is not None and tuple(image_index.shape) != (P,)):
+        raise ValueError(f"proposal_crops: boxes must be [{P}, 4] and image_index [{P}]")
+    if image_index is None and int(images.shape[0]) < P:
+        raise ValueError(f"proposal_crops: {P} proposals but {int(images.shape[0])} images and no image_index")
+    if not 1 <= int(size) <= _lib.PROPOSAL_MAX_SIZE:
+        raise ValueError(f"proposal_crops: crop size {size} outside [1, {_lib.PROPOSAL_MAX_SIZE}]")
+    out = torch.empty(P, 3, int(size), int(size), dtype=torch.float32, device=masks.device)
+    status = torch.empty(P, dtype=torch.int32, device=masks.device)
+    call("fp_proposal_crops", ptr(images), int(images.shape[0]), int(images.shape[1]), int(images.shape[2]), ptr(masks), ptr(image_index), ptr(boxes),
+         P, int(size), ptr(out), ptr(status), stream())
+    return out, status
+
+
+def proposal_scores(desc_n: torch.Tensor, bank_n: torch.Tensor, obj_off: torch.Tensor, max_templates: int, k: int, return_sims: bool = False):
+    """fp_proposal_scores: desc_n f32 [P, D], bank_n f32 [N, D] (rows from normalize_rows), obj_off int32 [O + 1] over bank rows (device),
+    max_templates: the largest template count of an object (host).  -> (scores f32 [P, O], best_obj int32 [P], best_score f32 [P],
+    best_template int32 [P]); with return_sims also the similarities the retrieval left in scratch, f32 [O, P, max_templates] (columns past
+    an object's template count are not written)."""
+    _detection_tables("proposal_scores", ((desc_n, torch.float32), (bank_n, torch.float32), (obj_off, torch.int32)))
+    if desc_n.dim() != 2 or bank_n.dim() != 2 or desc_n.shape[1] != bank_n.shape[1] or obj_off.dim() != 1 or obj_off.shape[0] < 2:
+        raise ValueError(f"proposal_scores: desc_n [P, D], bank_n [N, D] and obj_off [O + 1] are needed, got {tuple(desc_n.shape)}, {tuple(bank_n.shape)}, {tuple(obj_off.shape)}")
+    P, D, N, O = int(desc_n.shape[0]), int(desc_n.shape[1]), int(bank_n.shape[0]), int(obj_off.shape[0]) - 1
+    if not 1 <= int(k) <= _lib.PROPOSAL_MAX_K or int(max_templates) < 1:
+        raise ValueError(f"proposal_scores: k = {k} outside [1, {_lib.PROPOSAL_MAX_K}] or max_templates = {max_templates} < 1")
+    dev = desc_n.device
+    scores = torch.empty(P, O, dtype=torch.float32, device=dev)
+    best_obj = torch.empty(P, dtype=torch.int32, device=dev)
+    best_score = torch.empty(P, dtype=torch.float32, device=dev)
+    best_tpl = torch.empty(P, dtype=torch.int32, device=dev)
+    nbytes = _lib.proposal_score_scratch_bytes(P, O, D, int(max_templates), int(k))
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    call("fp_proposal_scores", ptr(desc_n), P, D, ptr(bank_n) if N else None, N, ptr(obj_off), O, int(max_templates), int(k), ptr(scratch), nbytes,
+         ptr(scores), ptr(best_obj), ptr(best_score), ptr(best_tpl), stream())
+    if not return_sims:
+        return scores, best_obj, best_score, best_tpl
+    sims = scratch[:4 * O * P * int(max_templates)].view(torch.float32).view(O, P, int(max_templates))
+    return scores, best_obj, best_score, best_tpl, sims
+
+
+def proposal_rank(best_obj: torch.Tensor, best_score: torch.Tensor, area: torch.Tensor, crop_status: torch.Tensor, boxes: torch.Tensor,
+                  num_obj: int, min_area: int, min_score: float, max_group: int = 256):
+    """fp_proposal_rank for the proposals of ONE image.  -> (decision int32 [P] (an index into _lib.PROPOSAL_DECISIONS), order int32 [P],
+    group_off int32 [O + 1], pair_off int32 [O + 1], pairs int32 [max_pairs, 2], boxes_ranked int32 [P, 4]), all on the device."""
+    _detection_tables("proposal_rank", ((best_obj, torch.int32), (best_score, torch.float32), (area, torch.int32), (crop_status, torch.int32),
+                                        (boxes, torch.int32)))
+    P = int(best_obj.shape[0])
+    if not (best_score.shape == area.shape == crop_status.shape == best_obj.shape) or best_obj.dim() != 1 or tuple(boxes.shape) != (P, 4):
+        raise ValueError("proposal_rank: best_obj, best_score, area and crop_status are [P], boxes [P, 4]")
+    if P > _lib.PROPOSAL_MAX_RANKED or not 1 <= int(num_obj) <= _lib.PROPOSAL_MAX_RANKED:
+        raise ValueError(f"proposal_rank: {P} proposals of {num_obj} objects (at most {_lib.PROPOSAL_MAX_RANKED} each, one object at least)")
+    if not 1 <= int(max_group) <= 256 or min_score != min_score:
+        raise ValueError(f"proposal_rank: max_group = {max_group} outside [1, 256] or min_score is NaN")
+    dev = best_obj.device
+    max_pairs = P * (int(max_group) - 1) // 2
+    decision = torch.empty(P, dtype=torch.int32, device=dev)
+    order = torch.empty(P, dtype=torch.int32, device=dev)
+    group_off = torch.empty(int(num_obj) + 1, dtype=torch.int32, device=dev)
+    pair_off = torch.empty(int(num_obj) + 1, dtype=torch.int32, device=dev)
+    pairs = torch.empty(max_pairs, 2, dtype=torch.int32, device=dev)
+    ranked = torch.empty(P, 4, dtype=torch.int32, device=dev)
+    call("fp_proposal_rank", ptr(best_obj), ptr(best_score), ptr(area), ptr(crop_status), ptr(boxes), P, int(num_obj), int(min_area), float(min_score),
+         int(max_group), max_pairs, ptr(decision), ptr(order), ptr(group_off), ptr(pair_off), ptr(pairs), ptr(ranked), stream())
+    return decision, order, group_off, pair_off, pairs, ranked
+
+
+def box_iou(boxes: torch.Tensor, pairs: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp_box_iou: boxes int32 [N, 4] = (x1, y1, x2, y2), x2 / y2 exclusive; pairs int32 [M, 2].  -> (overlap f64 [M], status int32 [M]: 0
+    scored, 2 union 0 or an index outside the table), the form pose_nms_greedy takes."""
+    _detection_tables("box_iou", ((boxes, torch.int32), (pairs, torch.int32)))
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError(f"box_iou: boxes [N, 4] and pairs [M, 2] are needed, got {tuple(boxes.shape)} and {tuple(pairs.shape)}")
+    M = int(pairs.shape[0])
+    overlap = torch.empty(M, dtype=torch.float64, device=boxes.device)
+    status = torch.empty(M, dtype=torch.int32, device=boxes.device)
+    call("fp_box_iou", ptr(boxes), int(boxes.shape[0]), ptr(pairs), M, ptr(overlap), ptr(status), stream())
+    return overlap, status

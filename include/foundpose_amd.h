@@ -365,6 +365,91 @@ int fp_detection_ap(const int32_t* obj_off, int num_objects, const int32_t* orde
                     int num_ths, const int32_t* n_valid, const double* rec_thr, int num_rec, double* out_ap, double* out_q,
                     int32_t* out_totals, fp_stream_t stream);
 
+/* Labelling of class-agnostic mask proposals (this project's own restatement of the published behaviour of CNOS's
+ * second half), 1 of 4: the tight box and the area of every mask.  masks [num_prop, H, W] uint8, 0 / non-zero; H W at most 2^30.
+ * out_box [num_prop, 4] int32 = (x1, y1, x2, y2) of the set pixels, x2 and y2 EXCLUSIVE; out_area [num_prop] int32.  An empty mask gives
+ * (0, 0, 0, 0) and area 0.  Integers only (minima, maxima and a count): nothing is clamped; H, W < 1 or H W > 2^30 is refused.  A mask's
+ * result depends on its own bytes only: it is the same bits alone, in any batch and at any position.  (Added without a change of
+ * FP_ABI_VERSION: no existing entry point changed.) */
+int fp_mask_boxes(const uint8_t* masks, int num_prop, int H, int W, int32_t* out_box, int32_t* out_area, fp_stream_t stream);
+
+/* ... 2 of 4: the cut-out.  images [n_img, H, W, 3] fp32 HWC in [0, 1]; masks [num_prop, H, W] uint8; image_index [num_prop] int32 or
+ * null (proposal p then reads image p); boxes [num_prop, 4] as fp_mask_boxes writes them; S in [1, FP_PROPOSAL_MAX_SIZE].
+ * out [num_prop, 3, S, S] fp32 CHW, EVERY element written; out_status [num_prop] int32.  With w = x2 - x1, h = y2 - y1, L = max(w, h):
+ *   w' = max(1, (2 w S + L) / (2 L)) and h' alike in integer arithmetic (w S / L rounded half up; the longer side becomes exactly S);
+ *   ox = (S - w') / 2, oy = (S - h') / 2 (integer division): out[p, c, oy + i, ox + x] for i < h', x < w' is the window, all else is 0.
+ *   Inside the window the value is the separable antialiased-bilinear resample of image * (mask != 0) restricted to the box -- the
+ *   semantics of torch.nn.functional.interpolate(mode="bilinear", antialias=True, align_corners=False).  Per axis n_in -> n_out, in fp64:
+ *   scale = n_in / n_out, sup = max(scale, 1); output i has centre c = scale (i + 0.5), taps lo = max(0, (int)(c - sup + 0.5)) up to, not
+ *   including, hi = min(n_in, (int)(c + sup + 0.5)); raw weight r_j = max(0, 1 - |(j - c + 0.5) / sup|), their sum n added j ascending,
+ *   weight w_j = (float)(r_j (1 / n)).  Order, in fp32: horizontally u = fma(w_j, v_j, u) from 0 with j ascending along x for every source
+ *   row, then vertically out = fma(w_j, u_j, out) from 0 with j ascending along y.  A masked-out pixel enters as 0 and keeps its weight.
+ * Nothing is clamped; nothing outside the box is read.  Status 0: cropped; 2: an empty box (x2 <= x1 or y2 <= y1), a box that leaves the
+ * image, or an image_index outside [0, n_img): the crop is all zero and neither the image nor the mask is read.  S outside its range,
+ * more than 65535 proposals in one call or H W > 2^30 is refused.  A proposal's crop depends on its own box, mask and image only: it is the
+ * same bits alone, in any batch and at any position.  (Added without a change of FP_ABI_VERSION.) */
+#define FP_PROPOSAL_MAX_SIZE 1024
+int fp_proposal_crops(const float* images, int n_img, int H, int W, const uint8_t* masks, const int32_t* image_index, const int32_t* boxes,
+                      int num_prop, int S, float* out, int32_t* out_status, fp_stream_t stream);
+
+/* ... 3 of 4: the score of every (proposal, object) and the label.  desc_n [num_prop, dim] and bank_n [num_bank, dim] fp32, rows
+ * L2-normalised by fp_normalize_rows; obj_off [num_obj + 1] int32 over bank rows (device); max_templates: the largest template count of
+ * an object (host; a longer object is cut to it); k in [1, FP_PROPOSAL_MAX_K].  A similarity is the dot product in fp_cosine_topk's
+ * canonical summation order for num_words = dim: the call lists the proposals once per object in scratch and runs fp_cosine_topk's own
+ * kernels on them with tie_mode 0, so the bits are that chain's.  With T_o the object's template count, m = min(k, T_o) and v_1 >= ... >=
+ * v_m its m largest similarities (equal values ordered by the lower template id):
+ *   score(p, o) = (((v_1 + v_2) + ...) + v_m) / (float)m, fp32, one rounded add each left to right and ONE division; T_o = 0: -inf.
+ * out_scores [num_prop, num_obj]; out_best_obj [num_prop] int32: the object of the highest score, ties to the lower object index, a NaN
+ * never wins and neither does -inf; out_best_score [num_prop]; out_best_template [num_prop] int32: the object-local id of v_1 of the best
+ * object.  A proposal for which no object scores gets (-1, -inf, -1).  obj_off is clamped into [0, num_bank] and made non-decreasing
+ * before anything is read through it.  scratch: FP_PROPOSAL_SCORE_SCRATCH_BYTES(num_prop, num_obj, dim, max_templates, k) bytes, 16-byte
+ * aligned; the finished similarities stay at its start, [num_obj, num_prop, max_templates] floats (row (o, p), column = template of o), for
+ * the caller.  k outside its range, num_obj < 1, dim < 1 or num_obj num_prop > 2^20 is refused; num_prop = 0 returns without a launch.
+ * A proposal's results depend on its own descriptor and the bank only: they are the same bits alone, in any batch and at any position.
+ * (Added without a change of FP_ABI_VERSION.) */
+#define FP_PROPOSAL_MAX_K 16
+#define FP_PROPOSAL_SCORE_SCRATCH_BYTES(num_prop, num_obj, dim, max_templates, k)                                                  \
+  (16 * ((4 * FP_COSINE_SCRATCH_FLOATS((size_t)(num_obj) * (num_prop), max_templates) + 15) / 16) +                               \
+   16 * ((4 * (size_t)(num_obj) * (num_prop) * (dim) + 15) / 16) + 2 * 16 * ((4 * ((size_t)(num_obj) + 1) + 15) / 16) +           \
+   16 * ((4 * (size_t)(num_obj) * (num_prop) + 15) / 16) + 2 * 16 * ((4 * (size_t)(num_obj) * (num_prop) * (k) + 15) / 16))
+int fp_proposal_scores(const float* desc_n, int num_prop, int dim, const float* bank_n, int num_bank, const int32_t* obj_off, int num_obj,
+                       int max_templates, int k, void* scratch, size_t scratch_bytes, float* out_scores, int32_t* out_best_obj,
+                       float* out_best_score, int32_t* out_best_template, fp_stream_t stream);
+
+/* ... between 3 and 4: every proposal's decision, and the candidates of ONE image laid out for the suppression, without a read-back.
+ * best_obj / best_score [num_prop] as fp_proposal_scores wrote them, area [num_prop] and boxes [num_prop, 4] as fp_mask_boxes did,
+ * crop_status [num_prop] as fp_proposal_crops did.  out_decision [num_prop] int32, the first rule that applies:
+ *   FP_PROPOSAL_SMALL area < min_area; FP_PROPOSAL_EMPTY crop_status != 0; FP_PROPOSAL_NO_OBJECT best_obj outside [0, num_obj);
+ *   FP_PROPOSAL_LOW_SCORE !(best_score >= min_score) (a NaN too); else the proposal is a candidate of the group of its object, ranked
+ *   by score descending, equal scores in input order: FP_PROPOSAL_GROUP_LIMIT for rank >= max_group, else FP_PROPOSAL_CANDIDATE.
+ * The layout lists the groups in object order, each in rank order: out_group_off [num_obj + 1]; out_order [num_prop]: the proposal at
+ * each place (-1 behind the last); out_boxes_ranked [num_prop, 4]: its box (zeros behind the last); out_pair_off [num_obj + 1] and
+ * out_pairs [max_pairs, 2]: for a group of n candidates at places g0 .. g0 + n - 1 its n (n - 1) / 2 pairs (g0 + a, g0 + b), a < b, a-major;
+ * the unused tail holds (-1, -1), which fp_box_iou answers with status 2 and fp_pose_nms_greedy never reads.  max_pairs >= num_prop
+ * (max_group - 1) / 2.  One workgroup: at most FP_PROPOSAL_MAX_RANKED proposals and as many objects, max_group in [1, 256]; more, or a
+ * NaN min_score, is refused.  Integer counting and float comparisons only.  (Added without a change of FP_ABI_VERSION.) */
+#define FP_PROPOSAL_CANDIDATE 0
+#define FP_PROPOSAL_SMALL 1
+#define FP_PROPOSAL_EMPTY 2
+#define FP_PROPOSAL_NO_OBJECT 3
+#define FP_PROPOSAL_LOW_SCORE 4
+#define FP_PROPOSAL_GROUP_LIMIT 5
+#define FP_PROPOSAL_MAX_RANKED 4096
+int fp_proposal_rank(const int32_t* best_obj, const float* best_score, const int32_t* area, const int32_t* crop_status, const int32_t* boxes,
+                     int num_prop, int num_obj, int min_area, float min_score, int max_group, int max_pairs, int32_t* out_decision,
+                     int32_t* out_order, int32_t* out_group_off, int32_t* out_pair_off, int32_t* out_pairs, int32_t* out_boxes_ranked,
+                     fp_stream_t stream);
+
+/* ... 4 of 4: intersection over union of integer boxes, in the form fp_pose_nms_greedy takes.  boxes [num_boxes, 4] int32 = (x1, y1, x2,
+ * y2) with x2, y2 exclusive; pairs [num_pairs, 2] int32.  Per pair, in int64: area = max(x2 - x1, 0) max(y2 - y1, 0) of each box,
+ * intersection = max(min(x2) - max(x1), 0) max(min(y2) - max(y1), 0) (0 if either area is 0), union = area_i + area_j - intersection;
+ * out_overlap [num_pairs] f64 = (double)intersection / (double)union, one division of the two integers converted to double;
+ * out_status [num_pairs] int32: 0 scored; 2: union 0, or an index outside [0, num_boxes) -- the overlap is 0 and nothing is read through
+ * the index.  A pair's result depends on its two boxes only: it is the same bits alone, in any batch and at any position.  (Added without
+ * a change of FP_ABI_VERSION.) */
+int fp_box_iou(const int32_t* boxes, int num_boxes, const int32_t* pairs, int num_pairs, double* out_overlap, int32_t* out_status,
+               fp_stream_t stream);
+
 /* sample_feature_map_at_points (utils/feature_util.py:100-131): bilinear grid_sample, zeros padding,
  * align_corners=False.  fmap addressed by element strides (image, channel, y, x); point_img (may be null)
  * maps each point to its image.  out [num_points, C]. */
