@@ -1,6 +1,6 @@
 // C ABI of libfoundpose_amd.so (declared in include/foundpose_amd.h): argument checking, scratch carving
 // and kernel sequencing.  No device allocation, no global mutable state, no synchronisation except the table uploads of
-// fp_pose_errors and fp_vsd_counts (each waits for its own copy) and the range check read back by fp_featuremetric_refine / fp_depth_refine.
+// fp_pose_errors and fp_vsd_counts (each waits for its own copy) and the range check read back by the three refinements (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine).
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -852,90 +852,104 @@ int fp_pose_add_errors(const double* pts, int total_pts, const double* est, cons
   return launch_pose_add_errors(a, num_pairs, (max_tiles + tiles_per_block - 1) / tiles_per_block, ST(stream));
 }
 
-// ------------------------------------------------------------------ featuremetric refinement
+// ------------------------------------------------------------------ the three pose refinements
+// the argument checks the refinements share; `f` / `d` / `depth_weight`: the feature map, the depth stack and the weight of the entries that have one
+static int refine_check(const char* fn, const RefineLmArgs& lm, const RefineMapArgs* f, const RefineDepthArgs* d, const double* depth_weight) {
+  if (f) {
+    FP_REQUIRE(f->gh >= 2 && f->gw >= 2, "%s: the feature map is %d x %d, at least 2 x 2 needed", fn, f->gh, f->gw);
+    FP_REQUIRE(f->C >= 1 && f->W >= 1 && f->H >= 1, "%s: C %d, image %d x %d", fn, f->C, (int)f->W, (int)f->H);
+    FP_REQUIRE(f->sb >= 0 && f->sy >= 0 && f->sx >= 0 && f->sc >= 0, "%s: negative map stride", fn);
+  }
+  if (d) FP_REQUIRE(d->num_images >= 1 && d->H >= 2 && d->W >= 2, "%s: %d depth images of %d x %d, at least one of 2 x 2 needed", fn, d->num_images, d->W, d->H);
+  if (depth_weight) FP_REQUIRE(*depth_weight >= 0.0 && *depth_weight < INFINITY, "%s: depth_weight %g is not a finite number >= 0", fn, *depth_weight);
+  FP_REQUIRE(lm.num_det >= 1 && lm.num_det <= 65535, "%s: num_det %d outside [1, 65535]", fn, lm.num_det);
+  FP_REQUIRE(lm.max_points >= 1 && lm.num_rows >= 0, "%s: max_points %d, num_rows %lld", fn, lm.max_points, lm.num_rows);
+  FP_REQUIRE(lm.iters >= 0 && lm.iters <= 1000, "%s: iters %d outside [0, 1000]", fn, lm.iters);
+  return FP_OK;
+}
+
+// carves the scratch: states (at its start: the caller's) | partial records of `record` doubles per (detection, chunk) | valid flags (where
+// `valid` is given) | err, and clears err
+static int refine_carve(const char* fn, RefineLmArgs& lm, void* scratch, size_t scratch_bytes, size_t need, int record, uint8_t** valid, hipStream_t st) {
+  FP_REQUIRE(scratch_bytes >= need, "%s: scratch holds %zu bytes, %zu needed", fn, scratch_bytes, need);
+  lm.chunks = (lm.max_points + FP_REFINE_CHUNK - 1) / FP_REFINE_CHUNK;
+  char* sp = static_cast<char*>(scratch) + (size_t)FP_REFINE_STATE_BYTES * lm.num_det;
+  lm.part = reinterpret_cast<double*>(sp);
+  sp += 8 * (size_t)record * lm.num_det * lm.chunks;
+  if (valid) {
+    *valid = reinterpret_cast<uint8_t*>(sp);
+    sp += (((size_t)lm.num_det * lm.max_points + 7) / 8) * 8;
+  }
+  lm.err = reinterpret_cast<int32_t*>(sp);
+  if (hipError_t e = hipMemsetAsync(lm.err, 0, sizeof(int32_t), st); e != hipSuccess) {
+    fp_set_error("%s: clear: %s", fn, hipGetErrorString(e));
+    return FP_ERR_HIP;
+  }
+  return FP_OK;
+}
+
+// the one wait of a refinement call, after every iteration is enqueued: a bad bank row range or image index is reported here, never read
+static int refine_report(const char* fn, const RefineLmArgs& lm, int num_images, hipStream_t st) {
+  int32_t bad = 0;
+  if (hipError_t e = hipMemcpyWithStream(&bad, lm.err, sizeof(int32_t), hipMemcpyDeviceToHost, st); e != hipSuccess) {
+    fp_set_error("%s: status read: %s", fn, hipGetErrorString(e));
+    return FP_ERR_HIP;
+  }
+  FP_REQUIRE(bad <= 0, "%s: detection %d: bank rows outside [0, %lld) or more than max_points %d", fn, bad - 1, lm.num_rows, lm.max_points);
+  FP_REQUIRE(bad == 0, "%s: detection %d: image index outside [0, %d)", fn, -bad - 1, num_images);
+  return FP_OK;
+}
+
+static RefineLmArgs refine_lm_args(const double* cameras, const double* R_in, const double* t_in, const int32_t* row_begin, const int32_t* row_end,
+                                   const float* vertices, int64_t num_rows, const int32_t* has_pose, int num_det, int max_points, int iters,
+                                   double* R_out, double* t_out, double* cost_in, double* cost_out, int32_t* num_points, int32_t* iters_used,
+                                   int32_t* status, double* normal_eq) {
+  return RefineLmArgs{cameras, R_in, t_in, row_begin, row_end, vertices, (long long)num_rows, has_pose, num_det, max_points, iters, 0,
+                      R_out, t_out, cost_in, cost_out, num_points, iters_used, status, normal_eq, nullptr, nullptr};
+}
+
 int fp_featuremetric_refine(const float* map, int64_t sb, int64_t sy, int64_t sx, int64_t sc, int gh, int gw, int C, int W, int H,
                             const double* cameras, const double* R_in, const double* t_in, const int32_t* row_begin,
                             const int32_t* row_end, const float* feats, const float* vertices, int64_t num_rows,
                             const int32_t* has_pose, int num_det, int max_points, int iters, void* scratch, size_t scratch_bytes,
                             double* R_out, double* t_out, double* cost_in, double* cost_out, int32_t* num_points,
                             int32_t* iters_used, int32_t* status, double* normal_eq, fp_stream_t stream) {
+  const char* fn = "fp_featuremetric_refine";
   FP_REQUIRE(map && cameras && R_in && t_in && row_begin && row_end && feats && vertices && has_pose && scratch && R_out && t_out &&
              cost_in && cost_out && num_points && iters_used && status, "fp_featuremetric_refine: null pointer");
-  FP_REQUIRE(gh >= 2 && gw >= 2, "fp_featuremetric_refine: the feature map is %d x %d, at least 2 x 2 needed", gh, gw);
-  FP_REQUIRE(C >= 1 && W >= 1 && H >= 1, "fp_featuremetric_refine: C %d, image %d x %d", C, W, H);
-  FP_REQUIRE(sb >= 0 && sy >= 0 && sx >= 0 && sc >= 0, "fp_featuremetric_refine: negative map stride");
-  FP_REQUIRE(num_det >= 1 && num_det <= 65535, "fp_featuremetric_refine: num_det %d outside [1, 65535]", num_det);
-  FP_REQUIRE(max_points >= 1 && num_rows >= 0, "fp_featuremetric_refine: max_points %d, num_rows %lld", max_points, (long long)num_rows);
-  FP_REQUIRE(iters >= 0 && iters <= 1000, "fp_featuremetric_refine: iters %d outside [0, 1000]", iters);
-  const size_t need = FP_REFINE_SCRATCH_BYTES(num_det, max_points);
-  FP_REQUIRE(scratch_bytes >= need, "fp_featuremetric_refine: scratch holds %zu bytes, %zu needed", scratch_bytes, need);
   static_assert(sizeof(RefineState) <= FP_REFINE_STATE_BYTES, "FP_REFINE_STATE_BYTES");
-  const int chunks = (max_points + FP_REFINE_CHUNK - 1) / FP_REFINE_CHUNK;
-  char* sp = static_cast<char*>(scratch);
   RefineArgs a;
   memset(&a, 0, sizeof(a));
-  a.map = map; a.sb = sb; a.sy = sy; a.sx = sx; a.sc = sc; a.gh = gh; a.gw = gw; a.C = C; a.W = W; a.H = H;
-  a.cam = cameras; a.R_in = R_in; a.t_in = t_in; a.row_begin = row_begin; a.row_end = row_end; a.feats = feats; a.verts = vertices;
-  a.num_rows = num_rows; a.has_pose = has_pose; a.num_det = num_det; a.max_points = max_points; a.iters = iters; a.chunks = chunks;
-  a.R_out = R_out; a.t_out = t_out; a.cost_in = cost_in; a.cost_out = cost_out; a.num_points = num_points; a.iters_used = iters_used;
-  a.status = status; a.normal_eq = normal_eq;
-  a.state = reinterpret_cast<RefineState*>(sp);
-  sp += (size_t)FP_REFINE_STATE_BYTES * num_det;
-  a.part = reinterpret_cast<double*>(sp);
-  sp += 8 * (size_t)FP_REFINE_RECORD * num_det * chunks;
-  a.valid = reinterpret_cast<uint8_t*>(sp);
-  sp += (((size_t)num_det * max_points + 7) / 8) * 8;
-  a.err = reinterpret_cast<int32_t*>(sp);
-  HIP_TRY(hipMemsetAsync(a.err, 0, sizeof(int32_t), ST(stream)), "fp_featuremetric_refine: clear");
+  a.lm = refine_lm_args(cameras, R_in, t_in, row_begin, row_end, vertices, num_rows, has_pose, num_det, max_points, iters, R_out, t_out, cost_in,
+                        cost_out, num_points, iters_used, status, normal_eq);
+  a.f = RefineMapArgs{map, sb, sy, sx, sc, gh, gw, C, 0, (double)W, (double)H, feats, nullptr};
+  TRY(refine_check(fn, a.lm, &a.f, nullptr, nullptr));
+  a.state = static_cast<RefineState*>(scratch);
+  TRY(refine_carve(fn, a.lm, scratch, scratch_bytes, FP_REFINE_SCRATCH_BYTES(num_det, max_points), FP_REFINE_RECORD, &a.f.valid, ST(stream)));
   TRY(launch_featuremetric_refine(a, ST(stream)));
-  // the one wait of this call, after every iteration is enqueued: a bad bank row range is reported here, never read
-  int32_t bad = 0;
-  HIP_TRY(hipMemcpyWithStream(&bad, a.err, sizeof(int32_t), hipMemcpyDeviceToHost, ST(stream)), "fp_featuremetric_refine: status read");
-  FP_REQUIRE(bad == 0, "fp_featuremetric_refine: detection %d: bank rows outside [0, %lld) or more than max_points %d", bad - 1,
-             (long long)num_rows, max_points);
-  return FP_OK;
+  return refine_report(fn, a.lm, 0, ST(stream));   // no image index: err is never negative here
 }
 
-// ------------------------------------------------------------------ depth refinement
 int fp_depth_refine(const float* depth, int num_images, int H, int W, const int32_t* image_index, const double* cameras,
                     const double* R_in, const double* t_in, const int32_t* row_begin, const int32_t* row_end, const float* vertices,
                     int64_t num_rows, const int32_t* has_pose, const double* tau, int num_det, int max_points, int iters,
                     void* scratch, size_t scratch_bytes, double* R_out, double* t_out, double* cost_in, double* cost_out,
                     int32_t* num_points, int32_t* iters_used, int32_t* status, double* normal_eq, fp_stream_t stream) {
+  const char* fn = "fp_depth_refine";
   FP_REQUIRE(depth && image_index && cameras && R_in && t_in && row_begin && row_end && vertices && has_pose && tau && scratch && R_out &&
              t_out && cost_in && cost_out && num_points && iters_used && status, "fp_depth_refine: null pointer");
-  FP_REQUIRE(num_images >= 1 && H >= 2 && W >= 2, "fp_depth_refine: %d depth images of %d x %d, at least one of 2 x 2 needed", num_images, W, H);
-  FP_REQUIRE(num_det >= 1 && num_det <= 65535, "fp_depth_refine: num_det %d outside [1, 65535]", num_det);
-  FP_REQUIRE(max_points >= 1 && num_rows >= 0, "fp_depth_refine: max_points %d, num_rows %lld", max_points, (long long)num_rows);
-  FP_REQUIRE(iters >= 0 && iters <= 1000, "fp_depth_refine: iters %d outside [0, 1000]", iters);
-  const size_t need = FP_DEPTH_REFINE_SCRATCH_BYTES(num_det, max_points);
-  FP_REQUIRE(scratch_bytes >= need, "fp_depth_refine: scratch holds %zu bytes, %zu needed", scratch_bytes, need);
-  const int chunks = (max_points + FP_REFINE_CHUNK - 1) / FP_REFINE_CHUNK;
-  char* sp = static_cast<char*>(scratch);
   DepthRefineArgs a;
   memset(&a, 0, sizeof(a));
-  a.depth = depth; a.num_images = num_images; a.H = H; a.W = W; a.image_index = image_index;
-  a.cam = cameras; a.R_in = R_in; a.t_in = t_in; a.row_begin = row_begin; a.row_end = row_end; a.verts = vertices;
-  a.num_rows = num_rows; a.has_pose = has_pose; a.tau = tau; a.num_det = num_det; a.max_points = max_points; a.iters = iters; a.chunks = chunks;
-  a.R_out = R_out; a.t_out = t_out; a.cost_in = cost_in; a.cost_out = cost_out; a.num_points = num_points; a.iters_used = iters_used;
-  a.status = status; a.normal_eq = normal_eq;
-  a.state = reinterpret_cast<RefineState*>(sp);
-  sp += (size_t)FP_REFINE_STATE_BYTES * num_det;
-  a.part = reinterpret_cast<double*>(sp);
-  sp += 8 * (size_t)FP_REFINE_RECORD * num_det * chunks;
-  a.err = reinterpret_cast<int32_t*>(sp);
-  HIP_TRY(hipMemsetAsync(a.err, 0, sizeof(int32_t), ST(stream)), "fp_depth_refine: clear");
+  a.lm = refine_lm_args(cameras, R_in, t_in, row_begin, row_end, vertices, num_rows, has_pose, num_det, max_points, iters, R_out, t_out, cost_in,
+                        cost_out, num_points, iters_used, status, normal_eq);
+  a.d = RefineDepthArgs{depth, num_images, H, W, 0, image_index, tau};
+  TRY(refine_check(fn, a.lm, nullptr, &a.d, nullptr));
+  a.state = static_cast<RefineState*>(scratch);
+  TRY(refine_carve(fn, a.lm, scratch, scratch_bytes, FP_DEPTH_REFINE_SCRATCH_BYTES(num_det, max_points), FP_REFINE_RECORD, nullptr, ST(stream)));
   TRY(launch_depth_refine(a, ST(stream)));
-  // the one wait of this call, after every iteration is enqueued: a bad row range or image index is reported here, never read
-  int32_t bad = 0;
-  HIP_TRY(hipMemcpyWithStream(&bad, a.err, sizeof(int32_t), hipMemcpyDeviceToHost, ST(stream)), "fp_depth_refine: status read");
-  FP_REQUIRE(bad <= 0, "fp_depth_refine: detection %d: bank rows outside [0, %lld) or more than max_points %d", bad - 1,
-             (long long)num_rows, max_points);
-  FP_REQUIRE(bad == 0, "fp_depth_refine: detection %d: image index outside [0, %d)", -bad - 1, num_images);
-  return FP_OK;
+  return refine_report(fn, a.lm, num_images, ST(stream));
 }
 
-// ------------------------------------------------------------------ joint refinement on features and depth
 int fp_rgbd_refine(const float* map, int64_t sb, int64_t sy, int64_t sx, int64_t sc, int gh, int gw, int C, int W, int H,
                    const double* feature_cameras, const double* A, const double* a_vec, const float* depth, int num_images, int Hd, int Wd,
                    const int32_t* image_index, const double* frame_cameras, const double* R_in, const double* t_in,
@@ -944,47 +958,23 @@ int fp_rgbd_refine(const float* map, int64_t sb, int64_t sy, int64_t sx, int64_t
                    void* scratch, size_t scratch_bytes, double* R_out, double* t_out, double* cost_in, double* cost_out,
                    int32_t* num_points, int32_t* num_depth_inliers, int32_t* iters_used, int32_t* status, double* normal_eq,
                    fp_stream_t stream) {
+  const char* fn = "fp_rgbd_refine";
   FP_REQUIRE(map && feature_cameras && A && a_vec && depth && image_index && frame_cameras && R_in && t_in && row_begin && row_end && feats &&
              vertices && has_pose && tau && scratch && R_out && t_out && cost_in && cost_out && num_points && num_depth_inliers && iters_used &&
              status, "fp_rgbd_refine: null pointer");
-  FP_REQUIRE(gh >= 2 && gw >= 2, "fp_rgbd_refine: the feature map is %d x %d, at least 2 x 2 needed", gh, gw);
-  FP_REQUIRE(C >= 1 && W >= 1 && H >= 1, "fp_rgbd_refine: C %d, image %d x %d", C, W, H);
-  FP_REQUIRE(sb >= 0 && sy >= 0 && sx >= 0 && sc >= 0, "fp_rgbd_refine: negative map stride");
-  FP_REQUIRE(num_images >= 1 && Hd >= 2 && Wd >= 2, "fp_rgbd_refine: %d depth images of %d x %d, at least one of 2 x 2 needed", num_images, Wd, Hd);
-  FP_REQUIRE(depth_weight >= 0.0 && depth_weight < INFINITY, "fp_rgbd_refine: depth_weight %g is not a finite number >= 0", depth_weight);
-  FP_REQUIRE(num_det >= 1 && num_det <= 65535, "fp_rgbd_refine: num_det %d outside [1, 65535]", num_det);
-  FP_REQUIRE(max_points >= 1 && num_rows >= 0, "fp_rgbd_refine: max_points %d, num_rows %lld", max_points, (long long)num_rows);
-  FP_REQUIRE(iters >= 0 && iters <= 1000, "fp_rgbd_refine: iters %d outside [0, 1000]", iters);
-  const size_t need = FP_RGBD_REFINE_SCRATCH_BYTES(num_det, max_points);
-  FP_REQUIRE(scratch_bytes >= need, "fp_rgbd_refine: scratch holds %zu bytes, %zu needed", scratch_bytes, need);
   static_assert(sizeof(RgbdState) <= FP_REFINE_STATE_BYTES, "FP_REFINE_STATE_BYTES");
-  const int chunks = (max_points + FP_REFINE_CHUNK - 1) / FP_REFINE_CHUNK;
-  char* sp = static_cast<char*>(scratch);
   RgbdRefineArgs a;
   memset(&a, 0, sizeof(a));
-  a.map = map; a.sb = sb; a.sy = sy; a.sx = sx; a.sc = sc; a.gh = gh; a.gw = gw; a.C = C; a.W = W; a.H = H;
-  a.fcam = feature_cameras; a.A = A; a.a = a_vec; a.depth = depth; a.num_images = num_images; a.Hd = Hd; a.Wd = Wd; a.image_index = image_index;
-  a.cam = frame_cameras; a.R_in = R_in; a.t_in = t_in; a.row_begin = row_begin; a.row_end = row_end; a.feats = feats; a.verts = vertices;
-  a.num_rows = num_rows; a.has_pose = has_pose; a.tau = tau; a.wd = depth_weight; a.num_det = num_det; a.max_points = max_points;
-  a.iters = iters; a.chunks = chunks;
-  a.R_out = R_out; a.t_out = t_out; a.cost_in = cost_in; a.cost_out = cost_out; a.num_points = num_points; a.num_depth_inliers = num_depth_inliers;
-  a.iters_used = iters_used; a.status = status; a.normal_eq = normal_eq;
-  a.state = reinterpret_cast<RgbdState*>(sp);
-  sp += (size_t)FP_REFINE_STATE_BYTES * num_det;
-  a.part = reinterpret_cast<double*>(sp);
-  sp += 16 * (size_t)FP_REFINE_RECORD * num_det * chunks;
-  a.valid = reinterpret_cast<uint8_t*>(sp);
-  sp += (((size_t)num_det * max_points + 7) / 8) * 8;
-  a.err = reinterpret_cast<int32_t*>(sp);
-  HIP_TRY(hipMemsetAsync(a.err, 0, sizeof(int32_t), ST(stream)), "fp_rgbd_refine: clear");
+  a.lm = refine_lm_args(frame_cameras, R_in, t_in, row_begin, row_end, vertices, num_rows, has_pose, num_det, max_points, iters, R_out, t_out,
+                        cost_in, cost_out, num_points, iters_used, status, normal_eq);
+  a.f = RefineMapArgs{map, sb, sy, sx, sc, gh, gw, C, 0, (double)W, (double)H, feats, nullptr};
+  a.d = RefineDepthArgs{depth, num_images, Hd, Wd, 0, image_index, tau};
+  a.fcam = feature_cameras; a.A = A; a.a = a_vec; a.wd = depth_weight; a.num_depth_inliers = num_depth_inliers;
+  TRY(refine_check(fn, a.lm, &a.f, &a.d, &depth_weight));
+  a.state = static_cast<RgbdState*>(scratch);
+  TRY(refine_carve(fn, a.lm, scratch, scratch_bytes, FP_RGBD_REFINE_SCRATCH_BYTES(num_det, max_points), 2 * FP_REFINE_RECORD, &a.f.valid, ST(stream)));
   TRY(launch_rgbd_refine(a, ST(stream)));
-  // the one wait of this call, after every iteration is enqueued: a bad row range or image index is reported here, never read
-  int32_t bad = 0;
-  HIP_TRY(hipMemcpyWithStream(&bad, a.err, sizeof(int32_t), hipMemcpyDeviceToHost, ST(stream)), "fp_rgbd_refine: status read");
-  FP_REQUIRE(bad <= 0, "fp_rgbd_refine: detection %d: bank rows outside [0, %lld) or more than max_points %d", bad - 1,
-             (long long)num_rows, max_points);
-  FP_REQUIRE(bad == 0, "fp_rgbd_refine: detection %d: image index outside [0, %d)", -bad - 1, num_images);
-  return FP_OK;
+  return refine_report(fn, a.lm, num_images, ST(stream));
 }
 
 // ------------------------------------------------------------------ VSD

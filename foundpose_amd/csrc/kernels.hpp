@@ -304,7 +304,7 @@ struct PoseAddArgs {
 };
 int launch_pose_add_errors(const PoseAddArgs& a, int num_pairs, int max_blocks, hipStream_t st);
 
-// ---------------------------------------------------------------- refine.hip
+// ---------------------------------------------------------------- refine.hip, depth_refine.hip, rgbd_refine.hip (shared parts: refine_terms.hpp)
 struct RefineState {       // Levenberg-Marquardt state of one detection (scratch, FP_REFINE_STATE_BYTES)
   double R[9], t[3];       // current pose
   double Rt[9], tt[3];     // trial pose (the next pass evaluates it)
@@ -313,46 +313,36 @@ struct RefineState {       // Levenberg-Marquardt state of one detection (scratc
   int p0, np;              // bank rows [p0, p0 + np)
   int it, active, pending, accepted, skipped, nvalid;
 };
-struct RefineArgs {
-  const float* map; long long sb, sy, sx, sc; int gh, gw, C, pad0; double W, H;
-  const double* cam; const double* R_in; const double* t_in;
-  const int32_t* row_begin; const int32_t* row_end; const float* feats; const float* verts; long long num_rows;
-  const int32_t* has_pose; int num_det, max_points, iters, chunks;
-  double* R_out; double* t_out; double* cost_in; double* cost_out; int32_t* num_points; int32_t* iters_used; int32_t* status;
-  double* normal_eq;       // [num_det, 28] or null
-  RefineState* state; double* part; uint8_t* valid; int32_t* err;
-};
-int launch_featuremetric_refine(const RefineArgs& a, hipStream_t st);
-
-// ---------------------------------------------------------------- depth_refine.hip (the LM state is refine.hip's RefineState)
-struct DepthRefineArgs {
-  const float* depth; int num_images, H, W, pad0; const int32_t* image_index;   // [num_images, H, W] mm, 0 = no measurement
-  const double* cam; const double* R_in; const double* t_in;
-  const int32_t* row_begin; const int32_t* row_end; const float* verts; long long num_rows;
-  const int32_t* has_pose; const double* tau; int num_det, max_points, iters, chunks;
-  double* R_out; double* t_out; double* cost_in; double* cost_out; int32_t* num_points; int32_t* iters_used; int32_t* status;
-  double* normal_eq;       // [num_det, 28] or null
-  RefineState* state; double* part; int32_t* err;
-};
-int launch_depth_refine(const DepthRefineArgs& a, hipStream_t st);
-
-// ---------------------------------------------------------------- rgbd_refine.hip (features and depth in one objective)
 struct RgbdState {         // scratch, FP_REFINE_STATE_BYTES: the shared LM state (H, g, E are those of the mixed objective) and the depth decision
   RefineState s;
   int ninl, use_depth;     // depth inliers at the input pose; whether the depth term takes part (depth_weight > 0 and ninl >= 6)
 };
-struct RgbdRefineArgs {
-  const float* map; long long sb, sy, sx, sc; int gh, gw, C, pad0; double W, H;    // the feature map and its (crop) camera's image size
+struct RefineLmArgs {      // what every refiner has: the camera the pose lives in, the input poses, the bank rows, the outputs, the scratch
+  const double* cam; const double* R_in; const double* t_in;
+  const int32_t* row_begin; const int32_t* row_end; const float* verts; long long num_rows;
+  const int32_t* has_pose; int num_det, max_points, iters, chunks;
+  double* R_out; double* t_out; double* cost_in; double* cost_out; int32_t* num_points; int32_t* iters_used; int32_t* status;
+  double* normal_eq;       // [num_det, 28] (rgbd: 57) or null
+  double* part; int32_t* err;
+};
+struct RefineMapArgs {     // the feature term: the map, its camera's image size, the points' features, the points valid for the term
+  const float* map; long long sb, sy, sx, sc; int gh, gw, C, pad0; double W, H;
+  const float* feats; uint8_t* valid;
+};
+struct RefineDepthArgs {   // the depth term
+  const float* depth; int num_images, H, W, pad0; const int32_t* image_index;   // [num_images, H, W] mm, 0 = no measurement
+  const double* tau;
+};
+struct RefineArgs { RefineLmArgs lm; RefineMapArgs f; RefineState* state; };
+int launch_featuremetric_refine(const RefineArgs& a, hipStream_t st);
+struct DepthRefineArgs { RefineLmArgs lm; RefineDepthArgs d; RefineState* state; };
+int launch_depth_refine(const DepthRefineArgs& a, hipStream_t st);
+struct RgbdRefineArgs {    // features and depth in one objective; lm.cam is the frame camera
+  RefineLmArgs lm; RefineMapArgs f; RefineDepthArgs d;
   const double* fcam;      // [num_det, 4] the feature camera
   const double* A; const double* a;    // [num_det, 9], [num_det, 3]: X_f = A X_c + a, frame camera -> feature camera
-  const float* depth; int num_images, Hd, Wd, pad1; const int32_t* image_index;
-  const double* cam;       // [num_det, 4] the frame camera, in which the pose lives
-  const double* R_in; const double* t_in;
-  const int32_t* row_begin; const int32_t* row_end; const float* feats; const float* verts; long long num_rows;
-  const int32_t* has_pose; const double* tau; double wd; int num_det, max_points, iters, chunks;
-  double* R_out; double* t_out; double* cost_in; double* cost_out; int32_t* num_points; int32_t* num_depth_inliers; int32_t* iters_used; int32_t* status;
-  double* normal_eq;       // [num_det, 57] or null
-  RgbdState* state; double* part; uint8_t* valid; int32_t* err;
+  double wd; int32_t* num_depth_inliers;
+  RgbdState* state;
 };
 int launch_rgbd_refine(const RgbdRefineArgs& a, hipStream_t st);
 

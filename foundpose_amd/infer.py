@@ -326,28 +326,25 @@ def _to_device_image(img) -> torch.Tensor:
     return (img.to("cuda", torch.float32) / 255.0) if img.dtype == torch.uint8 else img.to("cuda", torch.float32)
 
 
+def _bbox_diagonal_fraction(repre, fraction: float) -> float:
+    """fraction x the diagonal of the bounding box of repre.vertices (mm), computed on the host."""
+    v = repre.vertices.detach().cpu().numpy().astype(np.float64)
+    return fraction * float(np.linalg.norm(v.max(0) - v.min(0)))
+
+
 def depth_refine_tau(opts: InferOpts, repre) -> float:
     """The truncation distance of the depth refinement for one object (mm), computed once per object on the host."""
-    if opts.depth_refine_max_dist > 0:
-        return float(opts.depth_refine_max_dist)
-    v = repre.vertices.detach().cpu().numpy().astype(np.float64)
-    return 0.1 * float(np.linalg.norm(v.max(0) - v.min(0)))
+    return float(opts.depth_refine_max_dist) if opts.depth_refine_max_dist > 0 else _bbox_diagonal_fraction(repre, 0.1)
 
 
 def depth_pnp_tau(opts: InferOpts, repre) -> float:
     """The 3D inlier threshold of pnp_type "kabsch_depth" for one object (mm), computed once per object on the host."""
-    if opts.depth_pnp_inlier_thresh > 0:
-        return float(opts.depth_pnp_inlier_thresh)
-    v = repre.vertices.detach().cpu().numpy().astype(np.float64)
-    return 0.05 * float(np.linalg.norm(v.max(0) - v.min(0)))
+    return float(opts.depth_pnp_inlier_thresh) if opts.depth_pnp_inlier_thresh > 0 else _bbox_diagonal_fraction(repre, 0.05)
 
 
 def depth_verify_tau(opts: InferOpts, repre) -> float:
     """The tolerance of coarse_select_type "depth_verify" for one object (mm), computed once per object on the host."""
-    if opts.depth_verify_thresh > 0:
-        return float(opts.depth_verify_thresh)
-    v = repre.vertices.detach().cpu().numpy().astype(np.float64)
-    return 0.02 * float(np.linalg.norm(v.max(0) - v.min(0)))
+    return float(opts.depth_verify_thresh) if opts.depth_verify_thresh > 0 else _bbox_diagonal_fraction(repre, 0.02)
 
 
 def _check_frame_depth(frame: Dict[str, Any], why: str = "the final pose type refines against depth") -> None:

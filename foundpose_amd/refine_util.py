@@ -23,6 +23,73 @@ from .pnp_util import _intrinsics
 STATUS_REFINED, STATUS_NOT_IMPROVED, STATUS_SKIPPED = 0, 1, 2
 
 
+def _map_shape(feature_map: torch.Tensor) -> Tuple[int, int, int, int]:
+    if feature_map.dim() != 4:
+        raise ValueError("feature_map must be [B, gh, gw, C]")
+    B, gh, gw, C = feature_map.shape
+    if gh < 2 or gw < 2:
+        raise ValueError(f"the feature map is {gh} x {gw}: refinement needs at least 2 x 2 cells")
+    return B, gh, gw, C
+
+
+def _depth_stack(depth: torch.Tensor) -> torch.Tensor:
+    if depth.dim() == 2:
+        depth = depth[None]
+    if depth.dim() != 3:
+        raise ValueError("depth must be [N, H, W] or [H, W]")
+    H, W = depth.shape[1:]
+    if H < 2 or W < 2:
+        raise ValueError(f"the depth image is {H} x {W}: refinement needs at least 2 x 2 pixels")
+    return depth
+
+
+def _tau_per_detection(tau, B: int) -> torch.Tensor:
+    """tau, a number or one per detection -> [B] f64 on the host."""
+    tau_h = torch.as_tensor(tau, dtype=torch.float64).reshape(-1).cpu()
+    if tau_h.numel() == 1:
+        tau_h = tau_h.expand(B)
+    if tau_h.numel() != B:
+        raise ValueError(f"{tau_h.numel()} tau values for {B} detections")
+    return tau_h.contiguous()
+
+
+def _upload_cameras(cameras: Sequence[Any], B: int, dev) -> torch.Tensor:
+    return upload_async(torch.tensor([_intrinsics(c) for c in cameras], dtype=torch.float64).reshape(B, 4), dev)
+
+
+def _lm_inputs(B: int, R, t, row_begin, row_end, has_pose, feats, vertices, max_points: Optional[int]):
+    """The conversions every refiner makes, in the order they are enqueued, and the max_points rule: None is read back from the device.
+    -> (R [B, 9] f64, t [B, 3] f64, row_begin, row_end, has_pose i32, feats f32 or None, vertices f32, max_points >= 1)."""
+    Rin = R.to(torch.float64).reshape(B, 9).contiguous()
+    tin = t.to(torch.float64).reshape(B, 3).contiguous()
+    rb = row_begin.to(torch.int32).contiguous()
+    re = row_end.to(torch.int32).contiguous()
+    hp = has_pose.to(torch.int32).contiguous()
+    f32 = None if feats is None else feats.float().contiguous()
+    v32 = vertices.float().contiguous()
+    if max_points is None:
+        max_points = int(torch.where(hp != 0, re - rb, torch.zeros_like(re)).max().item()) if B else 0
+    return Rin, tin, rb, re, hp, f32, v32, max(1, int(max_points))
+
+
+def _lm_outputs(B: int, dev, normal_eq_width: int, depth_inliers: bool = False) -> Tuple[Dict[str, torch.Tensor], list]:
+    """Allocates a refiner's outputs.  -> (the result dict, the output pointers in the order of the C ABI -- the dict's own, then normal_eq);
+    normal_eq_width 0: no normal equations."""
+    f64, i32, empty = torch.float64, torch.int32, torch.empty
+    out = {"R": empty(B, 9, dtype=f64, device=dev), "t": empty(B, 3, dtype=f64, device=dev), "cost_in": empty(B, dtype=f64, device=dev),
+           "cost_out": empty(B, dtype=f64, device=dev), "num_points": empty(B, dtype=i32, device=dev)}
+    if depth_inliers:
+        out["num_depth_inliers"] = empty(B, dtype=i32, device=dev)
+    out["iters_used"], out["status"] = empty(B, dtype=i32, device=dev), empty(B, dtype=i32, device=dev)
+    neq = empty(B, normal_eq_width, dtype=f64, device=dev) if normal_eq_width else None
+    ptrs = [ptr(v) for v in out.values()]
+    ptrs.append(ptr(neq))
+    out["R"] = out["R"].reshape(B, 3, 3)
+    if neq is not None:
+        out["normal_eq"] = neq
+    return out, ptrs
+
+
 def refine_featuremetric(feature_map: torch.Tensor, image_size: Tuple[int, int], cameras: Sequence[Any], R: torch.Tensor, t: torch.Tensor,
                          row_begin: torch.Tensor, row_end: torch.Tensor, feats: torch.Tensor, vertices: torch.Tensor, has_pose: torch.Tensor,
                          iters: int = 30, return_normal_equations: bool = False, max_points: Optional[int] = None) -> Dict[str, torch.Tensor]:
@@ -33,11 +100,7 @@ def refine_featuremetric(feature_map: torch.Tensor, image_size: Tuple[int, int],
     num_points, iters_used, status [B] i32 (0 refined, 1 no step accepted, 2 skipped), + normal_eq [B, 28] f64 (H upper
     triangle row-major | g | E at the input pose) with return_normal_equations."""
     require_cuda(feature_map, R, t, row_begin, row_end, feats, vertices, has_pose)
-    if feature_map.dim() != 4:
-        raise ValueError("feature_map must be [B, gh, gw, C]")
-    B, gh, gw, C = feature_map.shape
-    if gh < 2 or gw < 2:
-        raise ValueError(f"the feature map is {gh} x {gw}: refinement needs at least 2 x 2 cells")
+    B, gh, gw, C = _map_shape(feature_map)
     if int(iters) < 0:
         raise ValueError("iters must be >= 0")
     if feats.dim() != 2 or feats.shape[1] != C or vertices.shape != (feats.shape[0], 3):
@@ -47,33 +110,13 @@ def refine_featuremetric(feature_map: torch.Tensor, image_size: Tuple[int, int],
     dev = feature_map.device
     fmap = feature_map if feature_map.dtype == torch.float32 else feature_map.float()
     W, H = int(image_size[0]), int(image_size[1])
-    cam = upload_async(torch.tensor([_intrinsics(c) for c in cameras], dtype=torch.float64).reshape(B, 4), dev)
-    Rin = R.to(torch.float64).reshape(B, 9).contiguous()
-    tin = t.to(torch.float64).reshape(B, 3).contiguous()
-    rb = row_begin.to(torch.int32).contiguous()
-    re = row_end.to(torch.int32).contiguous()
-    hp = has_pose.to(torch.int32).contiguous()
-    f32 = feats.float().contiguous()
-    v32 = vertices.float().contiguous()
-    if max_points is None:
-        max_points = int(torch.where(hp != 0, re - rb, torch.zeros_like(re)).max().item()) if B else 0
-    max_points = max(1, int(max_points))
+    cam = _upload_cameras(cameras, B, dev)
+    Rin, tin, rb, re, hp, f32, v32, max_points = _lm_inputs(B, R, t, row_begin, row_end, has_pose, feats, vertices, max_points)
     scratch = torch.empty(refine_scratch_bytes(B, max_points), dtype=torch.uint8, device=dev)
-    Ro = torch.empty(B, 9, dtype=torch.float64, device=dev)
-    to = torch.empty(B, 3, dtype=torch.float64, device=dev)
-    cin = torch.empty(B, dtype=torch.float64, device=dev)
-    cout = torch.empty(B, dtype=torch.float64, device=dev)
-    npts = torch.empty(B, dtype=torch.int32, device=dev)
-    used = torch.empty(B, dtype=torch.int32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    neq = torch.empty(B, 28, dtype=torch.float64, device=dev) if return_normal_equations else None
+    out, outs = _lm_outputs(B, dev, 28 if return_normal_equations else 0)
     sb, sy, sx, sc = fmap.stride()
     call("fp_featuremetric_refine", ptr(fmap), sb, sy, sx, sc, gh, gw, C, W, H, ptr(cam), ptr(Rin), ptr(tin), ptr(rb), ptr(re), ptr(f32), ptr(v32),
-         int(f32.shape[0]), ptr(hp), B, max_points, int(iters), ptr(scratch), scratch.numel(), ptr(Ro), ptr(to), ptr(cin), ptr(cout), ptr(npts),
-         ptr(used), ptr(status), ptr(neq), stream())
-    out = {"R": Ro.reshape(B, 3, 3), "t": to, "cost_in": cin, "cost_out": cout, "num_points": npts, "iters_used": used, "status": status}
-    if neq is not None:
-        out["normal_eq"] = neq
+         int(f32.shape[0]), ptr(hp), B, max_points, int(iters), ptr(scratch), scratch.numel(), *outs, stream())
     return out
 
 
@@ -116,13 +159,8 @@ def refine_depth(depth: torch.Tensor, image_index: torch.Tensor, cameras: Sequen
     a number or one per detection.  max_points bounds row_end - row_begin (None: read back from the device).
     -> refine_featuremetric's dict; num_points counts the inliers at the input pose, cost = sum min(r^2, tau^2) / points."""
     require_cuda(depth, image_index, R, t, row_begin, row_end, vertices, has_pose)
-    if depth.dim() == 2:
-        depth = depth[None]
-    if depth.dim() != 3:
-        raise ValueError("depth must be [N, H, W] or [H, W]")
+    depth = _depth_stack(depth)
     N, H, W = depth.shape
-    if H < 2 or W < 2:
-        raise ValueError(f"the depth image is {H} x {W}: refinement needs at least 2 x 2 pixels")
     if int(iters) < 0:
         raise ValueError("iters must be >= 0")
     B = int(R.shape[0])
@@ -131,39 +169,16 @@ def refine_depth(depth: torch.Tensor, image_index: torch.Tensor, cameras: Sequen
     if vertices.dim() != 2 or vertices.shape[1] != 3:
         raise ValueError(f"vertices {tuple(vertices.shape)} are not [N, 3]")
     dev = depth.device
-    tau_h = torch.as_tensor(tau, dtype=torch.float64).reshape(-1).cpu()
-    if tau_h.numel() == 1:
-        tau_h = tau_h.expand(B)
-    if tau_h.numel() != B:
-        raise ValueError(f"{tau_h.numel()} tau values for {B} detections")
+    tau_h = _tau_per_detection(tau, B)
     d32 = depth.float().contiguous()
-    cam = upload_async(torch.tensor([_intrinsics(c) for c in cameras], dtype=torch.float64).reshape(B, 4), dev)
-    tau_d = upload_async(tau_h.contiguous(), dev)
+    cam = _upload_cameras(cameras, B, dev)
+    tau_d = upload_async(tau_h, dev)
     ii = image_index.to(torch.int32).contiguous()
-    Rin = R.to(torch.float64).reshape(B, 9).contiguous()
-    tin = t.to(torch.float64).reshape(B, 3).contiguous()
-    rb = row_begin.to(torch.int32).contiguous()
-    re = row_end.to(torch.int32).contiguous()
-    hp = has_pose.to(torch.int32).contiguous()
-    v32 = vertices.float().contiguous()
-    if max_points is None:
-        max_points = int(torch.where(hp != 0, re - rb, torch.zeros_like(re)).max().item()) if B else 0
-    max_points = max(1, int(max_points))
+    Rin, tin, rb, re, hp, _, v32, max_points = _lm_inputs(B, R, t, row_begin, row_end, has_pose, None, vertices, max_points)
     scratch = torch.empty(depth_refine_scratch_bytes(B, max_points), dtype=torch.uint8, device=dev)
-    Ro = torch.empty(B, 9, dtype=torch.float64, device=dev)
-    to = torch.empty(B, 3, dtype=torch.float64, device=dev)
-    cin = torch.empty(B, dtype=torch.float64, device=dev)
-    cout = torch.empty(B, dtype=torch.float64, device=dev)
-    npts = torch.empty(B, dtype=torch.int32, device=dev)
-    used = torch.empty(B, dtype=torch.int32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    neq = torch.empty(B, 28, dtype=torch.float64, device=dev) if return_normal_equations else None
+    out, outs = _lm_outputs(B, dev, 28 if return_normal_equations else 0)
     call("fp_depth_refine", ptr(d32), N, H, W, ptr(ii), ptr(cam), ptr(Rin), ptr(tin), ptr(rb), ptr(re), ptr(v32), int(v32.shape[0]), ptr(hp), ptr(tau_d),
-         B, max_points, int(iters), ptr(scratch), scratch.numel(), ptr(Ro), ptr(to), ptr(cin), ptr(cout), ptr(npts), ptr(used), ptr(status), ptr(neq),
-         stream())
-    out = {"R": Ro.reshape(B, 3, 3), "t": to, "cost_in": cin, "cost_out": cout, "num_points": npts, "iters_used": used, "status": status}
-    if neq is not None:
-        out["normal_eq"] = neq
+         B, max_points, int(iters), ptr(scratch), scratch.numel(), *outs, stream())
     return out
 
 
@@ -173,6 +188,30 @@ def _pose_matrices(R, t) -> np.ndarray:
     T = np.tile(np.eye(4), (len(R), 1, 1))
     T[:, :3, :3], T[:, :3, 3] = R.astype(np.float64).reshape(-1, 3, 3), t.astype(np.float64).reshape(-1, 3)
     return T
+
+
+def _into_frame_cameras(pose: Dict[str, torch.Tensor], frame_cameras: Sequence[Any], solve_cameras: Sequence[Any], dev):
+    """Moves pose["R"] / pose["t"] from solve_cameras into frame_cameras: inv(frame.T_world_from_eye) @ solve.T_world_from_eye @ T_m2c in
+    fp64.  -> (R, t, back): back [B, 4, 4] is the inverse move, None where both cameras are the same object and nothing is converted."""
+    if all(f is s for f, s in zip(frame_cameras, solve_cameras)):
+        return pose["R"], pose["t"], None
+    rel = np.stack([np.linalg.inv(np.asarray(f.T_world_from_eye, np.float64)) @ np.asarray(s.T_world_from_eye, np.float64)
+                    for f, s in zip(frame_cameras, solve_cameras)])
+    T = rel @ _pose_matrices(pose["R"], pose["t"])
+    R, t = upload_async(torch.from_numpy(T[:, :3, :3].copy()), dev), upload_async(torch.from_numpy(T[:, :3, 3].copy()), dev)
+    return R, t, np.linalg.inv(rel)
+
+
+def _back_to_solve_cameras(out: Dict[str, torch.Tensor], pose: Dict[str, torch.Tensor], back: Optional[np.ndarray], dev) -> Dict[str, torch.Tensor]:
+    """Moves a refiner's out["R"] / out["t"] back with _into_frame_cameras's `back`; poses whose status is not STATUS_REFINED did not move
+    and keep the bits they came with in `pose`."""
+    if back is not None:
+        moved = (out["status"] == STATUS_REFINED).cpu().numpy()
+        T = back @ _pose_matrices(out["R"], out["t"])
+        T0 = _pose_matrices(pose["R"], pose["t"])
+        T[~moved] = T0[~moved]
+        out["R"], out["t"] = torch.from_numpy(T[:, :3, :3].copy()).to(dev), torch.from_numpy(T[:, :3, 3].copy()).to(dev)
+    return out
 
 
 def refine_best_coarse_depth(res: MatchResult, pose: Dict[str, torch.Tensor], bank: DeviceBank, det_obj: Optional[Sequence[int]],
@@ -188,23 +227,10 @@ def refine_best_coarse_depth(res: MatchResult, pose: Dict[str, torch.Tensor], ba
     det_obj = [0] * B if det_obj is None else list(det_obj)
     rb, re, ok = best_template_rows(res, pose, bank, det_obj)
     dev = res.template_ids.device
-    same = all(f is s for f, s in zip(frame_cameras, solve_cameras))
-    R, t = pose["R"], pose["t"]
-    if not same:
-        rel = np.stack([np.linalg.inv(np.asarray(f.T_world_from_eye, np.float64)) @ np.asarray(s.T_world_from_eye, np.float64)
-                        for f, s in zip(frame_cameras, solve_cameras)])
-        T = rel @ _pose_matrices(R, t)
-        R, t = upload_async(torch.from_numpy(T[:, :3, :3].copy()), dev), upload_async(torch.from_numpy(T[:, :3, 3].copy()), dev)
+    R, t, back = _into_frame_cameras(pose, frame_cameras, solve_cameras, dev)
     ii = image_index if isinstance(image_index, torch.Tensor) else upload_async(torch.tensor(list(image_index), dtype=torch.int32), dev)
     out = refine_depth(depth, ii, frame_cameras, R, t, rb, re, bank.vertices, ok, tau, iters, max_points=bank.p_max)
-    if not same:
-        # detections whose pose did not move keep the solve-camera pose they came with, bit for bit
-        moved = (out["status"] == STATUS_REFINED).cpu().numpy()
-        T = np.linalg.inv(rel) @ _pose_matrices(out["R"], out["t"])
-        T0 = _pose_matrices(pose["R"], pose["t"])
-        T[~moved] = T0[~moved]
-        out["R"], out["t"] = torch.from_numpy(T[:, :3, :3].copy()).to(dev), torch.from_numpy(T[:, :3, 3].copy()).to(dev)
-    return out
+    return _back_to_solve_cameras(out, pose, back, dev)
 
 
 def refine_rgbd(feature_map: torch.Tensor, image_size: Tuple[int, int], feature_cameras: Sequence[Any], A: torch.Tensor, a: torch.Tensor,
@@ -219,18 +245,9 @@ def refine_rgbd(feature_map: torch.Tensor, image_size: Tuple[int, int], feature_
     -> refine_depth's dict (num_points: the valid points of the feature term) + num_depth_inliers [B] i32, the depth inliers at the input
     pose; with return_normal_equations normal_eq [B, 57] f64: H_f | g_f | E_f, H_d | g_d | E_d, E at the input pose."""
     require_cuda(feature_map, A, a, depth, image_index, R, t, row_begin, row_end, feats, vertices, has_pose)
-    if feature_map.dim() != 4:
-        raise ValueError("feature_map must be [B, gh, gw, C]")
-    B, gh, gw, C = feature_map.shape
-    if gh < 2 or gw < 2:
-        raise ValueError(f"the feature map is {gh} x {gw}: refinement needs at least 2 x 2 cells")
-    if depth.dim() == 2:
-        depth = depth[None]
-    if depth.dim() != 3:
-        raise ValueError("depth must be [N, H, W] or [H, W]")
+    B, gh, gw, C = _map_shape(feature_map)
+    depth = _depth_stack(depth)
     N, Hd, Wd = depth.shape
-    if Hd < 2 or Wd < 2:
-        raise ValueError(f"the depth image is {Hd} x {Wd}: refinement needs at least 2 x 2 pixels")
     if int(iters) < 0:
         raise ValueError("iters must be >= 0")
     if not (float(depth_weight) >= 0.0 and float(depth_weight) < float("inf")):
@@ -242,48 +259,23 @@ def refine_rgbd(feature_map: torch.Tensor, image_size: Tuple[int, int], feature_
     if tuple(A.shape) != (B, 3, 3) or tuple(a.shape) != (B, 3):
         raise ValueError(f"A {tuple(A.shape)} / a {tuple(a.shape)} are not [{B}, 3, 3] / [{B}, 3]")
     dev = feature_map.device
-    tau_h = torch.as_tensor(tau, dtype=torch.float64).reshape(-1).cpu()
-    if tau_h.numel() == 1:
-        tau_h = tau_h.expand(B)
-    if tau_h.numel() != B:
-        raise ValueError(f"{tau_h.numel()} tau values for {B} detections")
+    tau_h = _tau_per_detection(tau, B)
     fmap = feature_map if feature_map.dtype == torch.float32 else feature_map.float()
     W, H = int(image_size[0]), int(image_size[1])
-    fcam = upload_async(torch.tensor([_intrinsics(c) for c in feature_cameras], dtype=torch.float64).reshape(B, 4), dev)
-    cam = upload_async(torch.tensor([_intrinsics(c) for c in frame_cameras], dtype=torch.float64).reshape(B, 4), dev)
-    tau_d = upload_async(tau_h.contiguous(), dev)
+    fcam = _upload_cameras(feature_cameras, B, dev)
+    cam = _upload_cameras(frame_cameras, B, dev)
+    tau_d = upload_async(tau_h, dev)
     Ain = A.to(torch.float64).reshape(B, 9).contiguous()
     ain = a.to(torch.float64).reshape(B, 3).contiguous()
     d32 = depth.float().contiguous()
     ii = image_index.to(torch.int32).contiguous()
-    Rin = R.to(torch.float64).reshape(B, 9).contiguous()
-    tin = t.to(torch.float64).reshape(B, 3).contiguous()
-    rb = row_begin.to(torch.int32).contiguous()
-    re = row_end.to(torch.int32).contiguous()
-    hp = has_pose.to(torch.int32).contiguous()
-    f32 = feats.float().contiguous()
-    v32 = vertices.float().contiguous()
-    if max_points is None:
-        max_points = int(torch.where(hp != 0, re - rb, torch.zeros_like(re)).max().item()) if B else 0
-    max_points = max(1, int(max_points))
+    Rin, tin, rb, re, hp, f32, v32, max_points = _lm_inputs(B, R, t, row_begin, row_end, has_pose, feats, vertices, max_points)
     scratch = torch.empty(rgbd_refine_scratch_bytes(B, max_points), dtype=torch.uint8, device=dev)
-    Ro = torch.empty(B, 9, dtype=torch.float64, device=dev)
-    to = torch.empty(B, 3, dtype=torch.float64, device=dev)
-    cin = torch.empty(B, dtype=torch.float64, device=dev)
-    cout = torch.empty(B, dtype=torch.float64, device=dev)
-    npts = torch.empty(B, dtype=torch.int32, device=dev)
-    ninl = torch.empty(B, dtype=torch.int32, device=dev)
-    used = torch.empty(B, dtype=torch.int32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    neq = torch.empty(B, 57, dtype=torch.float64, device=dev) if return_normal_equations else None
+    out, outs = _lm_outputs(B, dev, 57 if return_normal_equations else 0, depth_inliers=True)
     sb, sy, sx, sc = fmap.stride()
     call("fp_rgbd_refine", ptr(fmap), sb, sy, sx, sc, gh, gw, C, W, H, ptr(fcam), ptr(Ain), ptr(ain), ptr(d32), N, Hd, Wd, ptr(ii), ptr(cam), ptr(Rin),
          ptr(tin), ptr(rb), ptr(re), ptr(f32), ptr(v32), int(f32.shape[0]), ptr(hp), ptr(tau_d), float(depth_weight), B, max_points, int(iters),
-         ptr(scratch), scratch.numel(), ptr(Ro), ptr(to), ptr(cin), ptr(cout), ptr(npts), ptr(ninl), ptr(used), ptr(status), ptr(neq), stream())
-    out = {"R": Ro.reshape(B, 3, 3), "t": to, "cost_in": cin, "cost_out": cout, "num_points": npts, "num_depth_inliers": ninl, "iters_used": used,
-           "status": status}
-    if neq is not None:
-        out["normal_eq"] = neq
+         ptr(scratch), scratch.numel(), *outs, stream())
     return out
 
 
@@ -302,24 +294,10 @@ def refine_best_coarse_rgbd(res: MatchResult, best: Dict[str, torch.Tensor], ban
     det_obj = [0] * B if det_obj is None else list(det_obj)
     rb, re, ok = best_template_rows(res, best, bank, det_obj)
     dev = res.template_ids.device
-    same = all(f is s for f, s in zip(frame_cameras, solve_cameras))
-    R, t = best["R"], best["t"]
-    Aa = np.tile(np.eye(4), (B, 1, 1))
-    if not same:
-        rel = np.stack([np.linalg.inv(np.asarray(f.T_world_from_eye, np.float64)) @ np.asarray(s.T_world_from_eye, np.float64)
-                        for f, s in zip(frame_cameras, solve_cameras)])
-        Aa = np.linalg.inv(rel)
-        T = rel @ _pose_matrices(R, t)
-        R, t = upload_async(torch.from_numpy(T[:, :3, :3].copy()), dev), upload_async(torch.from_numpy(T[:, :3, 3].copy()), dev)
+    R, t, back = _into_frame_cameras(best, frame_cameras, solve_cameras, dev)
+    Aa = np.tile(np.eye(4), (B, 1, 1)) if back is None else back   # frame camera -> feature camera: the inverse of that move
     A, a = upload_async(torch.from_numpy(Aa[:, :3, :3].copy()), dev), upload_async(torch.from_numpy(Aa[:, :3, 3].copy()), dev)
     ii = image_index if isinstance(image_index, torch.Tensor) else upload_async(torch.tensor(list(image_index), dtype=torch.int32), dev)
     out = refine_rgbd(res.feature_map, image_size, solve_cameras, A, a, depth, ii, frame_cameras, R, t, rb, re, bank.feats, bank.vertices, ok, tau,
                       depth_weight, iters, max_points=bank.p_max)
-    if not same:
-        # detections whose pose did not move keep the solve-camera pose they came with, bit for bit
-        moved = (out["status"] == STATUS_REFINED).cpu().numpy()
-        T = Aa @ _pose_matrices(out["R"], out["t"])
-        T0 = _pose_matrices(best["R"], best["t"])
-        T[~moved] = T0[~moved]
-        out["R"], out["t"] = torch.from_numpy(T[:, :3, :3].copy()).to(dev), torch.from_numpy(T[:, :3, 3].copy()).to(dev)
-    return out
+    return _back_to_solve_cameras(out, best, back, dev)
