@@ -72,6 +72,10 @@ _PROTOS = {
     "fp_proposal_scores": [vp, i32, i32, vp, i32, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp],
     "fp_proposal_rank": [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "fp_box_iou": [vp, i32, vp, i32, vp, vp, vp],
+    "fp_mask_pack": [vp, i32, i32, i32, vp, vp, vp],
+    "fp_group_mask_iou": [vp, i32, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp],
+    "fp_group_box_iou": [vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp],
+    "fp_coco_match": [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp],
     "fp_sample_bilinear": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp],
     "fp_pca_project": [vp, i32, i32, vp, i32, vp, vp, vp],
     "fp_vit_forward": [C.POINTER(VitModel), C.POINTER(VitWorkspace), vp, i32, i32, i32, i32, vp],

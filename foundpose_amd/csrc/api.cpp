@@ -483,6 +483,69 @@ int fp_box_iou(const int32_t* boxes, int num_boxes, const int32_t* pairs, int nu
   return launch_box_iou(a, ST(stream));
 }
 
+// ------------------------------------------------------------------ COCO average precision of detections
+int fp_mask_pack(const uint8_t* masks, int num_masks, int H, int W, uint64_t* out_words, int32_t* out_area, fp_stream_t stream) {
+  FP_REQUIRE(num_masks >= 0, "fp_mask_pack: %d masks", num_masks);
+  if (num_masks == 0) return FP_OK;
+  FP_REQUIRE(masks && out_words && out_area, "fp_mask_pack: null pointer");
+  MaskPackArgs a;
+  memset(&a, 0, sizeof(a));
+  a.masks = masks; a.H = H; a.W = W; a.Wq = W >= 1 ? (W - 1) / 64 + 1 : 0; a.words = reinterpret_cast<unsigned long long*>(out_words); a.area = out_area;
+  return launch_mask_pack(a, num_masks, ST(stream));
+}
+
+static GroupTables group_tables(const int32_t* est_off, const int32_t* gt_off, const int32_t* pair_off, int num_groups, int num_a, int num_b,
+                                int num_pairs) {
+  GroupTables t;
+  t.est_off = est_off; t.gt_off = gt_off; t.pair_off = pair_off; t.n_groups = num_groups; t.n_a = num_a; t.n_b = num_b; t.n_pairs = num_pairs;
+  return t;
+}
+
+int fp_group_mask_iou(const uint64_t* words_a, int num_a, const uint64_t* words_b, int num_b, int L, const int32_t* est_off,
+                      const int32_t* gt_off, const int32_t* pair_off, int num_groups, int num_pairs, int32_t* scratch_tiles,
+                      int32_t* out_counts, double* out_overlap, int32_t* out_status, fp_stream_t stream) {
+  FP_REQUIRE(num_groups >= 0 && num_a >= 0 && num_b >= 0 && num_pairs >= 0, "fp_group_mask_iou: negative count");
+  if (num_groups == 0 || num_pairs == 0) return FP_OK;
+  FP_REQUIRE(est_off && gt_off && pair_off && scratch_tiles && out_counts && out_overlap && out_status, "fp_group_mask_iou: null pointer");
+  FP_REQUIRE((words_a || num_a == 0) && (words_b || num_b == 0), "fp_group_mask_iou: null words");
+  GroupMaskIouArgs a;
+  memset(&a, 0, sizeof(a));
+  a.t = group_tables(est_off, gt_off, pair_off, num_groups, num_a, num_b, num_pairs);
+  a.words_a = reinterpret_cast<const unsigned long long*>(words_a); a.words_b = reinterpret_cast<const unsigned long long*>(words_b); a.L = L;
+  a.tile_off = scratch_tiles; a.counts = out_counts; a.overlap = out_overlap; a.status = out_status;
+  return launch_group_mask_iou(a, ST(stream));
+}
+
+int fp_group_box_iou(const double* boxes_a, int num_a, const double* boxes_b, int num_b, const int32_t* est_off, const int32_t* gt_off,
+                     const int32_t* pair_off, int num_groups, int num_pairs, double* out_overlap, int32_t* out_status, fp_stream_t stream) {
+  FP_REQUIRE(num_groups >= 0 && num_a >= 0 && num_b >= 0 && num_pairs >= 0, "fp_group_box_iou: negative count");
+  if (num_groups == 0 || num_pairs == 0) return FP_OK;
+  FP_REQUIRE(est_off && gt_off && pair_off && out_overlap && out_status, "fp_group_box_iou: null pointer");
+  FP_REQUIRE((boxes_a || num_a == 0) && (boxes_b || num_b == 0), "fp_group_box_iou: null boxes");
+  GroupBoxIouArgs a;
+  memset(&a, 0, sizeof(a));
+  a.t = group_tables(est_off, gt_off, pair_off, num_groups, num_a, num_b, num_pairs);
+  a.boxes_a = boxes_a; a.boxes_b = boxes_b; a.overlap = out_overlap; a.status = out_status;
+  return launch_group_box_iou(a, ST(stream));
+}
+
+int fp_coco_match(const int32_t* est_off, const int32_t* gt_off, const int32_t* pair_off, int num_groups, const double* overlap,
+                  int num_pairs, const int32_t* gt_ignore, int num_gt, const double* ths, int num_ths, int num_est, int8_t* out_flag,
+                  int32_t* out_matched_gt, fp_stream_t stream) {
+  FP_REQUIRE(num_groups >= 0 && num_pairs >= 0 && num_gt >= 0 && num_est >= 0, "fp_coco_match: negative count");
+  FP_REQUIRE(num_ths >= 1 && num_ths <= FP_DETECTION_MAX_THS, "fp_coco_match: num_ths must be in [1, %d] (got %d)", FP_DETECTION_MAX_THS, num_ths);
+  if (num_groups == 0) return FP_OK;
+  FP_REQUIRE(est_off && gt_off && pair_off && ths, "fp_coco_match: null pointer");
+  FP_REQUIRE((out_flag && out_matched_gt) || num_est == 0, "fp_coco_match: null output");
+  FP_REQUIRE(overlap || num_pairs == 0, "fp_coco_match: null overlap");
+  FP_REQUIRE(gt_ignore || num_gt == 0, "fp_coco_match: null gt_ignore");
+  CocoMatchArgs a;
+  memset(&a, 0, sizeof(a));
+  a.t = group_tables(est_off, gt_off, pair_off, num_groups, num_est, num_gt, num_pairs);
+  a.overlap = overlap; a.gt_ignore = gt_ignore; a.ths = ths; a.T = num_ths; a.flag = (signed char*)out_flag; a.matched_gt = out_matched_gt;
+  return launch_coco_match(a, ST(stream));
+}
+
 // ------------------------------------------------------------------ ViT building blocks
 int fp_patchify(const float* images, int B, int H, int W, int patch, void* out, int ld_out, int out_dtype,
                 fp_stream_t stream) {

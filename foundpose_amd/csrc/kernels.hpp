@@ -548,6 +548,61 @@ struct DetApArgs {
 };
 int launch_detection_ap(const DetApArgs& a, int num_objects, hipStream_t st);
 
+// ---------------------------------------------------------------- coco_eval.hip
+constexpr int CE_THREADS = 256;                 // a workgroup of the packing and of the overlap kernels
+#ifndef FP_COCO_TILE_A                          // (tools/bench_coco.py times a 1 x 1 build beside this one: tools/build_variant.sh ... -DFP_COCO_TILE_A=1 -DFP_COCO_TILE_B=1)
+#define FP_COCO_TILE_A 4
+#endif
+#ifndef FP_COCO_TILE_B
+#define FP_COCO_TILE_B 4
+#endif
+constexpr int CE_TILE_A = FP_COCO_TILE_A, CE_TILE_B = FP_COCO_TILE_B;  // rows of a x rows of b whose words one workgroup holds in registers
+struct MaskPackArgs {
+  const unsigned char* masks;  // [N, H, W] 0 / non-zero
+  int H, W, Wq;                // Wq = ceil(W / 64), filled in by the entry point
+  unsigned long long* words;   // [N, H, Wq] bit x % 64 of word (y, x / 64) = pixel (x, y)
+  int* area;                   // [N] set pixels
+};
+int launch_mask_pack(const MaskPackArgs& a, int num_masks, hipStream_t st);
+
+struct GroupTables {           // the three tables fp_detection_match takes, for rows of a (estimates) and of b (GT instances)
+  const int* est_off;          // [groups + 1] each group's rows of a
+  const int* gt_off;           // [groups + 1] its rows of b
+  const int* pair_off;         // [groups + 1] its output rows: E_g x G_g, row-major
+  int n_groups, n_a, n_b, n_pairs;
+};
+struct GroupMaskIouArgs {
+  GroupTables t;
+  const unsigned long long* words_a;  // [n_a, L]
+  const unsigned long long* words_b;  // [n_b, L]
+  int L;
+  int* tile_off;               // [groups + 1] scratch: where each group's tiles start
+  int* counts;                 // [n_pairs, 2] intersection, union
+  double* overlap;             // [n_pairs]
+  int* status;                 // [n_pairs] 0 scored, 2 union 0
+};
+int launch_group_mask_iou(const GroupMaskIouArgs& a, hipStream_t st);
+
+struct GroupBoxIouArgs {
+  GroupTables t;
+  const double* boxes_a;       // [n_a, 4] x, y, w, h
+  const double* boxes_b;       // [n_b, 4]
+  double* overlap;             // [n_pairs]
+  int* status;                 // [n_pairs] 0 scored, 2 union not > 0 or a row of no group
+};
+int launch_group_box_iou(const GroupBoxIouArgs& a, hipStream_t st);
+
+struct CocoMatchArgs {
+  GroupTables t;               // n_a = estimates, n_b = GT instances
+  const double* overlap;       // [n_pairs] as either overlap kernel wrote it
+  const int* gt_ignore;        // [n_b] != 0: an ignored instance
+  const double* ths;           // [T]
+  int T;
+  signed char* flag;           // [n_a, T] 1 matched non-ignored, 2 matched ignored, 0 unmatched
+  int* matched_gt;             // [n_a, T] the group-local GT index or -1
+};
+int launch_coco_match(const CocoMatchArgs& a, hipStream_t st);
+
 // ---------------------------------------------------------------- proposals.hip
 constexpr int PC_MAX_SIZE = 1024;      // the crop's side: the axis tables and three rows of it fit the 64 KiB of a workgroup's LDS
 constexpr int PS_MAX_K = 16;           // similarities averaged per (proposal, object)

@@ -673,3 +673,84 @@ def box_iou(boxes: torch.Tensor, pairs: torch.Tensor) -> Tuple[torch.Tensor, tor
     status = torch.empty(M, dtype=torch.int32, device=boxes.device)
     call("fp_box_iou", ptr(boxes), int(boxes.shape[0]), ptr(pairs), M, ptr(overlap), ptr(status), stream())
     return overlap, status
+
+
+# ---------------------------------------------------------------- COCO average precision of detections
+def mask_pack(masks: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp_mask_pack: masks uint8 [N, H, W] (0 / non-zero) -> (words [N, H, Wq] with Wq = ceil(W / 64), the uint64 words as torch.int64: bit
+    x % 64 of word (y, x / 64) is pixel (x, y), the bits beyond W are 0; area int32 [N])."""
+    _detection_tables("mask_pack", ((masks, torch.uint8),))
+    if masks.dim() != 3 or masks.shape[1] < 1 or masks.shape[2] < 1 or int(masks.shape[1]) * int(masks.shape[2]) > 1 << 30:
+        raise ValueError(f"mask_pack: masks must be uint8 [N, H, W] with H, W >= 1 and H W <= 2^30, got {tuple(masks.shape)}")
+    N, H, W = (int(v) for v in masks.shape)
+    words = torch.empty(N, H, (W + 63) // 64, dtype=torch.int64, device=masks.device)
+    area = torch.empty(N, dtype=torch.int32, device=masks.device)
+    call("fp_mask_pack", ptr(masks), N, H, W, ptr(words), ptr(area), stream())
+    return words, area
+
+
+def _group_tables(name: str, est_off: torch.Tensor, gt_off: torch.Tensor, pair_off: torch.Tensor) -> int:
+    _detection_tables(name, ((est_off, torch.int32), (gt_off, torch.int32), (pair_off, torch.int32)))
+    NG = int(est_off.shape[0]) - 1
+    if est_off.dim() != 1 or NG < 0 or tuple(gt_off.shape) != (NG + 1,) or tuple(pair_off.shape) != (NG + 1,):
+        raise ValueError(f"{name}: est_off, gt_off and pair_off must be int32 [NG + 1]")
+    return NG
+
+
+def group_mask_iou(words_a: torch.Tensor, words_b: torch.Tensor, est_off: torch.Tensor, gt_off: torch.Tensor, pair_off: torch.Tensor,
+                   num_pairs: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fp_group_mask_iou on device tables whose CONTENTS have been validated already (eval_coco.match_groups' callers build them): words_a
+    [Na, ...] and words_b [Nb, ...] as mask_pack wrote them (one row length L), est_off / gt_off / pair_off int32 [NG + 1].  -> (counts int32
+    [num_pairs, 2] = (intersection, union), overlap f64 [num_pairs], status int32 [num_pairs]: 0 scored, 2 union 0); a row of no group keeps
+    (0, 0), 0 and 2."""
+    NG = _group_tables("group_mask_iou", est_off, gt_off, pair_off)
+    _detection_tables("group_mask_iou", ((words_a, torch.int64), (words_b, torch.int64)))
+    if words_a.dim() < 2 or words_b.dim() < 2 or tuple(words_a.shape[1:]) != tuple(words_b.shape[1:]) or num_pairs < 0:
+        raise ValueError(f"group_mask_iou: words_a [Na, ...] and words_b [Nb, ...] of one row shape are needed, got {tuple(words_a.shape)} and {tuple(words_b.shape)}")
+    L = 1
+    for v in words_a.shape[1:]:
+        L *= int(v)
+    if not 1 <= L <= 1 << 24:
+        raise ValueError(f"group_mask_iou: rows of {L} words (1 .. 2^24)")
+    dev = words_a.device
+    counts = torch.zeros(num_pairs, 2, dtype=torch.int32, device=dev)
+    overlap = torch.zeros(num_pairs, dtype=torch.float64, device=dev)
+    status = torch.full((num_pairs,), 2, dtype=torch.int32, device=dev)
+    tiles = torch.empty(NG + 1, dtype=torch.int32, device=dev)
+    call("fp_group_mask_iou", ptr(words_a), int(words_a.shape[0]), ptr(words_b), int(words_b.shape[0]), L, ptr(est_off), ptr(gt_off), ptr(pair_off), NG,
+         int(num_pairs), ptr(tiles), ptr(counts), ptr(overlap), ptr(status), stream())
+    return counts, overlap, status
+
+
+def group_box_iou(boxes_a: torch.Tensor, boxes_b: torch.Tensor, est_off: torch.Tensor, gt_off: torch.Tensor, pair_off: torch.Tensor,
+                  num_pairs: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp_group_box_iou: boxes_a f64 [Na, 4] and boxes_b f64 [Nb, 4] as COCO's (x, y, w, h), the group tables as above.  -> (overlap f64
+    [num_pairs], status int32 [num_pairs]: 0 scored, 2 when the union is not > 0 or no group owns the row)."""
+    NG = _group_tables("group_box_iou", est_off, gt_off, pair_off)
+    _detection_tables("group_box_iou", ((boxes_a, torch.float64), (boxes_b, torch.float64)))
+    if boxes_a.dim() != 2 or boxes_a.shape[1] != 4 or boxes_b.dim() != 2 or boxes_b.shape[1] != 4 or num_pairs < 0:
+        raise ValueError(f"group_box_iou: boxes_a [Na, 4] and boxes_b [Nb, 4] are needed, got {tuple(boxes_a.shape)} and {tuple(boxes_b.shape)}")
+    overlap = torch.zeros(num_pairs, dtype=torch.float64, device=boxes_a.device)
+    status = torch.full((num_pairs,), 2, dtype=torch.int32, device=boxes_a.device)
+    call("fp_group_box_iou", ptr(boxes_a), int(boxes_a.shape[0]), ptr(boxes_b), int(boxes_b.shape[0]), ptr(est_off), ptr(gt_off), ptr(pair_off), NG,
+         int(num_pairs), ptr(overlap), ptr(status), stream())
+    return overlap, status
+
+
+def coco_match(est_off: torch.Tensor, gt_off: torch.Tensor, pair_off: torch.Tensor, overlap: torch.Tensor, gt_ignore: torch.Tensor,
+               ths: torch.Tensor, num_est: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp_coco_match on device tables whose CONTENTS have been validated already (eval_coco.match_groups checks them on the host before it
+    uploads them): the group tables, overlap f64 [P] (not read back), gt_ignore int32 [G], ths f64 [T].  -> (flag int8 [num_est, T],
+    matched_gt int32 [num_est, T]); an estimate of no group keeps flag 0 and matched_gt -1."""
+    NG = _group_tables("coco_match", est_off, gt_off, pair_off)
+    _detection_tables("coco_match", ((overlap, torch.float64), (gt_ignore, torch.int32), (ths, torch.float64)))
+    if ths.dim() != 1 or not 1 <= int(ths.shape[0]) <= DETECTION_MAX_THS:
+        raise ValueError(f"coco_match: ths must be [T] with 1 <= T <= {DETECTION_MAX_THS}, got {tuple(ths.shape)}")
+    if overlap.dim() != 1 or gt_ignore.dim() != 1 or num_est < 0:
+        raise ValueError("coco_match: table sizes do not match")
+    T = int(ths.shape[0])
+    flag = torch.zeros(num_est, T, dtype=torch.int8, device=overlap.device)
+    matched = torch.full((num_est, T), -1, dtype=torch.int32, device=overlap.device)
+    call("fp_coco_match", ptr(est_off), ptr(gt_off), ptr(pair_off), NG, ptr(overlap), int(overlap.shape[0]), ptr(gt_ignore), int(gt_ignore.shape[0]),
+         ptr(ths), T, int(num_est), ptr(flag), ptr(matched), stream())
+    return flag, matched

@@ -450,6 +450,56 @@ int fp_proposal_rank(const int32_t* best_obj, const float* best_score, const int
 int fp_box_iou(const int32_t* boxes, int num_boxes, const int32_t* pairs, int num_pairs, double* out_overlap, int32_t* out_status,
                fp_stream_t stream);
 
+/* COCO average precision of a detections file (foundpose_amd/eval_coco.py): BOP's 2D detection and 2D segmentation
+ * scores.  Restates the published behaviour of pycocotools' COCOeval for instances without iscrowd; tests/coco_ref.py restates every entry.
+ * 1 of 4: byte masks -> bit masks.  masks [num_masks, H, W] uint8, 0 unset / any non-zero byte set; H W at most 2^30.  out_words
+ * [num_masks, H, Wq] uint64 with Wq = ceil(W / 64): bit x % 64 of word (y, x / 64) is pixel (x, y), the bits beyond W in a row's last word
+ * are 0, EVERY word is written; out_area [num_masks] int32: the set pixels.  H, W < 1 or H W > 2^30 is refused; num_masks = 0 returns
+ * without a launch.  A mask's result depends on its own bytes only: it is the same bits alone, in any batch and at any position.  (Added
+ * without a change of FP_ABI_VERSION: no existing entry point changed.) */
+int fp_mask_pack(const uint8_t* masks, int num_masks, int H, int W, uint64_t* out_words, int32_t* out_area, fp_stream_t stream);
+
+/* ... 2 of 4: intersection over union of bit masks, group by group.  words_a [num_a, L] and words_b [num_b, L] uint64 as fp_mask_pack
+ * wrote them (L = H Wq, 1 <= L <= 2^24); est_off / gt_off / pair_off [num_groups + 1] int32, the three tables fp_detection_match takes:
+ * group g owns the rows [est_off[g], est_off[g + 1]) of a (E_g of them), [gt_off[g], gt_off[g + 1]) of b (G_g) and the E_g G_g output
+ * rows from pair_off[g], row-major [E_g x G_g].  Per pair, in integers: inter = sum popcount(a & b), union = area_a + (area_b - inter)
+ * with the areas the popcounts of the rows themselves; out_counts [num_pairs, 2] int32 = (inter, union); out_overlap [num_pairs] f64 =
+ * (double)inter / (double)union, one division of two integers converted to double; out_status [num_pairs] int32: 0 scored, 2 union 0
+ * (overlap 0).  Exact, so independent of any summation order.  Only rows of some group are written.  Offsets are clamped to their arrays
+ * and a group to the rows the outputs have; nothing is read through an offset as it arrived.  scratch_tiles: num_groups + 1 int32.
+ * A group's result depends on its own rows only: the same bytes alone, in any batch and at any position.  (Added without a change of
+ * FP_ABI_VERSION.) */
+int fp_group_mask_iou(const uint64_t* words_a, int num_a, const uint64_t* words_b, int num_b, int L, const int32_t* est_off,
+                      const int32_t* gt_off, const int32_t* pair_off, int num_groups, int num_pairs, int32_t* scratch_tiles,
+                      int32_t* out_counts, double* out_overlap, int32_t* out_status, fp_stream_t stream);
+
+/* ... 2 of 4 for boxes: boxes_a [num_a, 4] and boxes_b [num_b, 4] f64 as COCO's (x, y, w, h), the same group tables.  Per pair, in fp64,
+ * every step one rounded operation in this order (no FMA contraction):
+ *   iw = fmin(xa + wa, xb + wb) - fmax(xa, xb), ih alike in y; inter = (iw > 0 && ih > 0) ? iw ih : 0;
+ *   union = (wa ha + wb hb) - inter; overlap = inter / union.
+ * out_status: 0 scored; 2 when !(union > 0) -- a NaN too -- or for an output row that no group owns: the overlap is 0.  EVERY row of
+ * out_overlap / out_status [num_pairs] is written.  Offsets are clamped as above.  (Added without a change of FP_ABI_VERSION.) */
+int fp_group_box_iou(const double* boxes_a, int num_a, const double* boxes_b, int num_b, const int32_t* est_off, const int32_t* gt_off,
+                     const int32_t* pair_off, int num_groups, int num_pairs, double* out_overlap, int32_t* out_status, fp_stream_t stream);
+
+/* ... 3 of 4: COCO's matching rule, once per (group, threshold).  The group tables as above with a = the estimates, laid out IN RANK ORDER
+ * (the caller sorts by score descending, equal scores in input order, and cuts a group to max_dets), and b = the GT instances, G_g <=
+ * FP_DETECTION_MAX_GROUP_GT; overlap [num_pairs] f64 as either call above wrote it; gt_ignore [num_gt] int32 (!= 0: an ignored
+ * instance; the caller lays a group's non-ignored instances out first, as pycocotools does); ths [num_ths] f64 ON THE DEVICE, 1 <=
+ * num_ths <= FP_DETECTION_MAX_THS, every threshold in (0, 1] (the caller checks the values).  Rule per (group, t), for e = 0 .. E_g - 1:
+ * with b = fmin(ths[t], 1 - 1e-10) the candidates are the not yet matched instances with overlap >= b (a NaN never is); the estimate takes
+ * the non-ignored candidate of the highest overlap if there is one, otherwise the ignored candidate of the highest overlap; equal
+ * overlaps go to the HIGHER GT index; the matched instance is used up whether ignored or not.  This is the loop of evaluateImg in closed
+ * form: its `if ious < iou: continue` lets a later equal candidate replace an earlier one.
+ * out_flag [num_est, num_ths] int8: 1 matched to a non-ignored instance, 2 matched to an ignored one, 0 unmatched -- fp_detection_match's
+ * codes, so fp_detection_ap takes the flags as they are (an even number of columns: the caller repeats the last column of an odd
+ * num_ths); out_matched_gt [num_est, num_ths] int32: the group-local GT index or -1.  Only estimates of some group are written.  Offsets
+ * are clamped to their arrays, a group to 256 instances (the caller refuses more) and to the rows overlap has.  A group's result depends
+ * on its own data only: the same bytes alone, in any batch and at any position.  (Added without a change of FP_ABI_VERSION.) */
+int fp_coco_match(const int32_t* est_off, const int32_t* gt_off, const int32_t* pair_off, int num_groups, const double* overlap,
+                  int num_pairs, const int32_t* gt_ignore, int num_gt, const double* ths, int num_ths, int num_est, int8_t* out_flag,
+                  int32_t* out_matched_gt, fp_stream_t stream);
+
 /* sample_feature_map_at_points (utils/feature_util.py:100-131): bilinear grid_sample, zeros padding,
  * align_corners=False.  fmap addressed by element strides (image, channel, y, x); point_img (may be null)
  * maps each point to its image.  out [num_points, C]. */
