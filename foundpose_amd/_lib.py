@@ -72,6 +72,8 @@ _PROTOS = {
     "fp_proposal_scores": [vp, i32, i32, vp, i32, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp],
     "fp_proposal_rank": [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "fp_box_iou": [vp, i32, vp, i32, vp, vp, vp],
+    "fp_proposal_patch_cover": [vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp],
+    "fp_proposal_appearance": [vp, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp],
     "fp_mask_pack": [vp, i32, i32, i32, vp, vp, vp],
     "fp_group_mask_iou": [vp, i32, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp],
     "fp_group_box_iou": [vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp],
@@ -230,6 +232,7 @@ def rgbd_refine_scratch_bytes(num_det: int, max_points: int) -> int:
 
 
 PROPOSAL_MAX_SIZE, PROPOSAL_MAX_K, PROPOSAL_MAX_RANKED = 1024, 16, 4096  # FP_PROPOSAL_MAX_* of the header
+APPEARANCE_MAX_DIM, APPEARANCE_MAX_PATCHES, APPEARANCE_MAX_PROPOSALS = 4096, 8192, 65535  # fp_proposal_appearance's limits
 PROPOSAL_DECISIONS = ("candidate", "small", "empty", "no_object", "low_score", "group_limit")  # FP_PROPOSAL_CANDIDATE .. _GROUP_LIMIT
 
 

@@ -483,6 +483,36 @@ int fp_box_iou(const int32_t* boxes, int num_boxes, const int32_t* pairs, int nu
   return launch_box_iou(a, ST(stream));
 }
 
+// ------------------------------------------------------------------ the appearance score of a proposal
+int fp_proposal_patch_cover(const uint8_t* masks, int n_img, int H, int W, const int32_t* image_index, const int32_t* boxes, int num_prop, int S,
+                            int patch_size, int32_t* out_cover, fp_stream_t stream) {
+  FP_REQUIRE(num_prop >= 0, "fp_proposal_patch_cover: %d proposals", num_prop);
+  FP_REQUIRE((masks && boxes && out_cover) || num_prop == 0, "fp_proposal_patch_cover: null pointer");
+  PatchCoverArgs a;
+  memset(&a, 0, sizeof(a));
+  a.masks = masks; a.image_index = image_index; a.boxes = boxes; a.n_img = n_img; a.H = H; a.W = W; a.S = S; a.ps = patch_size;
+  a.cover = out_cover;
+  return launch_proposal_patch_cover(a, num_prop, ST(stream));
+}
+
+int fp_proposal_appearance(const float* q_n, const int32_t* q_cover, int num_prop, int num_patches, int dim, const float* bank_patch_n,
+                           const int32_t* bank_cover, int num_bank, const int32_t* obj_off, int num_obj, const int32_t* best_obj,
+                           const int32_t* best_template, const float* best_score, int min_cover, float* out_best_sim, int32_t* out_best_patch,
+                           float* out_appearance, int32_t* out_n_valid, int32_t* out_status, float* out_score, fp_stream_t stream) {
+  FP_REQUIRE(num_prop >= 0 && num_bank >= 0, "fp_proposal_appearance: negative count");
+  FP_REQUIRE(obj_off, "fp_proposal_appearance: null obj_off");
+  FP_REQUIRE((q_n && q_cover && best_obj && best_template && best_score && out_best_sim && out_best_patch && out_appearance && out_n_valid &&
+              out_status && out_score) || num_prop == 0, "fp_proposal_appearance: null pointer");
+  FP_REQUIRE((bank_patch_n && bank_cover) || num_bank == 0, "fp_proposal_appearance: null bank");
+  ProposalAppearanceArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q = q_n; a.q_cover = q_cover; a.bank = bank_patch_n; a.bank_cover = bank_cover; a.obj_off = obj_off; a.best_obj = best_obj;
+  a.best_template = best_template; a.best_score = best_score; a.P = num_prop; a.Np = num_patches; a.D = dim; a.N = num_bank; a.O = num_obj;
+  a.min_cover = min_cover; a.best_sim = out_best_sim; a.best_patch = out_best_patch; a.appearance = out_appearance; a.n_valid = out_n_valid;
+  a.status = out_status; a.score = out_score;
+  return launch_proposal_appearance(a, ST(stream));
+}
+
 // ------------------------------------------------------------------ COCO average precision of detections
 int fp_mask_pack(const uint8_t* masks, int num_masks, int H, int W, uint64_t* out_words, int32_t* out_area, fp_stream_t stream) {
   FP_REQUIRE(num_masks >= 0, "fp_mask_pack: %d masks", num_masks);

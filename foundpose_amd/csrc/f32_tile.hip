@@ -17,44 +17,21 @@
 // ds_read_b32; global->LDS goes through registers so the transpose happens on the write.
 #include <type_traits>
 #include "common.hpp"
+#include "f32_stage.hpp"
 #include "kernels.hpp"
 #include "select.hpp"
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 32, LDS_STRIDE = 129;
-constexpr int STAGE_FLOATS = BK * LDS_STRIDE;  // per operand per stage
-
-struct Frag {
-  float4 v[4];
-};
-
-// 128 rows x 32 k of one operand -> 4 float4 per thread (8 lanes cover one 128-B row).  Branch-free: a position outside the
-// operand (row past the segment, k past K -- K % 4 == 0 is checked on the host) loads a clamped address and is zeroed, so
-// the four loads always issue back to back and nothing waits between them.
-FP_DEVICE void load_tile(Frag& f, const float* __restrict__ base, int ld, int row0, int nrows, int k0, int K, int tid) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int idx = tid + i * 256;
-    const int row = row0 + (idx >> 3), k = k0 + (idx & 7) * 4;
-    const bool ok = row < nrows && k < K;
-    const float4 v = *reinterpret_cast<const float4*>(base + (size_t)(row < nrows ? row : nrows - 1) * ld + (k < K ? k : K - 4));
-    f.v[i] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-
-FP_DEVICE void store_tile(const Frag& f, float* __restrict__ lds, int tid) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int idx = tid + i * 256;
-    int row = idx >> 3, c = idx & 7;
-    float* p = lds + (c * 4) * LDS_STRIDE + row;
-    p[0 * LDS_STRIDE] = f.v[i].x;
-    p[1 * LDS_STRIDE] = f.v[i].y;
-    p[2 * LDS_STRIDE] = f.v[i].z;
-    p[3 * LDS_STRIDE] = f.v[i].w;
-  }
-}
+// the tile constants and the operand staging (global -> registers -> the k-major LDS image) are shared with proposals.hip: f32_stage.hpp
+using f32_stage::BK;
+using f32_stage::BM;
+using f32_stage::BN;
+using f32_stage::Frag;
+using f32_stage::LDS_STRIDE;
+using f32_stage::STAGE_FLOATS;
+using f32_stage::load_tile;
+using f32_stage::store_tile;
 
 // Per-tile k-selection of the DIST_TOPK epilogue: two threads scan the two 64-column halves of a row of the tile's distance
 // image keeping KMAX sorted (d2, column) keys, one shuffle merges the halves, thread `half == 0` emits k keys.  Columns past

@@ -671,3 +671,33 @@ struct BoxIouArgs {
   int* status;             // [n_pairs] 0 scored, 2 union 0 or an index outside the table
 };
 int launch_box_iou(const BoxIouArgs& a, hipStream_t st);
+
+// the appearance score of a proposal
+struct PatchCoverArgs {
+  const unsigned char* masks;  // [P, H, W]
+  const int* image_index;  // [P] or null: only its range is checked, as proposal_crops checks it
+  const int* boxes;        // [P, 4] as mask_boxes writes them
+  int n_img, H, W, S, ps;
+  int* cover;              // [P, (S / ps)^2] covered pixels of every patch cell, row-major; every element written
+};
+int launch_proposal_patch_cover(const PatchCoverArgs& a, int num_prop, hipStream_t st);
+
+constexpr int PA_MAX_DIM = 4096, PA_MAX_PATCHES = 8192;
+struct ProposalAppearanceArgs {
+  const float* q;          // [P, Np, D] rows from normalize_rows
+  const int* q_cover;      // [P, Np]
+  const float* bank;       // [N, Np, D]
+  const int* bank_cover;   // [N, Np]
+  const int* obj_off;      // [O + 1] over the N bank rows, as the caller gave it
+  const int* best_obj;     // [P] as proposal_scores wrote them
+  const int* best_template;
+  const float* best_score;
+  int P, Np, D, N, O, min_cover;
+  float* best_sim;         // [P, Np] (0, -1) for an invalid query patch and for every patch of a row whose status is not 0
+  int* best_patch;         // [P, Np]
+  float* appearance;       // [P]
+  int* n_valid;            // [P]
+  int* status;             // [P] 0 scored, 1 no valid query patch, 2 no template row, 3 no valid template patch
+  float* score;            // [P] (best_score + appearance) * 0.5f
+};
+int launch_proposal_appearance(const ProposalAppearanceArgs& a, hipStream_t st);

@@ -30,8 +30,12 @@
 //
 // box_iou_kernel: one thread per pair; intersection and union in int64, one fp64 division.
 //
+// patch_cover_kernel / proposal_appearance_kernel / proposal_appearance_finish_kernel: the appearance score; their
+//   comments stand with them below.
+//
 // Every result depends on its own row's data only: it is the same bits alone, in any batch and at any position.
 #include "common.hpp"
+#include "f32_stage.hpp"
 #include "kernels.hpp"
 
 namespace {
@@ -377,7 +381,244 @@ __global__ __launch_bounds__(PC_THREADS) void box_iou_kernel(BoxIouArgs a) {
   a.status[q] = st;
 }
 
+// ------------------------------------------------------------------ which ViT patches of a cut-out belong to the object
+// One thread per patch cell.  The geometry is proposal_crops_kernel's; a crop pixel of the window reads the mask byte under its centre.
+__global__ __launch_bounds__(PC_THREADS) void patch_cover_kernel(PatchCoverArgs a) {
+  const int p = blockIdx.y, g = a.S / a.ps, cell = blockIdx.x * PC_THREADS + threadIdx.x;
+  if (cell >= g * g) return;
+  const int bx1 = a.boxes[(size_t)p * 4 + 0], by1 = a.boxes[(size_t)p * 4 + 1], bx2 = a.boxes[(size_t)p * 4 + 2], by2 = a.boxes[(size_t)p * 4 + 3];
+  const int img = a.image_index ? a.image_index[p] : p;
+  const bool ok = img >= 0 && img < a.n_img && bx1 >= 0 && by1 >= 0 && bx2 <= a.W && by2 <= a.H && bx2 > bx1 && by2 > by1;
+  int n = 0;
+  if (ok) {
+    const int S = a.S, w = bx2 - bx1, h = by2 - by1, L = max(w, h);
+    const int wo = max(1, (int)((2ll * w * S + L) / (2ll * L))), ho = max(1, (int)((2ll * h * S + L) / (2ll * L)));  // <= S
+    const int ox = (S - wo) / 2, oy = (S - ho) / 2;
+    const int cy = cell / g, cx = cell - cy * g;
+    const int X0 = max(cx * a.ps, ox), X1 = min(cx * a.ps + a.ps, ox + wo), Y0 = max(cy * a.ps, oy), Y1 = min(cy * a.ps + a.ps, oy + ho);
+    const unsigned char* __restrict__ mask = a.masks + (size_t)p * a.H * a.W;
+    for (int Y = Y0; Y < Y1; ++Y) {
+      const int sy = by1 + (int)(((2ll * (Y - oy) + 1) * h) / (2ll * ho));  // < by2: 2 (Y - oy) + 1 < 2 h'
+      const unsigned char* __restrict__ mrow = mask + (size_t)sy * a.W;
+      for (int X = X0; X < X1; ++X) {
+        const int sx = bx1 + (int)(((2ll * (X - ox) + 1) * w) / (2ll * wo));  // < bx2
+        n += mrow[sx] != 0 ? 1 : 0;
+      }
+    }
+  }
+  a.cover[(size_t)p * g * g + cell] = n;
+}
+
+// ------------------------------------------------------------------ the appearance score
+// proposal_appearance_kernel: one 256-thread workgroup per (proposal, 128 query patches).  It walks the patches of the proposal's best
+//   template in 128-column tiles with f32_tile.hip's staging (f32_stage.hpp: 128 x 32 of each operand through registers into a k-major
+//   LDS image, [k][row], stride 129 dwords; two stages) and its instruction, v_mfma_f32_32x32x2_f32 with k ascending: one accumulator per
+//   (query patch, template patch), so a similarity is the chain acc = fmaf(q[k], t[k], acc).  Wave w owns query rows 32 w .. 32 w + 31 and
+//   the tile's four 32-column blocks.  Behind the last k step of a column tile every lane folds its 16 rows x 4 columns into a running
+//   (value, column) pair per row over the VALID columns -- columns arrive ascending in a lane, so the strict ">" keeps the lower one -- and
+//   behind the last tile a butterfly over the 32 lanes of a row merges the pairs (greater value, then lower column).  Rows past Np and
+//   columns past Np are zero-filled from clamped addresses inside the proposal's / the template's own rows: a ragged tile never touches a
+//   neighbour.  proposal_appearance_finish_kernel: one thread per proposal adds the valid rows' values in ascending order.
+constexpr int PA_BM = f32_stage::BM, PA_BN = f32_stage::BN, PA_BK = f32_stage::BK, PA_LDS = f32_stage::LDS_STRIDE, PA_STAGE = f32_stage::STAGE_FLOATS;
+
+// The bank row of proposal p's best template, or -1 (status 2); obj_off is clamped into [0, N] and made non-decreasing on the way.
+FP_DEVICE int appearance_row(const ProposalAppearanceArgs& a, int p) {
+  const int o = a.best_obj[p], t = a.best_template[p];
+  if (o < 0 || o >= a.O || t < 0) return -1;
+  int prev = min(max(a.obj_off[0], 0), a.N);
+  for (int i = 0; i < o; ++i) prev = min(max(a.obj_off[i + 1], prev), a.N);
+  const int end = min(max(a.obj_off[o + 1], prev), a.N);
+  return t < end - prev ? prev + t : -1;  // prev + t < end <= N
+}
+
+__global__ __launch_bounds__(256) void proposal_appearance_kernel(ProposalAppearanceArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float pa_smem[];
+  float* As = pa_smem;                 // [2][PA_BK][129]
+  float* Bs = pa_smem + 2 * PA_STAGE;  // [2][PA_BK][129]
+  const int p = blockIdx.y, m0 = blockIdx.x * PA_BM, tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int Np = a.Np, D = a.D;
+  const int live_m = Np - m0 < PA_BM ? Np - m0 : PA_BM;  // >= 1: the grid has cdiv(Np, 128) tiles
+  const int row = appearance_row(a, p);                  // block-uniform
+  float* __restrict__ out_sim = a.best_sim + (size_t)p * Np + m0;
+  int* __restrict__ out_patch = a.best_patch + (size_t)p * Np + m0;
+  const int* __restrict__ qc = a.q_cover + (size_t)p * Np + m0;
+  const int* __restrict__ bc = a.bank_cover + (size_t)(row < 0 ? 0 : row) * Np;
+
+  // nothing to score here: no template row, a template of no valid patch, or no valid query patch in this tile
+  int tv = 0, qv = 0;
+  if (row >= 0) {
+    for (int i = tid; i < Np; i += 256) tv |= bc[i] >= a.min_cover ? 1 : 0;
+    if (tid < live_m) qv = qc[tid] >= a.min_cover ? 1 : 0;
+  }
+  const int any_t = __syncthreads_or(tv), any_q = __syncthreads_or(qv);
+  if (row < 0 || !any_t || !any_q) {
+    for (int i = tid; i < live_m; i += 256) {
+      out_sim[i] = 0.f;
+      out_patch[i] = -1;
+    }
+    return;
+  }
+
+  const float* __restrict__ Ab = a.q + (size_t)p * Np * D;
+  const float* __restrict__ Bb = a.bank + (size_t)row * Np * D;
+  const int nk = (D + PA_BK - 1) / PA_BK, steps = ((Np + PA_BN - 1) / PA_BN) * nk;
+  const int kh = lane >> 5, l31 = lane & 31, rb = wave * 32;
+  const bool wlive = rb < live_m;  // wave-uniform: a wave of no live row only stages
+
+  float bv[16];
+  int bi[16];
+  f32x16 acc[4];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    bv[r] = -INFINITY;
+    bi[r] = -1;
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
+
+  f32_stage::Frag fa, fb;
+  f32_stage::load_tile(fa, Ab, D, m0, Np, 0, D, tid);
+  f32_stage::load_tile(fb, Bb, D, 0, Np, 0, D, tid);
+  f32_stage::store_tile(fa, As, tid);
+  f32_stage::store_tile(fb, Bs, tid);
+  __syncthreads();
+
+  for (int s = 0; s < steps; ++s) {  // (column tile, k step), k fastest
+    const int cur = s & 1, t = s / nk, kt = s - t * nk, n0 = t * PA_BN;
+    if (s + 1 < steps) {
+      const int t1 = (s + 1) / nk, k1 = (s + 1) - t1 * nk;
+      f32_stage::load_tile(fa, Ab, D, m0, Np, k1 * PA_BK, D, tid);
+      f32_stage::load_tile(fb, Bb, D, t1 * PA_BN, Np, k1 * PA_BK, D, tid);
+    }
+    const int ncb = Np - n0 >= PA_BN ? 4 : (Np - n0 + 31) / 32;  // 32-column blocks of this tile with a live column (block-uniform)
+    if (wlive) {
+      const float* as0 = As + cur * PA_STAGE + rb + l31 + kh * PA_LDS;
+      const float* bs0 = Bs + cur * PA_STAGE + l31 + kh * PA_LDS;
+#pragma unroll
+      for (int kk = 0; kk < PA_BK / 2; ++kk) {
+        const int krow = kk * 2 * PA_LDS;
+        const float a0 = as0[krow];
+        const float b0 = bs0[krow], b1 = bs0[krow + 32], b2 = bs0[krow + 64], b3 = bs0[krow + 96];
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0], 0, 0, 0);
+        if (ncb > 1) acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[1], 0, 0, 0);
+        if (ncb > 2) acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b2, acc[2], 0, 0, 0);
+        if (ncb > 3) acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b3, acc[3], 0, 0, 0);
+      }
+      if (kt == nk - 1) {
+        // acc[c][r] is sim(i, j) with i = m0 + rb + (r & 3) + 8 (r >> 2) + 4 kh, j = n0 + 32 c + l31
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int j = n0 + c * 32 + l31;
+          const bool valid = j < Np && bc[j < Np ? j : Np - 1] >= a.min_cover;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float v = acc[c][r];
+            const bool take = valid && v > bv[r];  // false for a NaN and at equality
+            bv[r] = take ? v : bv[r];
+            bi[r] = take ? j : bi[r];
+            acc[c][r] = 0.f;
+          }
+        }
+      }
+    }
+    if (s + 1 < steps) {
+      f32_stage::store_tile(fa, As + (cur ^ 1) * PA_STAGE, tid);
+      f32_stage::store_tile(fb, Bs + (cur ^ 1) * PA_STAGE, tid);
+    }
+    __syncthreads();
+  }
+  if (!wlive) return;
+
+  // a row's 32 lanes hold its candidates: the greater value wins, the lower column among equal values (-1, as unsigned, never does)
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float ov = __shfl_xor(bv[r], o, 64);
+      const int oi = __shfl_xor(bi[r], o, 64);
+      const bool take = ov > bv[r] || (ov == bv[r] && (unsigned)oi < (unsigned)bi[r]);
+      bv[r] = take ? ov : bv[r];
+      bi[r] = take ? oi : bi[r];
+    }
+  }
+  if (l31 == 0) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = rb + (r & 3) + 8 * (r >> 2) + 4 * kh;
+      if (i >= live_m) continue;
+      const bool valid = qc[i] >= a.min_cover;
+      out_sim[i] = valid ? bv[r] : 0.f;
+      out_patch[i] = valid ? bi[r] : -1;
+    }
+  }
+}
+
+__global__ __launch_bounds__(PC_THREADS) void proposal_appearance_finish_kernel(ProposalAppearanceArgs a) {
+#pragma clang fp contract(off)
+  const int p = blockIdx.x * PC_THREADS + threadIdx.x;
+  if (p >= a.P) return;
+  const int row = appearance_row(a, p);
+  int nv = 0, st = 2;
+  float app = 0.f;
+  if (row >= 0) {
+    const int* __restrict__ qc = a.q_cover + (size_t)p * a.Np;
+    const int* __restrict__ bc = a.bank_cover + (size_t)row * a.Np;
+    bool tv = false;
+    for (int j = 0; j < a.Np; ++j) nv += qc[j] >= a.min_cover ? 1 : 0;
+    for (int i = 0; i < a.Np; ++i) tv = tv || bc[i] >= a.min_cover;
+    st = nv == 0 ? 1 : (tv ? 0 : 3);
+    if (st == 0) {
+      const float* __restrict__ bs = a.best_sim + (size_t)p * a.Np;
+      float s = 0.f;
+      bool first = true;
+      for (int j = 0; j < a.Np; ++j) {
+        if (qc[j] < a.min_cover) continue;
+        s = first ? bs[j] : s + bs[j];
+        first = false;
+      }
+      app = s / (float)nv;
+    }
+  }
+  a.appearance[p] = app;
+  a.n_valid[p] = nv;
+  a.status[p] = st;
+  a.score[p] = (a.best_score[p] + app) * 0.5f;
+}
+
 }  // namespace
+
+int launch_proposal_patch_cover(const PatchCoverArgs& a, int num_prop, hipStream_t st) {
+  FP_REQUIRE(num_prop >= 0 && num_prop <= 65535, "proposal_patch_cover: %d proposals (0 .. 65535 per call)", num_prop);
+  FP_REQUIRE(a.S >= 1 && a.S <= PC_MAX_SIZE, "proposal_patch_cover: crop size %d outside [1, %d]", a.S, PC_MAX_SIZE);
+  FP_REQUIRE(a.ps >= 1 && a.S % a.ps == 0, "proposal_patch_cover: the crop size %d is no multiple of the patch size %d", a.S, a.ps);
+  FP_REQUIRE(a.n_img >= 1 && a.H >= 1 && a.W >= 1 && (long long)a.H * a.W <= (1ll << 30),
+             "proposal_patch_cover: %d images of %d x %d (H, W >= 1, H W at most 2^30)", a.n_img, a.W, a.H);
+  if (num_prop == 0) return FP_OK;
+  const int g = a.S / a.ps;
+  hipLaunchKernelGGL(patch_cover_kernel, dim3(cdiv(g * g, PC_THREADS), num_prop), dim3(PC_THREADS), 0, st, a);
+  FP_CHECK_LAUNCH("proposal_patch_cover");
+  return FP_OK;
+}
+
+int launch_proposal_appearance(const ProposalAppearanceArgs& a, hipStream_t st) {
+  FP_REQUIRE(a.P >= 0 && a.P <= 65535, "proposal_appearance: %d proposals (0 .. 65535 per call)", a.P);
+  FP_REQUIRE(a.D >= 4 && a.D % 4 == 0 && a.D <= PA_MAX_DIM, "proposal_appearance: %d words (a multiple of 4, at most %d)", a.D, PA_MAX_DIM);
+  FP_REQUIRE(a.Np >= 1 && a.Np <= PA_MAX_PATCHES, "proposal_appearance: %d patches outside [1, %d]", a.Np, PA_MAX_PATCHES);
+  FP_REQUIRE(a.N >= 0 && a.O >= 1 && a.min_cover >= 1, "proposal_appearance: %d bank rows, %d objects, min_cover %d (N >= 0, O >= 1, min_cover >= 1)",
+             a.N, a.O, a.min_cover);
+  if (a.P == 0) return FP_OK;
+  const size_t lds = 4 * PA_STAGE * sizeof(float);  // two double-buffered operand stages
+  static FpDeviceOnce attr;
+  fp_allow_dynamic_lds(attr, &proposal_appearance_kernel, (int)lds);
+  hipLaunchKernelGGL(proposal_appearance_kernel, dim3(cdiv(a.Np, PA_BM), a.P), dim3(256), lds, st, a);
+  FP_CHECK_LAUNCH("proposal_appearance (tiles)");
+  hipLaunchKernelGGL(proposal_appearance_finish_kernel, dim3(cdiv(a.P, PC_THREADS)), dim3(PC_THREADS), 0, st, a);
+  FP_CHECK_LAUNCH("proposal_appearance (finish)");
+  return FP_OK;
+}
 
 int launch_mask_boxes(const MaskBoxArgs& a, int num_prop, hipStream_t st) {
   FP_REQUIRE(num_prop >= 0 && a.H >= 1 && a.W >= 1 && (long long)a.H * a.W <= (1ll << 30),

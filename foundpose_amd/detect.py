@@ -2,7 +2,8 @@
 
     python -m foundpose_amd.detect onboard --opts detect.json --output-path <root>
         reads <root>/templates/<templates_version>/<dataset>/<lid>/ (what gen_templates wrote) and writes detector.pth beside
-        <root>/object_repre/<version>/<dataset>/<lid>/repre.pth, for every object of object_lids
+        <root>/object_repre/<version>/<dataset>/<lid>/repre.pth, for every object of object_lids; with detector_score_type
+        "semantic_appearance"  also detector_patches.pth, the templates' patch descriptors, which run then loads
     python -m foundpose_amd.detect run --opts detect.json --proposals proposals.json --dataset-dir <split> --output-path <root> --output detections.json
         labels the proposals of every image they name and writes a CNOS detections file (what infer --detections takes) and
         detector-decisions.json beside it
@@ -50,7 +51,7 @@ def onboard(opts: detect_util.DetectOpts, output_path: str, extractor, templates
         else:
             rgb, masks = _load_templates(gen_repre.load_template_metadata(output_path, opts, lid))
         bank = detect_util.build_detector_bank(extractor, rgb.cuda(), masks.cuda(), opts.detector_crop_size, opts.detector_template_stride,
-                                               opts.detector_batch)
+                                               opts.detector_batch, with_patches=opts.detector_score_type == "semantic_appearance")
         written.append(detect_util.save_detector_bank(bank, _repre_dir(output_path, opts, lid)))
     return written
 
@@ -59,7 +60,8 @@ def load_banks(opts: detect_util.DetectOpts, output_path: str, lids: Optional[Se
     lids = list(lids if lids is not None else (opts.object_lids or []))
     if not lids:
         raise ValueError("object_lids names the objects to detect")
-    return {lid: detect_util.load_detector_bank(_repre_dir(output_path, opts, lid)) for lid in lids}
+    with_patches = opts.detector_score_type == "semantic_appearance"
+    return {lid: detect_util.load_detector_bank(_repre_dir(output_path, opts, lid), with_patches=with_patches) for lid in lids}
 
 
 def _load_frame_image(split_dir: str, sid: int, iid: int) -> np.ndarray:
@@ -116,7 +118,10 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         return
     with open(args.proposals) as f:
         proposals = json.load(f)
-    print("\n".join(run(opts, proposals, args.dataset_dir, load_banks(opts, args.output_path), extractor, args.output)))
+    # (the set holds its own copy of every table: the per-object ones are dropped as soon as it is built -- 6.7 GB of patch tables at 8 x 798
+    #  templates of ViT-L -- and only while bank_set concatenates them does the device hold both)
+    bs = detect_util.bank_set(load_banks(opts, args.output_path))
+    print("\n".join(run(opts, proposals, args.dataset_dir, bs, extractor, args.output)))
 
 
 if __name__ == "__main__":

@@ -675,6 +675,65 @@ def box_iou(boxes: torch.Tensor, pairs: torch.Tensor) -> Tuple[torch.Tensor, tor
     return overlap, status
 
 
+# ---------------------------------------------------------------- the appearance score of a proposal
+def proposal_patch_cover(masks: torch.Tensor, boxes: torch.Tensor, size: int, patch_size: int, image_index: Optional[torch.Tensor] = None,
+                         n_img: Optional[int] = None) -> torch.Tensor:
+    """fp_proposal_patch_cover: masks uint8 [P, H, W], boxes int32 [P, 4] as mask_boxes writes them, the crop size and the ViT's patch size
+    (which divides it), image_index int32 [P] over n_img images or None (proposal p reads image p of P).  -> cover int32 [P, (size /
+    patch_size)^2]: the pixels of every patch cell of proposal_crops' cut-out that the mask covers, cells in token order."""
+    tables = [(masks, torch.uint8), (boxes, torch.int32)] + ([(image_index, torch.int32)] if image_index is not None else [])
+    _detection_tables("proposal_patch_cover", tables)
+    if masks.dim() != 3 or masks.shape[1] < 1 or masks.shape[2] < 1:
+        raise ValueError(f"proposal_patch_cover: masks must be uint8 [P, H, W] with H, W >= 1, got {tuple(masks.shape)}")
+    P = int(masks.shape[0])
+    if tuple(boxes.shape) != (P, 4) or (image_index is not None and tuple(image_index.shape) != (P,)):
+        raise ValueError(f"proposal_patch_cover: boxes must be [{P}, 4] and image_index [{P}]")
+    if not 1 <= int(size) <= _lib.PROPOSAL_MAX_SIZE or int(patch_size) < 1 or int(size) % int(patch_size):
+        raise ValueError(f"proposal_patch_cover: crop size {size} outside [1, {_lib.PROPOSAL_MAX_SIZE}] or no multiple of the patch size {patch_size}")
+    n_img = int(n_img) if n_img is not None else (1 if image_index is not None else max(P, 1))
+    g = int(size) // int(patch_size)
+    cover = torch.empty(P, g * g, dtype=torch.int32, device=masks.device)
+    call("fp_proposal_patch_cover", ptr(masks), n_img, int(masks.shape[1]), int(masks.shape[2]), ptr(image_index), ptr(boxes), P, int(size),
+         int(patch_size), ptr(cover), stream())
+    return cover
+
+
+def proposal_appearance(q_n: torch.Tensor, q_cover: torch.Tensor, bank_patch_n: torch.Tensor, bank_cover: torch.Tensor, obj_off: torch.Tensor,
+                        best_obj: torch.Tensor, best_template: torch.Tensor, best_score: torch.Tensor, min_cover: int):
+    """fp_proposal_appearance: q_n f32 [P, Np, D] and bank_patch_n f32 [N, Np, D] (rows from normalize_rows), q_cover int32 [P, Np] and
+    bank_cover int32 [N, Np] (proposal_patch_cover), obj_off int32 [O + 1], best_obj / best_template int32 [P] and best_score f32 [P] as
+    proposal_scores takes and writes them.  -> (score f32 [P] = (best_score + appearance) / 2, appearance f32 [P], n_valid int32 [P],
+    status int32 [P] (0 scored, 1 no valid query patch, 2 no template row, 3 no valid template patch), best_sim f32 [P, Np],
+    best_patch int32 [P, Np]), all on the device."""
+    _detection_tables("proposal_appearance", ((q_n, torch.float32), (q_cover, torch.int32), (bank_patch_n, torch.float32), (bank_cover, torch.int32),
+                                              (obj_off, torch.int32), (best_obj, torch.int32), (best_template, torch.int32),
+                                              (best_score, torch.float32)))
+    if q_n.dim() != 3 or bank_patch_n.dim() != 3 or tuple(q_n.shape[1:]) != tuple(bank_patch_n.shape[1:]) or obj_off.dim() != 1 or obj_off.shape[0] < 2:
+        raise ValueError(f"proposal_appearance: q_n [P, Np, D], bank_patch_n [N, Np, D] and obj_off [O + 1] are needed, got {tuple(q_n.shape)}, "
+                         f"{tuple(bank_patch_n.shape)}, {tuple(obj_off.shape)}")
+    P, Np, D = (int(v) for v in q_n.shape)
+    N, O = int(bank_patch_n.shape[0]), int(obj_off.shape[0]) - 1
+    if tuple(q_cover.shape) != (P, Np) or tuple(bank_cover.shape) != (N, Np) or not (tuple(best_obj.shape) == tuple(best_template.shape)
+                                                                                     == tuple(best_score.shape) == (P,)):
+        raise ValueError(f"proposal_appearance: q_cover [{P}, {Np}], bank_cover [{N}, {Np}] and best_obj / best_template / best_score [{P}] are needed")
+    if D % 4 or D > _lib.APPEARANCE_MAX_DIM or not 1 <= Np <= _lib.APPEARANCE_MAX_PATCHES or P > _lib.APPEARANCE_MAX_PROPOSALS:
+        raise ValueError(f"proposal_appearance: D = {D} (a multiple of 4, at most {_lib.APPEARANCE_MAX_DIM}), Np = {Np} (1 .. "
+                         f"{_lib.APPEARANCE_MAX_PATCHES}), P = {P} (at most {_lib.APPEARANCE_MAX_PROPOSALS})")
+    if isinstance(min_cover, bool) or not isinstance(min_cover, int) or min_cover < 1:
+        raise ValueError(f"proposal_appearance: min_cover must be an integer >= 1, got {min_cover!r}")
+    dev = q_n.device
+    best_sim = torch.empty(P, Np, dtype=torch.float32, device=dev)
+    best_patch = torch.empty(P, Np, dtype=torch.int32, device=dev)
+    appearance = torch.empty(P, dtype=torch.float32, device=dev)
+    n_valid = torch.empty(P, dtype=torch.int32, device=dev)
+    status = torch.empty(P, dtype=torch.int32, device=dev)
+    score = torch.empty(P, dtype=torch.float32, device=dev)
+    call("fp_proposal_appearance", ptr(q_n), ptr(q_cover), P, Np, D, ptr(bank_patch_n) if N else None, ptr(bank_cover) if N else None, N, ptr(obj_off), O,
+         ptr(best_obj), ptr(best_template), ptr(best_score), int(min_cover), ptr(best_sim), ptr(best_patch), ptr(appearance), ptr(n_valid),
+         ptr(status), ptr(score), stream())
+    return score, appearance, n_valid, status, best_sim, best_patch
+
+
 # ---------------------------------------------------------------- COCO average precision of detections (DESIGN.md section 24)
 def mask_pack(masks: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """fp_mask_pack: masks uint8 [N, H, W] (0 / non-zero) -> (words [N, H, Wq] with Wq = ceil(W / 64), the uint64 words as torch.int64: bit

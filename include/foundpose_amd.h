@@ -450,6 +450,42 @@ int fp_proposal_rank(const int32_t* best_obj, const float* best_score, const int
 int fp_box_iou(const int32_t* boxes, int num_boxes, const int32_t* pairs, int num_pairs, double* out_overlap, int32_t* out_status,
                fp_stream_t stream);
 
+/* The appearance score of a proposal (the patch-descriptor score of CNOS's later versions and of SAM-6D's instance
+ * segmentation stage, restated), 1 of 2: which ViT patches of a cut-out belong to the object.  masks, image_index, boxes, n_img, H, W and
+ * S as fp_proposal_crops takes them; patch_size divides S (else refused); g = S / patch_size.  out_cover [num_prop, g g] int32, cells
+ * row-major (the token order of the ViT), EVERY element written.  With w, h, L, w', h', ox, oy as fp_proposal_crops defines them, crop
+ * pixel (X, Y) lies in the window iff ox <= X < ox + w' and oy <= Y < oy + h'; it then reads the mask byte at
+ *   sx = x1 + ((2 (X - ox) + 1) w) / (2 w'),  sy = y1 + ((2 (Y - oy) + 1) h) / (2 h')   (integer divisions in int64; always inside the box)
+ * and is covered iff that byte is non-zero.  cover(cell) = the covered pixels among the cell's patch_size^2.  A proposal whose crop status
+ * would be 2 (an empty box, a box that leaves the image, an image_index outside [0, n_img)) gets all zeros and nothing is read.  Integers
+ * only; a proposal's row depends on its own box and mask only: the same bits alone, in any batch and at any position.  (Added without a
+ * change of FP_ABI_VERSION: no existing entry point changed.) */
+int fp_proposal_patch_cover(const uint8_t* masks, int n_img, int H, int W, const int32_t* image_index, const int32_t* boxes, int num_prop, int S,
+                            int patch_size, int32_t* out_cover, fp_stream_t stream);
+
+/* ... 2 of 2: the score.  q_n [num_prop, num_patches, dim] fp32: the proposals' patch tokens, rows L2-normalised by fp_normalize_rows;
+ * q_cover [num_prop, num_patches] int32; bank_patch_n [num_bank, num_patches, dim] and bank_cover [num_bank, num_patches]: the same of the
+ * templates, in the row order of fp_proposal_scores' bank; obj_off [num_obj + 1], best_obj / best_template / best_score [num_prop] as
+ * fp_proposal_scores takes and writes them (all on the device); min_cover >= 1.  Per proposal p:
+ *   row     obj_off is clamped into [0, num_bank] and made non-decreasing; row = obj_off[best_obj] + best_template.  best_obj outside
+ *           [0, num_obj) or best_template outside [0, T_o): status 2, and nothing is read through either index.
+ *   valid   query patch j iff q_cover[p, j] >= min_cover; template patch i iff bank_cover[row, i] >= min_cover.
+ *   sim     sim(j, i) = the fp32 chain acc = fmaf(q[k], t[k], acc), k = 0 .. dim - 1 ascending from acc = 0, one accumulator per (j, i).
+ *   best    for a valid j: out_best_sim[p, j] = the maximum over the valid i from -inf, replaced only on v > best (equal values keep the
+ *           lower i, a NaN never wins), out_best_patch[p, j] = that i (-1 if none won); an invalid j gets (0.0f, -1).
+ *   score   out_n_valid[p] = the number of valid j; out_appearance[p] = (((s_j1 + s_j2) + ...)) / (float)n_valid in fp32 over the valid j
+ *           ascending, one rounded add each and ONE division.
+ *   status  0 scored; 1 no valid query patch; 2 no template row (n_valid = 0); 3 the template has no valid patch.  A status other than 0
+ *           gives appearance 0, n_valid as counted, and (0.0f, -1) in every element of the row of out_best_sim / out_best_patch.
+ *   out_score[p] = (best_score[p] + appearance[p]) * 0.5f; -inf stays -inf.
+ * Every element of every output is written.  dim % 4 != 0, dim > 4096, num_patches outside [1, 8192], num_prop > 65535, num_obj < 1 or
+ * min_cover < 1 is refused; num_prop = 0 returns without a launch.  A proposal's results depend on its own row and its template's only: the
+ * same bits alone, in any batch and at any position.  (Added without a change of FP_ABI_VERSION.) */
+int fp_proposal_appearance(const float* q_n, const int32_t* q_cover, int num_prop, int num_patches, int dim, const float* bank_patch_n,
+                           const int32_t* bank_cover, int num_bank, const int32_t* obj_off, int num_obj, const int32_t* best_obj,
+                           const int32_t* best_template, const float* best_score, int min_cover, float* out_best_sim, int32_t* out_best_patch,
+                           float* out_appearance, int32_t* out_n_valid, int32_t* out_status, float* out_score, fp_stream_t stream);
+
 /* COCO average precision of a detections file (foundpose_amd/eval_coco.py): BOP's 2D detection and 2D segmentation
  * scores.  Restates the published behaviour of pycocotools' COCOeval for instances without iscrowd; tests/coco_ref.py restates every entry.
  * 1 of 4: byte masks -> bit masks.  masks [num_masks, H, W] uint8, 0 unset / any non-zero byte set; H W at most 2^30.  out_words
