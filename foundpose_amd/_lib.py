@@ -112,6 +112,8 @@ _PROTOS = {
     "fp_template_downsample": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
     "fp_pose_errors": [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp, vp],
     "fp_pose_add_errors": [vp, i32, vp, vp, vp, i32, vp, C.c_size_t, vp, vp],
+    "fp_pts_diameter": [vp, i32, vp, C.c_size_t, vp, vp, vp],
+    "fp_directed_hausdorff": [vp, i32, i32, vp, i32, vp, C.c_size_t, vp, vp, vp],
     "fp_vsd_counts": [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp],
     "fp_featuremetric_refine": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32,
                                 vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
@@ -200,6 +202,22 @@ POSE_ADD_TILE = 256  # FP_POSE_ADD_TILE of the header
 def pose_add_scratch_bytes(num_pairs: int, max_pts: int) -> int:
     """FP_POSE_ADD_SCRATCH_BYTES of include/foundpose_amd.h."""
     return 32 * ((num_pairs + 7) // 8) * 8 + 16 * num_pairs * ((max_pts + POSE_ADD_TILE - 1) // POSE_ADD_TILE)
+
+
+PTS_TILE = 1024  # FP_PTS_TILE of the header
+PTS_DIAMETER_MAX_V = 65535 * PTS_TILE  # FP_PTS_DIAMETER_MAX_V of the header
+
+
+def pts_diameter_scratch_bytes(num_pts: int) -> int:
+    """FP_PTS_DIAMETER_SCRATCH_BYTES of include/foundpose_amd.h."""
+    tiles = (num_pts + PTS_TILE - 1) // PTS_TILE
+    return 16 * (tiles * (tiles + 1) // 2)
+
+
+def pts_hausdorff_scratch_bytes(num_pts: int, query_stride: int, num_transforms: int) -> int:
+    """FP_PTS_HAUSDORFF_SCRATCH_BYTES of include/foundpose_amd.h."""
+    nq = (num_pts + query_stride - 1) // query_stride
+    return 16 * num_transforms * ((nq + PTS_TILE - 1) // PTS_TILE)
 
 
 VSD_MAX_TAUS = 16  # FP_VSD_MAX_TAUS of the header

@@ -945,6 +945,29 @@ int fp_pose_add_errors(const double* pts, int total_pts, const double* est, cons
   return launch_pose_add_errors(a, num_pairs, (max_tiles + tiles_per_block - 1) / tiles_per_block, ST(stream));
 }
 
+int fp_pts_diameter(const double* pts, int V, void* scratch, size_t scratch_bytes, double* out_d, int32_t* out_pair, fp_stream_t stream) {
+  FP_REQUIRE(pts && scratch && out_d && out_pair, "fp_pts_diameter: null pointer");
+  FP_REQUIRE(V >= 1 && V <= FP_PTS_DIAMETER_MAX_V, "fp_pts_diameter: V %d outside [1, %d]", V, FP_PTS_DIAMETER_MAX_V);
+  FP_REQUIRE(scratch_bytes >= FP_PTS_DIAMETER_SCRATCH_BYTES(V), "fp_pts_diameter: scratch holds %zu bytes, %zu needed", scratch_bytes,
+             (size_t)FP_PTS_DIAMETER_SCRATCH_BYTES(V));
+  static_assert(sizeof(PtsPart) == 16, "layout of FP_PTS_*_SCRATCH_BYTES");
+  PtsDiameterArgs a{pts, V, (int)FP_PTS_TILES(V), static_cast<PtsPart*>(scratch), out_d, out_pair};
+  return launch_pts_diameter(a, ST(stream));
+}
+
+int fp_directed_hausdorff(const double* pts, int V, int query_stride, const double* transforms, int K, void* scratch,
+                          size_t scratch_bytes, double* out_h, int32_t* out_arg, fp_stream_t stream) {
+  FP_REQUIRE(pts && transforms && scratch && out_h && out_arg, "fp_directed_hausdorff: null pointer");
+  FP_REQUIRE(K >= 1 && K <= 65535, "fp_directed_hausdorff: K %d outside [1, 65535]", K);
+  FP_REQUIRE(V >= 1, "fp_directed_hausdorff: empty point array");
+  FP_REQUIRE(query_stride >= 1, "fp_directed_hausdorff: query_stride %d < 1", query_stride);
+  const size_t need = FP_PTS_HAUSDORFF_SCRATCH_BYTES(V, query_stride, K);
+  FP_REQUIRE(scratch_bytes >= need, "fp_directed_hausdorff: scratch holds %zu bytes, %zu needed", scratch_bytes, need);
+  const int nq = (int)(((long long)V + query_stride - 1) / query_stride);
+  PtsHausdorffArgs a{pts, V, query_stride, nq, transforms, static_cast<PtsPart*>(scratch), out_h, out_arg};
+  return launch_pts_hausdorff(a, K, ST(stream));
+}
+
 // ------------------------------------------------------------------ the three pose refinements
 // the argument checks the refinements share; `f` / `d` / `depth_weight`: the feature map, the depth stack and the weight of the entries that have one
 static int refine_check(const char* fn, const RefineLmArgs& lm, const RefineMapArgs* f, const RefineDepthArgs* d, const double* depth_weight) {

@@ -304,6 +304,24 @@ struct PoseAddArgs {
 };
 int launch_pose_add_errors(const PoseAddArgs& a, int num_pairs, int max_blocks, hipStream_t st);
 
+// ---------------------------------------------------------------- point_extremes.hip
+struct PtsPart { double v; int a, b; };  // a workgroup's maximum (a squared distance) and the index / index pair it came from
+struct PtsDiameterArgs {
+  const double* pts; int V;
+  int tiles;               // ceil(V / FP_PTS_TILE); tile pairs a <= b: tiles (tiles + 1) / 2 workgroups and partials
+  PtsPart* parts;
+  double* out_d; int* out_pair;
+};
+struct PtsHausdorffArgs {
+  const double* pts; int V;
+  int stride, nq;          // queries v = 0, stride, ...: nq = ceil(V / stride) of them
+  const double* tf;        // [K, 12]
+  PtsPart* parts;          // [K, ceil(nq / FP_PTS_TILE)]
+  double* out_h; int* out_arg;
+};
+int launch_pts_diameter(const PtsDiameterArgs& a, hipStream_t st);
+int launch_pts_hausdorff(const PtsHausdorffArgs& a, int K, hipStream_t st);
+
 // ---------------------------------------------------------------- refine.hip, depth_refine.hip, rgbd_refine.hip (shared parts: refine_terms.hpp)
 struct RefineState {       // Levenberg-Marquardt state of one detection (scratch, FP_REFINE_STATE_BYTES)
   double R[9], t[3];       // current pose

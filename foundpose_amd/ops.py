@@ -408,6 +408,53 @@ def pose_add_errors(pts: torch.Tensor, est: torch.Tensor, gt: torch.Tensor, rang
     return err
 
 
+def _pts_f64(fn: str, name: str, t, cols: int) -> None:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{fn}: {name} is a device tensor; there is no CPU path")
+    if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError(f"{fn}: {name} must be float64 [N, {cols}], got {t.dtype} {tuple(t.shape)}")
+
+
+def pts_diameter(pts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The largest distance between two points of pts [V, 3] (fp64, on the device; fp_pts_diameter) -> (d [1] fp64, pair [2] int32 = the
+    lexicographically lowest (i, j), i < j, that attains it; V = 1: 0.0 and (0, 0)).  Checked here, before any launch: ValueError."""
+    _pts_f64("pts_diameter", "pts", pts, 3)
+    v = pts.shape[0]
+    if v < 1 or v > _lib.PTS_DIAMETER_MAX_V:
+        raise ValueError(f"pts_diameter: {v} points, 1 .. {_lib.PTS_DIAMETER_MAX_V} per call")
+    pts = pts.contiguous()
+    d = torch.empty(1, dtype=torch.float64, device=pts.device)
+    pair = torch.empty(2, dtype=torch.int32, device=pts.device)
+    nbytes = _lib.pts_diameter_scratch_bytes(v)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
+    call("fp_pts_diameter", ptr(pts), v, ptr(scratch), nbytes, ptr(d), ptr(pair), stream())
+    return d, pair
+
+
+def directed_hausdorff(pts: torch.Tensor, transforms: torch.Tensor, query_stride: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per transform k of transforms [K, 12] = R row-major | t, the directed Hausdorff distance from the transformed points
+    v = 0, s, 2 s, ... (s = query_stride) of pts [V, 3] to ALL untransformed points (fp64, on the device; fp_directed_hausdorff)
+    -> (h [K] fp64, arg [K] int32 = the lowest v that attains it).  Checked here, before any launch: ValueError."""
+    _pts_f64("directed_hausdorff", "pts", pts, 3)
+    _pts_f64("directed_hausdorff", "transforms", transforms, 12)
+    if isinstance(query_stride, bool) or not hasattr(query_stride, "__index__"):
+        raise ValueError(f"directed_hausdorff: query_stride must be an integer, got {query_stride!r}")
+    v, k, s = pts.shape[0], transforms.shape[0], int(query_stride)
+    if v < 1 or v > 2**31 - 1:
+        raise ValueError(f"directed_hausdorff: {v} points, 1 .. 2^31 - 1 per call")
+    if k < 1 or k > 65535:
+        raise ValueError(f"directed_hausdorff: {k} transforms, 1 .. 65535 per call")
+    if s < 1 or s > 2**31 - 1:
+        raise ValueError(f"directed_hausdorff: query_stride {s} outside [1, 2^31 - 1]")
+    pts, transforms = pts.contiguous(), transforms.contiguous()
+    h = torch.empty(k, dtype=torch.float64, device=pts.device)
+    arg = torch.empty(k, dtype=torch.int32, device=pts.device)
+    nbytes = _lib.pts_hausdorff_scratch_bytes(v, s, k)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
+    call("fp_directed_hausdorff", ptr(pts), v, s, ptr(transforms), k, ptr(scratch), nbytes, ptr(h), ptr(arg), stream())
+    return h, arg
+
+
 def vsd_counts(depth_test: torch.Tensor, depth_est: torch.Tensor, depth_gt: torch.Tensor, pairs, params, taus) -> torch.Tensor:
     """VSD counts of a batch of (estimate, GT) pairs (fp_vsd_counts): depth_test [N_test, H, W], depth_est [N_est, H, W],
     depth_gt [N_gt, H, W] fp32 mm (on the device); pairs [P, 7] int (host) = (test, est, gt, x0, y0, x1, y1) with the inclusive

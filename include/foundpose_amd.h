@@ -903,6 +903,34 @@ int fp_pose_errors(const double* pts, int total_pts, const double* est, const do
 int fp_pose_add_errors(const double* pts, int total_pts, const double* est, const double* gt, const int32_t* ranges, int num_pairs,
                        void* scratch, size_t scratch_bytes, double* err, fp_stream_t stream);
 
+/* ---- farthest pair and directed Hausdorff distance inside one point set (models_info.py; DESIGN.md section 26,
+ * tests/models_info_ref.py restates it) ------------------------------------------------------------------------------------
+ * fp64 in and out, brute force, every operation rounded on its own as in the ADD / ADI entry above: a squared distance is
+ * (dx dx + dy dy) + dz dz, squared distances are compared and one correctly rounded sqrt follows the reduction.  Results are
+ * bit-identical across runs and launch shapes.  Both calls are asynchronous on `stream`.
+ *
+ * The diameter: pts [V, 3] (device) -> out_d [1] = sqrt(max_{i<j} d2(p_i, p_j)), out_pair int32 [2] = the lexicographically
+ * lowest pair (i, j), i < j, that attains it.  The maximum starts at 0 with the pair (0, 0) and a candidate replaces it only
+ * when strictly greater: a NaN never wins, and V = 1 (or V coincident points) gives 0.0 and (0, 0).  Work is done for pairs of
+ * FP_PTS_TILE-point tiles a <= b only.  1 <= V <= FP_PTS_DIAMETER_MAX_V; scratch: FP_PTS_DIAMETER_SCRATCH_BYTES(V) bytes.
+ *
+ * The directed Hausdorff distance of K transformed copies: transforms [K, 12] = R row-major | t (device).  For candidate k the
+ * queries are the points v = 0, s, 2 s, ... < V (s = query_stride), q_v = ((r0 x + r1 y) + r2 z) + t per row,
+ * m_v = min_u d2(q_v, p_u) over ALL V untransformed points (from +inf, strictly smaller only: a NaN never wins),
+ * out_h[k] = sqrt(max_v m_v), out_arg[k] = the lowest v that attains the maximum.  1 <= K <= 65535, V >= 1, query_stride >= 1;
+ * scratch: FP_PTS_HAUSDORFF_SCRATCH_BYTES(V, query_stride, K) bytes.
+ *
+ * A NULL pointer, an argument outside its limits or too little scratch: FP_ERR_INVALID, nothing written. */
+#define FP_PTS_TILE 1024 /* queries of one workgroup = targets of one LDS tile */
+#define FP_PTS_DIAMETER_MAX_V (65535 * FP_PTS_TILE)
+#define FP_PTS_TILES(n) (((size_t)(n) + FP_PTS_TILE - 1) / FP_PTS_TILE)
+#define FP_PTS_DIAMETER_SCRATCH_BYTES(V) (16 * (FP_PTS_TILES(V) * (FP_PTS_TILES(V) + 1) / 2))
+#define FP_PTS_HAUSDORFF_SCRATCH_BYTES(V, query_stride, K) \
+  (16 * (size_t)(K) * FP_PTS_TILES(((size_t)(V) + (size_t)(query_stride) - 1) / (size_t)(query_stride)))
+int fp_pts_diameter(const double* pts, int V, void* scratch, size_t scratch_bytes, double* out_d, int32_t* out_pair, fp_stream_t stream);
+int fp_directed_hausdorff(const double* pts, int V, int query_stride, const double* transforms, int K, void* scratch,
+                          size_t scratch_bytes, double* out_h, int32_t* out_arg, fp_stream_t stream);
+
 /* ---- VSD (bop_toolkit_lib pose_error.vsd, `bop19` visibility, `step` cost) ----------------------
  * Counts for the Visible Surface Discrepancy of num_pairs (estimate, GT) pairs.  Device arrays:
  *   depth_test [num_test, height, width]  fp32 mm, 0 = no measurement (the test images)
