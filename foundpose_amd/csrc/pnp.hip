@@ -5,7 +5,8 @@
 //                               reprojectionError, confidence, flags=SOLVEPNP_ITERATIVE) + optional cv2.solvePnPRefineLM on
 //                               the inliers; quality = number of RANSAC inliers
 //   scripts/infer.py:552-602 .. one call per retrieved template (>= 6 correspondences), best quality wins (host side)
-// cv2 (opencv-python 4.5.5.62) is not in the image, so its arithmetic cannot be pinned; this is its published scheme with
+// cv2 (opencv-python 4.5.5.62) is not in the image, so its arithmetic cannot be pinned (what is pinned, hypothesis by hypothesis, is this
+// kernel's own contract: the numpy restatement tests/pnp_ref.py); this is its published scheme with
 // a GPU-shaped minimal solver: RANSAC over minimal samples, inliers = reprojection error <= threshold, the best model is
 // the first one with the highest inlier count within the adaptively shortened iteration budget
 // (RANSACUpdateNumIters), then iterative refinement of that model on its inliers.  Differences, stated:
