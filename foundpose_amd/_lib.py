@@ -115,6 +115,7 @@ _PROTOS = {
     "fp_pts_diameter": [vp, i32, vp, C.c_size_t, vp, vp, vp],
     "fp_directed_hausdorff": [vp, i32, i32, vp, i32, vp, C.c_size_t, vp, vp, vp],
     "fp_vsd_counts": [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp],
+    "fp_gt_visibility": [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, vp, C.c_size_t, vp, vp, vp, vp],
     "fp_featuremetric_refine": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32,
                                 vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "fp_depth_refine": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
@@ -226,6 +227,11 @@ VSD_MAX_TAUS = 16  # FP_VSD_MAX_TAUS of the header
 def vsd_scratch_bytes(num_pairs: int) -> int:
     """FP_VSD_SCRATCH_BYTES of include/foundpose_amd.h."""
     return 96 * num_pairs
+
+
+def gt_vis_scratch_bytes(num_inst: int) -> int:
+    """FP_GT_VIS_SCRATCH_BYTES of include/foundpose_amd.h."""
+    return 80 * num_inst
 
 
 REFINE_CHUNK, REFINE_RECORD, REFINE_STATE_BYTES = 32, 32, 512  # FP_REFINE_* of the header

@@ -1,6 +1,6 @@
 // C ABI of libfoundpose_amd.so (declared in include/foundpose_amd.h): argument checking, scratch carving
 // and kernel sequencing.  No device allocation, no global mutable state, no synchronisation except the table uploads of
-// fp_pose_errors and fp_vsd_counts (each waits for its own copy) and the range check read back by the three refinements (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine).
+// fp_pose_errors, fp_vsd_counts and fp_gt_visibility (each waits for its own copy) and the range check read back by the three refinements (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine).
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -1144,6 +1144,60 @@ int fp_vsd_counts(const float* depth_test, int num_test, const float* depth_est,
   a.num_pairs = num_pairs, a.width = width, a.num_taus = num_taus;
   a.counts = reinterpret_cast<long long*>(counts);
   return launch_vsd_counts(a, blocks, ST(stream));
+}
+
+// ------------------------------------------------------------------ GT annotations from renders
+int fp_gt_visibility(const float* depth_test, int num_test, int height, int width, const float* depth_obj, int render_height,
+                     int render_width, const int32_t* inst, const double* params, int num_inst, void* scratch, size_t scratch_bytes,
+                     int32_t* out, uint8_t* mask, uint8_t* mask_visib, fp_stream_t stream) {
+  FP_REQUIRE(depth_test && depth_obj && inst && params && scratch && out && mask && mask_visib, "fp_gt_visibility: null pointer");
+  FP_REQUIRE(num_inst >= 1 && num_inst <= FP_GT_VIS_MAX_INST, "fp_gt_visibility: num_inst %d outside [1, %d]", num_inst, FP_GT_VIS_MAX_INST);
+  FP_REQUIRE(height >= 1 && width >= 1 && num_test >= 1 && render_height >= 1 && render_width >= 1,
+             "fp_gt_visibility: empty image, render or stack (%d x %d in %d x %d; %d images)", width, height, render_width, render_height, num_test);
+  FP_REQUIRE((long long)render_width * render_height <= 0x7fffffffll, "fp_gt_visibility: a render of %d x %d has more than 2^31 - 1 pixels",
+             render_width, render_height);
+  FP_REQUIRE(scratch_bytes >= FP_GT_VIS_SCRATCH_BYTES(num_inst), "fp_gt_visibility: scratch holds %zu bytes, %zu needed", scratch_bytes,
+             FP_GT_VIS_SCRATCH_BYTES(num_inst));
+  static_assert(sizeof(GtVisInst) == 80, "layout of FP_GT_VIS_SCRATCH_BYTES");
+  std::vector<GtVisInst> tab(num_inst);
+  const long long img = (long long)height * width;
+  long long blocks = 0;
+  for (int p = 0; p < num_inst; ++p) {
+    const int32_t* r = inst + 7 * (size_t)p;
+    const double* q = params + 5 * (size_t)p;
+    FP_REQUIRE(r[0] >= 0 && r[0] < num_test, "fp_gt_visibility: instance %d: test index %d outside [0, %d)", p, r[0], num_test);
+    FP_REQUIRE(r[1] >= 0 && r[2] >= 0 && r[1] <= (long long)r[3] + 1 && r[2] <= (long long)r[4] + 1 && r[3] < render_width && r[4] < render_height,
+               "fp_gt_visibility: instance %d: box (%d, %d, %d, %d) outside the %d x %d render", p, r[1], r[2], r[3], r[4], render_width, render_height);
+    FP_REQUIRE(r[5] >= 0 && r[6] >= 0 && (long long)r[5] + width <= render_width && (long long)r[6] + height <= render_height,
+               "fp_gt_visibility: instance %d: the %d x %d image at (%d, %d) leaves the %d x %d render", p, width, height, r[5], r[6],
+               render_width, render_height);
+    FP_REQUIRE(q[0] > 0 && q[1] > 0, "fp_gt_visibility: instance %d: fx and fy must be > 0", p);
+    FP_REQUIRE(q[4] == q[4], "fp_gt_visibility: instance %d: delta is NaN", p);
+    GtVisInst& v = tab[p];
+    v.test_off = r[0] * img;
+    v.x0 = r[1], v.y0 = r[2];
+    v.bw = r[3] - r[1] + 1, v.bh = r[4] - r[2] + 1;
+    if (v.bw == 0 || v.bh == 0) v.bw = v.bh = 0;
+    v.ox = r[5], v.oy = r[6];
+    v.blk0 = blocks;
+    v.fx = q[0], v.fy = q[1], v.cx = q[2], v.cy = q[3];
+    v.delta = (float)q[4];
+    v.pad = 0;
+    blocks += ((long long)v.bw * v.bh + FP_GT_VIS_BLOCK_PIXELS - 1) / FP_GT_VIS_BLOCK_PIXELS;
+  }
+  FP_REQUIRE(blocks <= 0x7fffffffll, "fp_gt_visibility: %lld workgroups exceed the grid", blocks);
+  const size_t mask_bytes = (size_t)num_inst * (size_t)img;
+  HIP_TRY(hipMemsetAsync(mask, 0, mask_bytes, ST(stream)), "fp_gt_visibility: zeroing mask");
+  HIP_TRY(hipMemsetAsync(mask_visib, 0, mask_bytes, ST(stream)), "fp_gt_visibility: zeroing mask_visib");
+  // the table lives in this frame, so the copy completes before it goes out of scope
+  HIP_TRY(hipMemcpyWithStream(scratch, tab.data(), sizeof(GtVisInst) * (size_t)num_inst, hipMemcpyHostToDevice, ST(stream)), "fp_gt_visibility: table upload");
+  GtVisArgs a;
+  memset(&a, 0, sizeof(a));
+  a.depth_test = depth_test, a.depth_obj = depth_obj;
+  a.inst = reinterpret_cast<const GtVisInst*>(scratch);
+  a.num_inst = num_inst, a.height = height, a.width = width, a.render_h = render_height, a.render_w = render_width;
+  a.out = out, a.mask = mask, a.mask_visib = mask_visib;
+  return launch_gt_visibility(a, blocks, ST(stream));
 }
 
 // ------------------------------------------------------------------ ViT forward (launch sequence in C++)

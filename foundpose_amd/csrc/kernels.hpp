@@ -382,6 +382,26 @@ struct VsdArgs {
 };
 int launch_vsd_counts(const VsdArgs& a, long long num_blocks, hipStream_t st);
 
+// ---------------------------------------------------------------- gt_info.hip
+struct GtVisInst {                       // one GT instance, built on the host by fp_gt_visibility
+  long long test_off;                    // element offset of the frame's depth image (index * height * width)
+  long long blk0;                        // first workgroup of the instance: ceil(bw * bh / FP_GT_VIS_BLOCK_PIXELS) of them
+  int x0, y0, bw, bh;                    // the box scanned, in render coordinates: bw x bh pixels from (x0, y0); 0 x 0 when empty
+  int ox, oy;                            // where the image starts inside the render
+  double fx, fy, cx, cy;                 // of the image
+  float delta;                           // (float)delta: numpy compares the fp32 difference in fp32
+  int pad;
+};
+struct GtVisArgs {
+  const float* depth_test;               // [num_test, height, width]
+  const float* depth_obj;                // [num_inst, render_h, render_w]
+  const GtVisInst* inst;                 // [num_inst] device copy
+  int num_inst, height, width, render_h, render_w, pad;
+  int* out;                              // [num_inst, 11], initialised by gt_vis_init_kernel
+  uint8_t* mask; uint8_t* mask_visib;    // [num_inst, height, width], zeroed by the host on the stream
+};
+int launch_gt_visibility(const GtVisArgs& a, long long num_blocks, hipStream_t st);
+
 // ---------------------------------------------------------------- vis.hip
 int launch_vis_mask_tint(const uint8_t* img, const uint8_t* mask, long long pixels, uint8_t* out, hipStream_t st);
 int launch_vis_contour(const uint8_t* mask, int batch, int h, int w, int dil, int r, int g, int b, uint8_t* img, hipStream_t st);

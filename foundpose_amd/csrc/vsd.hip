@@ -17,6 +17,7 @@
 // counter goes into the output the host zeroed on the stream.  Integer sums: bit-identical across runs and batches.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "bop_dist.hpp"   // dmul, dadd, dist, visib
 #include "../../include/foundpose_amd.h"
 
 #pragma clang fp contract(off)
@@ -28,18 +29,6 @@ constexpr int VSD_PPT = 4;                          // pixels per thread
 constexpr int VSD_BLOCK_PIX = VSD_THREADS * VSD_PPT;  // = FP_VSD_BLOCK_PIXELS
 constexpr int VSD_NC = 2 + FP_VSD_MAX_TAUS;         // counters per pair, at most
 static_assert(VSD_BLOCK_PIX == FP_VSD_BLOCK_PIXELS, "block size of the header");
-
-FP_DEVICE double dmul(double a, double b) { return __dmul_rn(a, b); }
-FP_DEVICE double dadd(double a, double b) { return __dadd_rn(a, b); }
-// misc.depth_im_to_dist_im_fast: sqrt(Xs**2 + Ys**2 + depth**2) with Xs = xs * depth, Ys = ys * depth
-FP_DEVICE double dist(double xs, double ys, float d) {
-  const double dd = (double)d, X = dmul(xs, dd), Y = dmul(ys, dd);
-  return __dsqrt_rn(dadd(dadd(dmul(X, X), dmul(Y, Y)), dmul(dd, dd)));
-}
-// visibility._estimate_visib_mask, bop19: (d_model.astype(f32) - d_test.astype(f32) <= delta | d_test == 0) & d_model > 0
-FP_DEVICE bool visib(double dm, double dt, float delta) {
-  return (__fsub_rn((float)dm, (float)dt) <= delta || dt == 0.0) && dm > 0.0;
-}
 
 __global__ __launch_bounds__(VSD_THREADS) void vsd_counts_kernel(VsdArgs a) {
   const long long blk = blockIdx.x;

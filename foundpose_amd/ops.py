@@ -487,6 +487,50 @@ def vsd_counts(depth_test: torch.Tensor, depth_est: torch.Tensor, depth_gt: torc
     return counts
 
 
+def gt_visibility(depth_test: torch.Tensor, depth_obj: torch.Tensor, inst, params) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Pixel counts, boxes and masks of a batch of GT instances (fp_gt_visibility): depth_test [N, H, W] and
+    depth_obj [P, Hr, Wr] fp32 mm (on the device), instance p rendered alone into a window that holds the image at (ox, oy); inst [P, 7]
+    int (host) = (test, x0, y0, x1, y1, ox, oy) with the inclusive scan box in render coordinates (x1 = x0 - 1: empty); params [P, 5]
+    (host) = (fx, fy, cx, cy, delta) of the image.  -> (out [P, 11] int32 = px_count_all, px_count_valid, px_count_visib, the silhouette
+    box and the visible box as (min x, min y, max x, max y) in image coordinates, INT_MAX / INT_MIN when empty; mask, mask_visib [P, H, W]
+    uint8 255 / 0).  A refused call raises ValueError and writes nothing."""
+    import numpy as np
+    host = []
+    for name, a in (("inst", inst), ("params", params)):
+        if isinstance(a, torch.Tensor):
+            if a.is_cuda:
+                raise ValueError(f"gt_visibility: {name} is a host table (it is validated on the host)")
+            a = a.numpy()
+        host.append(a)
+    for name, t in (("depth_test", depth_test), ("depth_obj", depth_obj)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"gt_visibility: {name} must be a tensor on the device (there is no CPU path)")
+        if t.dim() != 3 or t.dtype != torch.float32:
+            raise ValueError(f"gt_visibility: {name} must be float32 [N, H, W]")
+    r = np.asarray(host[0], dtype=np.int64).reshape(-1, 7)
+    if np.any(np.abs(r) > 2**31 - 1):
+        raise ValueError("gt_visibility: inst entries must fit int32")
+    r = np.ascontiguousarray(r, np.int32)
+    q = np.ascontiguousarray(np.asarray(host[1], dtype=np.float64).reshape(-1, 5))
+    n = r.shape[0]
+    if q.shape[0] != n or depth_obj.shape[0] != n:
+        raise ValueError(f"gt_visibility: {n} instance records, {q.shape[0]} parameter rows, {depth_obj.shape[0]} renders")
+    dt, do = depth_test.contiguous(), depth_obj.contiguous()
+    (h, w), (hr, wr) = dt.shape[1:], do.shape[1:]
+    out = torch.empty(max(n, 1), 11, dtype=torch.int32, device=dt.device)[:n]
+    mask = torch.empty(max(n, 1), h, w, dtype=torch.uint8, device=dt.device)[:n]
+    mask_visib = torch.empty_like(mask)
+    nbytes = _lib.gt_vis_scratch_bytes(n)
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dt.device)
+    rc = _lib.lib().fp_gt_visibility(ptr(dt), dt.shape[0], h, w, ptr(do), hr, wr, r.ctypes.data_as(_lib.vp), q.ctypes.data_as(_lib.vp), n,
+                                     ptr(scratch), nbytes, ptr(out), ptr(mask), ptr(mask_visib), stream())
+    if rc == 1:   # FP_ERR_INVALID: the one validation is the C entry's
+        raise ValueError(_lib.lib().fp_last_error().decode())
+    if rc != 0:
+        raise _lib.FoundPoseNativeError(f"fp_gt_visibility failed (code {rc}): {_lib.lib().fp_last_error().decode()}")
+    return out, mask, mask_visib
+
+
 def texture_mips(rgb: torch.Tensor) -> torch.Tensor:
     """The mip pyramid of a texture (fp_texture_mips): rgb uint8 [H, W, 3] on the device -> int32 [total] holding packed RGBA8
     texels (view as uint32), the levels back to back in the layout of _lib.texture_levels(W, H)."""

@@ -961,6 +961,36 @@ int fp_vsd_counts(const float* depth_test, int num_test, const float* depth_est,
                   int height, int width, const int32_t* pairs, const double* params, int num_pairs, const double* taus,
                   int num_taus, void* scratch, size_t scratch_bytes, int64_t* counts, fp_stream_t stream);
 
+/* ---- GT annotations from renders (bop_toolkit's calc_gt_info.py / calc_gt_masks.py, `bop19` visibility) ----
+ * Pixel counts, boxes and masks of num_inst ground-truth instances.  Device arrays:
+ *   depth_test [num_test, height, width]              fp32 mm, 0 = no measurement (the frames' depth images)
+ *   depth_obj  [num_inst, render_height, render_width] fp32 mm, 0 = background: instance p rendered alone into a window that holds
+ *                                                     the image at columns [ox, ox + width), rows [oy, oy + height)
+ *   out        [num_inst, 11] int32: px_count_all, px_count_valid, px_count_visib, the silhouette box (min x, min y, max x, max y)
+ *              and the visible box in the same form, both in IMAGE coordinates (render coordinate - offset: the silhouette box can
+ *              be negative or reach past the image); an empty box is INT_MAX, INT_MAX, INT_MIN, INT_MIN
+ *   mask, mask_visib [num_inst, height, width] uint8, 255 / 0
+ * The call defines every byte of the three outputs: it zeroes the two mask stacks with a memset on `stream`, initialises `out` and
+ * then writes the masks inside the scan boxes.
+ * HOST arrays (validated, then copied into scratch on `stream`; the call waits for that copy, as the VSD entry does):
+ *   inst   int32 [num_inst, 7]  (test index, x0, y0, x1, y1, ox, oy): the inclusive box scanned, in render coordinates (x1 = x0 - 1 or
+ *                               y1 = y0 - 1: empty); every pixel outside it must have depth_obj = 0.  (ox, oy): the image's offset.
+ *   params fp64 [num_inst, 5]   (fx, fy, cx, cy, delta mm) of the IMAGE (not of the shifted render camera)
+ * Per box pixel: depth_obj > 0 counts into px_count_all and extends the silhouette box.  Inside the image window, with (col, row) the
+ * image coordinates, fp64, every operation rounded on its own: xs = (col - cx) / fx, ys = (row - cy) / fy, dist = sqrt(((xs d)^2 +
+ * (ys d)^2) + d^2); mask = dist_obj > 0; px_count_valid counts mask && dist_test > 0; visib = ((float)dist_obj - (float)dist_test <=
+ * (float)delta || dist_test == 0) && dist_obj > 0 with the difference in fp32, counted into px_count_visib, extending the visible box.
+ * Integer sums and extremes: bit-identical across runs, batch compositions and launch shapes.  scratch: FP_GT_VIS_SCRATCH_BYTES(num_inst).
+ * A NULL pointer, num_inst < 1 or > FP_GT_VIS_MAX_INST, sizes < 1, render_width * render_height > 2^31 - 1, a test index outside the
+ * stack, a box outside the render, a window outside the render, fx or fy not > 0, a NaN delta or too little scratch: FP_ERR_INVALID,
+ * nothing written.  (Added without a change of FP_ABI_VERSION: no existing entry point changed.) */
+#define FP_GT_VIS_BLOCK_PIXELS 1024
+#define FP_GT_VIS_MAX_INST (1 << 24)
+#define FP_GT_VIS_SCRATCH_BYTES(num_inst) (80 * (size_t)(num_inst))
+int fp_gt_visibility(const float* depth_test, int num_test, int height, int width, const float* depth_obj, int render_height,
+                     int render_width, const int32_t* inst, const double* params, int num_inst, void* scratch, size_t scratch_bytes,
+                     int32_t* out, uint8_t* mask, uint8_t* mask_visib, fp_stream_t stream);
+
 /* ---- featuremetric refinement of the best coarse pose (tests/featuremetric_ref.py restates it) ----
  * Levenberg-Marquardt on the 6-DoF pose of each of num_det detections, aligning a template's per-point features with the
  * query's projected patch-feature map.  Device arrays:
