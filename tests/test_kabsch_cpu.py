@@ -1,6 +1,7 @@
 """pnp_type "kabsch_depth" without a GPU: the numpy restatement (tests/kabsch_ref.py) recovers planted poses, its congruence gate never
 rejects an all-inlier sample, the GPU tests' fixture is far from every decision boundary, the C ABI declares fp_kabsch_ransac, and the
-drivers' options are validated before device work."""
+drivers' options are validated before device work; and the fixtures of tests/test_gpu_kabsch_restatement.py are built and their conditions
+asserted from the restatement alone (margins, the sweeps' class counts, the replay's witnesses, best_h, eig_gap, the lift's hand list)."""
 
 import os
 import re
@@ -184,3 +185,136 @@ def test_camera_pairs_and_missing_arguments_are_refused_without_a_gpu():
         pnp_util.estimate_poses(r, [frame], "kabsch_depth")
     with pytest.raises(ValueError, match="Unsupported PnP type"):
         pnp_util.estimate_poses(Res(), [frame], "epnp")
+
+
+# ------------------------------------------------------------ the fixtures of tests/test_gpu_kabsch_restatement.py, conditions without a GPU
+def test_sampler_allows_one_draw_and_sixty_four_redraws():
+    """"at most 64 redraws per index, then the hypothesis fails" -- an index whose first acceptable value is its 65th
+    draw succeeds, one draw later it fails.  The chain is mix64's, so the masks are made from it."""
+    key, N = 99, 1 << 20     # (the restatement's sampler takes any N; 70 values of 2^20 are distinct here, asserted)
+    chain, s = [], key
+    for _ in range(70):
+        s = kr.mix64(s)
+        chain.append(s % N)
+    assert len(set(chain)) == 70
+    for first_ok, expect in ((65, 65), (64, 64), (66, kr.EXHAUSTED)):
+        valid = np.zeros(N, bool)
+        valid[chain[first_ok - 1:]] = True
+        ids, draws = kr.sample3_draws(key, N, valid)
+        assert draws[0] == expect and (ids is None) == (expect == kr.EXHAUSTED)
+        if ids is not None:
+            assert ids == chain[first_ok - 1:first_ok + 2] and draws[1:] == [1, 1]
+    # the limit is per index: the second index has 65 draws of its own
+    valid = np.zeros(N, bool)
+    valid[[chain[0], chain[65]]] = True
+    assert kr.sample3_draws(key, N, valid)[1] == [1, 65, kr.EXHAUSTED]
+
+
+def test_triangle_margin_exempts_only_an_exact_zero():
+    q = np.array([[0.0, 0, 0], [16.0, 0, 0], [48.0, 0, 0], [48.0, 1e-9, 0]])
+    m = kr.Margin()
+    assert kr.tri_frame(q[0], q[1], q[2], m) is None and m.value == 16.0 / 48.0  # exactly collinear on an axis: no margin but the first edge's own
+    assert kr.tri_frame(q[0], q[1], q[3], m) is not None and m.value < 1e-10     # nearly collinear: decided, but within rounding of not
+    m = kr.Margin()
+    assert kr.tri_frame(q[0], q[0], q[2], m) is None and m.value == np.inf
+
+
+def test_lift_rounds_half_to_even_and_refuses_what_is_no_measurement():
+    cam = (128.0, 128.0, 32.0, 24.0)
+    depth = np.zeros((48, 64), np.float32)
+    depth[5, [10, 12, 0, 62, 63]] = 600.0
+    depth[6, :4] = (0.0, -1.0, np.nan, np.inf)
+    below = np.nextafter(np.float32(-0.5), np.float32(-1.0))
+    uv = np.array([[10.5, 5.0], [11.5, 5.0], [9.5, 5.0], [12.5, 5.0], [-0.5, 5.0], [below, 5.0], [62.5, 5.0], [63.5, 5.0], [np.nan, 5.0], [10.0, np.nan],
+                   [0.0, 6.0], [1.0, 6.0], [2.0, 6.0], [3.0, 6.0]], np.float32)
+    m = kr.Margin()
+    with np.errstate(invalid="ignore"):
+        Y, valid = kr.lift(uv, cam, cam, np.eye(3), depth, m, tie_margin=False)
+    # 10.5 and 9.5 -> 10, 11.5 and 12.5 -> 12: only pixels 10 and 12 hold depth, so any other rule loses one of the four
+    assert valid.astype(int).tolist() == [1, 1, 1, 1, 1, 0, 1, 0, 0, 0, 0, 0, 0, 1]
+    assert m.value > 0.5 and np.isinf(Y[13, 2]) and Y[0, 2] == 600.0
+    m = kr.Margin()
+    kr.lift(uv[:1], cam, cam, np.eye(3), depth, m)
+    assert m.value == 0.0      # with the tie margin a tie is what it is elsewhere: undecided
+
+
+def test_sweep_fixture_conditions():
+    fix = kr.sweep_fixture()
+    ref = kr.run_ref_on(fix, False, fix["pair_keys"], cache={})
+    print(f"hypothesis sweep: min_margin {ref['min_margin']:.3e}, {kr.sweep_classes(ref)}")
+    assert kr.sweep_conditions(fix, ref) == []
+    assert len(ref["success"]) == 4096 and fix["iters"] == 1 and (ref["num_valid"] == 44).all()
+    # the cache changes nothing: a few pairs alone, without one
+    some = [0, 17, 4095]
+    sub = dict(fix, coord_2d=fix["coord_2d"][some], coord_3d=fix["coord_3d"][some], counts=fix["counts"][some], n_slots=3)
+    alone = kr.run_ref_on(sub, False, fix["pair_keys"][some])
+    for k in ("success", "quality", "inliers", "ransac_R", "ransac_t", "cnt", "draws"):
+        assert np.array_equal(alone[k], ref[k][some]), k
+
+
+def test_sparse_fixture_conditions():
+    fix = kr.sparse_fixture()
+    ref = kr.run_ref_on(fix, False, fix["pair_keys"], cache={})
+    print(f"sparse-validity sweep: min_margin {ref['min_margin']:.3e}, {kr.sparse_classes(ref)}")
+    assert kr.sparse_conditions(fix, ref) == []
+    assert len(ref["success"]) == 2048
+
+
+def test_stride_fixture_conditions():
+    fix = kr.stride_fixture()
+    refs = kr.stride_refs(fix)
+    facts = kr.stride_facts(fix, refs)
+    print(f"stride fixture: min_margin {min(r['min_margin'] for r in refs.values()):.3e}; beyond the budget {facts['beyond']}; ties {facts['ties']}; "
+          f"shrinks {facts['shrinks']}")
+    assert kr.stride_conditions(fix, refs) == []
+    assert fix["counts"].tolist() == [700, 300, 257, 64, 757, 700] and fix["K"] == 700 and fix["iters"] == 1024
+    assert np.array_equal(fix["A"][0], np.eye(3)) and not np.allclose(fix["A"][1], np.eye(3))
+    assert abs(1.0 - fix["good"][5].sum() / 700.0 - 0.7) < 0.01
+    # a restatement on the other confidence, or the other keys, is told apart by the comparison the GPU test uses
+    as_dev = kr.as_device
+    for (conf, keyed), ref in refs.items():
+        assert kr.compare(as_dev(ref), ref)[0] == []
+        assert kr.compare(as_dev(ref), refs[(0.5 if conf == 0.99 else 0.99, keyed)])[0]
+        assert kr.compare(as_dev(ref), refs[(conf, not keyed)])[0]
+
+
+def test_late_winner_fixture_conditions():
+    fix = kr.late_winner_fixture()
+    ref = kr.run_ref_on(fix)
+    print(f"late winner: min_margin {ref['min_margin']:.3e}, best_h {ref['best_h'][0]}, {ref['quality'][0]} inliers")
+    assert kr.late_conditions(fix, ref) == []
+    assert ref["best_h"][0] >= 256 and ref["best_h"][0] % 256 != 0 and fix["iters"] == 1024 and fix["K"] == 64
+
+
+def test_limit_fixture_conditions():
+    fix = kr.limit_fixture()
+    ref = kr.run_ref_on(fix)
+    print(f"the limits: min_margin {ref['min_margin']:.3e}, best_h {ref['best_h'].tolist()}, quality {ref['quality'].tolist()}")
+    assert kr.limit_conditions(fix, ref) == []
+    assert fix["K"] == fix["iters"] == 4096 and fix["counts"].tolist() == [4096, 4196]
+
+
+def test_edge_fixture_conditions_and_hand_list():
+    fix = kr.edge_fixture()
+    ref = kr.run_ref_on(fix)
+    print(f"lift edges: min_margin (ties left out) {ref['min_margin']:.3e}")
+    assert kr.edge_conditions(fix, ref) == []
+    assert sum(kr.EDGE_VALID) == 21 and sum(kr.EDGE_INLIER) == 20 and len(kr.EDGE_VALID) == fix["K"] == 30
+    # every tie point's residual is far inside tau, every refused one would have been an inlier had its pixel been read: the mask tells
+    Y, valid = kr.lift(fix["coord_2d"][0], kr.camera_tuple(fix["solve"][0]), kr.camera_tuple(fix["frames"][0]), np.eye(3), fix["depth"][0])
+    assert valid.astype(int).tolist() == kr.EDGE_VALID
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = np.sqrt(kr.residuals2(*fix["poses"][0], fix["coord_3d"][0], Y))
+    assert d[np.array(kr.EDGE_INLIER, bool)].max() < 1e-3 * fix["tau"][0]
+
+
+def test_conditioning_fixture_conditions():
+    fix = kr.conditioning_fixture()
+    ref = kr.run_ref_on(fix)
+    print(f"refit conditioning: min_margin {ref['min_margin']:.3e}, eig_gap {ref['eig_gap'].round(3).tolist()}, quality {ref['quality'].tolist()}")
+    assert kr.conditioning_conditions(fix, ref) == []
+    assert (ref["eig_gap"] > 1e-6).all()
+    assert np.array_equal(fix["poses"][2][0], np.eye(3)) and fix["poses"][5][1][2] == 5000.0
+    for p in (3, 4):   # half-turns: R = R^T, trace -1 (the quaternion's w is 0)
+        R = fix["poses"][p][0]
+        assert np.abs(R - R.T).max() < 1e-15 and abs(np.trace(R) + 1.0) < 1e-15
