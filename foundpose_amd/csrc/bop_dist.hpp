@@ -1,12 +1,11 @@
 // BOP's distance image and visibility test, shared by vsd.hip and gt_info.hip: one copy, so the two cannot drift apart.
-// fp64, every operation rounded on its own (explicit _rn intrinsics: no contraction whatever the translation unit's setting).
+// fp64, every operation rounded on its own (rounded.hpp's _rn wrappers: no contraction whatever the translation unit's setting).
 #pragma once
 #include "common.hpp"
+#include "rounded.hpp"
 
 namespace {
 
-FP_DEVICE double dmul(double a, double b) { return __dmul_rn(a, b); }
-FP_DEVICE double dadd(double a, double b) { return __dadd_rn(a, b); }
 // misc.depth_im_to_dist_im_fast: sqrt(Xs**2 + Ys**2 + depth**2) with Xs = xs * depth, Ys = ys * depth
 FP_DEVICE double dist(double xs, double ys, float d) {
   const double dd = (double)d, X = dmul(xs, dd), Y = dmul(ys, dd);

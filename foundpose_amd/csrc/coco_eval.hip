@@ -35,8 +35,6 @@ constexpr int CE_WAVES = CE_THREADS / 64;
 constexpr int CE_SUMS = CE_TILE_A * CE_TILE_B + CE_TILE_A + CE_TILE_B;  // intersections, areas of a, areas of b
 constexpr int CM_GT_PER_LANE = DA_MAX_GROUP_GT / 64;                     // 4
 
-FP_DEVICE int clampi(int x, int lo, int hi) { return min(max(x, lo), hi); }
-
 // A group as the kernels use it (the host validates the tables; the clamps keep a bad one that arrives all the same inside the arrays):
 // rows [e0, e0 + E) of a, [g0, g0 + G) of b, output rows p0 + e G + j, all of them below n_pairs.
 struct GroupDims { int e0, E, g0, G, p0; };

@@ -204,6 +204,7 @@ FP_DEVICE unsigned xcd_remap(unsigned bid, unsigned nwg) {
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+FP_DEVICE int clampi(int x, int lo, int hi) { return min(max(x, lo), hi); }
 
 // ---- per-device launch-time caches.  hipFuncSetAttribute(MaxDynamicSharedMemorySize) and the CU count are properties
 // of a (kernel, device) pair: the flag is kept per device id, so a process that drives several GPUs sets the attribute

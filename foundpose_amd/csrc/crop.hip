@@ -17,15 +17,10 @@
 //   nearest      S[cvRound(map_y)][cvRound(map_x)], 0 outside
 #include "common.hpp"
 #include "kernels.hpp"
+#include "rounded.hpp"
 #include "../../include/foundpose_amd.h"
 
 namespace {
-
-FP_DEVICE double dmul(double a, double b) { return __dmul_rn(a, b); }
-FP_DEVICE double dadd(double a, double b) { return __dadd_rn(a, b); }
-FP_DEVICE double dot3(double a0, double a1, double a2, double b0, double b1, double b2) {
-  return dadd(dadd(dmul(a0, b0), dmul(a1, b1)), dmul(a2, b2));
-}
 
 // Destination pixel (x, y) of one crop -> fp32 source window position (map_x, map_y).  p: the crop's 32 parameters.
 FP_DEVICE void crop_map(const double* p, int x, int y, int depth_check, float& fx, float& fy) {

@@ -25,8 +25,6 @@ constexpr int DA_MATCH_WAVES = DA_THREADS / DA_WAVE;          // (group, column)
 constexpr int DA_GT_PER_LANE = DA_MAX_GROUP_GT / DA_WAVE;     // 4
 constexpr int DA_NO_GT = 0x7fffffff;
 
-FP_DEVICE int clampi(int x, int lo, int hi) { return min(max(x, lo), hi); }
-
 __global__ __launch_bounds__(DA_THREADS) void detection_match_kernel(DetMatchArgs a) {
   const int lane = threadIdx.x & (DA_WAVE - 1);
   const int C = 2 * a.T;

@@ -3,68 +3,26 @@
 // reference solves its coarse poses on pixels only.
 //   lift    every correspondence's pixel (solve camera) -> ray -> frame camera (rotation A, the cameras share their centre) -> nearest
 //           depth pixel -> the measured point Y in the SOLVE camera, so that poses come out model -> solve camera like fp_pnp_ransac's;
-//   RANSAC  3 distinct valid correspondences per hypothesis (the sampler of pnp.hip), an edge-length congruence gate, the closed-form
+//   RANSAC  3 distinct valid correspondences per hypothesis (the sampler of ransac.hpp), an edge-length congruence gate, the closed-form
 //           fit R = F_Y F_X^T of the two triangle frames, t = mean(Y) - R mean(X); score = valid points within tau (mm) of their
-//           measurement; all hypotheses in parallel, then pnp.hip's sequential best-model rule replayed over the counts (model_points 3);
+//           measurement; all hypotheses in parallel, then the sequential best-model rule replayed over the counts (model_points 3, out
+//           of the valid correspondences);
 //   refit   Horn's closed form on the winner's inliers: centroids and the cross-covariance by block reductions in a fixed order, the
 //           largest eigenvector of the 4x4 quaternion matrix by cyclic Jacobi on one lane.
-// One 256-thread workgroup per pair; arithmetic in fp64, points stored as fp32.  mix64, update_num_iters, normalize3 and tri_frame are
-// copies of pnp.hip's (its device code stays untouched); every sum has a fixed order and there are no atomics, so a pair's result
-// depends on (seed, key, its own data) only.
+// One 256-thread workgroup per pair; arithmetic in fp64, points stored as fp32.  The sampler, the replay, the triangle frame, the output
+// records and the block reduction are ransac.hpp's, shared with pnp.hip; the lift, the gate, the fit, the residual and the refit are this
+// file's, and so are the two fields PnP does not have (num_valid, the status -1).  Every sum has a fixed order and there are no atomics,
+// so a pair's result depends on (seed, key, its own data) only.
 #include "common.hpp"
 #include "kernels.hpp"
-#include "rot.hpp"
+#include "ransac.hpp"
 
 namespace {
 
-constexpr int KB_THREADS = 256;
 constexpr int KB_MAX_ITERS = 4096;
 constexpr int KB_MAX_K = 4096;
 constexpr int KB_JACOBI_SWEEPS = 30;
-
-struct Pose {
-  double R[9];
-  double t[3];
-};
-
-FP_DEVICE unsigned long long mix64(unsigned long long z) {  // splitmix64 finaliser (pnp.hip)
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-FP_DEVICE bool normalize3(double* a) {
-  const double n = sqrt(dot3(a, a));
-  if (!(n > 1e-300)) return false;
-  a[0] /= n; a[1] /= n; a[2] /= n;
-  return true;
-}
-
-// orthonormal frame of a triangle: e1 along Q1-Q0, e3 normal, e2 = e3 x e1 (columns of F) (pnp.hip)
-FP_DEVICE bool tri_frame(const double* q0, const double* q1, const double* q2, double* F) {
-  double e1[3] = {q1[0] - q0[0], q1[1] - q0[1], q1[2] - q0[2]};
-  double d2[3] = {q2[0] - q0[0], q2[1] - q0[1], q2[2] - q0[2]};
-  double e3[3], e2[3];
-  if (!normalize3(e1)) return false;
-  cross3(e1, d2, e3);
-  if (!normalize3(e3)) return false;
-  cross3(e3, e1, e2);
-  for (int r = 0; r < 3; ++r) { F[r * 3 + 0] = e1[r]; F[r * 3 + 1] = e2[r]; F[r * 3 + 2] = e3[r]; }
-  return true;
-}
-
-// RANSACUpdateNumIters of OpenCV's point-set registrator (pnp.hip)
-FP_DEVICE int update_num_iters(double p, double ep, int model_points, int max_iters) {
-  p = fmin(fmax(p, 0.0), 1.0);
-  ep = fmin(fmax(ep, 0.0), 1.0);
-  double num = fmax(1.0 - p, 2.2250738585072014e-308);
-  double denom = 1.0 - pow(1.0 - ep, (double)model_points);
-  if (denom < 2.2250738585072014e-308) return 0;
-  num = log(num);
-  denom = log(denom);
-  return (denom >= 0 || -num >= max_iters * (-denom)) ? max_iters : (int)rint(num / denom);
-}
+constexpr int KB_LAST_ATTEMPT = 64;  // an index is drawn at most 65 times: attempts 0..64
 
 struct LiftCams {
   double fx, fy, cx, cy;      // solve camera
@@ -106,21 +64,11 @@ FP_DEVICE double resid2(const Pose& P, const float* X, const float* Y) {
   return x * x + y * y + z * z;
 }
 
-// hypothesis h of a pair: 3 distinct valid correspondences (an invalid or repeated index is drawn again, at most 64 times per index), the
-// congruence gate, the triangle-frame fit
+// hypothesis h of a pair: 3 distinct valid correspondences (an invalid or repeated index is drawn again, at most 64 redraws per index),
+// the congruence gate, the triangle-frame fit
 FP_DEVICE bool hypothesis(unsigned long long key, int N, const float* X3, const float* Y3, const unsigned char* valid, double tau, Pose* out) {
   int id[3];
-  unsigned long long s = key;
-  for (int j = 0; j < 3; ++j) {
-    for (int attempt = 0;; ++attempt) {
-      s = mix64(s);
-      const int c = (int)(s % (unsigned long long)N);
-      bool bad = !valid[c];
-      for (int i = 0; i < j; ++i) bad |= id[i] == c;
-      if (!bad) { id[j] = c; break; }
-      if (attempt >= 64) return false;
-    }
-  }
+  if (!ransac_draw<3, KB_LAST_ATTEMPT>(key, N, id, [&](int c) -> bool { return valid[c]; })) return false;
   double X[3][3], Y[3][3];
   for (int j = 0; j < 3; ++j)
     for (int r = 0; r < 3; ++r) { X[j][r] = X3[id[j] * 3 + r]; Y[j][r] = Y3[id[j] * 3 + r]; }
@@ -137,22 +85,6 @@ FP_DEVICE bool hypothesis(unsigned long long key, int N, const float* X3, const 
   for (int r = 0; r < 3; ++r) { mx[r] = (X[0][r] + X[1][r] + X[2][r]) / 3.0; my[r] = (Y[0][r] + Y[1][r] + Y[2][r]) / 3.0; }
   for (int i = 0; i < 3; ++i) out->t[i] = my[i] - (out->R[i * 3 + 0] * mx[0] + out->R[i * 3 + 1] * mx[1] + out->R[i * 3 + 2] * mx[2]);
   return true;
-}
-
-// NV per-thread partial sums -> their block totals in out[] (lane 0 writes; fixed order: butterfly within a wave, then waves 0..3)
-template <int NV>
-FP_DEVICE void block_sums(double* v, double (*acc)[12], double* out, int tid) {
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    double s = v[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((tid & 63) == 0) acc[tid >> 6][i] = s;
-  }
-  __syncthreads();
-  if (tid == 0)
-    for (int i = 0; i < NV; ++i) out[i] = acc[0][i] + acc[1][i] + acc[2][i] + acc[3][i];
-  __syncthreads();
 }
 
 // Largest eigenvector of the symmetric 4x4 M by cyclic Jacobi (row-major, destroyed): sweeps over the six off-diagonal pairs in the order
@@ -209,7 +141,7 @@ FP_DEVICE void jacobi4_largest(double* M, double* q) {
   for (int k = 0; k < 4; ++k) q[k] /= n;
 }
 
-__global__ __launch_bounds__(KB_THREADS) void kabsch_ransac_kernel(KabschArgs a) {
+__global__ __launch_bounds__(RANSAC_THREADS) void kabsch_ransac_kernel(KabschArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* X3 = reinterpret_cast<float*>(smem);                   // [k_max, 3] model points
   float* Y3 = X3 + (size_t)a.k_max * 3;                         // [k_max, 3] measured points, solve camera
@@ -225,15 +157,8 @@ __global__ __launch_bounds__(KB_THREADS) void kabsch_ransac_kernel(KabschArgs a)
   const int det = pair / a.n_slots;
   const int N = min(max(a.counts[pair], 0), a.k_max);
   auto fail = [&](int code, int num_valid) {
-    if (tid == 0) {
-      a.success[pair] = code;
-      a.n_inliers[pair] = 0;
-      a.num_valid[pair] = num_valid;
-      for (int i = 0; i < 9; ++i) a.R[(size_t)pair * 9 + i] = (i % 4 == 0) ? 1.0 : 0.0;
-      for (int i = 0; i < 3; ++i) a.t[(size_t)pair * 3 + i] = 0.0;
-      if (a.ransac_pose) for (int i = 0; i < 12; ++i) a.ransac_pose[(size_t)pair * 12 + i] = 0.0;
-    }
-    for (int i = tid; i < a.k_max; i += KB_THREADS) a.inlier_mask[(size_t)pair * a.k_max + i] = 0;
+    if (tid == 0) a.num_valid[pair] = num_valid;
+    ransac_write_failure(a, pair, tid, code);
   };
   const int image = a.image_index[det];
   if (image < 0 || image >= a.num_images) { fail(-1, 0); return; }  // block-uniform; reported as success = -1, the image is never read
@@ -247,7 +172,7 @@ __global__ __launch_bounds__(KB_THREADS) void kabsch_ransac_kernel(KabschArgs a)
   for (int i = 0; i < 9; ++i) lc.A[i] = a.A[det * 9 + i];
   const float* img = a.depth + (size_t)image * a.H * a.W;
   int nv = 0;
-  for (int p = tid; p < N; p += KB_THREADS) {
+  for (int p = tid; p < N; p += RANSAC_THREADS) {
     const size_t g = (size_t)pair * a.k_max + p;
     float Y[3] = {0.f, 0.f, 0.f};
     const bool ok = lift_point(lc, (double)a.coord_2d[g * 2 + 0], (double)a.coord_2d[g * 2 + 1], img, a.H, a.W, Y);
@@ -262,55 +187,35 @@ __global__ __launch_bounds__(KB_THREADS) void kabsch_ransac_kernel(KabschArgs a)
   const int num_valid = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
   if (num_valid < a.min_corresp) { fail(0, num_valid); return; }  // block-uniform
   const double thr2 = tau * tau;
-  const unsigned long long key = a.pair_keys ? a.pair_keys[pair] : (unsigned long long)pair;
-  const unsigned long long base = mix64(a.seed ^ (key * 0xD6E8FEB86659FD93ull));
+  const unsigned long long base = ransac_pair_base(a.seed, a.pair_keys, pair);
 
   // ---- all hypotheses, scored in parallel
-  for (int h = tid; h < a.iters; h += KB_THREADS) {
+  for (int h = tid; h < a.iters; h += RANSAC_THREADS) {
     Pose P;
     int c = 0;
-    if (hypothesis(base + (unsigned long long)h * 0x9E3779B97F4A7C15ull, N, X3, Y3, valid, tau, &P))
+    if (hypothesis(ransac_hypothesis_key(base, h), N, X3, Y3, valid, tau, &P))
       for (int p = 0; p < N; ++p) c += (valid[p] && resid2(P, X3 + p * 3, Y3 + p * 3) <= thr2) ? 1 : 0;
     cnt[h] = c;
   }
   __syncthreads();
   // ---- the sequential best-model rule with the adaptive iteration budget, replayed over the counts
-  if (tid == 0) {
-    int best = -1, best_c = 2, niters = a.iters;  // a model must beat model_points - 1 = 2 inliers
-    for (int h = 0; h < niters; ++h) {
-      if (cnt[h] > best_c) {
-        best_c = cnt[h];
-        best = h;
-        niters = update_num_iters(a.conf, (double)(num_valid - best_c) / num_valid, 3, niters);
-      }
-    }
-    s_best = best;
-    s_count = best_c;
-  }
+  if (tid == 0) s_best = ransac_replay(cnt, a.iters, a.conf, 3, num_valid, &s_count);  // 3 model points, out of the valid correspondences
   __syncthreads();
   if (s_best < 0) { fail(0, num_valid); return; }
-  if (tid == (s_best % KB_THREADS)) {  // the owner regenerates the winning hypothesis (deterministic)
+  if (tid == (s_best % RANSAC_THREADS)) {  // the owner regenerates the winning hypothesis (deterministic)
     Pose P;
-    hypothesis(base + (unsigned long long)s_best * 0x9E3779B97F4A7C15ull, N, X3, Y3, valid, tau, &P);
+    hypothesis(ransac_hypothesis_key(base, s_best), N, X3, Y3, valid, tau, &P);
     cur = P;
   }
   __syncthreads();
-  for (int p = tid; p < a.k_max; p += KB_THREADS) {
-    const unsigned char m = p < N && valid[p] && resid2(cur, X3 + p * 3, Y3 + p * 3) <= thr2;
-    if (p < N) inl[p] = m;
-    a.inlier_mask[(size_t)pair * a.k_max + p] = m;
-  }
-  if (tid == 0 && a.ransac_pose) {
-    for (int i = 0; i < 9; ++i) a.ransac_pose[(size_t)pair * 12 + i] = cur.R[i];
-    for (int i = 0; i < 3; ++i) a.ransac_pose[(size_t)pair * 12 + 9 + i] = cur.t[i];
-  }
+  ransac_write_winner(a, pair, tid, N, cur, inl, [&](int p) { return valid[p] && resid2(cur, X3 + p * 3, Y3 + p * 3) <= thr2; });
   __syncthreads();
 
   // ---- Horn's closed-form least-squares fit on the inliers
   if (a.refit) {
     double v[9];
     for (int i = 0; i < 6; ++i) v[i] = 0.0;
-    for (int p = tid; p < N; p += KB_THREADS) {
+    for (int p = tid; p < N; p += RANSAC_THREADS) {
       if (!inl[p]) continue;
       for (int r = 0; r < 3; ++r) { v[r] += X3[p * 3 + r]; v[3 + r] += Y3[p * 3 + r]; }
     }
@@ -319,7 +224,7 @@ __global__ __launch_bounds__(KB_THREADS) void kabsch_ransac_kernel(KabschArgs a)
     for (int r = 0; r < 3; ++r) { mx[r] = tot[r] / s_count; my[r] = tot[3 + r] / s_count; }
     __syncthreads();  // tot is read before the next reduction rewrites it
     for (int i = 0; i < 9; ++i) v[i] = 0.0;
-    for (int p = tid; p < N; p += KB_THREADS) {
+    for (int p = tid; p < N; p += RANSAC_THREADS) {
       if (!inl[p]) continue;
       const double x[3] = {X3[p * 3 + 0] - mx[0], X3[p * 3 + 1] - mx[1], X3[p * 3 + 2] - mx[2]};
       const double y[3] = {Y3[p * 3 + 0] - my[0], Y3[p * 3 + 1] - my[1], Y3[p * 3 + 2] - my[2]};
@@ -348,11 +253,8 @@ __global__ __launch_bounds__(KB_THREADS) void kabsch_ransac_kernel(KabschArgs a)
     __syncthreads();
   }
   if (tid == 0) {
-    a.success[pair] = 1;
-    a.n_inliers[pair] = s_count;
     a.num_valid[pair] = num_valid;
-    for (int i = 0; i < 9; ++i) a.R[(size_t)pair * 9 + i] = cur.R[i];
-    for (int i = 0; i < 3; ++i) a.t[(size_t)pair * 3 + i] = cur.t[i];
+    ransac_write_pose(a, pair, s_count, cur);
   }
 }
 
@@ -368,7 +270,7 @@ int launch_kabsch_ransac(const KabschArgs& a, int num_pairs, hipStream_t st) {
   const size_t lds = (size_t)a.k_max * 6 * 4 + (size_t)a.iters * 4 + (size_t)a.k_max * 2;
   static FpDeviceOnce attr;
   fp_allow_dynamic_lds(attr, &kabsch_ransac_kernel, KB_MAX_K * 6 * 4 + KB_MAX_ITERS * 4 + KB_MAX_K * 2);
-  hipLaunchKernelGGL(kabsch_ransac_kernel, dim3(num_pairs), dim3(KB_THREADS), lds, st, a);
+  hipLaunchKernelGGL(kabsch_ransac_kernel, dim3(num_pairs), dim3(RANSAC_THREADS), lds, st, a);
   FP_CHECK_LAUNCH("kabsch_ransac");
   return FP_OK;
 }

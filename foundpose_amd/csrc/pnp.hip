@@ -18,46 +18,17 @@
 //     the reprojection error in pixels, rotation updated on the manifold.
 // One 256-thread workgroup per (detection, template slot) pair; everything in fp64.  HBM traffic is a few KB per pair:
 // the kernel is latency / fp64-VALU bound.
+// This file holds what is PnP's own: the quartic, P3P, the reprojection residual, the fourth-point choice and the Levenberg-Marquardt
+// tail (its damped solve is not refine_terms.hpp's lm_solve: it damps with fmax(M_ii, 1e-12) and factorises in another order).  The
+// sampler, the best-model replay, the output records and the block reduction are ransac.hpp's, which kabsch.hip uses too.
 #include "common.hpp"
 #include "kernels.hpp"
-#include "rot.hpp"
+#include "ransac.hpp"
 
 namespace {
 
-constexpr int PNP_THREADS = 256;
 constexpr int PNP_MAX_ITERS = 4096;
-
-struct Pose {
-  double R[9];
-  double t[3];
-};
-
-FP_DEVICE unsigned long long mix64(unsigned long long z) {  // splitmix64 finaliser
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-FP_DEVICE bool normalize3(double* a) {
-  const double n = sqrt(dot3(a, a));
-  if (!(n > 1e-300)) return false;
-  a[0] /= n; a[1] /= n; a[2] /= n;
-  return true;
-}
-
-// orthonormal frame of a triangle: e1 along Q1-Q0, e3 normal, e2 = e3 x e1 (columns of F)
-FP_DEVICE bool tri_frame(const double* q0, const double* q1, const double* q2, double* F) {
-  double e1[3] = {q1[0] - q0[0], q1[1] - q0[1], q1[2] - q0[2]};
-  double d2[3] = {q2[0] - q0[0], q2[1] - q0[1], q2[2] - q0[2]};
-  double e3[3], e2[3];
-  if (!normalize3(e1)) return false;
-  cross3(e1, d2, e3);
-  if (!normalize3(e3)) return false;
-  cross3(e3, e1, e2);
-  for (int r = 0; r < 3; ++r) { F[r * 3 + 0] = e1[r]; F[r * 3 + 1] = e2[r]; F[r * 3 + 2] = e3[r]; }
-  return true;
-}
+constexpr int PNP_LAST_ATTEMPT = 65;  // an index is drawn at most 66 times: attempts 0..65
 
 // Real roots of x^4 + b3 x^3 + b2 x^2 + b1 x + b0 (Durand-Kerner on the four complex roots, then two Newton steps).
 FP_DEVICE int quartic_real_roots(double b3, double b2, double b1, double b0, double* out) {
@@ -166,17 +137,7 @@ FP_DEVICE double reproj_err2(const Pose& P, const float* X, const float* uv, dou
 // hypothesis h of a pair: sample 4 distinct correspondences, P3P on the first three, the fourth picks the solution
 FP_DEVICE bool hypothesis(unsigned long long key, int N, const float* X3, const float* UV, double fx, double fy, double cx, double cy, Pose* out) {
   int id[4];
-  unsigned long long s = key;
-  for (int j = 0; j < 4; ++j) {
-    for (int attempt = 0;; ++attempt) {
-      s = mix64(s);
-      const int c = (int)(s % (unsigned long long)N);
-      bool dup = false;
-      for (int i = 0; i < j; ++i) dup |= id[i] == c;
-      if (!dup) { id[j] = c; break; }
-      if (attempt > 64) return false;
-    }
-  }
+  if (!ransac_draw<4, PNP_LAST_ATTEMPT>(key, N, id, [](int) { return true; })) return false;  // every index is acceptable
   double X[3][3], f[3][3];
   for (int j = 0; j < 3; ++j) {
     for (int r = 0; r < 3; ++r) X[j][r] = X3[id[j] * 3 + r];
@@ -198,34 +159,12 @@ FP_DEVICE bool hypothesis(unsigned long long key, int N, const float* X3, const 
   return true;
 }
 
-FP_DEVICE double block_sum(double v, double* red, int tid) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
-// RANSACUpdateNumIters of OpenCV's point-set registrator
-FP_DEVICE int update_num_iters(double p, double ep, int model_points, int max_iters) {
-  p = fmin(fmax(p, 0.0), 1.0);
-  ep = fmin(fmax(ep, 0.0), 1.0);
-  double num = fmax(1.0 - p, 2.2250738585072014e-308);
-  double denom = 1.0 - pow(1.0 - ep, (double)model_points);
-  if (denom < 2.2250738585072014e-308) return 0;
-  num = log(num);
-  denom = log(denom);
-  return (denom >= 0 || -num >= max_iters * (-denom)) ? max_iters : (int)rint(num / denom);
-}
-
-__global__ __launch_bounds__(PNP_THREADS) void pnp_ransac_kernel(PnpArgs a) {
+__global__ __launch_bounds__(RANSAC_THREADS) void pnp_ransac_kernel(PnpArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* X3 = reinterpret_cast<float*>(smem);                 // [k_max, 3]
   float* UV = X3 + (size_t)a.k_max * 3;                       // [k_max, 2]
   int* cnt = reinterpret_cast<int*>(UV + (size_t)a.k_max * 2);  // [iters]
   unsigned char* inl = reinterpret_cast<unsigned char*>(cnt + a.iters);  // [k_max]
-  __shared__ double red[4];
   __shared__ double acc[4][28];
   __shared__ Pose cur, cand;
   __shared__ int s_best, s_count, s_flag;
@@ -236,64 +175,33 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_ransac_kernel(PnpArgs a) {
   const int det = pair / a.n_slots;
   const int N = min(a.counts[pair], a.k_max);
   const double fx = a.cam[det * 4 + 0], fy = a.cam[det * 4 + 1], cx = a.cam[det * 4 + 2], cy = a.cam[det * 4 + 3];
-  auto fail = [&]() {
-    if (tid == 0) {
-      a.success[pair] = 0;
-      a.n_inliers[pair] = 0;
-      for (int i = 0; i < 9; ++i) a.R[(size_t)pair * 9 + i] = (i % 4 == 0) ? 1.0 : 0.0;
-      for (int i = 0; i < 3; ++i) a.t[(size_t)pair * 3 + i] = 0.0;
-      if (a.ransac_pose) for (int i = 0; i < 12; ++i) a.ransac_pose[(size_t)pair * 12 + i] = 0.0;
-    }
-    for (int i = tid; i < a.k_max; i += PNP_THREADS) a.inlier_mask[(size_t)pair * a.k_max + i] = 0;
-  };
-  if (N < a.min_corresp) { fail(); return; }  // block-uniform
-  for (int i = tid; i < N * 3; i += PNP_THREADS) X3[i] = a.coord_3d[(size_t)pair * a.k_max * 3 + i];
-  for (int i = tid; i < N * 2; i += PNP_THREADS) UV[i] = a.coord_2d[(size_t)pair * a.k_max * 2 + i];
+  if (N < a.min_corresp) { ransac_write_failure(a, pair, tid, 0); return; }  // block-uniform
+  for (int i = tid; i < N * 3; i += RANSAC_THREADS) X3[i] = a.coord_3d[(size_t)pair * a.k_max * 3 + i];
+  for (int i = tid; i < N * 2; i += RANSAC_THREADS) UV[i] = a.coord_2d[(size_t)pair * a.k_max * 2 + i];
   __syncthreads();
   const double thr2 = a.thresh * a.thresh;
-  // the sampler key: the caller's (a pair then draws the same hypotheses wherever it sits in a launch) or the pair's index in this launch
-  const unsigned long long key = a.pair_keys ? a.pair_keys[pair] : (unsigned long long)pair;
-  const unsigned long long base = mix64(a.seed ^ (key * 0xD6E8FEB86659FD93ull));
+  const unsigned long long base = ransac_pair_base(a.seed, a.pair_keys, pair);
 
   // ---- all hypotheses, scored in parallel
-  for (int h = tid; h < a.iters; h += PNP_THREADS) {
+  for (int h = tid; h < a.iters; h += RANSAC_THREADS) {
     Pose P;
     int c = 0;
-    if (hypothesis(base + (unsigned long long)h * 0x9E3779B97F4A7C15ull, N, X3, UV, fx, fy, cx, cy, &P))
+    if (hypothesis(ransac_hypothesis_key(base, h), N, X3, UV, fx, fy, cx, cy, &P))
       for (int p = 0; p < N; ++p) c += reproj_err2(P, X3 + p * 3, UV + p * 2, fx, fy, cx, cy) <= thr2 ? 1 : 0;
     cnt[h] = c;
   }
   __syncthreads();
   // ---- the sequential best-model rule with the adaptive iteration budget, replayed over the counts
-  if (tid == 0) {
-    int best = -1, best_c = 3, niters = a.iters;  // a model must beat model_points - 1 = 3 inliers
-    for (int h = 0; h < niters; ++h) {
-      if (cnt[h] > best_c) {
-        best_c = cnt[h];
-        best = h;
-        niters = update_num_iters(a.conf, (double)(N - best_c) / N, 4, niters);
-      }
-    }
-    s_best = best;
-    s_count = best_c;
-  }
+  if (tid == 0) s_best = ransac_replay(cnt, a.iters, a.conf, 4, N, &s_count);  // 4 model points, out of all N correspondences
   __syncthreads();
-  if (s_best < 0) { fail(); return; }
-  if (tid == (s_best % PNP_THREADS)) {  // the owner regenerates the winning hypothesis (deterministic)
+  if (s_best < 0) { ransac_write_failure(a, pair, tid, 0); return; }
+  if (tid == (s_best % RANSAC_THREADS)) {  // the owner regenerates the winning hypothesis (deterministic)
     Pose P;
-    hypothesis(base + (unsigned long long)s_best * 0x9E3779B97F4A7C15ull, N, X3, UV, fx, fy, cx, cy, &P);
+    hypothesis(ransac_hypothesis_key(base, s_best), N, X3, UV, fx, fy, cx, cy, &P);
     cur = P;
   }
   __syncthreads();
-  for (int p = tid; p < a.k_max; p += PNP_THREADS) {
-    const unsigned char m = p < N && reproj_err2(cur, X3 + p * 3, UV + p * 2, fx, fy, cx, cy) <= thr2;
-    if (p < N) inl[p] = m;
-    a.inlier_mask[(size_t)pair * a.k_max + p] = m;
-  }
-  if (tid == 0 && a.ransac_pose) {
-    for (int i = 0; i < 9; ++i) a.ransac_pose[(size_t)pair * 12 + i] = cur.R[i];
-    for (int i = 0; i < 3; ++i) a.ransac_pose[(size_t)pair * 12 + 9 + i] = cur.t[i];
-  }
+  ransac_write_winner(a, pair, tid, N, cur, inl, [&](int p) { return reproj_err2(cur, X3 + p * 3, UV + p * 2, fx, fy, cx, cy) <= thr2; });
   __syncthreads();
 
   // ---- Levenberg-Marquardt on the inliers: cost, J^T J (21 upper entries) and J^T r (6) of a pose, block-reduced
@@ -301,7 +209,7 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_ransac_kernel(PnpArgs a) {
     double v[28];
 #pragma unroll
     for (int i = 0; i < 28; ++i) v[i] = 0.0;
-    for (int p = tid; p < N; p += PNP_THREADS) {
+    for (int p = tid; p < N; p += RANSAC_THREADS) {
       if (!inl[p]) continue;
       const float* Xp = X3 + p * 3;
       const double x = P.R[0] * Xp[0] + P.R[1] * Xp[1] + P.R[2] * Xp[2] + P.t[0];
@@ -329,19 +237,12 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_ransac_kernel(PnpArgs a) {
 #pragma unroll
       for (int i = 0; i < 6; ++i) v[21 + i] += Ju[i] * ru + Jv[i] * rv;
     }
-    const int first = want_jac ? 0 : 27;
-    for (int i = first; i < 28; ++i) {
-      double s = v[i];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-      if ((tid & 63) == 0) acc[tid >> 6][i] = s;
-    }
-    __syncthreads();
+    block_partials<28>(v, acc, tid, want_jac ? 0 : 27);  // the cost alone is slot 27
     if (tid == 0 && want_jac) {
-      for (int i = 0; i < 21; ++i) s_A[i] = acc[0][i] + acc[1][i] + acc[2][i] + acc[3][i];
-      for (int i = 0; i < 6; ++i) s_g[i] = acc[0][21 + i] + acc[1][21 + i] + acc[2][21 + i] + acc[3][21 + i];
+      for (int i = 0; i < 21; ++i) s_A[i] = block_total(acc, i);
+      for (int i = 0; i < 6; ++i) s_g[i] = block_total(acc, 21 + i);
     }
-    const double cost = acc[0][27] + acc[1][27] + acc[2][27] + acc[3][27];
+    const double cost = block_total(acc, 27);
     __syncthreads();
     return cost;
   };
@@ -414,12 +315,7 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_ransac_kernel(PnpArgs a) {
     if (step_flag == 2) break;
   }
   __syncthreads();
-  if (tid == 0) {
-    a.success[pair] = 1;
-    a.n_inliers[pair] = s_count;
-    for (int i = 0; i < 9; ++i) a.R[(size_t)pair * 9 + i] = cur.R[i];
-    for (int i = 0; i < 3; ++i) a.t[(size_t)pair * 3 + i] = cur.t[i];
-  }
+  if (tid == 0) ransac_write_pose(a, pair, s_count, cur);
 }
 
 }  // namespace
@@ -433,7 +329,7 @@ int launch_pnp_ransac(const PnpArgs& a, int num_pairs, hipStream_t st) {
   const size_t lds = (size_t)a.k_max * 5 * 4 + (size_t)a.iters * 4 + (size_t)a.k_max;
   static FpDeviceOnce attr;
   fp_allow_dynamic_lds(attr, &pnp_ransac_kernel, 4096 * 5 * 4 + PNP_MAX_ITERS * 4 + 4096);
-  hipLaunchKernelGGL(pnp_ransac_kernel, dim3(num_pairs), dim3(PNP_THREADS), lds, st, a);
+  hipLaunchKernelGGL(pnp_ransac_kernel, dim3(num_pairs), dim3(RANSAC_THREADS), lds, st, a);
   FP_CHECK_LAUNCH("pnp_ransac");
   return FP_OK;
 }

@@ -24,6 +24,7 @@
 //                         pts_diameter_fold_kernel: one workgroup folds the partials and takes the root.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "rounded.hpp"
 #include "../../include/foundpose_amd.h"
 
 namespace {
@@ -32,15 +33,6 @@ constexpr int PE_THREADS = 256;
 constexpr int PE_Q = 4;                     // queries per thread
 constexpr int PE_TILE = PE_THREADS * PE_Q;  // queries per workgroup = targets per LDS tile (24 KB)
 static_assert(PE_TILE == FP_PTS_TILE, "FP_PTS_TILE of the header");
-
-FP_DEVICE double dmul(double a, double b) { return __dmul_rn(a, b); }
-FP_DEVICE double dadd(double a, double b) { return __dadd_rn(a, b); }
-FP_DEVICE double dsub(double a, double b) { return __dsub_rn(a, b); }
-// r.dot(p) + t: ((r0 x + r1 y) + r2 z) + t
-FP_DEVICE double affine(const double* r, double t, double x, double y, double z) {
-  return dadd(dadd(dadd(dmul(r[0], x), dmul(r[1], y)), dmul(r[2], z)), t);
-}
-FP_DEVICE double sqdist(double dx, double dy, double dz) { return dadd(dadd(dmul(dx, dx), dmul(dy, dy)), dmul(dz, dz)); }
 
 // a maximum with the index pair it came from; v is never a NaN.  `wins`: greater, or equal with the lexicographically lower pair.
 struct Cand { double v; int a, b; };

@@ -24,6 +24,7 @@
 // tile partials in tile order and divides.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "rounded.hpp"
 #include "../../include/foundpose_amd.h"
 
 namespace {
@@ -34,15 +35,6 @@ constexpr int PA_BLOCK = PA_TILE * PA_Q;    // query points per workgroup
 constexpr int PA_LDS_PTS = 1024;            // estimate points per LDS tile (24 KB)
 static_assert(PA_BLOCK == FP_POSE_ADD_BLOCK, "FP_POSE_ADD_BLOCK of the header");
 static_assert(PA_LDS_PTS % PA_TILE == 0 && PA_LDS_PTS % 4 == 0 && 2 * PA_BLOCK <= 3 * PA_LDS_PTS, "the value tiles reuse the point tile's LDS");
-
-FP_DEVICE double dmul(double a, double b) { return __dmul_rn(a, b); }
-FP_DEVICE double dadd(double a, double b) { return __dadd_rn(a, b); }
-FP_DEVICE double dsub(double a, double b) { return __dsub_rn(a, b); }
-// r.dot(p) + t: ((r0 x + r1 y) + r2 z) + t
-FP_DEVICE double affine(const double* r, double t, double x, double y, double z) {
-  return dadd(dadd(dadd(dmul(r[0], x), dmul(r[1], y)), dmul(r[2], z)), t);
-}
-FP_DEVICE double sqdist(double dx, double dy, double dz) { return dadd(dadd(dmul(dx, dx), dmul(dy, dy)), dmul(dz, dz)); }
 
 __global__ __launch_bounds__(PA_TILE) void pose_add_nn_kernel(PoseAddArgs a) {
   const PoseAddPair pd = a.pairs[blockIdx.y];

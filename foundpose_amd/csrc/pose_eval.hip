@@ -26,6 +26,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "rounded.hpp"
 #include "../../include/foundpose_amd.h"
 
 namespace {
@@ -36,13 +37,6 @@ constexpr int PE_SYM_CHUNK = 16;                  // symmetries per wave
 constexpr int PE_WAVES = 4;                       // waves per workgroup (partial kernel)
 constexpr int PE_FOLD_THREADS = 256;
 
-FP_DEVICE double dmul(double a, double b) { return __dmul_rn(a, b); }
-FP_DEVICE double dadd(double a, double b) { return __dadd_rn(a, b); }
-FP_DEVICE double dsub(double a, double b) { return __dsub_rn(a, b); }
-// r.dot(p) + t: ((r0 x + r1 y) + r2 z) + t
-FP_DEVICE double affine(const double* r, double t, double x, double y, double z) {
-  return dadd(dadd(dadd(dmul(r[0], x), dmul(r[1], y)), dmul(r[2], z)), t);
-}
 FP_DEVICE bool isnan_d(double a) { return a != a; }
 
 // (a, ia) preferred to (b, ib) for a maximum with np.argmax's rules: a NaN beats every number, ties -> lower index

@@ -22,6 +22,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "rounded.hpp"
 #include "../../include/foundpose_amd.h"
 
 namespace {
@@ -29,12 +30,6 @@ namespace {
 constexpr int TILE = FP_RENDER_TILE;  // 32 x 32 pixels per raster workgroup
 constexpr int CHUNK = 256;            // triangle records staged through LDS per step
 
-FP_DEVICE double dmul(double a, double b) { return __dmul_rn(a, b); }
-FP_DEVICE double dadd(double a, double b) { return __dadd_rn(a, b); }
-FP_DEVICE double ddiv(double a, double b) { return __ddiv_rn(a, b); }
-FP_DEVICE double dot3(double a0, double a1, double a2, double b0, double b1, double b2) {
-  return dadd(dadd(dmul(a0, b0), dmul(a1, b1)), dmul(a2, b2));
-}
 FP_DEVICE float fm(float a, float b) { return __fmul_rn(a, b); }
 FP_DEVICE float fa(float a, float b) { return __fadd_rn(a, b); }
 FP_DEVICE float fsub(float a, float b) { return __fsub_rn(a, b); }
