@@ -116,6 +116,10 @@ _PROTOS = {
     "fp_directed_hausdorff": [vp, i32, i32, vp, i32, vp, C.c_size_t, vp, vp, vp],
     "fp_vsd_counts": [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp],
     "fp_gt_visibility": [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, vp, C.c_size_t, vp, vp, vp, vp],
+    "fp_depth_plane_fit": [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, f64, f64, f64, u64, vp, C.c_size_t, vp, vp, vp, vp],
+    "fp_depth_components": [vp, i32, i32, i32, vp, vp, vp, vp, f64, f64, f32, vp, C.c_size_t, vp, vp],
+    "fp_component_table": [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, C.c_size_t, vp, vp, vp, vp],
+    "fp_component_runs": [vp, i32, i32, i32, vp, i32, i64, vp, vp, vp],
     "fp_featuremetric_refine": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32,
                                 vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "fp_depth_refine": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
@@ -232,6 +236,25 @@ def vsd_scratch_bytes(num_pairs: int) -> int:
 def gt_vis_scratch_bytes(num_inst: int) -> int:
     """FP_GT_VIS_SCRATCH_BYTES of include/foundpose_amd.h."""
     return 80 * num_inst
+
+
+DEPTH_MAX_PLANES, DEPTH_MAX_HYPOTHESES, DEPTH_MAX_PROPOSALS, DEPTH_PLANE_CHUNK = 4, 4096, 1024, 4096  # FP_DEPTH_* of the header
+
+
+def depth_plane_scratch_bytes(num_frames: int, pixels: int, hypotheses: int) -> int:
+    """FP_DEPTH_PLANE_SCRATCH_BYTES of include/foundpose_amd.h."""
+    return (256 * num_frames + 16 * ((num_frames * pixels + 15) // 16) + 8 * ((num_frames * hypotheses + 1) // 2)
+            + 64 * num_frames * ((pixels + DEPTH_PLANE_CHUNK - 1) // DEPTH_PLANE_CHUNK))
+
+
+def depth_components_scratch_bytes(num_frames: int, pixels: int) -> int:
+    """FP_DEPTH_COMPONENTS_SCRATCH_BYTES of include/foundpose_amd.h."""
+    return 64 * num_frames + 4 * num_frames * pixels
+
+
+def component_table_scratch_bytes(num_frames: int, pixels: int) -> int:
+    """FP_COMPONENT_TABLE_SCRATCH_BYTES of include/foundpose_amd.h."""
+    return 16 * num_frames + 28 * num_frames * pixels
 
 
 REFINE_CHUNK, REFINE_RECORD, REFINE_STATE_BYTES = 32, 32, 512  # FP_REFINE_* of the header

@@ -1,6 +1,6 @@
 // C ABI of libfoundpose_amd.so (declared in include/foundpose_amd.h): argument checking, scratch carving
 // and kernel sequencing.  No device allocation, no global mutable state, no synchronisation except the table uploads of
-// fp_pose_errors, fp_vsd_counts and fp_gt_visibility (each waits for its own copy) and the range check read back by the three refinements (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine).
+// fp_pose_errors, fp_vsd_counts, fp_gt_visibility, fp_depth_plane_fit and fp_depth_components (each waits for its own copy) and the range check read back by the three refinements (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine).
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -1198,6 +1198,141 @@ int fp_gt_visibility(const float* depth_test, int num_test, int height, int widt
   a.num_inst = num_inst, a.height = height, a.width = width, a.render_h = render_height, a.render_w = render_width;
   a.out = out, a.mask = mask, a.mask_visib = mask_visib;
   return launch_gt_visibility(a, blocks, ST(stream));
+}
+
+// ------------------------------------------------------------------ mask proposals from depth
+}  // extern "C"
+
+// the checks the two depth entries share; the frame table goes into `tab`
+static int depth_frames(const char* who, const void* depth, int num_frames, int height, int width, const double* cameras, double max_depth_mm,
+                        std::vector<DpFrame>& tab) {
+  FP_REQUIRE(depth && cameras, "%s: null pointer", who);
+  FP_REQUIRE(num_frames >= 1 && num_frames <= FP_DEPTH_MAX_FRAMES, "%s: num_frames %d outside [1, %d]", who, num_frames, FP_DEPTH_MAX_FRAMES);
+  FP_REQUIRE(height >= 1 && width >= 1 && (long long)height * width <= 0x7fffffffll, "%s: an image of %d x %d (1 .. 2^31 - 1 pixels)", who, width, height);
+  FP_REQUIRE(max_depth_mm >= 0.0 && std::isfinite(max_depth_mm), "%s: max_depth_mm must be finite and >= 0", who);
+  tab.resize(num_frames);
+  for (int f = 0; f < num_frames; ++f) {
+    const double* c = cameras + 4 * (size_t)f;
+    FP_REQUIRE(std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]) && std::isfinite(c[3]) && c[0] > 0 && c[1] > 0,
+               "%s: frame %d: the camera must be finite with fx, fy > 0", who, f);
+    memset(&tab[f], 0, sizeof(DpFrame));
+    tab[f].fx = c[0], tab[f].fy = c[1], tab[f].cx = c[2], tab[f].cy = c[3];
+  }
+  return FP_OK;
+}
+
+extern "C" {
+
+int fp_depth_plane_fit(const float* depth, int num_frames, int height, int width, const double* cameras, const uint64_t* frame_keys,
+                       const double* prior_planes, const int32_t* num_prior, int hypotheses, int stride, double plane_thresh_mm,
+                       double max_depth_mm, double min_plane_share, uint64_t seed, void* scratch, size_t scratch_bytes,
+                       double* plane_out, int32_t* info, int32_t* hyp_counts, fp_stream_t stream) {
+  FP_REQUIRE(frame_keys && prior_planes && num_prior && scratch && plane_out && info, "fp_depth_plane_fit: null pointer");
+  std::vector<DpFrame> tab;
+  TRY(depth_frames("fp_depth_plane_fit", depth, num_frames, height, width, cameras, max_depth_mm, tab));
+  FP_REQUIRE(hypotheses >= 1 && hypotheses <= FP_DEPTH_MAX_HYPOTHESES, "fp_depth_plane_fit: hypotheses %d outside [1, %d]", hypotheses, FP_DEPTH_MAX_HYPOTHESES);
+  FP_REQUIRE(stride >= 1 && stride <= 64, "fp_depth_plane_fit: stride %d outside [1, 64]", stride);
+  FP_REQUIRE(plane_thresh_mm > 0.0 && std::isfinite(plane_thresh_mm), "fp_depth_plane_fit: plane_thresh_mm must be finite and > 0");
+  FP_REQUIRE(min_plane_share >= 0.0 && min_plane_share <= 1.0, "fp_depth_plane_fit: min_plane_share outside [0, 1]");
+  const size_t hw = (size_t)height * width, n = (size_t)num_frames;
+  FP_REQUIRE(scratch_bytes >= FP_DEPTH_PLANE_SCRATCH_BYTES(n, hw, hypotheses), "fp_depth_plane_fit: scratch holds %zu bytes, %zu needed",
+             scratch_bytes, FP_DEPTH_PLANE_SCRATCH_BYTES(n, hw, hypotheses));
+  static_assert(sizeof(DpFrame) == 48, "layout of the frame table");
+  for (int f = 0; f < num_frames; ++f) tab[f].key = frame_keys[f];
+  char* s = reinterpret_cast<char*>(scratch);
+  DpPlaneArgs a;
+  memset(&a, 0, sizeof(a));
+  a.depth = depth, a.prior = prior_planes, a.num_prior = num_prior;
+  a.n = num_frames, a.h = height, a.w = width, a.hyp = hypotheses, a.stride = stride;
+  a.chunks = (int)((hw + FP_DEPTH_PLANE_CHUNK - 1) / FP_DEPTH_PLANE_CHUNK);
+  a.thresh = plane_thresh_mm, a.max_depth = max_depth_mm, a.min_share = min_plane_share, a.seed = seed;
+  a.frames = reinterpret_cast<const DpFrame*>(s);
+  a.cnt2 = reinterpret_cast<int*>(s + 64 * n);
+  a.state = reinterpret_cast<double*>(s + 128 * n);
+  a.elig = reinterpret_cast<unsigned char*>(s + 256 * n);
+  int* hyp_scratch = reinterpret_cast<int*>(s + 256 * n + 16 * ((n * hw + 15) / 16));
+  a.hyp_cnt = hyp_counts ? hyp_counts : hyp_scratch;
+  a.part = reinterpret_cast<double*>(reinterpret_cast<char*>(hyp_scratch) + 8 * ((n * (size_t)hypotheses + 1) / 2));
+  a.plane_out = plane_out, a.info = info;
+  // the table lives in this frame, so the copy completes before it goes out of scope
+  HIP_TRY(hipMemcpyWithStream(s, tab.data(), sizeof(DpFrame) * n, hipMemcpyHostToDevice, ST(stream)), "fp_depth_plane_fit: table upload");
+  HIP_TRY(hipMemsetAsync(a.cnt2, 0, 8 * n, ST(stream)), "fp_depth_plane_fit: zeroing the counters");
+  return launch_depth_plane_fit(a, ST(stream));
+}
+
+int fp_depth_components(const float* depth, int num_frames, int height, int width, const double* cameras, const float* slope_fx,
+                        const double* planes, const int32_t* num_planes, double max_depth_mm, double object_margin_mm, float connect_mm,
+                        void* scratch, size_t scratch_bytes, int32_t* labels, fp_stream_t stream) {
+  FP_REQUIRE(slope_fx && planes && num_planes && scratch && labels, "fp_depth_components: null pointer");
+  std::vector<DpFrame> tab;
+  TRY(depth_frames("fp_depth_components", depth, num_frames, height, width, cameras, max_depth_mm, tab));
+  FP_REQUIRE(std::isfinite(object_margin_mm), "fp_depth_components: object_margin_mm must be finite");
+  FP_REQUIRE(connect_mm >= 0.f && std::isfinite(connect_mm), "fp_depth_components: connect_mm must be finite and >= 0");
+  const size_t hw = (size_t)height * width, n = (size_t)num_frames;
+  for (int f = 0; f < num_frames; ++f) {
+    FP_REQUIRE(slope_fx[f] >= 0.f && std::isfinite(slope_fx[f]), "fp_depth_components: frame %d: slope_fx must be finite and >= 0", f);
+    tab[f].slope_fx = slope_fx[f];
+  }
+  FP_REQUIRE(scratch_bytes >= FP_DEPTH_COMPONENTS_SCRATCH_BYTES(n, hw), "fp_depth_components: scratch holds %zu bytes, %zu needed", scratch_bytes,
+             FP_DEPTH_COMPONENTS_SCRATCH_BYTES(n, hw));
+  char* s = reinterpret_cast<char*>(scratch);
+  DpCompArgs a;
+  memset(&a, 0, sizeof(a));
+  a.depth = depth, a.planes = planes, a.num_planes = num_planes;
+  a.n = num_frames, a.h = height, a.w = width, a.connect_mm = connect_mm, a.max_depth = max_depth_mm, a.margin = object_margin_mm;
+  a.frames = reinterpret_cast<const DpFrame*>(s);
+  a.parent = reinterpret_cast<int*>(s + 64 * n);
+  a.labels = labels;
+  HIP_TRY(hipMemcpyWithStream(s, tab.data(), sizeof(DpFrame) * n, hipMemcpyHostToDevice, ST(stream)), "fp_depth_components: table upload");
+  return launch_depth_components(a, ST(stream));
+}
+
+int fp_component_table(const int32_t* labels, int num_frames, int height, int width, int min_pixels, int max_area, int max_proposals,
+                       int level, const int32_t* finer, int num_finer, void* scratch, size_t scratch_bytes, int32_t* table,
+                       int32_t* counts, int32_t* rank_map, fp_stream_t stream) {
+  FP_REQUIRE(labels && scratch && table && counts && rank_map, "fp_component_table: null pointer");
+  FP_REQUIRE(num_frames >= 1 && num_frames <= FP_DEPTH_MAX_FRAMES, "fp_component_table: num_frames %d outside [1, %d]", num_frames, FP_DEPTH_MAX_FRAMES);
+  FP_REQUIRE(height >= 1 && width >= 1 && (long long)height * width <= 0x7fffffffll, "fp_component_table: an image of %d x %d (1 .. 2^31 - 1 pixels)",
+             width, height);
+  FP_REQUIRE(min_pixels >= 1 && max_area >= min_pixels, "fp_component_table: min_pixels %d, max_area %d (1 <= min_pixels <= max_area)", min_pixels, max_area);
+  FP_REQUIRE(max_proposals >= 1 && max_proposals <= FP_DEPTH_MAX_PROPOSALS, "fp_component_table: max_proposals %d outside [1, %d]", max_proposals,
+             FP_DEPTH_MAX_PROPOSALS);
+  FP_REQUIRE(level >= 0 && level <= 2 && num_finer >= 0 && num_finer <= 2, "fp_component_table: level %d, num_finer %d (both in [0, 2])", level, num_finer);
+  FP_REQUIRE((num_finer == 0) == (finer == nullptr), "fp_component_table: finer and num_finer disagree");
+  const size_t hw = (size_t)height * width, n = (size_t)num_frames;
+  FP_REQUIRE(scratch_bytes >= FP_COMPONENT_TABLE_SCRATCH_BYTES(n, hw), "fp_component_table: scratch holds %zu bytes, %zu needed", scratch_bytes,
+             FP_COMPONENT_TABLE_SCRATCH_BYTES(n, hw));
+  char* s = reinterpret_cast<char*>(scratch);
+  DpTableArgs a;
+  memset(&a, 0, sizeof(a));
+  a.labels = labels, a.finer = finer;
+  a.n = num_frames, a.h = height, a.w = width, a.min_pixels = min_pixels, a.max_area = max_area, a.max_prop = max_proposals, a.level = level;
+  a.num_finer = num_finer;
+  a.ncand = reinterpret_cast<int*>(s);
+  a.cand = reinterpret_cast<int*>(s + 16 * n);
+  a.slots = reinterpret_cast<int*>(s + 16 * n + 4 * n * hw);
+  a.table = table, a.counts = counts, a.rank_map = rank_map;
+  return launch_component_table(a, ST(stream));
+}
+
+int fp_component_runs(const int32_t* rank_map, int num_maps, int height, int width, const int32_t* num_kept, int max_proposals,
+                      int64_t capacity, int64_t* events, int32_t* num_events, fp_stream_t stream) {
+  FP_REQUIRE(rank_map && num_kept && num_events, "fp_component_runs: null pointer");
+  FP_REQUIRE(num_maps >= 1 && height >= 1 && width >= 1 && (long long)height * width <= 0x7fffffffll, "fp_component_runs: %d maps of %d x %d", num_maps,
+             width, height);
+  FP_REQUIRE(max_proposals >= 1 && max_proposals <= FP_DEPTH_MAX_PROPOSALS, "fp_component_runs: max_proposals %d outside [1, %d]", max_proposals,
+             FP_DEPTH_MAX_PROPOSALS);
+  FP_REQUIRE(num_maps <= 65535 && (long long)num_maps * ((long long)height * width + 1 + max_proposals) <= (1ll << 30),
+             "fp_component_runs: %d maps of %d x %d exceed 2^30 positions (or 65535 maps)", num_maps, width, height);
+  FP_REQUIRE(capacity >= 0 && (capacity == 0 || events), "fp_component_runs: capacity %lld without an events array", (long long)capacity);
+  DpRunsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.rank_map = rank_map, a.num_kept = num_kept;
+  a.m = num_maps, a.h = height, a.w = width, a.max_prop = max_proposals, a.capacity = capacity;
+  a.events = reinterpret_cast<long long*>(events), a.count = num_events;
+  HIP_TRY(hipMemsetAsync(num_events, 0, 4, ST(stream)), "fp_component_runs: zeroing the counter");
+  if (capacity > 0) HIP_TRY(hipMemsetAsync(events, 0x7f, 8 * (size_t)capacity, ST(stream)), "fp_component_runs: filling events");
+  return launch_component_runs(a, ST(stream));
 }
 
 // ------------------------------------------------------------------ ViT forward (launch sequence in C++)

@@ -402,6 +402,64 @@ struct GtVisArgs {
 };
 int launch_gt_visibility(const GtVisArgs& a, long long num_blocks, hipStream_t st);
 
+// ---------------------------------------------------------------- depth_proposals.hip
+struct DpFrame {                         // one frame, built on the host by fp_depth_plane_fit / fp_depth_components
+  double fx, fy, cx, cy;
+  unsigned long long key;                // the sampler's frame key (plane fit only)
+  float slope_fx;                        // connect_slope / fx (components only)
+  int pad;
+};
+struct DpPlaneArgs {
+  const float* depth;                    // [n, h, w]
+  const DpFrame* frames;                 // [n] device copy
+  const double* prior;                   // [n, FP_DEPTH_MAX_PLANES, 4]
+  const int* num_prior;                  // [n]
+  int n, h, w, hyp, stride, chunks;
+  double thresh, max_depth, min_share;
+  unsigned long long seed;
+  unsigned char* elig;                   // [n, h w]
+  int* cnt2;                             // [n, 2] valid, eligible; zeroed by the host on the stream
+  int* hyp_cnt;                          // [n, hyp]
+  double* state;                         // [n, 16]
+  double* part;                          // [n, chunks, 8]
+  double* plane_out;                     // [n, 4]
+  int* info;                             // [n, 8]
+};
+int launch_depth_plane_fit(const DpPlaneArgs& a, hipStream_t st);
+struct DpCompArgs {
+  const float* depth;                    // [n, h, w]
+  const DpFrame* frames;                 // [n] device copy
+  const double* planes;                  // [n, FP_DEPTH_MAX_PLANES, 4]
+  const int* num_planes;                 // [n]
+  int n, h, w;
+  float connect_mm;
+  double max_depth, margin;
+  int* parent;                           // [n, h w] scratch
+  int* labels;                           // [n, h, w]
+};
+int launch_depth_components(const DpCompArgs& a, hipStream_t st);
+struct DpTableArgs {
+  const int* labels;                     // [n, h, w]
+  const int* finer;                      // [num_finer, n, max_prop, 7] tables of finer levels, or NULL
+  int n, h, w, min_pixels, max_area, max_prop, level, num_finer;
+  int* slots;                            // [n, h w, 6] scratch
+  int* cand;                             // [n, h w] scratch
+  int* ncand;                            // [n] scratch
+  int* table;                            // [n, max_prop, 7]
+  int* counts;                           // [n, 4]
+  int* rank_map;                         // [n, h, w]
+};
+int launch_component_table(const DpTableArgs& a, hipStream_t st);
+struct DpRunsArgs {
+  const int* rank_map;                   // [m, h, w]
+  const int* num_kept;                   // [m]
+  int m, h, w, max_prop;
+  long long capacity;
+  long long* events;                     // [capacity]
+  int* count;                            // [1], zeroed by the host on the stream
+};
+int launch_component_runs(const DpRunsArgs& a, hipStream_t st);
+
 // ---------------------------------------------------------------- vis.hip
 int launch_vis_mask_tint(const uint8_t* img, const uint8_t* mask, long long pixels, uint8_t* out, hipStream_t st);
 int launch_vis_contour(const uint8_t* mask, int batch, int h, int w, int dil, int r, int g, int b, uint8_t* img, hipStream_t st);

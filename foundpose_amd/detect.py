@@ -6,7 +6,8 @@
         "semantic_appearance"  also detector_patches.pth, the templates' patch descriptors, which run then loads
     python -m foundpose_amd.detect run --opts detect.json --proposals proposals.json --dataset-dir <split> --output-path <root> --output detections.json
         labels the proposals of every image they name and writes a CNOS detections file (what infer --detections takes) and
-        detector-decisions.json beside it
+        detector-decisions.json beside it; --proposals-from-depth [opts.json] in place of --proposals segments the split's depth images
+        in process (depth_proposals.proposals_for_split) and labels those
 
 proposals.json is a list of CNOS-shaped records {scene_id, image_id, segmentation (COCO RLE), time}; category_id, score and bbox, if
 present, are ignored."""
@@ -107,7 +108,11 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         sp.add_argument("--weights", default=None, help="DINOv2 checkpoint file or directory; default $FOUNDPOSE_DINOV2_WEIGHTS, then the torch hub "
                         "cache; without one the run fails (no random-weight fallback)")
         if name == "run":
-            sp.add_argument("--proposals", required=True, help="the segmenter's proposals: a JSON list of {scene_id, image_id, segmentation, time}")
+            src = sp.add_mutually_exclusive_group(required=True)
+            src.add_argument("--proposals", help="the segmenter's proposals: a JSON list of {scene_id, image_id, segmentation, time}")
+            src.add_argument("--proposals-from-depth", nargs="?", const="", default=None, metavar="OPTS_JSON",
+                             help="segment the split's depth images instead (depth_proposals, DESIGN.md section 28); the optional file "
+                             "holds {'depth_proposal_opts': {...}}")
             sp.add_argument("--dataset-dir", required=True, help="BOP split directory (<datasets>/<dataset>/<split>)")
             sp.add_argument("--output", required=True, help="the detections file to write; detector-decisions.json goes beside it")
     args = ap.parse_args(argv)
@@ -116,8 +121,12 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
     if args.command == "onboard":
         print("\n".join(onboard(opts, args.output_path, extractor)))
         return
-    with open(args.proposals) as f:
-        proposals = json.load(f)
+    if args.proposals is not None:
+        with open(args.proposals) as f:
+            proposals = json.load(f)
+    else:
+        from . import depth_proposals
+        proposals = depth_proposals.proposals_for_split(args.dataset_dir, args.proposals_from_depth or None)
     # (the set holds its own copy of every table: the per-object ones are dropped as soon as it is built -- 6.7 GB of patch tables at 8 x 798
     #  templates of ViT-L -- and only while bank_set concatenates them does the device hold both)
     bs = detect_util.bank_set(load_banks(opts, args.output_path))

@@ -531,6 +531,131 @@ def gt_visibility(depth_test: torch.Tensor, depth_obj: torch.Tensor, inst, param
     return out, mask, mask_visib
 
 
+def _depth_checked(name: str, rc: int) -> None:
+    if rc == 1:   # FP_ERR_INVALID: the one validation is the C entry's
+        raise ValueError(_lib.lib().fp_last_error().decode())
+    if rc != 0:
+        raise _lib.FoundPoseNativeError(f"{name} failed (code {rc}): {_lib.lib().fp_last_error().decode()}")
+
+
+def _depth_stack(name: str, t: torch.Tensor, dtype) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name} must be a tensor on the device (there is no CPU path)")
+    if t.dim() != 3 or t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype} [N, H, W]")
+    return t.contiguous()
+
+
+def _depth_planes(planes: torch.Tensor, count: torch.Tensor, n: int):
+    if not (isinstance(planes, torch.Tensor) and planes.is_cuda and planes.dtype == torch.float64 and tuple(planes.shape) == (n, _lib.DEPTH_MAX_PLANES, 4)):
+        raise ValueError(f"planes must be float64 [{n}, {_lib.DEPTH_MAX_PLANES}, 4] on the device")
+    if not (isinstance(count, torch.Tensor) and count.is_cuda and count.dtype == torch.int32 and tuple(count.shape) == (n,)):
+        raise ValueError(f"the plane counts must be int32 [{n}] on the device")
+    return planes.contiguous(), count.contiguous()
+
+
+def depth_plane_fit(depth: torch.Tensor, cameras, frame_keys, prior_planes: torch.Tensor, num_prior: torch.Tensor, hypotheses: int = 256,
+                    stride: int = 4, plane_thresh_mm: float = 10.0, max_depth_mm: float = 0.0, min_plane_share: float = 0.05, seed: int = 0,
+                    want_counts: bool = False):
+    """One more supporting plane per frame (fp_depth_plane_fit): depth [N, H, W] fp32 mm on the device, cameras
+    [N, 4] and frame_keys [N] on the host, the frames' earlier planes [N, 4, 4] fp64 and their number int32 [N] on the device.
+    -> (plane fp64 [N, 4], info int32 [N, 8], the counts of all hypotheses int32 [N, hypotheses] or None).  A refused call raises
+    ValueError and writes nothing."""
+    import numpy as np
+    d = _depth_stack("depth_plane_fit: depth", depth, torch.float32)
+    n, h, w = d.shape
+    cam = np.ascontiguousarray(np.asarray(cameras, dtype=np.float64).reshape(-1, 4))
+    keys = np.ascontiguousarray(np.asarray(frame_keys, dtype=np.uint64).reshape(-1))
+    if cam.shape[0] != n or keys.shape[0] != n:
+        raise ValueError(f"depth_plane_fit: {n} frames, {cam.shape[0]} cameras, {keys.shape[0]} keys")
+    pp, npr = _depth_planes(prior_planes, num_prior, n)
+    plane = torch.empty(max(n, 1), 4, dtype=torch.float64, device=d.device)[:n]
+    info = torch.empty(max(n, 1), 8, dtype=torch.int32, device=d.device)[:n]
+    counts = torch.empty(max(n, 1), max(int(hypotheses), 1), dtype=torch.int32, device=d.device)[:n] if want_counts else None
+    nbytes = _lib.depth_plane_scratch_bytes(n, h * w, max(int(hypotheses), 0))
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=d.device)
+    rc = _lib.lib().fp_depth_plane_fit(ptr(d), n, h, w, cam.ctypes.data_as(_lib.vp), keys.ctypes.data_as(_lib.vp), ptr(pp), ptr(npr), int(hypotheses),
+                                       int(stride), float(plane_thresh_mm), float(max_depth_mm), float(min_plane_share), int(seed) & (2**64 - 1),
+                                       ptr(scratch), nbytes, ptr(plane), ptr(info), ptr(counts), stream())
+    _depth_checked("fp_depth_plane_fit", rc)
+    return plane, info, counts
+
+
+def depth_components(depth: torch.Tensor, cameras, slope_fx, planes: torch.Tensor, num_planes: torch.Tensor, max_depth_mm: float = 0.0,
+                     object_margin_mm: float = 15.0, connect_mm: float = 5.0) -> torch.Tensor:
+    """Foreground and connected components of one level (fp_depth_components): slope_fx [N] fp32 on the host = connect_slope / fx.
+    -> labels int32 [N, H, W], the smallest linear index of the pixel's component, -1 for background."""
+    import numpy as np
+    d = _depth_stack("depth_components: depth", depth, torch.float32)
+    n, h, w = d.shape
+    cam = np.ascontiguousarray(np.asarray(cameras, dtype=np.float64).reshape(-1, 4))
+    sl = np.ascontiguousarray(np.asarray(slope_fx, dtype=np.float32).reshape(-1))
+    if cam.shape[0] != n or sl.shape[0] != n:
+        raise ValueError(f"depth_components: {n} frames, {cam.shape[0]} cameras, {sl.shape[0]} slopes")
+    pl, npl = _depth_planes(planes, num_planes, n)
+    labels = torch.empty(max(n, 1), h, w, dtype=torch.int32, device=d.device)[:n]
+    nbytes = _lib.depth_components_scratch_bytes(n, h * w)
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=d.device)
+    rc = _lib.lib().fp_depth_components(ptr(d), n, h, w, cam.ctypes.data_as(_lib.vp), sl.ctypes.data_as(_lib.vp), ptr(pl), ptr(npl),
+                                        float(max_depth_mm), float(object_margin_mm), float(np.float32(connect_mm)), ptr(scratch), nbytes,
+                                        ptr(labels), stream())
+    _depth_checked("fp_depth_components", rc)
+    return labels
+
+
+def component_table(labels: torch.Tensor, min_pixels: int, max_area: int, max_proposals: int, level: int = 0,
+                    finer: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The kept components of a label map (fp_component_table): -> (table int32 [N, max_proposals, 7] = (label, area, x0, y0, x1, y1,
+    level) by rank, counts int32 [N, 4] = (components, within the area limits, kept, dropped as a finer level's), rank_map int32
+    [N, H, W]).  finer: int32 [F, N, max_proposals, 7], the tables of finer levels."""
+    lab = _depth_stack("component_table: labels", labels, torch.int32)
+    n, h, w = lab.shape
+    nf = 0
+    if finer is not None:
+        if not (finer.is_cuda and finer.dtype == torch.int32 and finer.dim() == 4 and tuple(finer.shape[1:]) == (n, int(max_proposals), 7)):
+            raise ValueError(f"component_table: finer must be int32 [F, {n}, {max_proposals}, 7] on the device")
+        finer, nf = finer.contiguous(), finer.shape[0]
+    p = max(int(max_proposals), 1)
+    table = torch.empty(max(n, 1), p, 7, dtype=torch.int32, device=lab.device)[:n]
+    counts = torch.empty(max(n, 1), 4, dtype=torch.int32, device=lab.device)[:n]
+    rank_map = torch.empty(max(n, 1), h, w, dtype=torch.int32, device=lab.device)[:n]
+    nbytes = _lib.component_table_scratch_bytes(n, h * w)
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=lab.device)
+    rc = _lib.lib().fp_component_table(ptr(lab), n, h, w, int(min_pixels), int(max_area), int(max_proposals), int(level), ptr(finer), nf,
+                                       ptr(scratch), nbytes, ptr(table), ptr(counts), ptr(rank_map), stream())
+    _depth_checked("fp_component_table", rc)
+    return table, counts, rank_map
+
+
+def component_runs(rank_maps: torch.Tensor, num_kept: torch.Tensor, max_proposals: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """COCO's uncompressed run lengths of every kept component of a stack of rank maps (fp_component_runs marks the run boundaries;
+    sorting them and taking differences is plumbing): rank_maps int32 [M, H, W], num_kept int32 [M] on the device -> (runs int32
+    [total], run_off int32 [M * max_proposals + 1]): the list of rank r of map m is runs[run_off[g] : run_off[g + 1]], g = m *
+    max_proposals + r (empty beyond num_kept[m]).  Reads the event count back (one synchronisation)."""
+    maps = _depth_stack("component_runs: rank_maps", rank_maps, torch.int32)
+    m, h, w = maps.shape
+    if not (isinstance(num_kept, torch.Tensor) and num_kept.is_cuda and num_kept.dtype == torch.int32 and tuple(num_kept.shape) == (m,)):
+        raise ValueError(f"component_runs: num_kept must be int32 [{m}] on the device")
+    kept = num_kept.contiguous()
+    count = torch.empty(1, dtype=torch.int32, device=maps.device)
+    rc = _lib.lib().fp_component_runs(ptr(maps), m, h, w, ptr(kept), int(max_proposals), 0, None, ptr(count), stream())
+    _depth_checked("fp_component_runs", rc)
+    total = int(count.item())
+    groups = m * int(max_proposals)
+    if total == 0:
+        return torch.zeros(0, dtype=torch.int32, device=maps.device), torch.zeros(groups + 1, dtype=torch.int32, device=maps.device)
+    events = torch.empty(total, dtype=torch.int64, device=maps.device)
+    rc = _lib.lib().fp_component_runs(ptr(maps), m, h, w, ptr(kept), int(max_proposals), total, ptr(events), ptr(count), stream())
+    _depth_checked("fp_component_runs", rc)
+    events = torch.sort(events).values
+    group, pos = events >> 32, events & 0xffffffff
+    prev = torch.zeros_like(pos)
+    prev[1:] = torch.where(group[1:] == group[:-1], pos[:-1], torch.zeros_like(pos[:-1]))
+    run_off = torch.zeros(groups + 1, dtype=torch.int64, device=maps.device)
+    run_off[1:] = torch.cumsum(torch.bincount(group, minlength=groups), 0)
+    return (pos - prev).to(torch.int32), run_off.to(torch.int32)
+
+
 def texture_mips(rgb: torch.Tensor) -> torch.Tensor:
     """The mip pyramid of a texture (fp_texture_mips): rgb uint8 [H, W, 3] on the device -> int32 [total] holding packed RGBA8
     texels (view as uint32), the levels back to back in the layout of _lib.texture_levels(W, H)."""

@@ -991,6 +991,92 @@ int fp_gt_visibility(const float* depth_test, int num_test, int height, int widt
                      int render_width, const int32_t* inst, const double* params, int num_inst, void* scratch, size_t scratch_bytes,
                      int32_t* out, uint8_t* mask, uint8_t* mask_visib, fp_stream_t stream);
 
+/* ---- mask proposals from depth: plane removal and connected components (tests/depth_proposals_ref.py restates
+ *      it) ----
+ * Four entry points, called in this order per batch of num_frames frames of one size.  Shared conventions:
+ *   depth   fp32 [num_frames, height, width] on the device, mm, 0 = no measurement.  A pixel is VALID when depth > 0 and
+ *           (max_depth_mm == 0 or depth <= max_depth_mm, compared in fp64).  Its point is ((u - cx) / fx z, (v - cy) / fy z, z) with
+ *           integer pixel centres, in fp64, every operation rounded on its own; the height over a plane (n, d) is ((n0 x + n1 y) +
+ *           n2 z) + d.
+ *   cameras fp64 [num_frames, 4] (fx, fy, cx, cy): a HOST array, validated (fx, fy > 0, everything finite), then copied into scratch on
+ *           `stream`; the call waits for that copy, as fp_gt_visibility does.
+ *   planes  fp64 [num_frames, FP_DEPTH_MAX_PLANES, 4] rows (n0, n1, n2, d) on the device, with an int32 [num_frames] count beside it.
+ * height * width <= 2^31 - 1 and num_frames <= FP_DEPTH_MAX_FRAMES.  Integer results (labels, counts, tables, events) and the planes
+ * (fp64 sums in a fixed order, no float atomics) are bit-identical across runs and batch compositions: a frame gives the same result
+ * alone and inside a batch.  Every byte of every output is defined by the call.  A NULL pointer (unless stated), a size or option
+ * outside its range, a bad camera or too little scratch: FP_ERR_INVALID, nothing written.  (Added without a change of FP_ABI_VERSION:
+ * no existing entry point changed.)
+ *
+ * fp_depth_plane_fit: one more plane per frame.  frame_keys: HOST uint64 [num_frames].  prior_planes / num_prior: the frame's earlier
+ * planes; num_prior[f] = k in [0, FP_DEPTH_MAX_PLANES) makes this plane k of the frame, any other value skips the frame (info[6] = -1,
+ * zeros elsewhere).  A valid pixel is ELIGIBLE when it is not within plane_thresh_mm (|height| <= threshold) of a prior plane.
+ * Hypothesis h in [0, hypotheses) draws three distinct eligible pixels (linear index y * width + x below height * width) with the keyed
+ * sampler of fp_pnp_ransac_keyed (pair key frame_key * 8 + k, at most 65 attempts per index; a draw that gives up is a dead hypothesis);
+ * n = (X1 - X0) x (X2 - X0), dead when |n|^2 <= 1e-12 |X1 - X0|^2 |X2 - X0|^2 or the normalisation fails; d = -n . X0, both negated
+ * when d < 0.  Its count: the eligible pixels with y % stride == 0 and x % stride == 0 and |height| <= plane_thresh_mm (0 when dead).
+ * The winner is the first hypothesis of the highest count; it is refitted twice by least squares over ALL eligible pixels within the
+ * threshold of the current plane (centroid, then the 3 x 3 scatter about it; per-workgroup partials of FP_DEPTH_PLANE_CHUNK pixels
+ * folded in ascending order; the normal is the eigenvector of the smallest eigenvalue by cyclic Jacobi, re-oriented to d >= 0; a refit
+ * with fewer than 3 pixels keeps the plane).  The support is the number of eligible pixels within the threshold of the final plane;
+ * the plane is accepted when the winner is alive, support >= 3 and (double)support >= min_plane_share * (double)valid.
+ *   plane_out  fp64 [num_frames, 4]   (n, d), zeros when the winner is dead or the frame is skipped
+ *   info       int32 [num_frames, 8]  winner (-1: skipped), its sub-grid count, support, eligible pixels, valid pixels, accepted,
+ *                                     plane index k (-1: skipped), 0
+ *   hyp_counts int32 [num_frames, hypotheses] or NULL: the counts of all hypotheses
+ * hypotheses in [1, FP_DEPTH_MAX_HYPOTHESES], stride in [1, 64], plane_thresh_mm > 0, max_depth_mm >= 0, min_plane_share in [0, 1].
+ * scratch: FP_DEPTH_PLANE_SCRATCH_BYTES(num_frames, height * width, hypotheses).
+ *
+ * fp_depth_components: foreground and components of one level.  planes / num_planes: the frame's accepted planes (num_planes is
+ * clamped to [0, FP_DEPTH_MAX_PLANES]).  A valid pixel is FOREGROUND when height > object_margin_mm over every one of them.  Two
+ * 4-neighbours are connected when both are foreground and |za - zb| <= connect_mm + slope_fx[f] * min(za, zb) in fp32, each operation
+ * rounded on its own (slope_fx: HOST fp32 [num_frames], connect_slope / fx, finite and >= 0).  labels int32 [num_frames, height,
+ * width]: the smallest linear index y * width + x of the pixel's component, -1 for background.
+ * scratch: FP_DEPTH_COMPONENTS_SCRATCH_BYTES(num_frames, height * width).
+ *
+ * fp_component_table: a level's components -> the kept ones.  A component is a candidate when min_pixels <= area <= max_area and no row
+ * of the frame in `finer` (int32 [num_finer, num_frames, max_proposals, 7], tables this entry wrote for finer levels; NULL with
+ * num_finer = 0) has its (label, area).  Candidates are ranked by area descending, then label ascending; at most max_proposals are kept.
+ *   table    int32 [num_frames, max_proposals, 7]  (label, area, x0, y0, x1, y1, level) per rank (the box inclusive); unused rows
+ *                                                  (-1, 0, 0, 0, 0, 0, 0)
+ *   counts   int32 [num_frames, 4]                 components, those within the area limits, kept, dropped as a finer level's
+ *   rank_map int32 [num_frames, height, width]     the rank of the pixel's component, -1: none
+ * min_pixels >= 1, max_area >= min_pixels, max_proposals in [1, FP_DEPTH_MAX_PROPOSALS], level and num_finer in [0, 2].
+ * scratch: FP_COMPONENT_TABLE_SCRATCH_BYTES(num_frames, height * width).
+ *
+ * fp_component_runs: the run-length events of num_maps rank maps (any stack of fp_component_table's, e.g. frames x levels).  In the
+ * column-major scan of map m (position p = x * height + y) rank r(p) differs from r(p - 1) exactly where a run of r(p) starts and a
+ * run of r(p - 1) ends; every rank below num_kept[m] (clamped to [0, max_proposals]; ranks at or above it count as -1) also gets the
+ * terminal position height * width once.  Each event is the int64 ((m * max_proposals + rank) << 32) | position.  Sorted ascending, the
+ * positions of one (m, rank), differenced from 0, are COCO's uncompressed counts: runs alternate 0 / 1 from a run of 0 that may be
+ * empty, continue across column ends and add up to height * width.
+ *   num_events int32 [1]         the number of events, whatever the capacity
+ *   events     int64 [capacity]  the events in no particular order, the rest filled with 0x7f7f7f7f7f7f7f7f (sorts last); may be NULL
+ *                                with capacity 0 (a counting call)
+ * num_maps <= 65535 and num_maps * (height * width + 1 + max_proposals) <= 2^30; capacity >= 0. */
+#define FP_DEPTH_MAX_FRAMES 4096
+#define FP_DEPTH_MAX_PLANES 4
+#define FP_DEPTH_MAX_HYPOTHESES 4096
+#define FP_DEPTH_MAX_PROPOSALS 1024
+#define FP_DEPTH_PLANE_CHUNK 4096
+#define FP_DEPTH_PLANE_SCRATCH_BYTES(num_frames, pixels, hypotheses)                                                        \
+  (256 * (size_t)(num_frames) + 16 * (((size_t)(num_frames) * (size_t)(pixels) + 15) / 16) +                                \
+   8 * (((size_t)(num_frames) * (size_t)(hypotheses) + 1) / 2) +                                                            \
+   64 * (size_t)(num_frames) * (((size_t)(pixels) + FP_DEPTH_PLANE_CHUNK - 1) / FP_DEPTH_PLANE_CHUNK))
+#define FP_DEPTH_COMPONENTS_SCRATCH_BYTES(num_frames, pixels) (64 * (size_t)(num_frames) + 4 * (size_t)(num_frames) * (size_t)(pixels))
+#define FP_COMPONENT_TABLE_SCRATCH_BYTES(num_frames, pixels) (16 * (size_t)(num_frames) + 28 * (size_t)(num_frames) * (size_t)(pixels))
+int fp_depth_plane_fit(const float* depth, int num_frames, int height, int width, const double* cameras, const uint64_t* frame_keys,
+                       const double* prior_planes, const int32_t* num_prior, int hypotheses, int stride, double plane_thresh_mm,
+                       double max_depth_mm, double min_plane_share, uint64_t seed, void* scratch, size_t scratch_bytes,
+                       double* plane_out, int32_t* info, int32_t* hyp_counts, fp_stream_t stream);
+int fp_depth_components(const float* depth, int num_frames, int height, int width, const double* cameras, const float* slope_fx,
+                        const double* planes, const int32_t* num_planes, double max_depth_mm, double object_margin_mm, float connect_mm,
+                        void* scratch, size_t scratch_bytes, int32_t* labels, fp_stream_t stream);
+int fp_component_table(const int32_t* labels, int num_frames, int height, int width, int min_pixels, int max_area, int max_proposals,
+                       int level, const int32_t* finer, int num_finer, void* scratch, size_t scratch_bytes, int32_t* table,
+                       int32_t* counts, int32_t* rank_map, fp_stream_t stream);
+int fp_component_runs(const int32_t* rank_map, int num_maps, int height, int width, const int32_t* num_kept, int max_proposals,
+                      int64_t capacity, int64_t* events, int32_t* num_events, fp_stream_t stream);
+
 /* ---- featuremetric refinement of the best coarse pose (tests/featuremetric_ref.py restates it) ----
  * Levenberg-Marquardt on the 6-DoF pose of each of num_det detections, aligning a template's per-point features with the
  * query's projected patch-feature map.  Device arrays:
