@@ -18,6 +18,7 @@ test_targets_bop24.json) name images only, and every detection of every object g
 """
 
 import argparse
+import functools
 import json
 import math
 import os
@@ -442,215 +443,7 @@ def _record_poses(evaluator: eval_util.PoseEvaluator, opts: InferOpts, object_li
     flush()
 
 
-def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBasedObjectRepre, frames: Iterable[Dict[str, Any]],
-                 detections: Dict[Any, Any], extractor=None, num_target_insts: Optional[Dict[Tuple[int, int], int]] = None,
-                 precision: str = "bf16", seed: int = 0, weights: Optional[str] = None,
-                 eval_model: Optional[eval_util.EvalModel] = None, renderer=None, output_dir: Optional[str] = None,
-                 frame_poses: Optional[Dict[Tuple[int, int], List[Tuple[int, np.ndarray]]]] = None) -> eval_util.PoseEvaluator:
-    """One object over a stream of frames (the body of infer.py's per-object loop).  A frame is
-    {"scene_id", "im_id", "image": HWC uint8 or float [0,1] (numpy or tensor), "camera": PinholePlaneCameraModel (c2w)} and, for the
-    depth-reading options (the final pose types of DEPTH_POSE_TYPES, pnp_type "kabsch_depth", coarse_select_type "depth_verify"), "depth":
-    float32 mm [H, W] (numpy or tensor, 0 = no measurement).
-    eval_model (eval_util.load_eval_model): instances whose annotation carries a ground-truth `pose` (model -> world) are
-    evaluated against it (PoseEvaluator.update_batch, one launch per frame, inlier radius opts.pnp_inlier_thresh as in
-    infer.py:831); without it, or for annotations without a pose, the driver records what it always has.
-    renderer (a HipRasterizer holding this object's mesh under `object_lid`) together with opts.vis_results: one picture per estimated
-    pose is written to vis_util.tile_path(output_dir, ...) and its share of the time recorded as times["vis"]; frame_poses, when
-    given, collects (object_lid, T_m2c in the frame's own camera) per (scene_id, im_id) for the frame summaries.  Without a renderer
-    nothing of this runs, whatever vis_results says."""
-    vis = renderer is not None and bool(opts.vis_results)
-    if vis:   # refused before any device work
-        vis_util.check_opts(opts)
-        if output_dir is None:
-            raise ValueError("pictures need an output_dir")
-    refine, check_max_queries = _check_driver_opts(opts)
-    use_depth = opts.final_pose_type in DEPTH_POSE_TYPES
-    depth_pnp = opts.pnp_type in DEPTH_PNP_TYPES
-    verify = opts.coarse_select_type in DEPTH_SELECT_TYPES
-    mask_verify = opts.coarse_select_type in MASK_SELECT_TYPES
-    if extractor is None:  # infer.py:125-128; the checkpoint: weights=, $FOUNDPOSE_DINOV2_WEIGHTS or the torch hub cache, else this raises
-        extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
-    bank = DeviceBank([repre])
-    eng = fe.FoundPoseEngine(extractor, bank, opts.grid_cell_size, opts.match_top_n_templates, opts.match_top_k_buddies, tie_order="torch")
-    eng.record_stage_times = True
-    evaluator = eval_util.PoseEvaluator()
-    vertices = repre.vertices.cpu().numpy()
-    vis_templates = repre.templates.cuda() if vis else None
-    tau = depth_refine_tau(opts, repre) if use_depth else None
-    pnp_tau = depth_pnp_tau(opts, repre) if depth_pnp else None
-    verify_tau = depth_verify_tau(opts, repre) if verify else None
-
-    for frame in frames:
-        scene_id, im_id, cam = frame["scene_id"], frame["im_id"], frame["camera"]
-        kept = select_instances(opts, object_lid, frame, detections, num_target_insts, eval_model, evaluator.detection_times)
-        if not kept:
-            continue
-        if use_depth or depth_pnp or verify:
-            _check_frame_depth(frame, _depth_reason(opts))
-        t0 = time.perf_counter()
-        img = _to_device_image(frame["image"])
-        masks = torch.from_numpy(np.stack([i["input_mask_modal"] for _, i in kept]).astype(np.uint8)).cuda()
-        boxes = [i["input_box_amodal"].tolist() for _, i in kept]
-        if opts.crop:
-            crops, crop_masks, cams = crop_util.crop_detections(img, masks, boxes, cam, tuple(opts.crop_size), opts.crop_rel_pad)
-        else:
-            # crop=False (infer.py:355-357, 411-416): the whole image and the modal mask of every instance go to the extractor unchanged, the
-            # original camera stays the camera the poses are solved in.  The image must tile into patches -- the backbone's patch embedding
-            # asserts it in the reference as well (every instance then shares one feature map; it is computed per instance here, like there).
-            ps = extractor.patch_size
-            if img.shape[0] % ps or img.shape[1] % ps:
-                raise AssertionError(f"Input image height {img.shape[0]} / width {img.shape[1]} is not a multiple of patch size {ps} (crop=False)")
-            check_max_queries((cam.width, cam.height))
-            crops = img.permute(2, 0, 1)[None].expand(len(kept), -1, -1, -1).contiguous()
-            crop_masks, cams = masks, [cam] * len(kept)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        res = eng.infer_batch(crops, crop_masks, [0] * len(kept), keep_feature_map=refine or vis)
-        torch.cuda.synchronize()
-        t2 = time.perf_counter()
-        depth = None
-        if depth_pnp:   # one stack per frame, shared with the depth refiners below (the upload is part of pose_coarse)
-            depth = _frame_depth(frame, _depth_reason(opts))
-            poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
-                                            opts.pnp_refine_lm, seed=seed, frame_cameras=[cam] * len(kept), depth=depth[None],
-                                            image_index=[0] * len(kept), depth_inlier_thresh_mm=pnp_tau)
-        else:
-            poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
-                                            opts.pnp_refine_lm, seed=seed)
-        checked = None
-        if verify:   # every hypothesis against the frame's depth (the stack of kabsch_depth when that built one); part of pose_coarse
-            if depth is None:
-                depth = _frame_depth(frame, _depth_reason(opts))
-            checked = pnp_util.verify_poses_depth(poses, bank, [0] * len(kept), cams, [cam] * len(kept), depth[None], [0] * len(kept), verify_tau,
-                                                  max_points=opts.depth_verify_max_points)
-        elif mask_verify:   # ... or against its detection's mask in the frame's image; part of pose_coarse
-            checked = pnp_util.verify_poses_mask(poses, bank, [0] * len(kept), cams, [cam] * len(kept), masks,
-                                                 max_points=opts.mask_verify_max_points, grid=opts.mask_verify_grid)
-        torch.cuda.synchronize()
-        t3 = time.perf_counter()
-        best = pnp_util.select_best_coarse(poses) if checked is None else pnp_util.select_best_verified(poses, checked)
-        found, cid = best["found"].cpu().tolist(), best["corresp_id"].cpu().tolist()
-        Rb, tb = best["R"].cpu().numpy(), best["t"].cpu().numpy()
-        t4 = time.perf_counter()
-        t5 = None
-        if refine or use_depth:   # infer.py:619: the refined pose of the best coarse pose is the final pose
-            if use_depth and depth is None:   # (the upload is part of pose_refine)
-                depth = _frame_depth(frame)
-            Rb, tb = _refine_final(opts, res, best, bank, [0] * len(kept), [cam] * len(kept), cams, (crops.shape[-1], crops.shape[-2]),
-                                   depth if use_depth else None, [0] * len(kept), [tau] * len(kept))
-            t5 = time.perf_counter()
-        n = len(kept)
-        times = _stage_times(eng, n, t0, t1, t2, t3, t4, t5)
-        if vis:   # compositing on the device, one copy of the batch's tiles to pinned memory, PNG encoding on the host
-            tv = time.perf_counter()
-            to_T = lambda R, t: np.block([[np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3, 1)], [np.array([[0.0, 0.0, 0.0, 1.0]])]])
-            coarse = [to_T(best["R"][b].cpu().numpy(), best["t"][b].cpu().numpy()) if found[b] else None for b in range(n)] if t5 is not None else [None] * n
-            final = [to_T(Rb[b], tb[b]) if found[b] else None for b in range(n)]
-            gt_pose = [getattr(inst.get("gt_anno"), "pose", None) for _, inst in kept]
-            gt = [None if p is None else np.linalg.inv(cams[b].T_world_from_eye) @ to_T(p.R, p.t) for b, p in enumerate(gt_pose)]
-            tiles, vis_records = vis_util.vis_inference_results_batch(
-                crops, crop_masks, cams, res, found, cid, coarse, final, repre, renderer, object_lid, extractor=extractor,
-                poses_gt=gt if any(g is not None for g in gt) else None, draw_coarse=t5 is not None, vis_corresp_top_n=opts.vis_corresp_top_n,
-                vis_feat_map=opts.vis_feat_map, vis_for_paper=opts.vis_for_paper, templates=vis_templates)
-            host = vis_util.tiles_to_host(tiles)
-            for b, (inst_j, _) in enumerate(kept):
-                if found[b]:
-                    vis_util.write_png(vis_util.tile_path(output_dir, scene_id, im_id, object_lid, inst_j, 0), host[b])
-                    for note in vis_records[b]["notes"]:
-                        print(f"vis: scene {scene_id} image {im_id} object {object_lid} instance {inst_j}: {note}")
-            times["vis"] = (time.perf_counter() - tv) / n
-        records = []
-        for b, (inst_j, inst) in enumerate(kept):
-            if not found[b]:
-                continue
-            if vis and frame_poses is not None:
-                T_m2c = np.eye(4)
-                T_m2c[:3, :3], T_m2c[:3, 3] = Rb[b], tb[b]
-                frame_poses.setdefault((scene_id, im_id), []).append((object_lid, np.linalg.inv(cam.T_world_from_eye) @ (cams[b].T_world_from_eye @ T_m2c)))
-            records.append((b, scene_id, im_id, inst_j, inst, cam, cams[b], cid[b], Rb[b], tb[b]))
-        _record_poses(evaluator, opts, object_lid, repre, vertices, eval_model, res, records, times)
-    return evaluator
-
-
-def _select_frame_poses(opts: InferOpts, repres: Dict[int, repre_util.FeatureBasedObjectRepre], lids: Sequence[int], csv_path: str) -> List[str]:
-    """frame_select_type "pose_nms" (DESIGN.md section 20), after the per-object estimated-poses.json files and the csv of every pose are
-    written: the poses of each frame compared with each other (pose_nms.suppress_duplicates, samples from the repres' vertices), the csv
-    written again with the kept rows only -- the stage's wall time, divided equally over the images that have rows, added to their `time`
-    -- and every row's decision written to pose-nms.json beside it.  -> the paths written besides the csv."""
-    _check_driver_opts(opts)
-    rows = eval_bop19.load_results_csv(csv_path)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    samples = pose_nms.samples_from_vertices({lid: repres[lid].vertices for lid in lids}, opts.pose_nms_max_points)
-    result = pose_nms.suppress_duplicates(rows, samples, opts.pose_nms_thresh, opts.pose_nms_grid, opts.pose_nms_cross_object)
-    torch.cuda.synchronize()
-    images = {(r["scene_id"], r["im_id"]) for r in rows}
-    share = (time.perf_counter() - t0) / max(len(images), 1)
-    pose_nms.write_results_csv(csv_path, [dict(r, time=r["time"] + share) for i, r in enumerate(rows) if result["keep"][i]])
-    path = os.path.join(os.path.dirname(csv_path), "pose-nms.json")
-    with open(path, "w") as f:
-        json.dump(pose_nms.decision_records(rows, result), f, indent=1)
-    return [path]
-
-
-def infer(opts: InferOpts, frames_by_object, detections, repres: Dict[int, repre_util.FeatureBasedObjectRepre], output_dir: str, extractor=None,
-          precision: str = "bf16", num_target_insts: Optional[Dict[int, Dict[Tuple[int, int], int]]] = None, weights: Optional[str] = None,
-          eval_models: Optional[Dict[int, eval_util.EvalModel]] = None, renderer=None) -> List[str]:
-    """All objects: `frames_by_object(lid)` yields the frames that show object `lid`; one estimated-poses.json per object
-    under <output_dir>/<lid>/ (infer.py:813-816), then the BOP19 csv.
-    num_target_insts: {object lid: {(scene_id, im_id): inst_count}} from test_targets_bop19.json -- the number of poses to
-    estimate per (image, object) is num_preds_factor x inst_count (infer.py:308-346); frames without an entry are skipped.
-    eval_models: {object lid: eval_util.EvalModel} -- evaluate the hypotheses of frames whose annotations carry a pose.
-    renderer: a HipRasterizer holding the mesh of every object under its lid -- with opts.vis_results, one picture per estimated pose
-    (<output_dir>/<lid>/<scene>_<im>_<lid>_<inst>_0.png) and, after all objects, one summary per frame (<output_dir>/vis/<scene>_<im>.png)
-    with every final pose in the frame's own camera.  Without it no picture is made and nothing else changes.
-    opts.task "detection" (DESIGN.md section 21): num_target_insts only names the target images -- a collection of (scene_id, im_id), or
-    the dict above with its counts and object ids unread (detection_targets) -- and in each of them every detection of every object with
-    score >= detection_min_score gets a pose, at most detection_max_per_object per object; `frames_by_object(lid)` then yields every
-    target image."""
-    lids = list(opts.object_lids) if opts.object_lids is not None else sorted(repres)
-    if opts.task == "detection":
-        num_target_insts = detection_targets(num_target_insts, lids)
-    if renderer is not None and not opts.vis_results:
-        print("vis_results is false in the options: no pictures are written")
-        renderer = None
-    if renderer is not None:
-        vis_util.check_opts(opts)
-    frame_poses: Dict[Tuple[int, int], List[Tuple[int, np.ndarray]]] = {}
-    if extractor is None:
-        extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
-    paths = []
-    for lid in lids:
-        ev = infer_object(opts, lid, repres[lid], frames_by_object(lid), detections, extractor,
-                          num_target_insts=None if num_target_insts is None else num_target_insts.get(lid, {}),
-                          eval_model=None if eval_models is None else eval_models.get(lid), renderer=renderer, output_dir=output_dir,
-                          frame_poses=frame_poses if renderer is not None else None)
-        if opts.save_estimates:
-            p = os.path.join(output_dir, str(lid), "estimated-poses.json")
-            ev.save_results_json(p)
-            paths.append(p)
-    if opts.save_estimates:
-        paths.append(eval_util.prepare_bop_submission(output_dir, opts.object_dataset, lids))
-        if opts.frame_select_type == "pose_nms":
-            paths.extend(_select_frame_poses(opts, repres, lids, paths[-1]))
-    if renderer is not None and frame_poses:   # the frames are read again rather than kept: one image in memory at a time
-        done = set()
-        for lid in lids:
-            for frame in frames_by_object(lid):
-                key = (frame["scene_id"], frame["im_id"])
-                if key in done or key not in frame_poses:
-                    continue
-                done.add(key)
-                pic, _, notes = vis_util.vis_frame_summary(frame["image"], frame["camera"], [(o, T, None) for o, T in frame_poses[key]], renderer)
-                for note in notes:
-                    print(f"vis: scene {key[0]} image {key[1]}: {note}")
-                p = vis_util.summary_path(output_dir, *key)
-                vis_util.write_png(p, vis_util.tiles_to_host(pic))
-                paths.append(p)
-    return paths
-
-
-# ---------------------------------------------------------------------------------------------------- frame-major, cross-object batches
+# ---------------------------------------------------------------------------------------------------- one flush for both drivers
 class QueuedDetection(NamedTuple):
     """One kept instance waiting for its batch."""
     frame_no: int                   # running number of its frame in the stream
@@ -697,6 +490,283 @@ def plan_flush(queue: Sequence[QueuedDetection]) -> FlushPlan:
     return FlushPlan(order, [queue[i].obj for i in order], [slot[queue[i].frame_no] for i in order], [queue[i].group_index for i in order], frames)
 
 
+def single_group_plan(n: int) -> FlushPlan:
+    """plan_flush of the per-object driver's queue -- the n kept instances of ONE (frame 0, object 0) group, in order -- without the sort."""
+    return FlushPlan(list(range(n)), [0] * n, [0] * n, list(range(n)), [0])
+
+
+def _extractor_on_device(opts: InferOpts, extractor, precision: str, weights: Optional[str]):
+    if extractor is None:  # infer.py:125-128; the checkpoint: weights=, $FOUNDPOSE_DINOV2_WEIGHTS or the torch hub cache, else this raises
+        extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
+    return extractor
+
+
+class _Pipeline:
+    """What a driver call sets up once and every flush reads, over `repres` in bank order (models, vertices and the taus: one per object).
+    Everything a driver refuses is refused here (_check_driver_opts), before any device work."""
+
+    def __init__(self, opts: InferOpts, extractor, repres: Sequence[repre_util.FeatureBasedObjectRepre],
+                 models: Sequence[Optional[eval_util.EvalModel]], seed: int, precision: str = "bf16", weights: Optional[str] = None) -> None:
+        self.opts, self.models, self.seed = opts, list(models), seed
+        self.refine, self.check_max_queries = _check_driver_opts(opts)
+        self.use_depth = opts.final_pose_type in DEPTH_POSE_TYPES        # the final pose is refined against depth,
+        self.depth_pnp = opts.pnp_type in DEPTH_PNP_TYPES                # the coarse poses are solved on it,
+        self.verify = opts.coarse_select_type in DEPTH_SELECT_TYPES      # the coarse hypotheses are checked against it
+        self.mask_verify = opts.coarse_select_type in MASK_SELECT_TYPES  # ... or against the detection's mask
+        self.extractor = _extractor_on_device(opts, extractor, precision, weights)
+        self.bank = DeviceBank(list(repres))
+        self.eng = fe.FoundPoseEngine(self.extractor, self.bank, opts.grid_cell_size, opts.match_top_n_templates, opts.match_top_k_buddies, tie_order="torch")
+        self.eng.record_stage_times = True
+        self.vertices = [r.vertices.cpu().numpy() for r in repres]
+        self.taus = [depth_refine_tau(opts, r) for r in repres] if self.use_depth else None
+        self.pnp_taus = [depth_pnp_tau(opts, r) for r in repres] if self.depth_pnp else None
+        self.verify_taus = [depth_verify_tau(opts, r) for r in repres] if self.verify else None
+
+
+def _check_frame_work(pipe: _Pipeline, frame: Dict[str, Any]) -> None:
+    """A frame whose first kept detection is being queued: it must carry the depth the options read and, with crop=False (infer.py:355-357,
+    411-416: the whole image and the modal mask of every instance go to the extractor unchanged), tile into patches -- the backbone's patch
+    embedding asserts it in the reference as well -- and have no more grid points than max_num_queries."""
+    opts = pipe.opts
+    if pipe.use_depth or pipe.depth_pnp or pipe.verify:
+        _check_frame_depth(frame, _depth_reason(opts))
+    if not opts.crop:
+        h, w = np.shape(frame["image"])[:2]
+        ps = pipe.extractor.patch_size
+        if h % ps or w % ps:
+            raise AssertionError(f"Input image height {h} / width {w} is not a multiple of patch size {ps} (crop=False)")
+        pipe.check_max_queries((frame["camera"].width, frame["camera"].height))
+
+
+class _Flush(NamedTuple):
+    """What one flush leaves behind; every per-detection field is in batch order (FlushPlan.order)."""
+    rows: List[QueuedDetection]
+    crops: torch.Tensor
+    crop_masks: torch.Tensor
+    cams: List[Any]                  # the cameras the poses are solved in: the crop cameras, or the frames' own with crop=False
+    res: Any                         # the engine's MatchResult
+    best: Dict[str, torch.Tensor]    # the coarse selection (on the device)
+    found: List[bool]
+    cid: List[int]                   # id of the best correspondence set
+    R: np.ndarray                    # the final poses, in `cams`
+    t: np.ndarray
+    refined: bool                    # a refinement ran: R, t are not best's, and times has "pose_refine"
+    times: Dict[str, float]
+
+
+def _run_flush(pipe: _Pipeline, queue: Sequence[QueuedDetection], plan: FlushPlan, *, device_masks: bool = False,
+               keep_feature_map: bool = False) -> _Flush:
+    """One batch through upload, crop cameras and warp, the engine, the coarse poses, their verification, the selection and the refinement:
+    the body of both drivers.  device_masks: the queue's masks are uint8 tensors on the device already; keep_feature_map: the engine keeps
+    the projected feature map even where no refinement needs it (for the pictures)."""
+    opts, eng, bank = pipe.opts, pipe.eng, pipe.bank
+    t0 = time.perf_counter()
+    dets = [queue[i] for i in plan.order]
+    by_no = {e.frame_no: e.frame for e in queue}
+    images = torch.stack([_to_device_image(by_no[f]["image"]) for f in plan.frames])
+    if device_masks:   # views into their frames' stacks: nothing is uploaded
+        masks = torch.stack([e.inst["input_mask_modal"] for e in dets])
+    else:
+        masks = torch.from_numpy(np.stack([e.inst["input_mask_modal"] for e in dets]).astype(np.uint8)).cuda()
+    src_cams = [e.frame["camera"] for e in dets]
+    if opts.crop:
+        cams = []
+        for e in dets:
+            b = e.inst["input_box_amodal"].tolist()
+            box = crop_util.calc_crop_box(crop_util.AlignedBox2f(b[0], b[1], b[2], b[3]), make_square=True)
+            cams.append(crop_util.construct_crop_camera(box, e.frame["camera"], tuple(opts.crop_size), opts.crop_rel_pad))
+        crops, crop_masks = crop_util.warp_crops(images, masks, src_cams, cams, plan.image_index)
+    else:   # crop=False: every detection gets its frame's whole image and solves in the frame's own camera (_check_frame_work)
+        crops = images[torch.as_tensor(plan.image_index, device=images.device)].permute(0, 3, 1, 2).contiguous()
+        crop_masks, cams = masks, src_cams
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    res = eng.infer_batch(crops, crop_masks, plan.det_obj, keep_feature_map=pipe.refine or keep_feature_map)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    n_slots = int(res.counts.shape[1])
+    keys = [[g * n_slots + j for j in range(n_slots)] for g in plan.pair_group_index]
+
+    @functools.lru_cache(maxsize=None)   # made once, on first need: the upload is part of the stage that asks first
+    def depth():   # the depth images of the flush, stacked like its RGB images and read through plan.image_index
+        return torch.stack([_frame_depth(by_no[f], _depth_reason(opts)) for f in plan.frames])
+    depth_kw = {}
+    if pipe.depth_pnp:
+        depth_kw = dict(frame_cameras=src_cams, depth=depth(), image_index=plan.image_index, depth_inlier_thresh_mm=[pipe.pnp_taus[o] for o in plan.det_obj])
+    poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
+                                    opts.pnp_refine_lm, seed=pipe.seed, pair_keys=keys, **depth_kw)
+    checked = None
+    if pipe.verify:   # every hypothesis against its frame's depth; part of pose_coarse
+        checked = pnp_util.verify_poses_depth(poses, bank, plan.det_obj, cams, src_cams, depth(), plan.image_index,
+                                              [pipe.verify_taus[o] for o in plan.det_obj], max_points=opts.depth_verify_max_points)
+    elif pipe.mask_verify:   # ... or against its detection's mask in its frame's image; part of pose_coarse
+        checked = pnp_util.verify_poses_mask(poses, bank, plan.det_obj, cams, src_cams, masks,
+                                             max_points=opts.mask_verify_max_points, grid=opts.mask_verify_grid)
+    torch.cuda.synchronize()
+    t3 = time.perf_counter()
+    best = pnp_util.select_best_coarse(poses) if checked is None else pnp_util.select_best_verified(poses, checked)
+    found, cid = best["found"].cpu().tolist(), best["corresp_id"].cpu().tolist()
+    Rb, tb = best["R"].cpu().numpy(), best["t"].cpu().numpy()
+    t4 = time.perf_counter()
+    t5 = None
+    if pipe.refine or pipe.use_depth:   # infer.py:619: the refined pose of the best coarse pose is the final pose
+        Rb, tb = _refine_final(opts, res, best, bank, plan.det_obj, src_cams, cams, (crops.shape[-1], crops.shape[-2]),
+                               depth() if pipe.use_depth else None, plan.image_index,
+                               [pipe.taus[o] for o in plan.det_obj] if pipe.use_depth else None)
+        t5 = time.perf_counter()
+    return _Flush(dets, crops, crop_masks, cams, res, best, found, cid, Rb, tb, t5 is not None, _stage_times(eng, len(dets), t0, t1, t2, t3, t4, t5))
+
+
+def infer_object(opts: InferOpts, object_lid: int, repre: repre_util.FeatureBasedObjectRepre, frames: Iterable[Dict[str, Any]],
+                 detections: Dict[Any, Any], extractor=None, num_target_insts: Optional[Dict[Tuple[int, int], int]] = None,
+                 precision: str = "bf16", seed: int = 0, weights: Optional[str] = None,
+                 eval_model: Optional[eval_util.EvalModel] = None, renderer=None, output_dir: Optional[str] = None,
+                 frame_poses: Optional[Dict[Tuple[int, int], List[Tuple[int, np.ndarray]]]] = None) -> eval_util.PoseEvaluator:
+    """One object over a stream of frames (the body of infer.py's per-object loop).  A frame is
+    {"scene_id", "im_id", "image": HWC uint8 or float [0,1] (numpy or tensor), "camera": PinholePlaneCameraModel (c2w)} and, for the
+    depth-reading options (the final pose types of DEPTH_POSE_TYPES, pnp_type "kabsch_depth", coarse_select_type "depth_verify"), "depth":
+    float32 mm [H, W] (numpy or tensor, 0 = no measurement).
+    eval_model (eval_util.load_eval_model): instances whose annotation carries a ground-truth `pose` (model -> world) are
+    evaluated against it (PoseEvaluator.update_batch, one launch per frame, inlier radius opts.pnp_inlier_thresh as in
+    infer.py:831); without it, or for annotations without a pose, the driver records what it always has.
+    renderer (a HipRasterizer holding this object's mesh under `object_lid`) together with opts.vis_results: one picture per estimated
+    pose is written to vis_util.tile_path(output_dir, ...) and its share of the time recorded as times["vis"]; frame_poses, when
+    given, collects (object_lid, T_m2c in the frame's own camera) per (scene_id, im_id) for the frame summaries.  Without a renderer
+    nothing of this runs, whatever vis_results says."""
+    vis = renderer is not None and bool(opts.vis_results)
+    if vis:   # refused before any device work
+        vis_util.check_opts(opts)
+        if output_dir is None:
+            raise ValueError("pictures need an output_dir")
+    pipe = _Pipeline(opts, extractor, [repre], [eval_model], seed, precision, weights)
+    evaluator = eval_util.PoseEvaluator()
+    vis_templates = repre.templates.cuda() if vis else None
+
+    for frame in frames:
+        scene_id, im_id, cam = frame["scene_id"], frame["im_id"], frame["camera"]
+        kept = select_instances(opts, object_lid, frame, detections, num_target_insts, eval_model, evaluator.detection_times)
+        if not kept:
+            continue
+        _check_frame_work(pipe, frame)
+        n = len(kept)
+        queue = [QueuedDetection(0, (cam.width, cam.height), 0, i, inst_j, inst, frame) for i, (inst_j, inst) in enumerate(kept)]
+        fl = _run_flush(pipe, queue, single_group_plan(n), keep_feature_map=vis)
+        cams, res, best, found, cid, Rb, tb, times = fl.cams, fl.res, fl.best, fl.found, fl.cid, fl.R, fl.t, fl.times
+        if vis:   # compositing on the device, one copy of the batch's tiles to pinned memory, PNG encoding on the host
+            tv = time.perf_counter()
+            to_T = lambda R, t: np.block([[np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3, 1)], [np.array([[0.0, 0.0, 0.0, 1.0]])]])
+            coarse = [to_T(best["R"][b].cpu().numpy(), best["t"][b].cpu().numpy()) if found[b] else None for b in range(n)] if fl.refined else [None] * n
+            final = [to_T(Rb[b], tb[b]) if found[b] else None for b in range(n)]
+            gt_pose = [getattr(inst.get("gt_anno"), "pose", None) for _, inst in kept]
+            gt = [None if p is None else np.linalg.inv(cams[b].T_world_from_eye) @ to_T(p.R, p.t) for b, p in enumerate(gt_pose)]
+            tiles, vis_records = vis_util.vis_inference_results_batch(
+                fl.crops, fl.crop_masks, cams, res, found, cid, coarse, final, repre, renderer, object_lid, extractor=pipe.extractor,
+                poses_gt=gt if any(g is not None for g in gt) else None, draw_coarse=fl.refined, vis_corresp_top_n=opts.vis_corresp_top_n,
+                vis_feat_map=opts.vis_feat_map, vis_for_paper=opts.vis_for_paper, templates=vis_templates)
+            host = vis_util.tiles_to_host(tiles)
+            for b, (inst_j, _) in enumerate(kept):
+                if found[b]:
+                    vis_util.write_png(vis_util.tile_path(output_dir, scene_id, im_id, object_lid, inst_j, 0), host[b])
+                    for note in vis_records[b]["notes"]:
+                        print(f"vis: scene {scene_id} image {im_id} object {object_lid} instance {inst_j}: {note}")
+            times["vis"] = (time.perf_counter() - tv) / n
+        records = []
+        for b, (inst_j, inst) in enumerate(kept):
+            if not found[b]:
+                continue
+            if vis and frame_poses is not None:
+                T_m2c = np.eye(4)
+                T_m2c[:3, :3], T_m2c[:3, 3] = Rb[b], tb[b]
+                frame_poses.setdefault((scene_id, im_id), []).append((object_lid, np.linalg.inv(cam.T_world_from_eye) @ (cams[b].T_world_from_eye @ T_m2c)))
+            records.append((b, scene_id, im_id, inst_j, inst, cam, cams[b], cid[b], Rb[b], tb[b]))
+        _record_poses(evaluator, opts, object_lid, repre, pipe.vertices[0], eval_model, res, records, times)
+    return evaluator
+
+
+def _select_frame_poses(opts: InferOpts, repres: Dict[int, repre_util.FeatureBasedObjectRepre], lids: Sequence[int], csv_path: str) -> List[str]:
+    """frame_select_type "pose_nms" (DESIGN.md section 20), after the per-object estimated-poses.json files and the csv of every pose are
+    written: the poses of each frame compared with each other (pose_nms.suppress_duplicates, samples from the repres' vertices), the csv
+    written again with the kept rows only -- the stage's wall time, divided equally over the images that have rows, added to their `time`
+    -- and every row's decision written to pose-nms.json beside it.  -> the paths written besides the csv."""
+    _check_driver_opts(opts)
+    rows = eval_bop19.load_results_csv(csv_path)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    samples = pose_nms.samples_from_vertices({lid: repres[lid].vertices for lid in lids}, opts.pose_nms_max_points)
+    result = pose_nms.suppress_duplicates(rows, samples, opts.pose_nms_thresh, opts.pose_nms_grid, opts.pose_nms_cross_object)
+    torch.cuda.synchronize()
+    images = {(r["scene_id"], r["im_id"]) for r in rows}
+    share = (time.perf_counter() - t0) / max(len(images), 1)
+    pose_nms.write_results_csv(csv_path, [dict(r, time=r["time"] + share) for i, r in enumerate(rows) if result["keep"][i]])
+    path = os.path.join(os.path.dirname(csv_path), "pose-nms.json")
+    with open(path, "w") as f:
+        json.dump(pose_nms.decision_records(rows, result), f, indent=1)
+    return [path]
+
+
+def _write_results(opts: InferOpts, lids: Sequence[int], evaluators: Sequence[eval_util.PoseEvaluator],
+                   repres: Dict[int, repre_util.FeatureBasedObjectRepre], output_dir: str) -> List[str]:
+    """The files of a run, once every pose is estimated (save_estimates): <output_dir>/<lid>/estimated-poses.json per object (infer.py:813-816),
+    the BOP csv, and what frame_select_type "pose_nms" does with it.  -> their paths, in this order."""
+    paths = []
+    if opts.save_estimates:
+        for lid, ev in zip(lids, evaluators):
+            paths.append(os.path.join(output_dir, str(lid), "estimated-poses.json"))
+            ev.save_results_json(paths[-1])
+        paths.append(eval_util.prepare_bop_submission(output_dir, opts.object_dataset, lids))
+        if opts.frame_select_type == "pose_nms":
+            paths.extend(_select_frame_poses(opts, repres, lids, paths[-1]))
+    return paths
+
+
+def infer(opts: InferOpts, frames_by_object, detections, repres: Dict[int, repre_util.FeatureBasedObjectRepre], output_dir: str, extractor=None,
+          precision: str = "bf16", num_target_insts: Optional[Dict[int, Dict[Tuple[int, int], int]]] = None, weights: Optional[str] = None,
+          eval_models: Optional[Dict[int, eval_util.EvalModel]] = None, renderer=None) -> List[str]:
+    """All objects: `frames_by_object(lid)` yields the frames that show object `lid`; one estimated-poses.json per object
+    under <output_dir>/<lid>/ (infer.py:813-816), then the BOP19 csv.
+    num_target_insts: {object lid: {(scene_id, im_id): inst_count}} from test_targets_bop19.json -- the number of poses to
+    estimate per (image, object) is num_preds_factor x inst_count (infer.py:308-346); frames without an entry are skipped.
+    eval_models: {object lid: eval_util.EvalModel} -- evaluate the hypotheses of frames whose annotations carry a pose.
+    renderer: a HipRasterizer holding the mesh of every object under its lid -- with opts.vis_results, one picture per estimated pose
+    (<output_dir>/<lid>/<scene>_<im>_<lid>_<inst>_0.png) and, after all objects, one summary per frame (<output_dir>/vis/<scene>_<im>.png)
+    with every final pose in the frame's own camera.  Without it no picture is made and nothing else changes.
+    opts.task "detection" (DESIGN.md section 21): num_target_insts only names the target images -- a collection of (scene_id, im_id), or
+    the dict above with its counts and object ids unread (detection_targets) -- and in each of them every detection of every object with
+    score >= detection_min_score gets a pose, at most detection_max_per_object per object; `frames_by_object(lid)` then yields every
+    target image."""
+    lids = list(opts.object_lids) if opts.object_lids is not None else sorted(repres)
+    if opts.task == "detection":
+        num_target_insts = detection_targets(num_target_insts, lids)
+    if renderer is not None and not opts.vis_results:
+        print("vis_results is false in the options: no pictures are written")
+        renderer = None
+    if renderer is not None:
+        vis_util.check_opts(opts)
+    frame_poses: Dict[Tuple[int, int], List[Tuple[int, np.ndarray]]] = {}
+    extractor = _extractor_on_device(opts, extractor, precision, weights)   # one for all objects
+    evaluators = [infer_object(opts, lid, repres[lid], frames_by_object(lid), detections, extractor,
+                               num_target_insts=None if num_target_insts is None else num_target_insts.get(lid, {}),
+                               eval_model=None if eval_models is None else eval_models.get(lid), renderer=renderer, output_dir=output_dir,
+                               frame_poses=frame_poses if renderer is not None else None) for lid in lids]
+    paths = _write_results(opts, lids, evaluators, repres, output_dir)
+    if renderer is not None and frame_poses:   # the frames are read again rather than kept: one image in memory at a time
+        done = set()
+        for lid in lids:
+            for frame in frames_by_object(lid):
+                key = (frame["scene_id"], frame["im_id"])
+                if key in done or key not in frame_poses:
+                    continue
+                done.add(key)
+                pic, _, notes = vis_util.vis_frame_summary(frame["image"], frame["camera"], [(o, T, None) for o, T in frame_poses[key]], renderer)
+                for note in notes:
+                    print(f"vis: scene {key[0]} image {key[1]}: {note}")
+                p = vis_util.summary_path(output_dir, *key)
+                vis_util.write_png(p, vis_util.tiles_to_host(pic))
+                paths.append(p)
+    return paths
+
+
+# ---------------------------------------------------------------------------------------------------- frame-major, cross-object batches
 def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections, repres: Dict[int, repre_util.FeatureBasedObjectRepre],
                   output_dir: str, *, batch_detections: int = 32, extractor=None, precision: str = "bf16",
                   num_target_insts: Optional[Dict[int, Dict[Tuple[int, int], int]]] = None, weights: Optional[str] = None,
@@ -705,9 +775,10 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
     """infer() for a whole split in ONE pass over its frames: the kept instances of every (frame, object) are queued and go through the
     crop producer, the engine and the PnP tail `batch_detections` at a time, across frames and objects (one DeviceBank of all objects).
     `frames` yields each image once (load_bop_frames_all); `gt_annos` may hold annotations of several objects.  The poses, scores and
-    files are those of infer(): the instances are selected by the same function, the crops are the same bits, the engine's results do not
-    depend on the batch, and RANSAC's sampler is keyed by the pair's index in its own (frame, object) group -- what the per-object driver's
-    launch gives it -- instead of its place in the batch.  Pictures are not made here: infer() / infer_object() write them.
+    files are those of infer(): the instances are selected by the same function and go through the same flush (_run_flush), in which a
+    detection's crop and the engine's results do not depend on the batch, and RANSAC's sampler is keyed by the pair's index in its own
+    (frame, object) group -- the per-object driver's whole batch -- instead of its place in the batch.  Pictures are not made here: infer() /
+    infer_object() write them.
     device_masks: the detections' run lengths are decoded, opened and cropped on the device (select_instances_device)
     instead of on the host; the masks are the same bits and so is everything written."""
     if batch_detections < 1:
@@ -715,25 +786,12 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
     if renderer is not None:
         raise NotImplementedError("result pictures are written by the per-object driver (infer.infer / infer.infer_object, batch_detections=0): "
                                   "the batched driver makes none")
-    refine, check_max_queries = _check_driver_opts(opts)
-    use_depth = opts.final_pose_type in DEPTH_POSE_TYPES
-    depth_pnp = opts.pnp_type in DEPTH_PNP_TYPES
-    verify = opts.coarse_select_type in DEPTH_SELECT_TYPES
-    mask_verify = opts.coarse_select_type in MASK_SELECT_TYPES
     lids = sorted(opts.object_lids) if opts.object_lids is not None else sorted(repres)
+    models = [None if eval_models is None else eval_models.get(l) for l in lids]
+    pipe = _Pipeline(opts, extractor, [repres[l] for l in lids], models, seed, precision, weights)
     if opts.task == "detection":   # the targets name images only (infer()'s note): every target image under every object
         num_target_insts = detection_targets(num_target_insts, lids)
-    if extractor is None:
-        extractor = feature_util.make_feature_extractor(opts.extractor_name, precision=precision, weights=weights).to("cuda")
-    bank = DeviceBank([repres[l] for l in lids])
-    eng = fe.FoundPoseEngine(extractor, bank, opts.grid_cell_size, opts.match_top_n_templates, opts.match_top_k_buddies, tie_order="torch")
-    eng.record_stage_times = True
     evaluators = [eval_util.PoseEvaluator() for _ in lids]
-    vertices = [repres[l].vertices.cpu().numpy() for l in lids]
-    models = [None if eval_models is None else eval_models.get(l) for l in lids]
-    taus = [depth_refine_tau(opts, repres[l]) for l in lids] if use_depth else None
-    pnp_taus = [depth_pnp_tau(opts, repres[l]) for l in lids] if depth_pnp else None
-    verify_taus = [depth_verify_tau(opts, repres[l]) for l in lids] if verify else None
 
     def entries():
         for frame_no, frame in enumerate(frames):
@@ -748,96 +806,20 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
                 else:
                     kept = select_instances(opts, lid, frame, detections, None if num_target_insts is None else num_target_insts.get(lid, {}),
                                             models[o], evaluators[o].detection_times)
-                if kept and (use_depth or depth_pnp or verify):
-                    _check_frame_depth(frame, _depth_reason(opts))
-                if kept and not opts.crop and not checked:   # (as in infer_object: only a frame that has work is checked)
-                    h, w = frame["image"].shape[:2]
-                    ps = extractor.patch_size
-                    if h % ps or w % ps:
-                        raise AssertionError(f"Input image height {h} / width {w} is not a multiple of patch size {ps} (crop=False)")
-                    check_max_queries((cam.width, cam.height))
+                if kept and not checked:   # (only a frame that has work is checked)
+                    _check_frame_work(pipe, frame)
                     checked = True
                 for i, (inst_j, inst) in enumerate(kept):
                     yield QueuedDetection(frame_no, (cam.width, cam.height), o, i, inst_j, inst, frame)
 
     for queue in iter_batches(entries(), batch_detections):
-        t0 = time.perf_counter()
-        plan = plan_flush(queue)
-        dets = [queue[i] for i in plan.order]
-        n = len(dets)
-        by_no = {e.frame_no: e.frame for e in queue}
-        images = torch.stack([_to_device_image(by_no[f]["image"]) for f in plan.frames])
-        if device_masks and opts.use_detections:   # views into their frames' stacks: nothing is uploaded
-            masks = torch.stack([e.inst["input_mask_modal"] for e in dets])
-        else:
-            masks = torch.from_numpy(np.stack([e.inst["input_mask_modal"] for e in dets]).astype(np.uint8)).cuda()
-        src_cams = [e.frame["camera"] for e in dets]
-        if opts.crop:
-            cams = []
-            for e in dets:
-                b = e.inst["input_box_amodal"].tolist()
-                box = crop_util.calc_crop_box(crop_util.AlignedBox2f(b[0], b[1], b[2], b[3]), make_square=True)
-                cams.append(crop_util.construct_crop_camera(box, e.frame["camera"], tuple(opts.crop_size), opts.crop_rel_pad))
-            crops, crop_masks = crop_util.warp_crops(images, masks, src_cams, cams, plan.image_index)
-        else:   # crop=False: every detection gets its frame's whole image and solves in the frame's own camera (see infer_object)
-            crops = images[torch.as_tensor(plan.image_index, device=images.device)].permute(0, 3, 1, 2).contiguous()
-            crop_masks, cams = masks, src_cams
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        res = eng.infer_batch(crops, crop_masks, plan.det_obj, keep_feature_map=refine)
-        torch.cuda.synchronize()
-        t2 = time.perf_counter()
-        n_slots = int(res.counts.shape[1])
-        keys = [[g * n_slots + j for j in range(n_slots)] for g in plan.pair_group_index]
-        depth = None
-        if depth_pnp:   # the depth images of the flush, stacked once and shared with the depth refiners below (the upload is part of pose_coarse)
-            depth = torch.stack([_frame_depth(by_no[f], _depth_reason(opts)) for f in plan.frames])
-            poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
-                                            opts.pnp_refine_lm, seed=seed, pair_keys=keys, frame_cameras=src_cams, depth=depth,
-                                            image_index=plan.image_index, depth_inlier_thresh_mm=[pnp_taus[o] for o in plan.det_obj])
-        else:
-            poses = pnp_util.estimate_poses(res, cams, opts.pnp_type, opts.pnp_ransac_iter, opts.pnp_inlier_thresh, opts.pnp_required_ransac_conf,
-                                            opts.pnp_refine_lm, seed=seed, pair_keys=keys)
-        checked = None
-        if verify:   # every hypothesis against its frame's depth (the stack of kabsch_depth when that built one); part of pose_coarse
-            if depth is None:
-                depth = torch.stack([_frame_depth(by_no[f], _depth_reason(opts)) for f in plan.frames])
-            checked = pnp_util.verify_poses_depth(poses, bank, plan.det_obj, cams, src_cams, depth, plan.image_index,
-                                                  [verify_taus[o] for o in plan.det_obj], max_points=opts.depth_verify_max_points)
-        elif mask_verify:   # ... or against its detection's mask in its frame's image; part of pose_coarse
-            checked = pnp_util.verify_poses_mask(poses, bank, plan.det_obj, cams, src_cams, masks,
-                                                 max_points=opts.mask_verify_max_points, grid=opts.mask_verify_grid)
-        torch.cuda.synchronize()
-        t3 = time.perf_counter()
-        best = pnp_util.select_best_coarse(poses) if checked is None else pnp_util.select_best_verified(poses, checked)
-        found, cid = best["found"].cpu().tolist(), best["corresp_id"].cpu().tolist()
-        Rb, tb = best["R"].cpu().numpy(), best["t"].cpu().numpy()
-        t4 = time.perf_counter()
-        t5 = None
-        if refine or use_depth:
-            # the depth images of the flush, stacked like its RGB images and read through plan.image_index (the upload is part of pose_refine)
-            if use_depth and depth is None:
-                depth = torch.stack([_frame_depth(by_no[f]) for f in plan.frames])
-            Rb, tb = _refine_final(opts, res, best, bank, plan.det_obj, src_cams, cams, (crops.shape[-1], crops.shape[-2]),
-                                   depth if use_depth else None, plan.image_index,
-                                   [taus[o] for o in plan.det_obj] if use_depth else None)
-            t5 = time.perf_counter()
-        times = _stage_times(eng, n, t0, t1, t2, t3, t4, t5)
+        fl = _run_flush(pipe, queue, plan_flush(queue), device_masks=device_masks and opts.use_detections)
         for o, lid in enumerate(lids):   # rows are grouped by object, and within an object in frame, then instance order
-            records = [(b, e.frame["scene_id"], e.frame["im_id"], e.inst_id, e.inst, e.frame["camera"], cams[b], cid[b], Rb[b], tb[b])
-                       for b, e in enumerate(dets) if e.obj == o and found[b]]
+            records = [(b, e.frame["scene_id"], e.frame["im_id"], e.inst_id, e.inst, e.frame["camera"], fl.cams[b], fl.cid[b], fl.R[b], fl.t[b])
+                       for b, e in enumerate(fl.rows) if e.obj == o and fl.found[b]]
             if records:
-                _record_poses(evaluators[o], opts, lid, repres[lid], vertices[o], models[o], res, records, times)
-    paths = []
-    if opts.save_estimates:
-        for o, lid in enumerate(lids):
-            p = os.path.join(output_dir, str(lid), "estimated-poses.json")
-            evaluators[o].save_results_json(p)
-            paths.append(p)
-        paths.append(eval_util.prepare_bop_submission(output_dir, opts.object_dataset, lids))
-        if opts.frame_select_type == "pose_nms":
-            paths.extend(_select_frame_poses(opts, repres, lids, paths[-1]))
-    return paths
+                _record_poses(evaluators[o], opts, lid, repres[lid], pipe.vertices[o], models[o], fl.res, records, fl.times)
+    return _write_results(opts, lids, evaluators, repres, output_dir)
 
 
 # ---------------------------------------------------------------------------------------------------- BOP split on disk

@@ -62,16 +62,7 @@ def solve_pnp_ransac_batch(coord_2d: torch.Tensor, coord_3d: torch.Tensor, count
     mask = torch.zeros(P, K, dtype=torch.uint8, device=dev)
     rp = torch.zeros(P, 12, dtype=torch.float64, device=dev) if return_ransac_pose else None
     lm_iters = 20 + (20 if pnp_refine_lm else 0)
-    keys = None
-    if pair_keys is not None:
-        if isinstance(pair_keys, torch.Tensor):
-            if pair_keys.dtype != torch.int64:
-                raise ValueError(f"pair_keys must be int64, got {pair_keys.dtype}")
-        else:
-            pair_keys = torch.tensor(pair_keys, dtype=torch.int64)
-        if tuple(pair_keys.shape) != (B, n):
-            raise ValueError(f"pair_keys must have shape [{B}, {n}], got {list(pair_keys.shape)}")
-        keys = pair_keys.contiguous() if pair_keys.is_cuda else upload_async(pair_keys, dev)   # (the int64 bits are the uint64 keys)
+    keys = _pair_keys_tensor(pair_keys, B, n, dev)
     entry, key_arg = ("fp_pnp_ransac", ()) if keys is None else ("fp_pnp_ransac_keyed", (ptr(keys),))
     call(entry, ptr(c2), ptr(c3), ptr(cnt), ptr(cam), *key_arg, P, n, K, int(pnp_ransac_iter), float(pnp_inlier_thresh),
          float(pnp_required_ransac_conf), lm_iters, int(min_corresp), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(success), ptr(R), ptr(t), ptr(ninl), ptr(mask), ptr(rp), stream())
@@ -198,6 +189,14 @@ def estimate_poses(res: MatchResult, cameras: Sequence[Any], pnp_type: str = "op
                                   pnp_required_ransac_conf, pnp_refine_lm, seed, pair_keys=pair_keys)
 
 
+def _selection(poses: Dict[str, torch.Tensor], found: torch.Tensor, first: torch.Tensor, quality: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The selectors' result: the pose of slot first[b] of every detection b."""
+    idx = first[:, None, None]
+    return {"found": found, "corresp_id": first,
+            "R": poses["R"].gather(1, idx[..., None].expand(-1, 1, 3, 3))[:, 0], "t": poses["t"].gather(1, idx.expand(-1, 1, 3))[:, 0],
+            "quality": quality}
+
+
 def select_best_coarse(poses: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """infer.py:582-602: among a detection's successful coarse poses the one of the highest quality, the first on ties.
     -> found [B] bool, corresp_id [B], R [B, 3, 3], t [B, 3], quality [B]."""
@@ -205,14 +204,49 @@ def select_best_coarse(poses: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor
     best_q, _ = q.max(dim=1)
     n = q.shape[1]
     first = torch.where(q == best_q[:, None], torch.arange(n, device=q.device)[None, :], torch.full_like(q, n, dtype=torch.int64)).min(dim=1).values
-    first = first.clamp_max(n - 1)
-    idx = first[:, None, None]
-    return {"found": best_q >= 0, "corresp_id": first,
-            "R": poses["R"].gather(1, idx[..., None].expand(-1, 1, 3, 3))[:, 0], "t": poses["t"].gather(1, idx.expand(-1, 1, 3))[:, 0],
-            "quality": best_q}
+    return _selection(poses, best_q >= 0, first.clamp_max(n - 1), best_q)
 
 
 VERIFY_MIN_GRID, VERIFY_MAX_GRID = 8, 128   # the z-buffer's side in cells (csrc/verify.hip: G * G words of LDS)
+
+
+def _check_verify_grid(grid) -> None:
+    if isinstance(grid, bool) or not isinstance(grid, int) or not VERIFY_MIN_GRID <= grid <= VERIFY_MAX_GRID:
+        raise ValueError(f"grid must be an integer in [{VERIFY_MIN_GRID}, {VERIFY_MAX_GRID}], got {grid!r}")
+
+
+def _verify_sample(bank, max_points: int, det_obj: Sequence[int], solve_cameras: Sequence[Any], frame_cameras: Sequence[Any], what: str):
+    """What both verifiers place at a pose: -> (bank.verify_points(max_points), the detections' object indices checked against it, the
+    rotations solve camera -> frame camera [B, 3, 3])."""
+    vp = bank.verify_points(max_points)
+    objs = [int(o) for o in det_obj]
+    for b, o in enumerate(objs):
+        if not 0 <= o < len(vp.ranges):
+            raise ValueError(f"detection {b}: object {o} outside the bank's [0, {len(vp.ranges)})")
+    return vp, objs, solve_to_frame_rotations(solve_cameras, frame_cameras, what)
+
+
+def _verify_results(B: int, n: int, num_counts: int, dev):
+    """-> (the kernels' zeroed outputs counts [P, num_counts], score [P], status [P], the verifiers' dict of them as [B, n, ...] views)."""
+    counts = torch.zeros(B * n, num_counts, dtype=torch.int32, device=dev)
+    score = torch.zeros(B * n, dtype=torch.float64, device=dev)
+    status = torch.zeros(B * n, dtype=torch.int32, device=dev)
+    return counts, score, status, {"counts": counts.reshape(B, n, num_counts), "score": score.reshape(B, n), "status": status.reshape(B, n)}
+
+
+def _verify_inputs(poses: Dict[str, torch.Tensor], frame_cameras: Sequence[Any], A: np.ndarray, vp, objs: List[int], more_reals: Sequence[torch.Tensor],
+                   ints: torch.Tensor):
+    """The verifiers' device inputs.  One byte buffer, one upload: the fp64 table [B, 17 + ...] = (the frame cameras' intrinsics 4, A 9, the
+    objects' sphere centres 3 and radii 1, then more_reals) followed by the int32 table `ints` [B, c], each read back as its own type.
+    -> (success int32, R f64, t f64, intrinsics, A, centres, radii -- contiguous --, the table's further columns, ints on the device)."""
+    B, dev = len(objs), poses["success"].device
+    reals = torch.cat([torch.tensor([_intrinsics(c) for c in frame_cameras], dtype=torch.float64).reshape(B, 4), torch.from_numpy(A.reshape(B, 9)),
+                       torch.from_numpy(vp.centers[objs].reshape(B, 3)), torch.from_numpy(vp.radii[objs].reshape(B, 1)), *more_reals], dim=1).contiguous()
+    raw = upload_async(torch.cat([reals.view(torch.uint8).reshape(-1), ints.view(torch.uint8).reshape(-1)]), dev)
+    split = reals.numel() * 8   # (the int32 part starts at a multiple of 8 bytes)
+    table, idev = raw[:split].view(torch.float64).reshape(reals.shape), raw[split:].view(torch.int32).reshape(ints.shape)
+    return (poses["success"].to(torch.int32).contiguous(), poses["R"].to(torch.float64).contiguous(), poses["t"].to(torch.float64).contiguous(),
+            table[:, :4].contiguous(), table[:, 4:13].contiguous(), table[:, 13:16].contiguous(), table[:, 16].contiguous(), table[:, 17:], idev)
 
 
 def verify_poses_depth(poses: Dict[str, torch.Tensor], bank, det_obj: Sequence[int], solve_cameras: Sequence[Any], frame_cameras: Sequence[Any],
@@ -235,8 +269,7 @@ def verify_poses_depth(poses: Dict[str, torch.Tensor], bank, det_obj: Sequence[i
         raise ValueError(f"{len(solve_cameras)} solve cameras, {len(frame_cameras)} frame cameras and {len(det_obj)} objects for {B} detections")
     if depth.dim() != 3 or depth.dtype != torch.float32:
         raise ValueError(f"depth must be a float32 stack [N, H, W], got {depth.dtype} {list(depth.shape)}")
-    if isinstance(grid, bool) or not isinstance(grid, int) or not VERIFY_MIN_GRID <= grid <= VERIFY_MAX_GRID:
-        raise ValueError(f"grid must be an integer in [{VERIFY_MIN_GRID}, {VERIFY_MAX_GRID}], got {grid!r}")
+    _check_verify_grid(grid)
     if isinstance(min_visible, bool) or not isinstance(min_visible, int) or min_visible < 1:
         raise ValueError(f"min_visible must be an integer >= 1, got {min_visible!r}")
     N, H, W = (int(s) for s in depth.shape)
@@ -251,35 +284,18 @@ def verify_poses_depth(poses: Dict[str, torch.Tensor], bank, det_obj: Sequence[i
     tau = np.full(B, thresh_mm, np.float64) if np.ndim(thresh_mm) == 0 else np.array(thresh_mm, np.float64).reshape(-1)
     if tau.shape != (B,) or not np.all(tau > 0) or not np.all(np.isfinite(tau)):
         raise ValueError(f"thresh_mm must be one finite number > 0 or {B} of them, got {thresh_mm!r}")
-    vp = bank.verify_points(max_points)
-    objs = [int(o) for o in det_obj]
-    for b, o in enumerate(objs):
-        if not 0 <= o < len(vp.ranges):
-            raise ValueError(f"detection {b}: object {o} outside the bank's [0, {len(vp.ranges)})")
-    A = solve_to_frame_rotations(solve_cameras, frame_cameras, "depth verification")
-    P = B * n
-    counts = torch.zeros(P, 6, dtype=torch.int32, device=dev)
-    score = torch.zeros(P, dtype=torch.float64, device=dev)
-    status = torch.zeros(P, dtype=torch.int32, device=dev)
-    if P == 0:   # nothing to launch
-        return {"counts": counts.reshape(B, n, 6), "score": score.reshape(B, n), "status": status.reshape(B, n)}
-    # one byte buffer, one upload: the fp64 table [B, 18] followed by the int32 table [B, 3] (image, begin, end), each read back as its own type
-    reals = torch.cat([torch.tensor([_intrinsics(c) for c in frame_cameras], dtype=torch.float64).reshape(B, 4), torch.from_numpy(A.reshape(B, 9)),
-                       torch.from_numpy(tau).reshape(B, 1), torch.from_numpy(vp.centers[objs].reshape(B, 3)),
-                       torch.from_numpy(vp.radii[objs].reshape(B, 1))], dim=1).contiguous()
-    ints = torch.tensor([[i, *vp.ranges[o]] for i, o in zip(ii, objs)], dtype=torch.int32).reshape(B, 3)
-    raw = upload_async(torch.cat([reals.view(torch.uint8).reshape(-1), ints.view(torch.uint8).reshape(-1)]), dev)
-    table = raw[:B * 18 * 8].view(torch.float64).reshape(B, 18)   # (the int32 part starts at a multiple of 8 bytes)
-    idev = raw[B * 18 * 8:].view(torch.int32).reshape(B, 3)
-    cam, Ad, taud = table[:, :4].contiguous(), table[:, 4:13].contiguous(), table[:, 13].contiguous()
-    cen, rad = table[:, 14:17].contiguous(), table[:, 17].contiguous()
-    iid, rng = idev[:, 0].contiguous(), idev[:, 1:3].contiguous()
-    ok = success.to(torch.int32).contiguous()
-    Rd, td = R.to(torch.float64).contiguous(), t.to(torch.float64).contiguous()
+    vp, objs, A = _verify_sample(bank, max_points, det_obj, solve_cameras, frame_cameras, "depth verification")
+    counts, score, status, out = _verify_results(B, n, 6, dev)
+    if B * n == 0:   # nothing to launch
+        return out
+    # the table's extra column: tau; the int32 table [B, 3]: (image, begin, end)
+    ok, Rd, td, cam, Ad, cen, rad, more, idev = _verify_inputs(poses, frame_cameras, A, vp, objs, [torch.from_numpy(tau).reshape(B, 1)],
+                                                               torch.tensor([[i, *vp.ranges[o]] for i, o in zip(ii, objs)], dtype=torch.int32).reshape(B, 3))
+    taud, iid, rng = more[:, 0].contiguous(), idev[:, 0].contiguous(), idev[:, 1:3].contiguous()
     dimg = depth.contiguous()
     call("fp_pose_verify_depth", ptr(ok), ptr(Rd), ptr(td), ptr(cam), ptr(Ad), ptr(iid), ptr(taud), ptr(rng), ptr(cen), ptr(rad), ptr(vp.points),
-         int(vp.points.shape[0]), ptr(dimg), N, H, W, P, n, grid, min_visible, ptr(counts), ptr(score), ptr(status), stream())
-    return {"counts": counts.reshape(B, n, 6), "score": score.reshape(B, n), "status": status.reshape(B, n)}
+         int(vp.points.shape[0]), ptr(dimg), N, H, W, B * n, n, grid, min_visible, ptr(counts), ptr(score), ptr(status), stream())
+    return out
 
 
 def verify_poses_mask(poses: Dict[str, torch.Tensor], bank, det_obj: Sequence[int], solve_cameras: Sequence[Any], frame_cameras: Sequence[Any],
@@ -294,8 +310,7 @@ def verify_poses_mask(poses: Dict[str, torch.Tensor], bank, det_obj: Sequence[in
     or the model's sphere reaches the camera).  B = 0 or n = 0 returns empty tensors without a launch.  Masks of another type or shape,
     lengths that do not match, a bad object index, grid, min_pixels or camera pair raise ValueError before anything is launched."""
     success, R, t = poses["success"], poses["R"], poses["t"]
-    if isinstance(grid, bool) or not isinstance(grid, int) or not VERIFY_MIN_GRID <= grid <= VERIFY_MAX_GRID:
-        raise ValueError(f"grid must be an integer in [{VERIFY_MIN_GRID}, {VERIFY_MAX_GRID}], got {grid!r}")
+    _check_verify_grid(grid)
     if isinstance(min_pixels, bool) or not isinstance(min_pixels, int) or min_pixels < 1:
         raise ValueError(f"min_pixels must be an integer >= 1, got {min_pixels!r}")
     if not isinstance(masks, torch.Tensor) or masks.dtype != torch.uint8 or masks.dim() != 3:
@@ -312,33 +327,18 @@ def verify_poses_mask(poses: Dict[str, torch.Tensor], bank, det_obj: Sequence[in
         raise ValueError(f"masks must be a uint8 tensor [B, H, W] on the device, got one on {masks.device}")
     require_cuda(success, R, t)
     dev = success.device
-    vp = bank.verify_points(max_points)
-    objs = [int(o) for o in det_obj]
-    for b, o in enumerate(objs):
-        if not 0 <= o < len(vp.ranges):
-            raise ValueError(f"detection {b}: object {o} outside the bank's [0, {len(vp.ranges)})")
-    A = solve_to_frame_rotations(solve_cameras, frame_cameras, "mask verification")
-    P = B * n
-    counts = torch.zeros(P, 4, dtype=torch.int32, device=dev)
-    score = torch.zeros(P, dtype=torch.float64, device=dev)
-    status = torch.zeros(P, dtype=torch.int32, device=dev)
-    if P == 0:   # nothing to launch
-        return {"counts": counts.reshape(B, n, 4), "score": score.reshape(B, n), "status": status.reshape(B, n)}
-    # one byte buffer, one upload: the fp64 table [B, 17] followed by the int32 table [B, 2] (begin, end), each read back as its own type
-    reals = torch.cat([torch.tensor([_intrinsics(c) for c in frame_cameras], dtype=torch.float64).reshape(B, 4), torch.from_numpy(A.reshape(B, 9)),
-                       torch.from_numpy(vp.centers[objs].reshape(B, 3)), torch.from_numpy(vp.radii[objs].reshape(B, 1))], dim=1).contiguous()
-    ints = torch.tensor([vp.ranges[o] for o in objs], dtype=torch.int32).reshape(B, 2)
-    raw = upload_async(torch.cat([reals.view(torch.uint8).reshape(-1), ints.view(torch.uint8).reshape(-1)]), dev)
-    table = raw[:B * 17 * 8].view(torch.float64).reshape(B, 17)   # (the int32 part starts at a multiple of 8 bytes)
-    rng = raw[B * 17 * 8:].view(torch.int32).reshape(B, 2)
-    cam, Ad, cen, rad = table[:, :4].contiguous(), table[:, 4:13].contiguous(), table[:, 13:16].contiguous(), table[:, 16].contiguous()
-    ok = success.to(torch.int32).contiguous()
-    Rd, td = R.to(torch.float64).contiguous(), t.to(torch.float64).contiguous()
+    vp, objs, A = _verify_sample(bank, max_points, det_obj, solve_cameras, frame_cameras, "mask verification")
+    counts, score, status, out = _verify_results(B, n, 4, dev)
+    if B * n == 0:   # nothing to launch
+        return out
+    # no extra column; the int32 table [B, 2]: (begin, end)
+    ok, Rd, td, cam, Ad, cen, rad, _, rng = _verify_inputs(poses, frame_cameras, A, vp, objs, [],
+                                                           torch.tensor([vp.ranges[o] for o in objs], dtype=torch.int32).reshape(B, 2))
     mk = masks.contiguous()
     area = mk.ne(0).flatten(1).sum(1, dtype=torch.int32)   # plumbing on the device, no synchronisation: the set pixels of each mask
     call("fp_pose_verify_mask", ptr(ok), ptr(Rd), ptr(td), ptr(cam), ptr(Ad), ptr(rng), ptr(cen), ptr(rad), ptr(vp.points), int(vp.points.shape[0]),
-         ptr(mk), ptr(area), H, W, P, n, grid, min_pixels, ptr(counts), ptr(score), ptr(status), stream())
-    return {"counts": counts.reshape(B, n, 4), "score": score.reshape(B, n), "status": status.reshape(B, n)}
+         ptr(mk), ptr(area), H, W, B * n, n, grid, min_pixels, ptr(counts), ptr(score), ptr(status), stream())
+    return out
 
 
 def select_best_verified(poses: Dict[str, torch.Tensor], verify: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -356,12 +356,9 @@ def select_best_verified(poses: Dict[str, torch.Tensor], verify: Dict[str, torch
     first = torch.where(cand, torch.arange(n, device=ok.device)[None, :], torch.full_like(cand, n, dtype=torch.int64)).min(dim=1).values
     found = first < n
     first = first.clamp_max(n - 1)
-    idx = first[:, None, None]
     pick = lambda v: v.gather(1, first[:, None])[:, 0]
-    return {"found": found, "corresp_id": first,
-            "R": poses["R"].gather(1, idx[..., None].expand(-1, 1, 3, 3))[:, 0], "t": poses["t"].gather(1, idx.expand(-1, 1, 3))[:, 0],
-            "quality": torch.where(found, pick(quality), torch.full_like(pick(quality), -1.0)),
-            "verify_score": torch.where(found, pick(verify["score"]), torch.zeros_like(pick(verify["score"])))}
+    return dict(_selection(poses, found, first, torch.where(found, pick(quality), torch.full_like(pick(quality), -1.0))),
+                verify_score=torch.where(found, pick(verify["score"]), torch.zeros_like(pick(verify["score"]))))
 
 
 def estimate_pose(corresp: Dict[str, Any], camera_c2w: Any, pnp_type: str, pnp_ransac_iter: int, pnp_inlier_thresh: float,

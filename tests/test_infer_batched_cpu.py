@@ -36,6 +36,13 @@ def test_plan_flush_orders_by_object_and_keeps_frame_and_group():
     assert empty.order == [] and empty.frames == []
 
 
+@pytest.mark.parametrize("n", [1, 3])
+def test_single_group_plan_is_plan_flush_of_one_frame_and_one_object(n):
+    """The per-object driver's plan: its queue is one (frame 0, object 0) group, and plan_flush of that queue is what it passes on."""
+    queue = [Q(0, BIG, 0, i, inst_id=5 + i) for i in range(n)]
+    assert infer.single_group_plan(n) == infer.plan_flush(queue)
+
+
 def test_iter_batches_flush_rule():
     assert _ids(infer.iter_batches(iter(STREAM), 4)) == [[0, 1, 2, 3], [4], [5, 6]]     # full batch straddling frames; size change; end of stream
     assert _ids(infer.iter_batches(iter(STREAM), 1)) == [[i] for i in range(7)]
