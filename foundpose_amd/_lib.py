@@ -120,6 +120,9 @@ _PROTOS = {
     "fp_depth_components": [vp, i32, i32, i32, vp, vp, vp, vp, f64, f64, f32, vp, C.c_size_t, vp, vp],
     "fp_component_table": [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, C.c_size_t, vp, vp, vp, vp],
     "fp_component_runs": [vp, i32, i32, i32, vp, i32, i64, vp, vp, vp],
+    "fp_tsdf_integrate": [vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, f64, vp, C.c_size_t, vp, vp, vp, vp, vp],
+    "fp_tsdf_count_triangles": [vp, vp, i32, i32, i32, i32, vp, vp],
+    "fp_tsdf_emit_triangles": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp],
     "fp_featuremetric_refine": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32,
                                 vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "fp_depth_refine": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
@@ -255,6 +258,14 @@ def depth_components_scratch_bytes(num_frames: int, pixels: int) -> int:
 def component_table_scratch_bytes(num_frames: int, pixels: int) -> int:
     """FP_COMPONENT_TABLE_SCRATCH_BYTES of include/foundpose_amd.h."""
     return 16 * num_frames + 28 * num_frames * pixels
+
+
+TSDF_MAX_DIM, TSDF_MAX_VOXELS, TSDF_MAX_FRAMES, TSDF_FRAME_DOUBLES = 512, 1 << 27, 4096, 16  # FP_TSDF_* of the header
+
+
+def tsdf_scratch_bytes(num_frames: int) -> int:
+    """FP_TSDF_SCRATCH_BYTES of include/foundpose_amd.h."""
+    return 8 * TSDF_FRAME_DOUBLES * num_frames
 
 
 REFINE_CHUNK, REFINE_RECORD, REFINE_STATE_BYTES = 32, 32, 512  # FP_REFINE_* of the header

@@ -1,6 +1,6 @@
 // C ABI of libfoundpose_amd.so (declared in include/foundpose_amd.h): argument checking, scratch carving
 // and kernel sequencing.  No device allocation, no global mutable state, no synchronisation except the table uploads of
-// fp_pose_errors, fp_vsd_counts, fp_gt_visibility, fp_depth_plane_fit and fp_depth_components (each waits for its own copy) and the range check read back by the three refinements (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine).
+// fp_pose_errors, fp_vsd_counts, fp_gt_visibility, fp_depth_plane_fit, fp_depth_components and fp_tsdf_integrate (each waits for its own copy) and the range check read back by the three refinements (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine).
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -1198,6 +1198,84 @@ int fp_gt_visibility(const float* depth_test, int num_test, int height, int widt
   a.num_inst = num_inst, a.height = height, a.width = width, a.render_h = render_height, a.render_w = render_width;
   a.out = out, a.mask = mask, a.mask_visib = mask_visib;
   return launch_gt_visibility(a, blocks, ST(stream));
+}
+
+// ------------------------------------------------------------------ TSDF fusion and surface extraction
+}  // extern "C"
+
+// the checks the three TSDF entries share: the box (origin, voxel size) and the dimensions
+static int tsdf_volume(const char* who, const double* box, int nx, int ny, int nz, int min_dim, TsdfVolume& vol) {
+  FP_REQUIRE(nx >= min_dim && ny >= min_dim && nz >= min_dim && nx <= FP_TSDF_MAX_DIM && ny <= FP_TSDF_MAX_DIM && nz <= FP_TSDF_MAX_DIM,
+             "%s: dimensions %d x %d x %d outside [%d, %d]", who, nx, ny, nz, min_dim, FP_TSDF_MAX_DIM);
+  FP_REQUIRE((long long)nx * ny * nz <= FP_TSDF_MAX_VOXELS, "%s: %d x %d x %d voxels exceed %lld", who, nx, ny, nz, (long long)FP_TSDF_MAX_VOXELS);
+  memset(&vol, 0, sizeof(vol));
+  vol.nx = nx, vol.ny = ny, vol.nz = nz;
+  if (box != nullptr) {
+    FP_REQUIRE(std::isfinite(box[0]) && std::isfinite(box[1]) && std::isfinite(box[2]) && std::isfinite(box[3]) && box[3] > 0,
+               "%s: the origin must be finite and the voxel size finite and > 0", who);
+    vol.ox = box[0], vol.oy = box[1], vol.oz = box[2], vol.h = box[3];
+  }
+  return FP_OK;
+}
+
+extern "C" {
+
+int fp_tsdf_integrate(const float* depth, const uint8_t* mask, const uint8_t* rgb, int num_frames, int height, int width,
+                      const double* frames, const double* box, int nx, int ny, int nz, double trunc_mm, void* scratch,
+                      size_t scratch_bytes, float* sdf_sum, int32_t* sdf_cnt, float* rgb_sum, int32_t* rgb_cnt, fp_stream_t stream) {
+  FP_REQUIRE(depth && mask && rgb && frames && box && scratch && sdf_sum && sdf_cnt && rgb_sum && rgb_cnt, "fp_tsdf_integrate: null pointer");
+  FP_REQUIRE(num_frames >= 1 && num_frames <= FP_TSDF_MAX_FRAMES, "fp_tsdf_integrate: num_frames %d outside [1, %d]", num_frames, FP_TSDF_MAX_FRAMES);
+  FP_REQUIRE(height >= 1 && width >= 1 && (long long)height * width <= 0x7fffffffll, "fp_tsdf_integrate: images of %d x %d pixels", width, height);
+  FP_REQUIRE(std::isfinite(trunc_mm) && trunc_mm > 0, "fp_tsdf_integrate: the truncation distance must be finite and > 0");
+  FP_REQUIRE(scratch_bytes >= FP_TSDF_SCRATCH_BYTES(num_frames), "fp_tsdf_integrate: scratch holds %zu bytes, %zu needed", scratch_bytes,
+             FP_TSDF_SCRATCH_BYTES(num_frames));
+  static_assert(sizeof(TsdfFrame) == 8 * FP_TSDF_FRAME_DOUBLES, "layout of FP_TSDF_SCRATCH_BYTES: a frame row is the device record");
+  TsdfIntegrateArgs a;
+  memset(&a, 0, sizeof(a));
+  TRY(tsdf_volume("fp_tsdf_integrate", box, nx, ny, nz, 1, a.vol));
+  for (int f = 0; f < num_frames; ++f) {
+    const double* q = frames + (size_t)FP_TSDF_FRAME_DOUBLES * f;
+    for (int c = 0; c < FP_TSDF_FRAME_DOUBLES; ++c)
+      FP_REQUIRE(std::isfinite(q[c]), "fp_tsdf_integrate: frame %d: entry %d of its camera and pose is not finite", f, c);
+    FP_REQUIRE(q[0] > 0 && q[1] > 0, "fp_tsdf_integrate: frame %d: fx and fy must be > 0", f);
+  }
+  // the caller's table is the device record as it stands; the call waits for the copy, so the caller may free it on return
+  HIP_TRY(hipMemcpyWithStream(scratch, frames, sizeof(TsdfFrame) * (size_t)num_frames, hipMemcpyHostToDevice, ST(stream)), "fp_tsdf_integrate: table upload");
+  a.depth = depth, a.mask = mask, a.rgb = rgb;
+  a.frames = reinterpret_cast<const TsdfFrame*>(scratch);
+  a.num_frames = num_frames, a.height = height, a.width = width;
+  a.tau = trunc_mm;
+  a.sdf_sum = sdf_sum, a.sdf_cnt = sdf_cnt, a.rgb_sum = rgb_sum, a.rgb_cnt = rgb_cnt;
+  return launch_tsdf_integrate(a, ST(stream));
+}
+
+int fp_tsdf_count_triangles(const float* sdf_sum, const int32_t* sdf_cnt, int nx, int ny, int nz, int min_count, int32_t* counts,
+                            fp_stream_t stream) {
+  FP_REQUIRE(sdf_sum && sdf_cnt && counts, "fp_tsdf_count_triangles: null pointer");
+  FP_REQUIRE(min_count >= 1, "fp_tsdf_count_triangles: min_count %d must be >= 1", min_count);
+  TsdfExtractArgs a;
+  memset(&a, 0, sizeof(a));
+  TRY(tsdf_volume("fp_tsdf_count_triangles", nullptr, nx, ny, nz, 2, a.vol));
+  a.sdf_sum = sdf_sum, a.sdf_cnt = sdf_cnt, a.min_count = min_count, a.counts = counts;
+  return launch_tsdf_extract(a, false, ST(stream));
+}
+
+int fp_tsdf_emit_triangles(const float* sdf_sum, const int32_t* sdf_cnt, const float* rgb_sum, const int32_t* rgb_cnt, const double* box,
+                           int nx, int ny, int nz, int min_count, const int64_t* offsets, int64_t num_triangles, int64_t* keys,
+                           float* positions, float* colors, fp_stream_t stream) {
+  FP_REQUIRE(sdf_sum && sdf_cnt && rgb_sum && rgb_cnt && box && offsets, "fp_tsdf_emit_triangles: null pointer");
+  FP_REQUIRE(min_count >= 1, "fp_tsdf_emit_triangles: min_count %d must be >= 1", min_count);
+  FP_REQUIRE(num_triangles >= 0 && num_triangles <= FP_TSDF_MAX_TRIANGLES, "fp_tsdf_emit_triangles: %lld triangles outside [0, %lld]",
+             (long long)num_triangles, (long long)FP_TSDF_MAX_TRIANGLES);
+  FP_REQUIRE(num_triangles == 0 || (keys && positions && colors), "fp_tsdf_emit_triangles: null output");
+  TsdfExtractArgs a;
+  memset(&a, 0, sizeof(a));
+  TRY(tsdf_volume("fp_tsdf_emit_triangles", box, nx, ny, nz, 2, a.vol));
+  if (num_triangles == 0) return FP_OK;
+  a.sdf_sum = sdf_sum, a.sdf_cnt = sdf_cnt, a.rgb_sum = rgb_sum, a.rgb_cnt = rgb_cnt, a.min_count = min_count;
+  a.offsets = reinterpret_cast<const long long*>(offsets), a.num_triangles = num_triangles;
+  a.keys = reinterpret_cast<long long*>(keys), a.pos = positions, a.col = colors;
+  return launch_tsdf_extract(a, true, ST(stream));
 }
 
 // ------------------------------------------------------------------ mask proposals from depth

@@ -402,6 +402,28 @@ struct GtVisArgs {
 };
 int launch_gt_visibility(const GtVisArgs& a, long long num_blocks, hipStream_t st);
 
+// ---------------------------------------------------------------- tsdf.hip
+struct TsdfVolume { double ox, oy, oz, h; int nx, ny, nz, pad; };   // voxel (i, j, k) is centred at origin + ((i, j, k) + 0.5) h; x fastest
+struct TsdfFrame { double fx, fy, cx, cy, R[9], t[3]; };            // one frame's camera and model -> camera pose (FP_TSDF_FRAME_DOUBLES doubles)
+struct TsdfIntegrateArgs {
+  TsdfVolume vol;
+  const float* depth; const uint8_t* mask; const uint8_t* rgb;      // [num_frames, height, width (, 3)]
+  const TsdfFrame* frames;                                          // [num_frames] device copy
+  int num_frames, height, width, pad;
+  double tau;
+  float* sdf_sum; int* sdf_cnt; float* rgb_sum; int* rgb_cnt;       // rgb_sum: 3 planes
+};
+struct TsdfExtractArgs {
+  TsdfVolume vol;
+  const float* sdf_sum; const int* sdf_cnt; const float* rgb_sum; const int* rgb_cnt;
+  int min_count, pad;
+  int* counts;                                                      // count: [cells]
+  const long long* offsets; long long num_triangles;                // emit: [cells], and the length of the outputs
+  long long* keys; float* pos; float* col;                          // emit: [3 T], [3 T, 3], [3 T, 3]
+};
+int launch_tsdf_integrate(const TsdfIntegrateArgs& a, hipStream_t st);
+int launch_tsdf_extract(const TsdfExtractArgs& a, bool emit, hipStream_t st);
+
 // ---------------------------------------------------------------- depth_proposals.hip
 struct DpFrame {                         // one frame, built on the host by fp_depth_plane_fit / fp_depth_components
   double fx, fy, cx, cy;

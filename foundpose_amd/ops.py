@@ -531,6 +531,119 @@ def gt_visibility(depth_test: torch.Tensor, depth_obj: torch.Tensor, inst, param
     return out, mask, mask_visib
 
 
+TSDF_PLANES = ("sdf_sum", "sdf_cnt", "rgb_sum", "rgb_cnt")
+
+
+def _tsdf_box(fn: str, origin, voxel_mm, dims):
+    """The checks the three TSDF wrappers share -> (box fp64 [4] on the host, (nx, ny, nz))."""
+    import numpy as np
+    try:
+        box = np.ascontiguousarray(np.concatenate([np.asarray(origin, np.float64).reshape(3), [float(voxel_mm)]]))
+        nx, ny, nz = (int(d) for d in dims)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{fn}: origin is three numbers, voxel_mm one, dims three integers ({e})")
+    if not np.all(np.isfinite(box)) or not box[3] > 0:
+        raise ValueError(f"{fn}: the origin must be finite and the voxel size finite and > 0")
+    if min(nx, ny, nz) < 1 or max(nx, ny, nz) > _lib.TSDF_MAX_DIM:
+        raise ValueError(f"{fn}: dimensions {nx} x {ny} x {nz} outside [1, {_lib.TSDF_MAX_DIM}]")
+    if nx * ny * nz > _lib.TSDF_MAX_VOXELS:
+        raise ValueError(f"{fn}: {nx} x {ny} x {nz} = {nx * ny * nz} voxels exceed {_lib.TSDF_MAX_VOXELS}")
+    return box, (nx, ny, nz)
+
+
+def _tsdf_state(fn: str, volume, dims) -> None:
+    nx, ny, nz = dims
+    for name in TSDF_PLANES:
+        t = volume.get(name) if isinstance(volume, dict) else None
+        want = (3, nz, ny, nx) if name == "rgb_sum" else (nz, ny, nx)
+        dt = torch.float32 if name.endswith("sum") else torch.int32
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{fn}: {name} must be a tensor on the device (there is no CPU path)")
+        if t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
+            raise ValueError(f"{fn}: {name} must be contiguous {dt} {want}, got {t.dtype} {tuple(t.shape)}")
+
+
+def tsdf_new_volume(origin, voxel_mm: float, dims, device="cuda") -> dict:
+    """An empty TSDF volume: a box in the model frame (mm) from `origin`, dims = (nx, ny, nz) voxels of
+    voxel_mm, x fastest, voxel centres at origin + (index + 0.5) voxel_mm.  -> dict(origin, voxel_mm, dims, sdf_sum fp32 [nz, ny, nx],
+    sdf_cnt int32, rgb_sum fp32 [3, nz, ny, nx], rgb_cnt int32), all zeros."""
+    box, (nx, ny, nz) = _tsdf_box("tsdf_new_volume", origin, voxel_mm, dims)
+    z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=device)   # noqa: E731
+    return {"origin": tuple(float(v) for v in box[:3]), "voxel_mm": float(box[3]), "dims": (nx, ny, nz),
+            "sdf_sum": z(nz, ny, nx, dt=torch.float32), "sdf_cnt": z(nz, ny, nx, dt=torch.int32),
+            "rgb_sum": z(3, nz, ny, nx, dt=torch.float32), "rgb_cnt": z(nz, ny, nx, dt=torch.int32)}
+
+
+def tsdf_integrate(volume: dict, depth: torch.Tensor, mask: torch.Tensor, rgb: torch.Tensor, cams, poses, trunc_mm: float) -> None:
+    """Adds F frames, in order, to `volume` in place (fp_tsdf_integrate): depth fp32 [F, H, W] mm (0 = no measurement), mask uint8
+    [F, H, W], rgb uint8 [F, H, W, 3] on the device; cams [F, 4] = (fx, fy, cx, cy) and poses [F, 12] = model -> camera R row-major | t
+    on the host.  Checked here, before any launch: ValueError, nothing written."""
+    import numpy as np
+    fn = "tsdf_integrate"
+    box, dims = _tsdf_box(fn, volume.get("origin") if isinstance(volume, dict) else None, volume.get("voxel_mm") if isinstance(volume, dict) else None,
+                          volume.get("dims", ()) if isinstance(volume, dict) else ())
+    _tsdf_state(fn, volume, dims)
+    for name, t, dt, nd in (("depth", depth, torch.float32, 3), ("mask", mask, torch.uint8, 3), ("rgb", rgb, torch.uint8, 4)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{fn}: {name} must be a tensor on the device (there is no CPU path)")
+        if t.dtype != dt or t.dim() != nd:
+            raise ValueError(f"{fn}: {name} must be {dt} with {nd} dimensions, got {t.dtype} {tuple(t.shape)}")
+    f, h, w = depth.shape
+    if tuple(mask.shape) != (f, h, w) or tuple(rgb.shape) != (f, h, w, 3):
+        raise ValueError(f"{fn}: depth {tuple(depth.shape)}, mask {tuple(mask.shape)} and rgb {tuple(rgb.shape)} are not one stack of frames")
+    if f < 1 or f > _lib.TSDF_MAX_FRAMES or h < 1 or w < 1 or h * w > 2**31 - 1:
+        raise ValueError(f"{fn}: {f} frames of {w} x {h}; 1 .. {_lib.TSDF_MAX_FRAMES} frames of at most 2^31 - 1 pixels per call")
+    host = []
+    for name, a, cols in (("cams", cams, 4), ("poses", poses, 12)):
+        if isinstance(a, torch.Tensor):
+            if a.is_cuda:
+                raise ValueError(f"{fn}: {name} is a host table (it is validated on the host)")
+            a = a.numpy()
+        a = np.asarray(a, np.float64)
+        if a.shape != (f, cols) or not np.all(np.isfinite(a)):
+            raise ValueError(f"{fn}: {name} must be finite [{f}, {cols}], got {a.shape}")
+        host.append(a)
+    if not np.all(host[0][:, :2] > 0):
+        raise ValueError(f"{fn}: fx and fy must be > 0")
+    tau = float(trunc_mm)
+    if not (np.isfinite(tau) and tau > 0):
+        raise ValueError(f"{fn}: trunc_mm must be finite and > 0, got {trunc_mm!r}")
+    frames = np.ascontiguousarray(np.concatenate(host, 1))
+    depth, mask, rgb = depth.contiguous(), mask.contiguous(), rgb.contiguous()
+    nbytes = _lib.tsdf_scratch_bytes(f)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=depth.device)
+    call("fp_tsdf_integrate", ptr(depth), ptr(mask), ptr(rgb), f, h, w, frames.ctypes.data_as(_lib.vp), box.ctypes.data_as(_lib.vp), *dims, tau,
+         ptr(scratch), nbytes, ptr(volume["sdf_sum"]), ptr(volume["sdf_cnt"]), ptr(volume["rgb_sum"]), ptr(volume["rgb_cnt"]), stream())
+
+
+def tsdf_extract(volume: dict, min_count: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Marching tetrahedra over `volume` (fp_tsdf_count_triangles, an exclusive scan by torch.cumsum, fp_tsdf_emit_triangles) -> (counts
+    int32 [nz - 1, ny - 1, nx - 1] triangles per cell, keys int64 [3 T], positions fp32 [3 T, 3], colors fp32 [3 T, 3]): per triangle
+    corner the grid edge it lies on, unwelded.  Checked here, before any launch: ValueError."""
+    fn = "tsdf_extract"
+    box, dims = _tsdf_box(fn, volume.get("origin") if isinstance(volume, dict) else None, volume.get("voxel_mm") if isinstance(volume, dict) else None,
+                          volume.get("dims", ()) if isinstance(volume, dict) else ())
+    _tsdf_state(fn, volume, dims)
+    if min(dims) < 2:
+        raise ValueError(f"{fn}: dimensions {dims} leave no cell between voxel centres")
+    if isinstance(min_count, bool) or not hasattr(min_count, "__index__") or int(min_count) < 1 or int(min_count) > 2**31 - 1:
+        raise ValueError(f"{fn}: min_count must be an integer >= 1, got {min_count!r}")
+    nx, ny, nz = dims
+    dev = volume["sdf_sum"].device
+    counts = torch.empty(nz - 1, ny - 1, nx - 1, dtype=torch.int32, device=dev)
+    call("fp_tsdf_count_triangles", ptr(volume["sdf_sum"]), ptr(volume["sdf_cnt"]), nx, ny, nz, int(min_count), ptr(counts), stream())
+    ends = torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)
+    total = int(ends[-1])
+    offsets = (ends - counts.reshape(-1)).contiguous()
+    keys = torch.empty(3 * total, dtype=torch.int64, device=dev)
+    pos = torch.empty(3 * total, 3, dtype=torch.float32, device=dev)
+    col = torch.empty(3 * total, 3, dtype=torch.float32, device=dev)
+    call("fp_tsdf_emit_triangles", ptr(volume["sdf_sum"]), ptr(volume["sdf_cnt"]), ptr(volume["rgb_sum"]), ptr(volume["rgb_cnt"]),
+         box.ctypes.data_as(_lib.vp), nx, ny, nz, int(min_count), ptr(offsets), total, ptr(keys) if total else None, ptr(pos) if total else None,
+         ptr(col) if total else None, stream())
+    return counts, keys, pos, col
+
+
 def _depth_checked(name: str, rc: int) -> None:
     if rc == 1:   # FP_ERR_INVALID: the one validation is the C entry's
         raise ValueError(_lib.lib().fp_last_error().decode())

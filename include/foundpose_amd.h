@@ -1077,6 +1077,61 @@ int fp_component_table(const int32_t* labels, int num_frames, int height, int wi
 int fp_component_runs(const int32_t* rank_map, int num_maps, int height, int width, const int32_t* num_kept, int max_proposals,
                       int64_t capacity, int64_t* events, int32_t* num_events, fp_stream_t stream);
 
+/* ---- TSDF fusion of posed RGB-D frames and surface extraction (reconstruct.py; tests/tsdf_ref.py restates
+ *      both stages) ----
+ * The volume is a box in the model frame, mm: `box` = HOST fp64 [4] (origin x, y, z, voxel size h), nx x ny x nz voxels, x fastest,
+ * voxel (i, j, k) centred at origin + ((i, j, k) + 0.5) h.  1 <= each dimension <= FP_TSDF_MAX_DIM (>= 2 for the two extraction
+ * entries) and nx ny nz <= FP_TSDF_MAX_VOXELS.  Its state is six device planes of nx ny nz entries each: sdf_sum fp32, sdf_cnt int32,
+ * rgb_sum fp32 [3, nz, ny, nx] (three planes: r, g, b), rgb_cnt int32; a new volume is all zeros.  Sums and counts, never running
+ * means: the state after frames 1 .. F is bit-identical however the frames are split into calls.
+ *
+ * fp_tsdf_integrate adds num_frames frames, in ascending order, to the state.  Device arrays: depth fp32 [F, height, width] mm (a value
+ * that is not > 0 is no measurement), mask uint8 [F, height, width], rgb uint8 [F, height, width, 3].  HOST array: frames fp64
+ * [F, FP_TSDF_FRAME_DOUBLES] rows (fx, fy, cx, cy, R row-major, t), the model -> camera pose; it is validated (everything finite, fx and
+ * fy > 0), then copied into scratch on `stream`, and the call waits for that copy as fp_gt_visibility does.  Per voxel centre X and
+ * frame, fp64, every operation rounded on its own:
+ *   x, y, z = ((r0 X + r1 Y) + r2 Z) + t per row of R; the frame is skipped unless z > 1
+ *   u = (fx x) / z + cx, v = (fy y) / z + cy (pixel centres at integers); the tap is (floor(u + 0.5), floor(v + 0.5)), and the frame is
+ *   skipped when it lies outside the image (no tap outside the image is read) or its depth d is no measurement
+ *   mask == 0: when d >= z, sdf_sum += 1 and sdf_cnt += 1 (seen through: empty space); otherwise nothing (hidden)
+ *   mask != 0: s = d - z; nothing when s < -trunc_mm; otherwise sdf_sum += (float)min(1, s / trunc_mm), sdf_cnt += 1, and when also
+ *   |s| <= trunc_mm, rgb_sum += (float)rgb / 255.0f per channel (fp32 division) and rgb_cnt += 1.  The fp32 sums add in frame order.
+ * One thread per voxel, no atomics, no reduction across threads.  1 <= F <= FP_TSDF_MAX_FRAMES, height * width <= 2^31 - 1,
+ * trunc_mm finite and > 0; scratch: FP_TSDF_SCRATCH_BYTES(F).
+ *
+ * Extraction is marching tetrahedra on the cells between voxel centres ((nx - 1)(ny - 1)(nz - 1) of them, x fastest).  A cell's
+ * corners are numbered by bits (x = bit 0, y = bit 1, z = bit 2) and it is cut into the six tetrahedra (0, a, b, 7), (a, b) =
+ * (1,3), (3,2), (2,6), (6,4), (4,5), (5,1), the same way in every cell, so neighbouring cells agree on every shared face.  A cell takes
+ * part only when all eight corners have sdf_cnt >= min_count (>= 1).  A corner's value is f = (double)sdf_sum / (double)sdf_cnt; it is
+ * inside when f < 0 (an exact 0 is outside).  A tetrahedron with 1 or 3 corners inside gives one triangle, with 2 inside two.
+ * fp_tsdf_count_triangles writes counts int32 [cells], the triangles per cell.
+ * fp_tsdf_emit_triangles takes offsets int64 [cells] (device), the exclusive scan of those counts, and num_triangles, their sum, and
+ * writes per triangle corner keys int64 [3 T], positions fp32 [3 T, 3] and colors fp32 [3 T, 3]; a cell whose offset would leave
+ * [0, num_triangles) writes nothing.  Every vertex lies on an edge of the split, which joins a lower corner to one with more bits set:
+ *   key      = (linear voxel index of the lower corner) * 7 + direction, the direction indexing the corner offsets (1,0,0), (0,1,0),
+ *              (0,0,1), (1,1,0), (0,1,1), (1,0,1), (1,1,1)
+ *   position = (float)(p_lo + w (p_hi - p_lo)) per axis, w = f_lo / (f_lo - f_hi), fp64 from the lower corner: the same bits from
+ *              whichever tetrahedron or cell reaches the edge
+ *   color    = (float)(c_lo + w (c_hi - c_lo)), c = (double)rgb_sum / (double)rgb_cnt; a corner with rgb_cnt = 0 has no colour: the
+ *              other corner's is used, or 0.5 when neither has one
+ * The winding makes the face normal point from inside to outside, towards rising f.
+ * A NULL pointer, a size or option outside its range or too little scratch: FP_ERR_INVALID, nothing written.  (Added without a
+ * change of FP_ABI_VERSION: no existing entry point changed.) */
+#define FP_TSDF_MAX_DIM 512
+#define FP_TSDF_MAX_VOXELS (1ll << 27)
+#define FP_TSDF_MAX_FRAMES 4096
+#define FP_TSDF_MAX_TRIANGLES (12 * FP_TSDF_MAX_VOXELS)
+#define FP_TSDF_FRAME_DOUBLES 16
+#define FP_TSDF_SCRATCH_BYTES(num_frames) (8 * FP_TSDF_FRAME_DOUBLES * (size_t)(num_frames))
+int fp_tsdf_integrate(const float* depth, const uint8_t* mask, const uint8_t* rgb, int num_frames, int height, int width,
+                      const double* frames, const double* box, int nx, int ny, int nz, double trunc_mm, void* scratch,
+                      size_t scratch_bytes, float* sdf_sum, int32_t* sdf_cnt, float* rgb_sum, int32_t* rgb_cnt, fp_stream_t stream);
+int fp_tsdf_count_triangles(const float* sdf_sum, const int32_t* sdf_cnt, int nx, int ny, int nz, int min_count, int32_t* counts,
+                            fp_stream_t stream);
+int fp_tsdf_emit_triangles(const float* sdf_sum, const int32_t* sdf_cnt, const float* rgb_sum, const int32_t* rgb_cnt, const double* box,
+                           int nx, int ny, int nz, int min_count, const int64_t* offsets, int64_t num_triangles, int64_t* keys,
+                           float* positions, float* colors, fp_stream_t stream);
+
 /* ---- featuremetric refinement of the best coarse pose (tests/featuremetric_ref.py restates it) ----
  * Levenberg-Marquardt on the 6-DoF pose of each of num_det detections, aligning a template's per-point features with the
  * query's projected patch-feature map.  Device arrays:
