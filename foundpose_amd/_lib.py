@@ -123,6 +123,8 @@ _PROTOS = {
     "fp_tsdf_integrate": [vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, f64, vp, C.c_size_t, vp, vp, vp, vp, vp],
     "fp_tsdf_count_triangles": [vp, vp, i32, i32, i32, i32, vp, vp],
     "fp_tsdf_emit_triangles": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp],
+    "fp_tsdf_track": [vp, vp, vp, i32, i32, i32, i32, f64, vp, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp,
+                      vp, vp],
     "fp_featuremetric_refine": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32,
                                 vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "fp_depth_refine": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
@@ -281,6 +283,11 @@ def depth_refine_scratch_bytes(num_det: int, max_points: int) -> int:
     """FP_DEPTH_REFINE_SCRATCH_BYTES of include/foundpose_amd.h."""
     chunks = (max_points + REFINE_CHUNK - 1) // REFINE_CHUNK
     return REFINE_STATE_BYTES * num_det + 8 * REFINE_RECORD * num_det * chunks + 8
+
+
+def tsdf_track_scratch_bytes(num_det: int, max_points: int) -> int:
+    """FP_TSDF_TRACK_SCRATCH_BYTES of include/foundpose_amd.h."""
+    return depth_refine_scratch_bytes(num_det, max_points)
 
 
 def rgbd_refine_scratch_bytes(num_det: int, max_points: int) -> int:

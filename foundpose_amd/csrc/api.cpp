@@ -1,6 +1,6 @@
 // C ABI of libfoundpose_amd.so (declared in include/foundpose_amd.h): argument checking, scratch carving
 // and kernel sequencing.  No device allocation, no global mutable state, no synchronisation except the table uploads of
-// fp_pose_errors, fp_vsd_counts, fp_gt_visibility, fp_depth_plane_fit, fp_depth_components and fp_tsdf_integrate (each waits for its own copy) and the range check read back by the three refinements (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine).
+// fp_pose_errors, fp_vsd_counts, fp_gt_visibility, fp_depth_plane_fit, fp_depth_components and fp_tsdf_integrate (each waits for its own copy) and the range check read back by the three refinements (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine) and by fp_tsdf_track.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -1276,6 +1276,33 @@ int fp_tsdf_emit_triangles(const float* sdf_sum, const int32_t* sdf_cnt, const f
   a.offsets = reinterpret_cast<const long long*>(offsets), a.num_triangles = num_triangles;
   a.keys = reinterpret_cast<long long*>(keys), a.pos = positions, a.col = colors;
   return launch_tsdf_extract(a, true, ST(stream));
+}
+
+int fp_tsdf_track(const float* sdf_sum, const int32_t* sdf_cnt, const double* box, int nx, int ny, int nz, int min_count, double trunc_mm,
+                  const float* points, int64_t num_rows, const int32_t* row_begin, const int32_t* row_end, const double* R_in,
+                  const double* t_in, const int32_t* has_pose, const double* max_dist, int num_det, int max_points, int iters,
+                  void* scratch, size_t scratch_bytes, double* R_out, double* t_out, double* cost_in, double* cost_out,
+                  int32_t* num_points, int32_t* iters_used, int32_t* status, double* normal_eq, fp_stream_t stream) {
+  const char* fn = "fp_tsdf_track";
+  FP_REQUIRE(sdf_sum && sdf_cnt && box && points && row_begin && row_end && R_in && t_in && has_pose && max_dist && scratch && R_out && t_out &&
+             cost_in && cost_out && num_points && iters_used && status, "fp_tsdf_track: null pointer");
+  FP_REQUIRE(min_count >= 1, "fp_tsdf_track: min_count %d must be >= 1", min_count);
+  FP_REQUIRE(std::isfinite(trunc_mm) && trunc_mm > 0, "fp_tsdf_track: the truncation distance must be finite and > 0");
+  TsdfTrackArgs a;
+  memset(&a, 0, sizeof(a));
+  TRY(tsdf_volume(fn, box, nx, ny, nz, 2, a.vol));
+  a.lm = refine_lm_args(nullptr, R_in, t_in, row_begin, row_end, points, num_rows, has_pose, num_det, max_points, iters, R_out, t_out, cost_in,
+                        cost_out, num_points, iters_used, status, normal_eq);
+  TRY(refine_check(fn, a.lm, nullptr, nullptr, nullptr));
+  a.sdf_sum = sdf_sum, a.sdf_cnt = sdf_cnt, a.min_count = min_count, a.tau = trunc_mm, a.max_dist = max_dist;
+  a.state = static_cast<RefineState*>(scratch);
+  TRY(refine_carve(fn, a.lm, scratch, scratch_bytes, FP_TSDF_TRACK_SCRATCH_BYTES(num_det, max_points), FP_REFINE_RECORD, nullptr, ST(stream)));
+  TRY(launch_tsdf_track(a, ST(stream)));
+  // the one wait of the call, after every iteration is enqueued: a bad row range is reported here, never read
+  int32_t bad = 0;
+  HIP_TRY(hipMemcpyWithStream(&bad, a.lm.err, sizeof(int32_t), hipMemcpyDeviceToHost, ST(stream)), "fp_tsdf_track: status read");
+  FP_REQUIRE(bad == 0, "fp_tsdf_track: problem %d: rows outside [0, %lld) or more than max_points %d", bad - 1, a.lm.num_rows, max_points);
+  return FP_OK;
 }
 
 // ------------------------------------------------------------------ mask proposals from depth

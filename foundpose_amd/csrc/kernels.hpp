@@ -424,6 +424,18 @@ struct TsdfExtractArgs {
 int launch_tsdf_integrate(const TsdfIntegrateArgs& a, hipStream_t st);
 int launch_tsdf_extract(const TsdfExtractArgs& a, bool emit, hipStream_t st);
 
+// ---------------------------------------------------------------- tsdf_track.hip (the LM parts: refine_terms.hpp)
+struct TsdfTrackArgs {     // lm.verts are the camera-frame points, lm.cam is not used
+  RefineLmArgs lm;
+  TsdfVolume vol;
+  const float* sdf_sum; const int* sdf_cnt;
+  int min_count, pad;
+  double tau;              // trunc_mm: r = tau phi
+  const double* max_dist;  // [num_det] the inlier distance (mm)
+  RefineState* state;
+};
+int launch_tsdf_track(const TsdfTrackArgs& a, hipStream_t st);
+
 // ---------------------------------------------------------------- depth_proposals.hip
 struct DpFrame {                         // one frame, built on the host by fp_depth_plane_fit / fp_depth_components
   double fx, fy, cx, cy;

@@ -1,0 +1,186 @@
+// Frame-to-model tracking against a TSDF volume (reconstruct.py with pose_source "track"): Levenberg-Marquardt on
+// the model -> camera pose that lays a frame's camera-frame depth points onto the zero level of the volume fp_tsdf_integrate has built
+// so far.  The residual of a point is the trilinear sample of the volume at X_m = R^T (X_c - t), in mm (r = tau phi); the objective is
+// section 14's truncated quadratic.  tests/tsdf_track_ref.py restates the contract in numpy fp64.
+//
+// Kernels, all enqueued by fp_tsdf_track without a host round trip between them:
+//   tsdf_track_setup     one thread per problem: validates the row range, initialises the LM state (lm_setup, no image index)
+//   tsdf_track_pass      (chunk of FP_REFINE_CHUNK points, problem), one wave: ONE POINT PER LANE -- the point into the model frame, the
+//                        cell it falls into, eight sdf_cnt taps, then (only where all eight were seen min_count times) eight sdf_sum taps,
+//                        the sample, its gradient and the Jacobian row (fp64; track_point) -- then a butterfly over the chunk's lanes for
+//                        the 29 terms, one partial record per workgroup.  The two x-neighbours of a tap pair are adjacent in memory.
+//   tsdf_track_solve     one wave per problem: folds the partials in chunk order, accepts / rejects the trial pose, solves for the next
+//   tsdf_track_finalize  one thread per problem: the outputs (lm_finalize)
+// A bad row range anywhere in the batch fails the whole call, as in the refiners; here the pass, the solve and the finalize then leave
+// at their first instruction, so that such a call writes none of its outputs.
+// The LM parts are refine_terms.hpp's, unchanged; the pass / solve skeleton is depth_refine.hip's (same record layout, same cost
+// normalisation, same stop on fewer than 6 inliers).  The per-point term stays in this file: refine_terms.hpp is compiled into the
+// three pose refiners, and their code is left as it is.  Every floating-point statement of the term stands as one source expression
+// (the library is built with -ffp-contract=on).  Every sum has a fixed order (lanes: butterfly; chunks: ascending), no atomics, and a
+// problem's chunk decomposition depends only on its own point count: results are bit-identical across runs and batch compositions.
+#include "common.hpp"
+#include "kernels.hpp"
+#include "refine_terms.hpp"
+
+namespace {
+
+constexpr int TT_REC = FP_REFINE_RECORD;   // the partial record of depth_refine.hip: H (21), g (6), sum rho [27], pad, inliers [29], pad
+static_assert(FP_REFINE_CHUNK == 32, "one half-wave per chunk");
+
+// One camera-frame point Xv under the pose (R, t) against the volume.  acc arrives zeroed and leaves with the point's FP_DEPTH_TERMS
+// values: H (21), g (6), rho [27], the inlier flag [28].
+FP_DEVICE void track_point(const TsdfTrackArgs& a, int b, const double* R, const double* t, const float* Xv, double (&acc)[FP_DEPTH_TERMS]) {
+  const double md = a.max_dist[b], tau = a.tau, h = a.vol.h;
+  const double Xc[3] = {Xv[0], Xv[1], Xv[2]};
+  const double d0 = Xc[0] - t[0], d1 = Xc[1] - t[1], d2 = Xc[2] - t[2];
+  double Xm[3];
+  for (int i = 0; i < 3; ++i) Xm[i] = R[i] * d0 + R[3 + i] * d1 + R[6 + i] * d2;
+  const double gx = (Xm[0] - a.vol.ox) / h - 0.5, gy = (Xm[1] - a.vol.oy) / h - 0.5, gz = (Xm[2] - a.vol.oz) / h - 0.5;
+  // measurable: the cell's lower corner floor(g) lies in [0, n - 2] on every axis (a NaN or an infinity compares false), decided in fp64
+  // before any conversion or read, and all eight corners were seen min_count times
+  bool ok = gx >= 0.0 && gx < (double)(a.vol.nx - 1) && gy >= 0.0 && gy < (double)(a.vol.ny - 1) && gz >= 0.0 && gz < (double)(a.vol.nz - 1);
+  double rho = md * md;
+  if (ok) {
+    const int i0 = (int)floor(gx), j0 = (int)floor(gy), k0 = (int)floor(gz);
+    const double ax = gx - i0, ay = gy - j0, az = gz - k0;
+    const long long sy = a.vol.nx, sz = (long long)a.vol.nx * a.vol.ny;
+    const long long base = (long long)k0 * sz + (long long)j0 * sy + i0;
+    const int* c0 = a.sdf_cnt + base;
+    const int n0 = c0[0], n1 = c0[1], n2 = c0[sy], n3 = c0[sy + 1], n4 = c0[sz], n5 = c0[sz + 1], n6 = c0[sz + sy], n7 = c0[sz + sy + 1];
+    const int mc = a.min_count;
+    ok = n0 >= mc && n1 >= mc && n2 >= mc && n3 >= mc && n4 >= mc && n5 >= mc && n6 >= mc && n7 >= mc;
+    if (ok) {   // only now is sdf_sum read
+      const float* s0 = a.sdf_sum + base;
+      const double f0 = (double)s0[0] / (double)n0, f1 = (double)s0[1] / (double)n1, f2 = (double)s0[sy] / (double)n2, f3 = (double)s0[sy + 1] / (double)n3;
+      const double f4 = (double)s0[sz] / (double)n4, f5 = (double)s0[sz + 1] / (double)n5, f6 = (double)s0[sz + sy] / (double)n6, f7 = (double)s0[sz + sy + 1] / (double)n7;
+      // x first, then y, then z
+      const double c00 = (1.0 - ax) * f0 + ax * f1, c10 = (1.0 - ax) * f2 + ax * f3, c01 = (1.0 - ax) * f4 + ax * f5, c11 = (1.0 - ax) * f6 + ax * f7;
+      const double phi = (1.0 - az) * ((1.0 - ay) * c00 + ay * c10) + az * ((1.0 - ay) * c01 + ay * c11);
+      const double r = tau * phi;
+      if (fabs(r) < md) {   // an inlier: the only points with a gradient
+        // the exact gradient of the interpolant: the four differences along an axis, bilinear over the other two, over h
+        const double px = ((1.0 - az) * ((1.0 - ay) * (f1 - f0) + ay * (f3 - f2)) + az * ((1.0 - ay) * (f5 - f4) + ay * (f7 - f6))) / h;
+        const double py = ((1.0 - az) * ((1.0 - ax) * (f2 - f0) + ax * (f3 - f1)) + az * ((1.0 - ax) * (f6 - f4) + ax * (f7 - f5))) / h;
+        const double pz = ((1.0 - ay) * ((1.0 - ax) * (f4 - f0) + ax * (f5 - f1)) + ay * ((1.0 - ax) * (f6 - f2) + ax * (f7 - f3))) / h;
+        // q = tau R grad phi, the gradient in the camera frame.  Under the left twist (w, v) of lm_propose the model point moves by
+        // R^T (X_c x w - v), so dr = w . (q x X_c) - q . v
+        double q[3], J[6];
+        for (int i = 0; i < 3; ++i) q[i] = tau * (R[3 * i] * px + R[3 * i + 1] * py + R[3 * i + 2] * pz);
+        cross3(q, Xc, J);
+        for (int i = 0; i < 3; ++i) J[3 + i] = -q[i];
+        int k2 = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+          for (int j = i; j < 6; ++j, ++k2) acc[k2] = J[i] * J[j];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) acc[21 + i] = J[i] * r;
+        rho = r * r;
+        acc[28] = 1.0;
+      }
+    }
+  }
+  acc[27] = rho;
+}
+
+__global__ void __launch_bounds__(64) tsdf_track_setup_kernel(TsdfTrackArgs a) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  RefineLmArgs lm = a.lm;
+  lm.normal_eq = nullptr;   // a call with a bad row range writes none of its outputs: the finalize zeroes the rows no solve has written
+  if (b < lm.num_det) lm_setup(lm, nullptr, a.state[b], b, 28);
+}
+
+// A chunk is FP_REFINE_CHUNK = 32 points (the chunk of the three refiners: lm_fold and the scratch layout are shared), so lanes 32..63
+// of the wave idle by construction, as in depth_refine_pass_kernel.
+__global__ void __launch_bounds__(64) tsdf_track_pass_kernel(TsdfTrackArgs a) {
+  if (a.lm.err[0] != 0) return;   // a bad row range somewhere in the batch (set by the setup, a launch ago): the call fails, nothing is computed
+  const int b = blockIdx.y;
+  const RefineState& s = a.state[b];
+  if (!s.active || !s.pending) return;
+  const int np = s.np, chunk0 = blockIdx.x * FP_REFINE_CHUNK;
+  if (chunk0 >= np) return;
+  const int lane = threadIdx.x;
+  const int p = chunk0 + lane;
+  double acc[FP_DEPTH_TERMS];
+#pragma unroll
+  for (int k = 0; k < FP_DEPTH_TERMS; ++k) acc[k] = 0.0;
+  if (lane < FP_REFINE_CHUNK && p < np) track_point(a, b, s.Rt, s.tt, a.lm.verts + 3 * ((long long)s.p0 + p), acc);
+  // lanes 32..63 carry zeros and fold among themselves: lane 0 ends with the sum of lanes 0..31 in butterfly order
+#pragma unroll
+  for (int k = 0; k < FP_DEPTH_TERMS; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int o = FP_REFINE_CHUNK / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    acc[k] = v;
+  }
+  if (lane == 0) {
+    double* out = a.lm.part + ((long long)b * a.lm.chunks + blockIdx.x) * TT_REC;
+#pragma unroll
+    for (int k = 0; k < 28; ++k) out[k] = acc[k];
+    out[28] = 0.0;
+    out[29] = acc[28];
+    out[30] = out[31] = 0.0;
+  }
+}
+
+__global__ void __launch_bounds__(64) tsdf_track_solve_kernel(TsdfTrackArgs a, int mode) {
+  __shared__ double tot[TT_REC];
+  if (a.lm.err[0] != 0) return;
+  const int b = blockIdx.x;
+  RefineState& s = a.state[b];
+  if (!s.active || !s.pending) return;
+  lm_fold(a.lm, b, s.np, TT_REC, threadIdx.x, tot);
+  if (threadIdx.x != 0) return;
+  s.pending = 0;
+  const double Et = tot[27] / s.np;   // the point set is every row of the range: costs at different poses are comparable
+  if (mode == SOLVE_STEP && !(Et < s.E)) {
+    lm_reject(s, a.lm.iters);
+    return;
+  }
+  if (mode == SOLVE_FIRST) {
+    s.E = s.E_in = Et;
+    s.nvalid = (int)tot[29];
+    if (a.lm.normal_eq) {
+      for (int i = 0; i < 27; ++i) a.lm.normal_eq[28 * b + i] = tot[i];
+      a.lm.normal_eq[28 * b + 27] = Et;
+    }
+  } else if (!lm_accept(s, Et)) {
+    return;
+  }
+  lm_set_system(s, tot);
+  if (mode == SOLVE_FIRST) {
+    if (s.nvalid < 6) { lm_stop(s); return; }
+    s.skipped = 0;
+  }
+  lm_propose(s, a.lm.iters);
+}
+
+__global__ void __launch_bounds__(64) tsdf_track_finalize_kernel(TsdfTrackArgs a) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (a.lm.err[0] != 0 || b >= a.lm.num_det) return;
+  if (a.lm.normal_eq && a.state[b].np == 0)   // no pose or an empty range: no solve ran
+    for (int i = 0; i < 28; ++i) a.lm.normal_eq[28 * b + i] = 0.0;
+  lm_finalize(a.lm, a.state[b], b);
+}
+
+}  // namespace
+
+int launch_tsdf_track(const TsdfTrackArgs& a, hipStream_t st) {
+  const dim3 pgrid(a.lm.chunks, a.lm.num_det), sgrid(a.lm.num_det);
+  const int tgrid = cdiv(a.lm.num_det, 64);
+  hipLaunchKernelGGL(tsdf_track_setup_kernel, dim3(tgrid), dim3(64), 0, st, a);
+  FP_CHECK_LAUNCH("tsdf_track_setup");
+  hipLaunchKernelGGL(tsdf_track_pass_kernel, pgrid, dim3(64), 0, st, a);
+  FP_CHECK_LAUNCH("tsdf_track_pass");
+  hipLaunchKernelGGL(tsdf_track_solve_kernel, sgrid, dim3(64), 0, st, a, (int)SOLVE_FIRST);
+  FP_CHECK_LAUNCH("tsdf_track_solve");
+  for (int k = 0; k < a.lm.iters; ++k) {
+    hipLaunchKernelGGL(tsdf_track_pass_kernel, pgrid, dim3(64), 0, st, a);
+    FP_CHECK_LAUNCH("tsdf_track_pass");
+    hipLaunchKernelGGL(tsdf_track_solve_kernel, sgrid, dim3(64), 0, st, a, (int)SOLVE_STEP);
+    FP_CHECK_LAUNCH("tsdf_track_solve");
+  }
+  hipLaunchKernelGGL(tsdf_track_finalize_kernel, dim3(tgrid), dim3(64), 0, st, a);
+  FP_CHECK_LAUNCH("tsdf_track_finalize");
+  return FP_OK;
+}

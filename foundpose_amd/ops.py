@@ -644,6 +644,67 @@ def tsdf_extract(volume: dict, min_count: int) -> Tuple[torch.Tensor, torch.Tens
     return counts, keys, pos, col
 
 
+def tsdf_track(volume: dict, points: torch.Tensor, row_begin: torch.Tensor, row_end: torch.Tensor, R: torch.Tensor, t: torch.Tensor, max_dist,
+               min_count: int, trunc_mm: float, iters: int, has_pose: Optional[torch.Tensor] = None, want_normal_eq: bool = False) -> dict:
+    """Tracks B independent problems against `volume` (fp_tsdf_track; DESIGN.md section 30): points fp32 [N, 3], camera-frame mm;
+    row_begin / row_end int [B]: a problem's rows of points; R [B, 3, 3] / t [B, 3] the start poses, model -> camera; max_dist: the
+    inlier distance in mm, a number or one per problem (not validated: a NaN or a value <= 0 skips the problem); trunc_mm: the tau the
+    volume was built with; has_pose [B] bool (None: all).  Everything else is checked here, before any launch: ValueError.
+    -> dict of device tensors: R [B, 3, 3] f64, t [B, 3] f64, cost_in, cost_out [B] f64, num_points (inliers at the start pose),
+    iters_used, status [B] i32 (0 refined, 1 no step accepted, 2 skipped), + normal_eq [B, 28] f64 with want_normal_eq."""
+    import numpy as np
+    fn = "tsdf_track"
+    box, dims = _tsdf_box(fn, volume.get("origin") if isinstance(volume, dict) else None, volume.get("voxel_mm") if isinstance(volume, dict) else None,
+                          volume.get("dims", ()) if isinstance(volume, dict) else ())
+    _tsdf_state(fn, volume, dims)
+    if min(dims) < 2:
+        raise ValueError(f"{fn}: dimensions {dims} leave no cell between voxel centres")
+    if isinstance(min_count, bool) or not hasattr(min_count, "__index__") or int(min_count) < 1 or int(min_count) > 2**31 - 1:
+        raise ValueError(f"{fn}: min_count must be an integer >= 1, got {min_count!r}")
+    tau = float(trunc_mm)
+    if not (np.isfinite(tau) and tau > 0):
+        raise ValueError(f"{fn}: trunc_mm must be finite and > 0, got {trunc_mm!r}")
+    if isinstance(iters, bool) or not hasattr(iters, "__index__") or not 0 <= int(iters) <= 1000:
+        raise ValueError(f"{fn}: iters must be an integer in [0, 1000], got {iters!r}")
+    for name, x in (("points", points), ("row_begin", row_begin), ("row_end", row_end), ("R", R), ("t", t)) + ((("has_pose", has_pose),) if has_pose is not None else ()):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise ValueError(f"{fn}: {name} must be a tensor on the device (there is no CPU path)")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"{fn}: points {tuple(points.shape)} are not [N, 3]")
+    B = int(row_begin.numel())
+    if B < 1 or B > 65535 or row_begin.dim() != 1 or tuple(row_end.shape) != (B,) or R.numel() != 9 * B or t.numel() != 3 * B:
+        raise ValueError(f"{fn}: row_begin {tuple(row_begin.shape)}, row_end {tuple(row_end.shape)}, R {tuple(R.shape)} and t {tuple(t.shape)} are not "
+                         "one batch of 1 .. 65535 problems")
+    if has_pose is not None and tuple(has_pose.shape) != (B,):
+        raise ValueError(f"{fn}: has_pose {tuple(has_pose.shape)} is not [{B}]")
+    md = np.asarray(max_dist.detach().cpu().numpy() if isinstance(max_dist, torch.Tensor) else max_dist, np.float64)
+    if md.ndim == 0:
+        md = np.full(B, float(md))
+    if md.shape != (B,):
+        raise ValueError(f"{fn}: max_dist is one number or one per problem, got {md.shape}")
+    dev = points.device
+    p32 = points.float().contiguous()
+    Rin, tin = R.to(torch.float64).reshape(B, 9).contiguous(), t.to(torch.float64).reshape(B, 3).contiguous()
+    rb, re = row_begin.to(torch.int32).contiguous(), row_end.to(torch.int32).contiguous()
+    hp = torch.ones(B, dtype=torch.int32, device=dev) if has_pose is None else has_pose.to(torch.int32).contiguous()
+    md_d = _lib.upload_async(torch.from_numpy(np.ascontiguousarray(md)), dev)
+    max_points = max(1, int(torch.where(hp != 0, re - rb, torch.zeros_like(re)).max().item()))
+    f64, i32, empty = torch.float64, torch.int32, torch.empty
+    out = {"R": empty(B, 9, dtype=f64, device=dev), "t": empty(B, 3, dtype=f64, device=dev), "cost_in": empty(B, dtype=f64, device=dev),
+           "cost_out": empty(B, dtype=f64, device=dev), "num_points": empty(B, dtype=i32, device=dev), "iters_used": empty(B, dtype=i32, device=dev),
+           "status": empty(B, dtype=i32, device=dev)}
+    neq = empty(B, 28, dtype=f64, device=dev) if want_normal_eq else None
+    nbytes = _lib.tsdf_track_scratch_bytes(B, max_points)
+    scratch = empty(nbytes, dtype=torch.uint8, device=dev)
+    call("fp_tsdf_track", ptr(volume["sdf_sum"]), ptr(volume["sdf_cnt"]), box.ctypes.data_as(_lib.vp), *dims, int(min_count), tau, ptr(p32),
+         int(p32.shape[0]), ptr(rb), ptr(re), ptr(Rin), ptr(tin), ptr(hp), ptr(md_d), B, max_points, int(iters), ptr(scratch), nbytes,
+         *[ptr(v) for v in out.values()], ptr(neq), stream())
+    out["R"] = out["R"].reshape(B, 3, 3)
+    if neq is not None:
+        out["normal_eq"] = neq
+    return out
+
+
 def _depth_checked(name: str, rc: int) -> None:
     if rc == 1:   # FP_ERR_INVALID: the one validation is the C entry's
         raise ValueError(_lib.lib().fp_last_error().decode())

@@ -1,7 +1,7 @@
 """Reconstructs an object mesh from posed RGB-D frames: TSDF fusion and marching tetrahedra on the MI355X.
 
     python -m foundpose_amd.reconstruct --sequence <scene dir> [--sequence <scene dir> ...] --obj-id N --output <models dir>
-        [--opts opts.json] [--report report.json] [--overwrite]
+        [--opts opts.json] [--report report.json] [--overwrite] [--tracked-poses <dir>]
 
 Each sequence is a BOP scene directory (`rgb/`, `depth/`, `<mask_dir>/<im>_<gt index>.png`, `scene_gt.json`, `scene_camera.json` with
 `depth_scale`): the reference sequences of BOP's model-free tasks, or an object on a turntable in front of a depth camera.  Every
@@ -10,7 +10,12 @@ one truncated signed distance volume (fp_tsdf_integrate), a surface is pulled ou
 fp_tsdf_emit_triangles), welded, and written as the vertex-coloured `obj_%06d.ply` that gen_templates, gen_repre, models_info and
 detect onboard start from.  There is no CPU path.
 
-Limits: poses and masks are trusted as given; a voxel reads the nearest depth pixel, across depth edges too; surface that no frame
+With opts `pose_source: "track"` one known pose per sequence is enough: the frames are the images of
+scene_camera.json, only the first image's scene_gt.json pose is used (and every Nth with `track_anchor_every`), every other frame is
+tracked against the volume fused so far (fp_tsdf_track) and fused at its tracked pose; `bounds` must then be given, and
+--tracked-poses writes the poses per sequence in scene_gt.json's format.
+
+Limits: with pose_source "given" poses and masks are trusted as given; a voxel reads the nearest depth pixel, across depth edges too; surface that no frame
 saw stays open (the report says so, nothing is filled); no accuracy on real BOP data is claimed."""
 
 import argparse
@@ -36,6 +41,15 @@ class ReconstructOpts(NamedTuple):
     mask_dir: str = "mask_visib"
     keep_largest: bool = True
     frame_batch: int = 32
+    pose_source: str = "given"     # "given": every frame's pose comes from scene_gt.json; "track": frames are tracked against the volume (section 30)
+    track_anchor_every: int = 0    # 0: only the first frame of a sequence takes its pose from scene_gt.json; N > 0: every Nth frame does too
+    track_iters: int = 20          # Levenberg-Marquardt iterations per tracked frame
+    track_max_dist_voxels: float = 3.0   # the inlier distance, in voxels (<= trunc_voxels)
+    track_min_count: int = 1       # a cell takes part in tracking when all its corners were seen this often
+    track_max_points: int = 16384  # cap on the points of a frame
+    track_motion: str = "velocity"   # "velocity" or "hold": how a frame's start pose is predicted
+    track_min_inlier_share: float = 0.5   # a tracked frame below this share of inliers is lost
+    track_max_lost: int = 3        # consecutive lost frames allowed
 
     @property
     def trunc_mm(self) -> float:
@@ -68,6 +82,23 @@ def check_opts(o: ReconstructOpts) -> ReconstructOpts:
         b = np.asarray(o.bounds, np.float64)
         if b.shape != (2, 3) or not np.all(np.isfinite(b)) or not np.all(b[1] > b[0]):
             raise ValueError(f"bounds must be ((x0, y0, z0), (x1, y1, z1)) with every x1 > x0, got {o.bounds!r}")
+    if o.pose_source not in ("given", "track"):
+        raise ValueError(f"pose_source must be 'given' or 'track', got {o.pose_source!r}")
+    if o.track_motion not in ("velocity", "hold"):
+        raise ValueError(f"track_motion must be 'velocity' or 'hold', got {o.track_motion!r}")
+    for name, low, high in (("track_anchor_every", 0, None), ("track_iters", 0, 1000), ("track_min_count", 1, None), ("track_max_points", 1, None),
+                            ("track_max_lost", 0, None)):
+        v = getattr(o, name)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or v < low or (high is not None and v > high):
+            raise ValueError(f"{name} must be an integer >= {low}" + (f" and <= {high}" if high is not None else "") + f", got {v!r}")
+    v = o.track_max_dist_voxels
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and v > 0):
+        raise ValueError(f"track_max_dist_voxels must be finite and > 0, got {v!r}")
+    if v > o.trunc_voxels:
+        raise ValueError(f"track_max_dist_voxels {v!r} exceeds trunc_voxels {o.trunc_voxels!r}: beyond the truncation distance the volume holds no distance")
+    v = o.track_min_inlier_share
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v <= 1:
+        raise ValueError(f"track_min_inlier_share must lie in [0, 1], got {v!r}")
     return o
 
 
@@ -161,6 +192,73 @@ def read_sequence(scene_dir: str, obj_id: int, mask_dir: str) -> List[Frame]:
     return frames
 
 
+def read_sequence_tracked(scene_dir: str, obj_id: int, mask_dir: str) -> Tuple[List[Frame], List[Optional[np.ndarray]], List[int]]:
+    """Track mode's reader: every image of scene_camera.json, in order -> (frames, given, image ids).  given[k] is the pose of the
+    image's first scene_gt.json entry that shows obj_id, or None (Frame.pose is then NaN); the mask is <im>_<gt index>.png when that
+    entry exists, else <im>_000000.png.  read_sequence is left as it is."""
+    from PIL import Image
+
+    from .eval_bop19 import load_depth
+    gt_path = os.path.join(scene_dir, "scene_gt.json")
+    gts = {int(k): v for k, v in _read_json(gt_path).items()} if os.path.exists(gt_path) else {}
+    cams = {int(k): v for k, v in _read_json(os.path.join(scene_dir, "scene_camera.json")).items()}
+    frames, given, ims = [], [], []
+    for im in sorted(cams):
+        if "depth_scale" not in cams[im]:
+            raise ValueError(f"{scene_dir}: image {im} has no depth_scale in scene_camera.json")
+        hit = next(((g, e) for g, e in enumerate(gts.get(im, [])) if int(e["obj_id"]) == int(obj_id)), None)
+        K = np.asarray(cams[im]["cam_K"], np.float64).reshape(3, 3)
+        depth = load_depth(os.path.join(scene_dir, "depth", f"{im:06d}.png"), float(cams[im]["depth_scale"]))
+        rgb_path = next((p for p in (os.path.join(scene_dir, "rgb", f"{im:06d}.{x}") for x in ("png", "jpg")) if os.path.exists(p)), None)
+        if rgb_path is None:
+            raise FileNotFoundError(f"{scene_dir}: no rgb/{im:06d}.png or .jpg")
+        with Image.open(rgb_path) as pic:
+            rgb = np.array(pic.convert("RGB"), np.uint8, order="C")
+        with Image.open(os.path.join(scene_dir, mask_dir, f"{im:06d}_{hit[0] if hit else 0:06d}.png")) as pic:
+            mask = np.array(pic.convert("L"), np.uint8, order="C")
+        if not (depth.shape == mask.shape == rgb.shape[:2]):
+            raise ValueError(f"{scene_dir}: image {im}: depth {depth.shape}, mask {mask.shape} and rgb {rgb.shape[:2]} differ in size")
+        pose = None if hit is None else np.concatenate([np.asarray(hit[1]["cam_R_m2c"], np.float64).reshape(9),
+                                                        np.asarray(hit[1]["cam_t_m2c"], np.float64).reshape(3)])
+        frames.append(Frame(depth, mask, rgb, (K[0, 0], K[1, 1], K[0, 2], K[1, 2]), np.full(12, np.nan) if pose is None else pose))
+        given.append(pose)
+        ims.append(im)
+    return frames, given, ims
+
+
+def predict_pose(history: Sequence[Tuple[int, np.ndarray]], index: int, motion: str) -> np.ndarray:
+    """The start pose (4 x 4, fp64, on the host) of frame `index` of a sequence from `history` = [(frame index, T)] of its kept frames:
+    "hold" is the last kept pose; "velocity" is T1 T2^-1 T1 of the two frames before it when both were kept, R re-orthonormalised by
+    SVD, and "hold" otherwise (before two poses exist, and after a lost frame)."""
+    T1 = history[-1][1]
+    if motion == "velocity" and len(history) >= 2 and history[-1][0] == index - 1 and history[-2][0] == index - 2:
+        T = T1 @ np.linalg.inv(history[-2][1]) @ T1
+        U, _, Vt = np.linalg.svd(T[:3, :3])
+        T[:3, :3] = U @ np.diag([1.0, 1.0, np.linalg.det(U @ Vt)]) @ Vt
+        T[3] = (0.0, 0.0, 0.0, 1.0)
+        return T
+    return T1.copy()
+
+
+def anchor_box_hint(frames: Sequence[Frame], given: Sequence[Optional[np.ndarray]]) -> str:
+    """The box of the masked depth points of the frames with a pose, in the model frame (numpy, on the host: a hint for opts.bounds)."""
+    lo, hi = np.full(3, np.inf), np.full(3, -np.inf)
+    for f, p in zip(frames, given):
+        if p is None:
+            continue
+        v, u = np.nonzero((f.mask != 0) & (f.depth > 0))
+        if not len(u):
+            continue
+        d = f.depth[v, u].astype(np.float64)
+        xc = np.stack([(u - f.cam[2]) / f.cam[0] * d, (v - f.cam[3]) / f.cam[1] * d, d], 1)
+        xm = (xc - p[9:]) @ p[:9].reshape(3, 3)
+        lo, hi = np.minimum(lo, xm.min(0)), np.maximum(hi, xm.max(0))
+    if not np.all(np.isfinite(lo)):
+        return "no frame with a pose has a masked depth pixel"
+    return (f"the masked depth points of the frames with a pose span {np.round(lo, 1).tolist()} .. {np.round(hi, 1).tolist()} mm in the model frame: "
+            "start from that box and leave room for the side of the object those frames do not see")
+
+
 # ---------------------------------------------------------------------------------------------------------- device work
 def _batches(frames: Sequence[Frame], step: int):
     """Consecutive frames of one image size, `step` at most: the order of the frames is the order of the sums."""
@@ -236,6 +334,114 @@ def fuse(frames: Sequence[Frame], opts=None, device="cuda") -> Dict[str, Any]:
     return vol
 
 
+def _lift(depth, mask, cam, max_points: int):
+    """depth fp32 [H, W], mask uint8 [H, W] on the device -> fp32 [P, 3] camera-frame points (lift_points' rule)."""
+    import torch
+    W = depth.shape[1]
+    sel = ((mask != 0) & (depth > 0)).reshape(-1).nonzero()[:, 0]               # row-major order
+    step = max(1, -(-int(sel.numel()) // int(max_points)))
+    sel = sel[::step]
+    u, v = (sel % W).double(), torch.div(sel, W, rounding_mode="floor").double()
+    d = depth.reshape(-1)[sel].double()
+    fx, fy, cx, cy = (float(c) for c in cam)
+    return torch.stack([(u - cx) / fx * d, (v - cy) / fy * d, d], 1).float().contiguous()
+
+
+def lift_points(frame: Frame, max_points: int, device="cuda"):
+    """The camera-frame points a frame is tracked with, fp32 [P, 3] on the device: the pixels with mask != 0 and depth > 0 in row-major
+    order, every ceil(n / max_points)-th of them, X_c = ((u - cx) / fx d, (v - cy) / fy d, d) in fp64 rounded to fp32; pixel centres
+    lie at integers, as in masked_point_percentiles."""
+    import torch
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(device)   # noqa: E731
+    return _lift(up(frame.depth, np.float32), up(frame.mask, np.uint8), frame.cam, max_points)
+
+
+def fuse_tracked(frames: Sequence[Frame], given: Sequence[Optional[np.ndarray]], opts=None, device="cuda", sequence: Optional[Sequence[int]] = None):
+    """Track mode's fusion (DESIGN.md section 30): the frames go through one at a time, in order.  given[k] is a 12-vector pose or None;
+    sequence[k] names the sequence a frame belongs to (None: one sequence), and the first frame of every sequence must have a pose.
+    An anchor -- the first frame of a sequence and, with track_anchor_every = N > 0, every Nth frame of it that has a pose -- is
+    integrated at its given pose.  Any other frame is tracked (ops.tsdf_track) against the volume of the frames before it, from the start
+    pose predict_pose gives, scored by one more evaluation at the result, and integrated at the tracked pose -- or lost: not
+    integrated, and the next frame starts from the last kept pose.  More than track_max_lost lost frames in a row raise RuntimeError.
+    -> (volume, poses: a 12-vector or None (lost) per frame, records: one dict per frame)."""
+    import torch
+
+    from . import ops
+    opts = load_opts(opts)
+    if not frames:
+        raise ValueError("no frame to fuse")
+    if len(given) != len(frames) or (sequence is not None and len(sequence) != len(frames)):
+        raise ValueError(f"{len(frames)} frames, {len(given)} given poses" + ("" if sequence is None else f", {len(sequence)} sequence ids"))
+    sequence = [0] * len(frames) if sequence is None else list(sequence)
+    first: Dict[Any, int] = {}
+    for k, s in enumerate(sequence):
+        if s not in first:
+            first[s] = k
+            if given[k] is None:
+                raise ValueError(f"frame {k}, the first of sequence {s}, has no pose: tracking starts from one known pose per sequence")
+    if opts.bounds is None:
+        raise ValueError("pose_source 'track' needs opts.bounds: the poses do not exist before fusion, so the volume cannot be chosen from them; "
+                         + anchor_box_hint(frames, given))
+    origin, dims = choose_volume(frames, opts, device)
+    vol = ops.tsdf_new_volume(origin, opts.voxel_mm, dims, device)
+    tau, md = opts.trunc_mm, float(opts.track_max_dist_voxels) * float(opts.voxel_mm)
+    zero = torch.zeros(1, dtype=torch.int32, device=device)
+    poses: List[Optional[np.ndarray]] = []
+    records: List[Dict[str, Any]] = []
+    history: List[Tuple[int, np.ndarray]] = []
+    lost_run = 0
+    for k, fr in enumerate(frames):
+        if first[sequence[k]] == k:
+            history = []
+        idx = k - first[sequence[k]]
+        depth, mask, rgb = _upload([fr], device)
+        rec: Dict[str, Any] = {"frame": k, "sequence": sequence[k]}
+        if idx == 0 or (opts.track_anchor_every > 0 and idx % opts.track_anchor_every == 0 and given[k] is not None):
+            pose, lost_run = np.asarray(given[k], np.float64).reshape(12), 0
+            rec["role"] = "anchor"
+        else:
+            t_start = time.perf_counter()
+            T0 = predict_pose(history, idx, opts.track_motion)
+            pts = _lift(depth[0], mask[0], fr.cam, opts.track_max_points)
+            n = int(pts.shape[0])
+            end = torch.full((1,), n, dtype=torch.int32, device=device)
+            if n > 0:
+                run = lambda R, t, iters: ops.tsdf_track(vol, pts, zero, end, R, t, md, int(opts.track_min_count), tau, iters)   # noqa: E731
+                out = run(torch.from_numpy(T0[:3, :3].copy()).to(device), torch.from_numpy(T0[:3, 3].copy()).to(device), int(opts.track_iters))
+                at = run(out["R"], out["t"], 0)                                 # the inliers and the cost at the result
+                o = {key: v.cpu().numpy()[0] for key, v in out.items()}
+                inl, cost = int(at["num_points"].cpu()[0]), float(at["cost_out"].cpu()[0])
+                share = inl / n
+                rms = math.sqrt(max(cost * n - (n - inl) * md * md, 0.0) / inl) if inl else 0.0   # cost n = sum r^2 over inliers + md^2 per other point
+            else:
+                o = {"R": T0[:3, :3], "t": T0[:3, 3], "cost_in": 0.0, "cost_out": 0.0, "num_points": 0, "iters_used": 0, "status": 2}
+                inl, share, rms = 0, 0.0, 0.0
+            kept = share >= opts.track_min_inlier_share and int(o["status"]) != 2
+            rec["seconds"] = time.perf_counter() - t_start                      # lifting, both calls and the read-back that waits for them
+            rec.update(role="tracked" if kept else "lost", start=np.concatenate([T0[:3, :3].reshape(9), T0[:3, 3]]).tolist(), points=n, inliers_in=int(o["num_points"]), inliers_out=inl, share=share, rms=rms,
+                       cost_in=float(o["cost_in"]), cost_out=float(o["cost_out"]), iters=int(o["iters_used"]), status=int(o["status"]))
+            pose = np.concatenate([np.asarray(o["R"], np.float64).reshape(9), np.asarray(o["t"], np.float64).reshape(3)]) if kept else None
+            if kept:
+                lost_run = 0
+            else:
+                lost_run += 1
+                if lost_run > opts.track_max_lost:
+                    raise RuntimeError(f"frame {k} (sequence {sequence[k]}): tracking lost on more than track_max_lost = {opts.track_max_lost} "
+                                       f"consecutive frames (inlier share {share:.2f}, status {int(o['status'])})")
+            if pose is not None and given[k] is not None:
+                g = np.asarray(given[k], np.float64).reshape(12)
+                c = (np.trace(pose[:9].reshape(3, 3).T @ g[:9].reshape(3, 3)) - 1.0) / 2.0
+                rec.update(rot_err_deg=float(np.degrees(np.arccos(np.clip(c, -1.0, 1.0)))), t_err_mm=float(np.linalg.norm(pose[9:] - g[9:])))
+        records.append(rec)
+        poses.append(pose)
+        if pose is not None:
+            ops.tsdf_integrate(vol, depth, mask, rgb, np.array([fr.cam], np.float64), pose[None], tau)
+            T = np.eye(4)
+            T[:3, :3], T[:3, 3] = pose[:9].reshape(3, 3), pose[9:]
+            history.append((idx, T))
+    return vol, poses, records
+
+
 def extract_mesh(volume: Dict[str, Any], opts=None):
     """The surface of a fused volume -> renderer.Mesh.  Triangle corners are welded on the device by their edge keys (torch.unique: the
     sorted key order is the vertex order), triangles whose three welded positions are not pairwise distinct are dropped, with
@@ -270,27 +476,58 @@ def extract_mesh(volume: Dict[str, Any], opts=None):
 
 
 def reconstruct(sequences: Sequence[str], obj_id: int, output_dir: str, opts=None, report_path: Optional[str] = None, overwrite: bool = False,
-                device: str = "cuda") -> Dict[str, Any]:
-    """Reads the sequences, fuses, extracts and writes <output_dir>/obj_%06d.ply (and the report) -> the report."""
+                device: str = "cuda", tracked_poses_dir: Optional[str] = None) -> Dict[str, Any]:
+    """Reads the sequences, fuses, extracts and writes <output_dir>/obj_%06d.ply (and the report) -> the report.  With
+    opts.pose_source "track" the frames are tracked (fuse_tracked), the report gains "tracking", and tracked_poses_dir, when given,
+    receives per sequence k <k:06d>_scene_gt.json with this object's entry for every frame that was kept."""
     import torch
 
     from . import _lib
     from .renderer import save_ply
     t0 = time.perf_counter()
     opts = load_opts(opts)
+    track = opts.pose_source == "track"
+    if tracked_poses_dir and not track:
+        raise ValueError("tracked poses are written with pose_source 'track' only")
     out_path = os.path.join(output_dir, f"obj_{int(obj_id):06d}.ply")
-    refuse_existing([out_path] + ([report_path] if report_path else []), overwrite)
+    pose_paths = [os.path.join(tracked_poses_dir, f"{k:06d}_scene_gt.json") for k in range(len(sequences))] if tracked_poses_dir else []
+    refuse_existing([out_path] + ([report_path] if report_path else []) + pose_paths, overwrite)
     frames: List[Frame] = []
-    for sd in sequences:
-        got = read_sequence(sd, obj_id, opts.mask_dir)
-        if not got:
-            raise ValueError(f"{sd}: no frame shows object {obj_id}")
+    given: List[Optional[np.ndarray]] = []
+    seq_of: List[int] = []
+    images: List[int] = []
+    for k, sd in enumerate(sequences):
+        if track:
+            got, poses_k, ims = read_sequence_tracked(sd, obj_id, opts.mask_dir)
+            if not got:
+                raise ValueError(f"{sd}: scene_camera.json lists no image")
+            if poses_k[0] is None:
+                raise ValueError(f"{sd}: its first image does not show object {obj_id} in scene_gt.json: tracking starts from one known pose per sequence")
+            given += poses_k
+            seq_of += [k] * len(got)
+            images += ims
+        else:
+            got = read_sequence(sd, obj_id, opts.mask_dir)
+            if not got:
+                raise ValueError(f"{sd}: no frame shows object {obj_id}")
         frames += got
+    if track and opts.bounds is None:
+        fuse_tracked(frames, given, opts, device, seq_of)                       # raises: bounds are needed, with a hint
     t_read = time.perf_counter()
     _lib.lib()
     if not torch.cuda.is_available():
         raise _lib.FoundPoseNativeError("reconstruct runs on the MI355X only: no device is available and no CPU path exists")
-    vol = fuse(frames, opts, device)
+    tracking = None
+    if track:
+        vol, poses, records = fuse_tracked(frames, given, opts, device, seq_of)
+        torch.cuda.synchronize()
+        for rec, im in zip(records, images):
+            rec["image"] = im
+        roles = [r["role"] for r in records]
+        tracking = {"frames": records, "totals": {role: roles.count(role) for role in ("anchor", "tracked", "lost")},
+                    "seconds": float(sum(r.get("seconds", 0.0) for r in records))}
+    else:
+        vol = fuse(frames, opts, device)
     observed = int((vol["sdf_cnt"] >= opts.min_count).sum())
     torch.cuda.synchronize()
     t_fuse = time.perf_counter()
@@ -300,12 +537,22 @@ def reconstruct(sequences: Sequence[str], obj_id: int, output_dir: str, opts=Non
     save_ply(out_path, mesh)
     topo = mesh_topology(mesh.faces)
     lo = np.asarray(vol["origin"])
-    report = {"obj_id": int(obj_id), "output": out_path, "sequences": [os.path.abspath(s) for s in sequences], "frames_used": len(frames),
+    if tracking is not None and tracked_poses_dir:
+        os.makedirs(tracked_poses_dir, exist_ok=True)
+        for k, path in enumerate(pose_paths):                                    # scene_gt.json's format; lost frames are omitted
+            entries = {str(im): [{"cam_R_m2c": p[:9].tolist(), "cam_t_m2c": p[9:].tolist(), "obj_id": int(obj_id)}]
+                       for im, s, p in zip(images, seq_of, poses) if s == k and p is not None}
+            with open(path, "w") as f:
+                json.dump(entries, f)
+    used = len(frames) if tracking is None else tracking["totals"]["anchor"] + tracking["totals"]["tracked"]
+    report = {"obj_id": int(obj_id), "output": out_path, "sequences": [os.path.abspath(s) for s in sequences], "frames_used": used,
               "opts": opts._asdict(), "bounds": [lo.tolist(), (lo + np.asarray(vol["dims"]) * vol["voxel_mm"]).tolist()],
               "dims": list(vol["dims"]), "observed_voxels": observed, "vertices": int(len(mesh.vertices)), "triangles": int(len(mesh.faces)),
               **topo,
               "note": None if topo["watertight"] else "the surface is open where no frame saw it; nothing is filled",
               "seconds": {"read": t_read - t0, "fuse": t_fuse - t_read, "extract": t_mesh - t_fuse, "total": time.perf_counter() - t0}}
+    if tracking is not None:
+        report["tracking"] = tracking
     if report_path:
         with open(report_path, "w") as f:
             json.dump(report, f, indent=1)
@@ -321,8 +568,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--report", default=None, help="write the report to this JSON file")
     ap.add_argument("--overwrite", action="store_true", help="replace an existing output")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--tracked-poses", default=None, help="pose_source 'track': write <k:06d>_scene_gt.json per sequence k into this directory")
     a = ap.parse_args(argv)
-    r = reconstruct(a.sequence, a.obj_id, a.output, a.opts, a.report, a.overwrite, a.device)
+    r = reconstruct(a.sequence, a.obj_id, a.output, a.opts, a.report, a.overwrite, a.device, a.tracked_poses)
+    if "tracking" in r:
+        tot = r["tracking"]["totals"]
+        print(f"tracking: {tot['anchor']} anchor(s), {tot['tracked']} tracked, {tot['lost']} lost in {r['tracking']['seconds']:.2f} s")
     print(f"{r['output']}: {r['vertices']} vertices, {r['triangles']} triangles from {r['frames_used']} frame(s) in a volume of "
           f"{r['dims'][0]} x {r['dims'][1]} x {r['dims'][2]} voxels; {r['boundary_edges']} boundary edge(s), "
           f"{'watertight' if r['watertight'] else 'open: ' + str(r['note'])}; {r['seconds']['total']:.2f} s")

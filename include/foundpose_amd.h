@@ -1190,6 +1190,40 @@ int fp_depth_refine(const float* depth, int num_images, int H, int W, const int3
                     void* scratch, size_t scratch_bytes, double* R_out, double* t_out, double* cost_in, double* cost_out,
                     int32_t* num_points, int32_t* iters_used, int32_t* status, double* normal_eq, fp_stream_t stream);
 
+/* ---- frame-to-model tracking against a TSDF volume (reconstruct.py, pose_source "track"; DESIGN.md section 30;
+ *      tests/tsdf_track_ref.py restates it) ----
+ * Levenberg-Marquardt on the model -> camera pose of each of num_det independent problems against ONE volume of fp_tsdf_integrate:
+ * sdf_sum, sdf_cnt, box (HOST fp64 [4]) and nx, ny, nz as there, every dimension >= 2 as for extraction; min_count >= 1; trunc_mm the
+ * truncation distance tau the volume was built with, finite and > 0.  Device arrays:
+ *   points      fp32 [num_rows, 3]  camera-frame points (mm), e.g. a frame's masked depth pixels lifted through its camera
+ *   row_begin, row_end int32 [num_det]  a problem's rows [row_begin, row_end) of points, at most max_points; a range outside
+ *               [0, num_rows] or longer than max_points is never read: the call then returns FP_ERR_INVALID naming the problem (it waits
+ *               for the work queued on `stream` to learn this)
+ *   R_in, t_in  fp64 [num_det, 9], [num_det, 3]  the input pose, model -> camera (mm);  has_pose int32 [num_det]  0: skipped (status 2)
+ *   max_dist    fp64 [num_det]  the inlier distance (mm).  Not validated: a NaN or a value <= 0 leaves no inlier, so that problem is
+ *               skipped (status 2) with its pose untouched
+ * Per point X_c, fp64: d = X_c - t, X_m[i] = R[0][i] d0 + R[1][i] d1 + R[2][i] d2; per axis the grid coordinate g = (X_m - origin) / h
+ * - 0.5, i0 = floor(g), alpha = g - i0.  Measurable: g finite and 0 <= i0 <= n - 2 on every axis (decided in fp64 before any conversion
+ * or read; no voxel outside the volume is ever read) and all eight corners of the cell have sdf_cnt >= min_count (a point that is not
+ * measurable reads no sdf_sum).  A corner's value is f = (double)sdf_sum / (double)sdf_cnt; phi is the trilinear interpolant of the
+ * eight (x first, then y, then z), grad phi its exact gradient (per axis the four differences along it, bilinear over the other two
+ * axes, over h), r = trunc_mm phi (mm).  rho = r^2 for an inlier (measurable, |r| < max_dist), max_dist^2 otherwise (no gradient);
+ * cost = sum rho / (row_end - row_begin); with q = trunc_mm R grad phi the Jacobian row for the left-multiplied twist (rotation,
+ * translation) is [q x X_c | -q]; H, g over the inliers.  The LM loop, lambda schedule and stopping rules are fp_featuremetric_refine's,
+ * at most `iters` (0..1000) iterations, all enqueued at once.
+ * Outputs: those of fp_depth_refine -- R_out, t_out, cost_in, cost_out, num_points (inliers at the input pose), iters_used, status
+ * (0 refined, 1 no step accepted, 2 skipped: no pose, empty range or < 6 inliers at the input pose; for 1 and 2 the pose is the input
+ * bit for bit); normal_eq fp64 [num_det, 28] may be null: H (upper triangle, row-major), g, cost at the input pose.  cost_out <=
+ * cost_in always.  Deterministic and bit-identical across batch compositions; no float atomics.  A NULL pointer, a size or option
+ * outside its range or too little scratch: FP_ERR_INVALID, nothing written.  scratch: FP_TSDF_TRACK_SCRATCH_BYTES.  (Added without a
+ * change of FP_ABI_VERSION: no existing entry point changed.) */
+#define FP_TSDF_TRACK_SCRATCH_BYTES(num_det, max_points) FP_DEPTH_REFINE_SCRATCH_BYTES(num_det, max_points)
+int fp_tsdf_track(const float* sdf_sum, const int32_t* sdf_cnt, const double* box, int nx, int ny, int nz, int min_count, double trunc_mm,
+                  const float* points, int64_t num_rows, const int32_t* row_begin, const int32_t* row_end, const double* R_in,
+                  const double* t_in, const int32_t* has_pose, const double* max_dist, int num_det, int max_points, int iters,
+                  void* scratch, size_t scratch_bytes, double* R_out, double* t_out, double* cost_in, double* cost_out,
+                  int32_t* num_points, int32_t* iters_used, int32_t* status, double* normal_eq, fp_stream_t stream);
+
 /* ---- joint refinement on features and depth (tests/rgbd_refine_ref.py restates it) --------------------------
  * One Levenberg-Marquardt objective E = E_f + depth_weight E_d per detection.  The pose (R, t) is model -> FRAME camera (mm).
  *   map, strides, gh, gw, C, W, H, feature_cameras   the featuremetric call's map arguments: the projected feature map and the camera
