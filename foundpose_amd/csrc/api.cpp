@@ -1,6 +1,6 @@
 // C ABI of libfoundpose_amd.so (declared in include/foundpose_amd.h): argument checking, scratch carving
 // and kernel sequencing.  No device allocation, no global mutable state, no synchronisation except the table uploads of
-// fp_pose_errors, fp_vsd_counts, fp_gt_visibility, fp_depth_plane_fit, fp_depth_components and fp_tsdf_integrate (each waits for its own copy) and the range check read back by the three refinements (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine) and by fp_tsdf_track.
+// fp_pose_errors, fp_vsd_counts, fp_gt_visibility, fp_depth_plane_fit, fp_depth_components and fp_tsdf_integrate (each waits for its own copy) and the range check read back by the four Levenberg-Marquardt solvers (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine, fp_tsdf_track).
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -968,8 +968,8 @@ int fp_directed_hausdorff(const double* pts, int V, int query_stride, const doub
   return launch_pts_hausdorff(a, K, ST(stream));
 }
 
-// ------------------------------------------------------------------ the three pose refinements
-// the argument checks the refinements share; `f` / `d` / `depth_weight`: the feature map, the depth stack and the weight of the entries that have one
+// ------------------------------------------------------------------ the four Levenberg-Marquardt solvers: the three pose refinements, and fp_tsdf_track further down
+// the argument checks the solvers share; `f` / `d` / `depth_weight`: the feature map, the depth stack and the weight of the entries that have one
 static int refine_check(const char* fn, const RefineLmArgs& lm, const RefineMapArgs* f, const RefineDepthArgs* d, const double* depth_weight) {
   if (f) {
     FP_REQUIRE(f->gh >= 2 && f->gw >= 2, "%s: the feature map is %d x %d, at least 2 x 2 needed", fn, f->gh, f->gw);
@@ -1004,14 +1004,16 @@ static int refine_carve(const char* fn, RefineLmArgs& lm, void* scratch, size_t 
   return FP_OK;
 }
 
-// the one wait of a refinement call, after every iteration is enqueued: a bad bank row range or image index is reported here, never read
-static int refine_report(const char* fn, const RefineLmArgs& lm, int num_images, hipStream_t st) {
+// the one wait of a solver's call, after every iteration is enqueued: a bad row range or image index is reported here, never read.
+// `rows_fmt`: the caller's words for a bad row range
+static int refine_report(const char* fn, const RefineLmArgs& lm, int num_images, hipStream_t st,
+                         const char* rows_fmt = "%s: detection %d: bank rows outside [0, %lld) or more than max_points %d") {
   int32_t bad = 0;
   if (hipError_t e = hipMemcpyWithStream(&bad, lm.err, sizeof(int32_t), hipMemcpyDeviceToHost, st); e != hipSuccess) {
     fp_set_error("%s: status read: %s", fn, hipGetErrorString(e));
     return FP_ERR_HIP;
   }
-  FP_REQUIRE(bad <= 0, "%s: detection %d: bank rows outside [0, %lld) or more than max_points %d", fn, bad - 1, lm.num_rows, lm.max_points);
+  FP_REQUIRE(bad <= 0, rows_fmt, fn, bad - 1, lm.num_rows, lm.max_points);
   FP_REQUIRE(bad == 0, "%s: detection %d: image index outside [0, %d)", fn, -bad - 1, num_images);
   return FP_OK;
 }
@@ -1298,11 +1300,8 @@ int fp_tsdf_track(const float* sdf_sum, const int32_t* sdf_cnt, const double* bo
   a.state = static_cast<RefineState*>(scratch);
   TRY(refine_carve(fn, a.lm, scratch, scratch_bytes, FP_TSDF_TRACK_SCRATCH_BYTES(num_det, max_points), FP_REFINE_RECORD, nullptr, ST(stream)));
   TRY(launch_tsdf_track(a, ST(stream)));
-  // the one wait of the call, after every iteration is enqueued: a bad row range is reported here, never read
-  int32_t bad = 0;
-  HIP_TRY(hipMemcpyWithStream(&bad, a.lm.err, sizeof(int32_t), hipMemcpyDeviceToHost, ST(stream)), "fp_tsdf_track: status read");
-  FP_REQUIRE(bad == 0, "fp_tsdf_track: problem %d: rows outside [0, %lld) or more than max_points %d", bad - 1, a.lm.num_rows, max_points);
-  return FP_OK;
+  // no image index: err is never negative here
+  return refine_report(fn, a.lm, 0, ST(stream), "%s: problem %d: rows outside [0, %lld) or more than max_points %d");
 }
 
 // ------------------------------------------------------------------ mask proposals from depth

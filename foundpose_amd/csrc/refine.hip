@@ -9,8 +9,9 @@
 //   refine_solve     one wave per detection: folds the partials in chunk order, then accepts / rejects the trial pose and
 //                    solves the damped 6x6 system for the next one (fp64 Cholesky)
 //   refine_finalize  one thread per detection: the outputs (lm_finalize)
-// The parts named in brackets, the fold and the accept / reject / propose steps of the solve live in refine_terms.hpp, shared with
-// depth_refine.hip and rgbd_refine.hip; this file keeps the reduction of its pass, the sigma stage and its unnormalised H, g, E.
+// The parts named in brackets, the fold, the sigma stage (lm_sigma), the accept / reject / propose steps of the solve and the order of
+// the launches (lm_enqueue) live in refine_terms.hpp, shared with depth_refine.hip, rgbd_refine.hip and tsdf_track.hip; this file keeps
+// the reduction of its pass and its unnormalised H, g, E.
 // The pass/solve pair runs `iters` times.  Detections that have stopped leave both kernels at their first instruction.
 // Every sum has a fixed order (lanes: butterfly; waves: 0..3; chunks: ascending), no atomics, and a detection's chunk
 // decomposition depends only on its own point count: results are bit-identical across runs and batch compositions.
@@ -72,11 +73,8 @@ __global__ void __launch_bounds__(64) refine_solve_kernel(RefineArgs a, int mode
   lm_fold(a.lm, b, s.np, RF_REC, threadIdx.x, tot);
   if (threadIdx.x != 0) return;
   if (mode == SOLVE_SIGMA) {
-    s.nvalid = (int)tot[29];
-    if (s.nvalid < 6) { lm_stop(s); return; }
-    s.skipped = 0;
-    s.sigma2 = fmax(tot[28] / s.nvalid, 1e-12);
-    return;   // pending stays 1: the next pass evaluates the input pose
+    lm_sigma(s, tot);
+    return;
   }
   s.pending = 0;
   const double Et = tot[27];
@@ -103,25 +101,9 @@ __global__ void __launch_bounds__(64) refine_finalize_kernel(RefineArgs a) {
 }  // namespace
 
 int launch_featuremetric_refine(const RefineArgs& a, hipStream_t st) {
-  const dim3 pgrid(a.lm.chunks, a.lm.num_det), sgrid(a.lm.num_det);
-  const int tgrid = cdiv(a.lm.num_det, 64);
-  hipLaunchKernelGGL(refine_setup_kernel, dim3(tgrid), dim3(64), 0, st, a);
-  FP_CHECK_LAUNCH("refine_setup");
-  hipLaunchKernelGGL(refine_pass_kernel, pgrid, dim3(64 * RF_WAVES), 0, st, a, (int)MODE_INIT);
-  FP_CHECK_LAUNCH("refine_pass");
-  hipLaunchKernelGGL(refine_solve_kernel, sgrid, dim3(64), 0, st, a, (int)SOLVE_SIGMA);
-  FP_CHECK_LAUNCH("refine_solve");
-  hipLaunchKernelGGL(refine_pass_kernel, pgrid, dim3(64 * RF_WAVES), 0, st, a, (int)MODE_EVAL);
-  FP_CHECK_LAUNCH("refine_pass");
-  hipLaunchKernelGGL(refine_solve_kernel, sgrid, dim3(64), 0, st, a, (int)SOLVE_FIRST);
-  FP_CHECK_LAUNCH("refine_solve");
-  for (int k = 0; k < a.lm.iters; ++k) {
-    hipLaunchKernelGGL(refine_pass_kernel, pgrid, dim3(64 * RF_WAVES), 0, st, a, (int)MODE_EVAL);
-    FP_CHECK_LAUNCH("refine_pass");
-    hipLaunchKernelGGL(refine_solve_kernel, sgrid, dim3(64), 0, st, a, (int)SOLVE_STEP);
-    FP_CHECK_LAUNCH("refine_solve");
-  }
-  hipLaunchKernelGGL(refine_finalize_kernel, dim3(tgrid), dim3(64), 0, st, a);
-  FP_CHECK_LAUNCH("refine_finalize");
-  return FP_OK;
+  return lm_enqueue(a.lm, 64 * RF_WAVES, true,   // with the sigma stage
+                    [&](dim3 g, dim3 blk) { return lm_launch("refine_setup", refine_setup_kernel, g, blk, st, a); },
+                    [&](dim3 g, dim3 blk, int mode) { return lm_launch("refine_pass", refine_pass_kernel, g, blk, st, a, mode); },
+                    [&](dim3 g, dim3 blk, int mode) { return lm_launch("refine_solve", refine_solve_kernel, g, blk, st, a, mode); },
+                    [&](dim3 g, dim3 blk) { return lm_launch("refine_finalize", refine_finalize_kernel, g, blk, st, a); });
 }

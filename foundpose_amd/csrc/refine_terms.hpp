@@ -1,9 +1,13 @@
-// The parts shared by the three Levenberg-Marquardt pose refinements (refine.hip, depth_refine.hip, rgbd_refine.hip; DESIGN.md
-// sections 11, 14 and 15): state initialisation and row claim, the outputs, the fold of the partial records, the damped 6x6 solve, the
-// proposal / acceptance / rejection of a trial pose on a RefineState, and the two per-point terms -- features and depth -- of the passes.
-// What differs between the refiners (the camera of the feature term, its cost slot, the tap-spread test, each pass's reduction, each
-// solve's normalisation and stopping rule) is a template parameter here or stays in the caller.
-// The functions are defined here, at global scope, without `static`: that is safe only because FP_DEVICE is
+// The parts shared by the four Levenberg-Marquardt solvers -- the three pose refinements (refine.hip, depth_refine.hip, rgbd_refine.hip;
+// DESIGN.md sections 11, 14 and 15) and the frame-to-model tracker (tsdf_track.hip; section 30): state initialisation and row claim, the
+// outputs, the fold of the partial records, the damped 6x6 solve, the proposal / acceptance / rejection of a trial pose on a RefineState,
+// the sigma stage of the two feature solves, the whole one-point-per-lane pass and its solve (depth_refine.hip and tsdf_track.hip: only
+// the per-point term differs), the two per-point terms -- features and depth -- of the refiners' passes, and, on the host, the order in
+// which a call enqueues its kernels.
+// What differs between the solvers (the camera of the feature term, its cost slot, the tap-spread test, the reduction of a feature
+// pass, the normalisation and stopping rule of a feature solve, the tracker's per-point term and its rule for a failed call) is a
+// template parameter here or stays in the caller.
+// The device functions are defined here, at global scope, without `static`: that is safe only because FP_DEVICE is
 // __device__ __forceinline__ (every use is inlined, no symbol is emitted twice).  Keep them FP_DEVICE.
 // Every floating-point statement stands as one source expression: the library is built with -ffp-contract=on, so splitting or merging
 // one changes which multiplies fuse with which adds, and with that the output bits.
@@ -151,6 +155,82 @@ FP_DEVICE void lm_reject(RefineState& s, int iters) {
   s.lam *= 10.0;
   if (s.lam > 1e12) { lm_stop(s); return; }
   lm_propose(s, iters);
+}
+
+// the sigma stage of a feature solve (SOLVE_SIGMA, lane 0): tot = the fold of a MODE_INIT pass, sum s [28] over the valid points [29]
+FP_DEVICE void lm_sigma(RefineState& s, const double* tot) {
+  s.nvalid = (int)tot[29];
+  if (s.nvalid < 6) { lm_stop(s); return; }
+  s.skipped = 0;
+  s.sigma2 = fmax(tot[28] / s.nvalid, 1e-12);
+  // pending stays 1: the next pass evaluates the input pose
+}
+
+// ---- one point per lane (depth_refine.hip, tsdf_track.hip): the pass, one wave per (chunk, problem) = (blockIdx.x, b), and its solve,
+// one wave per problem.  The record is FP_REFINE_RECORD doubles: H (21, upper triangle row-major), g (6), sum rho [27], pad, inliers [29],
+// pad.  The cost is normalised by the point count, a problem with fewer than 6 inliers at the input pose stops (there is no z-bad count:
+// a point that cannot be measured is an outlier like any other).
+static_assert(FP_REFINE_CHUNK == 32, "one half-wave per chunk");
+// point(R, t, Xv, acc) is the caller's term: acc arrives zeroed and leaves with the point's FP_DEPTH_TERMS values (see depth_point).
+// A chunk is FP_REFINE_CHUNK = 32 points, so lanes 32..63 of the wave idle by construction.  A 64-point chunk would fill the wave, but
+// FP_REFINE_CHUNK is shared with the feature passes (scratch layout, chunk order of their sums, lm_fold): changing it changes the
+// output bits of all four solvers.  At these sizes a call is bound by its launches, not by the pass.
+template <class Point>
+FP_DEVICE void lm_lane_pass(const RefineLmArgs& a, const RefineState& s, int b, Point point) {
+  if (!s.active || !s.pending) return;
+  const int np = s.np, chunk0 = blockIdx.x * FP_REFINE_CHUNK;
+  if (chunk0 >= np) return;
+  const int lane = threadIdx.x;
+  const int p = chunk0 + lane;
+  double acc[FP_DEPTH_TERMS];
+#pragma unroll
+  for (int k = 0; k < FP_DEPTH_TERMS; ++k) acc[k] = 0.0;
+  if (lane < FP_REFINE_CHUNK && p < np) point(s.Rt, s.tt, a.verts + 3 * ((long long)s.p0 + p), acc);
+  // lanes 32..63 carry zeros and fold among themselves: lane 0 ends with the sum of lanes 0..31 in butterfly order
+#pragma unroll
+  for (int k = 0; k < FP_DEPTH_TERMS; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int o = FP_REFINE_CHUNK / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    acc[k] = v;
+  }
+  if (lane == 0) {
+    double* out = a.part + ((long long)b * a.chunks + blockIdx.x) * FP_REFINE_RECORD;
+#pragma unroll
+    for (int k = 0; k < 28; ++k) out[k] = acc[k];
+    out[28] = 0.0;
+    out[29] = acc[28];
+    out[30] = out[31] = 0.0;
+  }
+}
+
+// tot: FP_REFINE_RECORD doubles of LDS; every thread of the workgroup calls it
+FP_DEVICE void lm_lane_solve(const RefineLmArgs& a, RefineState& s, int b, int mode, double* tot) {
+  if (!s.active || !s.pending) return;
+  lm_fold(a, b, s.np, FP_REFINE_RECORD, threadIdx.x, tot);
+  if (threadIdx.x != 0) return;
+  s.pending = 0;
+  const double Et = tot[27] / s.np;   // the point set is every row of the range: costs at different poses are comparable
+  if (mode == SOLVE_STEP && !(Et < s.E)) {
+    lm_reject(s, a.iters);
+    return;
+  }
+  if (mode == SOLVE_FIRST) {
+    s.E = s.E_in = Et;
+    s.nvalid = (int)tot[29];
+    if (a.normal_eq) {
+      for (int i = 0; i < 27; ++i) a.normal_eq[28 * b + i] = tot[i];
+      a.normal_eq[28 * b + 27] = Et;
+    }
+  } else if (!lm_accept(s, Et)) {
+    return;
+  }
+  lm_set_system(s, tot);
+  if (mode == SOLVE_FIRST) {
+    if (s.nvalid < 6) { lm_stop(s); return; }
+    s.skipped = 0;
+  }
+  lm_propose(s, a.iters);
 }
 
 // ---- the feature term of one point (sections 11 and 15), run by a whole wave: the 64 lanes split the channels, every lane carries the
@@ -303,4 +383,32 @@ FP_DEVICE void depth_point(const RefineDepthArgs& a, const double* cam, int b, c
     }
   }
   acc[27] = rho;
+}
+
+// ---- the host side: what a call enqueues, without a round trip between the launches
+// one launch under the name its failure is reported by; `mode` goes to the kernels that take one
+template <class Args, class... Mode>
+int lm_launch(const char* name, void (*kernel)(Args, Mode...), dim3 grid, dim3 block, hipStream_t st, const Args& a, Mode... mode) {
+  hipLaunchKernelGGL(kernel, grid, block, 0, st, a, mode...);
+  FP_CHECK_LAUNCH(name);
+  return FP_OK;
+}
+// setup, [init pass, sigma solve,] pass, first solve, iters x (pass, step solve), finalize: 3 + 2 iters + 1 launches, 5 + 2 iters + 1 with
+// the sigma stage.  setup / finalize (grid, block) run one thread per problem, pass (grid, block, mode) a workgroup of pass_block threads
+// per (chunk, problem), solve (grid, block, mode) one wave per problem; each returns its lm_launch.
+template <class Setup, class Pass, class Solve, class Finalize>
+int lm_enqueue(const RefineLmArgs& lm, int pass_block, bool sigma, Setup setup, Pass pass, Solve solve, Finalize finalize) {
+  const dim3 pgrid(lm.chunks, lm.num_det), sgrid(lm.num_det), tgrid(cdiv(lm.num_det, 64)), wave(64), pblock(pass_block);
+  if (int rc = setup(tgrid, wave)) return rc;
+  if (sigma) {
+    if (int rc = pass(pgrid, pblock, (int)MODE_INIT)) return rc;
+    if (int rc = solve(sgrid, wave, (int)SOLVE_SIGMA)) return rc;
+  }
+  if (int rc = pass(pgrid, pblock, (int)MODE_EVAL)) return rc;
+  if (int rc = solve(sgrid, wave, (int)SOLVE_FIRST)) return rc;
+  for (int k = 0; k < lm.iters; ++k) {
+    if (int rc = pass(pgrid, pblock, (int)MODE_EVAL)) return rc;
+    if (int rc = solve(sgrid, wave, (int)SOLVE_STEP)) return rc;
+  }
+  return finalize(tgrid, wave);
 }

@@ -13,9 +13,10 @@
 //   rgbd_solve     one wave per detection: folds the partials in chunk order, mixes the halves with 1 / (|V| sigma^2) and
 //                  w_d / (N tau^2), accepts / rejects the trial pose and solves for the next one
 //   rgbd_finalize  one thread per detection: the outputs (lm_finalize, and the depth inliers)
-// The parts named in brackets, the fold and the accept / reject / propose steps of the solve live in refine_terms.hpp, shared with
-// refine.hip and depth_refine.hip; this file keeps the (A, a) camera of its feature term, the tap-spread test, the LDS rows of its
-// depth reduction, the mixing of the two halves and the use_depth decision.
+// The parts named in brackets, the fold, the sigma stage (lm_sigma), the accept / reject / propose steps of the solve and the order of
+// the launches (lm_enqueue) live in refine_terms.hpp, shared with refine.hip, depth_refine.hip and tsdf_track.hip; this file keeps the
+// (A, a) camera of its feature term, the tap-spread test, the LDS rows of its depth reduction, the mixing of the two halves and the
+// use_depth decision.
 // 2 + 2 iters launches after the setup chain, as refine.hip alone.  Detections that have stopped leave pass and solve at their first
 // instruction.  Every sum has a fixed order (lanes: butterfly; points of a wave: ascending; waves: 0..3; the 32 depth rows of a chunk:
 // ascending; chunks: ascending), no atomics, and a detection's chunk decomposition depends only on its own point count: results are
@@ -112,11 +113,8 @@ __global__ void __launch_bounds__(64) rgbd_solve_kernel(RgbdRefineArgs a, int mo
   lm_fold(a.lm, b, s.np, RG_REC, threadIdx.x, tot);
   if (threadIdx.x != 0) return;
   if (mode == SOLVE_SIGMA) {
-    s.nvalid = (int)tot[29];
-    if (s.nvalid < 6) { lm_stop(s); return; }
-    s.skipped = 0;
-    s.sigma2 = fmax(tot[28] / s.nvalid, 1e-12);
-    return;   // pending stays 1: the next pass evaluates the input pose
+    lm_sigma(s, tot);
+    return;
   }
   s.pending = 0;
   const double* td = tot + RG_HALF;
@@ -161,25 +159,9 @@ __global__ void __launch_bounds__(64) rgbd_finalize_kernel(RgbdRefineArgs a) {
 }  // namespace
 
 int launch_rgbd_refine(const RgbdRefineArgs& a, hipStream_t st) {
-  const dim3 pgrid(a.lm.chunks, a.lm.num_det), sgrid(a.lm.num_det);
-  const int tgrid = cdiv(a.lm.num_det, 64);
-  hipLaunchKernelGGL(rgbd_setup_kernel, dim3(tgrid), dim3(64), 0, st, a);
-  FP_CHECK_LAUNCH("rgbd_setup");
-  hipLaunchKernelGGL(rgbd_pass_kernel, pgrid, dim3(64 * RG_WAVES), 0, st, a, (int)MODE_INIT);
-  FP_CHECK_LAUNCH("rgbd_pass");
-  hipLaunchKernelGGL(rgbd_solve_kernel, sgrid, dim3(64), 0, st, a, (int)SOLVE_SIGMA);
-  FP_CHECK_LAUNCH("rgbd_solve");
-  hipLaunchKernelGGL(rgbd_pass_kernel, pgrid, dim3(64 * RG_WAVES), 0, st, a, (int)MODE_EVAL);
-  FP_CHECK_LAUNCH("rgbd_pass");
-  hipLaunchKernelGGL(rgbd_solve_kernel, sgrid, dim3(64), 0, st, a, (int)SOLVE_FIRST);
-  FP_CHECK_LAUNCH("rgbd_solve");
-  for (int k = 0; k < a.lm.iters; ++k) {
-    hipLaunchKernelGGL(rgbd_pass_kernel, pgrid, dim3(64 * RG_WAVES), 0, st, a, (int)MODE_EVAL);
-    FP_CHECK_LAUNCH("rgbd_pass");
-    hipLaunchKernelGGL(rgbd_solve_kernel, sgrid, dim3(64), 0, st, a, (int)SOLVE_STEP);
-    FP_CHECK_LAUNCH("rgbd_solve");
-  }
-  hipLaunchKernelGGL(rgbd_finalize_kernel, dim3(tgrid), dim3(64), 0, st, a);
-  FP_CHECK_LAUNCH("rgbd_finalize");
-  return FP_OK;
+  return lm_enqueue(a.lm, 64 * RG_WAVES, true,   // with the sigma stage
+                    [&](dim3 g, dim3 blk) { return lm_launch("rgbd_setup", rgbd_setup_kernel, g, blk, st, a); },
+                    [&](dim3 g, dim3 blk, int mode) { return lm_launch("rgbd_pass", rgbd_pass_kernel, g, blk, st, a, mode); },
+                    [&](dim3 g, dim3 blk, int mode) { return lm_launch("rgbd_solve", rgbd_solve_kernel, g, blk, st, a, mode); },
+                    [&](dim3 g, dim3 blk) { return lm_launch("rgbd_finalize", rgbd_finalize_kernel, g, blk, st, a); });
 }

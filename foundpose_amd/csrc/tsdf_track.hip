@@ -8,24 +8,25 @@
 //   tsdf_track_pass      (chunk of FP_REFINE_CHUNK points, problem), one wave: ONE POINT PER LANE -- the point into the model frame, the
 //                        cell it falls into, eight sdf_cnt taps, then (only where all eight were seen min_count times) eight sdf_sum taps,
 //                        the sample, its gradient and the Jacobian row (fp64; track_point) -- then a butterfly over the chunk's lanes for
-//                        the 29 terms, one partial record per workgroup.  The two x-neighbours of a tap pair are adjacent in memory.
+//                        the 29 terms, one partial record per workgroup (lm_lane_pass).  The two x-neighbours of a tap pair are adjacent
+//                        in memory.
 //   tsdf_track_solve     one wave per problem: folds the partials in chunk order, accepts / rejects the trial pose, solves for the next
+//                        (lm_lane_solve)
 //   tsdf_track_finalize  one thread per problem: the outputs (lm_finalize)
 // A bad row range anywhere in the batch fails the whole call, as in the refiners; here the pass, the solve and the finalize then leave
 // at their first instruction, so that such a call writes none of its outputs.
-// The LM parts are refine_terms.hpp's, unchanged; the pass / solve skeleton is depth_refine.hip's (same record layout, same cost
-// normalisation, same stop on fewer than 6 inliers).  The per-point term stays in this file: refine_terms.hpp is compiled into the
-// three pose refiners, and their code is left as it is.  Every floating-point statement of the term stands as one source expression
-// (the library is built with -ffp-contract=on).  Every sum has a fixed order (lanes: butterfly; chunks: ascending), no atomics, and a
-// problem's chunk decomposition depends only on its own point count: results are bit-identical across runs and batch compositions.
+// The parts named in brackets and the order of the launches (lm_enqueue) live in refine_terms.hpp; the one-point-per-lane pass and its
+// solve are the ones depth_refine.hip runs (same record layout, same cost normalisation, same stop on fewer than 6 inliers).  This file
+// keeps what is the tracker's own: the per-point term, and the rule for a failed call -- the leading err test of its kernels, the
+// setup that hides normal_eq from lm_setup and the finalize that zeroes the rows no solve has written.  Every floating-point statement
+// of the term stands as one source expression (the library is built with -ffp-contract=on).  Every sum has a fixed order (lanes:
+// butterfly; chunks: ascending), no atomics, and a problem's chunk decomposition depends only on its own point count: results are
+// bit-identical across runs and batch compositions.
 #include "common.hpp"
 #include "kernels.hpp"
 #include "refine_terms.hpp"
 
 namespace {
-
-constexpr int TT_REC = FP_REFINE_RECORD;   // the partial record of depth_refine.hip: H (21), g (6), sum rho [27], pad, inliers [29], pad
-static_assert(FP_REFINE_CHUNK == 32, "one half-wave per chunk");
 
 // One camera-frame point Xv under the pose (R, t) against the volume.  acc arrives zeroed and leaves with the point's FP_DEPTH_TERMS
 // values: H (21), g (6), rho [27], the inlier flag [28].
@@ -90,69 +91,19 @@ __global__ void __launch_bounds__(64) tsdf_track_setup_kernel(TsdfTrackArgs a) {
   if (b < lm.num_det) lm_setup(lm, nullptr, a.state[b], b, 28);
 }
 
-// A chunk is FP_REFINE_CHUNK = 32 points (the chunk of the three refiners: lm_fold and the scratch layout are shared), so lanes 32..63
-// of the wave idle by construction, as in depth_refine_pass_kernel.
+// The leading test of the three kernels below: a bad row range somewhere in the batch (err, set by the setup a launch ago) fails the
+// call, and nothing is computed.
 __global__ void __launch_bounds__(64) tsdf_track_pass_kernel(TsdfTrackArgs a) {
-  if (a.lm.err[0] != 0) return;   // a bad row range somewhere in the batch (set by the setup, a launch ago): the call fails, nothing is computed
+  if (a.lm.err[0] != 0) return;
   const int b = blockIdx.y;
-  const RefineState& s = a.state[b];
-  if (!s.active || !s.pending) return;
-  const int np = s.np, chunk0 = blockIdx.x * FP_REFINE_CHUNK;
-  if (chunk0 >= np) return;
-  const int lane = threadIdx.x;
-  const int p = chunk0 + lane;
-  double acc[FP_DEPTH_TERMS];
-#pragma unroll
-  for (int k = 0; k < FP_DEPTH_TERMS; ++k) acc[k] = 0.0;
-  if (lane < FP_REFINE_CHUNK && p < np) track_point(a, b, s.Rt, s.tt, a.lm.verts + 3 * ((long long)s.p0 + p), acc);
-  // lanes 32..63 carry zeros and fold among themselves: lane 0 ends with the sum of lanes 0..31 in butterfly order
-#pragma unroll
-  for (int k = 0; k < FP_DEPTH_TERMS; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int o = FP_REFINE_CHUNK / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    acc[k] = v;
-  }
-  if (lane == 0) {
-    double* out = a.lm.part + ((long long)b * a.lm.chunks + blockIdx.x) * TT_REC;
-#pragma unroll
-    for (int k = 0; k < 28; ++k) out[k] = acc[k];
-    out[28] = 0.0;
-    out[29] = acc[28];
-    out[30] = out[31] = 0.0;
-  }
+  lm_lane_pass(a.lm, a.state[b], b,
+               [&](const double* R, const double* t, const float* Xv, double (&acc)[FP_DEPTH_TERMS]) { track_point(a, b, R, t, Xv, acc); });
 }
 
 __global__ void __launch_bounds__(64) tsdf_track_solve_kernel(TsdfTrackArgs a, int mode) {
-  __shared__ double tot[TT_REC];
+  __shared__ double tot[FP_REFINE_RECORD];
   if (a.lm.err[0] != 0) return;
-  const int b = blockIdx.x;
-  RefineState& s = a.state[b];
-  if (!s.active || !s.pending) return;
-  lm_fold(a.lm, b, s.np, TT_REC, threadIdx.x, tot);
-  if (threadIdx.x != 0) return;
-  s.pending = 0;
-  const double Et = tot[27] / s.np;   // the point set is every row of the range: costs at different poses are comparable
-  if (mode == SOLVE_STEP && !(Et < s.E)) {
-    lm_reject(s, a.lm.iters);
-    return;
-  }
-  if (mode == SOLVE_FIRST) {
-    s.E = s.E_in = Et;
-    s.nvalid = (int)tot[29];
-    if (a.lm.normal_eq) {
-      for (int i = 0; i < 27; ++i) a.lm.normal_eq[28 * b + i] = tot[i];
-      a.lm.normal_eq[28 * b + 27] = Et;
-    }
-  } else if (!lm_accept(s, Et)) {
-    return;
-  }
-  lm_set_system(s, tot);
-  if (mode == SOLVE_FIRST) {
-    if (s.nvalid < 6) { lm_stop(s); return; }
-    s.skipped = 0;
-  }
-  lm_propose(s, a.lm.iters);
+  lm_lane_solve(a.lm, a.state[blockIdx.x], blockIdx.x, mode, tot);
 }
 
 __global__ void __launch_bounds__(64) tsdf_track_finalize_kernel(TsdfTrackArgs a) {
@@ -166,21 +117,9 @@ __global__ void __launch_bounds__(64) tsdf_track_finalize_kernel(TsdfTrackArgs a
 }  // namespace
 
 int launch_tsdf_track(const TsdfTrackArgs& a, hipStream_t st) {
-  const dim3 pgrid(a.lm.chunks, a.lm.num_det), sgrid(a.lm.num_det);
-  const int tgrid = cdiv(a.lm.num_det, 64);
-  hipLaunchKernelGGL(tsdf_track_setup_kernel, dim3(tgrid), dim3(64), 0, st, a);
-  FP_CHECK_LAUNCH("tsdf_track_setup");
-  hipLaunchKernelGGL(tsdf_track_pass_kernel, pgrid, dim3(64), 0, st, a);
-  FP_CHECK_LAUNCH("tsdf_track_pass");
-  hipLaunchKernelGGL(tsdf_track_solve_kernel, sgrid, dim3(64), 0, st, a, (int)SOLVE_FIRST);
-  FP_CHECK_LAUNCH("tsdf_track_solve");
-  for (int k = 0; k < a.lm.iters; ++k) {
-    hipLaunchKernelGGL(tsdf_track_pass_kernel, pgrid, dim3(64), 0, st, a);
-    FP_CHECK_LAUNCH("tsdf_track_pass");
-    hipLaunchKernelGGL(tsdf_track_solve_kernel, sgrid, dim3(64), 0, st, a, (int)SOLVE_STEP);
-    FP_CHECK_LAUNCH("tsdf_track_solve");
-  }
-  hipLaunchKernelGGL(tsdf_track_finalize_kernel, dim3(tgrid), dim3(64), 0, st, a);
-  FP_CHECK_LAUNCH("tsdf_track_finalize");
-  return FP_OK;
+  return lm_enqueue(a.lm, 64, false,   // no sigma stage
+                    [&](dim3 g, dim3 blk) { return lm_launch("tsdf_track_setup", tsdf_track_setup_kernel, g, blk, st, a); },
+                    [&](dim3 g, dim3 blk, int) { return lm_launch("tsdf_track_pass", tsdf_track_pass_kernel, g, blk, st, a); },
+                    [&](dim3 g, dim3 blk, int mode) { return lm_launch("tsdf_track_solve", tsdf_track_solve_kernel, g, blk, st, a, mode); },
+                    [&](dim3 g, dim3 blk) { return lm_launch("tsdf_track_finalize", tsdf_track_finalize_kernel, g, blk, st, a); });
 }

@@ -4,7 +4,7 @@ torch is plumbing here (device memory + the current HIP stream); every computati
 hand-written gfx950 kernel behind include/foundpose_amd.h.
 """
 
-from typing import Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -644,6 +644,40 @@ def tsdf_extract(volume: dict, min_count: int) -> Tuple[torch.Tensor, torch.Tens
     return counts, keys, pos, col
 
 
+def _lm_inputs(B: int, R, t, row_begin, row_end, has_pose, feats, vertices, max_points: Optional[int]):
+    """The conversions every Levenberg-Marquardt solver (refine_util's three refiners, tsdf_track) makes, in the order they are enqueued, and
+    the max_points rule: None is read back from the device.
+    -> (R [B, 9] f64, t [B, 3] f64, row_begin, row_end, has_pose i32, feats f32 or None, vertices f32, max_points >= 1)."""
+    Rin = R.to(torch.float64).reshape(B, 9).contiguous()
+    tin = t.to(torch.float64).reshape(B, 3).contiguous()
+    rb = row_begin.to(torch.int32).contiguous()
+    re = row_end.to(torch.int32).contiguous()
+    hp = has_pose.to(torch.int32).contiguous()
+    f32 = None if feats is None else feats.float().contiguous()
+    v32 = vertices.float().contiguous()
+    if max_points is None:
+        max_points = int(torch.where(hp != 0, re - rb, torch.zeros_like(re)).max().item()) if B else 0
+    return Rin, tin, rb, re, hp, f32, v32, max(1, int(max_points))
+
+
+def _lm_outputs(B: int, dev, normal_eq_width: int, depth_inliers: bool = False) -> Tuple[Dict[str, torch.Tensor], list]:
+    """Allocates such a solver's outputs.  -> (the result dict, the output pointers in the order of the C ABI -- the dict's own, then normal_eq);
+    normal_eq_width 0: no normal equations."""
+    f64, i32, empty = torch.float64, torch.int32, torch.empty
+    out = {"R": empty(B, 9, dtype=f64, device=dev), "t": empty(B, 3, dtype=f64, device=dev), "cost_in": empty(B, dtype=f64, device=dev),
+           "cost_out": empty(B, dtype=f64, device=dev), "num_points": empty(B, dtype=i32, device=dev)}
+    if depth_inliers:
+        out["num_depth_inliers"] = empty(B, dtype=i32, device=dev)
+    out["iters_used"], out["status"] = empty(B, dtype=i32, device=dev), empty(B, dtype=i32, device=dev)
+    neq = empty(B, normal_eq_width, dtype=f64, device=dev) if normal_eq_width else None
+    ptrs = [ptr(v) for v in out.values()]
+    ptrs.append(ptr(neq))
+    out["R"] = out["R"].reshape(B, 3, 3)
+    if neq is not None:
+        out["normal_eq"] = neq
+    return out, ptrs
+
+
 def tsdf_track(volume: dict, points: torch.Tensor, row_begin: torch.Tensor, row_end: torch.Tensor, R: torch.Tensor, t: torch.Tensor, max_dist,
                min_count: int, trunc_mm: float, iters: int, has_pose: Optional[torch.Tensor] = None, want_normal_eq: bool = False) -> dict:
     """Tracks B independent problems against `volume` (fp_tsdf_track; DESIGN.md section 30): points fp32 [N, 3], camera-frame mm;
@@ -683,25 +717,15 @@ def tsdf_track(volume: dict, points: torch.Tensor, row_begin: torch.Tensor, row_
     if md.shape != (B,):
         raise ValueError(f"{fn}: max_dist is one number or one per problem, got {md.shape}")
     dev = points.device
-    p32 = points.float().contiguous()
-    Rin, tin = R.to(torch.float64).reshape(B, 9).contiguous(), t.to(torch.float64).reshape(B, 3).contiguous()
-    rb, re = row_begin.to(torch.int32).contiguous(), row_end.to(torch.int32).contiguous()
-    hp = torch.ones(B, dtype=torch.int32, device=dev) if has_pose is None else has_pose.to(torch.int32).contiguous()
+    hp = torch.ones(B, dtype=torch.int32, device=dev) if has_pose is None else has_pose
+    Rin, tin, rb, re, hp, _, p32, max_points = _lm_inputs(B, R, t, row_begin, row_end, hp, None, points, None)
     md_d = _lib.upload_async(torch.from_numpy(np.ascontiguousarray(md)), dev)
-    max_points = max(1, int(torch.where(hp != 0, re - rb, torch.zeros_like(re)).max().item()))
-    f64, i32, empty = torch.float64, torch.int32, torch.empty
-    out = {"R": empty(B, 9, dtype=f64, device=dev), "t": empty(B, 3, dtype=f64, device=dev), "cost_in": empty(B, dtype=f64, device=dev),
-           "cost_out": empty(B, dtype=f64, device=dev), "num_points": empty(B, dtype=i32, device=dev), "iters_used": empty(B, dtype=i32, device=dev),
-           "status": empty(B, dtype=i32, device=dev)}
-    neq = empty(B, 28, dtype=f64, device=dev) if want_normal_eq else None
+    out, outs = _lm_outputs(B, dev, 28 if want_normal_eq else 0)
     nbytes = _lib.tsdf_track_scratch_bytes(B, max_points)
-    scratch = empty(nbytes, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     call("fp_tsdf_track", ptr(volume["sdf_sum"]), ptr(volume["sdf_cnt"]), box.ctypes.data_as(_lib.vp), *dims, int(min_count), tau, ptr(p32),
          int(p32.shape[0]), ptr(rb), ptr(re), ptr(Rin), ptr(tin), ptr(hp), ptr(md_d), B, max_points, int(iters), ptr(scratch), nbytes,
-         *[ptr(v) for v in out.values()], ptr(neq), stream())
-    out["R"] = out["R"].reshape(B, 3, 3)
-    if neq is not None:
-        out["normal_eq"] = neq
+         *outs, stream())
     return out
 
 

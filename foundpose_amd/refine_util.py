@@ -18,6 +18,7 @@ import torch
 from ._lib import call, depth_refine_scratch_bytes, ptr, refine_scratch_bytes, require_cuda, rgbd_refine_scratch_bytes, stream, upload_async
 from .bank import DeviceBank
 from .matching import MatchResult
+from .ops import _lm_inputs, _lm_outputs
 from .pnp_util import _intrinsics
 
 STATUS_REFINED, STATUS_NOT_IMPROVED, STATUS_SKIPPED = 0, 1, 2
@@ -55,39 +56,6 @@ def _tau_per_detection(tau, B: int) -> torch.Tensor:
 
 def _upload_cameras(cameras: Sequence[Any], B: int, dev) -> torch.Tensor:
     return upload_async(torch.tensor([_intrinsics(c) for c in cameras], dtype=torch.float64).reshape(B, 4), dev)
-
-
-def _lm_inputs(B: int, R, t, row_begin, row_end, has_pose, feats, vertices, max_points: Optional[int]):
-    """The conversions every refiner makes, in the order they are enqueued, and the max_points rule: None is read back from the device.
-    -> (R [B, 9] f64, t [B, 3] f64, row_begin, row_end, has_pose i32, feats f32 or None, vertices f32, max_points >= 1)."""
-    Rin = R.to(torch.float64).reshape(B, 9).contiguous()
-    tin = t.to(torch.float64).reshape(B, 3).contiguous()
-    rb = row_begin.to(torch.int32).contiguous()
-    re = row_end.to(torch.int32).contiguous()
-    hp = has_pose.to(torch.int32).contiguous()
-    f32 = None if feats is None else feats.float().contiguous()
-    v32 = vertices.float().contiguous()
-    if max_points is None:
-        max_points = int(torch.where(hp != 0, re - rb, torch.zeros_like(re)).max().item()) if B else 0
-    return Rin, tin, rb, re, hp, f32, v32, max(1, int(max_points))
-
-
-def _lm_outputs(B: int, dev, normal_eq_width: int, depth_inliers: bool = False) -> Tuple[Dict[str, torch.Tensor], list]:
-    """Allocates a refiner's outputs.  -> (the result dict, the output pointers in the order of the C ABI -- the dict's own, then normal_eq);
-    normal_eq_width 0: no normal equations."""
-    f64, i32, empty = torch.float64, torch.int32, torch.empty
-    out = {"R": empty(B, 9, dtype=f64, device=dev), "t": empty(B, 3, dtype=f64, device=dev), "cost_in": empty(B, dtype=f64, device=dev),
-           "cost_out": empty(B, dtype=f64, device=dev), "num_points": empty(B, dtype=i32, device=dev)}
-    if depth_inliers:
-        out["num_depth_inliers"] = empty(B, dtype=i32, device=dev)
-    out["iters_used"], out["status"] = empty(B, dtype=i32, device=dev), empty(B, dtype=i32, device=dev)
-    neq = empty(B, normal_eq_width, dtype=f64, device=dev) if normal_eq_width else None
-    ptrs = [ptr(v) for v in out.values()]
-    ptrs.append(ptr(neq))
-    out["R"] = out["R"].reshape(B, 3, 3)
-    if neq is not None:
-        out["normal_eq"] = neq
-    return out, ptrs
 
 
 def refine_featuremetric(feature_map: torch.Tensor, image_size: Tuple[int, int], cameras: Sequence[Any], R: torch.Tensor, t: torch.Tensor,
