@@ -125,6 +125,8 @@ _PROTOS = {
     "fp_tsdf_emit_triangles": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp],
     "fp_tsdf_track": [vp, vp, vp, i32, i32, i32, i32, f64, vp, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp,
                       vp, vp],
+    "fp_tsdf_track_rgb": [vp, vp, vp, vp, vp, i32, i32, i32, i32, f64, vp, vp, i64, vp, vp, vp, vp, vp, vp, f64, f64, i32, i32, i32, vp, C.c_size_t,
+                          vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "fp_featuremetric_refine": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32,
                                 vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "fp_depth_refine": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],

@@ -1,6 +1,6 @@
 // C ABI of libfoundpose_amd.so (declared in include/foundpose_amd.h): argument checking, scratch carving
 // and kernel sequencing.  No device allocation, no global mutable state, no synchronisation except the table uploads of
-// fp_pose_errors, fp_vsd_counts, fp_gt_visibility, fp_depth_plane_fit, fp_depth_components and fp_tsdf_integrate (each waits for its own copy) and the range check read back by the four Levenberg-Marquardt solvers (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine, fp_tsdf_track).
+// fp_pose_errors, fp_vsd_counts, fp_gt_visibility, fp_depth_plane_fit, fp_depth_components and fp_tsdf_integrate (each waits for its own copy) and the range check read back by the four Levenberg-Marquardt solvers (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine, fp_tsdf_track and its colour sibling fp_tsdf_track_rgb).
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -1302,6 +1302,33 @@ int fp_tsdf_track(const float* sdf_sum, const int32_t* sdf_cnt, const double* bo
   TRY(launch_tsdf_track(a, ST(stream)));
   // no image index: err is never negative here
   return refine_report(fn, a.lm, 0, ST(stream), "%s: problem %d: rows outside [0, %lld) or more than max_points %d");
+}
+
+int fp_tsdf_track_rgb(const float* sdf_sum, const int32_t* sdf_cnt, const float* rgb_sum, const int32_t* rgb_cnt, const double* box, int nx,
+                      int ny, int nz, int min_count, double trunc_mm, const float* points, const float* colors, int64_t num_rows,
+                      const int32_t* row_begin, const int32_t* row_end, const double* R_in, const double* t_in, const int32_t* has_pose,
+                      const double* max_dist, double color_weight, double color_max, int num_det, int max_points, int iters, void* scratch,
+                      size_t scratch_bytes, double* R_out, double* t_out, double* cost_in, double* cost_out, int32_t* num_points,
+                      int32_t* iters_used, int32_t* status, double* normal_eq, fp_stream_t stream) {
+  const char* fn = "fp_tsdf_track_rgb";
+  FP_REQUIRE(sdf_sum && sdf_cnt && rgb_sum && rgb_cnt && box && points && colors && row_begin && row_end && R_in && t_in && has_pose && max_dist &&
+             scratch && R_out && t_out && cost_in && cost_out && num_points && iters_used && status, "fp_tsdf_track_rgb: null pointer");
+  FP_REQUIRE(min_count >= 1, "fp_tsdf_track_rgb: min_count %d must be >= 1", min_count);
+  FP_REQUIRE(std::isfinite(trunc_mm) && trunc_mm > 0, "fp_tsdf_track_rgb: the truncation distance must be finite and > 0");
+  FP_REQUIRE(std::isfinite(color_weight) && color_weight > 0, "fp_tsdf_track_rgb: color_weight must be finite and > 0");
+  FP_REQUIRE(std::isfinite(color_max) && color_max > 0, "fp_tsdf_track_rgb: color_max must be finite and > 0");
+  TsdfTrackRgbArgs a;
+  memset(&a, 0, sizeof(a));
+  TRY(tsdf_volume(fn, box, nx, ny, nz, 2, a.g.vol));
+  a.g.lm = refine_lm_args(nullptr, R_in, t_in, row_begin, row_end, points, num_rows, has_pose, num_det, max_points, iters, R_out, t_out, cost_in,
+                          cost_out, num_points, iters_used, status, normal_eq);
+  TRY(refine_check(fn, a.g.lm, nullptr, nullptr, nullptr));
+  a.g.sdf_sum = sdf_sum, a.g.sdf_cnt = sdf_cnt, a.g.min_count = min_count, a.g.tau = trunc_mm, a.g.max_dist = max_dist;
+  a.rgb_sum = rgb_sum, a.rgb_cnt = rgb_cnt, a.colors = colors, a.color_weight = color_weight, a.color_max = color_max;
+  a.g.state = static_cast<RefineState*>(scratch);
+  TRY(refine_carve(fn, a.g.lm, scratch, scratch_bytes, FP_TSDF_TRACK_SCRATCH_BYTES(num_det, max_points), FP_REFINE_RECORD, nullptr, ST(stream)));
+  TRY(launch_tsdf_track_rgb(a, ST(stream)));
+  return refine_report(fn, a.g.lm, 0, ST(stream), "%s: problem %d: rows outside [0, %lld) or more than max_points %d");
 }
 
 // ------------------------------------------------------------------ mask proposals from depth

@@ -434,7 +434,15 @@ struct TsdfTrackArgs {     // lm.verts are the camera-frame points, lm.cam is no
   const double* max_dist;  // [num_det] the inlier distance (mm)
   RefineState* state;
 };
+struct TsdfTrackRgbArgs {  // fp_tsdf_track_rgb: the geometric arguments as they stand, and what the colour term reads (section 31)
+  TsdfTrackArgs g;
+  const float* rgb_sum; const int* rgb_cnt;   // rgb_sum: 3 planes
+  const float* colors;     // [num_rows, 3], row-aligned with lm.verts
+  double color_weight;     // lambda: mm per unit of colour
+  double color_max;        // the channel inlier bound
+};
 int launch_tsdf_track(const TsdfTrackArgs& a, hipStream_t st);
+int launch_tsdf_track_rgb(const TsdfTrackRgbArgs& a, hipStream_t st);
 
 // ---------------------------------------------------------------- depth_proposals.hip
 struct DpFrame {                         // one frame, built on the host by fp_depth_plane_fit / fp_depth_components

@@ -679,13 +679,17 @@ def _lm_outputs(B: int, dev, normal_eq_width: int, depth_inliers: bool = False) 
 
 
 def tsdf_track(volume: dict, points: torch.Tensor, row_begin: torch.Tensor, row_end: torch.Tensor, R: torch.Tensor, t: torch.Tensor, max_dist,
-               min_count: int, trunc_mm: float, iters: int, has_pose: Optional[torch.Tensor] = None, want_normal_eq: bool = False) -> dict:
+               min_count: int, trunc_mm: float, iters: int, has_pose: Optional[torch.Tensor] = None, want_normal_eq: bool = False,
+               colors: Optional[torch.Tensor] = None, color_weight: float = 0.0, color_max: float = 0.25) -> dict:
     """Tracks B independent problems against `volume` (fp_tsdf_track; DESIGN.md section 30): points fp32 [N, 3], camera-frame mm;
     row_begin / row_end int [B]: a problem's rows of points; R [B, 3, 3] / t [B, 3] the start poses, model -> camera; max_dist: the
     inlier distance in mm, a number or one per problem (not validated: a NaN or a value <= 0 skips the problem); trunc_mm: the tau the
     volume was built with; has_pose [B] bool (None: all).  Everything else is checked here, before any launch: ValueError.
     -> dict of device tensors: R [B, 3, 3] f64, t [B, 3] f64, cost_in, cost_out [B] f64, num_points (inliers at the start pose),
-    iters_used, status [B] i32 (0 refined, 1 no step accepted, 2 skipped), + normal_eq [B, 28] f64 with want_normal_eq."""
+    iters_used, status [B] i32 (0 refined, 1 no step accepted, 2 skipped), + normal_eq [B, 28] f64 with want_normal_eq.
+    colors fp32 [N, 3] on the points' device, in [0, 1], row-aligned with points: the colour term of DESIGN.md section 31 joins the
+    objective (fp_tsdf_track_rgb) with color_weight (mm per unit of colour) and color_max (the channel inlier bound), both finite and
+    > 0; the costs and normal_eq are then the joint system's, num_points stays the geometric inlier count.  None: the call above."""
     import numpy as np
     fn = "tsdf_track"
     box, dims = _tsdf_box(fn, volume.get("origin") if isinstance(volume, dict) else None, volume.get("voxel_mm") if isinstance(volume, dict) else None,
@@ -716,6 +720,14 @@ def tsdf_track(volume: dict, points: torch.Tensor, row_begin: torch.Tensor, row_
         md = np.full(B, float(md))
     if md.shape != (B,):
         raise ValueError(f"{fn}: max_dist is one number or one per problem, got {md.shape}")
+    if colors is not None:
+        if not isinstance(colors, torch.Tensor) or not colors.is_cuda or colors.device != points.device:
+            raise ValueError(f"{fn}: colors must be a tensor on the device of points (there is no CPU path)")
+        if colors.dtype != torch.float32 or tuple(colors.shape) != tuple(points.shape):
+            raise ValueError(f"{fn}: colors must be float32 {tuple(points.shape)}, one row per row of points, got {colors.dtype} {tuple(colors.shape)}")
+        for name, v in (("color_weight", color_weight), ("color_max", color_max)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (np.isfinite(v) and v > 0):
+                raise ValueError(f"{fn}: {name} must be finite and > 0 with colors, got {v!r}")
     dev = points.device
     hp = torch.ones(B, dtype=torch.int32, device=dev) if has_pose is None else has_pose
     Rin, tin, rb, re, hp, _, p32, max_points = _lm_inputs(B, R, t, row_begin, row_end, hp, None, points, None)
@@ -723,6 +735,11 @@ def tsdf_track(volume: dict, points: torch.Tensor, row_begin: torch.Tensor, row_
     out, outs = _lm_outputs(B, dev, 28 if want_normal_eq else 0)
     nbytes = _lib.tsdf_track_scratch_bytes(B, max_points)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if colors is not None:
+        call("fp_tsdf_track_rgb", ptr(volume["sdf_sum"]), ptr(volume["sdf_cnt"]), ptr(volume["rgb_sum"]), ptr(volume["rgb_cnt"]),
+             box.ctypes.data_as(_lib.vp), *dims, int(min_count), tau, ptr(p32), ptr(colors.contiguous()), int(p32.shape[0]), ptr(rb), ptr(re), ptr(Rin),
+             ptr(tin), ptr(hp), ptr(md_d), float(color_weight), float(color_max), B, max_points, int(iters), ptr(scratch), nbytes, *outs, stream())
+        return out
     call("fp_tsdf_track", ptr(volume["sdf_sum"]), ptr(volume["sdf_cnt"]), box.ctypes.data_as(_lib.vp), *dims, int(min_count), tau, ptr(p32),
          int(p32.shape[0]), ptr(rb), ptr(re), ptr(Rin), ptr(tin), ptr(hp), ptr(md_d), B, max_points, int(iters), ptr(scratch), nbytes,
          *outs, stream())

@@ -13,7 +13,8 @@ detect onboard start from.  There is no CPU path.
 With opts `pose_source: "track"` one known pose per sequence is enough: the frames are the images of
 scene_camera.json, only the first image's scene_gt.json pose is used (and every Nth with `track_anchor_every`), every other frame is
 tracked against the volume fused so far (fp_tsdf_track) and fused at its tracked pose; `bounds` must then be given, and
---tracked-poses writes the poses per sequence in scene_gt.json's format.
+--tracked-poses writes the poses per sequence in scene_gt.json's format.  With `track_color_weight` > 0 a frame
+is tracked on shape and on the colour the volume holds (fp_tsdf_track_rgb): for objects whose shape leaves a rotation open.
 
 Limits: with pose_source "given" poses and masks are trusted as given; a voxel reads the nearest depth pixel, across depth edges too; surface that no frame
 saw stays open (the report says so, nothing is filled); no accuracy on real BOP data is claimed."""
@@ -50,6 +51,8 @@ class ReconstructOpts(NamedTuple):
     track_motion: str = "velocity"   # "velocity" or "hold": how a frame's start pose is predicted
     track_min_inlier_share: float = 0.5   # a tracked frame below this share of inliers is lost
     track_max_lost: int = 3        # consecutive lost frames allowed
+    track_color_weight: float = 0.0   # mm per unit of colour; 0: frames are tracked on shape alone, > 0: on shape and colour (section 31)
+    track_color_max: float = 0.25  # a colour channel further than this from the volume's colour is an outlier
 
     @property
     def trunc_mm(self) -> float:
@@ -99,6 +102,12 @@ def check_opts(o: ReconstructOpts) -> ReconstructOpts:
     v = o.track_min_inlier_share
     if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v <= 1:
         raise ValueError(f"track_min_inlier_share must lie in [0, 1], got {v!r}")
+    v = o.track_color_weight
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and v >= 0):
+        raise ValueError(f"track_color_weight must be finite and >= 0 (0: shape alone), got {v!r}")
+    v = o.track_color_max
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and v > 0):
+        raise ValueError(f"track_color_max must be finite and > 0, got {v!r}")
     return o
 
 
@@ -334,17 +343,32 @@ def fuse(frames: Sequence[Frame], opts=None, device="cuda") -> Dict[str, Any]:
     return vol
 
 
-def _lift(depth, mask, cam, max_points: int):
+def _selected(depth, mask, max_points: int):
+    """The flat indices of the pixels a frame is tracked with (lift_points' rule), in row-major order."""
+    sel = ((mask != 0) & (depth > 0)).reshape(-1).nonzero()[:, 0]               # row-major order
+    step = max(1, -(-int(sel.numel()) // int(max_points)))
+    return sel[::step]
+
+
+def _lift(depth, mask, cam, max_points: int, sel=None):
     """depth fp32 [H, W], mask uint8 [H, W] on the device -> fp32 [P, 3] camera-frame points (lift_points' rule)."""
     import torch
     W = depth.shape[1]
-    sel = ((mask != 0) & (depth > 0)).reshape(-1).nonzero()[:, 0]               # row-major order
-    step = max(1, -(-int(sel.numel()) // int(max_points)))
-    sel = sel[::step]
+    if sel is None:
+        sel = _selected(depth, mask, max_points)
     u, v = (sel % W).double(), torch.div(sel, W, rounding_mode="floor").double()
     d = depth.reshape(-1)[sel].double()
     fx, fy, cx, cy = (float(c) for c in cam)
     return torch.stack([(u - cx) / fx * d, (v - cy) / fy * d, d], 1).float().contiguous()
+
+
+def _lift_rgb(depth, mask, rgb, cam, max_points: int):
+    """_lift, and the colours of the same pixels: rgb uint8 [H, W, 3] on the device -> (fp32 [P, 3] points, fp32 [P, 3] colours =
+    uint8 / 255 as an fp32 division: what fp_tsdf_integrate adds to the volume)."""
+    import torch
+    sel = _selected(depth, mask, max_points)
+    colors = rgb.reshape(-1, 3)[sel].to(torch.float32) / torch.tensor(255.0, dtype=torch.float32, device=rgb.device)
+    return _lift(depth, mask, cam, max_points, sel), colors.contiguous()
 
 
 def lift_points(frame: Frame, max_points: int, device="cuda"):
@@ -356,6 +380,14 @@ def lift_points(frame: Frame, max_points: int, device="cuda"):
     return _lift(up(frame.depth, np.float32), up(frame.mask, np.uint8), frame.cam, max_points)
 
 
+def lift_points_rgb(frame: Frame, max_points: int, device="cuda"):
+    """lift_points' points and the colours of the same pixels -> (fp32 [P, 3], fp32 [P, 3]) on the device: the same selection rule, the
+    colours uint8 / 255 as an fp32 division (what integration adds to the volume's colour sums)."""
+    import torch
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(device)   # noqa: E731
+    return _lift_rgb(up(frame.depth, np.float32), up(frame.mask, np.uint8), up(frame.rgb, np.uint8), frame.cam, max_points)
+
+
 def fuse_tracked(frames: Sequence[Frame], given: Sequence[Optional[np.ndarray]], opts=None, device="cuda", sequence: Optional[Sequence[int]] = None):
     """Track mode's fusion (DESIGN.md section 30): the frames go through one at a time, in order.  given[k] is a 12-vector pose or None;
     sequence[k] names the sequence a frame belongs to (None: one sequence), and the first frame of every sequence must have a pose.
@@ -363,6 +395,8 @@ def fuse_tracked(frames: Sequence[Frame], given: Sequence[Optional[np.ndarray]],
     integrated at its given pose.  Any other frame is tracked (ops.tsdf_track) against the volume of the frames before it, from the start
     pose predict_pose gives, scored by one more evaluation at the result, and integrated at the tracked pose -- or lost: not
     integrated, and the next frame starts from the last kept pose.  More than track_max_lost lost frames in a row raise RuntimeError.
+    With track_color_weight > 0 (section 31) the tracking call also takes the colours of the frame's points; the score at the result stays
+    geometric, and the frame's record names the weight (its cost_in / cost_out are then the joint objective's).
     -> (volume, poses: a 12-vector or None (lost) per frame, records: one dict per frame)."""
     import torch
 
@@ -385,6 +419,7 @@ def fuse_tracked(frames: Sequence[Frame], given: Sequence[Optional[np.ndarray]],
     origin, dims = choose_volume(frames, opts, device)
     vol = ops.tsdf_new_volume(origin, opts.voxel_mm, dims, device)
     tau, md = opts.trunc_mm, float(opts.track_max_dist_voxels) * float(opts.voxel_mm)
+    color_weight = float(opts.track_color_weight)
     zero = torch.zeros(1, dtype=torch.int32, device=device)
     poses: List[Optional[np.ndarray]] = []
     records: List[Dict[str, Any]] = []
@@ -402,13 +437,22 @@ def fuse_tracked(frames: Sequence[Frame], given: Sequence[Optional[np.ndarray]],
         else:
             t_start = time.perf_counter()
             T0 = predict_pose(history, idx, opts.track_motion)
-            pts = _lift(depth[0], mask[0], fr.cam, opts.track_max_points)
+            if color_weight > 0:
+                pts, cols = _lift_rgb(depth[0], mask[0], rgb[0], fr.cam, opts.track_max_points)
+                rec["color_weight"] = color_weight                              # cost_in / cost_out below are then the joint objective's
+            else:
+                pts = _lift(depth[0], mask[0], fr.cam, opts.track_max_points)
             n = int(pts.shape[0])
             end = torch.full((1,), n, dtype=torch.int32, device=device)
             if n > 0:
                 run = lambda R, t, iters: ops.tsdf_track(vol, pts, zero, end, R, t, md, int(opts.track_min_count), tau, iters)   # noqa: E731
-                out = run(torch.from_numpy(T0[:3, :3].copy()).to(device), torch.from_numpy(T0[:3, 3].copy()).to(device), int(opts.track_iters))
-                at = run(out["R"], out["t"], 0)                                 # the inliers and the cost at the result
+                R0, t0 = torch.from_numpy(T0[:3, :3].copy()).to(device), torch.from_numpy(T0[:3, 3].copy()).to(device)
+                if color_weight > 0:
+                    out = ops.tsdf_track(vol, pts, zero, end, R0, t0, md, int(opts.track_min_count), tau, int(opts.track_iters), colors=cols,
+                                         color_weight=color_weight, color_max=float(opts.track_color_max))
+                else:
+                    out = run(R0, t0, int(opts.track_iters))
+                at = run(out["R"], out["t"], 0)                                 # the inliers and the cost at the result: shape alone, either way
                 o = {key: v.cpu().numpy()[0] for key, v in out.items()}
                 inl, cost = int(at["num_points"].cpu()[0]), float(at["cost_out"].cpu()[0])
                 share = inl / n
@@ -526,6 +570,8 @@ def reconstruct(sequences: Sequence[str], obj_id: int, output_dir: str, opts=Non
         roles = [r["role"] for r in records]
         tracking = {"frames": records, "totals": {role: roles.count(role) for role in ("anchor", "tracked", "lost")},
                     "seconds": float(sum(r.get("seconds", 0.0) for r in records))}
+        if opts.track_color_weight > 0:                                          # tracked on shape and colour (section 31)
+            tracking["totals"]["color_weight"] = float(opts.track_color_weight)
     else:
         vol = fuse(frames, opts, device)
     observed = int((vol["sdf_cnt"] >= opts.min_count).sum())
@@ -573,7 +619,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     r = reconstruct(a.sequence, a.obj_id, a.output, a.opts, a.report, a.overwrite, a.device, a.tracked_poses)
     if "tracking" in r:
         tot = r["tracking"]["totals"]
-        print(f"tracking: {tot['anchor']} anchor(s), {tot['tracked']} tracked, {tot['lost']} lost in {r['tracking']['seconds']:.2f} s")
+        print(f"tracking: {tot['anchor']} anchor(s), {tot['tracked']} tracked, {tot['lost']} lost in {r['tracking']['seconds']:.2f} s"
+              + (f" (on shape and colour, weight {tot['color_weight']:g} mm per unit)" if "color_weight" in tot else ""))
     print(f"{r['output']}: {r['vertices']} vertices, {r['triangles']} triangles from {r['frames_used']} frame(s) in a volume of "
           f"{r['dims'][0]} x {r['dims'][1]} x {r['dims'][2]} voxels; {r['boundary_edges']} boundary edge(s), "
           f"{'watertight' if r['watertight'] else 'open: ' + str(r['note'])}; {r['seconds']['total']:.2f} s")

@@ -1224,6 +1224,30 @@ int fp_tsdf_track(const float* sdf_sum, const int32_t* sdf_cnt, const double* bo
                   void* scratch, size_t scratch_bytes, double* R_out, double* t_out, double* cost_in, double* cost_out,
                   int32_t* num_points, int32_t* iters_used, int32_t* status, double* normal_eq, fp_stream_t stream);
 
+/* ---- frame-to-model tracking on shape and colour (reconstruct.py, track_color_weight > 0; DESIGN.md section 31;
+ *      tests/tsdf_track_rgb_ref.py restates it) ----
+ * fp_tsdf_track with a second per-point term: every argument of fp_tsdf_track means what it means there, plus
+ *   rgb_sum, rgb_cnt  fp32 [3, nz, ny, nx] (planar), int32 [nz, ny, nx]  the colour planes fp_tsdf_integrate wrote beside the distances
+ *   colors      fp32 [num_rows, 3]  the colour of every row of points, in [0, 1] (uint8 / 255 as fp_tsdf_integrate adds it)
+ *   color_weight  lambda, mm per unit of colour, finite and > 0;  color_max  the channel inlier bound, finite and > 0
+ * The geometric part of a point is evaluated exactly as in fp_tsdf_track.  Then, fp64: the point is colour-measurable when it is a
+ * geometric inlier and all eight corners of its cell have rgb_cnt >= min_count (rgb_cnt is read only for geometric inliers, rgb_sum
+ * only where all eight pass).  Per channel ch a corner's colour is (double)rgb_sum[ch] / (double)rgb_cnt, C_ch the trilinear
+ * interpolant (x, then y, then z), grad C_ch its exact gradient over h -- phi's formulas; e_ch = C_ch - (double)colors[ch]; a channel
+ * is an inlier when the point is colour-measurable and |e_ch| < color_max.  rho = rho_geom + sum_ch rho_ch, rho_ch = (lambda e_ch)^2
+ * for a channel inlier and (lambda color_max)^2 otherwise (a geometric outlier, a point that is not colour-measurable, a NaN); cost =
+ * sum rho / (row_end - row_begin).  A channel inlier adds the row [q_ch x X_c | -q_ch], q_ch = lambda R grad C_ch, with the residual
+ * lambda e_ch to H and g: geometry first, then channel 0, 1, 2.  num_points, the stop on fewer than 6 inliers and status 2 count
+ * GEOMETRIC inliers, as in fp_tsdf_track; normal_eq holds the joint system.  Outputs, scratch (FP_TSDF_TRACK_SCRATCH_BYTES), determinism
+ * and the rule that a refused call writes nothing are fp_tsdf_track's.  (Added without a change of FP_ABI_VERSION: no existing entry
+ * point changed.) */
+int fp_tsdf_track_rgb(const float* sdf_sum, const int32_t* sdf_cnt, const float* rgb_sum, const int32_t* rgb_cnt, const double* box, int nx,
+                      int ny, int nz, int min_count, double trunc_mm, const float* points, const float* colors, int64_t num_rows,
+                      const int32_t* row_begin, const int32_t* row_end, const double* R_in, const double* t_in, const int32_t* has_pose,
+                      const double* max_dist, double color_weight, double color_max, int num_det, int max_points, int iters, void* scratch,
+                      size_t scratch_bytes, double* R_out, double* t_out, double* cost_in, double* cost_out, int32_t* num_points,
+                      int32_t* iters_used, int32_t* status, double* normal_eq, fp_stream_t stream);
+
 /* ---- joint refinement on features and depth (tests/rgbd_refine_ref.py restates it) --------------------------
  * One Levenberg-Marquardt objective E = E_f + depth_weight E_d per detection.  The pose (R, t) is model -> FRAME camera (mm).
  *   map, strides, gh, gw, C, W, H, feature_cameras   the featuremetric call's map arguments: the projected feature map and the camera

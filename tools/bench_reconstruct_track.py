@@ -6,7 +6,8 @@ same volume and points on one CPU thread -- which is all it is compared with.
 
 The scene is bench_reconstruct.py's blob of radius 90 mm rendered by the HIP rasterizer, here from a ring of cameras 5 degrees apart at
 600 mm over a background plane at 1 500 mm.  The first --frames views are fused at their true poses; the next view is the tracked frame,
-started from the pose of the view before it ("hold": 5 degrees off), 20 iterations.  Device time: HIP events around one ops.tsdf_track
+started from the pose of the view before it ("hold": 5 degrees off), 20 iterations -- once on shape alone and once on shape and colour
+(fp_tsdf_track_rgb with the frame's colours, weight 30 mm per unit, color_max 0.25).  Device time: HIP events around one ops.tsdf_track
 call (its launches and the read-back of the range check; the allocation of its outputs is inside, the lifting of the points outside),
 the median of --iters calls after 2 warm-up calls, one process.  The split into pass and solve launches is the sum of the kernels'
 own durations from one more call under torch.profiler; what the events hold beyond those sums is the time between kernels."""
@@ -21,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tools.bench_reconstruct import _look_at, _timed   # noqa: E402
 
 
-def _kernel_split(fn):
+def _kernel_split(fn, pass_kernel="tsdf_track_pass_kernel"):
     """One call under torch.profiler -> {"pass": (launches, ms), "solve": (launches, ms)} from the kernels' own durations, or None."""
     import torch
     from torch.profiler import ProfilerActivity, profile
@@ -31,7 +32,7 @@ def _kernel_split(fn):
             torch.cuda.synchronize()
         out = {}
         for name in ("pass", "solve"):
-            evs = [e for e in prof.events() if f"tsdf_track_{name}_kernel" in e.name]
+            evs = [e for e in prof.events() if (pass_kernel if name == "pass" else "tsdf_track_solve_kernel") in e.name]
             ms = sum(float(getattr(e, "device_time", 0.0) or getattr(e, "cuda_time", 0.0)) for e in evs) / 1e3
             if not evs or ms <= 0:
                 return None
@@ -110,6 +111,21 @@ def main():
                      f"{taps / (mp * 1e-3 / np_) / 1e9:.1f} GB/s while a pass runs"
                      f"\n    a solve folds {chunks} partial records one after the other (lm_fold: one lane per term, chunk order): "
                      f"{msol * 1e6 / ns / chunks:5.0f} ns per record, about one load's latency each -- {100.0 * msol / ms:4.1f} % of the call")
+        lines.append(line)
+        # the same frame and volume on shape and colour (fp_tsdf_track_rgb): weight 30 mm per unit, color_max 0.25
+        pts_c, cols = reconstruct._lift_rgb(depth[F], mask[F], rgb[F], cam, cap)
+        assert torch.equal(pts_c, pts)
+        call_c = lambda: ops.tsdf_track(vol, pts, zero, end, R0, t0, md, 1, tau, LM_ITERS, colors=cols, color_weight=30.0, color_max=0.25)   # noqa: E731
+        ms_c, out_c = _timed(call_c, args.iters)
+        c = (np.trace(out_c["R"][0].cpu().numpy().T @ poses[F][0]) - 1.0) / 2.0
+        err_c = (float(np.degrees(np.arccos(np.clip(c, -1, 1)))), float(np.linalg.norm(out_c["t"][0].cpu().numpy() - poses[F][1])))
+        line = (f"    with colours (weight 30, color_max 0.25): {ms_c:7.3f} ms per tracked frame   {int(out_c['iters_used'][0])} of {LM_ITERS} iterations used, "
+                f"status {int(out_c['status'][0])}, {err_c[0]:.3f} deg / {err_c[1]:.3f} mm from the true pose")
+        split = _kernel_split(call_c, "tsdf_track_rgb_pass_kernel")
+        if split:
+            (np_, mp), (ns, msol) = split["pass"], split["solve"]
+            line += (f"\n        kernels' own durations: pass {mp:6.3f} ms in {np_} launches ({mp * 1e3 / np_:5.1f} us each; at most forty-eight 4-byte taps per point), "
+                     f"solve {msol:6.3f} ms in {ns} launches ({msol * 1e3 / ns:5.1f} us each); between kernels and around them {ms_c - mp - msol:6.3f} ms")
         lines.append(line)
         if not args.no_cpu:
             from tests import tsdf_track_ref as tr
