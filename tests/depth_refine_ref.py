@@ -7,6 +7,7 @@ distance tau (mm).  Everything after the fp32 taps is fp64.
 
 import numpy as np
 
+from tests import lm_ref
 from tests.featuremetric_ref import rot_angle_deg, rot_exp, update  # noqa: F401  (the same twist and update as section 11)
 
 
@@ -74,41 +75,19 @@ def lm_solve(Hm, g, lam):
     return np.linalg.solve(L.T, np.linalg.solve(L, -g))
 
 
-def refine(R, t, X, cam, D, tau, iters=30, has_pose=True):
+def refine(R, t, X, cam, D, tau, iters=30, has_pose=True, **lm):
     """The Levenberg-Marquardt loop of section 11 on the depth term.  -> dict R, t, cost_in, cost_out, num_points (inliers at the
-    input pose), iters_used, status."""
+    input pose), iters_used, status, trace (tests/lm_ref.lm_loop; **lm: its fault switches)."""
     R = np.asarray(R, np.float64)
     t = np.asarray(t, np.float64)
-    out = dict(R=R.copy(), t=t.copy(), cost_in=0.0, cost_out=0.0, num_points=0, iters_used=0, status=2)
+    out = dict(R=R.copy(), t=t.copy(), cost_in=0.0, cost_out=0.0, num_points=0, iters_used=0, status=2, trace=[])
     if not has_pose or len(X) == 0:
         return out
     E, Hm, g, inl = system(R, t, X, cam, D, tau)
     out.update(cost_in=E, cost_out=E, num_points=int(inl.sum()))
     if inl.sum() < 6:
         return out
-    lam, it, accepted = 1e-3, 0, False
-    while it < iters:
-        d = lm_solve(Hm, g, lam)
-        it += 1
-        if d is None:
-            lam *= 10.0
-            if lam > 1e12:
-                break
-            continue
-        Rt, tt = update(R, t, d)
-        Et, Ht, gt, _ = system(Rt, tt, X, cam, D, tau)
-        if Et < E:
-            rel = (E - Et) / E
-            R, t, E, Hm, g = Rt, tt, Et, Ht, gt
-            lam = max(lam / 10.0, 1e-12)
-            accepted = True
-            if rel < 1e-10:
-                break
-        else:
-            lam *= 10.0
-            if lam > 1e12:
-                break
-    out.update(R=R, t=t, cost_out=E, iters_used=it, status=0 if accepted else 1)
+    out.update(lm_ref.lm_loop(lambda R, t: system(R, t, X, cam, D, tau), R, t, E, Hm, g, iters, lm_solve, **lm))
     return out
 
 

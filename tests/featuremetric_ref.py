@@ -8,24 +8,8 @@ per point are accumulated in fp32, everything after them is fp64.
 
 import numpy as np
 
-
-def rot_exp(w):
-    """exp([w]x) (Rodrigues; series below 1e-8 rad) -- csrc/rot.hpp."""
-    w = np.asarray(w, np.float64)
-    th2 = float(w @ w)
-    th = np.sqrt(th2)
-    if th < 1e-8:
-        a, b = 1.0 - th2 / 6.0, 0.5 - th2 / 24.0
-    else:
-        a, b = np.sin(th) / th, (1.0 - np.cos(th)) / th2
-    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]], np.float64)
-    return np.eye(3) + a * K + b * (K @ K)
-
-
-def update(R, t, d):
-    """R' = exp([w]x) R, t' = exp([w]x) t + v for d = (w, v)."""
-    E = rot_exp(d[:3])
-    return E @ R, E @ t + d[3:]
+from tests import lm_ref
+from tests.lm_ref import rot_exp, update  # noqa: F401  (the twist and the update live beside the loop; the other restatements import them from here)
 
 
 def map_coords(R, t, X, cam, W, H, gw, gh):
@@ -127,11 +111,11 @@ def lm_solve(Hm, g, lam):
     return np.linalg.solve(L.T, np.linalg.solve(L, -g))
 
 
-def refine(R, t, X, f, cam, W, H, M, iters=30, has_pose=True):
-    """The Levenberg-Marquardt loop.  -> dict R, t, cost_in, cost_out, num_points, iters_used, status."""
+def refine(R, t, X, f, cam, W, H, M, iters=30, has_pose=True, **lm):
+    """The Levenberg-Marquardt loop.  -> dict R, t, cost_in, cost_out, num_points, iters_used, status, trace (tests/lm_ref.lm_loop; **lm: its fault switches)."""
     R = np.asarray(R, np.float64)
     t = np.asarray(t, np.float64)
-    out = dict(R=R.copy(), t=t.copy(), cost_in=0.0, cost_out=0.0, num_points=0, iters_used=0, status=2)
+    out = dict(R=R.copy(), t=t.copy(), cost_in=0.0, cost_out=0.0, num_points=0, iters_used=0, status=2, trace=[])
     if not has_pose or len(X) == 0:
         return out
     valid = valid_set(R, t, X, cam, W, H, M)
@@ -141,29 +125,8 @@ def refine(R, t, X, f, cam, W, H, M, iters=30, has_pose=True):
     s2 = sigma2_at(R, t, X, f, cam, W, H, M, valid)
     E, Hm, g, _ = system(R, t, X, f, cam, W, H, M, valid, s2)
     out["cost_in"] = E
-    lam, it, accepted = 1e-3, 0, False
-    while it < iters:
-        d = lm_solve(Hm, g, lam)
-        it += 1
-        if d is None:
-            lam *= 10.0
-            if lam > 1e12:
-                break
-            continue
-        Rt, tt = update(R, t, d)
-        Et, Ht, gt, zbad = system(Rt, tt, X, f, cam, W, H, M, valid, s2)
-        if not zbad and Et < E:
-            rel = (E - Et) / E
-            R, t, E, Hm, g = Rt, tt, Et, Ht, gt
-            lam = max(lam / 10.0, 1e-12)
-            accepted = True
-            if rel < 1e-10:
-                break
-        else:
-            lam *= 10.0
-            if lam > 1e12:
-                break
-    out.update(R=R, t=t, cost_out=E, iters_used=it, status=0 if accepted else 1)
+    out.update(lm_ref.lm_loop(lambda R, t: system(R, t, X, f, cam, W, H, M, valid, s2), R, t, E, Hm, g, iters, lm_solve, admissible=lambda zbad: not zbad,
+                              z_gap=lambda R, t: 1.0 - float(point_terms(R, t, X[valid], f[valid], cam, W, H, M)["z"].min()), **lm))
     return out
 
 

@@ -11,6 +11,7 @@ H = H_f / (|V| sigma^2) + w_d H_d / (N tau^2), g likewise.  The twist is left-mu
 import numpy as np
 
 from tests import featuremetric_ref as fr
+from tests import lm_ref
 from tests.featuremetric_ref import rot_angle_deg, rot_exp, update  # noqa: F401
 
 
@@ -136,6 +137,10 @@ class Problem:
         nd = len(self.X) * self.tau * self.tau
         return Ef + self.wd * Ed, Hf / nf + self.wd * Hd / nd, gf / nf + self.wd * gd / nd, zbad
 
+    def z_gap(self, R, t):
+        """1 - the smallest z_f over the frozen valid set: how far on the wrong side of 1 mm an inadmissible pose's deciding point lies."""
+        return 1.0 - float(feature_terms(R, t, self.X[self.valid], self.f[self.valid], self.A, self.a, self.fcam, self.W, self.H, self.M)["z"].min())
+
 
 def normal_equations(R, t, pr):
     """The kernel's optional [57] output at the input pose: H_f (21) | g_f (6) | E_f, H_d (21) | g_d (6) | E_d, E."""
@@ -145,11 +150,11 @@ def normal_equations(R, t, pr):
     return np.concatenate([Hf[iu], gf, [Ef], Hd[iu], gd, [Ed], [pr.system(R, t)[0]]])
 
 
-def refine(R, t, pr, iters=30, has_pose=True):
-    """Section 11's Levenberg-Marquardt loop on E.  -> dict R, t, cost_in, cost_out, num_points, num_depth_inliers, iters_used, status."""
+def refine(R, t, pr, iters=30, has_pose=True, **lm):
+    """Section 11's Levenberg-Marquardt loop on E.  -> dict R, t, cost_in, cost_out, num_points, num_depth_inliers, iters_used, status, trace (tests/lm_ref.lm_loop; **lm: its fault switches)."""
     R = np.asarray(R, np.float64)
     t = np.asarray(t, np.float64)
-    out = dict(R=R.copy(), t=t.copy(), cost_in=0.0, cost_out=0.0, num_points=0, num_depth_inliers=0, iters_used=0, status=2)
+    out = dict(R=R.copy(), t=t.copy(), cost_in=0.0, cost_out=0.0, num_points=0, num_depth_inliers=0, iters_used=0, status=2, trace=[])
     if not has_pose or len(pr.X) == 0:
         return out
     ok = pr.start(R, t)
@@ -159,29 +164,7 @@ def refine(R, t, pr, iters=30, has_pose=True):
     out["num_depth_inliers"] = pr.ninl
     E, Hm, g, _ = pr.system(R, t)
     out["cost_in"] = E
-    lam, it, accepted = 1e-3, 0, False
-    while it < iters:
-        d = fr.lm_solve(Hm, g, lam)
-        it += 1
-        if d is None:
-            lam *= 10.0
-            if lam > 1e12:
-                break
-            continue
-        Rt, tt = update(R, t, d)
-        Et, Ht, gt, zbad = pr.system(Rt, tt)
-        if not zbad and Et < E:
-            rel = (E - Et) / E
-            R, t, E, Hm, g = Rt, tt, Et, Ht, gt
-            lam = max(lam / 10.0, 1e-12)
-            accepted = True
-            if rel < 1e-10:
-                break
-        else:
-            lam *= 10.0
-            if lam > 1e12:
-                break
-    out.update(R=R, t=t, cost_out=E, iters_used=it, status=0 if accepted else 1)
+    out.update(lm_ref.lm_loop(pr.system, R, t, E, Hm, g, iters, fr.lm_solve, admissible=lambda zbad: not zbad, z_gap=pr.z_gap, **lm))
     return out
 
 

@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from tests import tsdf_ref
+from tests import lm_ref, tsdf_ref
 from tests.depth_refine_ref import lm_solve
 from tests.featuremetric_ref import rot_angle_deg, rot_exp, update  # noqa: F401
 
@@ -84,41 +84,19 @@ def normal_equations(vol, R, t, Xc, tau, min_count, max_dist):
     return np.concatenate([Hm[np.triu_indices(6)], g, [E]])
 
 
-def track(vol, R, t, Xc, tau, min_count, max_dist, iters=20, has_pose=True):
+def track(vol, R, t, Xc, tau, min_count, max_dist, iters=20, has_pose=True, **lm):
     """The Levenberg-Marquardt loop of refine_terms.hpp on the term above: lambda from 1e-3, / 10 on accept (floor 1e-12), x 10 on reject
     or failed Cholesky (which counts as an iteration), stop at lambda > 1e12, at a relative decrease < 1e-10 or at `iters`.
-    -> dict R, t, cost_in, cost_out, num_points (inliers at the input pose), iters_used, status."""
+    -> dict R, t, cost_in, cost_out, num_points (inliers at the input pose), iters_used, status, trace (tests/lm_ref.lm_loop; **lm: its fault switches)."""
     R, t = np.asarray(R, np.float64), np.asarray(t, np.float64)
-    out = dict(R=R.copy(), t=t.copy(), cost_in=0.0, cost_out=0.0, num_points=0, iters_used=0, status=2)
+    out = dict(R=R.copy(), t=t.copy(), cost_in=0.0, cost_out=0.0, num_points=0, iters_used=0, status=2, trace=[])
     if not has_pose or len(Xc) == 0:
         return out
     E, Hm, g, inl = system(vol, R, t, Xc, tau, min_count, max_dist)
     out.update(cost_in=E, cost_out=E, num_points=int(inl.sum()))
     if inl.sum() < 6:
         return out
-    lam, it, accepted = 1e-3, 0, False
-    while it < iters:
-        d = lm_solve(Hm, g, lam)
-        it += 1
-        if d is None:
-            lam *= 10.0
-            if lam > 1e12:
-                break
-            continue
-        Rt, tt = update(R, t, d)
-        Et, Ht, gt, _ = system(vol, Rt, tt, Xc, tau, min_count, max_dist)
-        if Et < E:
-            rel = (E - Et) / E
-            R, t, E, Hm, g = Rt, tt, Et, Ht, gt
-            lam = max(lam / 10.0, 1e-12)
-            accepted = True
-            if rel < 1e-10:
-                break
-        else:
-            lam *= 10.0
-            if lam > 1e12:
-                break
-    out.update(R=R, t=t, cost_out=E, iters_used=it, status=0 if accepted else 1)
+    out.update(lm_ref.lm_loop(lambda R, t: system(vol, R, t, Xc, tau, min_count, max_dist), R, t, E, Hm, g, iters, lm_solve, **lm))
     return out
 
 

@@ -9,10 +9,9 @@ import functools
 
 import numpy as np
 
-from tests import tsdf_ref
+from tests import lm_ref, tsdf_ref
 from tests import tsdf_track_ref as tr
 from tests.depth_refine_ref import lm_solve
-from tests.featuremetric_ref import update
 
 F32 = np.float32
 
@@ -89,41 +88,19 @@ def normal_equations(vol, R, t, Xc, colors, tau, min_count, max_dist, weight, co
     return np.concatenate([Hm[np.triu_indices(6)], g, [E]])
 
 
-def track(vol, R, t, Xc, colors, tau, min_count, max_dist, weight, color_max, iters=20, has_pose=True):
+def track(vol, R, t, Xc, colors, tau, min_count, max_dist, weight, color_max, iters=20, has_pose=True, **lm):
     """tsdf_track_ref.track's loop (refine_terms.hpp's schedule) on the joint system; num_points and the stop on fewer than 6 inliers
-    count geometric inliers.  -> dict R, t, cost_in, cost_out, num_points, iters_used, status."""
+    count geometric inliers.  -> dict R, t, cost_in, cost_out, num_points, iters_used, status, trace (tests/lm_ref.lm_loop; **lm: its fault switches)."""
     sys_at = lambda R, t: system(vol, R, t, Xc, colors, tau, min_count, max_dist, weight, color_max)   # noqa: E731
     R, t = np.asarray(R, np.float64), np.asarray(t, np.float64)
-    out = dict(R=R.copy(), t=t.copy(), cost_in=0.0, cost_out=0.0, num_points=0, iters_used=0, status=2)
+    out = dict(R=R.copy(), t=t.copy(), cost_in=0.0, cost_out=0.0, num_points=0, iters_used=0, status=2, trace=[])
     if not has_pose or len(Xc) == 0:
         return out
     E, Hm, g, inl = sys_at(R, t)
     out.update(cost_in=E, cost_out=E, num_points=int(inl.sum()))
     if inl.sum() < 6:
         return out
-    lam, it, accepted = 1e-3, 0, False
-    while it < iters:
-        d = lm_solve(Hm, g, lam)
-        it += 1
-        if d is None:
-            lam *= 10.0
-            if lam > 1e12:
-                break
-            continue
-        Rt, tt = update(R, t, d)
-        Et, Ht, gt, _ = sys_at(Rt, tt)
-        if Et < E:
-            rel = (E - Et) / E
-            R, t, E, Hm, g = Rt, tt, Et, Ht, gt
-            lam = max(lam / 10.0, 1e-12)
-            accepted = True
-            if rel < 1e-10:
-                break
-        else:
-            lam *= 10.0
-            if lam > 1e12:
-                break
-    out.update(R=R, t=t, cost_out=E, iters_used=it, status=0 if accepted else 1)
+    out.update(lm_ref.lm_loop(sys_at, R, t, E, Hm, g, iters, lm_solve, **lm))
     return out
 
 
