@@ -123,6 +123,8 @@ _PROTOS = {
     "fp_tsdf_integrate": [vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, f64, vp, C.c_size_t, vp, vp, vp, vp, vp],
     "fp_tsdf_count_triangles": [vp, vp, i32, i32, i32, i32, vp, vp],
     "fp_tsdf_emit_triangles": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp],
+    "fp_mesh_cell_keys": [vp, i64, vp, i32, i32, i32, vp, vp],
+    "fp_mesh_cluster": [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, f64, vp, vp, vp, vp, vp, vp, vp],
     "fp_tsdf_track": [vp, vp, vp, i32, i32, i32, i32, f64, vp, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp,
                       vp, vp],
     "fp_tsdf_track_rgb": [vp, vp, vp, vp, vp, i32, i32, i32, i32, f64, vp, vp, i64, vp, vp, vp, vp, vp, vp, f64, f64, i32, i32, i32, vp, C.c_size_t,
@@ -265,6 +267,9 @@ def component_table_scratch_bytes(num_frames: int, pixels: int) -> int:
 
 
 TSDF_MAX_DIM, TSDF_MAX_VOXELS, TSDF_MAX_FRAMES, TSDF_FRAME_DOUBLES = 512, 1 << 27, 4096, 16  # FP_TSDF_* of the header
+
+
+MESH_MAX_DIM, MESH_MAX_ROWS = 1 << 20, 2**31 - 1  # FP_MESH_* of the header
 
 
 def tsdf_scratch_bytes(num_frames: int) -> int:

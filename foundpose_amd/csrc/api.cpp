@@ -1280,6 +1280,65 @@ int fp_tsdf_emit_triangles(const float* sdf_sum, const int32_t* sdf_cnt, const f
   return launch_tsdf_extract(a, true, ST(stream));
 }
 
+// ------------------------------------------------------------------ mesh simplification (simplify.hip)
+}  // extern "C"
+
+// the checks the two mesh entries share: the grid (origin, cell size) and its dimensions
+static int mesh_grid(const char* who, const double* grid, int nx, int ny, int nz, MeshGrid& g) {
+  FP_REQUIRE(grid != nullptr, "%s: null pointer", who);
+  FP_REQUIRE(nx >= 1 && ny >= 1 && nz >= 1 && nx <= FP_MESH_MAX_DIM && ny <= FP_MESH_MAX_DIM && nz <= FP_MESH_MAX_DIM,
+             "%s: dimensions %d x %d x %d outside [1, %d]", who, nx, ny, nz, FP_MESH_MAX_DIM);
+  FP_REQUIRE(std::isfinite(grid[0]) && std::isfinite(grid[1]) && std::isfinite(grid[2]) && std::isfinite(grid[3]) && grid[3] > 0,
+             "%s: the origin must be finite and the cell size finite and > 0", who);
+  memset(&g, 0, sizeof(g));
+  g.ox = grid[0], g.oy = grid[1], g.oz = grid[2], g.c = grid[3];
+  g.nx = nx, g.ny = ny, g.nz = nz;
+  return FP_OK;
+}
+
+extern "C" {
+
+int fp_mesh_cell_keys(const float* vertices, int64_t num_vertices, const double* grid, int nx, int ny, int nz, int64_t* keys,
+                      fp_stream_t stream) {
+  FP_REQUIRE(num_vertices >= 0 && num_vertices <= FP_MESH_MAX_ROWS, "fp_mesh_cell_keys: %lld vertices outside [0, %lld]",
+             (long long)num_vertices, (long long)FP_MESH_MAX_ROWS);
+  FP_REQUIRE(num_vertices == 0 || (vertices && keys), "fp_mesh_cell_keys: null pointer");
+  MeshKeysArgs a;
+  memset(&a, 0, sizeof(a));
+  TRY(mesh_grid("fp_mesh_cell_keys", grid, nx, ny, nz, a.grid));
+  a.verts = vertices, a.num_vertices = num_vertices, a.keys = reinterpret_cast<long long*>(keys);
+  return launch_mesh_cell_keys(a, ST(stream));
+}
+
+int fp_mesh_cluster(const float* vertices, const float* colors, int64_t num_vertices, const int32_t* faces, int64_t num_faces,
+                    const int64_t* cell_keys, int64_t num_cells, const int64_t* vert_order, const int64_t* vert_begin,
+                    const int64_t* corner_order, const int64_t* corner_begin, const double* grid, int nx, int ny, int nz, double eig_eps,
+                    float* positions, float* out_colors, double* quadrics, double* means, double* err, int32_t* status,
+                    fp_stream_t stream) {
+  const char* fn = "fp_mesh_cluster";
+  FP_REQUIRE(num_vertices >= 1 && num_vertices <= FP_MESH_MAX_ROWS, "%s: %lld vertices outside [1, %lld]", fn, (long long)num_vertices,
+             (long long)FP_MESH_MAX_ROWS);
+  FP_REQUIRE(num_faces >= 0 && 3 * num_faces <= FP_MESH_MAX_ROWS, "%s: %lld faces: 3 F outside [0, %lld]", fn, (long long)num_faces,
+             (long long)FP_MESH_MAX_ROWS);
+  FP_REQUIRE(num_cells >= 1 && num_cells <= num_vertices, "%s: %lld cells outside [1, %lld vertices]", fn, (long long)num_cells,
+             (long long)num_vertices);
+  FP_REQUIRE(vertices && colors && cell_keys && vert_order && vert_begin && corner_begin && positions && out_colors && quadrics && means &&
+             err && status, "%s: null pointer", fn);
+  FP_REQUIRE(num_faces == 0 || (faces && corner_order), "%s: null faces or corner_order with %lld faces", fn, (long long)num_faces);
+  FP_REQUIRE(std::isfinite(eig_eps) && eig_eps >= 0 && eig_eps < 1, "%s: eig_eps must lie in [0, 1)", fn);
+  MeshClusterArgs a;
+  memset(&a, 0, sizeof(a));
+  TRY(mesh_grid(fn, grid, nx, ny, nz, a.grid));
+  a.verts = vertices, a.colors = colors, a.num_vertices = num_vertices;
+  a.faces = faces, a.num_faces = num_faces;
+  a.cell_keys = reinterpret_cast<const long long*>(cell_keys), a.num_cells = num_cells;
+  a.vert_order = reinterpret_cast<const long long*>(vert_order), a.vert_begin = reinterpret_cast<const long long*>(vert_begin);
+  a.corner_order = reinterpret_cast<const long long*>(corner_order), a.corner_begin = reinterpret_cast<const long long*>(corner_begin);
+  a.eig_eps = eig_eps;
+  a.pos = positions, a.col = out_colors, a.quadrics = quadrics, a.means = means, a.err = err, a.status = status;
+  return launch_mesh_cluster(a, ST(stream));
+}
+
 int fp_tsdf_track(const float* sdf_sum, const int32_t* sdf_cnt, const double* box, int nx, int ny, int nz, int min_count, double trunc_mm,
                   const float* points, int64_t num_rows, const int32_t* row_begin, const int32_t* row_end, const double* R_in,
                   const double* t_in, const int32_t* has_pose, const double* max_dist, int num_det, int max_points, int iters,

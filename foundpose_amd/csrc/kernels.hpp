@@ -424,6 +424,26 @@ struct TsdfExtractArgs {
 int launch_tsdf_integrate(const TsdfIntegrateArgs& a, hipStream_t st);
 int launch_tsdf_extract(const TsdfExtractArgs& a, bool emit, hipStream_t st);
 
+// ---------------------------------------------------------------- simplify.hip
+struct MeshGrid { double ox, oy, oz, c; int nx, ny, nz, pad; };     // cell (i, j, k) spans origin + (i, j, k) c .. + c; x fastest
+struct MeshKeysArgs {
+  MeshGrid grid;
+  const float* verts; long long num_vertices;                       // [V, 3]
+  long long* keys;                                                  // [V]
+};
+struct MeshClusterArgs {
+  MeshGrid grid;
+  const float* verts; const float* colors; long long num_vertices;  // [V, 3] each
+  const int* faces; long long num_faces;                            // [F, 3]
+  const long long* cell_keys; long long num_cells;                  // [C]
+  const long long* vert_order; const long long* vert_begin;         // [V], [C + 1]
+  const long long* corner_order; const long long* corner_begin;     // [3 F], [C + 1]
+  double eig_eps;
+  float* pos; float* col; double* quadrics; double* means; double* err; int* status;   // [C, 3], [C, 3], [C, 10], [C, 3], [C], [C]
+};
+int launch_mesh_cell_keys(const MeshKeysArgs& a, hipStream_t st);
+int launch_mesh_cluster(const MeshClusterArgs& a, hipStream_t st);
+
 // ---------------------------------------------------------------- tsdf_track.hip (the LM parts: refine_terms.hpp)
 struct TsdfTrackArgs {     // lm.verts are the camera-frame points, lm.cam is not used
   RefineLmArgs lm;

@@ -644,6 +644,98 @@ def tsdf_extract(volume: dict, min_count: int) -> Tuple[torch.Tensor, torch.Tens
     return counts, keys, pos, col
 
 
+def _mesh_grid(fn: str, origin, cell_mm, dims):
+    """The checks the two mesh wrappers share -> (grid fp64 [4] on the host, (nx, ny, nz))."""
+    import numpy as np
+    try:
+        grid = np.ascontiguousarray(np.concatenate([np.asarray(origin, np.float64).reshape(3), [float(cell_mm)]]))
+        nx, ny, nz = (int(d) for d in dims)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{fn}: origin is three numbers, cell_mm one, dims three integers ({e})")
+    if not np.all(np.isfinite(grid)) or not grid[3] > 0:
+        raise ValueError(f"{fn}: the origin must be finite and the cell size finite and > 0")
+    if min(nx, ny, nz) < 1 or max(nx, ny, nz) > _lib.MESH_MAX_DIM:
+        raise ValueError(f"{fn}: dimensions {nx} x {ny} x {nz} outside [1, {_lib.MESH_MAX_DIM}]")
+    return grid, (nx, ny, nz)
+
+
+def _mesh_vertices(fn: str, vertices: torch.Tensor) -> torch.Tensor:
+    require_cuda(vertices)
+    if vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] > _lib.MESH_MAX_ROWS:
+        raise ValueError(f"{fn}: vertices must be float32 [V, 3] with V <= {_lib.MESH_MAX_ROWS}, got {vertices.dtype} {tuple(vertices.shape)}")
+    return vertices.contiguous()
+
+
+def mesh_cell_keys(vertices: torch.Tensor, origin, cell_mm: float, dims) -> torch.Tensor:
+    """fp_mesh_cell_keys: vertices fp32 [V, 3] -> int64 [V], the cell (k ny + j) nx + i of the grid of `dims` = (nx, ny, nz) cells of
+    cell_mm from `origin` each vertex falls into, clamped to the grid.  Checked here, before any launch: ValueError."""
+    fn = "mesh_cell_keys"
+    vertices = _mesh_vertices(fn, vertices)
+    grid, (nx, ny, nz) = _mesh_grid(fn, origin, cell_mm, dims)
+    keys = torch.empty(vertices.shape[0], dtype=torch.int64, device=vertices.device)
+    call("fp_mesh_cell_keys", ptr(vertices), vertices.shape[0], grid.ctypes.data_as(_lib.vp), nx, ny, nz, ptr(keys), stream())
+    return keys
+
+
+def mesh_cluster_tables(keys: torch.Tensor, faces: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The plumbing between the two mesh kernels, all torch: keys int64 [V] (mesh_cell_keys), faces int32 [F, 3] with every index in
+    [0, V) (the caller checks that) -> cells int64 [C] (the occupied cells, ascending: the output vertex order), rank int64 [V] (each
+    vertex's cell), vert_order [V] (vertex ids by (rank, id)) with vert_begin [C + 1], corner_order [3 F] (corner ids 3 f + k by
+    (rank of the corner's vertex, corner id)) with corner_begin [C + 1]."""
+    require_cuda(keys, faces)
+    cells, rank = torch.unique(keys, sorted=True, return_inverse=True)
+    num_cells = cells.shape[0]
+
+    def grouped(r):
+        order = torch.sort(r, stable=True)[1]
+        begin = torch.zeros(num_cells + 1, dtype=torch.int64, device=keys.device)
+        begin[1:] = torch.cumsum(torch.bincount(r, minlength=num_cells), 0)
+        return order.contiguous(), begin
+    vert_order, vert_begin = grouped(rank)
+    corner_order, corner_begin = grouped(rank[faces.reshape(-1).long()])
+    return {"cells": cells.contiguous(), "rank": rank, "vert_order": vert_order, "vert_begin": vert_begin, "corner_order": corner_order,
+            "corner_begin": corner_begin}
+
+
+def mesh_cluster(vertices: torch.Tensor, colors: torch.Tensor, faces: torch.Tensor, tables: Dict[str, torch.Tensor], origin, cell_mm: float,
+                 dims, eig_eps: float = 1e-3) -> Dict[str, torch.Tensor]:
+    """fp_mesh_cluster: one vertex per occupied cell of `tables` (mesh_cluster_tables), placed where the summed plane quadrics of the
+    faces touching the cell are smallest.  vertices, colors fp32 [V, 3], faces int32 [F, 3] (F may be 0) ->
+    dict(positions fp32 [C, 3], colors fp32 [C, 3], quadrics fp64 [C, 10], means fp64 [C, 3], err fp64 [C], status int32 [C]: the
+    number of kept eigenvalues, or -1 where the solve left the cell's neighbourhood and the mean was taken).  Checked here, before any
+    launch: ValueError."""
+    import math
+    fn = "mesh_cluster"
+    vertices = _mesh_vertices(fn, vertices)
+    require_cuda(colors, faces, *tables.values())
+    num_v = vertices.shape[0]
+    if colors.dtype != torch.float32 or tuple(colors.shape) != (num_v, 3):
+        raise ValueError(f"{fn}: colors must be float32 [{num_v}, 3], got {colors.dtype} {tuple(colors.shape)}")
+    if faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3 or 3 * faces.shape[0] > _lib.MESH_MAX_ROWS:
+        raise ValueError(f"{fn}: faces must be int32 [F, 3] with 3 F <= {_lib.MESH_MAX_ROWS}, got {faces.dtype} {tuple(faces.shape)}")
+    num_f = faces.shape[0]
+    grid, (nx, ny, nz) = _mesh_grid(fn, origin, cell_mm, dims)
+    if isinstance(eig_eps, bool) or not isinstance(eig_eps, (int, float)) or not math.isfinite(eig_eps) or not 0 <= eig_eps < 1:
+        raise ValueError(f"{fn}: eig_eps must be a number in [0, 1), got {eig_eps!r}")
+    num_c = tables["cells"].shape[0]
+    want = {"cells": num_c, "vert_order": num_v, "vert_begin": num_c + 1, "corner_order": 3 * num_f, "corner_begin": num_c + 1}
+    for name, n in want.items():
+        t = tables[name]
+        if t.dtype != torch.int64 or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"{fn}: tables[{name!r}] must be contiguous int64 [{n}], got {t.dtype} {tuple(t.shape)}")
+    if num_v < 1 or not 1 <= num_c <= num_v:
+        raise ValueError(f"{fn}: {num_v} vertices in {num_c} cells")
+    colors, faces = colors.contiguous(), faces.contiguous()
+    dev = vertices.device
+    out = {"positions": torch.empty(num_c, 3, dtype=torch.float32, device=dev), "colors": torch.empty(num_c, 3, dtype=torch.float32, device=dev),
+           "quadrics": torch.empty(num_c, 10, dtype=torch.float64, device=dev), "means": torch.empty(num_c, 3, dtype=torch.float64, device=dev),
+           "err": torch.empty(num_c, dtype=torch.float64, device=dev), "status": torch.empty(num_c, dtype=torch.int32, device=dev)}
+    call("fp_mesh_cluster", ptr(vertices), ptr(colors), num_v, ptr(faces) if num_f else None, num_f, ptr(tables["cells"]), num_c,
+         ptr(tables["vert_order"]), ptr(tables["vert_begin"]), ptr(tables["corner_order"]) if num_f else None, ptr(tables["corner_begin"]),
+         grid.ctypes.data_as(_lib.vp), nx, ny, nz, float(eig_eps), *(ptr(t) for t in out.values()), stream())
+    return out
+
+
 def _lm_inputs(B: int, R, t, row_begin, row_end, has_pose, feats, vertices, max_points: Optional[int]):
     """The conversions every Levenberg-Marquardt solver (refine_util's three refiners, tsdf_track) makes, in the order they are enqueued, and
     the max_points rule: None is read back from the device.

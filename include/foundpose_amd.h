@@ -1132,6 +1132,49 @@ int fp_tsdf_emit_triangles(const float* sdf_sum, const int32_t* sdf_cnt, const f
                            int nx, int ny, int nz, int min_count, const int64_t* offsets, int64_t num_triangles, int64_t* keys,
                            float* positions, float* colors, fp_stream_t stream);
 
+/* ---- mesh simplification: vertex clustering with quadric error positions (simplify.py; tests/simplify_ref.py
+ *      restates both kernels) ----
+ * The grid: `grid` = HOST fp64 [4] (origin x, y, z, cell size c), all finite and c > 0, and nx x ny x nz cells, x fastest,
+ * 1 <= each dimension <= FP_MESH_MAX_DIM.  vertices fp32 [V, 3] on the device, 0 <= V <= FP_MESH_MAX_ROWS.
+ *
+ * fp_mesh_cell_keys writes keys int64 [V], one thread per vertex.  Per axis, fp64, every operation rounded on its own:
+ *   g = ((double)x - o) / c;  i = floor(g) clamped to [0, n - 1] (a NaN gives 0: no key leaves the grid);  key = (k ny + j) nx + i.
+ * (Added without a change of FP_ABI_VERSION: no existing entry point changed.)
+ *
+ * fp_mesh_cluster places one vertex per occupied cell, one wave per cell.  Device arrays besides vertices: colors fp32 [V, 3], faces
+ * int32 [F, 3] (0 <= 3 F <= FP_MESH_MAX_ROWS; may be NULL when F = 0), and the tables of the C occupied cells (1 <= C <= V), all int64:
+ *   cell_keys    [C]      the cells' keys, as fp_mesh_cell_keys writes them (ascending in simplify.py; the kernel needs no order)
+ *   vert_order   [V]      vertex ids grouped by cell;  vert_begin [C + 1]: cell c owns vert_order[vert_begin[c] .. vert_begin[c + 1])
+ *   corner_order [3 F]    corner ids 3 f + k grouped by the cell of the corner's vertex;  corner_begin [C + 1] likewise
+ * A range is clamped to its array and an id or a face index outside its array contributes nothing: nothing outside the arrays is read.
+ * All in fp64, every operation rounded on its own, square roots IEEE.  A corner record 3 f + k adds its face's plane quadric, the face's
+ * vertices p0, p1, p2 always in the face's own order (never rotated by k, so a face adds the same bits to every cell it touches):
+ *   m = (p1 - p0) x (p2 - p0), L = sqrt(m . m); nothing is added unless L > 0;  n = m / L, w = L / 2, d = -((n0 p0x + n1 p0y) + n2 p0z)
+ *   the ten terms, in output order: (w na) nb for ab = 00, 01, 02, 11, 12, 22;  (w na) d for a = 0, 1, 2;  (w d) d
+ * A face with two or three corners in a cell adds that many times (Garland's per-vertex rule).  Order of every sum: lane l of the wave
+ * starts from 0.0 and adds the cell's records begin + l, begin + l + 64, ... in ascending order; the 64 lanes are then combined by the
+ * xor butterfly at distances 32, 16, ..., 1.  Vertex records are summed the same way, positions and colours widened to fp64.  Then:
+ *   mean = sum p / count;  colour = (float)(sum colour / count)
+ *   A (the six terms) is decomposed by cyclic Jacobi, pairs (0,1), (0,2), (1,2), at most 30 sweeps, stopping when the squared
+ *   off-diagonal mass is not > 1e-30 of the whole; eigenvalue j is kept when lmax > 0 and l_j > eig_eps lmax
+ *   x = mean + sum over kept j = 0, 1, 2 in order of u_j (u_j . g) / l_j, g = -(b + A mean)
+ *   with lo = o + index c per axis: x is accepted when it is finite and lo - c / 2 <= x <= lo + 3 c / 2 on every axis; otherwise
+ *   x = mean and the status is -1.  A cell without a non-degenerate face (or F = 0) has lmax = 0 and gets its mean, status 0.
+ * Outputs per cell: positions fp32 [C, 3], out_colors fp32 [C, 3], quadrics fp64 [C, 10] (the ten sums), means fp64 [C, 3], err fp64 [C]
+ * = x'Ax + 2 b'x + s at the fp64 x (reported, never a criterion), status int32 [C]: the number of kept eigenvalues, or -1.
+ * No atomics; a cell's outputs depend on its own records only, so they are the same bits whatever else is in the call.
+ * eig_eps finite and in [0, 1).  A NULL pointer or a size or option outside its range: FP_ERR_INVALID, nothing written.  (Added without
+ * a change of FP_ABI_VERSION: no existing entry point changed.) */
+#define FP_MESH_MAX_DIM (1 << 20)
+#define FP_MESH_MAX_ROWS 0x7fffffffll
+int fp_mesh_cell_keys(const float* vertices, int64_t num_vertices, const double* grid, int nx, int ny, int nz, int64_t* keys,
+                      fp_stream_t stream);
+int fp_mesh_cluster(const float* vertices, const float* colors, int64_t num_vertices, const int32_t* faces, int64_t num_faces,
+                    const int64_t* cell_keys, int64_t num_cells, const int64_t* vert_order, const int64_t* vert_begin,
+                    const int64_t* corner_order, const int64_t* corner_begin, const double* grid, int nx, int ny, int nz, double eig_eps,
+                    float* positions, float* out_colors, double* quadrics, double* means, double* err, int32_t* status,
+                    fp_stream_t stream);
+
 /* ---- featuremetric refinement of the best coarse pose (tests/featuremetric_ref.py restates it) ----
  * Levenberg-Marquardt on the 6-DoF pose of each of num_det detections, aligning a template's per-point features with the
  * query's projected patch-feature map.  Device arrays:
