@@ -66,6 +66,9 @@ FP_DEVICE bf16x8 read_frag(const char* lds, int row, int chunk) {
 // magnitude below the bf16 half-ulp (2e-3) of the stored result -- at 6 VALU instructions per element instead of the
 // ~27 instruction-equivalents of an erf built from v_rcp + v_exp.  With 128 outputs per lane this epilogue was ~10 us
 // of VALU time per 256x256 tile, a third of fc1's run time (exact-erf GELU stays in the fp32 path, f32_tile.hip).
+// Beyond the clamp the result is x Phi_poly(+-3.9) with Phi_poly(3.9) = 1 + 3.37e-5 and Phi_poly(-3.9) = -3.37e-5: the error grows like 3.4e-5 |x| on both
+// sides and the negative tail has the WRONG SIGN (gelu_pk(-100) = +3.4e-3).  Pinned, with the bound above, by tests/test_gpu_pointwise.py against the fp32
+// restatement in tests/pointwise_ref.py (8.25e-5 |x| on 2 million points, tests/test_pointwise_cpu.py).
 FP_DEVICE f32x2 gelu_pk(f32x2 x) {
   constexpr float X = 3.9f;
   f32x2 xc;
@@ -84,7 +87,8 @@ FP_DEVICE f32x2 gelu_pk(f32x2 x) {
 }
 
 // ... and for the fp16 epilogue ("f16" mode; its stored result carries 11 bits): the same form with nine coefficients on |x| <= 4.4, fitted under the
-// constraint that x q(x^2) reaches 0.5 at the clamp (Phi = 1 exactly above it, -2.6e-8 below: no tail error that grows with |x|) and weighted by |x| (what
+// constraint that x q(x^2) reaches 0.5 at the clamp (Phi = 1 exactly above it: no positive tail error; -2.57e-8 below it, so the negative tail is +2.6e-8 |x|,
+// positive and growing, 1300 times smaller than the seven-coefficient form's -- tests/test_gpu_pointwise.py pins both) and weighted by |x| (what
 // is minimised is the error of GELU itself; constrained Lawson iteration, last coefficient adjusted in fp32): max |gelu error| 3.8e-5 in fp32 evaluation
 // against 4.0e-4 of the seven-coefficient form above -- below the rounding of an fp16 result of magnitude >= 0.08 -- at 7 VALU instructions per element
 // against ~12 of the erf form below.  Same index agreement with the fp32 mode as the erf form in same-box runs (154 / 143 against 156 / 141 slots of 160).
@@ -111,8 +115,9 @@ FP_DEVICE f32x2 gelu_pk9(f32x2 x) {
 // erfc(z) exp(z^2) is a degree-7 polynomial in t = 1 / (1 + 0.3275911 z) on z >= 0 (the Abramowitz-Stegun 7.1.26 form with two more
 // terms, refitted minimax against scipy's erfcx: |d erf| <= 3.5e-9 before rounding), and gelu(x) = x/2 + |x|/2 erf(|x| / sqrt 2), so
 // no sign handling and no cancellation for x > 0.  Evaluated in fp32 on two elements per instruction (v_pk_fma_f32) + one v_rcp_f32 and
-// one v_exp_f32 each: max |error| 4.2e-7 over [-12, 12] against the exact function -- closer to it than torch's own CPU gelu (1.2e-6,
-// tools/gelu_accuracy.py) and than the f16x3 products (2^-22 relative) -- at ~12 instruction-equivalents per element; ocml's erff cost ~35
+// one v_exp_f32 each: max |error| 4.2e-7 over [-12, 12] against the exact function (3.0e-7 with rcp and exp2 correctly rounded: the restatement in
+// tests/pointwise_ref.py on 2 million points, tests/test_pointwise_cpu.py; tests/test_gpu_pointwise.py holds the kernel to the 4.2e-7) -- closer to it
+// than torch's own CPU gelu (1.2e-6) and than the f16x3 products (2^-22 relative) -- at ~12 instruction-equivalents per element; ocml's erff cost ~35
 // and a sixth of the fc1 launch.
 FP_DEVICE f32x2 gelu_erf_pk(f32x2 x) {
   const f32x2 hx = x * f32x2{0.5f, 0.5f};
@@ -158,7 +163,9 @@ FP_DEVICE float row16_sum(float v) {
 // FP8 (F8 below): the operands are OCP fp8 (e4m3) instead of bf16.  An fp8 row of K elements is addressed as a bf16 row of K/2
 // elements (the host passes K/2, lda/2, ldw/2), so a K-tile is the same 128-B-per-row LDS image holding 128 k-values and
 // the staging code is shared; the tile is consumed by two v_mfma_scale_f32_32x32x64_f8f6f4 per accumulator (unit block
-// scales: plain fp8 products, fp32 accumulation, twice the bf16 MFMA rate) whose operand -- lane (row, kh) holds k =
+// scales: plain fp8 products, fp32 accumulation -- but NOT an exact sum of the 64 products of an instruction: each is aligned to the largest of them and cut off
+// (toward zero) below 2^-13 of that one's binade, measured bit for bit by the exactness construction of tests/pointwise_ref.py, DESIGN.md section 33 -- twice
+// the bf16 MFMA rate) whose operand -- lane (row, kh) holds k =
 // 32 kh .. 32 kh + 31 of a 64-wide step, tools/ubench/fp8_probe.hip -- is two adjacent 16-B chunks of the row.
 // Dequantisation lives in the epilogue: out = (acc + bias) * gamma with gamma = activation scale x per-channel weight
 // scale (x LayerScale) and bias pre-divided by that scale on the host.

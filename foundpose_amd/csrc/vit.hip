@@ -430,7 +430,10 @@ __global__ __launch_bounds__(256) void rowstats_cast_kernel(const float* __restr
 }
 
 // Folded LayerNorm: the residual GEMM's column tiles leave `parts` partial sums per row; one thread per row adds them in
-// slot order and leaves (rstd, mean * rstd), the two numbers the next GEMM's epilogue needs.
+// slot order and leaves (rstd, mean * rstd), the two numbers the next GEMM's epilogue needs.  The variance is s2 / D - mu^2 in fp32: it loses
+// kappa = E[x^2] / var times the fp32 unit (measured: relative rstd error <= 2.5 kappa 2^-24 -- 1e-5 at |mean| / std = 10, 1e-3 at 100, 6 to 8 % at 1000; it
+// reaches a bf16 half-ulp at |mean| / std of about 120), and a constant row c comes out at var = +-c^2 2^-24 instead of 0 unless 1 / D is a power of two.
+// tests/test_gpu_pointwise.py holds the kernel to that envelope, DESIGN.md section 33 records it.
 __global__ void ln_finalize_kernel(const float2* __restrict__ partial, int parts, int stride, int rows, float inv_dim, float eps, float2* __restrict__ out) {
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= rows) return;
