@@ -123,6 +123,7 @@ _PROTOS = {
     "fp_tsdf_integrate": [vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, f64, vp, C.c_size_t, vp, vp, vp, vp, vp],
     "fp_tsdf_count_triangles": [vp, vp, i32, i32, i32, i32, vp, vp],
     "fp_tsdf_emit_triangles": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp],
+    "fp_tsdf_diffuse": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "fp_mesh_cell_keys": [vp, i64, vp, i32, i32, i32, vp, vp],
     "fp_mesh_cluster": [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, f64, vp, vp, vp, vp, vp, vp, vp],
     "fp_tsdf_track": [vp, vp, vp, i32, i32, i32, i32, f64, vp, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp,
@@ -267,6 +268,7 @@ def component_table_scratch_bytes(num_frames: int, pixels: int) -> int:
 
 
 TSDF_MAX_DIM, TSDF_MAX_VOXELS, TSDF_MAX_FRAMES, TSDF_FRAME_DOUBLES = 512, 1 << 27, 4096, 16  # FP_TSDF_* of the header
+TSDF_DIFFUSE_MAX_ITERS = 4096  # FP_TSDF_DIFFUSE_MAX_ITERS
 
 
 MESH_MAX_DIM, MESH_MAX_ROWS = 1 << 20, 2**31 - 1  # FP_MESH_* of the header

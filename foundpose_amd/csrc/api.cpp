@@ -1280,6 +1280,31 @@ int fp_tsdf_emit_triangles(const float* sdf_sum, const int32_t* sdf_cnt, const f
   return launch_tsdf_extract(a, true, ST(stream));
 }
 
+int fp_tsdf_diffuse(float* val, uint8_t* state, float* val_tmp, uint8_t* state_tmp, int channels, int nx, int ny, int nz, int iters,
+                    fp_stream_t stream) {
+  FP_REQUIRE(val && state && val_tmp && state_tmp, "fp_tsdf_diffuse: null pointer");
+  FP_REQUIRE(val != val_tmp && state != state_tmp, "fp_tsdf_diffuse: the scratch buffers must not be the buffers themselves");
+  FP_REQUIRE(channels == 1 || channels == 3, "fp_tsdf_diffuse: channels %d must be 1 or 3", channels);
+  FP_REQUIRE(iters >= 0 && iters <= FP_TSDF_DIFFUSE_MAX_ITERS, "fp_tsdf_diffuse: iters %d outside [0, %d]", iters, FP_TSDF_DIFFUSE_MAX_ITERS);
+  TsdfVolume vol;
+  TRY(tsdf_volume("fp_tsdf_diffuse", nullptr, nx, ny, nz, 1, vol));
+  TsdfDiffuseArgs a;
+  memset(&a, 0, sizeof(a));
+  a.channels = channels, a.nx = nx, a.ny = ny, a.nz = nz;
+  for (int t = 0; t < iters; ++t) {                                 // even iterations read the buffers, odd ones the scratch
+    const bool fwd = t % 2 == 0;
+    a.val = fwd ? val : val_tmp, a.state = fwd ? state : state_tmp;
+    a.val_out = fwd ? val_tmp : val, a.state_out = fwd ? state_tmp : state;
+    TRY(launch_tsdf_diffuse(a, ST(stream)));
+  }
+  if (iters % 2 == 1) {                                             // the result lands in val / state
+    const size_t n = (size_t)nx * ny * nz;
+    HIP_TRY(hipMemcpyAsync(val, val_tmp, sizeof(float) * n * channels, hipMemcpyDeviceToDevice, ST(stream)), "fp_tsdf_diffuse: copy back");
+    HIP_TRY(hipMemcpyAsync(state, state_tmp, n, hipMemcpyDeviceToDevice, ST(stream)), "fp_tsdf_diffuse: copy back");
+  }
+  return FP_OK;
+}
+
 // ------------------------------------------------------------------ mesh simplification (simplify.hip)
 }  // extern "C"
 

@@ -424,6 +424,14 @@ struct TsdfExtractArgs {
 int launch_tsdf_integrate(const TsdfIntegrateArgs& a, hipStream_t st);
 int launch_tsdf_extract(const TsdfExtractArgs& a, bool emit, hipStream_t st);
 
+// ---------------------------------------------------------------- tsdf_fill.hip
+struct TsdfDiffuseArgs {                                            // one Jacobi iteration: (val, state) -> (val_out, state_out)
+  const float* val; const uint8_t* state;                           // [channels, nz, ny, nx], [nz, ny, nx]: 0 UNKNOWN, 1 FIXED, 2 FREE
+  float* val_out; uint8_t* state_out;
+  int channels, nx, ny, nz;
+};
+int launch_tsdf_diffuse(const TsdfDiffuseArgs& a, hipStream_t st);
+
 // ---------------------------------------------------------------- simplify.hip
 struct MeshGrid { double ox, oy, oz, c; int nx, ny, nz, pad; };     // cell (i, j, k) spans origin + (i, j, k) c .. + c; x fastest
 struct MeshKeysArgs {

@@ -644,6 +644,32 @@ def tsdf_extract(volume: dict, min_count: int) -> Tuple[torch.Tensor, torch.Tens
     return counts, keys, pos, col
 
 
+def tsdf_diffuse(val: torch.Tensor, state: torch.Tensor, iters: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`iters` Jacobi iterations of fp_tsdf_diffuse on val fp32 [C, nz, ny, nx], C 1 or 3, and state uint8
+    [nz, ny, nx] (0 UNKNOWN, 1 FIXED, 2 FREE) -> (val', state'), new tensors; the arguments are left as they are.  CPU tensors, other
+    dtypes or shapes, a state value above 2 (one read-back) and iters outside 0 .. 4096 are refused here, before any launch: ValueError."""
+    fn = "tsdf_diffuse"
+    for name, t, dt, nd in (("val", val, torch.float32, 4), ("state", state, torch.uint8, 3)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{fn}: {name} must be a tensor on the device (there is no CPU path)")
+        if t.dtype != dt or t.dim() != nd:
+            raise ValueError(f"{fn}: {name} must be {dt} with {nd} dimensions, got {t.dtype} {tuple(t.shape)}")
+    c, nz, ny, nx = (int(d) for d in val.shape)
+    if c not in (1, 3) or tuple(state.shape) != (nz, ny, nx):
+        raise ValueError(f"{fn}: val {tuple(val.shape)} must be [1 or 3, nz, ny, nx] and state {tuple(state.shape)} its [nz, ny, nx]")
+    if min(nx, ny, nz) < 1 or max(nx, ny, nz) > _lib.TSDF_MAX_DIM or nx * ny * nz > _lib.TSDF_MAX_VOXELS:
+        raise ValueError(f"{fn}: dimensions {nx} x {ny} x {nz} outside [1, {_lib.TSDF_MAX_DIM}] or beyond {_lib.TSDF_MAX_VOXELS} voxels")
+    if isinstance(iters, bool) or not hasattr(iters, "__index__") or not 0 <= int(iters) <= _lib.TSDF_DIFFUSE_MAX_ITERS:
+        raise ValueError(f"{fn}: iters must be an integer in [0, {_lib.TSDF_DIFFUSE_MAX_ITERS}], got {iters!r}")
+    if int(state.max()) > 2:
+        raise ValueError(f"{fn}: state holds {int(state.max())}; 0 UNKNOWN, 1 FIXED and 2 FREE are the states")
+    val, state = val.contiguous().clone(), state.contiguous().clone()
+    if int(iters) > 0:
+        val_tmp, state_tmp = torch.empty_like(val), torch.empty_like(state)
+        call("fp_tsdf_diffuse", ptr(val), ptr(state), ptr(val_tmp), ptr(state_tmp), c, nx, ny, nz, int(iters), stream())
+    return val, state
+
+
 def _mesh_grid(fn: str, origin, cell_mm, dims):
     """The checks the two mesh wrappers share -> (grid fp64 [4] on the host, (nx, ny, nz))."""
     import numpy as np

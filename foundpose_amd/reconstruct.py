@@ -16,8 +16,15 @@ tracked against the volume fused so far (fp_tsdf_track) and fused at its tracked
 --tracked-poses writes the poses per sequence in scene_gt.json's format.  With `track_color_weight` > 0 a frame
 is tracked on shape and on the colour the volume holds (fp_tsdf_track_rgb): for objects whose shape leaves a rotation open.
 
-Limits: with pose_source "given" poses and masks are trusted as given; a voxel reads the nearest depth pixel, across depth edges too; surface that no frame
-saw stays open (the report says so, nothing is filled); no accuracy on real BOP data is claimed."""
+With opts `fill: "carve"` the fused volume is closed before extraction (fill_volume): whatever no frame saw
+empty counts as inside, `fill_plane` declares the half-space of the table empty, the volume's outermost voxel layer is outside, and
+`fill_smooth_iters` iterations of a volumetric diffusion (fp_tsdf_diffuse) take the voxel staircase off the invented surface while
+`fill_color_iters` iterations carry colour onto it; every vertex between two observed voxels keeps its bits.
+
+Limits: with pose_source "given" poses and masks are trusted as given; a voxel reads the nearest depth pixel, across depth edges too; with
+fill "none", the default, surface that no frame saw stays open (the report says so, nothing is filled); fill "carve" closes it with the
+visual hull of what the frames carved, so an overhang no frame looked under is filled solid, and a background without valid depth carves
+nothing; no accuracy on real BOP data is claimed."""
 
 import argparse
 import json
@@ -32,6 +39,8 @@ from .gt_info import _read_json, refuse_existing
 
 PAD_FRACTION = 0.05                # automatic bounds: 2 tau + this share of the extent on every side
 PERCENTILES = (0.5, 99.5)          # ... around these percentiles of the masked depth points, per axis
+FILL_MAX_ITERS = 4096              # FP_TSDF_DIFFUSE_MAX_ITERS
+FILL_SNAP = 2.0 ** -10             # a filled value closer to zero than this becomes this: an exact 0 is outside, and a vertex on a corner collapses its triangle
 
 
 class ReconstructOpts(NamedTuple):
@@ -51,6 +60,11 @@ class ReconstructOpts(NamedTuple):
     track_motion: str = "velocity"   # "velocity" or "hold": how a frame's start pose is predicted
     track_min_inlier_share: float = 0.5   # a tracked frame below this share of inliers is lost
     track_max_lost: int = 3        # consecutive lost frames allowed
+    fill: str = "none"             # "none": surface no frame saw stays open; "carve": the volume is closed before extraction (section 34); the
+                                   # fill fields stand before the two colour fields, which tests/test_tsdf_track_rgb_cpu.py pins as the last
+    fill_smooth_iters: int = 4     # diffusion iterations over the distances the fill invents; more iterations erode the filled part
+    fill_color_iters: int = 64     # diffusion iterations that carry colour onto voxels without one
+    fill_plane: Optional[Tuple[float, float, float, float]] = None   # (a, b, c, d), model frame, mm: a x + b y + c z + d > 0 is known to be empty
     track_color_weight: float = 0.0   # mm per unit of colour; 0: frames are tracked on shape alone, > 0: on shape and colour (section 31)
     track_color_max: float = 0.25  # a colour channel further than this from the volume's colour is an outlier
 
@@ -71,6 +85,8 @@ def load_opts(path_or_dict=None) -> ReconstructOpts:
     d = dict(d.get("reconstruct_opts", d))
     if d.get("bounds") is not None:
         d["bounds"] = tuple(tuple(float(v) for v in row) for row in d["bounds"])
+    if isinstance(d.get("fill_plane"), list):
+        d["fill_plane"] = tuple(d["fill_plane"])
     return check_opts(ReconstructOpts(**d))
 
 
@@ -108,6 +124,17 @@ def check_opts(o: ReconstructOpts) -> ReconstructOpts:
     v = o.track_color_max
     if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and v > 0):
         raise ValueError(f"track_color_max must be finite and > 0, got {v!r}")
+    if o.fill not in ("none", "carve"):
+        raise ValueError(f"fill must be 'none' or 'carve', got {o.fill!r}")
+    for name in ("fill_smooth_iters", "fill_color_iters"):
+        v = getattr(o, name)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or v < 0 or v > FILL_MAX_ITERS:
+            raise ValueError(f"{name} must be an integer >= 0 and <= {FILL_MAX_ITERS}, got {v!r}")
+    if o.fill_plane is not None:
+        v = o.fill_plane
+        if (not isinstance(v, (tuple, list)) or len(v) != 4 or any(isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) for c in v)
+                or not any(c != 0 for c in v[:3])):
+            raise ValueError(f"fill_plane must be null or four finite numbers (a, b, c, d) with (a, b, c) != 0, got {v!r}")
     return o
 
 
@@ -486,6 +513,93 @@ def fuse_tracked(frames: Sequence[Frame], given: Sequence[Optional[np.ndarray]],
     return vol, poses, records
 
 
+def fill_volume(volume: Dict[str, Any], opts=None) -> Tuple[Dict[str, Any], Dict[str, Any]]:
+    """Closes a fused volume (tests/tsdf_fill_ref.py restates it bit for bit) -> (volume', stats).  The input is
+    left as it is; volume' is extracted with min_count = 1.  Elementwise torch on the device, every operation rounded on its own, around
+    two runs of fp_tsdf_diffuse:
+      1  f = (float)((double)sdf_sum / (double)sdf_cnt) where sdf_cnt > 0
+      2  src = sdf_cnt >= min_count; g = f where sdf_cnt > 0, else -1 (unseen is inside); fixed = src
+      3  fill_plane (a, b, c, d): non-src voxels whose centre has ((a X + b Y) + c Z) + d > 0 (fp64) get g = +1 and are fixed
+      4  the outermost voxel layer gets g = +1 and is fixed, whatever it held
+      5  fill_smooth_iters iterations of fp_tsdf_diffuse on g: FIXED where fixed, else FREE
+      6  non-fixed voxels with |g| < 2^-10 become +2^-10
+      7  src voxels off the outer layer keep sdf_sum and sdf_cnt; every other voxel gets sdf_sum = g, sdf_cnt = 1
+      8  m = rgb_sum / (float)rgb_cnt where rgb_cnt > 0: FIXED there, UNKNOWN elsewhere; fill_color_iters iterations on the three
+         channels; voxels that became FREE get rgb_sum = m, rgb_cnt = 1, the others keep what they had
+    stats: filled_voxels (non-src voxels that end inside), plane_voxels (step 3), clipped_voxels (src voxels of the outer layer with
+    f < 0: there the object sticks out of the bounds and gets a flat cap), snapped_voxels (step 6), uncoloured_voxels (voxels at an end
+    of a sign-changing edge of the tetrahedral split that still have no colour), smooth_iters, color_iters, last_change (the largest
+    |g_T - g_(T-1)| over non-fixed voxels; 0 when T = 0) and seconds."""
+    import torch
+
+    from . import ops
+    opts = load_opts(opts)
+    t0 = time.perf_counter()
+    nx, ny, nz = (int(d) for d in volume["dims"])
+    ops._tsdf_state("fill_volume", volume, (nx, ny, nz))
+    if min(nx, ny, nz) < 3:
+        raise ValueError(f"fill_volume: a volume of {nx} x {ny} x {nz} voxels has no interior: every dimension must be >= 3")
+    dev = volume["sdf_sum"].device
+    f32 = lambda x: torch.tensor(x, dtype=torch.float32, device=dev)   # noqa: E731
+    cnt = volume["sdf_cnt"]
+    seen, src = cnt > 0, cnt >= int(opts.min_count)
+    f = (volume["sdf_sum"].double() / cnt.double()).float()
+    g = torch.where(seen, f, f32(-1.0))
+    fixed = src.clone()
+    plane_voxels = 0
+    if opts.fill_plane is not None:
+        a, b, c, d = (float(v) for v in opts.fill_plane)
+        centre = lambda o, n: float(o) + (torch.arange(n, dtype=torch.float64, device=dev) + 0.5) * float(volume["voxel_mm"])   # noqa: E731
+        X, Y, Z = centre(volume["origin"][0], nx)[None, None, :], centre(volume["origin"][1], ny)[None, :, None], centre(volume["origin"][2], nz)[:, None, None]
+        empty = ~src & ((((a * X + b * Y) + c * Z) + d) > 0)
+        g = torch.where(empty, f32(1.0), g)
+        fixed |= empty
+        plane_voxels = int(empty.sum())
+    outer = torch.zeros_like(fixed)
+    outer[[0, -1]] = True
+    outer[:, [0, -1]] = True
+    outer[:, :, [0, -1]] = True
+    clipped = int((outer & src & (f < 0)).sum())
+    g = torch.where(outer, f32(1.0), g)
+    fixed |= outer
+    state = torch.where(fixed, 1, 2).to(torch.uint8)
+    T = int(opts.fill_smooth_iters)
+    free = ~fixed
+    last_change = 0.0
+    if T > 0:
+        before = ops.tsdf_diffuse(g[None], state, T - 1)[0]
+        g = ops.tsdf_diffuse(before, state, 1)[0][0]                              # T - 1 iterations and one more: the bits of T in one call
+        if bool(free.any()):
+            last_change = float((g - before[0]).abs()[free].max())
+    snap = free & (g.abs() < FILL_SNAP)
+    g = torch.where(snap, f32(FILL_SNAP), g)
+    keep = src & ~outer
+    out = dict(volume)
+    out["sdf_sum"] = torch.where(keep, volume["sdf_sum"], g).contiguous()
+    out["sdf_cnt"] = torch.where(keep, cnt, 1).to(torch.int32).contiguous()
+    has = volume["rgb_cnt"] > 0
+    m = (volume["rgb_sum"].double() / volume["rgb_cnt"].double()[None]).float()   # fp32 operands: the fp64 quotient rounds to the fp32 one
+    m = torch.where(has[None], m, f32(0.0))
+    m, cstate = ops.tsdf_diffuse(m, torch.where(has, 1, 0).to(torch.uint8), int(opts.fill_color_iters))
+    got = cstate == 2
+    out["rgb_sum"] = torch.where(got[None], m, volume["rgb_sum"]).contiguous()
+    out["rgb_cnt"] = torch.where(got, 1, volume["rgb_cnt"]).to(torch.int32).contiguous()
+    inside = torch.where(keep, f, g) < 0
+    near = torch.zeros_like(inside)
+    for dx, dy, dz in ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (0, 1, 1), (1, 0, 1), (1, 1, 1)):   # the edges of the tetrahedral split
+        lo = (slice(0, nz - dz), slice(0, ny - dy), slice(0, nx - dx))
+        hi = (slice(dz, nz), slice(dy, ny), slice(dx, nx))
+        cross = inside[lo] != inside[hi]
+        near[lo] |= cross
+        near[hi] |= cross
+    stats = {"filled_voxels": int((~src & inside).sum()), "plane_voxels": plane_voxels, "clipped_voxels": clipped, "snapped_voxels": int(snap.sum()),
+             "uncoloured_voxels": int((near & (out["rgb_cnt"] == 0)).sum()), "smooth_iters": T, "color_iters": int(opts.fill_color_iters),
+             "last_change": last_change}
+    torch.cuda.synchronize()
+    stats["seconds"] = time.perf_counter() - t0
+    return out, stats
+
+
 def extract_mesh(volume: Dict[str, Any], opts=None):
     """The surface of a fused volume -> renderer.Mesh.  Triangle corners are welded on the device by their edge keys (torch.unique: the
     sorted key order is the vertex order), triangles whose three welded positions are not pairwise distinct are dropped, with
@@ -577,7 +691,10 @@ def reconstruct(sequences: Sequence[str], obj_id: int, output_dir: str, opts=Non
     observed = int((vol["sdf_cnt"] >= opts.min_count).sum())
     torch.cuda.synchronize()
     t_fuse = time.perf_counter()
-    mesh = extract_mesh(vol, opts)
+    fill = None
+    if opts.fill == "carve":                                                     # the same step after fuse and after fuse_tracked (section 34)
+        vol, fill = fill_volume(vol, opts)
+    mesh = extract_mesh(vol, opts if fill is None else opts._replace(min_count=1))
     t_mesh = time.perf_counter()
     os.makedirs(output_dir, exist_ok=True)
     save_ply(out_path, mesh)
@@ -595,8 +712,12 @@ def reconstruct(sequences: Sequence[str], obj_id: int, output_dir: str, opts=Non
               "opts": opts._asdict(), "bounds": [lo.tolist(), (lo + np.asarray(vol["dims"]) * vol["voxel_mm"]).tolist()],
               "dims": list(vol["dims"]), "observed_voxels": observed, "vertices": int(len(mesh.vertices)), "triangles": int(len(mesh.faces)),
               **topo,
-              "note": None if topo["watertight"] else "the surface is open where no frame saw it; nothing is filled",
+              "note": None if topo["watertight"] else ("the surface is open where no frame saw it; nothing is filled" if fill is None else
+                                                       "the filled surface is still open: an observed value that is exactly 0 counts as outside and puts "
+                                                       "its vertices on the voxel's corner, where welding drops the collapsed triangles"),
               "seconds": {"read": t_read - t0, "fuse": t_fuse - t_read, "extract": t_mesh - t_fuse, "total": time.perf_counter() - t0}}
+    if fill is not None:
+        report["fill"] = fill                                                    # its seconds are part of "extract"
     if tracking is not None:
         report["tracking"] = tracking
     if report_path:
@@ -610,7 +731,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--sequence", action="append", required=True, help="a BOP scene directory; repeat to fuse several, in order")
     ap.add_argument("--obj-id", type=int, required=True)
     ap.add_argument("--output", required=True, help="the models directory obj_%%06d.ply is written into")
-    ap.add_argument("--opts", default=None, help="JSON with ReconstructOpts fields")
+    ap.add_argument("--opts", default=None, help="JSON with ReconstructOpts fields; fill: \"carve\" closes the surface no frame saw (fill_smooth_iters, "
+                    "fill_color_iters, fill_plane: [a, b, c, d] with a x + b y + c z + d > 0 known to be empty, model frame, mm)")
     ap.add_argument("--report", default=None, help="write the report to this JSON file")
     ap.add_argument("--overwrite", action="store_true", help="replace an existing output")
     ap.add_argument("--device", default="cuda")
@@ -621,6 +743,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         tot = r["tracking"]["totals"]
         print(f"tracking: {tot['anchor']} anchor(s), {tot['tracked']} tracked, {tot['lost']} lost in {r['tracking']['seconds']:.2f} s"
               + (f" (on shape and colour, weight {tot['color_weight']:g} mm per unit)" if "color_weight" in tot else ""))
+    if "fill" in r:
+        fl = r["fill"]
+        print(f"fill: {fl['filled_voxels']} voxel(s) filled, {fl['plane_voxels']} emptied by the plane, {fl['clipped_voxels']} clipped at the bounds, "
+              f"{fl['uncoloured_voxels']} at the surface without colour in {fl['seconds']:.2f} s")
     print(f"{r['output']}: {r['vertices']} vertices, {r['triangles']} triangles from {r['frames_used']} frame(s) in a volume of "
           f"{r['dims'][0]} x {r['dims'][1]} x {r['dims'][2]} voxels; {r['boundary_edges']} boundary edge(s), "
           f"{'watertight' if r['watertight'] else 'open: ' + str(r['note'])}; {r['seconds']['total']:.2f} s")

@@ -1132,6 +1132,26 @@ int fp_tsdf_emit_triangles(const float* sdf_sum, const int32_t* sdf_cnt, const f
                            int nx, int ny, int nz, int min_count, const int64_t* offsets, int64_t num_triangles, int64_t* keys,
                            float* positions, float* colors, fp_stream_t stream);
 
+/* ---- diffusion over a TSDF volume's grid: the smoother of hole filling (reconstruct.py, fill "carve"; DESIGN.md section 34;
+ *      tests/tsdf_fill_ref.py restates it) ----
+ * Device arrays: val fp32 [channels, nz, ny, nx] (x fastest, channels 1 or 3), state uint8 [nz, ny, nx] with 0 UNKNOWN, 1 FIXED, 2 FREE
+ * (any other value is the caller's error: the wrapper refuses it; the kernel reads it as FREE).  Dimensions 1 .. FP_TSDF_MAX_DIM each and
+ * nx ny nz <= FP_TSDF_MAX_VOXELS.  fp_tsdf_diffuse runs `iters` (0 .. FP_TSDF_DIFFUSE_MAX_ITERS; 0 touches nothing) Jacobi iterations,
+ * each reading only the iteration before it, and leaves the result in val / state; val_tmp / state_tmp are scratch of the same sizes,
+ * distinct from them, and hold nothing the caller may rely on afterwards.  One iteration, per voxel:
+ *   a FIXED voxel keeps its value and its state;
+ *   any other voxel visits, in the order centre, -x, +x, -y, +y, -z, +z, those of the seven that lie inside the volume and are not
+ *   UNKNOWN.  n is their number, the same for every channel; per channel acc starts at +0.0f and adds their values in that order in
+ *   fp32.  n = 0: the voxel stays (or becomes) UNKNOWN and its value +0.0f.  Otherwise its value is acc / (float)n (IEEE division) and
+ *   its state FREE.
+ * The value stored in an UNKNOWN voxel is never an operand: it is selected away, not multiplied by a mask, so a NaN there does not
+ * spread.  Every output is a pure function of the previous iteration's seven voxels, so the bits are the same for any tiling, vector
+ * width or split of T iterations into calls.  A NULL pointer, aliased scratch or a size outside its range: FP_ERR_INVALID, nothing
+ * written.  (Added without a change of FP_ABI_VERSION: no existing entry point changed.) */
+#define FP_TSDF_DIFFUSE_MAX_ITERS 4096
+int fp_tsdf_diffuse(float* val, uint8_t* state, float* val_tmp, uint8_t* state_tmp, int channels, int nx, int ny, int nz, int iters,
+                    fp_stream_t stream);
+
 /* ---- mesh simplification: vertex clustering with quadric error positions (simplify.py; tests/simplify_ref.py
  *      restates both kernels) ----
  * The grid: `grid` = HOST fp64 [4] (origin x, y, z, cell size c), all finite and c > 0, and nx x ny x nz cells, x fastest,
