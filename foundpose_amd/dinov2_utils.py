@@ -475,6 +475,27 @@ class DinoFeatureExtractor(torch.nn.Module):
                 "act_scales= (the table stored with the bank) or call calibrate_fp8(calibration_images) once")
         return images, B, H, W, gh, gw, ws
 
+    def embed_tokens(self, images: torch.Tensor, prefill=None, row_stats: bool = False) -> Dict[str, torch.Tensor]:
+        """The token embedding alone (fp_vit_forward with layer = -1, as calibrate_fp8 runs it): no block.  -> the LIVE workspace tensors of the
+        batch shape by name: patches (the patch GEMM's operand rows), x (the fp32 token rows) and, for a folded model, xb, xl, stats.
+        prefill(tensors), if given, is called on them before the launch -- the tests fill the workspace with a sentinel, so that a row or a padding
+        column the front forgets, or writes beyond its share, shows.  row_stats (folded models): fp_vit_forward_prefix with layer = 0 instead: the
+        embedding plus the entry of the folded-LayerNorm chain (xb, xl and the row sums), still no block."""
+        if self._model is None:
+            raise _lib.FoundPoseNativeError("call extractor.to('cuda') before running it")
+        images, B, H, W, gh, gw, ws = self._batch(images)
+        bufs = self._workspace(B, gh, gw)[1]
+        live = {"patches": bufs[0], "x": bufs[1]}
+        if self.fold_layernorm:
+            live["xb"], live["stats"], live["xl"] = bufs[-3:]
+        if prefill is not None:
+            prefill(live)
+        if row_stats:
+            call("fp_vit_forward_prefix", C.byref(self._model), C.byref(ws), ptr(images), B, H, W, 0, stream())
+        else:
+            call("fp_vit_forward", C.byref(self._model), C.byref(ws), ptr(images), B, H, W, -1, stream())
+        return live
+
     def forward_tokens(self, images: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> (fmap [B, Np, D] fp32 token-major, cls [B, D] fp32); the batched fast-path entry."""
         if self._model is None:
