@@ -362,6 +362,13 @@ int fp_pose_nms_greedy(const int32_t* group_off, const int32_t* pair_off, int nu
   return launch_pose_nms_greedy(a, num_groups, ST(stream));
 }
 
+static GroupTables group_tables(const int32_t* est_off, const int32_t* gt_off, const int32_t* pair_off, int num_groups, int num_a, int num_b,
+                                int num_pairs) {
+  GroupTables t;
+  t.est_off = est_off; t.gt_off = gt_off; t.pair_off = pair_off; t.n_groups = num_groups; t.n_a = num_a; t.n_b = num_b; t.n_pairs = num_pairs;
+  return t;
+}
+
 int fp_detection_match(const int32_t* est_off, const int32_t* gt_off, const int32_t* pair_off, int num_groups, const double* err,
                        int num_pairs, const int32_t* gt_valid, int num_gt, const int32_t* group_tab, const double* ths, int num_tabs,
                        int num_ths, int num_est, int8_t* out_flag, int32_t* out_matched_gt, fp_stream_t stream) {
@@ -373,8 +380,8 @@ int fp_detection_match(const int32_t* est_off, const int32_t* gt_off, const int3
   FP_REQUIRE(gt_valid || num_gt == 0, "fp_detection_match: null gt_valid");
   DetMatchArgs a;
   memset(&a, 0, sizeof(a));
-  a.est_off = est_off; a.gt_off = gt_off; a.pair_off = pair_off; a.err = err; a.gt_valid = gt_valid; a.group_tab = group_tab; a.ths = ths;
-  a.n_groups = num_groups; a.n_est = num_est; a.n_gt = num_gt; a.n_pairs = num_pairs; a.n_tab = num_tabs; a.T = num_ths;
+  a.t = group_tables(est_off, gt_off, pair_off, num_groups, num_est, num_gt, num_pairs);
+  a.err = err; a.gt_valid = gt_valid; a.group_tab = group_tab; a.ths = ths; a.n_tab = num_tabs; a.T = num_ths;
   a.flag = (signed char*)out_flag; a.matched_gt = out_matched_gt;
   return launch_detection_match(a, ST(stream));
 }
@@ -522,13 +529,6 @@ int fp_mask_pack(const uint8_t* masks, int num_masks, int H, int W, uint64_t* ou
   memset(&a, 0, sizeof(a));
   a.masks = masks; a.H = H; a.W = W; a.Wq = W >= 1 ? (W - 1) / 64 + 1 : 0; a.words = reinterpret_cast<unsigned long long*>(out_words); a.area = out_area;
   return launch_mask_pack(a, num_masks, ST(stream));
-}
-
-static GroupTables group_tables(const int32_t* est_off, const int32_t* gt_off, const int32_t* pair_off, int num_groups, int num_a, int num_b,
-                                int num_pairs) {
-  GroupTables t;
-  t.est_off = est_off; t.gt_off = gt_off; t.pair_off = pair_off; t.n_groups = num_groups; t.n_a = num_a; t.n_b = num_b; t.n_pairs = num_pairs;
-  return t;
 }
 
 int fp_group_mask_iou(const uint64_t* words_a, int num_a, const uint64_t* words_b, int num_b, int L, const int32_t* est_off,

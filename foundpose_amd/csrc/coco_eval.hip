@@ -8,46 +8,32 @@
 //   a dword), four neighbouring lanes OR their quarters together with two shuffles and the first of them stores the word: the wave reads 1 KiB
 //   of consecutive bytes per instruction.  Otherwise a thread assembles its word from bytes.  The area is the popcount of the words written.
 //
-// group_tiles_kernel: one workgroup.  The exclusive scan of the groups' tile counts, ceil(E_g / 4) ceil(G_g / 4), and ceil(E_g / 4) for a
+// group_tiles_kernel: one workgroup.  The exclusive scan (group_parts.hpp's block scan, in chunks of 256 groups) of the groups' tile counts, ceil(E_g / 4) ceil(G_g / 4), and ceil(E_g / 4) for a
 //   group of one instance: the tile table of the next kernel, made on the device because the group tables live there.
 //
 // group_mask_iou_kernel: the hot one.  A workgroup owns a tile of 4 a-rows x 4 b-rows of one group (4 x 1 where the group has one instance)
 //   and walks the L words of its rows once: per word 8 loads feed 16 AND + popcount for the intersections and 8 popcounts for the areas, all
 //   in registers.  A wave butterfly and 4 x 24 LDS slots finish the 24 sums; 16 threads write the tile's pairs.  Per pair this reads L / 2
 //   words instead of 2 L (1.25 L in a 4 x 1 tile).  The grid is the tile count's host-side upper bound; a workgroup finds its (group,
-//   a-tile, b-tile) by a binary search in the tile table and strides on, so no tile is lost when the bound is short.  Rows past the
+//   a-tile, b-tile) by a binary search in the tile table (last_at_or_before) and strides on, so no tile is lost when the bound is short.  Rows past the
 //   group's edge repeat its last row and are not written.
 //
 // group_box_iou_kernel: one thread per pair; the thread finds its group by a binary search in pair_off.  fp64, one rounded operation each.
 //
-// coco_match_kernel: one 64-thread workgroup per (group, threshold).  Lane l owns the GT instances l, l + 64, l + 128, l + 192 and keeps
-//   their matched bits in a register.  For every estimate in rank order each lane picks its best free candidate, a butterfly takes the
-//   lexicographic maximum of (non-ignored, overlap, GT index) and the owner of the winner sets its bit and writes.  No barrier, no LDS.
+// coco_match_kernel: one wave per (group, threshold), four waves per 256-thread workgroup.  The wave runs the shared greedy matcher of
+//   group_parts.hpp (no barrier, no LDS) under COCO's policy: an estimate may take a free GT whose overlap reaches min(threshold, 1 - 1e-10),
+//   the largest (non-ignored, overlap, GT index) wins, and a match with an ignored GT writes flag 2.
 //
 // All counting is integer arithmetic; an overlap is one division.  Every result depends on its own group's or mask's data only: it is the
 // same bits alone, in any batch and at any position.  FMA contraction is off in the box kernel; there are no atomics.
 #include "common.hpp"
-#include "kernels.hpp"
+#include "group_parts.hpp"
 
 namespace {
 
 constexpr int CE_WAVES = CE_THREADS / 64;
+static_assert(CE_THREADS == BS_THREADS, "group_tiles_kernel scans with block_scan_inclusive");
 constexpr int CE_SUMS = CE_TILE_A * CE_TILE_B + CE_TILE_A + CE_TILE_B;  // intersections, areas of a, areas of b
-constexpr int CM_GT_PER_LANE = DA_MAX_GROUP_GT / 64;                     // 4
-
-// A group as the kernels use it (the host validates the tables; the clamps keep a bad one that arrives all the same inside the arrays):
-// rows [e0, e0 + E) of a, [g0, g0 + G) of b, output rows p0 + e G + j, all of them below n_pairs.
-struct GroupDims { int e0, E, g0, G, p0; };
-FP_DEVICE GroupDims group_dims(const GroupTables& t, int g, int max_G) {
-  GroupDims d;
-  d.e0 = clampi(t.est_off[g], 0, t.n_a);
-  d.E = max(min(t.est_off[g + 1], t.n_a) - d.e0, 0);
-  d.g0 = clampi(t.gt_off[g], 0, t.n_b);
-  d.G = clampi(min(t.gt_off[g + 1], t.n_b) - d.g0, 0, max_G);
-  d.p0 = clampi(t.pair_off[g], 0, t.n_pairs);
-  if (d.G > 0) d.E = (int)min((long long)d.E, (long long)(t.n_pairs - d.p0) / d.G);
-  return d;
-}
 
 // ------------------------------------------------------------------ bytes -> bits
 // bit k = byte k of v is non-zero: the carry of 0x7f + (low seven bits) or the top bit itself marks the byte, the multiply gathers the marks
@@ -94,8 +80,7 @@ __global__ __launch_bounds__(CE_THREADS) void mask_pack_kernel(MaskPackArgs a) {
       cnt += __popcll(bits);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  cnt = wave_sum(cnt);
   if ((tid & 63) == 0) part[tid >> 6] = cnt;
   __syncthreads();
   if (tid == 0) {
@@ -110,33 +95,21 @@ __global__ __launch_bounds__(CE_THREADS) void mask_pack_kernel(MaskPackArgs a) {
 FP_DEVICE int tile_cols(int G) { return G == 1 ? 1 : (G + CE_TILE_B - 1) / CE_TILE_B; }
 
 __global__ __launch_bounds__(CE_THREADS) void group_tiles_kernel(GroupMaskIouArgs a) {
-  __shared__ long long wave_sum[CE_WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ long long slots[BS_WAVES];
+  const int tid = threadIdx.x;
   long long carry = 0;
   if (tid == 0) a.tile_off[0] = 0;
   for (int base = 0; base < a.t.n_groups; base += CE_THREADS) {
     const int g = base + tid;
-    long long incl = 0;
+    long long tiles = 0, chunk;
     if (g < a.t.n_groups) {
       const GroupDims d = group_dims(a.t, g, INT32_MAX);
-      incl = (long long)((d.E + CE_TILE_A - 1) / CE_TILE_A) * tile_cols(d.G);
+      tiles = (long long)((d.E + CE_TILE_A - 1) / CE_TILE_A) * tile_cols(d.G);
     }
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-      const long long up = __shfl_up(incl, s, 64);
-      if (lane >= s) incl += up;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    long long chunk = 0;
-#pragma unroll
-    for (int v = 0; v < CE_WAVES; ++v) {
-      if (v < wave) incl += wave_sum[v];
-      chunk += wave_sum[v];
-    }
+    const long long incl = block_scan_inclusive(tiles, slots, chunk);
     if (g < a.t.n_groups) a.tile_off[g + 1] = (int)min(carry + incl, (long long)INT32_MAX);  // (the launcher bounds the sum of a sound table)
     carry += chunk;
-    __syncthreads();  // wave_sum is written again in the next round
+    __syncthreads();  // slots are written again in the next round
   }
 }
 
@@ -173,10 +146,7 @@ FP_DEVICE void mask_iou_tile(const GroupMaskIouArgs& a, const GroupDims& d, int 
     for (int j = 0; j < TB; ++j) sum[TA * TB + TA + j] += __popcll(vb[j]);
   }
 #pragma unroll
-  for (int s = 0; s < NS; ++s) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum[s] += __shfl_xor(sum[s], o, 64);
-  }
+  for (int s = 0; s < NS; ++s) sum[s] = wave_sum(sum[s]);
   if (lane == 0) {
 #pragma unroll
     for (int s = 0; s < NS; ++s) red[wave][s] = sum[s];
@@ -209,11 +179,7 @@ __global__ __launch_bounds__(CE_THREADS) void group_mask_iou_kernel(GroupMaskIou
   const int NG = a.t.n_groups;
   const int total = a.tile_off[NG];
   for (int tile = blockIdx.x; tile < total; tile += gridDim.x) {  // block-uniform throughout
-    int lo = 0, hi = NG - 1;  // the last group whose first tile is <= tile: the one that owns it (groups without a tile share an offset)
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (a.tile_off[mid] <= tile) lo = mid; else hi = mid - 1;
-    }
+    const int lo = last_at_or_before(NG, tile, [&](int g) { return a.tile_off[g]; });  // the group that owns the tile
     const GroupDims d = group_dims(a.t, lo, INT32_MAX);
     if (d.E <= 0 || d.G <= 0) continue;
     const int nb = tile_cols(d.G);
@@ -230,11 +196,7 @@ __global__ __launch_bounds__(CE_THREADS) void group_box_iou_kernel(GroupBoxIouAr
 #pragma clang fp contract(off)
   const int q = blockIdx.x * CE_THREADS + threadIdx.x;
   if (q >= a.t.n_pairs) return;
-  int lo = 0, hi = a.t.n_groups - 1;  // the last group that starts at or before q
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (a.t.pair_off[mid] <= q) lo = mid; else hi = mid - 1;
-  }
+  const int lo = last_at_or_before(a.t.n_groups, q, [&](int g) { return a.t.pair_off[g]; });
   double ov = 0.0;
   int st = 2;  // a row that no group owns is answered like a union of 0
   const GroupDims d = group_dims(a.t, lo, INT32_MAX);
@@ -258,49 +220,27 @@ __global__ __launch_bounds__(CE_THREADS) void group_box_iou_kernel(GroupBoxIouAr
 }
 
 // ------------------------------------------------------------------ COCO's matching
-__global__ __launch_bounds__(64) void coco_match_kernel(CocoMatchArgs a) {
-  const int lane = threadIdx.x;
-  const int g = blockIdx.x / a.T, k = blockIdx.x - g * a.T;
-  const GroupDims d = group_dims(a.t, g, DA_MAX_GROUP_GT);
-  const double bound = fmin(a.ths[k], 1.0 - 1e-10);
-
-  unsigned taken = 0u;    // bit j: this lane's GT lane + 64 j is matched
-  unsigned ignored = 0u;  // bit j: ... is an ignored instance
-#pragma unroll
-  for (int j = 0; j < CM_GT_PER_LANE; ++j) {
-    const int gi = lane + 64 * j;
-    if (gi < d.G && a.gt_ignore[d.g0 + gi] != 0) ignored |= 1u << j;
+// COCO's matching rule for greedy_match: one IoU threshold.
+struct CocoPolicy {
+  const double* overlap;  // [P]
+  const int* gt_ignore;
+  double bound;           // min(threshold, 1 - 1e-10)
+  FP_DEVICE bool second_class(int gt_row) const { return gt_ignore[gt_row] != 0; }  // an ignored GT: it ranks below every regular one
+  FP_DEVICE double value(size_t row) const { return overlap[row]; }
+  FP_DEVICE bool candidate(double v) const { return v >= bound; }                   // false for a NaN
+  FP_DEVICE MatchKey none() const { return {2, 0.0, -1}; }
+  FP_DEVICE bool before(const MatchKey& a, const MatchKey& b) const {
+    return a.cls < b.cls || (a.cls == b.cls && (a.v > b.v || (a.v == b.v && a.g > b.g)));
   }
+};
 
-  for (int e = 0; e < d.E; ++e) {
-    const double* row = a.overlap + (size_t)d.p0 + (size_t)e * d.G;
-    int best_cls = -1, best_g = -1;  // class 1: a non-ignored candidate, 0: an ignored one, -1: none
-    double best = 0.0;
-#pragma unroll
-    for (int j = 0; j < CM_GT_PER_LANE; ++j) {
-      const int gi = lane + 64 * j;
-      if (gi < d.G && !((taken >> j) & 1u)) {
-        const double v = row[gi];
-        const int cls = ((ignored >> j) & 1u) ? 0 : 1;
-        // ascending gi and a >=: the higher index keeps a tie; a NaN is never >= the bound
-        if (v >= bound && (cls > best_cls || (cls == best_cls && v >= best))) { best_cls = cls; best = v; best_g = gi; }
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const int oc = __shfl_xor(best_cls, o, 64), og = __shfl_xor(best_g, o, 64);
-      const double ob = __shfl_xor(best, o, 64);
-      if (oc > best_cls || (oc == best_cls && (ob > best || (ob == best && og > best_g)))) { best_cls = oc; best = ob; best_g = og; }
-    }
-    const size_t out = ((size_t)d.e0 + e) * a.T + k;
-    if (best_g < 0) {
-      if (lane == 0) { a.flag[out] = 0; a.matched_gt[out] = -1; }
-    } else if ((best_g & 63) == lane) {
-      taken |= 1u << (best_g >> 6);  // used up whether ignored or not
-      a.flag[out] = best_cls == 1 ? 1 : 2;
-      a.matched_gt[out] = best_g;
-    }
-  }
+__global__ __launch_bounds__(GM_THREADS) void coco_match_kernel(CocoMatchArgs a) {
+  const long long w = match_wave();
+  if (w >= (long long)a.t.n_groups * a.T) return;  // wave-uniform
+  const int g = (int)(w / a.T), k = (int)(w % a.T);
+  const GroupDims d = group_dims(a.t, g, GM_MAX_GT);
+  const CocoPolicy p{a.overlap, a.gt_ignore, fmin(a.ths[k], 1.0 - 1e-10)};
+  greedy_match(p, d, threadIdx.x & 63, a.flag, a.matched_gt, (size_t)d.e0 * a.T + k, a.T);
 }
 
 }  // namespace
@@ -343,9 +283,9 @@ int launch_coco_match(const CocoMatchArgs& a, hipStream_t st) {
   FP_REQUIRE(a.T >= 1 && a.T <= DA_MAX_THS, "coco_match: T must be in [1, %d] (got %d)", DA_MAX_THS, a.T);
   FP_REQUIRE(t.n_groups >= 0 && t.n_a >= 0 && t.n_b >= 0 && t.n_pairs >= 0, "coco_match: negative count");
   if (t.n_groups == 0) return FP_OK;
-  const long long blocks = (long long)t.n_groups * a.T;
+  const long long blocks = match_blocks((long long)t.n_groups * a.T);
   FP_REQUIRE(blocks <= 0x7fffffffLL, "coco_match: %d groups are too many for one launch", t.n_groups);
-  hipLaunchKernelGGL(coco_match_kernel, dim3((unsigned)blocks), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(coco_match_kernel, dim3((unsigned)blocks), dim3(GM_THREADS), 0, st, a);
   FP_CHECK_LAUNCH("coco_match");
   return FP_OK;
 }

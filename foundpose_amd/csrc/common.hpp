@@ -175,7 +175,8 @@ FP_DEVICE void splitx_store4(char* row, int c, unsigned hi01, unsigned p01, unsi
 }
 
 // ---- wave-level reductions (64 lanes)
-FP_DEVICE float wave_sum(float v) {
+template <class T>  // an arithmetic type; in a floating one the butterfly's order of additions is part of the result
+FP_DEVICE T wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;

@@ -1,8 +1,8 @@
 // Detection masks on the device (infer_batched's device_masks path): the COCO run lengths of N detections in, the
 // opened, centre-cropped uint8 [N, H, W] masks and their areas out -- the bits of infer_pose_util.rle_to_binary_mask, open_mask_3x3 and the
 // [dy : hc - dy, dx : wc - dx] slice of the host path.
-//   scan    one workgroup per detection: the inclusive prefix sums s_i of its runs, in chunks of 256 with a running carry; a negative count
-//           counts as 0 and the sums saturate at 2^31 - 1, so the sums never decrease whatever the input;
+//   scan    one workgroup per detection: the inclusive prefix sums s_i of its runs, in chunks of 256 (group_parts.hpp's block scan) with a
+//           running carry; a negative count counts as 0 and the sums saturate at 2^31 - 1, so the sums never decrease whatever the input;
 //   masks   one workgroup per 64 x 16 tile of the OUTPUT image.  Canvas pixel (x, y) has the column-major index p = x hc + y; with k = the
 //           number of s_i <= p (a binary search over the detection's sums) it is set iff k < R and k is odd.  With the opening the tile's
 //           pixels and a halo of 2 are decoded into LDS, eroded into LDS with a halo of 1 and dilated into the output: a pixel outside the
@@ -10,46 +10,31 @@
 //           output byte is written exactly once; the tile's count goes through the wave butterfly and one integer atomicAdd per workgroup.
 // Integers only: a detection's result depends on its own runs and on nothing else.
 #include "common.hpp"
-#include "kernels.hpp"
+#include "group_parts.hpp"
 
 namespace {
 
 constexpr int DM_THREADS = 256, DM_WAVES = DM_THREADS / 64;
+static_assert(DM_THREADS == BS_THREADS, "rle_scan_kernel scans with block_scan_inclusive");
 constexpr int DM_RW = DM_TILE_W + 4, DM_RH = DM_TILE_H + 4;  // decoded pixels: the tile and a halo of 2
 constexpr int DM_EW = DM_TILE_W + 2, DM_EH = DM_TILE_H + 2;  // eroded pixels: the tile and a halo of 1
 
-// the detection's runs [b, e) in counts / prefix, clamped to the arrays: no read outside them whatever run_off holds
-FP_DEVICE void det_runs(const DetMaskArgs& a, int n, int& b, int& e) {
-  b = min(max(a.run_off[n], 0), a.num_runs);
-  e = min(max(a.run_off[n + 1], b), a.num_runs);
-}
+// the detection's runs in counts / prefix, clamped to the arrays: no read outside them whatever run_off holds
+FP_DEVICE OffsetRange det_runs(const DetMaskArgs& a, int n) { return offset_range(a.run_off, n, a.num_runs); }
 
 __global__ __launch_bounds__(DM_THREADS) void rle_scan_kernel(DetMaskArgs a) {
-  __shared__ long long wave_total[DM_WAVES];
-  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int b, e;
-  det_runs(a, n, b, e);
+  __shared__ long long slots[BS_WAVES];
+  const int tid = threadIdx.x;
+  const OffsetRange r = det_runs(a, blockIdx.x);
+  const int e = r.begin + r.n;
   long long carry = 0;
-  for (int i0 = b; i0 < e; i0 += DM_THREADS) {  // block-uniform trip count
+  for (int i0 = r.begin; i0 < e; i0 += DM_THREADS) {  // block-uniform trip count
     const int i = i0 + tid;
-    long long v = i < e ? (long long)max(a.counts[i], 0) : 0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long t = __shfl_up(v, o, 64);
-      if (lane >= o) v += t;
-    }
-    if (lane == 63) wave_total[wave] = v;
-    __syncthreads();
-    long long before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < DM_WAVES; ++w) {
-      const long long t = wave_total[w];
-      before += w < wave ? t : 0;
-      all += t;
-    }
-    if (i < e) a.prefix[i] = (int)min(carry + before + v, (long long)INT32_MAX);
+    long long all;
+    const long long v = block_scan_inclusive(i < e ? (long long)max(a.counts[i], 0) : 0ll, slots, all);
+    if (i < e) a.prefix[i] = (int)min(carry + v, (long long)INT32_MAX);
     carry += all;  // at most 2^31 per run and 2^31 runs: no overflow
-    __syncthreads();
+    __syncthreads();  // slots are written again in the next round
   }
 }
 
@@ -74,10 +59,9 @@ __global__ __launch_bounds__(DM_THREADS) void det_mask_kernel(DetMaskArgs a) {
   const int tx = blk % a.tiles_x;
   blk /= a.tiles_x;
   const int ty = blk % a.tiles_y, n = blk / a.tiles_y;
-  int b, e;
-  det_runs(a, n, b, e);
-  const int* __restrict__ s = a.prefix + b;
-  const int R = e - b;
+  const OffsetRange runs = det_runs(a, n);
+  const int* __restrict__ s = a.prefix + runs.begin;
+  const int R = runs.n;
   const int dx = (a.wc - a.W) / 2, dy = (a.hc - a.H) / 2;
   const int ox0 = tx * DM_TILE_W, oy0 = ty * DM_TILE_H;  // the tile's origin in the output image; + (dx, dy) on the canvas
 
@@ -124,8 +108,7 @@ __global__ __launch_bounds__(DM_THREADS) void det_mask_kernel(DetMaskArgs a) {
       count += v;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) count += __shfl_xor(count, o, 64);
+  count = wave_sum(count);
   if ((tid & 63) == 0) wave_count[tid >> 6] = count;
   __syncthreads();
   if (tid == 0) {

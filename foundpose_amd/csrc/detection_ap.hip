@@ -2,11 +2,10 @@
 // accumulation per object, for all MSSD / MSPD thresholds at once.  The reference has no evaluation of this kind; the rules restate the
 // published behaviour of bop_toolkit's detection scores.
 //
-// detection_match_kernel: one wave per (estimate group, column); a column is one threshold of one error type.  Lane l owns the group's GT
-//   instances l, l + 64, l + 128, l + 192 (a group has at most 256) and keeps their matched bits in a register.  For every estimate, in
-//   rank order, each lane finds its best free GT with an error strictly below the threshold, a butterfly takes the lexicographic minimum
-//   of (error, GT index) over the wave, the owner of the winner sets its bit and writes the estimate's two outputs (lane 0 writes for an
-//   estimate without a match).  No barrier, no LDS: a wave beyond the last (group, column) leaves at once.
+// detection_match_kernel: one wave per (estimate group, column); a column is one threshold of one error type.  The wave runs the shared
+//   greedy matcher of group_parts.hpp (four waves per workgroup, no barrier, no LDS) under the task's policy: an estimate may take a free
+//   GT whose error is strictly below the threshold, the smallest (error, GT index) wins, and an invalid GT is taken like a valid one (the
+//   estimate is then ignored, flag 2).
 //
 // detection_ap_kernel: one 256-thread workgroup per (object, column).  Pass 1 counts the object's true positives, false positives and
 //   ignored estimates.  Thread i then finds, for recall threshold i, the smallest true-positive count m_i whose recall reaches it (a binary
@@ -16,69 +15,36 @@
 //   is the maximum over all.  Counts are integers, a precision and a recall are one division each, a maximum does not round: no result
 //   depends on the order in which threads arrive.  FMA contraction is off; there are no float atomics.
 #include "common.hpp"
-#include "kernels.hpp"
+#include "group_parts.hpp"
 
 namespace {
 
 constexpr int DA_WAVE = 64;
-constexpr int DA_MATCH_WAVES = DA_THREADS / DA_WAVE;          // (group, column)s of one workgroup
-constexpr int DA_GT_PER_LANE = DA_MAX_GROUP_GT / DA_WAVE;     // 4
-constexpr int DA_NO_GT = 0x7fffffff;
+constexpr int DA_WAVES = DA_THREADS / DA_WAVE;
+static_assert(DA_THREADS == BS_THREADS, "detection_ap_kernel scans with block_scan_inclusive");
 
-__global__ __launch_bounds__(DA_THREADS) void detection_match_kernel(DetMatchArgs a) {
-  const int lane = threadIdx.x & (DA_WAVE - 1);
+// The 6D detection task's matching rule for greedy_match: one error type at one threshold.
+struct DetectionPolicy {
+  const double* err;    // [P, 2], from the column's error type on
+  const int* gt_valid;
+  double th;
+  FP_DEVICE bool second_class(int gt_row) const { return !(gt_valid[gt_row] > 0); }  // an invalid GT: it is matched like a valid one
+  FP_DEVICE double value(size_t row) const { return err[row * 2]; }
+  FP_DEVICE bool candidate(double v) const { return v < th; }                        // false for a NaN; a candidate is never +inf
+  FP_DEVICE MatchKey none() const { return {0, __builtin_huge_val(), 0x7fffffff}; }
+  FP_DEVICE bool before(const MatchKey& a, const MatchKey& b) const { return a.v < b.v || (a.v == b.v && a.g < b.g); }  // the class does not rank
+};
+
+__global__ __launch_bounds__(GM_THREADS) void detection_match_kernel(DetMatchArgs a) {
   const int C = 2 * a.T;
-  const long long w = (long long)blockIdx.x * DA_MATCH_WAVES + (threadIdx.x >> 6);
-  if (w >= (long long)a.n_groups * C) return;  // wave-uniform
+  const long long w = match_wave();
+  if (w >= (long long)a.t.n_groups * C) return;  // wave-uniform
   const int g = (int)(w / C), c = (int)(w % C);
   const int type = c / a.T, k = c % a.T;
-
-  // (the host validates the tables; the clamps keep a bad one that reaches the kernel all the same inside the arrays)
-  const int e0 = clampi(a.est_off[g], 0, a.n_est);
-  int E = max(min(a.est_off[g + 1], a.n_est) - e0, 0);
-  const int g0 = clampi(a.gt_off[g], 0, a.n_gt);
-  const int G = clampi(min(a.gt_off[g + 1], a.n_gt) - g0, 0, DA_MAX_GROUP_GT);
-  const int p0 = clampi(a.pair_off[g], 0, a.n_pairs);
-  if (G > 0) E = (int)min((long long)E, (long long)(a.n_pairs - p0) / G);  // every row read lies in err
+  const GroupDims d = group_dims(a.t, g, GM_MAX_GT);
   const int tab = clampi(a.group_tab[g], 0, a.n_tab - 1);
-  const double th = a.ths[((size_t)tab * 2 + type) * a.T + k];
-
-  unsigned taken = 0u;   // bit j: this lane's GT lane + 64 j is matched
-  unsigned valid = 0u;   // bit j: ... is a valid GT
-#pragma unroll
-  for (int j = 0; j < DA_GT_PER_LANE; ++j) {
-    const int gi = lane + DA_WAVE * j;
-    if (gi < G && a.gt_valid[g0 + gi] > 0) valid |= 1u << j;
-  }
-
-  for (int e = 0; e < E; ++e) {
-    const double* row = a.err + ((size_t)p0 + (size_t)e * G) * 2 + type;
-    double best = __builtin_huge_val();  // a candidate's error is below the threshold, so it is never +inf
-    int best_g = DA_NO_GT;
-#pragma unroll
-    for (int j = 0; j < DA_GT_PER_LANE; ++j) {
-      const int gi = lane + DA_WAVE * j;
-      if (gi < G && !((taken >> j) & 1u)) {
-        const double v = row[(size_t)gi * 2];
-        if (v < th && v < best) { best = v; best_g = gi; }  // ascending gi and a strict <: the lower index keeps a tie; a NaN never enters
-      }
-    }
-#pragma unroll
-    for (int o = DA_WAVE / 2; o > 0; o >>= 1) {
-      const double ob = __shfl_xor(best, o, DA_WAVE);
-      const int og = __shfl_xor(best_g, o, DA_WAVE);
-      if (ob < best || (ob == best && og < best_g)) { best = ob; best_g = og; }
-    }
-    const size_t out = ((size_t)e0 + e) * C + c;
-    if (best_g == DA_NO_GT) {
-      if (lane == 0) { a.flag[out] = 0; a.matched_gt[out] = -1; }
-    } else if ((best_g & (DA_WAVE - 1)) == lane) {
-      const int j = best_g >> 6;
-      taken |= 1u << j;  // used up whether valid or not
-      a.flag[out] = ((valid >> j) & 1u) ? 1 : 2;
-      a.matched_gt[out] = best_g;
-    }
-  }
+  const DetectionPolicy p{a.err + type, a.gt_valid, a.ths[((size_t)tab * 2 + type) * a.T + k]};
+  greedy_match(p, d, threadIdx.x & 63, a.flag, a.matched_gt, (size_t)d.e0 * C + c, C);
 }
 
 // the flag of the object's estimate at rank position `pos`: 0 false positive, 1 true positive, anything else is left out
@@ -89,9 +55,9 @@ FP_DEVICE int flag_at(const DetApArgs& a, int begin, int pos, int C, int c) {
 
 __global__ __launch_bounds__(DA_THREADS) void detection_ap_kernel(DetApArgs a) {
 #pragma clang fp contract(off)
-  __shared__ int red[DA_MATCH_WAVES][3];
-  __shared__ int wave_sum[DA_MATCH_WAVES];     // tp in the low half, fp in the high half: a chunk holds at most 256 of each
-  __shared__ double wave_max[DA_MATCH_WAVES];
+  __shared__ int red[DA_WAVES][3];
+  __shared__ int scan_slots[BS_WAVES];         // tp in the low half, fp in the high half: a chunk holds at most 256 of each
+  __shared__ double wave_max[DA_WAVES];
   __shared__ int scan_tp[DA_THREADS];          // the running true-positive count at each position of the chunk
   __shared__ double env[DA_THREADS];           // the precision envelope at each position
   __shared__ double qs[DA_MAX_REC];
@@ -113,17 +79,12 @@ __global__ __launch_bounds__(DA_THREADS) void detection_ap_kernel(DetApArgs a) {
     t_fp += f == 0;
     t_ig += f != 0 && f != 1;
   }
-#pragma unroll
-  for (int s = DA_WAVE / 2; s > 0; s >>= 1) {
-    t_tp += __shfl_xor(t_tp, s, DA_WAVE);
-    t_fp += __shfl_xor(t_fp, s, DA_WAVE);
-    t_ig += __shfl_xor(t_ig, s, DA_WAVE);
-  }
+  t_tp = wave_sum(t_tp); t_fp = wave_sum(t_fp); t_ig = wave_sum(t_ig);
   if (lane == 0) { red[wave][0] = t_tp; red[wave][1] = t_fp; red[wave][2] = t_ig; }
   __syncthreads();
   t_tp = t_fp = t_ig = 0;
 #pragma unroll
-  for (int v = 0; v < DA_MATCH_WAVES; ++v) { t_tp += red[v][0]; t_fp += red[v][1]; t_ig += red[v][2]; }
+  for (int v = 0; v < DA_WAVES; ++v) { t_tp += red[v][0]; t_fp += red[v][1]; t_ig += red[v][2]; }
   if (tid < 3) a.totals[oc * 3 + tid] = tid == 0 ? t_tp : (tid == 1 ? t_fp : t_ig);
 
   if (nv <= 0) {  // block-uniform: an object without a valid GT has no AP
@@ -152,20 +113,8 @@ __global__ __launch_bounds__(DA_THREADS) void detection_ap_kernel(DetApArgs a) {
   for (int b = ((n - 1) / DA_THREADS) * DA_THREADS; n > 0 && b >= 0; b -= DA_THREADS) {
     const int pos = b + tid;
     const int f = pos < n ? flag_at(a, begin, pos, C, c) : 2;
-    int incl = (f == 1 ? 1 : 0) | (f == 0 ? 1 << 16 : 0);
-#pragma unroll
-    for (int s = 1; s < DA_WAVE; s <<= 1) {
-      const int up = __shfl_up(incl, s, DA_WAVE);
-      if (lane >= s) incl += up;
-    }
-    if (lane == DA_WAVE - 1) wave_sum[wave] = incl;
-    __syncthreads();
-    int chunk = 0;
-#pragma unroll
-    for (int v = 0; v < DA_MATCH_WAVES; ++v) {
-      if (v < wave) incl += wave_sum[v];
-      chunk += wave_sum[v];
-    }
+    int chunk;  // (scan_slots are next written a barrier later: the two below)
+    const int incl = block_scan_inclusive((f == 1 ? 1 : 0) | (f == 0 ? 1 << 16 : 0), scan_slots, chunk);
     const int before_tp = t_tp - after_tp - (chunk & 0xffff), before_fp = t_fp - after_fp - (chunk >> 16);
     const int tp_k = before_tp + (incl & 0xffff), fp_k = before_fp + (incl >> 16);
     double p = (f == 0 || f == 1) ? (double)tp_k / (double)(tp_k + fp_k) : -1.0;
@@ -178,7 +127,7 @@ __global__ __launch_bounds__(DA_THREADS) void detection_ap_kernel(DetApArgs a) {
     __syncthreads();
     double chunk_max = running;
 #pragma unroll
-    for (int v = 0; v < DA_MATCH_WAVES; ++v) {
+    for (int v = 0; v < DA_WAVES; ++v) {
       if (v > wave) p = fmax(p, wave_max[v]);
       chunk_max = fmax(chunk_max, wave_max[v]);
     }
@@ -216,13 +165,13 @@ __global__ __launch_bounds__(DA_THREADS) void detection_ap_kernel(DetApArgs a) {
 
 int launch_detection_match(const DetMatchArgs& a, hipStream_t st) {
   FP_REQUIRE(a.T >= 1 && a.T <= DA_MAX_THS, "detection_match: T must be in [1, %d] (got %d)", DA_MAX_THS, a.T);
-  FP_REQUIRE(a.n_groups >= 0 && a.n_est >= 0 && a.n_gt >= 0 && a.n_pairs >= 0, "detection_match: negative count");
-  if (a.n_groups == 0) return FP_OK;
+  const GroupTables& t = a.t;
+  FP_REQUIRE(t.n_groups >= 0 && t.n_a >= 0 && t.n_b >= 0 && t.n_pairs >= 0, "detection_match: negative count");
+  if (t.n_groups == 0) return FP_OK;
   FP_REQUIRE(a.n_tab >= 1, "detection_match: no threshold row");
-  const long long waves = (long long)a.n_groups * 2 * a.T;
-  const long long blocks = (waves + DA_MATCH_WAVES - 1) / DA_MATCH_WAVES;
-  FP_REQUIRE(blocks <= 0x7fffffffLL, "detection_match: %d groups are too many for one launch", a.n_groups);
-  hipLaunchKernelGGL(detection_match_kernel, dim3((unsigned)blocks), dim3(DA_THREADS), 0, st, a);
+  const long long blocks = match_blocks((long long)t.n_groups * 2 * a.T);
+  FP_REQUIRE(blocks <= 0x7fffffffLL, "detection_match: %d groups are too many for one launch", t.n_groups);
+  hipLaunchKernelGGL(detection_match_kernel, dim3((unsigned)blocks), dim3(GM_THREADS), 0, st, a);
   FP_CHECK_LAUNCH("detection_match");
   return FP_OK;
 }

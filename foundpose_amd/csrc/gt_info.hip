@@ -21,7 +21,7 @@
 #include <climits>
 
 #include "common.hpp"
-#include "kernels.hpp"
+#include "group_parts.hpp"  // last_at_or_before
 #include "bop_dist.hpp"   // dadd, dist, visib: the same functions vsd.hip uses
 #include "../../include/foundpose_amd.h"
 
@@ -47,12 +47,7 @@ __global__ __launch_bounds__(GT_THREADS) void gt_vis_init_kernel(int* out, int n
 
 __global__ __launch_bounds__(GT_THREADS) void gt_visibility_kernel(GtVisArgs a) {
   const long long blk = blockIdx.x;
-  int lo = 0, hi = a.num_inst - 1;  // the last instance whose first block is <= blk (instances with no block share a start)
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (a.inst[mid].blk0 <= blk) lo = mid;
-    else hi = mid - 1;
-  }
+  const int lo = last_at_or_before(a.num_inst, blk, [&](int i) { return a.inst[i].blk0; });  // the instance that owns the block
   const GtVisInst in = a.inst[lo];
   const int npix = in.bw * in.bh;
   const int base = (int)(blk - in.blk0) * GT_BLOCK_PIX;

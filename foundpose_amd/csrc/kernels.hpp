@@ -683,21 +683,25 @@ struct PoseNmsArgs {
 int launch_pose_nms_greedy(const PoseNmsArgs& a, int num_groups, hipStream_t st);
 
 // ---------------------------------------------------------------- detection_ap.hip
-constexpr int DA_THREADS = 256;        // a workgroup: 4 (group, column) waves of the matching, one (object, column) of the AP
+constexpr int DA_THREADS = 256;        // a workgroup of the AP kernel: one (object, column)
 constexpr int DA_MAX_GROUP_GT = 256;   // GT instances of one (image, object): 4 per lane
 constexpr int DA_MAX_THS = 16;         // thresholds per error type
 constexpr int DA_MAX_REC = 128;        // recall thresholds: one thread each
+struct GroupTables {       // groups of rows of a (estimates, in rank order) and of b (GT instances): csrc/group_parts.hpp reads them
+  const int* est_off;      // [groups + 1] each group's rows of a
+  const int* gt_off;       // [groups + 1] its rows of b
+  const int* pair_off;     // [groups + 1] its rows of the pair tables: E_g x G_g, row-major
+  int n_groups, n_a, n_b, n_pairs;
+};
 struct DetMatchArgs {
-  const int* est_off;      // [groups + 1] the estimates of each group, in rank order
-  const int* gt_off;       // [groups + 1] its GT instances
-  const int* pair_off;     // [groups + 1] its rows of err: E_g x G_g, row-major
+  GroupTables t;           // n_a = estimates, n_b = GT instances
   const double* err;       // [n_pairs, 2] (mssd, mspd), what fp_pose_errors wrote
-  const int* gt_valid;     // [n_gt] > 0: a valid GT
+  const int* gt_valid;     // [n_b] > 0: a valid GT
   const int* group_tab;    // [groups] the group's row of ths
   const double* ths;       // [n_tab, 2, T]
-  int n_groups, n_est, n_gt, n_pairs, n_tab, T;
-  signed char* flag;       // [n_est, 2 T] 1 true positive, 0 false positive, 2 ignored
-  int* matched_gt;         // [n_est, 2 T] the group-local GT index or -1
+  int n_tab, T;
+  signed char* flag;       // [n_a, 2 T] 1 true positive, 0 false positive, 2 ignored
+  int* matched_gt;         // [n_a, 2 T] the group-local GT index or -1
 };
 int launch_detection_match(const DetMatchArgs& a, hipStream_t st);
 
@@ -731,12 +735,6 @@ struct MaskPackArgs {
 };
 int launch_mask_pack(const MaskPackArgs& a, int num_masks, hipStream_t st);
 
-struct GroupTables {           // the three tables fp_detection_match takes, for rows of a (estimates) and of b (GT instances)
-  const int* est_off;          // [groups + 1] each group's rows of a
-  const int* gt_off;           // [groups + 1] its rows of b
-  const int* pair_off;         // [groups + 1] its output rows: E_g x G_g, row-major
-  int n_groups, n_a, n_b, n_pairs;
-};
 struct GroupMaskIouArgs {
   GroupTables t;
   const unsigned long long* words_a;  // [n_a, L]

@@ -16,7 +16,7 @@
 // either direction become a symmetric conflict bit matrix in LDS; then rank by rank, a pose that is still alive suppresses the later
 // poses it conflicts with.
 #include "common.hpp"
-#include "kernels.hpp"
+#include "group_parts.hpp"
 #include "verify_grid.hpp"  // FramePose, to_camera, PV_THREADS
 
 namespace {
@@ -130,9 +130,9 @@ __global__ __launch_bounds__(PN_MAX_GROUP) void pose_nms_greedy_kernel(PoseNmsAr
 
   const int group = blockIdx.x, tid = threadIdx.x;
   // (the host validates the tables; the clamps keep a bad one that reaches the kernel all the same inside the arrays)
-  const int begin = min(max(a.group_off[group], 0), a.n_poses);
-  const int n = min(max(min(a.group_off[group + 1], a.n_poses) - begin, 0), PN_MAX_GROUP);
-  const int pb = min(max(a.pair_off[group], 0), a.n_pairs), pe = min(max(a.pair_off[group + 1], 0), a.n_pairs);
+  const OffsetRange poses = offset_range(a.group_off, group, a.n_poses), prs = offset_range(a.pair_off, group, a.n_pairs);
+  const int begin = poses.begin, n = min(poses.n, PN_MAX_GROUP);
+  const int pb = prs.begin, pe = prs.begin + prs.n;
 
   // ---- phase A: the conflict matrix
   for (int i = tid; i < n * PN_ROW_WORDS; i += PN_MAX_GROUP) conflict[i] = 0u;

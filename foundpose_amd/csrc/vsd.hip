@@ -16,7 +16,7 @@
 // pixels in registers, the wave sums by shuffles, the workgroup through LDS, and one 64-bit integer atomic per non-zero
 // counter goes into the output the host zeroed on the stream.  Integer sums: bit-identical across runs and batches.
 #include "common.hpp"
-#include "kernels.hpp"
+#include "group_parts.hpp"  // last_at_or_before
 #include "bop_dist.hpp"   // dmul, dadd, dist, visib
 #include "../../include/foundpose_amd.h"
 
@@ -32,12 +32,7 @@ static_assert(VSD_BLOCK_PIX == FP_VSD_BLOCK_PIXELS, "block size of the header");
 
 __global__ __launch_bounds__(VSD_THREADS) void vsd_counts_kernel(VsdArgs a) {
   const long long blk = blockIdx.x;
-  int lo = 0, hi = a.num_pairs - 1;  // the last pair whose first block is <= blk (pairs with no block share a start)
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (a.pairs[mid].blk0 <= blk) lo = mid;
-    else hi = mid - 1;
-  }
+  const int lo = last_at_or_before(a.num_pairs, blk, [&](int i) { return a.pairs[i].blk0; });  // the pair that owns the block
   const VsdPair pr = a.pairs[lo];
   const int npix = pr.bw * pr.bh;
   const int base = (int)(blk - pr.blk0) * VSD_BLOCK_PIX;
@@ -72,8 +67,7 @@ __global__ __launch_bounds__(VSD_THREADS) void vsd_counts_kernel(VsdArgs a) {
   for (int c = 0; c < VSD_NC; ++c) {
     if (c < nc) {  // uniform
       int s = cnt[c];
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+      s = wave_sum(s);
       if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = s;
     }
   }

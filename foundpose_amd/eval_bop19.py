@@ -20,6 +20,8 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
+from .device_timer import DeviceTimer
+
 VSD_TAUS = np.arange(0.05, 0.51, 0.05)      # misalignment tolerances, fraction of the object diameter
 VSD_THS = np.arange(0.05, 0.51, 0.05)       # correctness thresholds on the VSD error
 MSSD_THS = np.arange(0.05, 0.51, 0.05)      # x diameter (mm)
@@ -238,18 +240,8 @@ def evaluate_bop19(result_csv: str, split_dir: str, targets: Union[None, str, Se
                       "valid": valid_gt_mask([float(ivs[g]["visib_fract"]) for g in gids], tgt[key])}
     work = [k for k in sorted(tgt) if per_t[k]["est"] and per_t[k]["gid"]]
 
-    ev = defaultdict(float)
-    events = []
-
-    def timed(kind, fn, *a, **kw):
-        if not timing:
-            return fn(*a, **kw)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = fn(*a, **kw)
-        e1.record()
-        events.append((kind, e0, e1))
-        return out
+    timer = DeviceTimer(timing)
+    timed = timer.timed
 
     # ---- MSSD / MSPD: one fp_pose_errors launch per chunk of (estimate, GT) pairs
     pe_items, pe_where = [], []
@@ -327,10 +319,7 @@ def evaluate_bop19(result_csv: str, split_dir: str, targets: Union[None, str, Se
     if details:
         out["errors"] = err_details
     if timing:
-        torch.cuda.synchronize()
-        for kind, e0, e1 in events:
-            ev[kind] += e0.elapsed_time(e1) / 1e3
-        out["device_seconds"] = dict(ev)
+        out["device_seconds"] = timer.seconds()
     return out
 
 

@@ -21,46 +21,15 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
+from .device_timer import DeviceTimer
 from .eval_bop19 import MSPD_THS, MSSD_THS, _m2c, _read_json, average_time_per_image, correct_thresholds, load_results_csv
+from .group_tables import MAX_GROUP_GT, MAX_REC, MAX_THS, check_groups, int32_table, offsets, upload
 
 MIN_VISIB_FRACT = 0.1                    # a GT instance is valid when at least this fraction of it is visible
 REC_THR = np.linspace(0, 1, 101)         # the recall thresholds precision is interpolated at
-MAX_THS, MAX_GROUP_GT, MAX_REC = 16, 256, 128   # ops.DETECTION_*: the limits of the two kernels
 
 
 # ---------------------------------------------------------------------------------------------------------- the two launches
-def _int32_table(name: str, a, size: Optional[int] = None) -> np.ndarray:
-    a = np.asarray(a)
-    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)) or (size is not None and a.size != size):
-        raise ValueError(f"{name} must be a 1-D integer table" + (f" of {size} entries" if size is not None else "") + f", got {a.dtype} {a.shape}")
-    a = a.astype(np.int64)
-    if a.size and (int(a.min()) < -2**31 or int(a.max()) > 2**31 - 1):
-        raise ValueError(f"{name} does not fit int32")
-    return a
-
-
-def _offsets(name: str, a) -> np.ndarray:
-    a = _int32_table(name, a)
-    if a.size < 1 or int(a[0]) < 0 or np.any(np.diff(a) < 0):
-        raise ValueError(f"{name} must hold at least one entry, start at >= 0 and ascend")
-    return a
-
-
-def _upload(tables: Sequence[np.ndarray], dtype, device):
-    """Host tables of one dtype -> device views of ONE pinned upload."""
-    import torch
-
-    from . import _lib
-    sizes = [int(t.size) for t in tables]
-    flat = np.concatenate([np.asarray(t, dtype).reshape(-1) for t in tables]) if sum(sizes) else np.zeros(0, dtype)
-    dev = _lib.upload_async(torch.from_numpy(flat), device)
-    out, pos = [], 0
-    for n in sizes:
-        out.append(dev[pos:pos + n])
-        pos += n
-    return out
-
-
 def match_groups(err, est_off, gt_off, pair_off, gt_valid, group_tab, ths):
     """fp_detection_match with its host tables checked first (ValueError before any launch): err f64 [P, 2] ON THE DEVICE (ops.pose_errors'
     first output); est_off / gt_off / pair_off [NG + 1] ascending, group g owning E_g estimates (in rank order), G_g <= 256 GT instances and
@@ -73,25 +42,16 @@ def match_groups(err, est_off, gt_off, pair_off, gt_valid, group_tab, ths):
         raise ValueError("match_groups: err is a device tensor (the errors are not read back); there is no CPU path")
     if err.dtype != torch.float64 or err.dim() != 2 or err.shape[1] != 2 or not err.is_contiguous():
         raise ValueError(f"match_groups: err must be a contiguous float64 [P, 2] tensor, got {err.dtype} {tuple(err.shape)}")
-    est_off, gt_off, pair_off = _offsets("est_off", est_off), _offsets("gt_off", gt_off), _offsets("pair_off", pair_off)
-    NG = est_off.size - 1
-    if gt_off.size != NG + 1 or pair_off.size != NG + 1:
-        raise ValueError("match_groups: est_off, gt_off and pair_off must have the same length")
-    gt_valid, group_tab = _int32_table("gt_valid", gt_valid), _int32_table("group_tab", group_tab, NG)
+    gt_valid = int32_table("gt_valid", gt_valid)
+    est_off, gt_off, pair_off, NG = check_groups("match_groups", est_off, gt_off, pair_off, gt_valid.size, int(err.shape[0]), "err", "gt_valid")
+    group_tab = int32_table("group_tab", group_tab, NG)
     ths = np.ascontiguousarray(np.asarray(ths, np.float64))
     if ths.ndim != 3 or ths.shape[1] != 2 or not 1 <= ths.shape[2] <= MAX_THS:
         raise ValueError(f"match_groups: ths must be [NTAB, 2, T] with 1 <= T <= {MAX_THS}, got {ths.shape}")
-    E, G = np.diff(est_off), np.diff(gt_off)
-    if NG and int(G.max()) > MAX_GROUP_GT:
-        raise ValueError(f"match_groups: group {int(np.argmax(G))} has {int(G.max())} GT instances (at most {MAX_GROUP_GT})")
-    if int(gt_off[-1]) > gt_valid.size:
-        raise ValueError(f"match_groups: gt_off reaches {int(gt_off[-1])}, gt_valid has {gt_valid.size} entries")
-    if np.any(np.diff(pair_off) != E * G) or int(pair_off[-1]) > int(err.shape[0]):
-        raise ValueError("match_groups: group g must own E_g x G_g rows of err from pair_off[g]")
     if NG and (ths.shape[0] < 1 or int(group_tab.min()) < 0 or int(group_tab.max()) >= ths.shape[0]):
         raise ValueError(f"match_groups: group_tab must index the {ths.shape[0]} rows of ths")
-    d_est, d_gt, d_pair, d_valid, d_tab = _upload([est_off, gt_off, pair_off, gt_valid, group_tab], np.int32, err.device)
-    d_ths, = _upload([ths], np.float64, err.device)
+    d_est, d_gt, d_pair, d_valid, d_tab = upload([est_off, gt_off, pair_off, gt_valid, group_tab], np.int32, err.device)
+    d_ths, = upload([ths], np.float64, err.device)
     return ops.detection_match(d_est, d_gt, d_pair, err, d_valid, d_tab, d_ths.reshape(ths.shape), int(est_off[-1]))
 
 
@@ -106,8 +66,8 @@ def ap_objects(flag, obj_off, order, n_valid, rec_thr=None):
         raise ValueError("ap_objects: flag is a device tensor (match_groups' output, not read back); there is no CPU path")
     if flag.dtype != torch.int8 or flag.dim() != 2 or flag.shape[1] % 2 or not 1 <= flag.shape[1] // 2 <= MAX_THS or not flag.is_contiguous():
         raise ValueError(f"ap_objects: flag must be a contiguous int8 [N_est, 2 T] tensor with 1 <= T <= {MAX_THS}, got {flag.dtype} {tuple(flag.shape)}")
-    obj_off, order = _offsets("obj_off", obj_off), _int32_table("order", order)
-    n_valid = _int32_table("n_valid", n_valid, obj_off.size - 1)
+    obj_off, order = offsets("obj_off", obj_off), int32_table("order", order)
+    n_valid = int32_table("n_valid", n_valid, obj_off.size - 1)
     rec_thr = np.ascontiguousarray(np.asarray(REC_THR if rec_thr is None else rec_thr, np.float64))
     if rec_thr.ndim != 1 or not 1 <= rec_thr.size <= MAX_REC:
         raise ValueError(f"ap_objects: 1 <= R <= {MAX_REC} recall thresholds are needed, got {rec_thr.shape}")
@@ -115,8 +75,8 @@ def ap_objects(flag, obj_off, order, n_valid, rec_thr=None):
         raise ValueError(f"ap_objects: obj_off reaches {int(obj_off[-1])}, order has {order.size} entries")
     if order.size and (int(order.min()) < 0 or int(order.max()) >= int(flag.shape[0])):
         raise ValueError(f"ap_objects: order must index the {int(flag.shape[0])} rows of flag")
-    d_off, d_order, d_valid = _upload([obj_off, order, n_valid], np.int32, flag.device)
-    d_thr, = _upload([rec_thr], np.float64, flag.device)
+    d_off, d_order, d_valid = upload([obj_off, order, n_valid], np.int32, flag.device)
+    d_thr, = upload([rec_thr], np.float64, flag.device)
     return ops.detection_ap(d_off, d_order, flag, d_valid, d_thr)
 
 
@@ -254,18 +214,8 @@ def evaluate_bop24(result_csv: str, split_dir: str, targets: Union[None, str, Se
     width_of = {k: image_width(split_dir, *k) for k in images if k in with_rows}
     tb = build_tables(rows, images, gts, infos, diameters, width_of)
 
-    ev = defaultdict(float)
-    events = []
-
-    def timed(kind, fn, *a, **kw):
-        if not timing:
-            return fn(*a, **kw)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = fn(*a, **kw)
-        e1.record()
-        events.append((kind, e0, e1))
-        return out
+    timer = DeviceTimer(timing)
+    timed = timer.timed
 
     # ---- MSSD / MSPD of every estimate x every GT instance of its group: one launch per block of images, nothing read back
     syms, pts_dev = {}, {}
@@ -316,10 +266,7 @@ def evaluate_bop24(result_csv: str, split_dir: str, targets: Union[None, str, Se
     if details:
         out["tables"] = dict(tb, err=err.cpu().numpy(), flag=flag.cpu().numpy(), matched_gt=matched.cpu().numpy(), ap=ap, q=q_d.cpu().numpy(), totals=totals)
     if timing:
-        torch.cuda.synchronize()
-        for kind, e0, e1 in events:
-            ev[kind] += e0.elapsed_time(e1) / 1e3
-        out["device_seconds"] = dict(ev)
+        out["device_seconds"] = timer.seconds()
     return out
 
 

@@ -23,8 +23,10 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
+from .device_timer import DeviceTimer
 from .eval_bop19 import _read_json
-from .eval_bop24 import MAX_GROUP_GT, MAX_THS, REC_THR, _int32_table, _offsets, _upload, ap_objects, target_images
+from .eval_bop24 import REC_THR, ap_objects, target_images
+from .group_tables import MAX_GROUP_GT, MAX_THS, check_groups, int32_table, upload
 
 IOU_THS = np.linspace(0.5, 0.95, 10)     # COCO's thresholds as pycocotools makes them
 MAX_DETS_LIMIT = 256                      # detections of one (image, object) that the matching takes
@@ -44,21 +46,11 @@ def match_groups(overlap, est_off, gt_off, pair_off, gt_ignore, ths=IOU_THS):
         raise ValueError("match_groups: overlap is a device tensor (the overlaps are not read back); there is no CPU path")
     if overlap.dtype != torch.float64 or overlap.dim() != 1 or not overlap.is_contiguous():
         raise ValueError(f"match_groups: overlap must be a contiguous float64 [P] tensor, got {overlap.dtype} {tuple(overlap.shape)}")
-    est_off, gt_off, pair_off = _offsets("est_off", est_off), _offsets("gt_off", gt_off), _offsets("pair_off", pair_off)
-    NG = est_off.size - 1
-    if gt_off.size != NG + 1 or pair_off.size != NG + 1:
-        raise ValueError("match_groups: est_off, gt_off and pair_off must have the same length")
-    gt_ignore = _int32_table("gt_ignore", gt_ignore)
+    gt_ignore = int32_table("gt_ignore", gt_ignore)
+    est_off, gt_off, pair_off, _ = check_groups("match_groups", est_off, gt_off, pair_off, gt_ignore.size, int(overlap.shape[0]), "overlap", "gt_ignore")
     ths = check_thresholds(ths)
-    E, G = np.diff(est_off), np.diff(gt_off)
-    if NG and int(G.max()) > MAX_GROUP_GT:
-        raise ValueError(f"match_groups: group {int(np.argmax(G))} has {int(G.max())} GT instances (at most {MAX_GROUP_GT})")
-    if int(gt_off[-1]) > gt_ignore.size:
-        raise ValueError(f"match_groups: gt_off reaches {int(gt_off[-1])}, gt_ignore has {gt_ignore.size} entries")
-    if np.any(np.diff(pair_off) != E * G) or int(pair_off[-1]) > int(overlap.shape[0]):
-        raise ValueError("match_groups: group g must own E_g x G_g rows of overlap from pair_off[g]")
-    d_est, d_gt, d_pair, d_ign = _upload([est_off, gt_off, pair_off, gt_ignore], np.int32, overlap.device)
-    d_ths, = _upload([ths], np.float64, overlap.device)
+    d_est, d_gt, d_pair, d_ign = upload([est_off, gt_off, pair_off, gt_ignore], np.int32, overlap.device)
+    d_ths, = upload([ths], np.float64, overlap.device)
     return ops.coco_match(d_est, d_gt, d_pair, overlap, d_ign, d_ths, int(est_off[-1]))
 
 
@@ -241,15 +233,8 @@ def evaluate_coco(detections, split_dir: str, targets: Union[None, str, Sequence
     T = int(ths.size)
     dev = torch.device(device)
     host = defaultdict(float)
-    events = []
-
-    def timed(kind, fn, *a, **kw):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = fn(*a, **kw)
-        e1.record()
-        events.append((kind, e0, e1))
-        return out
+    timer = DeviceTimer()
+    timed = timer.timed
 
     # ---- the blocks: consecutive target images of one size, image_block at most
     segm = iou_type == "segm"
@@ -302,7 +287,7 @@ def evaluate_coco(detections, split_dir: str, targets: Union[None, str, Sequence
                 if tuple(int(v) for v in r["segmentation"]["size"]) != (h, w):
                     raise ValueError(f"a detection of scene {r['scene_id']} image {r['image_id']} lies on a canvas of {r['segmentation']['size'][1]} x "
                                      f"{r['segmentation']['size'][0]}, the image is {w} x {h}")
-        d_est, d_gt, d_pair = _upload([tb["est_off"], tb["gt_off"], tb["pair_off"]], np.int32, dev)
+        d_est, d_gt, d_pair = upload([tb["est_off"], tb["gt_off"], tb["pair_off"]], np.int32, dev)
         if P == 0:
             overlap = torch.zeros(0, dtype=torch.float64, device=dev)
         elif segm:
@@ -322,7 +307,7 @@ def evaluate_coco(detections, split_dir: str, targets: Union[None, str, Sequence
             _, overlap, _ = timed("overlap", ops.group_mask_iou, words_a, words_b, d_est, d_gt, d_pair, P)
         else:
             boxes_a = np.array([[float(v) for v in r["bbox"]] for r in preds], np.float64).reshape(-1, 4)
-            d_a, d_b = _upload([boxes_a, tb["gt_boxes"]], np.float64, dev)
+            d_a, d_b = upload([boxes_a, tb["gt_boxes"]], np.float64, dev)
             overlap, _ = timed("overlap", ops.group_box_iou, d_a.reshape(-1, 4), d_b.reshape(-1, 4), d_est, d_gt, d_pair, P)
         flag, matched = timed("match", match_groups, overlap, tb["est_off"], tb["gt_off"], tb["pair_off"], tb["gt_ignore"], ths)
         flags.append(flag)
@@ -341,10 +326,7 @@ def evaluate_coco(detections, split_dir: str, targets: Union[None, str, Sequence
         flag = torch.cat([flag, flag[:, -1:]], dim=1)
     ap_d, q_d, totals_d = timed("ap", ap_objects, flag.contiguous(), obj_off, order, nv)
     ap, totals = ap_d.cpu().numpy()[:, :T], totals_d.cpu().numpy()[:, :T]
-    torch.cuda.synchronize()
-    dev_s = defaultdict(float)
-    for kind, e0, e1 in events:
-        dev_s[kind] += e0.elapsed_time(e1) / 1e3
+    dev_s = timer.seconds()
 
     s = summarize(ap, totals, nv, ths)
     out = {"coco_average_precision": s["ap"], "coco_average_precision_50": s["ap50"], "coco_average_precision_75": s["ap75"],
@@ -355,7 +337,7 @@ def evaluate_coco(detections, split_dir: str, targets: Union[None, str, Sequence
            "num_detections_of_other_images": int(num_other), "num_detections_beyond_max_dets": int(num_cut),
            "num_gt_instances": int(sum(n_valid.values()) + sum(n_ignored.values())), "num_ignored_gt_instances": int(sum(n_ignored.values())),
            "num_pairs": int(num_pairs), "num_ignored_detections": totals[:, :, 2].sum(0).tolist() if len(obj_ids) else [0] * T,
-           "per_object": {}, "device_seconds": dict(dev_s), "host_seconds": dict(host, total=time.perf_counter() - t_start)}
+           "per_object": {}, "device_seconds": dev_s, "host_seconds": dict(host, total=time.perf_counter() - t_start)}
     for o, lid in enumerate(obj_ids):
         has = int(nv[o]) > 0
         out["per_object"][str(lid)] = {

@@ -26,6 +26,7 @@ from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .device_timer import DeviceTimer
 from .eval_bop19 import DEFAULT_VSD_DELTA, MAX_IO_WORKERS, NEAR_LIMIT_MM, VSD_DELTA
 
 MIN_VISIB_FRACT = 0.1              # test_targets_bop19.json counts the instances at least this visible
@@ -214,15 +215,8 @@ def write_gt_info(split_dir: str, models_dir: str, dataset: Optional[str] = None
     ras = HipRasterizer(device)
     for lid, m in meshes.items():
         ras.add_object_model(lid, mesh=m)
-    events = []
-
-    def timed(kind, fn, *a, **kw):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = fn(*a, **kw)
-        e1.record()
-        events.append((kind, e0, e1))
-        return out
+    timer = DeviceTimer()
+    timed = timer.timed
 
     n_images = n_inst = n_low = 0
     all_inst: List[Tuple[int, int, int, float]] = []
@@ -305,10 +299,7 @@ def write_gt_info(split_dir: str, models_dir: str, dataset: Optional[str] = None
     if target_path:
         with open(target_path, "w") as f:
             json.dump(count_targets(all_inst, targets), f)
-    torch.cuda.synchronize()
-    dev_s = defaultdict(float)
-    for kind, e0, e1 in events:
-        dev_s[kind] += e0.elapsed_time(e1) / 1e3
+    dev_s = timer.seconds()
     return {"num_scenes": len(plan), "num_images": int(n_images), "num_instances": int(n_inst), "num_instances_below_min_visib": int(n_low),
             "min_visib_fract": MIN_VISIB_FRACT, "delta": delta, "dataset": dataset, "depth_from_gt": bool(depth_from_gt),
             "masks_written": bool(write_masks), "targets": target_path, "wall_seconds": time.perf_counter() - t_start,

@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import call, knn_scratch_bytes, ptr, stream, require_cuda
+from .group_tables import MAX_REC, MAX_THS
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
@@ -1068,9 +1069,6 @@ def pose_nms_greedy(group_off: torch.Tensor, pair_off: torch.Tensor, pairs: torc
     return keep, by
 
 
-DETECTION_MAX_THS, DETECTION_MAX_GROUP_GT, DETECTION_MAX_REC = 16, 256, 128  # FP_DETECTION_* of the header
-
-
 def _detection_tables(name: str, tables) -> None:
     for x, dt in tables:
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
@@ -1088,8 +1086,8 @@ def detection_match(est_off: torch.Tensor, gt_off: torch.Tensor, pair_off: torch
     _detection_tables("detection_match", ((est_off, torch.int32), (gt_off, torch.int32), (pair_off, torch.int32), (err, torch.float64),
                                           (gt_valid, torch.int32), (group_tab, torch.int32), (ths, torch.float64)))
     NG = int(est_off.shape[0]) - 1
-    if ths.dim() != 3 or ths.shape[1] != 2 or not 1 <= int(ths.shape[2]) <= DETECTION_MAX_THS or (NG > 0 and ths.shape[0] < 1):
-        raise ValueError(f"detection_match: ths must be [NTAB >= 1, 2, T] with 1 <= T <= {DETECTION_MAX_THS}, got {tuple(ths.shape)}")
+    if ths.dim() != 3 or ths.shape[1] != 2 or not 1 <= int(ths.shape[2]) <= MAX_THS or (NG > 0 and ths.shape[0] < 1):
+        raise ValueError(f"detection_match: ths must be [NTAB >= 1, 2, T] with 1 <= T <= {MAX_THS}, got {tuple(ths.shape)}")
     if NG < 0 or int(gt_off.shape[0]) != NG + 1 or int(pair_off.shape[0]) != NG + 1 or group_tab.numel() != NG or err.dim() != 2 or err.shape[1] != 2 \
             or num_est < 0:
         raise ValueError("detection_match: table sizes do not match")
@@ -1108,10 +1106,10 @@ def detection_ap(obj_off: torch.Tensor, order: torch.Tensor, flag: torch.Tensor,
     int32 [O, C, 3])."""
     _detection_tables("detection_ap", ((obj_off, torch.int32), (order, torch.int32), (flag, torch.int8), (n_valid, torch.int32), (rec_thr, torch.float64)))
     O, R = int(obj_off.shape[0]) - 1, int(rec_thr.numel())
-    if flag.dim() != 2 or flag.shape[1] % 2 or not 1 <= int(flag.shape[1]) // 2 <= DETECTION_MAX_THS:
-        raise ValueError(f"detection_ap: flag must be [N_est, 2 T] with 1 <= T <= {DETECTION_MAX_THS}, got {tuple(flag.shape)}")
-    if not 1 <= R <= DETECTION_MAX_REC:
-        raise ValueError(f"detection_ap: 1 <= R <= {DETECTION_MAX_REC} recall thresholds are needed, got {R}")
+    if flag.dim() != 2 or flag.shape[1] % 2 or not 1 <= int(flag.shape[1]) // 2 <= MAX_THS:
+        raise ValueError(f"detection_ap: flag must be [N_est, 2 T] with 1 <= T <= {MAX_THS}, got {tuple(flag.shape)}")
+    if not 1 <= R <= MAX_REC:
+        raise ValueError(f"detection_ap: 1 <= R <= {MAX_REC} recall thresholds are needed, got {R}")
     if O < 0 or n_valid.numel() != O or order.dim() != 1:
         raise ValueError("detection_ap: table sizes do not match")
     C = int(flag.shape[1])
@@ -1352,8 +1350,8 @@ def coco_match(est_off: torch.Tensor, gt_off: torch.Tensor, pair_off: torch.Tens
     matched_gt int32 [num_est, T]); an estimate of no group keeps flag 0 and matched_gt -1."""
     NG = _group_tables("coco_match", est_off, gt_off, pair_off)
     _detection_tables("coco_match", ((overlap, torch.float64), (gt_ignore, torch.int32), (ths, torch.float64)))
-    if ths.dim() != 1 or not 1 <= int(ths.shape[0]) <= DETECTION_MAX_THS:
-        raise ValueError(f"coco_match: ths must be [T] with 1 <= T <= {DETECTION_MAX_THS}, got {tuple(ths.shape)}")
+    if ths.dim() != 1 or not 1 <= int(ths.shape[0]) <= MAX_THS:
+        raise ValueError(f"coco_match: ths must be [T] with 1 <= T <= {MAX_THS}, got {tuple(ths.shape)}")
     if overlap.dim() != 1 or gt_ignore.dim() != 1 or num_est < 0:
         raise ValueError("coco_match: table sizes do not match")
     T = int(ths.shape[0])

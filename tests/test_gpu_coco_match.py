@@ -79,6 +79,24 @@ def test_a_group_of_256_by_256():
     assert len(got) > 200 and len(set(got)) == len(got)                                      # no instance is used twice
 
 
+@pytest.mark.parametrize("num_groups, empty_last", [(1, False), (5, False), (6, True)])
+def test_waves_of_the_last_workgroup(num_groups, empty_last):
+    """One wave per (group, threshold), four to a workgroup, T = 1: NG T = 1 leaves three idle waves in the only workgroup, 5 puts one
+    live wave into a second one, and in 6 the last live wave's group has no estimate.  Every case holds a matched and an unmatched estimate."""
+    rng = np.random.default_rng(40 + num_groups)
+    groups = []
+    for g in range(num_groups):
+        E, G = int(rng.integers(2, 9)), int(rng.integers(1, 9))
+        ov = VALUES[rng.integers(0, len(VALUES), (E, G))]
+        ov[0, 0], ov[1, :] = 0.75, 0.25                      # estimate 0 finds an instance, estimate 1 none
+        groups.append((ov, sorted(int(v) for v in rng.integers(0, 2, G))))
+    if empty_last:
+        groups[-1] = (np.zeros((0, 3)), [0, 0, 1])
+    flag, matched, off = check(groups, [0.5])
+    assert flag[0, 0] in (1, 2) and matched[0, 0] >= 0 and (flag[1, 0], matched[1, 0]) == (0, -1)
+    assert off[-1] == flag.shape[0] and (not empty_last or off[-1] == off[-2])
+
+
 def test_refused_before_any_launch():
     from foundpose_amd import eval_coco
     ov = torch.zeros(4, dtype=torch.float64, device=DEV)

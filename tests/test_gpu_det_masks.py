@@ -130,6 +130,27 @@ def test_many_runs():
         assert int(area[0]) == 0 and not opened.any()
 
 
+@pytest.mark.parametrize("open3x3", [False, True])
+def test_run_counts_around_one_scan_chunk(open3x3):
+    """The prefix sums are scanned in chunks of 256 runs with a carry: detections of exactly 255, 256 and 257 runs (one short of a chunk,
+    a whole one, one entry in a second) on a 32 x 32 canvas, in one batch.  Run lengths are >= 1 and sum to 1024.  The reference is the
+    decode rule as tests/test_det_masks_cpu.py restates it, then open_mask_3x3."""
+    from tests.test_det_masks_cpu import _decode_rule
+    rng = np.random.default_rng(255)
+    lists = []
+    for R in (255, 256, 257):
+        p = np.full(R, 0.4 / R)
+        p[[1, 60, 121, 180, 201, R - 2]] += 0.1              # a few long runs, set and unset: blocks that survive the opening
+        lists.append((rng.multinomial(1024 - R, p) + 1).tolist())
+    assert [len(c) for c in lists] == [255, 256, 257] and all(sum(c) == 1024 for c in lists)
+    masks, area = _run([{"counts": c, "size": [32, 32]} for c in lists], (32, 32), open3x3)
+    for i, c in enumerate(lists):
+        want = _decode_rule(c, 32, 32).astype(np.uint8)
+        if open3x3:
+            want = ipu.open_mask_3x3(want)
+        assert want.any() and np.array_equal(masks[i].numpy(), want) and int(area[i]) == int(want.sum()), len(c)
+
+
 def test_a_detection_depends_on_its_own_runs_only():
     """Eight detections of very different run counts in one call: the same bits as each alone and as the reversed batch."""
     hc, wc, image = 96, 128, (90, 120)

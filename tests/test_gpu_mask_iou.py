@@ -140,6 +140,34 @@ def test_a_group_alone_and_permuted_groups_give_the_same_bytes(groups):
         assert np.array_equal(c2[a], counts[b]) and np.array_equal(o2[a].view(np.int64), overlap[b].view(np.int64)) and np.array_equal(s2[a], status[b])
 
 
+@pytest.mark.parametrize("third", ["1x1", "1x2", "5x1"])
+@pytest.mark.parametrize("num_groups", [257, 600])
+def test_tile_table_across_the_scan_chunks(num_groups, third):
+    """The tile table is a scan in chunks of 256 groups with a carry: 257 groups put one entry into the second chunk, 600 cross two seams.
+    Groups of 1 x 1 on masks of 2 x 70 (L = 4 words, the last one partial); every third group is `third` instead.  1 x 2 still takes one
+    tile (4 x 4 tiles), 5 x 1 takes two, so only the last variant makes the tile counts differ between groups.  The reference is numpy's
+    popcount of the packed words."""
+    from foundpose_amd import ops
+    rng = np.random.default_rng(num_groups)
+    E3, G3 = (int(v) for v in third.split("x"))
+    shapes = [(E3, G3) if g % 3 == 2 else (1, 1) for g in range(num_groups)]
+    est_off, gt_off = np.cumsum([0] + [E for E, _ in shapes]), np.cumsum([0] + [G for _, G in shapes])
+    pair_off = np.cumsum([0] + [E * G for E, G in shapes])
+    a, b = random_masks(rng, int(est_off[-1]), 2, 70), random_masks(rng, int(gt_off[-1]), 2, 70)
+    a[est_off[4]], b[gt_off[4]] = 0, 0                                     # group 4 (1 x 1): union 0
+    wa, wb = (np_pack(m)[0].reshape(len(m), 4) for m in (a, b))
+    pop = lambda w: np.unpackbits(np.ascontiguousarray(w).view(np.uint8).reshape(len(w), -1), axis=1).sum(1).astype(np.int64)
+    rows_a = np.concatenate([np.repeat(np.arange(est_off[g], est_off[g + 1]), G) for g, (_, G) in enumerate(shapes)])
+    rows_b = np.concatenate([np.tile(np.arange(gt_off[g], gt_off[g + 1]), E) for g, (E, _) in enumerate(shapes)])
+    inter = pop(wa[rows_a] & wb[rows_b])
+    union = pop(wa[rows_a]) + pop(wb[rows_b]) - inter
+    want = np.where(union > 0, inter.astype(np.float64) / np.maximum(union, 1).astype(np.float64), 0.0)
+    counts, overlap, status = run_groups([a], [b], est_off, gt_off, pair_off)
+    assert np.array_equal(counts[:, 0], inter) and np.array_equal(counts[:, 1], union)
+    assert np.array_equal(overlap.view(np.int64), want.view(np.int64)) and np.array_equal(status, np.where(union > 0, 0, 2))
+    assert status[pair_off[4]] == 2 and (union > 0).sum() == len(union) - 1 and (inter > 0).any()
+
+
 def test_offsets_beyond_the_arrays_are_clamped(groups):
     """Tables that the host would refuse: the kernel clamps them into the arrays, writes only rows that exist and nothing faults."""
     A, B, *_ = groups

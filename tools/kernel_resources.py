@@ -16,8 +16,8 @@ for line in out.splitlines():
         cur = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
         rows[cur] = {}
         continue
-    m = re.search(r"remark:\s+(VGPRs|AGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
+    m = re.search(r"remark:\s+(TotalSGPRs|VGPRs|AGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
     if m and cur:
         rows[cur][m.group(1)] = int(m.group(2))
 for k, v in rows.items():
-    print(f"{v.get('VGPRs', 0):4d} vgpr {v.get('AGPRs', 0):4d} agpr  spill {v.get('VGPRs Spill', 0):3d}  scratch {v.get('ScratchSize [bytes/lane]', 0):4d}  occ {v.get('Occupancy [waves/SIMD]', 0)}  {k[:150]}")
+    print(f"{v.get('VGPRs', 0):4d} vgpr {v.get('AGPRs', 0):4d} agpr {v.get('TotalSGPRs', 0):4d} sgpr {v.get('LDS Size [bytes/block]', 0):6d} lds  spill {v.get('VGPRs Spill', 0):3d}  scratch {v.get('ScratchSize [bytes/lane]', 0):4d}  occ {v.get('Occupancy [waves/SIMD]', 0)}  {k[:150]}")
