@@ -116,24 +116,36 @@ def test_knn_interface_matches_reference_conventions():
 
 @pytest.mark.parametrize("soft", [False, True])
 def test_tfidf_build(soft):
+    """Segments next to each other in one launch vs calc_tfidf per segment.  The soft-assignment path stages (id, value) entries in
+    chunks of 4096: Q * knn_k = 4095 / 4098 / 4107 (the 37 x 37 grid of a 518-pixel crop) / 6144 / 8193 / 4112 put the seam just past,
+    inside and at the end of a segment, next to segments of length 1 and 0.  W = 1000 is no multiple of 256 (the threads' bin stride)
+    or of 16 (the norm chain's vector width: a scalar tail)."""
     from foundpose_amd import ops
-    rng = np.random.default_rng(5)
-    W, k = 256, 3
-    counts = [37, 1, 512, 90]
-    Q = sum(counts)
-    ids = rng.integers(0, W, (Q, k)).astype(np.int32)
-    d2 = (rng.random((Q, k)) * 30).astype(np.float32)
-    idf = (rng.random(W) * 3).astype(np.float32)
-    seg = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
-    desc, desc_n = ops.tfidf_build(cu(ids), cu(d2), cu(seg), cu(idf), soft, 10.0, sqrt_dists=True)
-    for s in range(len(counts)):
-        sl = slice(seg[s], seg[s + 1])
-        ref = om.calc_tfidf(ids[sl].astype(np.int64), np.sqrt(d2[sl]), idf, soft, 10.0)
-        if soft:  # expf vs numpy exp: 1-2 ulp on the weights
-            np.testing.assert_allclose(desc[s].cpu().numpy(), ref, rtol=2e-6, atol=1e-9)
-        else:
-            assert np.array_equal(desc[s].cpu().numpy(), ref)
-            assert np.array_equal(desc_n[s].cpu().numpy(), om.l2_normalize_rows(ref[None])[0])
+    for seed, W, k, counts in [(5, 256, 3, [37, 1, 512, 90]),
+                               (6, 256, 3, [1365, 1, 1366, 0, 1369, 5, 2048, 2731]),
+                               (7, 1000, 3, [1369, 0, 1, 2731, 1366, 1365]),
+                               (8, 256, 16, [257, 1, 0, 3]),
+                               (9, 1000, 16, [0, 257, 1])]:
+        rng = np.random.default_rng(seed)
+        Q = sum(counts)
+        ids = rng.integers(0, W, (Q, k)).astype(np.int32)
+        d2 = (rng.random((Q, k)) * 30).astype(np.float32)
+        idf = (rng.random(W) * 3).astype(np.float32)
+        seg = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        desc, desc_n = (t.cpu().numpy() for t in ops.tfidf_build(cu(ids), cu(d2), cu(seg), cu(idf), soft, 10.0, sqrt_dists=True))
+        for s in range(len(counts)):
+            what = (W, k, counts, s)
+            if counts[s] == 0:   # no patches: nothing to add, and 0 / max(0, eps) stays finite
+                assert not desc[s].any() and np.all(np.isfinite(desc_n[s])), what
+                continue
+            sl = slice(seg[s], seg[s + 1])
+            ref = om.calc_tfidf(ids[sl].astype(np.int64), np.sqrt(d2[sl]), idf, soft, 10.0)
+            if soft:  # expf vs numpy exp: 1-2 ulp on the weights
+                np.testing.assert_allclose(desc[s], ref, rtol=2e-6, atol=1e-9, err_msg=str(what))
+                assert np.array_equal(desc_n[s], om.l2_normalize_rows(desc[s][None])[0]), what   # the device's own desc, normalised
+            else:
+                assert np.array_equal(desc[s], ref), what
+                assert np.array_equal(desc_n[s], om.l2_normalize_rows(ref[None])[0]), what
 
 
 def _gpu_corresp(repre_np, pts, feats, top_n, top_k, tie_order="canonical"):
