@@ -1,11 +1,16 @@
 """ctypes binding of libfoundpose_amd.so (the C ABI in include/foundpose_amd.h).
 
+The header is the one declaration of the ABI: the argument types of every entry point, the list of exported symbols and ABI_VERSION are
+parsed from it on import (_parse_header).  What stays written by hand here -- the three ViT structs, the FP_* constants and the scratch-size
+formulas -- is compared with the header, compiled, by tests/test_cabi_symbols.py.
+
 There is NO fallback: if the library is missing or a call fails, this raises. The product
 path never computes on the CPU and never touches oracle/.
 """
 
 import ctypes as C
 import os
+import re
 
 import torch
 
@@ -18,7 +23,17 @@ FP_F32, FP_BF16, FP_FP8, FP_F16X3, FP_F16F8, FP_F16 = 0, 1, 2, 3, 4, 5
 GEMM_SPLIT_F16F8 = 1 << 20   # FP_GEMM_SPLIT_F16F8 of the header
 GEMM_F16 = 1 << 21           # FP_GEMM_F16 of the header: IEEE fp16 operands / outputs in fp_gemm_bf16, fp_gemm_bf16_ln
 SPLIT_SCALE_ACT, SPLIT_SCALE_QKV, SPLIT_SCALE_HID = 16.0, 16.0, 4.0  # FP_SPLIT_SCALE_* of the header
-ABI_VERSION = 20
+
+
+class FoundPoseNativeError(RuntimeError):
+    pass
+
+
+class FoundPoseSaturationError(FoundPoseNativeError):
+    """The f16x3 (near-exact) mode clamped an activation to the range of its split-fp16 row (+-4094 for LayerNorm outputs / q / k / v,
+    +-16376 for hidden activations; include/foundpose_amd.h): the features are then no longer the fp32 arithmetic's, and the mode whose
+    purpose is index-exact matching must not return a plausible wrong neighbour silently."""
+
 
 vp, i32, i64, f32, f64, u64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_uint64
 
@@ -46,114 +61,46 @@ class VitWorkspace(C.Structure):
     ]
 
 
-_PROTOS = {
-    "fp_abi_version": [],
-    "fp_sqnorm_rows": [vp, i64, i32, vp, vp],
-    "fp_normalize_rows": [vp, i64, i32, f32, vp, vp],
-    "fp_knn_l2": [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],
-    "fp_tfidf_build": [vp, vp, i32, vp, i32, vp, i32, i32, f32, i32, vp, vp, f32, vp],
-    "fp_cosine_topk": [vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp],
-    "fp_cosine_topk_prefiltered": [vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp],
-    "fp_cyclic_buddies": [vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32,
-                          vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
-    "fp_pack_records": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp],
-    "fp_pnp_ransac": [vp, vp, vp, vp, i32, i32, i32, i32, f64, f64, i32, i32, u64, vp, vp, vp, vp, vp, vp, vp],
-    "fp_pnp_ransac_keyed": [vp, vp, vp, vp, vp, i32, i32, i32, i32, f64, f64, i32, i32, u64, vp, vp, vp, vp, vp, vp, vp],
-    "fp_kabsch_ransac": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, f64, i32, i32, u64, vp, vp, vp, vp, vp, vp, vp, vp],
-    "fp_pose_verify_depth": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
-    "fp_pose_verify_mask": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
-    "fp_pose_overlap": [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp],
-    "fp_pose_nms_greedy": [vp, vp, i32, vp, vp, vp, i32, i32, f64, vp, vp, vp],
-    "fp_detection_match": [vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp],
-    "fp_detection_ap": [vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp],
-    "fp_detection_masks": [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
-    "fp_mask_boxes": [vp, i32, i32, i32, vp, vp, vp],
-    "fp_proposal_crops": [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp],
-    "fp_proposal_scores": [vp, i32, i32, vp, i32, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp],
-    "fp_proposal_rank": [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
-    "fp_box_iou": [vp, i32, vp, i32, vp, vp, vp],
-    "fp_proposal_patch_cover": [vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp],
-    "fp_proposal_appearance": [vp, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp],
-    "fp_mask_pack": [vp, i32, i32, i32, vp, vp, vp],
-    "fp_group_mask_iou": [vp, i32, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp],
-    "fp_group_box_iou": [vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp],
-    "fp_coco_match": [vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp],
-    "fp_sample_bilinear": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp],
-    "fp_pca_project": [vp, i32, i32, vp, i32, vp, vp, vp],
-    "fp_vit_forward": [C.POINTER(VitModel), C.POINTER(VitWorkspace), vp, i32, i32, i32, i32, vp],
-    "fp_vit_sample_features": [C.POINTER(VitModel), C.POINTER(VitWorkspace), i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp],
-    "fp_query_select": [vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "fp_vit_forward_prefix": [C.POINTER(VitModel), C.POINTER(VitWorkspace), vp, i32, i32, i32, i32, vp],
-    "fp_vit_block_selected": [C.POINTER(VitModel), C.POINTER(VitWorkspace), i32, i32, i32, i32, vp, vp, i32, i32, vp],
-    "fp_vit_sample_features_selected": [C.POINTER(VitModel), C.POINTER(VitWorkspace), i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp],
-    "fp_vit_features": [C.POINTER(VitModel), C.POINTER(VitWorkspace), i32, i32, i32, vp, vp, vp],
-    "fp_patchify": [vp, i32, i32, i32, i32, vp, i32, i32, vp],
-    "fp_layernorm": [vp, i32, vp, vp, f32, vp, i32, i32, i32, i32, i32, i32, i32, vp],
-    "fp_gemm_bf16": [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp],
-    "fp_gemm_bf16_ln": [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp],
-    "fp_gemm_resid_tile_rows": [i32, i32, i32],
-    "fp_gemm_wide_tile_rows": [i32, i32, i32, i32],
-    "fp_ln_finalize": [vp, i32, i32, i32, i32, f32, vp, vp],
-    "fp_gemm_fp8": [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, f32, vp],
-    "fp_quantize_fp8": [vp, i32, i64, f32, vp, vp],
-    "fp_gemm_split": [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, f32, f32, vp],
-    "fp_attention_split": [vp, i32, vp, i32, i32, i32, i32, i32, f32, f32, i32, vp],
-    "fp_layernorm_scaled": [vp, i32, vp, vp, f32, vp, i32, i32, f32, i32, i32, vp],
-    "fp_gemm_f32": [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp],
-    "fp_attention": [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp],
-    "fp_convert_f32_to_bf16": [vp, vp, i64, vp],
-    "fp_warp_crops": [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp],
-    "fp_warp_depth": [vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp],
-    "fp_render_setup": [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "fp_render_raster": [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "fp_texture_mips": [vp, i32, i32, vp, vp],
-    "fp_render_raster_textured": [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                  i32, i32, vp, vp],
-    "fp_template_downsample": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
-    "fp_pose_errors": [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp, vp],
-    "fp_pose_add_errors": [vp, i32, vp, vp, vp, i32, vp, C.c_size_t, vp, vp],
-    "fp_pts_diameter": [vp, i32, vp, C.c_size_t, vp, vp, vp],
-    "fp_directed_hausdorff": [vp, i32, i32, vp, i32, vp, C.c_size_t, vp, vp, vp],
-    "fp_vsd_counts": [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, C.c_size_t, vp, vp],
-    "fp_gt_visibility": [vp, i32, i32, i32, vp, i32, i32, vp, vp, i32, vp, C.c_size_t, vp, vp, vp, vp],
-    "fp_depth_plane_fit": [vp, i32, i32, i32, vp, vp, vp, vp, i32, i32, f64, f64, f64, u64, vp, C.c_size_t, vp, vp, vp, vp],
-    "fp_depth_components": [vp, i32, i32, i32, vp, vp, vp, vp, f64, f64, f32, vp, C.c_size_t, vp, vp],
-    "fp_component_table": [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, C.c_size_t, vp, vp, vp, vp],
-    "fp_component_runs": [vp, i32, i32, i32, vp, i32, i64, vp, vp, vp],
-    "fp_tsdf_integrate": [vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, f64, vp, C.c_size_t, vp, vp, vp, vp, vp],
-    "fp_tsdf_count_triangles": [vp, vp, i32, i32, i32, i32, vp, vp],
-    "fp_tsdf_emit_triangles": [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp],
-    "fp_tsdf_diffuse": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
-    "fp_mesh_cell_keys": [vp, i64, vp, i32, i32, i32, vp, vp],
-    "fp_mesh_cluster": [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, f64, vp, vp, vp, vp, vp, vp, vp],
-    "fp_tsdf_track": [vp, vp, vp, i32, i32, i32, i32, f64, vp, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp,
-                      vp, vp],
-    "fp_tsdf_track_rgb": [vp, vp, vp, vp, vp, i32, i32, i32, i32, f64, vp, vp, i64, vp, vp, vp, vp, vp, vp, f64, f64, i32, i32, i32, vp, C.c_size_t,
-                          vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "fp_featuremetric_refine": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, i32,
-                                vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "fp_depth_refine": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "fp_rgbd_refine": [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, C.c_double,
-                       i32, i32, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-    "fp_vis_pca_colorize": [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
-    "fp_vis_mask_tint": [vp, vp, i32, i32, i32, vp, vp],
-    "fp_vis_contour": [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp],
-    "fp_vis_resize_area": [vp, i32, i32, i32, i32, i32, vp, vp],
-    "fp_vis_draw_matches": [vp, vp, i32, i32, i32, i32, vp, f32, f32, f32, vp, vp],
-    "fp_vis_scene_composite": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
-}
+_BY_VALUE = {"int": i32, "int32_t": i32, "int64_t": i64, "float": f32, "double": f64, "uint64_t": u64, "size_t": C.c_size_t, "fp_stream_t": vp}
+_BY_POINTER = {"fp_vit_model": C.POINTER(VitModel), "fp_vit_workspace": C.POINTER(VitWorkspace)}  # every other pointer: c_void_p
+
+
+def _parse_header(path):
+    """The prototypes (name -> argtypes; all return int), every declared symbol and FP_ABI_VERSION, read from the header's declarations
+    `ret fp_name(args);`.  Nothing is guessed: whatever has no ctypes mapping below raises, naming the declaration."""
+    try:
+        text = open(path).read()
+    except OSError as e:
+        raise FoundPoseNativeError(f"cannot read the C ABI header {path}: {e}") from None
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    version = re.search(r"^#define\s+FP_ABI_VERSION\s+(\d+)\s*$", text, re.M)
+    if version is None:
+        raise FoundPoseNativeError(f"{path}: no #define FP_ABI_VERSION <integer>")
+    protos, names = {}, ["fp_last_error"]
+    for ret, name, params in re.findall(r"^([A-Za-z_][\w \t*]*?)\s*\b(fp_\w+)\s*\(([^()]*)\)\s*;", text, re.M):
+        ret = " ".join(ret.replace("*", " * ").split())
+        if name == "fp_last_error" and (ret, params.strip()) == ("const char *", "void"):
+            continue
+        if ret != "int":
+            raise FoundPoseNativeError(f"{path}: {name} returns '{ret}'; the binding knows int (and const char* fp_last_error(void)) only")
+        args = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            m = re.fullmatch(r"\s*(?:const\s+)?(\w+)\s*(\*?)\s*\w+\s*", p)
+            table = _BY_POINTER if m and m.group(2) else _BY_VALUE
+            if m is None or (table is _BY_VALUE and m.group(1) not in table):
+                raise FoundPoseNativeError(f"{path}: {name}: parameter '{' '.join(p.split())}' has no ctypes mapping")
+            args.append(table.get(m.group(1), vp))
+        protos[name] = args
+        names.append(name)
+    partial = sorted(set(re.findall(r"\b(fp_\w+)\s*\(", text)) - set(names))
+    if partial:
+        raise FoundPoseNativeError(f"{path}: cannot parse the declaration of {', '.join(partial)}")
+    return protos, sorted(names), int(version.group(1))
+
+
+_PROTOS, _SYMBOLS, ABI_VERSION = _parse_header(os.path.join(_HERE, "..", "include", "foundpose_amd.h"))
 
 _lib = None
-
-
-class FoundPoseNativeError(RuntimeError):
-    pass
-
-
-class FoundPoseSaturationError(FoundPoseNativeError):
-    """The f16x3 (near-exact) mode clamped an activation to the range of its split-fp16 row (+-4094 for LayerNorm outputs / q / k / v,
-    +-16376 for hidden activations; include/foundpose_amd.h): the features are then no longer the fp32 arithmetic's, and the mode whose
-    purpose is index-exact matching must not return a plausible wrong neighbour silently."""
 
 
 def lib() -> C.CDLL:
@@ -334,11 +281,15 @@ def texture_levels(width: int, height: int):
 
 
 def exported_symbols():
-    return sorted(list(_PROTOS) + ["fp_last_error"])
+    return list(_SYMBOLS)
 
 
-def call(name: str, *args) -> None:
+def call(name: str, *args, invalid=None) -> None:
+    """Runs an entry point; a non-zero status raises FoundPoseNativeError.  invalid: the exception type a wrapper raises instead for status 1
+    (an invalid argument) when the C entry's validation is its only one; the message is then the library's text alone."""
     rc = getattr(lib(), name)(*args)
+    if rc == 1 and invalid is not None:
+        raise invalid(lib().fp_last_error().decode())
     if rc != 0:
         raise FoundPoseNativeError(f"{name} failed (code {rc}): {lib().fp_last_error().decode()}")
 

@@ -106,6 +106,22 @@ int fp_tfidf_build(const int32_t* word_ids, const float* word_d2, int knn_k, con
                             soft_sigma_squared, sqrt_dists, desc, desc_n, eps, ST(stream));
 }
 
+// What both cosine entries pass to the kernels, and the one place that carves FP_COSINE_SCRATCH_FLOATS(num_det, max_templates) floats: the scores
+// [num_det, max_templates], the candidate keys (8 bytes each, hence the pad to an even float offset), and in the macro's last num_det floats one
+// replay flag per detection.
+static CosineArgs cosine_args(const float* desc_n, const int32_t* det_seg_off, const float* bank_n, const int32_t* obj_tpl_off, int num_det,
+                              int max_templates, int num_words, float* scratch) {
+  CosineArgs c;
+  memset(&c, 0, sizeof(c));
+  c.desc_n = desc_n; c.bank_n = bank_n; c.det_seg_off = det_seg_off; c.obj_tpl_off = obj_tpl_off; c.W = num_words;
+  c.sims = scratch; c.ld_sims = max_templates;
+  const size_t scores = (size_t)num_det * max_templates;
+  c.cand = reinterpret_cast<unsigned long long*>(scratch + scores + (scores & 1));
+  c.need_replay = reinterpret_cast<int*>(scratch + FP_COSINE_SCRATCH_FLOATS(num_det, max_templates) - (size_t)num_det);
+  return c;
+}
+static_assert(FP_COSINE_SCRATCH_FLOATS(3, 5) - 3 == 2 * 3 * 5 + 16 * 3 + 2, "the replay flags start 2 * scores + 16 * num_det + 2 floats into the cosine scratch");
+
 int fp_cosine_topk(const float* desc_n, const int32_t* det_seg_off, const int32_t* det_num_templates, int num_det,
                    int max_det_per_obj, const float* bank_n, const int32_t* obj_tpl_off, int num_obj,
                    int max_templates, int num_words, int n_top, float* scratch_sims, float* out_scores,
@@ -118,12 +134,7 @@ int fp_cosine_topk(const float* desc_n, const int32_t* det_seg_off, const int32_
   if (num_words % 16 == 0) {
     // one arithmetic (8 k-slice chains when num_words % 128 == 0) whatever the batch: a score never depends on how many
     // detections share the launch; > 32 detections of an object are served in 32-detection chunks by the same kernel
-    CosineArgs c;
-    memset(&c, 0, sizeof(c));
-    c.desc_n = desc_n; c.bank_n = bank_n; c.det_seg_off = det_seg_off; c.obj_tpl_off = obj_tpl_off; c.W = num_words;
-    c.sims = scratch_sims; c.ld_sims = max_templates;
-    c.cand = reinterpret_cast<unsigned long long*>(scratch_sims + (size_t)num_det * max_templates + ((size_t)num_det * max_templates & 1));
-    c.need_replay = reinterpret_cast<int*>(scratch_sims + 2 * (size_t)num_det * max_templates + 16 * (size_t)num_det + 2);  // behind the keys
+    const CosineArgs c = cosine_args(desc_n, det_seg_off, bank_n, obj_tpl_off, num_det, max_templates, num_words, scratch_sims);
     return launch_cosine_topk(c, num_det, num_obj, max_det_per_obj, max_templates, n_top, det_num_templates, out_scores,
                               out_ids, tie_mode, ST(stream));
   }
@@ -149,13 +160,9 @@ int fp_cosine_topk_prefiltered(const float* desc_n, const int32_t* det_seg_off, 
   if (num_words % 16 != 0)  // the generic exact path
     return fp_cosine_topk(desc_n, det_seg_off, det_num_templates, num_det, max_det_per_obj, bank_n, obj_tpl_off, num_obj, max_templates, num_words, n_top,
                           scratch, out_scores, out_ids, tie_mode, stream);
-  CosineArgs c;
-  memset(&c, 0, sizeof(c));
+  CosineArgs c = cosine_args(desc_n, det_seg_off, bank_n, obj_tpl_off, num_det, max_templates, num_words, scratch);
   c.force_prefilter = force;
-  c.desc_n = desc_n; c.bank_n = bank_n; c.bank_bf16 = bank_n_bf16; c.det_seg_off = det_seg_off; c.obj_tpl_off = obj_tpl_off; c.W = num_words;
-  c.sims = scratch; c.ld_sims = max_templates;
-  c.cand = reinterpret_cast<unsigned long long*>(scratch + (size_t)num_det * max_templates + ((size_t)num_det * max_templates & 1));
-  c.need_replay = reinterpret_cast<int*>(scratch + 2 * (size_t)num_det * max_templates + 16 * (size_t)num_det + 2);
+  c.bank_bf16 = bank_n_bf16;
   float* extra = scratch + FP_COSINE_SCRATCH_FLOATS(num_det, max_templates) + (FP_COSINE_SCRATCH_FLOATS(num_det, max_templates) & 1);
   return launch_cosine_topk_prefiltered(c, num_det, num_obj, max_det_per_obj, max_templates, n_top, det_num_templates, out_scores, out_ids, tie_mode, extra,
                                         ST(stream));

@@ -523,12 +523,8 @@ def gt_visibility(depth_test: torch.Tensor, depth_obj: torch.Tensor, inst, param
     mask_visib = torch.empty_like(mask)
     nbytes = _lib.gt_vis_scratch_bytes(n)
     scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dt.device)
-    rc = _lib.lib().fp_gt_visibility(ptr(dt), dt.shape[0], h, w, ptr(do), hr, wr, r.ctypes.data_as(_lib.vp), q.ctypes.data_as(_lib.vp), n,
-                                     ptr(scratch), nbytes, ptr(out), ptr(mask), ptr(mask_visib), stream())
-    if rc == 1:   # FP_ERR_INVALID: the one validation is the C entry's
-        raise ValueError(_lib.lib().fp_last_error().decode())
-    if rc != 0:
-        raise _lib.FoundPoseNativeError(f"fp_gt_visibility failed (code {rc}): {_lib.lib().fp_last_error().decode()}")
+    call("fp_gt_visibility", ptr(dt), dt.shape[0], h, w, ptr(do), hr, wr, r.ctypes.data_as(_lib.vp), q.ctypes.data_as(_lib.vp), n,
+         ptr(scratch), nbytes, ptr(out), ptr(mask), ptr(mask_visib), stream(), invalid=ValueError)
     return out, mask, mask_visib
 
 
@@ -865,13 +861,6 @@ def tsdf_track(volume: dict, points: torch.Tensor, row_begin: torch.Tensor, row_
     return out
 
 
-def _depth_checked(name: str, rc: int) -> None:
-    if rc == 1:   # FP_ERR_INVALID: the one validation is the C entry's
-        raise ValueError(_lib.lib().fp_last_error().decode())
-    if rc != 0:
-        raise _lib.FoundPoseNativeError(f"{name} failed (code {rc}): {_lib.lib().fp_last_error().decode()}")
-
-
 def _depth_stack(name: str, t: torch.Tensor, dtype) -> torch.Tensor:
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise ValueError(f"{name} must be a tensor on the device (there is no CPU path)")
@@ -908,10 +897,9 @@ def depth_plane_fit(depth: torch.Tensor, cameras, frame_keys, prior_planes: torc
     counts = torch.empty(max(n, 1), max(int(hypotheses), 1), dtype=torch.int32, device=d.device)[:n] if want_counts else None
     nbytes = _lib.depth_plane_scratch_bytes(n, h * w, max(int(hypotheses), 0))
     scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=d.device)
-    rc = _lib.lib().fp_depth_plane_fit(ptr(d), n, h, w, cam.ctypes.data_as(_lib.vp), keys.ctypes.data_as(_lib.vp), ptr(pp), ptr(npr), int(hypotheses),
-                                       int(stride), float(plane_thresh_mm), float(max_depth_mm), float(min_plane_share), int(seed) & (2**64 - 1),
-                                       ptr(scratch), nbytes, ptr(plane), ptr(info), ptr(counts), stream())
-    _depth_checked("fp_depth_plane_fit", rc)
+    call("fp_depth_plane_fit", ptr(d), n, h, w, cam.ctypes.data_as(_lib.vp), keys.ctypes.data_as(_lib.vp), ptr(pp), ptr(npr), int(hypotheses),
+         int(stride), float(plane_thresh_mm), float(max_depth_mm), float(min_plane_share), int(seed) & (2**64 - 1),
+         ptr(scratch), nbytes, ptr(plane), ptr(info), ptr(counts), stream(), invalid=ValueError)
     return plane, info, counts
 
 
@@ -930,10 +918,9 @@ def depth_components(depth: torch.Tensor, cameras, slope_fx, planes: torch.Tenso
     labels = torch.empty(max(n, 1), h, w, dtype=torch.int32, device=d.device)[:n]
     nbytes = _lib.depth_components_scratch_bytes(n, h * w)
     scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=d.device)
-    rc = _lib.lib().fp_depth_components(ptr(d), n, h, w, cam.ctypes.data_as(_lib.vp), sl.ctypes.data_as(_lib.vp), ptr(pl), ptr(npl),
-                                        float(max_depth_mm), float(object_margin_mm), float(np.float32(connect_mm)), ptr(scratch), nbytes,
-                                        ptr(labels), stream())
-    _depth_checked("fp_depth_components", rc)
+    call("fp_depth_components", ptr(d), n, h, w, cam.ctypes.data_as(_lib.vp), sl.ctypes.data_as(_lib.vp), ptr(pl), ptr(npl),
+         float(max_depth_mm), float(object_margin_mm), float(np.float32(connect_mm)), ptr(scratch), nbytes,
+         ptr(labels), stream(), invalid=ValueError)
     return labels
 
 
@@ -955,9 +942,8 @@ def component_table(labels: torch.Tensor, min_pixels: int, max_area: int, max_pr
     rank_map = torch.empty(max(n, 1), h, w, dtype=torch.int32, device=lab.device)[:n]
     nbytes = _lib.component_table_scratch_bytes(n, h * w)
     scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=lab.device)
-    rc = _lib.lib().fp_component_table(ptr(lab), n, h, w, int(min_pixels), int(max_area), int(max_proposals), int(level), ptr(finer), nf,
-                                       ptr(scratch), nbytes, ptr(table), ptr(counts), ptr(rank_map), stream())
-    _depth_checked("fp_component_table", rc)
+    call("fp_component_table", ptr(lab), n, h, w, int(min_pixels), int(max_area), int(max_proposals), int(level), ptr(finer), nf,
+         ptr(scratch), nbytes, ptr(table), ptr(counts), ptr(rank_map), stream(), invalid=ValueError)
     return table, counts, rank_map
 
 
@@ -972,15 +958,13 @@ def component_runs(rank_maps: torch.Tensor, num_kept: torch.Tensor, max_proposal
         raise ValueError(f"component_runs: num_kept must be int32 [{m}] on the device")
     kept = num_kept.contiguous()
     count = torch.empty(1, dtype=torch.int32, device=maps.device)
-    rc = _lib.lib().fp_component_runs(ptr(maps), m, h, w, ptr(kept), int(max_proposals), 0, None, ptr(count), stream())
-    _depth_checked("fp_component_runs", rc)
+    call("fp_component_runs", ptr(maps), m, h, w, ptr(kept), int(max_proposals), 0, None, ptr(count), stream(), invalid=ValueError)
     total = int(count.item())
     groups = m * int(max_proposals)
     if total == 0:
         return torch.zeros(0, dtype=torch.int32, device=maps.device), torch.zeros(groups + 1, dtype=torch.int32, device=maps.device)
     events = torch.empty(total, dtype=torch.int64, device=maps.device)
-    rc = _lib.lib().fp_component_runs(ptr(maps), m, h, w, ptr(kept), int(max_proposals), total, ptr(events), ptr(count), stream())
-    _depth_checked("fp_component_runs", rc)
+    call("fp_component_runs", ptr(maps), m, h, w, ptr(kept), int(max_proposals), total, ptr(events), ptr(count), stream(), invalid=ValueError)
     events = torch.sort(events).values
     group, pos = events >> 32, events & 0xffffffff
     prev = torch.zeros_like(pos)
