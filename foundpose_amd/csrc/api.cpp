@@ -61,12 +61,12 @@ const char* fp_last_error(void) { return g_err; }
 
 // ------------------------------------------------------------------ matching half
 int fp_sqnorm_rows(const float* x, int64_t n, int d, float* out, fp_stream_t stream) {
-  FP_REQUIRE(x && out, "fp_sqnorm_rows: null pointer");
+  FP_REQUIRE(n == 0 || (x && out), "fp_sqnorm_rows: null pointer");   // (an empty tensor has no storage: null is what it hands over)
   return launch_sqnorm_rows(x, n, d, d, out, ST(stream));
 }
 
 int fp_normalize_rows(const float* x, int64_t n, int d, float eps, float* out, fp_stream_t stream) {
-  FP_REQUIRE(x && out, "fp_normalize_rows: null pointer");
+  FP_REQUIRE(n == 0 || (x && out), "fp_normalize_rows: null pointer");
   return launch_normalize_rows(x, n, d, eps, out, ST(stream));
 }
 
@@ -216,7 +216,7 @@ int fp_pack_records(const int32_t* template_ids, const float* template_scores, c
 int fp_sample_bilinear(const float* fmap, int64_t stride_img, int64_t stride_c, int64_t stride_h, int64_t stride_w,
                        int C, int H, int W, int img_w, int img_h, const float* points, const int32_t* point_img,
                        int num_points, float* out, fp_stream_t stream) {
-  FP_REQUIRE(fmap && points && out, "fp_sample_bilinear: null pointer");
+  FP_REQUIRE(num_points == 0 || (fmap && points && out), "fp_sample_bilinear: null pointer");
   SampleArgs a;
   a.fmap = fmap; a.stride_img = stride_img; a.stride_c = stride_c; a.stride_h = stride_h; a.stride_w = stride_w;
   a.C = C; a.H = H; a.W = W; a.img_w = img_w; a.img_h = img_h;
@@ -226,7 +226,7 @@ int fp_sample_bilinear(const float* fmap, int64_t stride_img, int64_t stride_c, 
 
 int fp_pca_project(const float* x, int n, int D, const float* components, int d, const float* mean_proj, float* out,
                    fp_stream_t stream) {
-  FP_REQUIRE(x && components && out, "fp_pca_project: null pointer");
+  FP_REQUIRE(n == 0 || (x && components && out), "fp_pca_project: null pointer");
   if (n == 0) return FP_OK;
   F32TileArgs a = zero_tile_args();
   a.A = x; a.lda = D; a.B = components; a.ldb = D; a.K = D; a.M = n; a.N = d;

@@ -74,7 +74,8 @@ const char* fp_last_error(void);
  * Descriptor matching half
  * ---------------------------------------------------------------------------------------------- */
 
-/* out[i] = |x_i|^2 as a k-ascending fp32 fma chain.  Part of faiss IndexFlatL2 (utils/knn_util.py:48-50). */
+/* out[i] = |x_i|^2 as a k-ascending fp32 fma chain.  Part of faiss IndexFlatL2 (utils/knn_util.py:48-50).
+ * Here and in fp_normalize_rows, fp_sample_bilinear and fp_pca_project a count of 0 is a no-op, and the pointers may then be null. */
 int fp_sqnorm_rows(const float* x, int64_t n, int d, float* out, fp_stream_t stream);
 
 /* out = x / max(|x|, eps) per row: the per-operand normalisation of torch cosine_similarity
