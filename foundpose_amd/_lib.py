@@ -1,7 +1,7 @@
 """ctypes binding of libfoundpose_amd.so (the C ABI in include/foundpose_amd.h).
 
 The header is the one declaration of the ABI: the argument types of every entry point, the list of exported symbols and ABI_VERSION are
-parsed from it on import (_parse_header).  What stays written by hand here -- the three ViT structs, the FP_* constants and the scratch-size
+parsed from it on import (_parse_header); entry points declared in a header of their own beside it (EXTENSION_HEADERS) are parsed the same way.  What stays written by hand here -- the three ViT structs, the FP_* constants and the scratch-size
 formulas -- is compared with the header, compiled, by tests/test_cabi_symbols.py.
 
 There is NO fallback: if the library is missing or a call fails, this raises. The product
@@ -65,16 +65,17 @@ _BY_VALUE = {"int": i32, "int32_t": i32, "int64_t": i64, "float": f32, "double":
 _BY_POINTER = {"fp_vit_model": C.POINTER(VitModel), "fp_vit_workspace": C.POINTER(VitWorkspace)}  # every other pointer: c_void_p
 
 
-def _parse_header(path):
+def _parse_header(path, versioned=True):
     """The prototypes (name -> argtypes; all return int), every declared symbol and FP_ABI_VERSION, read from the header's declarations
-    `ret fp_name(args);`.  Nothing is guessed: whatever has no ctypes mapping below raises, naming the declaration."""
+    `ret fp_name(args);`.  Nothing is guessed: whatever has no ctypes mapping below raises, naming the declaration.
+    versioned=False: a header of further entry points beside the main one, which defines no version of its own (-> version None)."""
     try:
         text = open(path).read()
     except OSError as e:
         raise FoundPoseNativeError(f"cannot read the C ABI header {path}: {e}") from None
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     version = re.search(r"^#define\s+FP_ABI_VERSION\s+(\d+)\s*$", text, re.M)
-    if version is None:
+    if version is None and versioned:
         raise FoundPoseNativeError(f"{path}: no #define FP_ABI_VERSION <integer>")
     protos, names = {}, ["fp_last_error"]
     for ret, name, params in re.findall(r"^([A-Za-z_][\w \t*]*?)\s*\b(fp_\w+)\s*\(([^()]*)\)\s*;", text, re.M):
@@ -95,10 +96,13 @@ def _parse_header(path):
     partial = sorted(set(re.findall(r"\b(fp_\w+)\s*\(", text)) - set(names))
     if partial:
         raise FoundPoseNativeError(f"{path}: cannot parse the declaration of {', '.join(partial)}")
-    return protos, sorted(names), int(version.group(1))
+    return protos, sorted(names), int(version.group(1)) if version else None
 
 
 _PROTOS, _SYMBOLS, ABI_VERSION = _parse_header(os.path.join(_HERE, "..", "include", "foundpose_amd.h"))
+# entry points declared in headers of their own beside the main one (same library, same ABI version, same parser): header -> prototypes
+EXTENSION_HEADERS = ("foundpose_amd_multiview.h",)
+_EXT_PROTOS = {h: _parse_header(os.path.join(_HERE, "..", "include", h), versioned=False)[0] for h in EXTENSION_HEADERS}
 
 _lib = None
 
@@ -114,7 +118,7 @@ def lib() -> C.CDLL:
         handle = C.CDLL(LIB_PATH)
         handle.fp_last_error.restype = C.c_char_p
         handle.fp_last_error.argtypes = []
-        for name, args in _PROTOS.items():
+        for name, args in [*_PROTOS.items(), *(item for protos in _EXT_PROTOS.values() for item in protos.items())]:
             fn = getattr(handle, name)  # AttributeError here = header/library mismatch
             fn.argtypes = args
             fn.restype = i32
@@ -243,6 +247,11 @@ def depth_refine_scratch_bytes(num_det: int, max_points: int) -> int:
 
 def tsdf_track_scratch_bytes(num_det: int, max_points: int) -> int:
     """FP_TSDF_TRACK_SCRATCH_BYTES of include/foundpose_amd.h."""
+    return depth_refine_scratch_bytes(num_det, max_points)
+
+
+def multiview_scratch_bytes(num_det: int, max_points: int) -> int:
+    """fp_multiview_refine's scratch: FP_DEPTH_REFINE_SCRATCH_BYTES of include/foundpose_amd.h, the same layout."""
     return depth_refine_scratch_bytes(num_det, max_points)
 
 

@@ -1,6 +1,6 @@
 // C ABI of libfoundpose_amd.so (declared in include/foundpose_amd.h): argument checking, scratch carving
 // and kernel sequencing.  No device allocation, no global mutable state, no synchronisation except the table uploads of
-// fp_pose_errors, fp_vsd_counts, fp_gt_visibility, fp_depth_plane_fit, fp_depth_components and fp_tsdf_integrate (each waits for its own copy) and the range check read back by the four Levenberg-Marquardt solvers (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine, fp_tsdf_track and its colour sibling fp_tsdf_track_rgb).
+// fp_pose_errors, fp_vsd_counts, fp_gt_visibility, fp_depth_plane_fit, fp_depth_components and fp_tsdf_integrate (each waits for its own copy) and the range check read back by the five Levenberg-Marquardt solvers (fp_featuremetric_refine, fp_depth_refine, fp_rgbd_refine, fp_tsdf_track and its colour sibling fp_tsdf_track_rgb, fp_multiview_refine).
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/foundpose_amd.h"
+#include "../../include/foundpose_amd_multiview.h"
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -975,7 +976,7 @@ int fp_directed_hausdorff(const double* pts, int V, int query_stride, const doub
   return launch_pts_hausdorff(a, K, ST(stream));
 }
 
-// ------------------------------------------------------------------ the four Levenberg-Marquardt solvers: the three pose refinements, and fp_tsdf_track further down
+// ------------------------------------------------------------------ the five Levenberg-Marquardt solvers: the three pose refinements; fp_tsdf_track and fp_multiview_refine further down
 // the argument checks the solvers share; `f` / `d` / `depth_weight`: the feature map, the depth stack and the weight of the entries that have one
 static int refine_check(const char* fn, const RefineLmArgs& lm, const RefineMapArgs* f, const RefineDepthArgs* d, const double* depth_weight) {
   if (f) {
@@ -1014,14 +1015,15 @@ static int refine_carve(const char* fn, RefineLmArgs& lm, void* scratch, size_t 
 // the one wait of a solver's call, after every iteration is enqueued: a bad row range or image index is reported here, never read.
 // `rows_fmt`: the caller's words for a bad row range
 static int refine_report(const char* fn, const RefineLmArgs& lm, int num_images, hipStream_t st,
-                         const char* rows_fmt = "%s: detection %d: bank rows outside [0, %lld) or more than max_points %d") {
+                         const char* rows_fmt = "%s: detection %d: bank rows outside [0, %lld) or more than max_points %d",
+                         const char* index_fmt = "%s: detection %d: image index outside [0, %d)") {
   int32_t bad = 0;
   if (hipError_t e = hipMemcpyWithStream(&bad, lm.err, sizeof(int32_t), hipMemcpyDeviceToHost, st); e != hipSuccess) {
     fp_set_error("%s: status read: %s", fn, hipGetErrorString(e));
     return FP_ERR_HIP;
   }
   FP_REQUIRE(bad <= 0, rows_fmt, fn, bad - 1, lm.num_rows, lm.max_points);
-  FP_REQUIRE(bad == 0, "%s: detection %d: image index outside [0, %d)", fn, -bad - 1, num_images);
+  FP_REQUIRE(bad == 0, index_fmt, fn, -bad - 1, num_images);
   return FP_OK;
 }
 
@@ -1420,6 +1422,29 @@ int fp_tsdf_track_rgb(const float* sdf_sum, const int32_t* sdf_cnt, const float*
   TRY(refine_carve(fn, a.g.lm, scratch, scratch_bytes, FP_TSDF_TRACK_SCRATCH_BYTES(num_det, max_points), FP_REFINE_RECORD, nullptr, ST(stream)));
   TRY(launch_tsdf_track_rgb(a, ST(stream)));
   return refine_report(fn, a.g.lm, 0, ST(stream), "%s: problem %d: rows outside [0, %lld) or more than max_points %d");
+}
+
+int fp_multiview_refine(const float* points, const double* targets, const int32_t* view_index, int64_t num_rows, const double* view_cam,
+                        const double* view_T, int num_views, const int32_t* row_begin, const int32_t* row_end, const double* R_in,
+                        const double* t_in, const int32_t* has_pose, double huber_px, int num_det, int max_points, int iters, void* scratch,
+                        size_t scratch_bytes, double* R_out, double* t_out, double* cost_in, double* cost_out, int32_t* num_points,
+                        int32_t* iters_used, int32_t* status, double* normal_eq, fp_stream_t stream) {
+  const char* fn = "fp_multiview_refine";
+  FP_REQUIRE(points && targets && view_index && view_cam && view_T && row_begin && row_end && R_in && t_in && has_pose && scratch && R_out &&
+             t_out && cost_in && cost_out && num_points && iters_used && status, "fp_multiview_refine: null pointer");
+  FP_REQUIRE(num_views >= 1, "fp_multiview_refine: num_views %d must be >= 1", num_views);
+  FP_REQUIRE(std::isfinite(huber_px) && huber_px > 0, "fp_multiview_refine: huber_px must be finite and > 0");
+  MultiviewArgs a;
+  memset(&a, 0, sizeof(a));
+  a.lm = refine_lm_args(nullptr, R_in, t_in, row_begin, row_end, points, num_rows, has_pose, num_det, max_points, iters, R_out, t_out, cost_in,
+                        cost_out, num_points, iters_used, status, normal_eq);
+  TRY(refine_check(fn, a.lm, nullptr, nullptr, nullptr));
+  a.target = targets, a.view = view_index, a.view_cam = view_cam, a.view_T = view_T, a.num_views = num_views, a.delta = huber_px;
+  a.state = static_cast<RefineState*>(scratch);
+  TRY(refine_carve(fn, a.lm, scratch, scratch_bytes, FP_DEPTH_REFINE_SCRATCH_BYTES(num_det, max_points), FP_REFINE_RECORD, nullptr, ST(stream)));
+  TRY(launch_multiview_refine(a, ST(stream)));
+  return refine_report(fn, a.lm, num_views, ST(stream), "%s: problem %d: rows outside [0, %lld) or more than max_points %d",
+                       "%s: problem %d: a row's view index outside [0, %d)");
 }
 
 // ------------------------------------------------------------------ mask proposals from depth

@@ -472,8 +472,21 @@ struct TsdfTrackRgbArgs {  // fp_tsdf_track_rgb: the geometric arguments as they
 int launch_tsdf_track(const TsdfTrackArgs& a, hipStream_t st);
 int launch_tsdf_track_rgb(const TsdfTrackRgbArgs& a, hipStream_t st);
 
+// ---------------------------------------------------------------- multiview.hip (the LM parts: refine_terms.hpp)
+struct MultiviewArgs {     // fp_multiview_refine (section 37): lm.verts are the rows' model points, lm.cam is not used; the pose is model -> world
+  RefineLmArgs lm;
+  const double* target;    // [num_rows, 2] the pixel (u*, v*) a row's point should project to in its view
+  const int32_t* view;     // [num_rows] the row's view: an index into the two tables below
+  const double* view_cam;  // [num_views, 4] fx, fy, cx, cy
+  const double* view_T;    // [num_views, 12] R_v row-major | t_v, world -> camera
+  int num_views, pad;
+  double delta;            // huber_px
+  RefineState* state;
+};
+int launch_multiview_refine(const MultiviewArgs& a, hipStream_t st);
+
 // ---------------------------------------------------------------- depth_proposals.hip
-struct DpFrame {                         // one frame, built on the host by fp_depth_plane_fit / fp_depth_components
+struct DpFrame {                        // one frame, built on the host by fp_depth_plane_fit / fp_depth_components
   double fx, fy, cx, cy;
   unsigned long long key;                // the sampler's frame key (plane fit only)
   float slope_fx;                        // connect_slope / fx (components only)

@@ -166,7 +166,7 @@ FP_DEVICE void lm_sigma(RefineState& s, const double* tot) {
   // pending stays 1: the next pass evaluates the input pose
 }
 
-// ---- one point per lane (depth_refine.hip, tsdf_track.hip): the pass, one wave per (chunk, problem) = (blockIdx.x, b), and its solve,
+// ---- one point per lane (depth_refine.hip, tsdf_track.hip, and multiview.hip with one (view, point) row per lane): the pass, one wave per (chunk, problem) = (blockIdx.x, b), and its solve,
 // one wave per problem.  The record is FP_REFINE_RECORD doubles: H (21, upper triangle row-major), g (6), sum rho [27], pad, inliers [29],
 // pad.  The cost is normalised by the point count, a problem with fewer than 6 inliers at the input pose stops (there is no z-bad count:
 // a point that cannot be measured is an outlier like any other).

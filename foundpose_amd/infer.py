@@ -28,7 +28,7 @@ from typing import Any, Dict, Iterable, List, NamedTuple, Optional, Sequence, Tu
 import numpy as np
 import torch
 
-from . import crop_util, engine as fe, eval_bop19, eval_util, feature_util, infer_pose_util, pnp_util, pose_nms, refine_util, repre_util, vis_util
+from . import crop_util, engine as fe, eval_bop19, eval_util, feature_util, infer_pose_util, multiview, pnp_util, pose_nms, refine_util, repre_util, vis_util
 from .bank import DeviceBank
 
 
@@ -82,6 +82,12 @@ class InferOpts(NamedTuple):
     task: str = "localization"             # "localization": the targets say how many instances each (image, object) has and num_preds_factor x that many detections get a pose; "detection": the targets name images only and every detection of every object gets one (BOP24 6D detection)
     detection_min_score: float = 0.0       # task="detection": detections scored below this get no pose
     detection_max_per_object: int = 16     # ... and at most this many of one (image, object), best first; >= 1
+    scene_select_type: str = "none"        # what is done with the poses of a static SCENE together, after frame_select_type: "none" or "multiview" (the estimates of one object from several calibrated views fused into one world pose)
+    scene_fuse_match_thresh: float = 1.0   # scene_select_type="multiview": an estimate joins a cluster whose seed lies within this x the object's diameter, > 0
+    scene_fuse_huber_px: float = 10.0      # ... the Huber delta of the reprojection error in pixels, > 0
+    scene_fuse_points: int = 64            # ... the number of model points per member view, in [1, 4096]
+    scene_fuse_min_views: int = 2          # ... the smallest cluster that is refined, >= 2
+    scene_fuse_iters: int = 20             # ... Levenberg-Marquardt iterations, in [0, 1000]
 
 
 FINAL_POSE_TYPES = ("best_coarse", "featuremetric", "depth", "featuremetric_depth")
@@ -92,7 +98,13 @@ COARSE_SELECT_TYPES = ("inliers", "depth_verify", "mask_verify")
 DEPTH_SELECT_TYPES = ("depth_verify",)   # the coarse hypotheses are checked against the frame's "depth" (pnp_util.verify_poses_depth)
 MASK_SELECT_TYPES = ("mask_verify",)     # ... against the detection's own mask (pnp_util.verify_poses_mask): no depth
 FRAME_SELECT_TYPES = ("none", "pose_nms")
+SCENE_SELECT_TYPES = ("none", "multiview")
 TASKS = ("localization", "detection")
+
+
+def _scene_fuse_opts(opts: "InferOpts") -> multiview.FuseOpts:
+    return multiview.FuseOpts(opts.scene_fuse_match_thresh, opts.scene_fuse_huber_px, opts.scene_fuse_points, opts.scene_fuse_min_views,
+                              opts.scene_fuse_iters)
 
 
 def load_opts(path_or_dict) -> InferOpts:
@@ -146,6 +158,12 @@ def _check_driver_opts(opts: InferOpts):
         raise ValueError(f"pose_nms_max_points must be an integer >= 1, got {opts.pose_nms_max_points!r}")
     if not isinstance(opts.pose_nms_cross_object, bool):
         raise ValueError(f"pose_nms_cross_object must be true or false, got {opts.pose_nms_cross_object!r}")
+    if opts.scene_select_type not in SCENE_SELECT_TYPES:
+        raise ValueError(f"Unknown scene select type '{opts.scene_select_type}' (one of {', '.join(SCENE_SELECT_TYPES)})")
+    try:
+        multiview.check_opts(_scene_fuse_opts(opts))
+    except ValueError as e:
+        raise ValueError(f"scene_fuse_{e}") from None
     if opts.task not in TASKS:
         raise ValueError(f"Unknown task '{opts.task}' (one of {', '.join(TASKS)})")
     if isinstance(opts.detection_min_score, bool) or not isinstance(opts.detection_min_score, (int, float)) or not math.isfinite(opts.detection_min_score):
@@ -704,29 +722,59 @@ def _select_frame_poses(opts: InferOpts, repres: Dict[int, repre_util.FeatureBas
     return [path]
 
 
+def _fuse_scene_poses(opts: InferOpts, scene_cameras, scene_models, csv_path: str) -> List[str]:
+    """scene_select_type "multiview" (DESIGN.md section 37), after the csv is written and after frame_select_type has had its turn with it
+    (a frame's duplicates are gone before views are matched): the rows of every scene whose images all carry cam_R_w2c / cam_t_w2c fused
+    (multiview.fuse_results), the csv written again -- same rows, same order; the stage's wall time, divided equally over the images that
+    have rows, added to their `time` --, and every row's and cluster's record written to scene-fuse.json beside it.  A run without camera
+    poses leaves the csv's bytes as they are and the file says why.  -> the paths written besides the csv."""
+    _check_driver_opts(opts)
+    rows = eval_bop19.load_results_csv(csv_path)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    present = {r["obj_id"] for r in rows}
+    if scene_models is None or any(lid not in scene_models for lid in present):
+        raise ValueError("scene_select_type 'multiview' needs the objects' models (diameter and symmetries: models_info.json and the meshes of "
+                         f"--models-dir); missing for {sorted(present - set(scene_models or {}))}")
+    fused, report = multiview.fuse_results(rows, scene_cameras or {}, scene_models, _scene_fuse_opts(opts))
+    torch.cuda.synchronize()
+    if any(r["fused"] for r in report["rows"]):   # nothing fused: the csv keeps its bytes, its times included
+        images = {(r["scene_id"], r["im_id"]) for r in rows}
+        share = (time.perf_counter() - t0) / max(len(images), 1)
+        pose_nms.write_results_csv(csv_path, [dict(r, time=r["time"] + share) for r in fused])
+    path = os.path.join(os.path.dirname(csv_path), "scene-fuse.json")
+    multiview.write_report(path, report)
+    return [path]
+
+
 def _write_results(opts: InferOpts, lids: Sequence[int], evaluators: Sequence[eval_util.PoseEvaluator],
-                   repres: Dict[int, repre_util.FeatureBasedObjectRepre], output_dir: str) -> List[str]:
+                   repres: Dict[int, repre_util.FeatureBasedObjectRepre], output_dir: str, scene_cameras=None, scene_models=None) -> List[str]:
     """The files of a run, once every pose is estimated (save_estimates): <output_dir>/<lid>/estimated-poses.json per object (infer.py:813-816),
-    the BOP csv, and what frame_select_type "pose_nms" does with it.  -> their paths, in this order."""
+    the BOP csv, what frame_select_type "pose_nms" does with it and then what scene_select_type "multiview" does.  -> their paths, in this order."""
     paths = []
     if opts.save_estimates:
         for lid, ev in zip(lids, evaluators):
             paths.append(os.path.join(output_dir, str(lid), "estimated-poses.json"))
             ev.save_results_json(paths[-1])
-        paths.append(eval_util.prepare_bop_submission(output_dir, opts.object_dataset, lids))
+        csv_path = eval_util.prepare_bop_submission(output_dir, opts.object_dataset, lids)
+        paths.append(csv_path)
         if opts.frame_select_type == "pose_nms":
-            paths.extend(_select_frame_poses(opts, repres, lids, paths[-1]))
+            paths.extend(_select_frame_poses(opts, repres, lids, csv_path))
+        if opts.scene_select_type == "multiview":
+            paths.extend(_fuse_scene_poses(opts, scene_cameras, scene_models, csv_path))
     return paths
 
 
 def infer(opts: InferOpts, frames_by_object, detections, repres: Dict[int, repre_util.FeatureBasedObjectRepre], output_dir: str, extractor=None,
           precision: str = "bf16", num_target_insts: Optional[Dict[int, Dict[Tuple[int, int], int]]] = None, weights: Optional[str] = None,
-          eval_models: Optional[Dict[int, eval_util.EvalModel]] = None, renderer=None) -> List[str]:
+          eval_models: Optional[Dict[int, eval_util.EvalModel]] = None, renderer=None, scene_cameras=None, scene_models=None) -> List[str]:
     """All objects: `frames_by_object(lid)` yields the frames that show object `lid`; one estimated-poses.json per object
     under <output_dir>/<lid>/ (infer.py:813-816), then the BOP19 csv.
     num_target_insts: {object lid: {(scene_id, im_id): inst_count}} from test_targets_bop19.json -- the number of poses to
     estimate per (image, object) is num_preds_factor x inst_count (infer.py:308-346); frames without an entry are skipped.
     eval_models: {object lid: eval_util.EvalModel} -- evaluate the hypotheses of frames whose annotations carry a pose.
+    scene_cameras / scene_models: with opts.scene_select_type "multiview" (DESIGN.md section 37), {scene_id: the scene's scene_camera.json}
+    and {object lid: eval_util.EvalModel}; read by nothing else.
     renderer: a HipRasterizer holding the mesh of every object under its lid -- with opts.vis_results, one picture per estimated pose
     (<output_dir>/<lid>/<scene>_<im>_<lid>_<inst>_0.png) and, after all objects, one summary per frame (<output_dir>/vis/<scene>_<im>.png)
     with every final pose in the frame's own camera.  Without it no picture is made and nothing else changes.
@@ -748,7 +796,7 @@ def infer(opts: InferOpts, frames_by_object, detections, repres: Dict[int, repre
                                num_target_insts=None if num_target_insts is None else num_target_insts.get(lid, {}),
                                eval_model=None if eval_models is None else eval_models.get(lid), renderer=renderer, output_dir=output_dir,
                                frame_poses=frame_poses if renderer is not None else None) for lid in lids]
-    paths = _write_results(opts, lids, evaluators, repres, output_dir)
+    paths = _write_results(opts, lids, evaluators, repres, output_dir, scene_cameras, scene_models)
     if renderer is not None and frame_poses:   # the frames are read again rather than kept: one image in memory at a time
         done = set()
         for lid in lids:
@@ -771,7 +819,7 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
                   output_dir: str, *, batch_detections: int = 32, extractor=None, precision: str = "bf16",
                   num_target_insts: Optional[Dict[int, Dict[Tuple[int, int], int]]] = None, weights: Optional[str] = None,
                   eval_models: Optional[Dict[int, eval_util.EvalModel]] = None, seed: int = 0, renderer=None,
-                  device_masks: bool = False) -> List[str]:
+                  device_masks: bool = False, scene_cameras=None, scene_models=None) -> List[str]:
     """infer() for a whole split in ONE pass over its frames: the kept instances of every (frame, object) are queued and go through the
     crop producer, the engine and the PnP tail `batch_detections` at a time, across frames and objects (one DeviceBank of all objects).
     `frames` yields each image once (load_bop_frames_all); `gt_annos` may hold annotations of several objects.  The poses, scores and
@@ -780,7 +828,8 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
     (frame, object) group -- the per-object driver's whole batch -- instead of its place in the batch.  Pictures are not made here: infer() /
     infer_object() write them.
     device_masks: the detections' run lengths are decoded, opened and cropped on the device (select_instances_device)
-    instead of on the host; the masks are the same bits and so is everything written."""
+    instead of on the host; the masks are the same bits and so is everything written.
+    scene_cameras / scene_models: as in infer()."""
     if batch_detections < 1:
         raise ValueError(f"batch_detections must be >= 1, got {batch_detections}")
     if renderer is not None:
@@ -819,7 +868,7 @@ def infer_batched(opts: InferOpts, frames: Iterable[Dict[str, Any]], detections,
                        for b, e in enumerate(fl.rows) if e.obj == o and fl.found[b]]
             if records:
                 _record_poses(evaluators[o], opts, lid, repres[lid], pipe.vertices[o], models[o], fl.res, records, fl.times)
-    return _write_results(opts, lids, evaluators, repres, output_dir)
+    return _write_results(opts, lids, evaluators, repres, output_dir, scene_cameras, scene_models)
 
 
 # ---------------------------------------------------------------------------------------------------- BOP split on disk
@@ -985,15 +1034,20 @@ def main(argv: Optional[Sequence[str]] = None) -> None:
         with open(os.path.join(models_dir, "models_info.json")) as f:
             models_info = json.load(f)
         eval_models = {lid: eval_util.load_eval_model(models_dir, lid, opts.max_sym_disc_step, models_info) for lid in lids}
+    scene_cameras = scene_models = None
+    if opts.scene_select_type == "multiview":   # the models come from the directory --eval-gt resolves; a missing models_info.json raises
+        scene_cameras = multiview.load_scene_cameras(args.dataset_dir, {int(t["scene_id"]) for t in targets})
+        scene_models = eval_models if eval_models is not None else multiview.load_models(models_dir, lids, opts.max_sym_disc_step)
     if args.batch_detections >= 1:
         out = infer_batched(opts._replace(object_lids=list(lids)), load_bop_frames_all(args.dataset_dir, targets, with_gt=args.eval_gt, with_depth=with_depth), detections, repres,
                             args.output_dir, batch_detections=args.batch_detections, extractor=extractor.to("cuda"), precision=args.precision,
-                            num_target_insts=n_inst, eval_models=eval_models, device_masks=args.device_masks)
+                            num_target_insts=n_inst, eval_models=eval_models, device_masks=args.device_masks, scene_cameras=scene_cameras,
+                            scene_models=scene_models)
         print("\n".join(out))
         return
     out = infer(opts._replace(object_lids=list(lids)), lambda lid: load_bop_frames(args.dataset_dir, targets, lid, with_gt=args.eval_gt, with_depth=with_depth), detections,
                 repres, args.output_dir, extractor=extractor.to("cuda"), precision=args.precision, num_target_insts=n_inst, eval_models=eval_models,
-                renderer=renderer)
+                renderer=renderer, scene_cameras=scene_cameras, scene_models=scene_models)
     print("\n".join(out))
 
 

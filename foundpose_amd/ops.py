@@ -861,6 +861,77 @@ def tsdf_track(volume: dict, points: torch.Tensor, row_begin: torch.Tensor, row_
     return out
 
 
+def multiview_refine(points: torch.Tensor, targets: torch.Tensor, view_index: torch.Tensor, view_cam: torch.Tensor, view_T: torch.Tensor,
+                     row_begin: torch.Tensor, row_end: torch.Tensor, R: torch.Tensor, t: torch.Tensor, huber_px: float = 10.0, iters: int = 20,
+                     has_pose: Optional[torch.Tensor] = None, max_points: Optional[int] = None, want_normal_eq: bool = False) -> dict:
+    """Multi-view pose consensus of B independent problems (fp_multiview_refine; DESIGN.md section 37).  A problem's pose is model -> WORLD;
+    its rows [row_begin, row_end) are (view, model point) pairs: points fp32 [N, 3] the model point, targets fp64 [N, 2] the pixel it
+    should project to, view_index int32 [N] its row of view_cam fp64 [V, 4] (fx, fy, cx, cy) and view_T fp64 [V, 12] (R_v row-major | t_v,
+    world -> camera).  row_begin / row_end int32 [B]; R fp64 [B, 3, 3] / t fp64 [B, 3] the start poses; has_pose [B] bool or int32 (None:
+    all); huber_px the Huber delta in pixels; max_points the row cap of a problem the scratch is sized for (None: the longest range).
+    Everything is checked here, before any launch, with one read-back for the row ranges and the view indices: ValueError.
+    -> dict of device tensors: R [B, 3, 3] f64, t [B, 3] f64, cost_in, cost_out [B] f64, num_points (inliers at the start pose),
+    iters_used, status [B] i32 (0 refined, 1 no step accepted, 2 skipped), + normal_eq [B, 28] f64 with want_normal_eq."""
+    import math
+    fn = "multiview_refine"
+    spec = (("points", points, (torch.float32,), 2, 3), ("targets", targets, (torch.float64,), 2, 2), ("view_index", view_index, (torch.int32,), 1, None),
+            ("view_cam", view_cam, (torch.float64,), 2, 4), ("view_T", view_T, (torch.float64,), 2, 12), ("row_begin", row_begin, (torch.int32,), 1, None),
+            ("row_end", row_end, (torch.int32,), 1, None), ("R", R, (torch.float64,), 3, 3), ("t", t, (torch.float64,), 2, 3))
+    if has_pose is not None:
+        spec += (("has_pose", has_pose, (torch.int32, torch.bool), 1, None),)
+    dev = points.device if isinstance(points, torch.Tensor) else None
+    for name, x, dts, nd, last in spec:
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != dev:
+            raise ValueError(f"{fn}: {name} must be a tensor on the device of points (there is no CPU path)")
+        if x.dtype not in dts or x.dim() != nd or (last is not None and x.shape[-1] != last):
+            raise ValueError(f"{fn}: {name} must be {' or '.join(str(d) for d in dts)} with {nd} dimensions{'' if last is None else f', the last of {last}'}, "
+                             f"got {x.dtype} {tuple(x.shape)}")
+    N, V, B = int(points.shape[0]), int(view_cam.shape[0]), int(row_begin.shape[0])
+    if N < 1 or tuple(targets.shape) != (N, 2) or tuple(view_index.shape) != (N,):
+        raise ValueError(f"{fn}: targets {tuple(targets.shape)} and view_index {tuple(view_index.shape)} are not one row per row of points [{N}, 3]")
+    if V < 1 or tuple(view_T.shape) != (V, 12):
+        raise ValueError(f"{fn}: view_cam {tuple(view_cam.shape)} and view_T {tuple(view_T.shape)} are not [V, 4] and [V, 12] of the same V >= 1 views")
+    if B < 1 or B > 65535 or tuple(row_end.shape) != (B,) or tuple(R.shape) != (B, 3, 3) or tuple(t.shape) != (B, 3):
+        raise ValueError(f"{fn}: row_begin {tuple(row_begin.shape)}, row_end {tuple(row_end.shape)}, R {tuple(R.shape)} and t {tuple(t.shape)} are not "
+                         "one batch of 1 .. 65535 problems")
+    if has_pose is not None and tuple(has_pose.shape) != (B,):
+        raise ValueError(f"{fn}: has_pose {tuple(has_pose.shape)} is not [{B}]")
+    if isinstance(huber_px, bool) or not isinstance(huber_px, (int, float)) or not (math.isfinite(huber_px) and huber_px > 0):
+        raise ValueError(f"{fn}: huber_px must be finite and > 0, got {huber_px!r}")
+    if isinstance(iters, bool) or not hasattr(iters, "__index__") or not 0 <= int(iters) <= 1000:
+        raise ValueError(f"{fn}: iters must be an integer in [0, 1000], got {iters!r}")
+    if max_points is not None and (isinstance(max_points, bool) or not hasattr(max_points, "__index__") or int(max_points) < 1):
+        raise ValueError(f"{fn}: max_points must be an integer >= 1 or None, got {max_points!r}")
+    hp = torch.ones(B, dtype=torch.int32, device=dev) if has_pose is None else has_pose.to(torch.int32)
+    # the one read-back: the claimed ranges, then the view indices of the claimed rows
+    rb, re, live = row_begin.cpu().numpy().astype("int64"), row_end.cpu().numpy().astype("int64"), hp.cpu().numpy() != 0
+    for b in range(B):
+        if live[b] and not 0 <= rb[b] <= re[b] <= N:
+            raise ValueError(f"{fn}: problem {b}: rows [{rb[b]}, {re[b]}) outside [0, {N}]")
+    longest = int((re - rb)[live].max()) if live.any() else 0
+    if max_points is not None and longest > int(max_points):
+        raise ValueError(f"{fn}: problem {int(((re - rb) * live).argmax())} has {longest} rows, more than max_points {int(max_points)}")
+    cap = max(1, longest if max_points is None else int(max_points))
+    if N:
+        claimed = torch.zeros(N + 1, dtype=torch.int32, device=dev)
+        ones = (hp != 0).to(torch.int32)   # (a problem without a pose claims nothing, and its range is not looked at)
+        claimed.index_add_(0, torch.where(hp != 0, row_begin, 0).long(), ones)
+        claimed.index_add_(0, torch.where(hp != 0, row_end, 0).long(), -ones)
+        used = torch.cumsum(claimed[:N], 0) > 0
+        bad = used & ((view_index < 0) | (view_index >= V))
+        if bool(bad.any()):
+            row = int(torch.nonzero(bad)[0])
+            raise ValueError(f"{fn}: row {row}: view index {int(view_index[row])} outside [0, {V})")
+    out, outs = _lm_outputs(B, dev, 28 if want_normal_eq else 0)
+    nbytes = _lib.multiview_scratch_bytes(B, cap)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    points, targets, view_index, view_cam, view_T, row_begin, row_end, Rin, tin, hp = (
+        x.contiguous() for x in (points, targets, view_index, view_cam, view_T, row_begin, row_end, R.reshape(B, 9), t, hp))
+    call("fp_multiview_refine", ptr(points), ptr(targets), ptr(view_index), N, ptr(view_cam), ptr(view_T), V, ptr(row_begin), ptr(row_end), ptr(Rin),
+         ptr(tin), ptr(hp), float(huber_px), B, cap, int(iters), ptr(scratch), nbytes, *outs, stream())
+    return out
+
+
 def _depth_stack(name: str, t: torch.Tensor, dtype) -> torch.Tensor:
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise ValueError(f"{name} must be a tensor on the device (there is no CPU path)")
