@@ -103,6 +103,10 @@ _PROTOS, _SYMBOLS, ABI_VERSION = _parse_header(os.path.join(_HERE, "..", "includ
 # entry points declared in headers of their own beside the main one (same library, same ABI version, same parser): header -> prototypes
 EXTENSION_HEADERS = ("foundpose_amd_multiview.h",)
 _EXT_PROTOS = {h: _parse_header(os.path.join(_HERE, "..", "include", h), versioned=False)[0] for h in EXTENSION_HEADERS}
+# the headers of features added since, one per feature (same library, same ABI version, same parser): a new feature appends its header
+# here and nothing else changes -- lib() binds whatever the table holds, after the entry points above
+FEATURE_HEADERS = ("foundpose_amd_mask_refine.h",)
+_FEATURE_PROTOS = {h: _parse_header(os.path.join(_HERE, "..", "include", h), versioned=False)[0] for h in FEATURE_HEADERS}
 
 _lib = None
 
@@ -118,7 +122,7 @@ def lib() -> C.CDLL:
         handle = C.CDLL(LIB_PATH)
         handle.fp_last_error.restype = C.c_char_p
         handle.fp_last_error.argtypes = []
-        for name, args in [*_PROTOS.items(), *(item for protos in _EXT_PROTOS.values() for item in protos.items())]:
+        for name, args in [*_PROTOS.items(), *(item for table in (_EXT_PROTOS, _FEATURE_PROTOS) for protos in table.values() for item in protos.items())]:
             fn = getattr(handle, name)  # AttributeError here = header/library mismatch
             fn.argtypes = args
             fn.restype = i32
@@ -253,6 +257,14 @@ def tsdf_track_scratch_bytes(num_det: int, max_points: int) -> int:
 def multiview_scratch_bytes(num_det: int, max_points: int) -> int:
     """fp_multiview_refine's scratch: FP_DEPTH_REFINE_SCRATCH_BYTES of include/foundpose_amd.h, the same layout."""
     return depth_refine_scratch_bytes(num_det, max_points)
+
+
+def mask_refine_scratch_bytes(num_det: int, max_points: int, max_contour: int) -> int:
+    """FP_MASK_REFINE_SCRATCH_BYTES of include/foundpose_amd_mask_refine.h."""
+    chunks = (max_points + REFINE_CHUNK - 1) // REFINE_CHUNK
+    bchunks = (max_contour + REFINE_CHUNK - 1) // REFINE_CHUNK
+    return (REFINE_STATE_BYTES * num_det + 8 * REFINE_RECORD * num_det * (chunks + bchunks) + 8 + 16 * num_det * max_points
+            + ((num_det * max_points + 1) // 2) * 8)
 
 
 def rgbd_refine_scratch_bytes(num_det: int, max_points: int) -> int:

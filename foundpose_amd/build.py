@@ -13,8 +13,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "lib", "obj")
 SO = os.path.join(LIBDIR, "libfoundpose_amd.so")
-SOURCES = ["api.cpp", "f32_tile.hip", "match.hip", "retrieve.hip", "gemm_bf16.hip", "gemm_fp8.hip", "gemm_split.hip", "gemm_splitx.hip", "gemm_f16.hip", "attn.hip", "vit.hip", "crop.hip", "pnp.hip", "kabsch.hip", "verify.hip", "mask_verify.hip", "det_masks.hip", "pose_nms.hip", "detection_ap.hip", "coco_eval.hip", "proposals.hip", "render.hip", "pose_eval.hip", "pose_add.hip", "point_extremes.hip", "vsd.hip", "gt_info.hip", "tsdf.hip", "tsdf_fill.hip", "tsdf_track.hip", "multiview.hip", "simplify.hip", "depth_proposals.hip", "refine.hip", "depth_refine.hip", "rgbd_refine.hip", "vis.hip"]
-HEADERS = ["common.hpp", "f32_stage.hpp", "kernels.hpp", "select.hpp", "stl_order.hpp", "stl_wave.hpp", "rot.hpp", "ransac.hpp", "refine_terms.hpp", "verify_grid.hpp", "gemm_kernel.hpp", "rounded.hpp", "bop_dist.hpp", "group_parts.hpp", os.path.join("..", "..", "include", "foundpose_amd.h"), os.path.join("..", "..", "include", "foundpose_amd_multiview.h")]
+SOURCES = ["api.cpp", "f32_tile.hip", "match.hip", "retrieve.hip", "gemm_bf16.hip", "gemm_fp8.hip", "gemm_split.hip", "gemm_splitx.hip", "gemm_f16.hip", "attn.hip", "vit.hip", "crop.hip", "pnp.hip", "kabsch.hip", "verify.hip", "mask_verify.hip", "det_masks.hip", "pose_nms.hip", "detection_ap.hip", "coco_eval.hip", "proposals.hip", "render.hip", "pose_eval.hip", "pose_add.hip", "point_extremes.hip", "vsd.hip", "gt_info.hip", "tsdf.hip", "tsdf_fill.hip", "tsdf_track.hip", "multiview.hip", "mask_refine.hip", "simplify.hip", "depth_proposals.hip", "refine.hip", "depth_refine.hip", "rgbd_refine.hip", "vis.hip"]
+HEADERS = ["common.hpp", "f32_stage.hpp", "kernels.hpp", "select.hpp", "stl_order.hpp", "stl_wave.hpp", "rot.hpp", "ransac.hpp", "refine_terms.hpp", "verify_grid.hpp", "gemm_kernel.hpp", "rounded.hpp", "bop_dist.hpp", "group_parts.hpp", os.path.join("..", "..", "include", "foundpose_amd.h"), os.path.join("..", "..", "include", "foundpose_amd_multiview.h"),
+           os.path.join("..", "..", "include", "foundpose_amd_mask_refine.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Wno-unused-value",
          # MFMA results feed VALU epilogues/softmax directly: keep accumulators in the VGPR half of the unified
          # register file instead of AGPRs (saves ~100 v_accvgpr moves per attention tile)

@@ -10,6 +10,7 @@
 
 #include "../../include/foundpose_amd.h"
 #include "../../include/foundpose_amd_multiview.h"
+#include "../../include/foundpose_amd_mask_refine.h"
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -1445,6 +1446,53 @@ int fp_multiview_refine(const float* points, const double* targets, const int32_
   TRY(launch_multiview_refine(a, ST(stream)));
   return refine_report(fn, a.lm, num_views, ST(stream), "%s: problem %d: rows outside [0, %lld) or more than max_points %d",
                        "%s: problem %d: a row's view index outside [0, %d)");
+}
+
+// ------------------------------------------------------------------ silhouette refinement (include/foundpose_amd_mask_refine.h)
+int fp_mask_distance(const uint8_t* masks, int num_masks, int H, int W, int32_t* d2, fp_stream_t stream) {
+  FP_REQUIRE(masks && d2, "fp_mask_distance: null pointer");
+  FP_REQUIRE(num_masks >= 1 && num_masks <= 65535, "fp_mask_distance: num_masks %d outside [1, 65535]", num_masks);
+  FP_REQUIRE(H >= 1 && H <= FP_MASK_MAX_SIDE && W >= 1 && W <= FP_MASK_MAX_SIDE, "fp_mask_distance: masks of %d x %d, sides in [1, %d] needed", W, H,
+             FP_MASK_MAX_SIDE);
+  return launch_mask_distance(MaskDistanceArgs{masks, d2, num_masks, H, W}, ST(stream));
+}
+
+int fp_mask_refine(const int32_t* d2, int H, int W, const int32_t* contour, int64_t num_contour, const int32_t* contour_begin,
+                   const int32_t* contour_end, const double* cameras, const double* R_in, const double* t_in, const int32_t* row_begin,
+                   const int32_t* row_end, const float* vertices, int64_t num_rows, const int32_t* has_pose, double huber_px, int num_det,
+                   int max_points, int max_contour, int iters, void* scratch, size_t scratch_bytes, double* R_out, double* t_out,
+                   double* cost_in, double* cost_out, int32_t* num_points, int32_t* iters_used, int32_t* status, double* normal_eq,
+                   fp_stream_t stream) {
+  const char* fn = "fp_mask_refine";
+  FP_REQUIRE(d2 && contour && contour_begin && contour_end && cameras && R_in && t_in && row_begin && row_end && vertices && has_pose && scratch &&
+             R_out && t_out && cost_in && cost_out && num_points && iters_used && status, "fp_mask_refine: null pointer");
+  FP_REQUIRE(H >= 1 && H <= FP_MASK_MAX_SIDE && W >= 1 && W <= FP_MASK_MAX_SIDE, "fp_mask_refine: masks of %d x %d, sides in [1, %d] needed", W, H,
+             FP_MASK_MAX_SIDE);
+  FP_REQUIRE(num_contour >= 0 && num_contour <= 0x7fffffffll && max_contour >= 1, "fp_mask_refine: num_contour %lld, max_contour %d",
+             (long long)num_contour, max_contour);
+  FP_REQUIRE(std::isfinite(huber_px) && huber_px > 0, "fp_mask_refine: huber_px must be finite and > 0");
+  static_assert(sizeof(MaskRefineState) <= FP_REFINE_STATE_BYTES, "FP_REFINE_STATE_BYTES");
+  MaskRefineArgs a;
+  memset(&a, 0, sizeof(a));
+  a.lm = refine_lm_args(cameras, R_in, t_in, row_begin, row_end, vertices, num_rows, has_pose, num_det, max_points, iters, R_out, t_out, cost_in,
+                        cost_out, num_points, iters_used, status, normal_eq);
+  TRY(refine_check(fn, a.lm, nullptr, nullptr, nullptr));
+  a.d2 = d2, a.H = H, a.W = W, a.contour = contour, a.cbegin = contour_begin, a.cend = contour_end, a.num_contour = num_contour;
+  a.max_contour = max_contour, a.bchunks = (max_contour + FP_REFINE_CHUNK - 1) / FP_REFINE_CHUNK, a.delta = huber_px;
+  a.state = static_cast<MaskRefineState*>(scratch);
+  // states | forward records | err (refine_carve), then what this solver adds: backward records | u | v | in-front flags
+  TRY(refine_carve(fn, a.lm, scratch, scratch_bytes, FP_MASK_REFINE_SCRATCH_BYTES(num_det, max_points, max_contour), FP_REFINE_RECORD, nullptr, ST(stream)));
+  char* sp = reinterpret_cast<char*>(a.lm.err) + 8;
+  a.bpart = reinterpret_cast<double*>(sp);
+  sp += 8 * (size_t)FP_REFINE_RECORD * num_det * a.bchunks;
+  a.pu = reinterpret_cast<double*>(sp);
+  sp += 8 * (size_t)num_det * max_points;
+  a.pv = reinterpret_cast<double*>(sp);
+  sp += 8 * (size_t)num_det * max_points;
+  a.pf = reinterpret_cast<int32_t*>(sp);
+  TRY(launch_mask_refine(a, ST(stream)));
+  return refine_report(fn, a.lm, (int)num_contour, ST(stream), "%s: detection %d: bank rows outside [0, %lld) or more than max_points %d",
+                       "%s: detection %d: contour rows outside [0, %d] or more than max_contour");
 }
 
 // ------------------------------------------------------------------ mask proposals from depth

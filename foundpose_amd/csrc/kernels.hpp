@@ -485,6 +485,26 @@ struct MultiviewArgs {     // fp_multiview_refine (section 37): lm.verts are the
 };
 int launch_multiview_refine(const MultiviewArgs& a, hipStream_t st);
 
+// ---------------------------------------------------------------- mask_refine.hip (the LM parts: refine_terms.hpp)
+struct MaskDistanceArgs { const uint8_t* masks; int32_t* d2; int B, H, W; };   // fp_mask_distance (section 38)
+int launch_mask_distance(const MaskDistanceArgs& a, hipStream_t st);
+struct MaskRefineState {   // scratch, FP_REFINE_STATE_BYTES: the shared LM state and the detection's contour rows [k0, k0 + nk)
+  RefineState s;
+  int k0, nk;
+};
+struct MaskRefineArgs {    // fp_mask_refine (section 38): lm.cam is the frame camera, lm.part / lm.chunks the forward records
+  RefineLmArgs lm;
+  const int32_t* d2; int H, W;          // [num_det, H, W] squared distances to the detection's mask
+  const int32_t* contour;               // [num_contour, 2] (x, y)
+  const int32_t* cbegin; const int32_t* cend; long long num_contour;
+  int max_contour, bchunks;             // the cap of a detection's contour rows; ceil(max_contour / FP_REFINE_CHUNK)
+  double delta;                         // huber_px
+  double* bpart;                        // [num_det, bchunks, FP_REFINE_RECORD] the backward records
+  double* pu; double* pv; int32_t* pf;  // [num_det, max_points] a point's projection and whether it is in front, at the trial pose
+  MaskRefineState* state;
+};
+int launch_mask_refine(const MaskRefineArgs& a, hipStream_t st);
+
 // ---------------------------------------------------------------- depth_proposals.hip
 struct DpFrame {                        // one frame, built on the host by fp_depth_plane_fit / fp_depth_components
   double fx, fy, cx, cy;

@@ -88,10 +88,15 @@ class InferOpts(NamedTuple):
     scene_fuse_points: int = 64            # ... the number of model points per member view, in [1, 4096]
     scene_fuse_min_views: int = 2          # ... the smallest cluster that is refined, >= 2
     scene_fuse_iters: int = 20             # ... Levenberg-Marquardt iterations, in [0, 1000]
+    mask_refine_iters: int = 30            # final_pose_type="mask" / "featuremetric_mask": iterations against the detection's mask, in [0, 1000]
+    mask_refine_huber_px: float = 8.0      # ... the Huber delta of both residuals in pixels, > 0 (this default and the two below rest on no measurement)
+    mask_refine_max_points: int = 4096     # ... the number of model points placed at the pose, at most
+    mask_refine_max_contour: int = 1024    # ... the number of contour pixels of the mask that pull on the model, at most
 
 
 FINAL_POSE_TYPES = ("best_coarse", "featuremetric", "depth", "featuremetric_depth")
 JOINT_POSE_TYPES = ("featuremetric_depth_joint",)   # features and depth in one objective (refine_util.refine_best_coarse_rgbd); a final pose type too
+MASK_POSE_TYPES = ("mask", "featuremetric_mask")   # the final pose is refined against the detection's own mask (refine_util.refine_best_coarse_mask): no depth; final pose types too
 DEPTH_POSE_TYPES = ("depth", "featuremetric_depth") + JOINT_POSE_TYPES   # the final pose is refined against the frame's "depth"
 DEPTH_PNP_TYPES = ("kabsch_depth",)   # the coarse poses are solved on the frame's "depth" (pnp_util.solve_kabsch_ransac_batch)
 COARSE_SELECT_TYPES = ("inliers", "depth_verify", "mask_verify")
@@ -125,7 +130,7 @@ def _check_driver_opts(opts: InferOpts):
         raise ValueError(f"Unknown matching type '{opts.match_template_type}'.")
     if opts.match_feat_matching_type != "cyclic_buddies":
         raise ValueError(f"Unknown feature matching type ({opts.match_feat_matching_type}).")
-    if opts.final_pose_type not in FINAL_POSE_TYPES + JOINT_POSE_TYPES:
+    if opts.final_pose_type not in FINAL_POSE_TYPES + JOINT_POSE_TYPES + MASK_POSE_TYPES:
         raise ValueError(f"Unknown final pose type {opts.final_pose_type}")
     if opts.pnp_type not in pnp_util.PNP_TYPES:
         raise ValueError(f"Unknown PnP type '{opts.pnp_type}' (one of {', '.join(pnp_util.PNP_TYPES)})")
@@ -177,7 +182,7 @@ def _check_driver_opts(opts: InferOpts):
         if not opts.use_detections:
             raise ValueError("task 'detection' estimates a pose for every detection: use_detections must be true")
     # the best coarse pose refined on the projected feature map (refine_util): the engine keeps the map
-    refine = opts.final_pose_type in ("featuremetric", "featuremetric_depth") + JOINT_POSE_TYPES
+    refine = opts.final_pose_type in ("featuremetric", "featuremetric_depth", "featuremetric_mask") + JOINT_POSE_TYPES
     if refine and (not isinstance(opts.refine_iters, int) or opts.refine_iters < 0):
         raise ValueError(f"refine_iters must be an integer >= 0, got {opts.refine_iters!r}")
     if opts.final_pose_type in DEPTH_POSE_TYPES and (not isinstance(opts.depth_refine_iters, int) or opts.depth_refine_iters < 0):
@@ -187,6 +192,15 @@ def _check_driver_opts(opts: InferOpts):
     if isinstance(opts.depth_refine_weight, bool) or not isinstance(opts.depth_refine_weight, (int, float)) \
             or not 0 <= opts.depth_refine_weight < float("inf"):
         raise ValueError(f"depth_refine_weight must be a finite number >= 0, got {opts.depth_refine_weight!r}")
+    if isinstance(opts.mask_refine_iters, bool) or not isinstance(opts.mask_refine_iters, int) or not 0 <= opts.mask_refine_iters <= 1000:
+        raise ValueError(f"mask_refine_iters must be an integer in [0, 1000], got {opts.mask_refine_iters!r}")
+    if isinstance(opts.mask_refine_huber_px, bool) or not isinstance(opts.mask_refine_huber_px, (int, float)) \
+            or not (math.isfinite(opts.mask_refine_huber_px) and opts.mask_refine_huber_px > 0):
+        raise ValueError(f"mask_refine_huber_px must be a finite number > 0, got {opts.mask_refine_huber_px!r}")
+    if isinstance(opts.mask_refine_max_points, bool) or not isinstance(opts.mask_refine_max_points, int) or opts.mask_refine_max_points < 1:
+        raise ValueError(f"mask_refine_max_points must be an integer >= 1, got {opts.mask_refine_max_points!r}")
+    if isinstance(opts.mask_refine_max_contour, bool) or not isinstance(opts.mask_refine_max_contour, int) or opts.mask_refine_max_contour < 1:
+        raise ValueError(f"mask_refine_max_contour must be an integer >= 1, got {opts.mask_refine_max_contour!r}")
     # scripts/infer.py:482-485 subsamples the query points with torch.randperm when a mask yields more than max_num_queries of them
     # (default 1 000 000: never for a crop).  The batched path keeps every point; an option value that could trigger the subsampling
     # is refused instead of being ignored (crop=False: checked per frame against the image's own grid).
@@ -409,19 +423,22 @@ def _stage_times(eng, n: int, t0: float, t1: float, t2: float, t3: float, t4: fl
     return times
 
 
-def _refine_final(opts: InferOpts, res, best, bank: DeviceBank, det_obj, frame_cams, cams, crop_size, depth, image_index, taus):
+def _refine_final(opts: InferOpts, res, best, bank: DeviceBank, det_obj, frame_cams, cams, crop_size, depth, image_index, taus, masks=None):
     """The final pose of a batch for the refining pose types: featuremetric in the cameras PnP solved in, then / or against the frames' depth
-    in the frames' own cameras, or on both in one objective in the frames' cameras (refine_util).  Its time is times["pose_refine"].  -> (R [n, 3, 3], t [n, 3]) numpy, in the solve cameras."""
+    in the frames' own cameras, or on both in one objective in the frames' cameras, or (after the optional featuremetric stage) against the detections' `masks` in the frames' cameras (refine_util).  Its time is times["pose_refine"].  -> (R [n, 3, 3], t [n, 3]) numpy, in the solve cameras."""
     pose = best
     if opts.final_pose_type in JOINT_POSE_TYPES:
         pose = refine_util.refine_best_coarse_rgbd(res, best, bank, det_obj, frame_cams, cams, crop_size, depth, image_index, taus,
                                                    opts.depth_refine_weight, opts.refine_iters)
         return pose["R"].cpu().numpy(), pose["t"].cpu().numpy()
-    if opts.final_pose_type in ("featuremetric", "featuremetric_depth"):
+    if opts.final_pose_type in ("featuremetric", "featuremetric_depth", "featuremetric_mask"):
         ref = refine_util.refine_best_coarse(res, best, bank, det_obj, cams, crop_size, opts.refine_iters)
         pose = dict(best, R=ref["R"], t=ref["t"])
     if opts.final_pose_type in DEPTH_POSE_TYPES:
         pose = refine_util.refine_best_coarse_depth(res, pose, bank, det_obj, frame_cams, cams, depth, image_index, taus, opts.depth_refine_iters)
+    if opts.final_pose_type in MASK_POSE_TYPES:
+        pose = refine_util.refine_best_coarse_mask(pose, bank, det_obj, frame_cams, cams, masks, opts.mask_refine_huber_px, opts.mask_refine_iters,
+                                                   opts.mask_refine_max_points, opts.mask_refine_max_contour)
     return pose["R"].cpu().numpy(), pose["t"].cpu().numpy()
 
 
@@ -531,6 +548,7 @@ class _Pipeline:
         self.depth_pnp = opts.pnp_type in DEPTH_PNP_TYPES                # the coarse poses are solved on it,
         self.verify = opts.coarse_select_type in DEPTH_SELECT_TYPES      # the coarse hypotheses are checked against it
         self.mask_verify = opts.coarse_select_type in MASK_SELECT_TYPES  # ... or against the detection's mask
+        self.mask_refine = opts.final_pose_type in MASK_POSE_TYPES       # the final pose is refined against the detection's mask: no depth
         self.extractor = _extractor_on_device(opts, extractor, precision, weights)
         self.bank = DeviceBank(list(repres))
         self.eng = fe.FoundPoseEngine(self.extractor, self.bank, opts.grid_cell_size, opts.match_top_n_templates, opts.match_top_k_buddies, tie_order="torch")
@@ -627,10 +645,10 @@ def _run_flush(pipe: _Pipeline, queue: Sequence[QueuedDetection], plan: FlushPla
     Rb, tb = best["R"].cpu().numpy(), best["t"].cpu().numpy()
     t4 = time.perf_counter()
     t5 = None
-    if pipe.refine or pipe.use_depth:   # infer.py:619: the refined pose of the best coarse pose is the final pose
+    if pipe.refine or pipe.use_depth or pipe.mask_refine:   # infer.py:619: the refined pose of the best coarse pose is the final pose
         Rb, tb = _refine_final(opts, res, best, bank, plan.det_obj, src_cams, cams, (crops.shape[-1], crops.shape[-2]),
                                depth() if pipe.use_depth else None, plan.image_index,
-                               [pipe.taus[o] for o in plan.det_obj] if pipe.use_depth else None)
+                               [pipe.taus[o] for o in plan.det_obj] if pipe.use_depth else None, masks if pipe.mask_refine else None)
         t5 = time.perf_counter()
     return _Flush(dets, crops, crop_masks, cams, res, best, found, cid, Rb, tb, t5 is not None, _stage_times(eng, len(dets), t0, t1, t2, t3, t4, t5))
 

@@ -861,6 +861,24 @@ def tsdf_track(volume: dict, points: torch.Tensor, row_begin: torch.Tensor, row_
     return out
 
 
+def mask_distance(masks: torch.Tensor) -> torch.Tensor:
+    """The exact squared distance field of binary masks (fp_mask_distance): masks uint8 [B, H, W] on the device,
+    non-zero = set, 1 <= H, W <= 16384 -> int32 [B, H, W], the squared distance in pixels from each pixel to the nearest set pixel of
+    its mask (0 on a set pixel), 2^30 everywhere in a mask without a set pixel.  B = 0 returns without a launch."""
+    if not isinstance(masks, torch.Tensor) or not masks.is_cuda:
+        raise ValueError("mask_distance: masks must be a tensor on the device (there is no CPU path)")
+    if masks.dtype != torch.uint8 or masks.dim() != 3:
+        raise ValueError(f"mask_distance: masks must be uint8 [B, H, W], got {masks.dtype} {tuple(masks.shape)}")
+    B, H, W = (int(n) for n in masks.shape)
+    if not (1 <= H <= 16384 and 1 <= W <= 16384) or B > 65535:
+        raise ValueError(f"mask_distance: {B} masks of {W} x {H}: at most 65535 masks with sides in [1, 16384]")
+    d2 = torch.empty((B, H, W), dtype=torch.int32, device=masks.device)
+    if B:
+        m = masks.contiguous()
+        call("fp_mask_distance", ptr(m), B, H, W, ptr(d2), stream())
+    return d2
+
+
 def multiview_refine(points: torch.Tensor, targets: torch.Tensor, view_index: torch.Tensor, view_cam: torch.Tensor, view_T: torch.Tensor,
                      row_begin: torch.Tensor, row_end: torch.Tensor, R: torch.Tensor, t: torch.Tensor, huber_px: float = 10.0, iters: int = 20,
                      has_pose: Optional[torch.Tensor] = None, max_points: Optional[int] = None, want_normal_eq: bool = False) -> dict:

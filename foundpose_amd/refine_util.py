@@ -8,6 +8,9 @@ restated in numpy fp64 by tests/featuremetric_ref.py.  The depth term is this pr
 quadratic of (measured depth at a template point's projection) - (the point's depth), in the frame's own camera; one
 fp_depth_refine call (csrc/depth_refine.hip) per batch, restated by tests/depth_refine_ref.py.  The joint objective E_f + w_d E_d puts
 both terms into one normal equation: one fp_rgbd_refine call (csrc/rgbd_refine.hip) per batch, restated by tests/rgbd_refine_ref.py.
+The silhouette refinement (section 38) needs no depth: Levenberg-Marquardt on the distance of the whole-model sample's projections to
+the detection's mask and of the mask's contour pixels to their nearest projection, in the frame's own camera; fp_mask_distance and
+fp_mask_refine (csrc/mask_refine.hip), restated by tests/mask_refine_ref.py.
 """
 
 from typing import Any, Dict, Optional, Sequence, Tuple
@@ -15,10 +18,10 @@ from typing import Any, Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ._lib import call, depth_refine_scratch_bytes, ptr, refine_scratch_bytes, require_cuda, rgbd_refine_scratch_bytes, stream, upload_async
+from ._lib import call, depth_refine_scratch_bytes, mask_refine_scratch_bytes, ptr, refine_scratch_bytes, require_cuda, rgbd_refine_scratch_bytes, stream, upload_async
 from .bank import DeviceBank
 from .matching import MatchResult
-from .ops import _lm_inputs, _lm_outputs
+from .ops import _lm_inputs, _lm_outputs, mask_distance
 from .pnp_util import _intrinsics
 
 STATUS_REFINED, STATUS_NOT_IMPROVED, STATUS_SKIPPED = 0, 1, 2
@@ -269,3 +272,130 @@ def refine_best_coarse_rgbd(res: MatchResult, best: Dict[str, torch.Tensor], ban
     out = refine_rgbd(res.feature_map, image_size, solve_cameras, A, a, depth, ii, frame_cameras, R, t, rb, re, bank.feats, bank.vertices, ok, tau,
                       depth_weight, iters, max_points=bank.p_max)
     return _back_to_solve_cameras(out, best, back, dev)
+
+
+# ---------------------------------------------------------------------------------------------------- against the detection's mask (section 38)
+def _check_masks(masks, who: str) -> None:
+    if not isinstance(masks, torch.Tensor) or masks.dtype != torch.uint8 or masks.dim() != 3 or not masks.is_cuda:
+        raise ValueError(f"{who}: masks must be a uint8 tensor [B, H, W] on the device, got "
+                         f"{(masks.dtype, list(masks.shape), str(masks.device)) if isinstance(masks, torch.Tensor) else type(masks).__name__}")
+
+
+def _check_count(name: str, v, lo: int, hi: Optional[int] = None) -> int:
+    if isinstance(v, bool) or not isinstance(v, int) or v < lo or (hi is not None and v > hi):
+        raise ValueError(f"{name} must be an integer {'>= ' + str(lo) if hi is None else 'in [' + str(lo) + ', ' + str(hi) + ']'}, got {v!r}")
+    return v
+
+
+def _check_huber(v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not (np.isfinite(v) and v > 0):
+        raise ValueError(f"huber_px must be a finite number > 0, got {v!r}")
+    return float(v)
+
+
+def mask_contours(masks: torch.Tensor, max_contour: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The contour pixels of masks uint8 [B, H, W] (non-zero = set): the set pixels with at least one of their four neighbours INSIDE the
+    image unset -- a mask cut off by the image border has no contour there -- per mask in row-major order.  A mask with K > max_contour of
+    them keeps the entries floor(j K / max_contour), j = 0 .. max_contour - 1.
+    -> (rows int32 [sum K', 2] = (x, y), begin int32 [B], end int32 [B]) on the device.  Torch on the device, no per-mask loop.  The rule
+    is evaluated per pixel -- a contour pixel's index l within its mask by a cumulative sum over the frame, kept iff K <= max_contour or
+    l = floor(j K / max_contour) for the one j that can give it, j = ceil(l max_contour / K) -- so that the one nonzero() yields the kept
+    rows already and is the only synchronisation; the price is a few int64 temporaries of the masks' size."""
+    _check_masks(masks, "mask_contours")
+    cap = _check_count("max_contour", max_contour, 1)
+    m = masks != 0
+    inner = torch.ones_like(m)   # "every neighbour inside the image is set"
+    inner[:, 1:, :] &= m[:, :-1, :]
+    inner[:, :-1, :] &= m[:, 1:, :]
+    inner[:, :, 1:] &= m[:, :, :-1]
+    inner[:, :, :-1] &= m[:, :, 1:]
+    contour = (m & ~inner).flatten(1)                                 # [B, H W], row-major
+    l = torch.cumsum(contour, 1, dtype=torch.int64) - 1               # on a contour pixel: its index among its mask's contour pixels
+    K = l[:, -1:] + 1                                                 # [B, 1]
+    j = (l * cap + (K - 1)) // torch.clamp(K, min=1)                  # 64-bit integers
+    keep = contour & ((K <= cap) | ((j < cap) & ((j * K) // cap == l)))
+    kept = keep.sum(1)
+    end = torch.cumsum(kept, 0)
+    begin = end - kept
+    nz = torch.nonzero(keep.view_as(m))                               # [sum K', 3] = (b, y, x), sorted: row-major within a mask
+    rows = nz[:, [2, 1]].to(torch.int32).contiguous()
+    return rows, begin.to(torch.int32), end.to(torch.int32)
+
+
+def refine_mask(d2: torch.Tensor, contour: torch.Tensor, contour_begin: torch.Tensor, contour_end: torch.Tensor, cameras: Sequence[Any],
+                R: torch.Tensor, t: torch.Tensor, row_begin: torch.Tensor, row_end: torch.Tensor, vertices: torch.Tensor, has_pose: torch.Tensor,
+                huber_px: float = 8.0, iters: int = 30, return_normal_equations: bool = False, max_points: Optional[int] = None,
+                max_contour: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """The raw call of the silhouette refinement (fp_mask_refine).  d2 int32 [B, H, W]: ops.mask_distance of each
+    detection's mask in its FRAME camera's image; contour int32 [K_total, 2] with contour_begin / contour_end int [B]: mask_contours' rows;
+    cameras: the frame's pinhole camera per detection; R [B, 3, 3] / t [B, 3] model -> that camera (mm); row_begin / row_end [B] int:
+    each detection's rows of vertices [N, 3]; has_pose [B] bool; huber_px: the Huber delta in pixels.  max_points / max_contour bound
+    row_end - row_begin / contour_end - contour_begin (None: read back from the device).
+    -> refine_featuremetric's dict; num_points counts the measurable forward rows at the input pose."""
+    require_cuda(d2, contour, contour_begin, contour_end, R, t, row_begin, row_end, vertices, has_pose)
+    if d2.dtype != torch.int32 or d2.dim() != 3:
+        raise ValueError(f"d2 must be int32 [B, H, W], got {d2.dtype} {tuple(d2.shape)}")
+    B, H, W = (int(n) for n in d2.shape)
+    delta = _check_huber(huber_px)
+    _check_count("iters", iters, 0, 1000)
+    if int(R.shape[0]) != B or len(cameras) != B or int(contour_begin.numel()) != B or int(contour_end.numel()) != B:
+        raise ValueError(f"{int(R.shape[0])} poses, {len(cameras)} cameras and {int(contour_begin.numel())} contour ranges for {B} distance maps")
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"vertices {tuple(vertices.shape)} are not [N, 3]")
+    if contour.dim() != 2 or contour.shape[1] != 2:
+        raise ValueError(f"contour {tuple(contour.shape)} is not [K, 2]")
+    dev = d2.device
+    cam = _upload_cameras(cameras, B, dev)
+    d2c = d2.contiguous()
+    rows = contour.to(torch.int32).contiguous()
+    if rows.shape[0] == 0:
+        rows = torch.zeros(1, 2, dtype=torch.int32, device=dev)   # a pointer the entry can take; no range reaches it
+    cb, ce = contour_begin.to(torch.int32).contiguous(), contour_end.to(torch.int32).contiguous()
+    if max_contour is None:
+        max_contour = int((ce - cb).max().item())
+    max_contour = max(1, int(max_contour))
+    Rin, tin, rb, re, hp, _, v32, max_points = _lm_inputs(B, R, t, row_begin, row_end, has_pose, None, vertices, max_points)
+    scratch = torch.empty(mask_refine_scratch_bytes(B, max_points, max_contour), dtype=torch.uint8, device=dev)
+    out, outs = _lm_outputs(B, dev, 28 if return_normal_equations else 0)
+    call("fp_mask_refine", ptr(d2c), H, W, ptr(rows), int(contour.shape[0]), ptr(cb), ptr(ce), ptr(cam), ptr(Rin), ptr(tin), ptr(rb), ptr(re), ptr(v32),
+         int(v32.shape[0]), ptr(hp), delta, B, max_points, max_contour, int(iters), ptr(scratch), scratch.numel(), *outs, stream())
+    return out
+
+
+def refine_best_coarse_mask(pose: Dict[str, torch.Tensor], bank: DeviceBank, det_obj: Optional[Sequence[int]], frame_cameras: Sequence[Any],
+                            solve_cameras: Sequence[Any], masks: torch.Tensor, huber_px: float = 8.0, iters: int = 30, max_points: int = 4096,
+                            max_contour: int = 1024) -> Dict[str, torch.Tensor]:
+    """Refines a pose of every detection (pose: select_best_coarse's dict, its "R" / "t" possibly replaced by a featuremetric
+    refinement's) against the detection's own mask: masks uint8 [B, H, W] on the device, in the frame cameras' images.  The poses live
+    in solve_cameras; they are moved into frame_cameras as in refine_best_coarse_depth, refined there on the whole-model sample
+    bank.verify_points(max_points) against the mask's distance field and its contour (at most max_contour rows), and moved back; a pose
+    that was not refined comes back bit for bit.  Masks of another type or shape, lengths that do not match and bad options raise
+    ValueError before anything is launched; B = 0 returns empty tensors without a launch.  -> refine_mask's dict, R / t in the solve
+    cameras."""
+    _check_masks(masks, "refine_best_coarse_mask")
+    delta = _check_huber(huber_px)
+    _check_count("iters", iters, 0, 1000)
+    _check_count("max_points", max_points, 1)
+    _check_count("max_contour", max_contour, 1)
+    B = int(masks.shape[0])
+    det_obj = [0] * B if det_obj is None else list(det_obj)
+    if len(det_obj) != B or len(frame_cameras) != B or len(solve_cameras) != B or int(pose["R"].shape[0]) != B or int(pose["found"].shape[0]) != B:
+        raise ValueError(f"{len(det_obj)} objects, {len(frame_cameras)} frame cameras, {len(solve_cameras)} solve cameras and {int(pose['R'].shape[0])} poses "
+                         f"for {B} masks")
+    if any(isinstance(o, bool) or not 0 <= int(o) < len(bank.objects) for o in det_obj):
+        raise ValueError(f"an object index outside [0, {len(bank.objects)})")
+    H, W = int(masks.shape[1]), int(masks.shape[2])
+    if B and not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise ValueError(f"masks of {W} x {H}: sides in [1, 16384]")
+    dev = masks.device
+    if B == 0:
+        return _lm_outputs(0, dev, 0)[0]
+    vp = bank.verify_points(max_points)
+    rng = torch.tensor([vp.ranges[int(o)] for o in det_obj], dtype=torch.int32).reshape(B, 2)
+    cap = max(1, int((rng[:, 1] - rng[:, 0]).max()))
+    rng = upload_async(rng, dev)
+    R, t, back = _into_frame_cameras(pose, frame_cameras, solve_cameras, dev)
+    rows, cb, ce = mask_contours(masks, max_contour)
+    out = refine_mask(mask_distance(masks), rows, cb, ce, frame_cameras, R, t, rng[:, 0], rng[:, 1], vp.points, pose["found"].bool(), delta, iters,
+                      max_points=cap, max_contour=max_contour)
+    return _back_to_solve_cameras(out, pose, back, dev)
